@@ -9,9 +9,14 @@ contiguous slabs (one process per GPU) and ONE all-gather (RCCL over xGMI) assem
 every rank inside the timed region: strong scaling of the named config.
 
 Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel (fused PE+MLP, MFMA-bound) from
-HIP events recorded on the kernel's own stream inside the timed region; `cpu_baseline` times the CPU
-oracle (numpy/OpenBLAS restatement of the reference algorithm -- NOT TensorFlow, which is not
-installable here) on a bounded sample of the same workload on the host cores of rank 0.
+HIP events recorded on the kernel's own stream inside the timed region.  A plain run does only that: set-up,
+warm-up, the timed steps and the line.  `--full` adds everything else the benchmark measures and checks beside the
+headline (the other arithmetic modes, the sustained run, the shipped weights, BASELINE configs 4 and 5, the training
+step, the host boundary, the xyz-only network, frames in flight and the library's own all-gather cross-check at N > 1)
+and `cpu_baseline`, which times the CPU oracle (numpy/OpenBLAS restatement of the reference algorithm -- NOT
+TensorFlow) on a bounded sample of the same workload on the host cores of rank 0.  `--dump-outputs DIR` writes the RGB
+frame of the last timed step to DIR/rgb.npy (float32, one row per ray; under --rehearse-world only rank 0's slab): the
+inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -206,10 +211,16 @@ def main():
     ap.add_argument("--precision", default="f16x3", choices=["fp32", "f16x3", "f16"],
                     help="arithmetic of the 256-wide contractions: f16x3 = 3-pass split-fp16 MFMA with fp32 accumulate "
                          "(fp32-class accuracy, tests/test_gpu_parity.py); fp32 = exact fp32 MFMA")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: other modes, sizes and configurations, training, host boundary, CPU "
+                         "baseline and parity check (N > 1: frames in flight and the library all-gather cross-check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the RGB frame of the last timed step to DIR/rgb.npy (float32); with --rehearse-world k "
+                         "that is rank 0's slab of the k-way split, not the whole frame")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step measurement")
     ap.add_argument("--quick", action="store_true",
-                    help="headline + fp32 + fp16 modes only: skip the sustained run, the shipped-weights run and configs 4/5")
+                    help="with --full: headline + fp32 + fp16 modes only: skip the sustained run, the shipped-weights run and configs 4/5")
     ap.add_argument("--c-gather", action="store_true",
                     help="N>1: assemble the frame with the library's own ncclAllGather (nerf_render_image_sharded) "
                          "instead of torch.distributed.all_gather_into_tensor")
@@ -374,6 +385,10 @@ def main():
         img = step_marked(args.warmup + i, marks)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the timed path hands its caller in its last step: the frame's RGB (the gathered frame at N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rgb.npy"), img.detach().float().cpu().numpy().astype(np.float32))
     mlp_ms, n_launch, n_rows = model.ctx.read_timing()
     model.ctx.enable_timing(False)
     # per-step GPU times from the stream events (no host synchronisation inside the timed region)
@@ -393,7 +408,7 @@ def main():
 
     # K frames in flight between gathers: separates launch latency at small slabs from gather bandwidth (N>1 only)
     in_flight = None
-    if world > 1 and not c_gather:
+    if args.full and world > 1 and not c_gather:
         K = 8
         def step_k(seed0):
             parts = [model.render_image(c2w, FOV, H, W, batch_size_input=1 << 18, seed=seed0 + k, ray_begin=begin,
@@ -425,7 +440,7 @@ def main():
         args.no_cpu_baseline = True
     # (also under the one-GPU rehearsal -- BENCH_BACKEND=gloo with NERF_RCCL_LIB naming tests/stub_rccl.c's stand-in, the only
     # way two ranks can share a device -- so that this check itself has run before the driver's first real N > 1 launch)
-    if world > 1 and not c_gather and (backend == "nccl" or os.environ.get("NERF_RCCL_LIB")):
+    if args.full and world > 1 and not c_gather and (backend == "nccl" or os.environ.get("NERF_RCCL_LIB")):
         # every measurement is taken and every torch collective this run needs is behind us: now the library's own
         # communicator may be tried, on a context of ITS OWN (same weights, own stream; a ctx is single-caller)
         chk = N.Context(near=NEAR, far=FAR, n_angles=2, precision=args.precision, device=dev_index)
@@ -476,7 +491,7 @@ def main():
                                  avg_launch_ms=ms / max(nl, 1))}
 
     other = fp16_mode = sustained = shipped = cfg4 = cfg5 = None
-    if world == 1 and args.precision == "f16x3" and args.rehearse_world <= 1:
+    if args.full and world == 1 and args.precision == "f16x3" and args.rehearse_world <= 1:
         # the exact-fp32 mode and the single-pass fp16 mode of the same step, beside the headline mode
         other = dict(side_run(model, "fp32", 3, H, W, SC, SF, c2w, FOV), dtype="f32")
         other["roofline"]["frac_vs_fp32_matrix_peak"] = other["roofline"]["frac"]
@@ -586,7 +601,7 @@ def main():
 
     # the training step on the reference's batch, timed briefly beside the headline (N=1 only)
     train = None
-    if world == 1 and args.rehearse_world <= 1 and not args.no_train:
+    if args.full and world == 1 and args.rehearse_world <= 1 and not args.no_train:
         n_tr, k_tr = 4096, 30
         gen = torch.Generator(device="cuda").manual_seed(0)
         t_o = torch.zeros((n_tr, 4), device="cuda"); t_o[:, 2] = 1.0; t_o[:, 3] = 1.0
@@ -683,7 +698,7 @@ def main():
     # the drop-in boundary itself: the host-memory entry point (numpy in, numpy out), one synchronous call per frame --
     # page-locked outputs, copies on a second stream; next to the same call with device-resident outputs (N=1 only)
     host_boundary = None
-    if world == 1 and args.rehearse_world <= 1 and not args.quick:
+    if args.full and world == 1 and args.rehearse_world <= 1 and not args.quick:
         def frames_per_s(f, k):
             f(100), f(101)
             t_ = time.perf_counter()
@@ -708,7 +723,7 @@ def main():
     # the xyz-only network (n_angles_for_model = 0, src/NeRF.py:248-288; 5 of the 46 shipped configs) beside the
     # view-direction network: render rate and training step -- reported figures (the -m gpu suite only keeps sanity floors)
     xyz_only = None
-    if world == 1 and args.rehearse_world <= 1 and not args.quick:
+    if args.full and world == 1 and args.rehearse_world <= 1 and not args.quick:
         xyz_only = {}
         for na in (2, 0):
             cx = N.Context(near=NEAR, far=FAR, n_angles=na, precision="f16x3", device=dev_index)
@@ -810,7 +825,7 @@ def main():
             out["host_boundary"] = host_boundary
         if xyz_only is not None:
             out["xyz_only"] = xyz_only
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             model.set_weights(blob_c, blob_f)               # (the training measurement above moved them)
             model.ctx.set_precision(args.precision)
             frame0 = lambda sd: model.render_image(c2w, FOV, H, W, seed=sd, rgb_only=True)[0]     # noqa: E731

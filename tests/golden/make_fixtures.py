@@ -7,7 +7,7 @@ numpy.load(allow_pickle=False), two 50x50 JPGs via imageio, one PSNR .npy); impo
 code.  The pose post-processing below restates src/UtilsFiles.py:73-130 (get_data_from_colmap /
 load_llff_data) and src/UtilsCV.py:263-330 (poses_avg, recenter_poses, spherify_poses).
 
-Output: tests/golden/alexander50_epoch095.npz
+Output: tests/golden/alexander50_epoch095.npz, alexander50_epoch095_h5_layout.npz
 """
 import os
 import sys
@@ -65,6 +65,35 @@ def load_llff(path):                   # src/UtilsFiles.py:99-130
 def read_blob(f, group):
     names = [n.decode() if isinstance(n, bytes) else n for n in f[group].attrs["weight_names"]]
     return np.concatenate([np.asarray(f[group][n], np.float32).ravel() for n in names])
+
+
+def h5_layout(out):
+    """The shipped checkpoint file without its weights: every byte of NeRF_model_epoch_095.h5 except the contiguous data of
+    its 22 weight datasets, which are blob_coarse / blob_fine of alexander50_epoch095.npz.  tests/test_keras_h5.py puts them
+    back at the recorded offsets, checks the file's SHA-256 and reads it."""
+    import hashlib
+    path = RUN + "/saved_weights/NeRF_model_epoch_095.h5"
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    regions = []
+    with h5py.File(path, "r") as f:
+        for net, group in enumerate(("model", "model_1")):
+            begin = 0
+            for n in [n.decode() if isinstance(n, bytes) else n for n in f[group].attrs["weight_names"]]:
+                d = f[group][n]
+                assert d.dtype == np.dtype("<f4") and d.id.get_offset() is not None and d.id.get_storage_size() == 4 * d.size
+                regions.append((d.id.get_offset(), net, begin, d.size))
+                begin += d.size
+    regions.sort()
+    keep, pos = [], 0
+    for off, net, begin, count in regions:
+        assert off >= pos
+        keep.append(raw[pos:off])
+        pos = off + 4 * count
+    keep.append(raw[pos:])
+    r = np.asarray(regions, np.int64)
+    np.savez_compressed(out, layout=np.frombuffer(b"".join(keep), np.uint8), offset=r[:, 0], net=r[:, 1], begin=r[:, 2],
+                        count=r[:, 3], size=np.int64(len(raw)), sha256=np.str_(hashlib.sha256(raw).hexdigest()))
 
 
 def main(out):
@@ -126,3 +155,4 @@ if __name__ == "__main__":
     copy_dataset(os.path.join(os.path.dirname(__file__), "alexander50"))
     copy_configs(os.path.join(os.path.dirname(__file__), "configs"))
     main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(__file__), "alexander50_epoch095.npz"))
+    h5_layout(os.path.join(os.path.dirname(__file__), "alexander50_epoch095_h5_layout.npz"))

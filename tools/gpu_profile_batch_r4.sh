@@ -15,10 +15,10 @@ PMCSET="GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_W
 LDSSET="GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_LDS_ADDR_CONFLICT"
 if [ $part = a ]; then
   cd $R
-  timeout -k 10 500 python bench.py > $O/r4_bench_default.json 2> $O/r4_bench_default.err || exit 1
+  timeout -k 10 500 python bench.py --full > $O/r4_bench_default.json 2> $O/r4_bench_default.err || exit 1
   tail -c 300 $O/r4_bench_default.json; echo
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_r4_bench -o b --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --quick > $O/prof_r4_bench.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_r4_bench -o b --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --quick > $O/prof_r4_bench.log 2>&1 || exit 1
   echo "bench trace ok"
   # per-kernel times of a training step on ONE stream (NERF_TRAIN_OVERLAP=0: with the fine pass's weight-gradient launch on its
   # second stream the overlapped kernels' durations stretch and their sum says nothing); the step itself is timed both ways below
@@ -31,9 +31,9 @@ if [ $part = a ]; then
   done; done | tee $O/r4_train_step_both_ways.txt
   unset NERF_TRAIN_OVERLAP
   for mode in f16x3 f16; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $PMCSET -d $O/pmc4_${mode}a -o a --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}a.log 2>&1 || exit 1
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc4_${mode}b -o b --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}b.log 2>&1 || exit 1
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc4_${mode}c -o c --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}c.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $PMCSET -d $O/pmc4_${mode}a -o a --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}a.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc4_${mode}b -o b --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}b.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc4_${mode}c -o c --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick --precision $mode > $O/pmc4_${mode}c.log 2>&1 || exit 1
     echo "pmc $mode ok"
   done
 else

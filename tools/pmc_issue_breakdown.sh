@@ -1,10 +1,10 @@
 #!/bin/bash
 # Issue-side breakdown of the trainer kernels (three PMC passes, 8 SQ counters each): where a wave's cycles go.
 # Usage (GPU box): bash tools/pmc_issue_breakdown.sh [mixed|fp32|render]   -> gpurun_out/issue_<pol>{a,b,c}/
-# (render: bench.py --quick in the headline mode and the single-pass mode instead of the training step)
+# (render: bench.py --full --quick in the headline mode and the single-pass mode instead of the training step)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; pol=${1:-mixed}
 CMD="python3 $R/tools/train_bench.py 2 4096 $pol"
-[ "$pol" = render ] && CMD="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick"
+[ "$pol" = render ] && CMD="python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --quick"
 cd /tmp && export TMPDIR=/tmp
 A="SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT"
 B="SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INST_CYCLES_VMEM_WR SQ_BUSY_CYCLES"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise rocprofv3 --pmc passes (gpurun_out/pmc_*/ *_counter_collection.csv) for the MLP kernel
+"""Summarise rocprofv3 --pmc passes ($OUT/pmc_*/ *_counter_collection.csv) for the MLP kernel
 into profiles/: per-launch averages, the HBM traffic figure bench.py reports, MFMA utilisation.
 
 HBM bytes follow MI355X_MICROARCH.md section HBM: FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE
@@ -14,16 +14,17 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))     # the batch's output folder, as in tools/gpu_profile_batch.sh
 
 
 def main(tag, dtype, kernel_substr):
     vals = collections.defaultdict(list)
-    for f in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}[abc]", "*_counter_collection.csv"))):
+    for f in sorted(glob.glob(os.path.join(OUT, f"pmc_{tag}[abc]", "*_counter_collection.csv"))):
         for r in csv.DictReader(open(f)):
             if kernel_substr in r["Kernel_Name"]:
                 vals[r["Counter_Name"]].append(float(r["Counter_Value"]))
     durs = []
-    for f in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_{tag}a", "*_kernel_trace.csv"))):
+    for f in sorted(glob.glob(os.path.join(OUT, f"pmc_{tag}a", "*_kernel_trace.csv"))):
         for r in csv.DictReader(open(f)):
             if kernel_substr in r["Kernel_Name"]:
                 durs.append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/r2_pmc_summary.json from the PMC passes of tools/gpu_profile_batch_r2.sh (gpurun_out/pmc2_<tag>[abc]):
+"""profiles/r2_pmc_summary.json from the PMC passes of tools/gpu_profile_batch_r2.sh ($OUT/pmc2_<tag>[abc]):
 per kernel kind the per-launch averages -- clock (GRBM_GUI_ACTIVE / 8 / t), MFMA utilisation
 (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / cycles), wait fractions, LDS bank conflicts per busy cycle and HBM bytes
 ((2 * FETCH_SIZE + WRITE_SIZE) KiB: the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md) -- and refreshes
@@ -11,6 +11,7 @@ import json
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))     # the batch's output folder, as in tools/gpu_profile_batch_r2.sh
 KINDS = {  # tag -> [(kernel-name substring, label)]
     "f16x3": [("mlp_f16x3_kernel", "mlp_f16x3_kernel (render, 3-pass split fp16)")],
     "f16": [("mlp_f16_2t_kernel", "mlp_f16_2t_kernel (render, single-pass fp16, two tiles per wave)")],
@@ -37,11 +38,11 @@ def main():
         for sub, label in kinds:
             vals = collections.defaultdict(list)
             durs = []
-            for f in glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc2_{tag}[abc]", "*_counter_collection.csv")):
+            for f in glob.glob(os.path.join(OUT, f"pmc2_{tag}[abc]", "*_counter_collection.csv")):
                 for r in csv.DictReader(open(f)):
                     if sub in r["Kernel_Name"]:
                         vals[r["Counter_Name"]].append(float(r["Counter_Value"]))
-            for f in glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc2_{tag}a", "*_kernel_trace.csv")):
+            for f in glob.glob(os.path.join(OUT, f"pmc2_{tag}a", "*_kernel_trace.csv")):
                 for r in csv.DictReader(open(f)):
                     if sub in r["Kernel_Name"]:
                         durs.append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarise the rocprofv3 --pmc passes of the training step (gpurun_out/pmc_train[abc]) per GEMM kernel kind into
+"""Summarise the rocprofv3 --pmc passes of the training step ($OUT/pmc_train[abc]) per GEMM kernel kind into
 profiles/r1_train_pmc_summary.json: MFMA utilisation (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / GRBM_GUI_ACTIVE/8),
 wait fractions, LDS bank-conflict share, HBM bytes per launch ((2*FETCH_SIZE + WRITE_SIZE) KiB, the gfx950
 correction of MI355X_MICROARCH.md) -- averaged over all launches of the kind (coarse and fine passes, all layers)."""
@@ -10,6 +10,7 @@ import json
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))     # the batch's output folder, as in tools/gpu_profile_batch.sh
 KINDS = (("mlp_f16x3_stash_kernel", "fused forward with activation stash (3-pass split fp16)"),
          ("gemm_abt_h_kernel", "gemm_abt_h data gradient (3-pass split fp16)"),
          ("gemm_atb_h_kernel", "gemm_atb_h weight gradient (3-pass split fp16)"),
@@ -22,12 +23,12 @@ def main():
     vals = {k: collections.defaultdict(list) for _, k in KINDS}
     durs = {k: [] for _, k in KINDS}
     for tag in "abc":
-        for f in glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_train{tag}", "*_counter_collection.csv")):
+        for f in glob.glob(os.path.join(OUT, f"pmc_train{tag}", "*_counter_collection.csv")):
             for r in csv.DictReader(open(f)):
                 for sub, kind in KINDS:
                     if sub in r["Kernel_Name"]:
                         vals[kind][r["Counter_Name"]].append(float(r["Counter_Value"]))
-    for f in glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_traina", "*_kernel_trace.csv")):
+    for f in glob.glob(os.path.join(OUT, "pmc_traina", "*_kernel_trace.csv")):
         for r in csv.DictReader(open(f)):
             for sub, kind in KINDS:
                 if sub in r["Kernel_Name"]:
