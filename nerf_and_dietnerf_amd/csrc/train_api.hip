@@ -143,6 +143,18 @@ int layer_table(const nerf_config& cfg, TLayer L[12]) {
 
 void free_buf(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
 
+void free_pass(TPass& p) {
+    for (DevBuf* b : {&p.C4, &p.C8, &p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7, &p.H8b, &p.H9, &p.raw, &p.T, &p.w, &p.rgb,
+                      &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs})
+        free_buf(*b);
+    for (DevBuf& b : p.D) free_buf(b);
+}
+
+void free_slot(RenderSlot& s) {
+    for (TPass& p : s.pass) free_pass(p);
+    for (DevBuf* b : {&s.o, &s.d, &s.u_c, &s.u_f, &s.z_new}) free_buf(*b);
+}
+
 int relayout_net(nerf_ctx* c, TNet& n) {
     if (n.fstream)
         launch_repack_f16x3(n.blob, c->train->sidx, n.fstream, c->train->cidx, n.fcst,
@@ -231,6 +243,8 @@ int init_net(nerf_ctx* c, TrainState* t, int which) {
 
 // ---- one pass: forward ---------------------------------------------------------------------------
 struct PassDims { long long N; int S; long long M, Mp; };
+
+PassDims pass_dims(long long N, int S) { return {N, S, N * S, (N * S + 127) / 128 * 128}; }
 
 int ensure_pass(nerf_ctx* c, TPass& p, const PassDims& d) {
     const size_t f = sizeof(float);
@@ -614,6 +628,48 @@ int backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, cons
     return 0;
 }
 
+// dL/d(rgb) of pass `which` [+ dL/d(weights) from the sampler, d_wext] -> Graw through the compositing -> the network's
+// gradient blob [+ dL/dz into d_z]
+int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& pd, const float* o, const float* dirs,
+                            const float* d_rgb, const float* d_wext, float* d_z) {
+    const TPass& p = t->pass[which];
+    float* Graw = (float*)t->Graw.p;
+    HIP_OK(hipMemsetAsync(Graw + pd.M * 4, 0, (pd.Mp - pd.M) * 4 * sizeof(float), c->stream));
+    launch_composite_bwd((const float*)p.raw.p, (const float*)p.z.p, (const float*)p.T.p, pd.N, pd.S, d_rgb, d_wext, Graw,
+                         d_z, c->stream);
+    return backward_pass(c, t, which, pd, o, dirs, d_z);
+}
+
+// the sample counts of a training call; *fine: whether the fine pass runs
+int check_samples(const TrainState* t, long long N, int Sc, int Sf, bool* fine) {
+    if (N <= 0) return fail("need at least one ray (got %lld)", N);
+    if (Sc < 1 || Sc > 1024) return fail("bad coarse sample count %d", Sc);
+    *fine = Sf > 0 && t->net[1].present;
+    if (!*fine) return 0;
+    if (Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
+    if (Sf > 256) return fail("training supports at most 256 fine samples per ray (got %d)", Sf);
+    // same budget as the render path's sampler (nerf_api.hip): the backward sampler was validated up to 64 KiB of LDS
+    if (sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024 || sample_pdf_bwd_lds_bytes(Sc, Sf) > 64 * 1024)
+        return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget (forward %zu B, backward %zu B, limit 65536 B)", Sc, Sf,
+                    sample_pdf_lds_bytes(Sc, Sf), sample_pdf_bwd_lds_bytes(Sc, Sf));
+    return 0;
+}
+
+// the buffers every backward needs, for passes of up to Mmax (padded) rows and a coarse pass of Mc rows
+int ensure_bwd_workspace(nerf_ctx* c, TrainState* t, long long Mmax, long long Mc) {
+    const size_t f = sizeof(float);
+    int r = ensure(c, t->Ga, Mmax * 256 * f);
+    r |= ensure(c, t->Gb, Mmax * 256 * f);
+    r |= ensure(c, t->G9, Mmax * 128 * f);
+    r |= ensure(c, t->Graw, Mmax * 4 * f);
+    r |= ensure(c, t->dsig, Mmax * f);
+    r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
+    r |= ensure(c, t->partial, (size_t)2 * kTrainSplitsWide * (kLdC4 + 1) * 256 * f);   // also holds a pass's batched slabs
+    r |= ensure(c, t->d_wext, Mc * f);
+    r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
+    return r;
+}
+
 int stage_in(nerf_ctx* c, DevBuf& b, const float* src, size_t bytes, int mem, const float** out) {
     if (!src) { *out = nullptr; return 0; }
     if (mem == NERF_MEM_DEVICE) { *out = src; return 0; }
@@ -627,15 +683,8 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
     TrainState* t = c->train;
     if (!t || !t->training) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d || !target) return fail("NULL argument");
-    if (N <= 0) return fail("need at least one ray (got %lld)", (long long)N);
-    if (Sc < 1 || Sc > 1024) return fail("bad coarse sample count %d", Sc);
-    const bool fine = Sf > 0 && t->net[1].present;
-    if (fine && Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
-    if (fine && Sf > 256) return fail("training supports at most 256 fine samples per ray (got %d)", Sf);
-    // same budget as the render path's sampler (nerf_api.hip): the backward sampler was validated up to 64 KiB of LDS
-    if (fine && (sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024 || sample_pdf_bwd_lds_bytes(Sc, Sf) > 64 * 1024))
-        return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget (forward %zu B, backward %zu B, limit 65536 B)", Sc, Sf,
-                    sample_pdf_lds_bytes(Sc, Sf), sample_pdf_bwd_lds_bytes(Sc, Sf));
+    bool fine;
+    if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
     const size_t f = sizeof(float);
     const float *o, *d, *tg, *uc, *uf;
     if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
@@ -644,30 +693,20 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
     if (int r = stage_in(c, t->u_c, u_c, (size_t)N * Sc * f, mem, &uc)) return r;
     if (int r = stage_in(c, t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f, mem, &uf)) return r;
 
-    PassDims dc{N, Sc, N * Sc, (N * Sc + 127) / 128 * 128};
-    PassDims df{N, Sf, N * (long long)Sf, (N * (long long)Sf + 127) / 128 * 128};
-    const long long Mmax = fine && df.Mp > dc.Mp ? df.Mp : dc.Mp;
+    const PassDims dc = pass_dims(N, Sc), df = pass_dims(N, Sf);     // the fine pass renders the Sf new samples only
     int r = ensure_pass(c, t->pass[0], dc);
     if (fine) r |= ensure_pass(c, t->pass[1], df);
-    r |= ensure(c, t->Ga, Mmax * 256 * f);
-    r |= ensure(c, t->Gb, Mmax * 256 * f);
-    r |= ensure(c, t->G9, Mmax * 128 * f);
-    r |= ensure(c, t->Graw, Mmax * 4 * f);
-    r |= ensure(c, t->dsig, Mmax * f);
-    r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
-    r |= ensure(c, t->partial, (size_t)2 * kTrainSplitsWide * (kLdC4 + 1) * 256 * f);   // also holds a pass's batched slabs
+    r |= ensure_bwd_workspace(c, t, fine && df.Mp > dc.Mp ? df.Mp : dc.Mp, dc.M);
     r |= ensure(c, t->d_rgb, N * 3 * f);
-    r |= ensure(c, t->d_wext, dc.M * f);
     r |= ensure(c, t->d_zf, (fine ? df.M : 1) * f);
     r |= ensure(c, t->scal, 4 * f);
-    if (!t->macc.p) {
-        r |= ensure(c, t->macc, 4 * sizeof(double));
-        if (!r) HIP_OK(hipMemsetAsync(t->macc.p, 0, 4 * sizeof(double), c->stream));
+    if (!t->macc.p) {                             // (cleared when it is created, whatever else failed to grow)
+        const int rm = ensure(c, t->macc, 4 * sizeof(double));
+        if (!rm) HIP_OK(hipMemsetAsync(t->macc.p, 0, 4 * sizeof(double), c->stream));
+        r |= rm;
     }
-    r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
     if (r) return r;
     float* scal = (float*)t->scal.p;
-    float* Graw = (float*)t->Graw.p;
     float* d_rgb = (float*)t->d_rgb.p;
     // the finiteness flag collects over ONE gradient computation: gradients that were computed and never applied
     // (nerf_train_gradients without nerf_train_apply) must not decide the next step's verdict
@@ -687,20 +726,16 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
                           c->stream);
         if (int q = forward_pass(c, t, 1, df, o, d)) return q;
         launch_mse((const float*)pf.rgb.p, tg, N, (const OptState*)t->opt.p, t->loss_w[1], d_rgb, scal + 1, c->stream);
-        HIP_OK(hipMemsetAsync(Graw + df.M * 4, 0, (df.Mp - df.M) * 4 * f, c->stream));
         float* d_zf = through_sampler ? (float*)t->d_zf.p : nullptr;
-        launch_composite_bwd((const float*)pf.raw.p, (const float*)pf.z.p, (const float*)pf.T.p, N, Sf, d_rgb, nullptr,
-                             Graw, d_zf, c->stream);
-        if (int q = backward_pass(c, t, 1, df, o, d, d_zf)) return q;
+        if (int q = composite_backward_pass(c, t, 1, df, o, d, d_rgb, nullptr, d_zf)) return q;
         if (through_sampler)
             launch_sample_pdf_bwd((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, 0, d_zf,
                                   (float*)t->d_wext.p, c->stream);
     }
     launch_mse((const float*)pc.rgb.p, tg, N, (const OptState*)t->opt.p, t->loss_w[0], d_rgb, scal + 0, c->stream);
-    HIP_OK(hipMemsetAsync(Graw + dc.M * 4, 0, (dc.Mp - dc.M) * 4 * f, c->stream));
-    launch_composite_bwd((const float*)pc.raw.p, (const float*)pc.z.p, (const float*)pc.T.p, N, Sc, d_rgb,
-                         through_sampler ? (const float*)t->d_wext.p : nullptr, Graw, nullptr, c->stream);
-    if (int q = backward_pass(c, t, 0, dc, o, d, nullptr)) return q;
+    if (int q = composite_backward_pass(c, t, 0, dc, o, d, d_rgb, through_sampler ? (const float*)t->d_wext.p : nullptr,
+                                        nullptr))
+        return q;
     if (int q = join_side(c, t)) return q;
     if (t->mixed) {
         // LossScaleOptimizer: unscale, test for Inf/NaN; the verdict is taken on the device (opt_verdict_kernel) and gates
@@ -732,54 +767,53 @@ void take_verdict(nerf_ctx* c, bool recheck) {
 // (src/DietNeRF.py:204-222): coarse pass -> inverse-CDF samples -> fine pass on sort(concat(z_new, z_coarse)) -> rgb.
 // Given d_rgb = dL/d(render()[0]) it leaves dL/d(weights) of both networks in (or adds it to) the gradient blobs:
 // the fine network through its Sc+Sf merged samples, the coarse network only through the sampler (its own rgb is
-// not an output of render() when a fine network exists).
-int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const float* d_rgb_in, int64_t N, int Sc,
-                          int Sf, const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, bool accumulate,
-                          int mem) {
-    TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
-    if (!rays_o || !rays_d || !d_rgb_in) return fail("NULL argument");
-    if (N <= 0) return fail("need at least one ray (got %lld)", (long long)N);
-    if (Sc < 1 || Sc > 1024) return fail("bad coarse sample count %d", Sc);
-    const bool fine = Sf > 0 && t->net[1].present;
-    if (fine && Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
-    if (fine && Sf > 256) return fail("training supports at most 256 fine samples per ray (got %d)", Sf);
-    if (fine && (sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024 || sample_pdf_bwd_lds_bytes(Sc, Sf) > 64 * 1024))
-        return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget", Sc, Sf);
-    const size_t f = sizeof(float);
-    const float *o, *d, *dr, *uc, *uf;
-    if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
-    if (int r = stage_in(c, t->d, rays_d, N * 4 * f, mem, &d)) return r;
-    if (int r = stage_in(c, t->tgt, d_rgb_in, N * 3 * f, mem, &dr)) return r;
-    if (int r = stage_in(c, t->u_c, u_c, (size_t)N * Sc * f, mem, &uc)) return r;
-    if (int r = stage_in(c, t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f, mem, &uf)) return r;
-    const int Sm = Sc + Sf;                                          // the fine pass renders the merged samples
-    PassDims dc{N, Sc, N * Sc, (N * Sc + 127) / 128 * 128};
-    PassDims df{N, Sm, N * (long long)Sm, (N * (long long)Sm + 127) / 128 * 128};
-    const long long Mmax = fine ? df.Mp : dc.Mp;
+// not an output of render() when a fine network exists).  nerf_train_render_gradients runs the two cores below back to back;
+// nerf_train_render_forward / _backward run one each, with the activations kept in a RenderSlot in between.
+
+// The forward half, on TrainState::pass / z_new: coarse pass -> z_new and the merged, sorted depths -> fine pass.
+int render_forward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, const float* o,
+                        const float* d, const float* uc, const float* uf, uint64_t seed, long long ray_base) {
+    const long long N = dc.N;
+    const int Sc = dc.S, Sf = df.S - dc.S;                           // the fine pass renders the Sc + Sf merged samples
     int r = ensure_pass(c, t->pass[0], dc);
     if (fine) r |= ensure_pass(c, t->pass[1], df);
-    r |= ensure(c, t->Ga, Mmax * 256 * f);
-    r |= ensure(c, t->Gb, Mmax * 256 * f);
-    r |= ensure(c, t->G9, Mmax * 128 * f);
-    r |= ensure(c, t->Graw, Mmax * 4 * f);
-    r |= ensure(c, t->dsig, Mmax * f);
-    r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
-    r |= ensure(c, t->partial, (size_t)2 * kTrainSplitsWide * (kLdC4 + 1) * 256 * f);   // also holds a pass's batched slabs
-    r |= ensure(c, t->d_wext, dc.M * f);
-    r |= ensure(c, t->d_zf, (fine ? N * (long long)Sf : 1) * f);
-    r |= ensure(c, t->z_new, (fine ? N * (long long)Sf : 1) * f);
+    r |= ensure(c, t->z_new, (fine ? N * (long long)Sf : 1) * sizeof(float));
+    if (r) return r;
+    TPass& pc = t->pass[0];
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, uc, seed, ray_base, (float*)pc.z.p, c->stream);
+    if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
+    if (!fine) return 0;
+    launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,
+                      (float*)t->pass[1].z.p, c->stream);
+    return forward_pass(c, t, 1, df, o, d);
+}
+
+// The backward half's buffers: the common workspace, dL/dz of the new and of the merged depths, the sampler-only coarse
+// pass's zero d_rgb and, under mixed_float16, the scaled d_rgb and the gradients an accumulating call adds to.
+int ensure_render_bwd(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, bool accumulate) {
+    const size_t f = sizeof(float);
+    const long long N = dc.N;
+    int r = ensure_bwd_workspace(c, t, fine ? df.Mp : dc.Mp, dc.M);
+    r |= ensure(c, t->d_zf, (fine ? N * (long long)(df.S - dc.S) : 1) * f);
     r |= ensure(c, t->d_zm, (fine ? df.M : 1) * f);
     r |= ensure(c, t->zero_rgb, N * 3 * f);
-    r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
     if (t->mixed) {
         r |= ensure(c, t->d_rgb, N * 3 * f);
         if (accumulate)
             for (int w = 0; w < 2; ++w)
                 if (t->net[w].present) r |= ensure(c, t->gsave[w], t->nblob * f);
     }
-    if (r) return r;
-    float* Graw = (float*)t->Graw.p;
+    return r;
+}
+
+// The backward half, on what render_forward_core left in TrainState::pass / z_new; dr: the caller's d_rgb on the device.
+// Runs under a SlotLease (which clears acc_grads on the way out).
+int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, const float* o,
+                         const float* d, const float* uf, uint64_t seed, long long ray_base, const float* dr,
+                         bool accumulate) {
+    const size_t f = sizeof(float);
+    const long long N = dc.N;
+    const int Sc = dc.S, Sf = df.S - dc.S;
     const bool through_sampler = fine && t->cfg.sampler_gradient != 0;
     // the networks this call computes gradients for: the fine one through its merged pass, the coarse one through the
     // sampler (or, without a fine network, through its own rgb)
@@ -802,49 +836,27 @@ int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d,
     }
     t->acc_grads = accumulate && !t->mixed;      // (mixed: the scaled result overwrites, the addition happens after unscaling)
 
-    TPass& pc = t->pass[0];
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, uc, seed, ray_base, (float*)pc.z.p, c->stream);
-    if (int q = forward_pass(c, t, 0, dc, o, d)) { t->acc_grads = false; return q; }
-    int q = 0;
-    if (fine) {
-        TPass& pf = t->pass[1];
-        launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,
-                          (float*)pf.z.p, c->stream);                // z_new (sorted) and the merged, sorted depths
-        q = forward_pass(c, t, 1, df, o, d);
-        if (!q) {
-            HIP_OK(hipMemsetAsync(Graw + df.M * 4, 0, (df.Mp - df.M) * 4 * f, c->stream));
-            float* d_zm = through_sampler ? (float*)t->d_zm.p : nullptr;
-            launch_composite_bwd((const float*)pf.raw.p, (const float*)pf.z.p, (const float*)pf.T.p, N, Sm, dr, nullptr,
-                                 Graw, d_zm, c->stream);
-            q = backward_pass(c, t, 1, df, o, d, d_zm);
-            if (!q && through_sampler) {
-                launch_unmerge_grad((const float*)t->z_new.p, (const float*)pc.z.p, d_zm, N, Sc, Sf, (float*)t->d_zf.p,
-                                    c->stream);
-                launch_sample_pdf_bwd((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base,
-                                      (const float*)t->d_zf.p, (float*)t->d_wext.p, c->stream);
-            }
-        }
-        if (!q) {
-            if (through_sampler) {
-                // the coarse network: no direct rgb term, only dL/d(weights_coarse) from the sampler
-                HIP_OK(hipMemsetAsync(t->zero_rgb.p, 0, N * 3 * f, c->stream));
-                HIP_OK(hipMemsetAsync(Graw + dc.M * 4, 0, (dc.Mp - dc.M) * 4 * f, c->stream));
-                launch_composite_bwd((const float*)pc.raw.p, (const float*)pc.z.p, (const float*)pc.T.p, N, Sc,
-                                     (const float*)t->zero_rgb.p, (const float*)t->d_wext.p, Graw, nullptr, c->stream);
-                q = backward_pass(c, t, 0, dc, o, d, nullptr);
-            } else if (!accumulate) {
-                HIP_OK(hipMemsetAsync(t->net[0].grad, 0, t->nblob * f, c->stream));   // render() does not depend on it
-            }
-        }
+    const TPass& pc = t->pass[0];
+    if (!fine) {
+        if (int q = composite_backward_pass(c, t, 0, dc, o, d, dr, nullptr, nullptr)) return q;
     } else {
-        HIP_OK(hipMemsetAsync(Graw + dc.M * 4, 0, (dc.Mp - dc.M) * 4 * f, c->stream));
-        launch_composite_bwd((const float*)pc.raw.p, (const float*)pc.z.p, (const float*)pc.T.p, N, Sc, dr, nullptr, Graw,
-                             nullptr, c->stream);
-        q = backward_pass(c, t, 0, dc, o, d, nullptr);
+        float* d_zm = through_sampler ? (float*)t->d_zm.p : nullptr;
+        if (int q = composite_backward_pass(c, t, 1, df, o, d, dr, nullptr, d_zm)) return q;
+        if (through_sampler) {
+            launch_unmerge_grad((const float*)t->z_new.p, (const float*)pc.z.p, d_zm, N, Sc, Sf, (float*)t->d_zf.p,
+                                c->stream);
+            launch_sample_pdf_bwd((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base,
+                                  (const float*)t->d_zf.p, (float*)t->d_wext.p, c->stream);
+            // the coarse network: no direct rgb term, only dL/d(weights_coarse) from the sampler
+            HIP_OK(hipMemsetAsync(t->zero_rgb.p, 0, N * 3 * f, c->stream));
+            if (int q = composite_backward_pass(c, t, 0, dc, o, d, (const float*)t->zero_rgb.p, (const float*)t->d_wext.p,
+                                                nullptr))
+                return q;
+        } else if (!accumulate) {
+            HIP_OK(hipMemsetAsync(t->net[0].grad, 0, t->nblob * f, c->stream));   // render() does not depend on it
+        }
     }
-    t->acc_grads = false;
-    if (q) return q;
-    if (int qj = join_side(c, t)) return qj;
+    if (int q = join_side(c, t)) return q;
     if (t->mixed) {
         float* g[2]; const float* add[2]; int n = 0;
         for (int w = 0; w < 2; ++w)
@@ -883,19 +895,57 @@ static void slot_swap_out(TrainState* t, RenderSlot& s) {
     std::swap(t->z_new, s.z_new);
 }
 
+// The scope of one call through the render graph, left on every path (HIP_OK returns included): acc_grads does not outlive
+// it, and a slot's stash is TrainState::pass for exactly its duration.  The slot takes its stash back only after the side
+// stream has joined (the fine pass's batched weight-gradient launch reads it).
+struct SlotLease {
+    nerf_ctx* c;
+    TrainState* t;
+    RenderSlot* s;
+    SlotLease(nerf_ctx* c_, TrainState* t_, RenderSlot* s_ = nullptr) : c(c_), t(t_), s(s_) {
+        if (s) slot_swap_in(t, *s);
+    }
+    ~SlotLease() {
+        if (s) {
+            (void)join_side(c, t);
+            slot_swap_out(t, *s);
+        }
+        t->acc_grads = false;
+    }
+    SlotLease(const SlotLease&) = delete;
+    SlotLease& operator=(const SlotLease&) = delete;
+};
+
+int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const float* d_rgb_in, int64_t N, int Sc,
+                          int Sf, const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, bool accumulate,
+                          int mem) {
+    TrainState* t = c->train;
+    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!rays_o || !rays_d || !d_rgb_in) return fail("NULL argument");
+    bool fine;
+    if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
+    const size_t f = sizeof(float);
+    const float *o, *d, *dr, *uc, *uf;
+    if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
+    if (int r = stage_in(c, t->d, rays_d, N * 4 * f, mem, &d)) return r;
+    if (int r = stage_in(c, t->tgt, d_rgb_in, N * 3 * f, mem, &dr)) return r;
+    if (int r = stage_in(c, t->u_c, u_c, (size_t)N * Sc * f, mem, &uc)) return r;
+    if (int r = stage_in(c, t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f, mem, &uf)) return r;
+    const PassDims dc = pass_dims(N, Sc), df = pass_dims(N, Sc + Sf);
+    if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate)) return r;
+    SlotLease lease(c, t);                        // (no slot: the activations stay in TrainState::pass)
+    if (int r = render_forward_core(c, t, dc, df, fine, o, d, uc, uf, seed, ray_base)) return r;
+    return render_backward_core(c, t, dc, df, fine, o, d, uf, seed, ray_base, dr, accumulate);
+}
+
 int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float* rays_d, int64_t N, int Sc, int Sf,
                         const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, int mem) {
     TrainState* t = c->train;
     if (!t || !t->training) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d) return fail("NULL argument");
     if (slot < 0 || slot >= kMaxRenderSlots) return fail("slot %d out of range (0..%d)", slot, kMaxRenderSlots - 1);
-    if (N <= 0) return fail("need at least one ray (got %lld)", (long long)N);
-    if (Sc < 1 || Sc > 1024) return fail("bad coarse sample count %d", Sc);
-    const bool fine = Sf > 0 && t->net[1].present;
-    if (fine && Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
-    if (fine && Sf > 256) return fail("training supports at most 256 fine samples per ray (got %d)", Sf);
-    if (fine && (sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024 || sample_pdf_bwd_lds_bytes(Sc, Sf) > 64 * 1024))
-        return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget", Sc, Sf);
+    bool fine;
+    if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
     if ((size_t)slot >= t->slots.size()) t->slots.resize((size_t)slot + 1);
     RenderSlot& s = t->slots[slot];
     s.valid = false;
@@ -913,29 +963,12 @@ int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float*
     s.has_uf = fine && u_f != nullptr;
     if (s.has_uc) if (int r = keep(s.u_c, u_c, (size_t)N * Sc * f)) return r;
     if (s.has_uf) if (int r = keep(s.u_f, u_f, (size_t)N * Sf * f)) return r;
-    const float *o = (const float*)s.o.p, *d = (const float*)s.d.p;
     const float* uc = s.has_uc ? (const float*)s.u_c.p : nullptr;
     const float* uf = s.has_uf ? (const float*)s.u_f.p : nullptr;
-    const int Sm = Sc + Sf;
-    PassDims dc{N, Sc, N * Sc, (N * Sc + 127) / 128 * 128};
-    PassDims df{N, Sm, N * (long long)Sm, (N * (long long)Sm + 127) / 128 * 128};
-    slot_swap_in(t, s);
-    int r = ensure_pass(c, t->pass[0], dc);
-    if (fine) r |= ensure_pass(c, t->pass[1], df);
-    r |= ensure(c, t->z_new, (fine ? N * (long long)Sf : 1) * f);
-    if (!r) {
-        TPass& pc = t->pass[0];
-        launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, uc, seed, ray_base, (float*)pc.z.p, c->stream);
-        r = forward_pass(c, t, 0, dc, o, d);
-        if (!r && fine) {
-            launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,
-                              (float*)t->pass[1].z.p, c->stream);
-            r = forward_pass(c, t, 1, df, o, d);
-        }
-    }
-    slot_swap_out(t, s);
-    if (r) return r;
-    HIP_OK(hipGetLastError());
+    SlotLease lease(c, t, &s);
+    if (int r = render_forward_core(c, t, pass_dims(N, Sc), pass_dims(N, Sc + Sf), fine, (const float*)s.o.p,
+                                    (const float*)s.d.p, uc, uf, seed, ray_base))
+        return r;
     s.N = N; s.Sc = Sc; s.Sf = fine ? Sf : 0; s.seed = seed; s.ray_base = ray_base;
     s.valid = true;
     return 0;
@@ -949,99 +982,32 @@ int render_backward_impl(nerf_ctx* c, int slot, const float* d_rgb_in, bool accu
         return fail("slot %d holds no forward pass (nerf_train_render_forward first; a backward pass consumes it, and so does "
                     "an optimizer step)", slot);
     RenderSlot& s = t->slots[slot];
-    const long long N = s.N;
-    const int Sc = s.Sc, Sf = s.Sf;
-    const bool fine = Sf > 0;
-    const size_t f = sizeof(float);
+    const bool fine = s.Sf > 0;
+    const PassDims dc = pass_dims(s.N, s.Sc), df = pass_dims(s.N, s.Sc + s.Sf);
     const float* dr;
-    if (int r = stage_in(c, t->tgt, d_rgb_in, N * 3 * f, mem, &dr)) return r;
-    const int Sm = Sc + Sf;
-    PassDims dc{N, Sc, N * Sc, (N * Sc + 127) / 128 * 128};
-    PassDims df{N, Sm, N * (long long)Sm, (N * (long long)Sm + 127) / 128 * 128};
-    const long long Mmax = fine ? df.Mp : dc.Mp;
-    int r = ensure(c, t->Ga, Mmax * 256 * f);
-    r |= ensure(c, t->Gb, Mmax * 256 * f);
-    r |= ensure(c, t->G9, Mmax * 128 * f);
-    r |= ensure(c, t->Graw, Mmax * 4 * f);
-    r |= ensure(c, t->dsig, Mmax * f);
-    r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
-    r |= ensure(c, t->partial, (size_t)2 * kTrainSplitsWide * (kLdC4 + 1) * 256 * f);
-    r |= ensure(c, t->d_wext, dc.M * f);
-    r |= ensure(c, t->d_zf, (fine ? N * (long long)Sf : 1) * f);
-    r |= ensure(c, t->d_zm, (fine ? df.M : 1) * f);
-    r |= ensure(c, t->zero_rgb, N * 3 * f);
-    r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
-    if (t->mixed) {
-        r |= ensure(c, t->d_rgb, N * 3 * f);
-        if (accumulate)
-            for (int w = 0; w < 2; ++w)
-                if (t->net[w].present) r |= ensure(c, t->gsave[w], t->nblob * f);
+    if (int r = stage_in(c, t->tgt, d_rgb_in, s.N * 3 * sizeof(float), mem, &dr)) return r;
+    if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate)) return r;
+    s.valid = false;                              // consumed, whatever happens below
+    SlotLease lease(c, t, &s);
+    return render_backward_core(c, t, dc, df, fine, (const float*)s.o.p, (const float*)s.d.p,
+                                s.has_uf ? (const float*)s.u_f.p : nullptr, s.seed, s.ray_base, dr, accumulate);
+}
+
+// The outputs of a gradient / render call, each only if the caller asks for it: rgb (N x 3) and the two gradient blobs,
+// device -> host or device -> device by `mem`, synchronous for a host caller.  grad_fine needs the call's fine pass (Sf > 0
+// samples and a fine network); without one it fails after the copies before it are enqueued.
+int copy_out(nerf_ctx* c, int mem, int Sf, float* grad_coarse, float* grad_fine, float* rgb_out = nullptr,
+             const void* rgb = nullptr, long long N = 0) {
+    const TrainState* t = c->train;
+    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t nb = t->nblob * sizeof(float);
+    if (rgb_out) HIP_OK(hipMemcpyAsync(rgb_out, rgb, N * 3 * sizeof(float), kind, c->stream));
+    if (grad_coarse) HIP_OK(hipMemcpyAsync(grad_coarse, t->net[0].grad, nb, kind, c->stream));
+    if (grad_fine) {
+        if (!(Sf > 0 && t->net[1].present)) return fail("grad_fine requested but no fine pass ran (Sf = %d)", Sf);
+        HIP_OK(hipMemcpyAsync(grad_fine, t->net[1].grad, nb, kind, c->stream));
     }
-    if (r) return r;
-    float* Graw = (float*)t->Graw.p;
-    const bool through_sampler = fine && t->cfg.sampler_gradient != 0;
-    const bool computes[2] = {!fine || through_sampler, fine};
-    if (t->mixed) {                               // as render_gradients_impl: scale d_rgb on the device, unscale at the end
-        OptState* st = (OptState*)t->opt.p;
-        if (!accumulate) launch_opt_begin(st, c->stream);
-        launch_scale_by_loss_scale(dr, N * 3, st, (float*)t->d_rgb.p, c->stream);
-        dr = (const float*)t->d_rgb.p;
-        if (accumulate)
-            for (int w = 0; w < 2; ++w)
-                if (computes[w] && t->net[w].present)
-                    HIP_OK(hipMemcpyAsync(t->gsave[w].p, t->net[w].grad, t->nblob * f, hipMemcpyDeviceToDevice, c->stream));
-    }
-    t->acc_grads = accumulate && !t->mixed;
-    const float *o = (const float*)s.o.p, *d = (const float*)s.d.p;
-    const float* uf = s.has_uf ? (const float*)s.u_f.p : nullptr;
-    const uint64_t seed = s.seed;
-    const long long ray_base = s.ray_base;
-    slot_swap_in(t, s);
-    TPass& pc = t->pass[0];
-    int q = 0;
-    if (fine) {
-        TPass& pf = t->pass[1];
-        HIP_OK(hipMemsetAsync(Graw + df.M * 4, 0, (df.Mp - df.M) * 4 * f, c->stream));
-        float* d_zm = through_sampler ? (float*)t->d_zm.p : nullptr;
-        launch_composite_bwd((const float*)pf.raw.p, (const float*)pf.z.p, (const float*)pf.T.p, N, Sm, dr, nullptr, Graw, d_zm,
-                             c->stream);
-        q = backward_pass(c, t, 1, df, o, d, d_zm);
-        if (!q && through_sampler) {
-            launch_unmerge_grad((const float*)t->z_new.p, (const float*)pc.z.p, d_zm, N, Sc, Sf, (float*)t->d_zf.p, c->stream);
-            launch_sample_pdf_bwd((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base,
-                                  (const float*)t->d_zf.p, (float*)t->d_wext.p, c->stream);
-            HIP_OK(hipMemsetAsync(t->zero_rgb.p, 0, N * 3 * f, c->stream));
-            HIP_OK(hipMemsetAsync(Graw + dc.M * 4, 0, (dc.Mp - dc.M) * 4 * f, c->stream));
-            launch_composite_bwd((const float*)pc.raw.p, (const float*)pc.z.p, (const float*)pc.T.p, N, Sc,
-                                 (const float*)t->zero_rgb.p, (const float*)t->d_wext.p, Graw, nullptr, c->stream);
-            q = backward_pass(c, t, 0, dc, o, d, nullptr);
-        } else if (!q && !accumulate) {
-            HIP_OK(hipMemsetAsync(t->net[0].grad, 0, t->nblob * f, c->stream));   // render() does not depend on it
-        }
-    } else {
-        HIP_OK(hipMemsetAsync(Graw + dc.M * 4, 0, (dc.Mp - dc.M) * 4 * f, c->stream));
-        launch_composite_bwd((const float*)pc.raw.p, (const float*)pc.z.p, (const float*)pc.T.p, N, Sc, dr, nullptr, Graw, nullptr,
-                             c->stream);
-        q = backward_pass(c, t, 0, dc, o, d, nullptr);
-    }
-    t->acc_grads = false;
-    int qj = join_side(c, t);                     // (before the stash leaves TrainState::pass: the side stream reads it)
-    slot_swap_out(t, s);
-    s.valid = false;
-    if (q) return q;
-    if (qj) return qj;
-    if (t->mixed) {
-        float* g[2]; const float* add[2]; int n = 0;
-        for (int w = 0; w < 2; ++w)
-            if (computes[w] && t->net[w].present) {
-                g[n] = t->net[w].grad;
-                add[n] = accumulate ? (const float*)t->gsave[w].p : nullptr;
-                ++n;
-            }
-        launch_unscale_check(g[0], n > 1 ? g[1] : nullptr, t->nblob, (OptState*)t->opt.p, c->stream, false, add[0],
-                             n > 1 ? add[1] : nullptr);
-    }
-    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1098,20 +1064,8 @@ void train_free(nerf_ctx* c) {
     if (t->sidx) (void)hipFree(t->sidx);
     if (t->cidx) (void)hipFree(t->cidx);
     for (int32_t* bi : t->bidx) if (bi) (void)hipFree(bi);
-    std::vector<TPass*> passes = {&t->pass[0], &t->pass[1]};
-    for (RenderSlot& sl : t->slots) {
-        passes.push_back(&sl.pass[0]);
-        passes.push_back(&sl.pass[1]);
-        for (DevBuf* b : {&sl.o, &sl.d, &sl.u_c, &sl.u_f, &sl.z_new}) free_buf(*b);
-    }
-    for (TPass* pp : passes) {
-        TPass& p = *pp;
-        DevBuf* bs[] = {&p.C4, &p.C8, &p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7, &p.H8b, &p.H9, &p.raw, &p.T, &p.w,
-                        &p.rgb, &p.z};
-        for (DevBuf* b : bs) free_buf(*b);
-        free_buf(p.masks); free_buf(p.dxa); free_buf(p.dxb); free_buf(p.rs);
-        for (DevBuf& b : p.D) free_buf(b);
-    }
+    for (TPass& p : t->pass) free_pass(p);
+    for (RenderSlot& sl : t->slots) free_slot(sl);
     if (t->side) { (void)hipStreamSynchronize(t->side); (void)hipStreamDestroy(t->side); }
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
@@ -1330,18 +1284,10 @@ int nerf_train_gradients(nerf_ctx* c, const float* rays_orig, const float* rays_
                          float* grad_coarse, float* grad_fine, float* metrics, int mem) {
     ENTER(c);
     if (int r = gradients_impl(c, rays_orig, rays_dirs, target_rgb, N, Sc, Sf, u_coarse, u_fine, seed, mem)) return r;
-    TrainState* t = c->train;
-    const bool fine = Sf > 0 && t->net[1].present;
     // (mixed_float16: the gradients come back unscaled; the skip-or-apply verdict and the loss-scale move belong to
     // nerf_train_apply, which tests the blobs it is given)
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (grad_coarse) HIP_OK(hipMemcpyAsync(grad_coarse, t->net[0].grad, t->nblob * sizeof(float), kind, c->stream));
-    if (grad_fine) {
-        if (!fine) return fail("grad_fine requested but no fine pass ran (Sf = %d)", Sf);
-        HIP_OK(hipMemcpyAsync(grad_fine, t->net[1].grad, t->nblob * sizeof(float), kind, c->stream));
-    }
-    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
-    return read_metrics(c, fine, metrics);
+    if (int r = copy_out(c, mem, Sf, grad_coarse, grad_fine)) return r;
+    return read_metrics(c, Sf > 0 && c->train->net[1].present, metrics);
 }
 
 int nerf_train_render_gradients(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, const float* d_rgb, int64_t N,
@@ -1351,17 +1297,8 @@ int nerf_train_render_gradients(nerf_ctx* c, const float* rays_orig, const float
     ENTER(c);
     if (int r = render_gradients_impl(c, rays_orig, rays_dirs, d_rgb, N, Sc, Sf, u_coarse, u_fine, seed, ray_base,
                                       accumulate != 0, mem)) return r;
-    TrainState* t = c->train;
-    const bool fine = Sf > 0 && t->net[1].present;
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (rgb_out) HIP_OK(hipMemcpyAsync(rgb_out, t->pass[fine ? 1 : 0].rgb.p, N * 3 * sizeof(float), kind, c->stream));
-    if (grad_coarse) HIP_OK(hipMemcpyAsync(grad_coarse, t->net[0].grad, t->nblob * sizeof(float), kind, c->stream));
-    if (grad_fine) {
-        if (!fine) return fail("grad_fine requested but no fine pass ran (Sf = %d)", Sf);
-        HIP_OK(hipMemcpyAsync(grad_fine, t->net[1].grad, t->nblob * sizeof(float), kind, c->stream));
-    }
-    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    const bool fine = Sf > 0 && c->train->net[1].present;
+    return copy_out(c, mem, Sf, grad_coarse, grad_fine, rgb_out, c->train->pass[fine ? 1 : 0].rgb.p, N);
 }
 
 int nerf_train_render_forward(nerf_ctx* c, int32_t slot, const float* rays_orig, const float* rays_dirs, int64_t N, int32_t Sc,
@@ -1370,12 +1307,7 @@ int nerf_train_render_forward(nerf_ctx* c, int32_t slot, const float* rays_orig,
     ENTER(c);
     if (int r = render_forward_impl(c, slot, rays_orig, rays_dirs, N, Sc, Sf, u_coarse, u_fine, seed, ray_base, mem)) return r;
     const RenderSlot& s = c->train->slots[slot];
-    if (rgb_out) {
-        const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIP_OK(hipMemcpyAsync(rgb_out, s.pass[s.Sf > 0 ? 1 : 0].rgb.p, N * 3 * sizeof(float), kind, c->stream));
-    }
-    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return copy_out(c, mem, s.Sf, nullptr, nullptr, rgb_out, s.pass[s.Sf > 0 ? 1 : 0].rgb.p, N);
 }
 
 int nerf_train_render_backward(nerf_ctx* c, int32_t slot, const float* d_rgb, int32_t accumulate, float* grad_coarse,
@@ -1384,12 +1316,7 @@ int nerf_train_render_backward(nerf_ctx* c, int32_t slot, const float* d_rgb, in
     const bool fine = c->train && slot >= 0 && (size_t)slot < c->train->slots.size() && c->train->slots[slot].Sf > 0;
     if (grad_fine && !fine) return fail("grad_fine requested but slot %d ran no fine pass", slot);   // (before it is consumed)
     if (int r = render_backward_impl(c, slot, d_rgb, accumulate != 0, mem)) return r;
-    TrainState* t = c->train;
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (grad_coarse) HIP_OK(hipMemcpyAsync(grad_coarse, t->net[0].grad, t->nblob * sizeof(float), kind, c->stream));
-    if (grad_fine) HIP_OK(hipMemcpyAsync(grad_fine, t->net[1].grad, t->nblob * sizeof(float), kind, c->stream));
-    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return copy_out(c, mem, c->train->slots[slot].Sf, grad_coarse, grad_fine);
 }
 
 int nerf_train_render_release(nerf_ctx* c) {
@@ -1398,15 +1325,7 @@ int nerf_train_render_release(nerf_ctx* c) {
     if (!t) return 0;
     HIP_OK(hipStreamSynchronize(c->stream));
     if (t->side) HIP_OK(hipStreamSynchronize(t->side));
-    for (RenderSlot& sl : t->slots) {
-        for (TPass& p : sl.pass) {
-            DevBuf* bs[] = {&p.C4, &p.C8, &p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7, &p.H8b, &p.H9, &p.raw, &p.T, &p.w,
-                            &p.rgb, &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs};
-            for (DevBuf* b : bs) free_buf(*b);
-            for (DevBuf& b : p.D) free_buf(b);
-        }
-        for (DevBuf* b : {&sl.o, &sl.d, &sl.u_c, &sl.u_f, &sl.z_new}) free_buf(*b);
-    }
+    for (RenderSlot& sl : t->slots) free_slot(sl);
     t->slots.clear();
     (void)hipGetLastError();      // (a failed allocation while filling slots is what usually brings a caller here: start clean)
     return 0;
