@@ -44,11 +44,15 @@ enum {
 
 /* Network + frustum description: the 9 net/render keys of src/ConfigurationKeys.py:64-111. */
 typedef struct nerf_config {
-    int32_t n_pos_enc_xyz;    /* n_pos_enc_dim_xyz   (5)   */
-    int32_t n_pos_enc_dir;    /* n_pos_enc_view_dir  (4)   */
-    int32_t n_angles;         /* n_angles_for_model  (2)   */
-    int32_t hidden_dim;       /* hidden_layer_dim    (256) */
-    int32_t last_hidden_dim;  /* last_hidden_layer_dim (128) */
+    int32_t n_pos_enc_xyz;    /* n_pos_enc_dim_xyz   (5)   accepted: 1..10; 6..10 with precision f16x3 / f16 only */
+    int32_t n_pos_enc_dir;    /* n_pos_enc_view_dir  (4)   accepted: 1..4 */
+    int32_t n_angles;         /* n_angles_for_model  (2)   accepted: 0 (xyz-only network), 1, 2 */
+    int32_t hidden_dim;       /* hidden_layer_dim    (256) accepted: 256 only */
+    int32_t last_hidden_dim;  /* last_hidden_layer_dim (128) accepted: 128 only
+                               * Anything else fails nerf_ctx_create (nerf_blob_size returns 0) with a message naming the
+                               * accepted ranges.  Weight blobs follow the reference's Keras layer shapes for the given
+                               * values (src/NeRF.py:249-339): layer 0 has 3 + 6 n_pos_enc_xyz inputs, the view-direction
+                               * block 2 n_pos_enc_view_dir (n_angles + 1). */
     float leaky_relu_alpha;   /* leaky_relu_alpha    (0.05) */
     float near_boundary;      /* NeRF.near_boundary, src/NeRF.py:45 */
     float far_boundary;       /* NeRF.far_boundary,  src/NeRF.py:46 */

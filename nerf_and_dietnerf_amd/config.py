@@ -117,9 +117,10 @@ def get_nerf(config: Dict, near_boundary: float, far_boundary: float, *, images=
         model.load_weights(path)
     else:
         from .weights import glorot_blob            # Keras' Dense defaults: Glorot-uniform kernels, zero biases
-        na = net["n_angles_for_model"]
+        kw = dict(n_pos_enc_xyz=net["n_pos_enc_dim_xyz"], n_pos_enc_dir=net["n_pos_enc_view_dir"],
+                  n_angles=net["n_angles_for_model"])
         fine = render["n_render_samples_fine"] > 0
-        model.set_weights(glorot_blob(0, n_angles=na), glorot_blob(1, n_angles=na) if fine else None)
+        model.set_weights(glorot_blob(0, **kw), glorot_blob(1, **kw) if fine else None)
     model.compile(training[OPTIMIZER_LR], mixed_float16=policy == MIXED_FLOAT16)
     return model
 

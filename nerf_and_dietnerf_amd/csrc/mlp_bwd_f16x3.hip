@@ -680,14 +680,14 @@ void mlp_bwd_f16x3_set_attributes() {
 // The backward stream as an index map (host): idx[slot] = 2 * (src + 1) + is_lo, 0 = padding; src = index into the
 // blob (Keras get_weights() order).  Re-packed on the device after every optimizer step by repack_bwd_kernel.
 // ------------------------------------------------------------------------------------------------
-void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 entries */) {
+void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 entries */, int xyz_dim) {
     memset(idx, 0, (kBwdStreamBytes / 2) * sizeof(int32_t));
     const int kd = 256 + 8 * (n_angles + 1);
     const bool xyz_only = n_angles == 0;
-    const int shapes_dir[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
+    const int shapes_dir[12][2] = {{xyz_dim, 256}, {256, 256}, {256, 256}, {256, 256}, {xyz_dim + 256, 256}, {256, 256},
                                    {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}, {0, 0}};
     // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int shapes_xyz[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
+    const int shapes_xyz[12][2] = {{xyz_dim, 256}, {256, 256}, {256, 256}, {256, 256}, {xyz_dim + 256, 256}, {256, 256},
                                    {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
     const int (*shapes)[2] = xyz_only ? shapes_xyz : shapes_dir;
     long long koff[12], off = 0;
@@ -730,14 +730,14 @@ void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdS
         return [=](int u, int i, int n, int e, int h) -> long long {
             if (u < nx) {
                 const int row = 32 * u + i;
-                return row < kXyzDim ? koff[l] + (long long)row * 256 + frag_feature(n, e, h) : -1;
+                return row < xyz_dim ? koff[l] + (long long)row * 256 + frag_feature(n, e, h) : -1;
             }
             return koff[l] + (long long)(row0 + 32 * (u - nx) + i) * 256 + frag_feature(n, e, h);
         };
     };
     for (int l = xyz_only ? 8 : 7; l >= 5; --l) emit(8, 16, hidden(l, 0));
-    if (dx) emit(10, 16, with_xyz(4, 2, kXyzDim));
-    else emit(8, 16, hidden(4, kXyzDim));
+    if (dx) emit(10, 16, with_xyz(4, 2, xyz_dim));
+    else emit(8, 16, hidden(4, xyz_dim));
     for (int l = 3; l >= 1; --l) emit(8, 16, hidden(l, 0));
     if (dx) emit(2, 16, with_xyz(0, 2, 0));
 }

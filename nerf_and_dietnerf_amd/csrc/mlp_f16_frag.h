@@ -47,7 +47,14 @@ __device__ __forceinline__ void split_trunc(float y, float& hi_f, float& lo_f) {
 
 // ================= geometry of the forward streams and constant blocks (mlp_f16x3.hip, mlp_f16_2t.hip) =================
 // ---- stream geometry (quads of 1 KiB = one fp16 A fragment: 64 lanes x 8 halfs) ----
-constexpr int kHStepsPE = 3;      // 33 inputs -> 48 slots
+// Octaves the fused fp16 kernels of a translation unit encode: 5 (mlp_f16x3.hip), or 10 in the wide-PE build of the same
+// source (mlp_f16x3_wide.hip, networks with n_pos_enc_dim_xyz 6..10).  Both builds have the same chunk counts and stream sizes.
+#ifndef NERF_PE_LX
+#define NERF_PE_LX 5
+#endif
+constexpr int kPeLx = NERF_PE_LX;
+constexpr int kPeDim = 3 + 6 * kPeLx;                 // 33 (wide: 63)
+constexpr int kHStepsPE = (kPeDim + 15) / 16;         // 33 inputs -> 48 slots (wide: 63 -> 64)
 constexpr int kHStepsHid = 16;
 constexpr int kHStepsDir = 2;     // 24 inputs -> 32 slots
 constexpr int kHQpuPE = 2 * kHStepsPE;                       // hi + lo fragment per k-step

@@ -18,7 +18,11 @@
 #include <math.h>
 #include <string.h>
 
+#if NERF_PE_LX == 5
 namespace nerf {
+#else
+namespace nerf::wide {     // the wide-PE build (mlp_f16x3_wide.hip): same kernels with 10 xyz octaves
+#endif
 
 #ifdef NERF_STAMPS
 __device__ unsigned long long g_stamps_h[16];
@@ -53,7 +57,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                                              float alpha, float* st_prev, float* st_cur, frag4* mk_prev_ptr,
                                              frag4* mk_cur_ptr, frag4& mk_prev, frag4& mk_cur, f32x16 (&accs)[4],
                                              frag4 (&xh)[16], frag4 (&xl)[16], frag4 (&nh)[14], frag4 (&nl)[14],
-                                             const frag4 (&peh)[3], const frag4 (&pel)[3], const frag4 (&dh)[2],
+                                             const frag4 (&peh)[kHStepsPE], const frag4 (&pel)[kHStepsPE], const frag4 (&dh)[2],
                                              const frag4 (&dl)[2], float (&xc)[64], float& sigma_raw) {
     constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_HIDSIG ? 9 : BODY == BODY_LAST0 ? 4 : 8;
     constexpr int NSTEP = BODY == BODY_PE ? kHStepsPE : (BODY == BODY_HID || BODY == BODY_HIDSIG || BODY == BODY_LAST0) ? kHStepsHid
@@ -413,7 +417,7 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    frag4 xh[16], xl[16], nh[14], nl[14], peh[3], pel[3], dh[2], dl[2];
+    frag4 xh[16], xl[16], nh[14], nl[14], peh[kHStepsPE], pel[kHStepsPE], dh[2], dl[2];
     f32x16 accs[4];
     float xc[64];
     float sigma_raw = 0.f;
@@ -442,22 +446,28 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
         }
         const float kPi = 3.1415927410125732f;
         // 24 slots per lane half: h=0: sin of the 15 angles, x, y, z; h=1: cos of the 15 angles
-        float pv[24];
+        // (wide-PE build: 32 slots per half: sin / cos of the 30 angles, then h=0: x, y; h=1: z, pad -- h_pe_row)
+        float pv[8 * kHStepsPE];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float v = c == 0 ? px : c == 1 ? py : pz;
             if constexpr (FAST) {
-                sin_ladder_fp16_modes<kLx>(v * kPi, h, &pv[c * kLx]);     // angle doubling: single-pass fp16 modes only
+                sin_ladder_fp16_modes<kPeLx>(v * kPi, h, &pv[c * kPeLx]);     // angle doubling: single-pass fp16 modes only
             } else {
 #pragma unroll
-                for (int k = 0; k < kLx; ++k) pv[c * kLx + k] = sin_shifted(v * (kPi * (float)(1 << k)), h);
+                for (int k = 0; k < kPeLx; ++k) pv[c * kPeLx + k] = sin_shifted(v * (kPi * (float)(1 << k)), h);
             }
         }
-        pv[15] = h ? 0.f : px; pv[16] = h ? 0.f : py; pv[17] = h ? 0.f : pz;
+        if constexpr (kPeLx == 5) {
+            pv[15] = h ? 0.f : px; pv[16] = h ? 0.f : py; pv[17] = h ? 0.f : pz;
 #pragma unroll
-        for (int i = 18; i < 24; ++i) pv[i] = 0.f;
+            for (int i = 18; i < 24; ++i) pv[i] = 0.f;
+        } else {
+            static_assert(kPeLx == 10, "the wide-PE layout holds exactly 10 octaves");
+            pv[30] = h ? pz : px; pv[31] = h ? 0.f : py;
+        }
 #pragma unroll
-        for (int n = 0; n < 3; ++n) {
+        for (int n = 0; n < kHStepsPE; ++n) {
             float t8[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) t8[e] = pv[n * 8 + e];
@@ -618,7 +628,7 @@ void launch_mlp_f16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool si
     else hipLaunchKernelGGL(mlp_f16x3_kernel, dim3(grid), dim3(256), kLdsTotal, stream, a);
 }
 
-#ifdef NERF_STAMPS
+#if defined(NERF_STAMPS) && NERF_PE_LX == 5
 extern "C" void nerf_debug_read_stamps_h(unsigned long long* out) {
     (void)hipDeviceSynchronize();
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_h), sizeof(unsigned long long) * 16);
@@ -682,7 +692,11 @@ float f16_to_f32(uint16_t hbits) {
     return f;
 }
 int h_pe_row(int v, int h) {   // slot v (0..23) of lane half h -> row of the (33, .) kernel; -1 = pad
-    if (v < 15) { const int c = v / 5, k = v % 5; return c * 11 + 1 + 2 * k + h; }
+    if (v < 3 * kPeLx) { const int c = v / kPeLx, k = v % kPeLx; return c * (1 + 2 * kPeLx) + 1 + 2 * k + h; }
+    if (kPeLx != 5) {              // wide-PE build: slots 0..31 of the (63, .) kernel; raw x, y in half 0, z in half 1
+        if (v == 30) return h ? 2 * (1 + 2 * kPeLx) : 0;
+        return v == 31 && h == 0 ? 1 + 2 * kPeLx : -1;
+    }
     if (v < 18 && h == 0) return (v - 15) * 11;
     return -1;
 }
@@ -704,9 +718,9 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
     const int kd = 256 + 8 * (n_angles + 1);
     const bool xyz_only = n_angles == 0;
     // Keras creation order; xyz-only (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int shapes_dir[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
+    const int shapes_dir[12][2] = {{kPeDim, 256}, {256, 256}, {256, 256}, {256, 256}, {kPeDim + 256, 256}, {256, 256},
                                    {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}, {0, 0}};
-    const int shapes_xyz[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
+    const int shapes_xyz[12][2] = {{kPeDim, 256}, {256, 256}, {256, 256}, {256, 256}, {kPeDim + 256, 256}, {256, 256},
                                    {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
     const int (*shapes)[2] = xyz_only ? shapes_xyz : shapes_dir;
     struct Lay { long long k, b; int in, out; } L[12];
@@ -732,7 +746,7 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
                         else if (body == BODY_HID || body == BODY_HIDSIG || body == BODY_LAST0) row = h_hid_row(n, e, h);
                         else if (body == BODY_SKIP) {
                             if (n < kHStepsPE) row = h_pe_row(n * 8 + e, h);
-                            else row = kXyzDim + h_hid_row(n - kHStepsPE, e, h);
+                            else row = kPeDim + h_hid_row(n - kHStepsPE, e, h);
                         } else {
                             if (n < kHStepsHid) row = h_hid_row(n, e, h);
                             else { const int r = h_dir_row((n - kHStepsHid) * 8 + e, h, n_angles); row = r < 0 ? -1 : kHidden + r; }

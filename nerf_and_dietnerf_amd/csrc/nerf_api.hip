@@ -57,9 +57,99 @@ int enter(nerf_ctx* c) {
     return 0;
 }
 
-int upload_packed_weights(nerf_ctx* c, int which, const float* blob) {
+// The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
+static int layer_dims(int lx, int ld, int n_angles, int dims[12][2]) {
+    const int xd = 3 + 6 * lx;                                  // src/NeRF.py:312
+    const int kd = 256 + 2 * ld * (n_angles + 1);               // [hidden, dir_enc], src/NeRF.py:313-314
+    const int with_dirs[11][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
+                                  {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}};
+    // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
+    const int xyz_only[12][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
+                                 {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
+    const int n = n_angles == 0 ? 12 : 11;
+    for (int l = 0; l < n; ++l) {
+        dims[l][0] = n_angles == 0 ? xyz_only[l][0] : with_dirs[l][0];
+        dims[l][1] = n_angles == 0 ? xyz_only[l][1] : with_dirs[l][1];
+    }
+    return n;
+}
+
+size_t blob_floats(int lx, int ld, int n_angles) {
+    int dims[12][2];
+    const int n = layer_dims(lx, ld, n_angles, dims);
+    size_t s = 0;
+    for (int l = 0; l < n; ++l) s += (size_t)dims[l][0] * dims[l][1] + dims[l][1];
+    return s;
+}
+
+void blob_expand_index(int lx, int ld, int n_angles, int32_t* idx, int layout_lx) {
+    int wide[12][2], dims[12][2];
+    const int n = layer_dims(layout_lx, kLd, n_angles, wide);
+    layer_dims(lx, ld, n_angles, dims);
+    const int xd_layout = 3 + 6 * layout_lx;
+    // xyz encoding row of the (layout_lx) layout -> row of the (lx) layout: per component [x, sin0, cos0, sin1, cos1, ...]
+    auto xyz_row = [&](int r) {
+        const int c = r / (1 + 2 * layout_lx), j = r % (1 + 2 * layout_lx);
+        if (j == 0) return c * (1 + 2 * lx);
+        const int k = (j - 1) / 2, h = (j - 1) % 2;
+        return k < lx ? c * (1 + 2 * lx) + 1 + 2 * k + h : -1;
+    };
+    // direction encoding row: per component [sin0, cos0, sin1, cos1, ...] (src/UtilsNeuralRadianceField.py:52-65)
+    auto dir_row = [&](int r) {
+        const int c = r / (2 * kLd), j = r % (2 * kLd), k = j / 2, h = j % 2;
+        return k < ld ? c * 2 * ld + 2 * k + h : -1;
+    };
+    size_t src = 0, dst = 0;
+    for (int l = 0; l < n; ++l) {
+        for (int r = 0; r < wide[l][0]; ++r) {
+            int rs = r;
+            if (l == 0) rs = xyz_row(r);
+            else if (l == 4) rs = r < xd_layout ? xyz_row(r) : 3 + 6 * lx + (r - xd_layout);
+            else if (n_angles != 0 && (l == 8 || l == 10)) rs = r < kHidden ? r : (dir_row(r - kHidden) < 0 ? -1 : kHidden + dir_row(r - kHidden));
+            for (int f = 0; f < wide[l][1]; ++f)
+                idx[dst++] = rs < 0 ? 0 : (int32_t)(src + (size_t)rs * dims[l][1] + f + 1);
+        }
+        src += (size_t)dims[l][0] * dims[l][1];
+        for (int f = 0; f < wide[l][1]; ++f) idx[dst++] = (int32_t)(src + f + 1);
+        src += dims[l][1];
+    }
+}
+
+int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
     HIP_OK(hipSetDevice(c->cfg.device));
     NetWeights& n = c->net[which];
+    // the packers take the (kLx, kLd) layout (the wide-PE packers the (kLxWide, kLd) one): a network with fewer octaves is
+    // spread into it with zero rows
+    std::vector<float> spread;
+    const float* blob = blob_in;
+    const int L = pe_layout_lx(c->cfg.n_pos_enc_xyz);
+    if (c->cfg.n_pos_enc_xyz != L || c->cfg.n_pos_enc_dir != kLd) {
+        std::vector<int32_t> idx(blob_floats(L, kLd, c->cfg.n_angles));
+        blob_expand_index(c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, c->cfg.n_angles, idx.data(), L);
+        spread.resize(idx.size());
+        for (size_t i = 0; i < idx.size(); ++i) spread[i] = idx[i] ? blob_in[idx[i] - 1] : 0.f;
+        blob = spread.data();
+    }
+    if (L != kLx) {
+        // wide-PE network: the two fp16 streams (3-pass, hi-only) and their constants; there is no exact-fp32 kernel
+        const bool xyz = c->cfg.n_angles == 0;
+        const size_t b3 = xyz ? kStreamBytesF16Xyz : kStreamBytesF16, b1 = xyz ? kStreamBytesF16HiXyz : kStreamBytesF16Hi;
+        std::vector<uint16_t> s3(b3 / 2), s1(b1 / 2);
+        std::vector<float> cst(kConstFloats);
+        wide::pack_weights_f16x3(blob, c->cfg.n_angles, s3.data(), cst.data());
+        wide::pack_weights_f16(blob, c->cfg.n_angles, s1.data(), cst.data());
+        if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, b3));
+        if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, b1));
+        if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        HIP_OK(hipMemcpy(n.stream_h, s3.data(), b3, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(n.stream_h1, s1.data(), b1, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(n.cst_h, cst.data(), kConstBytes, hipMemcpyHostToDevice));
+        const size_t nfw = nerf_blob_size(&c->cfg);
+        if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nfw);
+        n.loaded = true;
+        return 0;
+    }
     if (c->cfg.n_angles == 0) {
         // xyz-only network: all three arithmetic modes run on the fused kernels' xyz-only variants, each with its own
         // stream and constant layout
@@ -80,7 +170,7 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob) {
         HIP_OK(hipMemcpy(n.stream_h1, sx1.data(), kStreamBytesF16HiXyz, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.cst_h, cx.data(), kConstBytes, hipMemcpyHostToDevice));
         const size_t nf0 = nerf_blob_size(&c->cfg);
-        if (n.host_blob.data() != blob) n.host_blob.assign(blob, blob + nf0);
+        if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf0);
         n.loaded = true;
         return 0;
     }
@@ -104,7 +194,7 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob) {
     if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16Hi));
     HIP_OK(hipMemcpy(n.stream_h1, sth1.data(), kStreamBytesF16Hi, hipMemcpyHostToDevice));
     const size_t nf = nerf_blob_size(&c->cfg);
-    if (n.host_blob.data() != blob) n.host_blob.assign(blob, blob + nf);
+    if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf);
     n.loaded = true;
     return 0;
 }
@@ -117,10 +207,11 @@ int check_cfg(const nerf_config* cfg) {
     if (!cfg) return fail("nerf_config is NULL");
     if (cfg->n_angles != 2 && cfg->n_angles != 1 && cfg->n_angles != 0)
         return fail("n_angles_for_model should be 1 or 2.");   // message of src/UtilsCV.py:138 (0 = xyz-only network)
-    if (cfg->n_pos_enc_xyz != kLx || cfg->n_pos_enc_dir != kLd || cfg->hidden_dim != kHidden ||
-        cfg->last_hidden_dim != kLast)
-        return fail("fused kernel is specialised for Lx=%d Ld=%d hidden=%d last=%d (got %d %d %d %d)", kLx, kLd,
-                    kHidden, kLast, cfg->n_pos_enc_xyz, cfg->n_pos_enc_dir, cfg->hidden_dim, cfg->last_hidden_dim);
+    if (cfg->n_pos_enc_xyz < 1 || cfg->n_pos_enc_xyz > kLxWide || cfg->n_pos_enc_dir < 1 || cfg->n_pos_enc_dir > kLd ||
+        cfg->hidden_dim != kHidden || cfg->last_hidden_dim != kLast)
+        return fail("supported networks: n_pos_enc_dim_xyz 1..%d, n_pos_enc_view_dir 1..%d, hidden %d, last hidden %d "
+                    "(got %d %d %d %d)", kLxWide, kLd, kHidden, kLast, cfg->n_pos_enc_xyz, cfg->n_pos_enc_dir, cfg->hidden_dim,
+                    cfg->last_hidden_dim);
     if (cfg->precision != NERF_PRECISION_FP32 && cfg->precision != NERF_PRECISION_F16X3 &&
         cfg->precision != NERF_PRECISION_F16)
         return fail("unknown precision %d (NERF_PRECISION_FP32 = 0, NERF_PRECISION_F16X3 = 1, NERF_PRECISION_F16 = 2)",
@@ -157,7 +248,11 @@ int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const 
     // single-pass mode: two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the
     // one-tile kernel; the xyz-only network has the one-tile variant only
     static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
-    if (c->cfg.precision == NERF_PRECISION_F16 && c->cfg.n_angles != 0 && !one_tile) launch_mlp_f16_2t(a, c->num_cus, c->stream);
+    if (c->cfg.n_pos_enc_xyz > kLx) {
+        // wide-PE network: the 3-pass or the one-tile single-pass kernel of the wide-PE build (no fp32 kernel, check_cfg)
+        if (!f16) return fail("n_pos_enc_dim_xyz %d: no exact-fp32 kernel (precision f16x3 or f16)", c->cfg.n_pos_enc_xyz);
+        wide::launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
+    } else if (c->cfg.precision == NERF_PRECISION_F16 && c->cfg.n_angles != 0 && !one_tile) launch_mlp_f16_2t(a, c->num_cus, c->stream);
     else if (f16) launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
     else launch_mlp_fp32(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
     if (c->timing) HIP_OK(hipEventRecord(e1, c->stream));
@@ -276,18 +371,16 @@ const char* nerf_last_error(void) { return g_err.c_str(); }
 
 size_t nerf_blob_size(const nerf_config* cfg) {
     if (check_cfg(cfg)) return 0;
-    if (cfg->n_angles == 0)   // get_network_only_xyz, src/NeRF.py:248-288: 12 Dense layers
-        return 33 * 256 + 256 + 3 * (256 * 256 + 256) + 289 * 256 + 256 + 3 * (256 * 256 + 256) + (256 * 256 + 256) +
-               256 * 128 + 128 + 128 * 3 + 3 + 256 + 1;
-    const size_t kd = 256 + 8 * (size_t)(cfg->n_angles + 1);   // [hidden, dir_enc]: 280 or 272
-    return 33 * 256 + 256 + 3 * (256 * 256 + 256) + 289 * 256 + 256 + 3 * (256 * 256 + 256) + kd * 128 + 128 +
-           128 * 3 + 3 + kd + 1;
+    return blob_floats(cfg->n_pos_enc_xyz, cfg->n_pos_enc_dir, cfg->n_angles);
 }
 
 int nerf_ctx_create(const nerf_config* cfg, nerf_ctx** out) {
     if (!out) return fail("out is NULL");
     *out = nullptr;
     if (int r = check_cfg(cfg)) return r;
+    if (cfg->n_pos_enc_xyz > kLx && cfg->precision == NERF_PRECISION_FP32)
+        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the fp16-core kernels only: precision f16x3 or f16, not fp32",
+                    cfg->n_pos_enc_xyz, kLx);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)
@@ -313,6 +406,7 @@ int nerf_ctx_create(const nerf_config* cfg, nerf_ctx** out) {
     }
     mlp_fp32_set_attributes();
     mlp_f16x3_set_attributes();
+    wide::mlp_f16x3_set_attributes();
     mlp_bwd_f16x3_set_attributes();
     mlp_f16_2t_set_attributes();
     *out = c;
@@ -367,6 +461,9 @@ int nerf_ctx_set_precision(nerf_ctx* c, int precision) {
     if (!c) return fail("ctx is NULL");
     if (precision != NERF_PRECISION_FP32 && precision != NERF_PRECISION_F16X3 && precision != NERF_PRECISION_F16)
         return fail("unknown precision %d", precision);
+    if (c->cfg.n_pos_enc_xyz > kLx && precision == NERF_PRECISION_FP32)
+        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the fp16-core kernels only: precision f16x3 or f16, not fp32",
+                    c->cfg.n_pos_enc_xyz, kLx);
     HIP_OK(hipStreamSynchronize(c->stream));
     c->cfg.precision = precision;
     return 0;

@@ -15,6 +15,14 @@ constexpr int kHidden = 256;
 constexpr int kLast = 128;
 constexpr int kXyzDim = 3 + 6 * kLx;   // 33
 constexpr int kDirDim = 6 * kLd;       // 24
+// Fewer octaves (1 <= Lx <= kLx, 1 <= Ld <= kLd) run on the same kernels, the way n_angles 1 does: the octaves the network
+// does not have are still encoded on device, but their weight rows are zeros.  Every packer and gather table is written
+// for the (kLx, kLd) blob; an (Lx, Ld) blob is first spread into that layout (blob_expand_index, nerf_api.hip).
+// Floats of the weight blob of an (lx, ld, n_angles) network (Keras get_weights() order, src/NeRF.py:249-339)
+size_t blob_floats(int lx, int ld, int n_angles);
+// idx[i], i < blob_floats(layout_lx, kLd, n_angles): 1 + the index of the same weight in the (lx, ld) blob, 0 where the
+// (layout_lx, kLd) layout holds an octave row the (lx, ld) network does not have (a zero); layout_lx = kLx or kLxWide
+void blob_expand_index(int lx, int ld, int n_angles, int32_t* idx, int layout_lx = kLx);
 
 // ---- weight stream geometry (see DESIGN.md "weight stream") ----
 // A "quad" is the A operand of 4 consecutive MFMA k-steps for one 32-wide output tile:
@@ -101,6 +109,20 @@ void mlp_f16x3_set_attributes();
 void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
 void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
 
+// mlp_f16x3_wide.hip -- the same entry points for networks with n_pos_enc_dim_xyz 6..10: kernels that encode kLxWide octaves,
+// packers / gather tables for the (kLxWide, kLd) blob layout (same stream sizes).  No exact-fp32 render kernel exists for them.
+constexpr int kLxWide = 10;
+namespace wide {
+void launch_mlp_f16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
+void launch_mlp_f16x3_stash(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
+void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx, int32_t* const_idx);
+void mlp_f16x3_set_attributes();
+void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out);
+void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out);
+}  // namespace wide
+// the octaves of the blob layout the kernels of an (lx, .) network are packed for: kLx, or kLxWide for lx > kLx
+inline int pe_layout_lx(int lx) { return lx > kLx ? kLxWide : kLx; }
+
 // mlp_f16_2t.hip -- single-pass fp16 render kernel with two 32-sample tiles per wave (same hi-only stream / constants)
 void launch_mlp_f16_2t(const MlpArgs& a, int num_cus, hipStream_t stream);
 void mlp_f16_2t_set_attributes();
@@ -141,7 +163,9 @@ struct MlpBwdArgs {
 void launch_mlp_bwd_f16x3(const MlpBwdArgs& a, bool dx, bool single_pass, int num_cus, hipStream_t stream,
                           bool xyz_only = false);
 void mlp_bwd_f16x3_set_attributes();
-void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 */);
+// xyz_dim: rows of the encoding block of the blob layout the table indexes (kXyzDim, or 3 + 6 kLxWide for the wide-PE
+// layout: the chain's two encoding tiles hold up to 64 rows)
+void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 */, int xyz_dim = kXyzDim);
 void launch_repack_bwd(const float* blob, const int32_t* idx, void* stream, hipStream_t s);
 
 // aux_kernels.hip

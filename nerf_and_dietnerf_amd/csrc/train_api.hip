@@ -118,16 +118,17 @@ struct TrainState {
 namespace {
 
 int layer_table(const nerf_config& cfg, TLayer L[12]) {
-    const int kd = 8 * (cfg.n_angles + 1);
-    // {K_real, N_real, Kp, Np, rowmap}
+    const int kd = 2 * cfg.n_pos_enc_dir * (cfg.n_angles + 1);   // direction encoding: 24 at (Ld 4, n_angles 2)
+    const int xd = 3 + 6 * cfg.n_pos_enc_xyz;                    // xyz encoding: 33 at Lx 5
+    // {K_real, N_real, Kp, Np, rowmap}; rowmap = xd on layer 4 (train_kernels.h, ReduceArgs::rowmap)
     const int with_dirs[11][5] = {
-        {33, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {289, 256, kLdC4, 256, 1},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
+        {xd, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
+        {256 + xd, 256, kLdC4, 256, xd},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
         {256 + kd, 128, kLdC8, 128, 0}, {128, 3, 128, 32, 0}, {256 + kd, 1, kLdC8, 32, 0}};
     // get_network_only_xyz (src/NeRF.py:248-288): ... h8 -> dense 256 -> dense 128 -> rgb; sigma from h8
     const int xyz_only[12][5] = {
-        {33, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {289, 256, kLdC4, 256, 1},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
+        {xd, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
+        {256 + xd, 256, kLdC4, 256, xd},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
         {256, 256, 256, 256, 0}, {256, 128, 256, 128, 0}, {128, 3, 128, 32, 0}, {256, 1, 256, 32, 0}};
     const int n = cfg.n_angles == 0 ? 12 : 11;
     size_t off = 0;
@@ -153,6 +154,23 @@ void free_pass(TPass& p) {
 void free_slot(RenderSlot& s) {
     for (TPass& p : s.pass) free_pass(p);
     for (DevBuf* b : {&s.o, &s.d, &s.u_c, &s.u_f, &s.z_new}) free_buf(*b);
+}
+
+// The gather tables index the (kLx, kLd) blob (nerf_kernels.h::blob_expand_index); a network with fewer octaves keeps its own
+// (shorter) blob on the device: its tables are re-aimed at it, and the slots of the octave rows it does not have become padding.
+// f16: entries are 2 * (src + 1) + is_lo (the fp16 streams); else src + 1
+// (the wide-PE tables index the (kLxWide, kLd) blob)
+void aim_gather(const nerf_config& cfg, int32_t* idx, size_t n, bool f16) {
+    const int L = pe_layout_lx(cfg.n_pos_enc_xyz);
+    if (cfg.n_pos_enc_xyz == L && cfg.n_pos_enc_dir == kLd) return;
+    std::vector<int32_t> map(blob_floats(L, kLd, cfg.n_angles));
+    blob_expand_index(cfg.n_pos_enc_xyz, cfg.n_pos_enc_dir, cfg.n_angles, map.data(), L);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t t = idx[i];
+        if (!t) continue;
+        const int32_t m = map[(f16 ? t >> 1 : t) - 1];
+        idx[i] = m == 0 ? 0 : f16 ? 2 * m + (t & 1) : m;
+    }
 }
 
 int relayout_net(nerf_ctx* c, TNet& n) {
@@ -191,7 +209,10 @@ int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
     if (!t->fused_forward) return 0;
     if (!t->sidx) {
         std::vector<int32_t> si(f16_stream_bytes(c->cfg.n_angles, t->mixed) / 2), ci(kConstFloats);
-        build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
+        if (c->cfg.n_pos_enc_xyz > kLx) wide::build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
+        else build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
+        aim_gather(c->cfg, si.data(), si.size(), true);
+        aim_gather(c->cfg, ci.data(), ci.size(), false);
         HIP_OK(hipMalloc((void**)&t->sidx, si.size() * sizeof(int32_t)));
         HIP_OK(hipMalloc((void**)&t->cidx, ci.size() * sizeof(int32_t)));
         HIP_OK(hipMemcpy(t->sidx, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -205,7 +226,8 @@ int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
         int32_t*& bi = t->bidx[n.bdx ? 1 : 0];
         if (!bi) {
             std::vector<int32_t> idx(kBwdStreamBytes / 2);
-            build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data());
+            build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data(), 3 + 6 * pe_layout_lx(c->cfg.n_pos_enc_xyz));
+            aim_gather(c->cfg, idx.data(), idx.size(), true);
             HIP_OK(hipMalloc((void**)&bi, idx.size() * sizeof(int32_t)));
             HIP_OK(hipMemcpy(bi, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
@@ -316,8 +338,8 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     float *raw = (float*)p.raw.p, *z = (float*)p.z.p;
-    launch_train_encode(o, dirs, z, 0, d.M, d.S, d.Mp, c->cfg.n_angles, 0, (float*)p.C4.p, (float*)p.C8.p, c->stream,
-                        t->mixed, t->frag);
+    launch_train_encode(o, dirs, z, 0, d.M, d.S, d.Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, 0,
+                        (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed, t->frag);
     if (t->frag && !n.fstream) return fail("internal: fused training forward without its weight stream");
     if (t->fused_forward && n.fstream) {
         // the render path's fused PE + MLP kernel (3-pass split fp16, fp32-class results) with every activation also
@@ -338,7 +360,8 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
 #ifdef NERF_DIAG_STASH_WRAP   // diagnostic BUILD only (make EXTRA=-DNERF_DIAG_STASH_WRAP): timing without HBM stores, wrong results
         a.diag_wrap = d.Mp >= 8192;
 #endif
-        launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
+        if (c->cfg.n_pos_enc_xyz > kLx) wide::launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
+        else launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
     } else {
         forward_layers(c, n, p, d.Mp, raw);
     }
@@ -581,7 +604,10 @@ int backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, cons
         if (int r = wgrad_flush(c, t, wq, Mp, t->overlap && which == 1 && !t->acc_grads)) return r;
         if (dx) {
             if (!n.bdx) return fail("internal: the sampler term needs the backward stream with encoding tiles");
-            launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, d_z, c->stream, true);
+            // the chain's encoding tiles are laid out for kLx (wide-PE: kLxWide) octaves; the ones the network lacks carry
+            // zero gradient
+            launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
+                          d_z, c->stream, true);
         }
         HIP_OK(hipGetLastError());
         return 0;
@@ -622,7 +648,7 @@ int backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, cons
     wgrad(c, t, n, 0, C4 + 256, kLdC4, Gb, 256, 256, 0, Mp, GM(8));
     if (dx) {
         dgrad_xyz(c, Gb, n.L[0].W, dA0, Mp, true);
-        launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, d_z, c->stream);
+        launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, d_z, c->stream);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -1100,14 +1126,27 @@ static int ensure_render_tables(nerf_ctx* c, TrainState* t) {
     };
     std::vector<int32_t> h(f16_stream_bytes(na, false) / 2), h1(f16_stream_bytes(na, true) / 2), ch(kConstFloats),
         ch1(kConstFloats);
-    build_f16x3_gather(na, false, h.data(), ch.data());
-    build_f16x3_gather(na, true, h1.data(), ch1.data());
+    const bool wide_pe = c->cfg.n_pos_enc_xyz > kLx;
+    (wide_pe ? wide::build_f16x3_gather : build_f16x3_gather)(na, false, h.data(), ch.data());
+    (wide_pe ? wide::build_f16x3_gather : build_f16x3_gather)(na, true, h1.data(), ch1.data());
     if (ch != ch1) return fail("internal: the two fp16 streams disagree about their constants");
+    aim_gather(c->cfg, h.data(), h.size(), true);
+    aim_gather(c->cfg, h1.data(), h1.size(), true);
+    aim_gather(c->cfg, ch.data(), ch.size(), false);
+    if (wide_pe) {                           // no exact-fp32 render kernel (and no fp32 stream) for a wide-PE network
+        if (int r = up(h1, &t->rt_h1)) return r;
+        if (int r = up(ch, &t->rt_ch)) return r;
+        return up(h, &t->rt_h);
+    }
     // fp32 stream: pack a blob whose entry i holds i + 1 (exact in fp32: the blob has 5e5 entries) -- what lands in a slot
-    // is the 1-based index of the weight that belongs there, 0 where the packer pads
+    // is the 1-based index of the weight that belongs there, 0 where the packer pads.  The packer takes the (kLx, kLd)
+    // layout: its entry i holds the 1-based index of the trained blob's weight there, 0 for an octave row it does not have
     const size_t nf = (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4;
-    std::vector<float> idx(t->nblob), sf(nf), cf(kConstFloats);
-    for (size_t i = 0; i < t->nblob; ++i) idx[i] = (float)(i + 1);
+    std::vector<int32_t> wide(blob_floats(kLx, kLd, na));
+    for (size_t i = 0; i < wide.size(); ++i) wide[i] = (int32_t)(i + 1);
+    aim_gather(c->cfg, wide.data(), wide.size(), false);
+    std::vector<float> idx(wide.size()), sf(nf), cf(kConstFloats);
+    for (size_t i = 0; i < wide.size(); ++i) idx[i] = (float)wide[i];
     pack_weights_fp32(idx.data(), na, sf.data(), cf.data());
     std::vector<int32_t> f(nf), cfi(kConstFloats);
     for (size_t i = 0; i < nf; ++i) f[i] = (int32_t)sf[i];
@@ -1116,7 +1155,7 @@ static int ensure_render_tables(nerf_ctx* c, TrainState* t) {
     if (int r = up(ch, &t->rt_ch)) return r;
     if (int r = up(f, &t->rt_f)) return r;
     if (int r = up(cfi, &t->rt_cf)) return r;
-    return up(h, &t->rt_h);                  // last: rt_h != nullptr means all five exist
+    return up(h, &t->rt_h);                  // last: rt_h != nullptr means all five (wide-PE: three) exist
 }
 
 // The render path's view of a network that is being trained.  After optimizer steps its three operand streams are
@@ -1133,8 +1172,10 @@ int train_flush_weights(nerf_ctx* c, int which, bool to_host) {
         const int na = c->cfg.n_angles;
         launch_repack_f16x3(n.blob, t->rt_h, nw.stream_h, t->rt_ch, nw.cst_h, f16_stream_bytes(na, false), c->stream);
         launch_repack_f16x3(n.blob, t->rt_h1, nw.stream_h1, t->rt_ch, nw.cst_h, f16_stream_bytes(na, true), c->stream);
-        launch_gather_blob(n.blob, t->rt_f, nw.stream, (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4, c->stream);
-        launch_gather_blob(n.blob, t->rt_cf, nw.cst, kConstFloats, c->stream);
+        if (t->rt_f) {
+            launch_gather_blob(n.blob, t->rt_f, nw.stream, (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4, c->stream);
+            launch_gather_blob(n.blob, t->rt_cf, nw.cst, kConstFloats, c->stream);
+        }
         HIP_OK(hipGetLastError());
         n.render_dirty = false;
         n.host_stale = true;

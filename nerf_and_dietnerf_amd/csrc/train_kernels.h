@@ -8,8 +8,8 @@
 namespace nerf {
 
 // padded training layout of the activations (floats per row)
-constexpr int kLdC4 = 320;    // [h4 (256) | xyz_enc (33) | 0-pad to 64]   input of layer 4; cols 256.. = input of layer 0
-constexpr int kLdC8 = 288;    // [h8 (256) | dir_enc (24 or 16) | 0-pad to 32]   input of layers 8 and 10
+constexpr int kLdC4 = 320;    // [h4 (256) | xyz_enc (3 + 6 Lx: 33) | 0-pad to 64]   input of layer 4; cols 256.. = input of layer 0
+constexpr int kLdC8 = 288;    // [h8 (256) | dir_enc (2 Ld (n_angles + 1): 24 or 16) | 0-pad to 32]   input of layers 8 and 10
 constexpr int kXyzPad = 64;
 constexpr int kDirPad = 32;
 constexpr int kTrainSplits = 128;   // row slabs of the weight-gradient reduction
@@ -83,7 +83,7 @@ struct ReduceArgs {
     const float* partial; int Kp; int Nw; int splits;
     float* grad_w; float* grad_b;       // destinations inside the gradient blob
     int K_real, N_real; int n_src_off;  // gradient column n comes from partial column n_src_off + n
-    int rowmap;                         // 0: identity; 1: layer 4 (blob rows [xyz(33); hidden(256)] <- training rows [hidden; xyz])
+    int rowmap;                         // 0: identity; > 0: layer 4 (blob rows [xyz(rowmap); hidden(256)] <- training rows [hidden; xyz])
     int accumulate;                     // 1: add to the gradient blob instead of overwriting it
 };
 void launch_reduce_grad(const ReduceArgs& a, hipStream_t s);
@@ -100,8 +100,9 @@ struct RelayoutArgs {
 void launch_relayout(const RelayoutArgs& a, hipStream_t s);
 
 // rows [row0, row0 + M) of the sample grid (rays x S, or xyz/view rows in xyz_mode) -> local rows 0..M of C4/C8
+// lx, ld: the network's octaves (1..10, 1..4); the columns follow the reference's layout for them, zeros beyond
 void launch_train_encode(const float* o, const float* d, const float* z, long long row0, long long M, int S,
-                         long long Mp, int n_angles, int xyz_mode, float* C4, float* C8, hipStream_t s,
+                         long long Mp, int n_angles, int lx, int ld, int xyz_mode, float* C4, float* C8, hipStream_t s,
                          bool half_out = false,    // half_out: C4 / C8 are fp16 rows of the same element pitch
                          bool frag = false);       // frag: C4 / C8 are fragment-major
 // Optimizer / loss-scale state kept ON THE DEVICE: the verdict of a step's gradients (mixed_float16 policy: Keras 2.7
@@ -134,8 +135,9 @@ void launch_composite_bwd(const float* raw, const float* z, const float* T, long
                           const float* d_w_ext, float* Graw, float* d_z, hipStream_t s);
 void launch_head_bwd(const float* Graw, const float* W9 /*[128][Np9] row-major, Np9 = 32*/, const float* H9,
                      long long M, float alpha, float* G9, unsigned* gmax, hipStream_t s);
+// lx: octaves of the encoding-gradient rows' layout ([x, sin0, cos0, ...] per component, 1 + 2 lx columns each; 1..10)
 void launch_pe_bwd(const float* dA0, const float* dA0b /* added to dA0, or null */, const float* o, const float* d,
-                   const float* z, long long N, int S, float* d_z, hipStream_t s,
+                   const float* z, long long N, int S, int lx, float* d_z, hipStream_t s,
                    bool frag = false);     // frag: dA0 / dA0b are fragment-major (the fused backward chain's dx buffers)
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
                          hipStream_t s);

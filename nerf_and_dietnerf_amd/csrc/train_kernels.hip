@@ -1503,8 +1503,8 @@ void launch_head_wgrad(const GemmAtb& g, hipStream_t s) {
 // reduce_grad / relayout / adam: element-wise over one layer
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int train_row_of_blob_row(int kb, int rowmap) {
-    // layer 4: the blob holds [xyz_enc (33) ; hidden (256)] rows, the training layout [hidden ; xyz_enc]
-    if (rowmap == 1) return kb < 33 ? 256 + kb : kb - 33;
+    // layer 4: the blob holds [xyz_enc (rowmap = 3 + 6 Lx) ; hidden (256)] rows, the training layout [hidden ; xyz_enc]
+    if (rowmap > 0) return kb < rowmap ? 256 + kb : kb - rowmap;
     return kb;
 }
 
@@ -1610,8 +1610,8 @@ __global__ void relayout_kernel(const RelayoutArgs a) {
     const int kt = e / a.Np, n = e % a.Np;
     // inverse of train_row_of_blob_row
     int kb = kt;
-    if (a.rowmap == 1) kb = kt < 256 ? kt + 33 : kt - 256;
-    const bool valid = n < a.N_real && kb >= 0 && kb < a.K_real && (a.rowmap != 1 || kt < 256 + 33);
+    if (a.rowmap > 0) kb = kt < 256 ? kt + a.rowmap : kt - 256;
+    const bool valid = n < a.N_real && kb >= 0 && kb < a.K_real && (a.rowmap <= 0 || kt < 256 + a.rowmap);
     const float v = valid ? a.w[(size_t)kb * a.N_real + n] : 0.f;
     a.W[(size_t)kt * a.Np + n] = v;
     a.WT[(size_t)n * a.Kp + kt] = v;
@@ -1689,7 +1689,8 @@ void launch_opt_tick(OptState* st, float beta1, float beta2, hipStream_t s) {
 //   sample_along_rays  src/UtilsCV.py:584-599, get_view_directions :124-143, positional encodings
 //   src/UtilsNeuralRadianceField.py:52-85.  Rows >= N*S (padding to 128) get zeros.
 // ------------------------------------------------------------------------------------------------
-template <typename T>      // T = float, or _Float16 for the mixed_float16 policy's half-width activation buffers
+// T = float, or _Float16 for the mixed_float16 policy's half-width activation buffers; LX, LD: the network's octaves
+template <typename T, int LX, int LD>
 __global__ void train_encode_kernel(const float* __restrict__ o, const float* __restrict__ d,
                                     const float* __restrict__ z, long long row0, long long M, int S, long long Mp,
                                     int n_angles, int xyz_mode, T* __restrict__ C4, T* __restrict__ C8, int frag) {
@@ -1721,14 +1722,15 @@ __global__ void train_encode_kernel(const float* __restrict__ o, const float* __
             p[2] = __fadd_rn(oo.z, __fmul_rn(dd.z, zz));
             v3[0] = dd.x; v3[1] = dd.y; v3[2] = dd.z;
         }
+        constexpr int XC = 1 + 2 * LX;       // columns per component: [x, sin0, cos0, sin1, cos1, ...]
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            ev[c * 11] = p[c];
+            ev[c * XC] = p[c];
 #pragma unroll
-            for (int k = 0; k < 5; ++k) {
+            for (int k = 0; k < LX; ++k) {
                 const float th = __fmul_rn(p[c], kPi * (float)(1 << k));
-                ev[c * 11 + 1 + 2 * k] = sin_shifted(th, 0);
-                ev[c * 11 + 2 + 2 * k] = sin_shifted(th, 1);
+                ev[c * XC + 1 + 2 * k] = sin_shifted(th, 0);
+                ev[c * XC + 2 + 2 * k] = sin_shifted(th, 1);
             }
         }
         const int ncomp = n_angles > 0 ? n_angles + 1 : 0;     // the xyz-only network has no direction input
@@ -1736,11 +1738,11 @@ __global__ void train_encode_kernel(const float* __restrict__ o, const float* __
         for (int c = 0; c < 3; ++c) {
             const float v = n_angles == 2 ? v3[c] : (c == 0 ? v3[0] : v3[2]);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < LD; ++k) {
                 const float th = __fmul_rn(v, kPi * (float)(1 << k));
                 const float sn = sin_shifted(th, 0), cs = sin_shifted(th, 1);
-                dv[c * 8 + 2 * k] = c < ncomp ? sn : 0.f;
-                dv[c * 8 + 2 * k + 1] = c < ncomp ? cs : 0.f;
+                dv[c * 2 * LD + 2 * k] = c < ncomp ? sn : 0.f;
+                dv[c * 2 * LD + 2 * k + 1] = c < ncomp ? cs : 0.f;
             }
         }
     }
@@ -1759,17 +1761,48 @@ __global__ void train_encode_kernel(const float* __restrict__ o, const float* __
     for (int i = 0; i < kDirPad; i += 4) put4(C8, kLdC8, i, dv + i);
 }
 
-void launch_train_encode(const float* o, const float* d, const float* z, long long row0, long long M, int S,
-                         long long Mp, int n_angles, int xyz_mode, float* C4, float* C8, hipStream_t s, bool half_out,
-                         bool frag) {
-    if (Mp <= 0) return;
+template <int LX, int LD>
+static void launch_train_encode_t(const float* o, const float* d, const float* z, long long row0, long long M, int S,
+                                  long long Mp, int n_angles, int xyz_mode, float* C4, float* C8, hipStream_t s,
+                                  bool half_out, bool frag) {
     const dim3 grid((unsigned)((Mp + 255) / 256)), block(256);
     if (half_out)
-        hipLaunchKernelGGL(train_encode_kernel<_Float16>, grid, block, 0, s, o, d, z, row0, M, S, Mp, n_angles, xyz_mode,
-                           reinterpret_cast<_Float16*>(C4), reinterpret_cast<_Float16*>(C8), frag ? 1 : 0);
+        hipLaunchKernelGGL((train_encode_kernel<_Float16, LX, LD>), grid, block, 0, s, o, d, z, row0, M, S, Mp, n_angles,
+                           xyz_mode, reinterpret_cast<_Float16*>(C4), reinterpret_cast<_Float16*>(C8), frag ? 1 : 0);
     else
-        hipLaunchKernelGGL(train_encode_kernel<float>, grid, block, 0, s, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8,
-                           frag ? 1 : 0);
+        hipLaunchKernelGGL((train_encode_kernel<float, LX, LD>), grid, block, 0, s, o, d, z, row0, M, S, Mp, n_angles,
+                           xyz_mode, C4, C8, frag ? 1 : 0);
+}
+
+template <int LX>
+static void launch_train_encode_lx(int ld, const float* o, const float* d, const float* z, long long row0, long long M,
+                                   int S, long long Mp, int n_angles, int xyz_mode, float* C4, float* C8, hipStream_t s,
+                                   bool half_out, bool frag) {
+    switch (ld) {
+        case 1: return launch_train_encode_t<LX, 1>(o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 2: return launch_train_encode_t<LX, 2>(o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 3: return launch_train_encode_t<LX, 3>(o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        default: return launch_train_encode_t<LX, 4>(o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+    }
+}
+
+// lx 1..10, ld 1..4 (nerf_api.hip::check_cfg)
+void launch_train_encode(const float* o, const float* d, const float* z, long long row0, long long M, int S,
+                         long long Mp, int n_angles, int lx, int ld, int xyz_mode, float* C4, float* C8, hipStream_t s,
+                         bool half_out, bool frag) {
+    if (Mp <= 0) return;
+    switch (lx) {
+        case 1: return launch_train_encode_lx<1>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 2: return launch_train_encode_lx<2>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 3: return launch_train_encode_lx<3>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 4: return launch_train_encode_lx<4>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 5: return launch_train_encode_lx<5>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 6: return launch_train_encode_lx<6>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 7: return launch_train_encode_lx<7>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 8: return launch_train_encode_lx<8>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        case 9: return launch_train_encode_lx<9>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+        default: return launch_train_encode_lx<10>(ld, o, d, z, row0, M, S, Mp, n_angles, xyz_mode, C4, C8, s, half_out, frag);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2000,6 +2033,7 @@ void launch_head_bwd(const float* Graw, const float* W9, const float* H9, long l
 // ------------------------------------------------------------------------------------------------
 // positional-encoding backward + sample_along_rays backward: d_z[m] += sum_c dL/dp_c * dir_c
 // ------------------------------------------------------------------------------------------------
+template <int LX>      // octaves of the gradient rows' layout
 __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __restrict__ dA0b /* second part to add, or null */,
                               const float* __restrict__ o, const float* __restrict__ d,
                               const float* __restrict__ z, long long M, int S, float* __restrict__ d_z, int frag) {
@@ -2015,9 +2049,10 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
     // the encoding gradient may come in two parts (fused backward: through layer 4 and through layer 0)
     // frag: the (Mp, 64) rows are fragment-major (frag_layout.h::frag_index; written by the fused backward chain):
     // neighbouring threads read neighbouring 16-byte slots
-    float g[36];
+    constexpr int Q = (3 * (1 + 2 * LX) + 3) / 4;    // float4s covering the 3 + 6 LX encoding columns (rows are 64 floats)
+    float g[4 * Q];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {                  // 33 floats, read as 9 float4 (rows are 64 floats: no overrun)
+    for (int q = 0; q < Q; ++q) {                  // 33 floats (LX 5) read as 9 float4, 63 (LX 10) as 16: no overrun
         const long long e = frag ? frag_index(m, 4 * q, kXyzPad) : m * kXyzPad + 4 * q;
         float4 v = *reinterpret_cast<const float4*>(dA0 + e);
         if (dA0b) { const float4 w = *reinterpret_cast<const float4*>(dA0b + e); v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
@@ -2026,13 +2061,14 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
     float acc = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float dp = g[c * 11];
+        constexpr int XC = 1 + 2 * LX;
+        float dp = g[c * XC];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
+        for (int k = 0; k < LX; ++k) {
             const float f = kPi * (float)(1 << k);
             const float th = __fmul_rn(p[c], f);
             const float sn = sin_shifted(th, 0), cs = sin_shifted(th, 1);
-            dp += (cs * g[c * 11 + 1 + 2 * k] - sn * g[c * 11 + 2 + 2 * k]) * f;
+            dp += (cs * g[c * XC + 1 + 2 * k] - sn * g[c * XC + 2 + 2 * k]) * f;
         }
         acc += dp * dv[c];
     }
@@ -2066,11 +2102,23 @@ void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm
 }
 
 void launch_pe_bwd(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N, int S,
-                   float* d_z, hipStream_t s, bool frag) {
+                   int lx, float* d_z, hipStream_t s, bool frag) {
     const long long M = N * S;
     if (M <= 0) return;
-    hipLaunchKernelGGL(pe_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, dA0, dA0b, o, d, z, M, S, d_z,
-                       frag ? 1 : 0);
+    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+    const int fr = frag ? 1 : 0;
+    switch (lx) {
+        case 1: hipLaunchKernelGGL(pe_bwd_kernel<1>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 2: hipLaunchKernelGGL(pe_bwd_kernel<2>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 3: hipLaunchKernelGGL(pe_bwd_kernel<3>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 4: hipLaunchKernelGGL(pe_bwd_kernel<4>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 5: hipLaunchKernelGGL(pe_bwd_kernel<5>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 6: hipLaunchKernelGGL(pe_bwd_kernel<6>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 7: hipLaunchKernelGGL(pe_bwd_kernel<7>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 8: hipLaunchKernelGGL(pe_bwd_kernel<8>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        case 9: hipLaunchKernelGGL(pe_bwd_kernel<9>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+        default: hipLaunchKernelGGL(pe_bwd_kernel<10>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -861,6 +861,11 @@ def render_rays(model: NetHandle, rays_orig, rays_dirs, z_values, n_pos_enc_for_
 
 def model_predict(model: NetHandle, n_enc_phi_theta: int, n_pos_enc_for_xyz: int, xyz, view_dirs=None):
     """src/UtilsNeuralRadianceField.py:214-234 -> (M,4) raw (R,G,B,Sigma)."""
+    cfg = model.ctx.cfg
+    # the encodings are the network's (its layer shapes follow them): counts that differ from it are a caller error
+    # (the xyz-only network has no direction input: n_enc_phi_theta is not used by it, src/UtilsNeuralRadianceField.py:229-234)
+    if n_pos_enc_for_xyz != cfg.n_pos_enc_xyz or (cfg.n_angles != 0 and n_enc_phi_theta != cfg.n_pos_enc_dir):
+        raise ValueError("encoding arguments do not match the network this model handle was built with")
     if view_dirs is None and model.ctx.cfg.n_angles != 0:
         raise ValueError("view_dirs is None but this model takes view directions")
     return model.ctx.model_predict(model.which, xyz, view_dirs)
