@@ -29,7 +29,8 @@ __device__ __forceinline__ float sin_shifted(float th, int h) {
 // out[k] = sin(2^k theta + h pi/2), k < L, for the SINGLE-PASS FP16 kernels only: one full evaluation of sin and cos at
 // k = 0 (same reduction and polynomials as sin_shifted) and the angle-doubling recurrence above it,
 // s' = 2 s c, c' = 1 - 2 s^2 -- 3 operations a level instead of ~22.  The error doubles per level (~2e-6 at k = 4),
-// two orders below the fp16 rounding the encodings get in those kernels; the fp32-class modes keep sin_shifted.
+// two orders below the fp16 rounding the encodings get in those kernels; at k = 9 (the wide-PE build) it reaches ~1e-3,
+// about two fp16 ulps (oracle.positional_encoding_ladder restates it); the fp32-class modes keep sin_shifted.
 template <int L>
 __device__ __forceinline__ void sin_ladder_fp16_modes(float th, int h, float* out) {
     const float n = rintf(th * 0.6366197466850281f);

@@ -273,6 +273,51 @@ def positional_encoding_for_xyz(xyz: np.ndarray, n_enc: int) -> np.ndarray:
     return np.concatenate([xyz[..., None], st], axis=-1).reshape(xyz.shape[0], -1).astype(F32)
 
 
+def _fmaf(a, b, c) -> np.ndarray:
+    """fmaf on fp32 values: the product of two fp32 values is exact in fp64, so one fp64 sum and a cast to fp32 (its
+    double rounding is off by an fp32 ulp only at exact fp64 ties)."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F32)
+
+
+def _sin_ladder_fp16_modes(th: np.ndarray, n_enc: int) -> np.ndarray:
+    """csrc/nerf_device.h::sin_ladder_fp16_modes in fp32: sin and cos of th by the Cody-Waite reduction and polynomials of
+    sin_shifted, then the angle-doubling recurrence s' = 2 s c, c' = fmaf(-2 s, s, 1) for the higher octaves -- the
+    single-pass fp16 kernels' encodings (mlp_f16_2t.hip, mlp_f16x3.hip FAST).  (..., n_enc, 2) [sin, cos]."""
+    th = np.asarray(th, F32)
+    n = np.rint(th * F32(0.6366197466850281))
+    r = _fmaf(-n, F32(1.5707963705062866), th)
+    r = _fmaf(-n, F32(-4.371138828673793e-08), r)
+    r = _fmaf(-n, F32(-1.7151245100058819e-15), r)
+    q = n.astype(np.int64)
+    r2 = r * r
+    sp = _fmaf(F32(-1.9515295891e-4), r2, F32(8.3321608736e-3))
+    sp = _fmaf(sp, r2, F32(-1.6666654611e-1))
+    sp = _fmaf(sp * r2, r, r)
+    cp = _fmaf(F32(2.443315711809948e-5), r2, F32(-1.388731625493765e-3))
+    cp = _fmaf(cp, r2, F32(4.166664568298827e-2))
+    cp = _fmaf(cp * r2, r2, _fmaf(F32(-0.5), r2, F32(1.0)))
+    odd, neg = (q & 1) == 1, (q & 2) == 2
+    s = np.where(odd, cp, sp)
+    c = np.where(odd, -sp, cp)
+    s, c = np.where(neg, -s, s), np.where(neg, -c, c)
+    out = [np.stack([s, c], axis=-1)]
+    for _ in range(1, n_enc):
+        t = s + s
+        s, c = t * c, _fmaf(-t, s, F32(1.0))
+        out.append(np.stack([s, c], axis=-1))
+    return np.stack(out, axis=-2).astype(F32)
+
+
+def positional_encoding_ladder(x: np.ndarray, n_enc: int, passthrough: bool) -> np.ndarray:
+    """positional_encoding_for_xyz (passthrough=True) / _for_views (False) as the single-pass fp16 kernels evaluate them
+    (_sin_ladder_fp16_modes of theta = fp32(pi x)): same layout, differences of ~2^k fp32 ulps at octave k."""
+    x = np.asarray(x, F32)
+    st = _sin_ladder_fp16_modes(x * F32(math.pi), n_enc).reshape(x.shape[0], x.shape[1], 2 * n_enc)
+    if passthrough:
+        st = np.concatenate([x[..., None], st], axis=-1)
+    return st.reshape(x.shape[0], -1).astype(F32)
+
+
 def leaky_relu(x: np.ndarray, alpha: float) -> np.ndarray:
     return np.maximum(x, F32(alpha) * x)
 
@@ -314,48 +359,76 @@ def mlp_forward(layers: Sequence[Tuple[np.ndarray, np.ndarray]], xyz_enc: np.nda
     return np.concatenate([rgb, sigma], axis=-1).astype(F32)  # :339
 
 
+def round_fp16(a) -> np.ndarray:
+    """Round to fp16 (RNE, one rounding from the input's precision) and hold the value as fp32."""
+    return np.asarray(a).astype(np.float16).astype(F32)
+
+
 def mlp_forward_fp16(layers: Sequence[Tuple[np.ndarray, np.ndarray]], xyz_enc: np.ndarray,
-                     dir_enc: np.ndarray, alpha: float = 0.05, packed_epilogue: bool = False) -> np.ndarray:
+                     dir_enc: np.ndarray, alpha: float = 0.05, packed_epilogue=False, rnd=round_fp16) -> np.ndarray:
     """Emulation of the library's NERF_PRECISION_F16 mode (the numerics class of the reference's production
     mixed_float16 policy, src/ExecutionRun.py:220-221; not TensorFlow's exact op order): operands of every
     256-wide contraction -- weights and layer inputs -- rounded to fp16 (RNE), products accumulated in fp32; the
     128 -> 3 rgb head in fp32 on the unrounded last hidden layer.
 
-    packed_epilogue = False (rounds 2-3; kept as the "visibly further away" emulation of the parity tests): fp32 bias as the
-    accumulator's start value, LeakyReLU in fp32, activations rounded to fp16 between layers.
-    packed_epilogue = True (the two-tile render kernel, csrc/mlp_f16_2t.hip, round 4): layers 0..7 round where Keras'
-    mixed_float16 Dense rounds -- the fp32 sum is cast to fp16 FIRST (v_cvt_pk_f16_f32), then the fp16 bias is added
-    (v_pk_add_f16: one rounding), then LeakyReLU in fp16 with alpha rounded to fp16 (v_pk_mul_f16, v_pk_max_f16);
-    layer 8 (which feeds the fp32 head) and the sigma head keep the fp32 epilogue.
-    packed_epilogue = "c_in" (the trainer's stash forward and the one-tile render kernel, csrc/mlp_f16x3.hip FAST, since
-    round 4): the fp32 bias is the accumulator's start value, the fp32 sum (bias included) is cast to fp16, then
-    LeakyReLU in fp16 as above (v_pk_mul_f16, v_pk_max_f16)."""
-    q = lambda a: np.asarray(a, F32).astype(np.float16).astype(F32)
+    Which kernel each packed_epilogue value describes (dispatch: csrc/nerf_api.hip, mlp_launch):
+      True    -- mlp_f16_2t_kernel (csrc/mlp_f16_2t.hip): Lx <= 5 with view directions (n_angles 2 or 1), the default.
+      "c_in"  -- mlp_f16_kernel / mlp_f16_xyz_kernel (csrc/mlp_f16x3.hip, FAST): the xyz-only network (n_angles 0) at
+                 Lx <= 5, the view-direction networks under NERF_F16_TILES=1, every network of the wide-PE build
+                 (csrc/mlp_f16x3_wide.hip, Lx 6..10), and the mixed_float16 trainer's stash forward (FAST + STASH).
+      False   -- no kernel since round 4: kept as the "visibly further away" emulation of the parity tests.
+
+    packed_epilogue = False: fp32 bias as the accumulator's start value, LeakyReLU in fp32, activations rounded to fp16
+    between layers.
+    packed_epilogue = True: hidden layers round where Keras' mixed_float16 Dense rounds -- the fp32 sum is cast to fp16
+    FIRST (v_cvt_pk_f16_f32), then the fp16 bias is added (v_pk_add_f16: one rounding), then LeakyReLU in fp16 with alpha
+    rounded to fp16 (v_pk_mul_f16, v_pk_max_f16).
+    packed_epilogue = "c_in": the fp32 bias is the accumulator's start value (load_bias), the fp32 sum (bias included) is
+    cast to fp16, then LeakyReLU in fp16 as above (mlp_f16x3.hip layer_body_h: act_pair / store_pair_p).
+    In every epilogue the layer that feeds the fp32 VALU head keeps an fp32 epilogue (mlp_f16x3.hip: BODY_LAST /
+    BODY_LAST0 take act() into xc[]), and sigma is the raw fp32 accumulator of an MFMA tile (bias as C-in).
+
+    The xyz-only network (12 layers, mlp_forward_xyz_only's wiring; mlp_f16_body<FAST, !STASH, XYZ>, mlp_f16x3.hip
+    :537-548): layers 0..7 as above; layer 8 (256 -> 256, BODY_HIDSIG) takes the fp16 output of layer 7 and rounds like
+    the hidden layers; its leading 9th tile is the sigma head, read from that same fp16 input (sigma_raw = prv[0], no
+    activation); layer 9 (256 -> 128, BODY_LAST0) keeps the fp32 epilogue (act() into xc[], :335-338) for the rgb head
+    (:558-582).  oracle/train_oracle.py::_mlp16 states the same arithmetic in torch.
+
+    xyz_enc / dir_enc: the kernels evaluate the encodings by an angle-doubling ladder (positional_encoding_ladder), which
+    differs from positional_encoding_for_* by ~2^k fp32 ulps at octave k: pass its encodings to emulate a kernel closely.
+
+    rnd: the fp16 rounding (round_fp16).  Pass ``lambda a: a`` to switch every rounding off: then the result is
+    mlp_forward's / mlp_forward_xyz_only's, which checks the wiring apart from the rounding."""
+    q = rnd
     if packed_epilogue == "c_in":
-        a16 = np.float16(alpha)
+        a16 = q(alpha)
 
         def dense(x, k, b):
-            y = (x @ q(k) + b).astype(np.float16)                                   # cast of the fp32 accumulator (bias inside)
-            z = (y.astype(F32) * F32(a16)).astype(np.float16)
-            return np.maximum(y, z).astype(F32)
+            y = q(x @ q(k) + b)                                                     # cast of the fp32 accumulator (bias inside)
+            return np.maximum(y, q(y * a16))
     elif packed_epilogue:
-        a16 = np.float16(alpha)
+        a16 = q(alpha)
 
         def dense(x, k, b):
-            y = (x @ q(k)).astype(np.float16)                                       # cast of the fp32 accumulator
-            y = (y.astype(np.float64) + np.asarray(b, F32).astype(np.float16).astype(np.float64)).astype(np.float16)
-            z = (y.astype(F32) * F32(a16)).astype(np.float16)                       # fp16 x fp16 is exact in fp32
-            return np.maximum(y, z).astype(F32)
+            y = q(x @ q(k))                                                         # cast of the fp32 accumulator
+            y = q(np.asarray(y, np.float64) + np.asarray(q(np.asarray(b, F32)), np.float64))   # fp16 + fp16, one rounding
+            return np.maximum(y, q(y * a16))                                        # fp16 x fp16 is exact in fp32
     else:
         dense = lambda x, k, b: q(leaky_relu(x @ q(k) + b, alpha))                 # noqa: E731
-    xq, dq = q(xyz_enc), q(dir_enc)
+    xq = q(np.asarray(xyz_enc, F32))
     h = dense(xq, *layers[0])
     for k, b in layers[1:4]:
         h = dense(h, k, b)
     h = dense(np.concatenate([xq, h], axis=-1), *layers[4])
     for k, b in layers[5:8]:
         h = dense(h, k, b)
-    hd = np.concatenate([h, dq], axis=-1)
+    if len(layers) == 12:                                                           # xyz-only network
+        h8 = dense(h, *layers[8])                                                   # BODY_HIDSIG hidden tiles
+        h9 = leaky_relu(h8 @ q(layers[9][0]) + layers[9][1], alpha)                 # BODY_LAST0: fp32 for the VALU head
+        rgb = h9 @ layers[10][0] + layers[10][1]
+        sigma = h @ q(layers[11][0]) + layers[11][1]                                # BODY_HIDSIG's leading sigma tile
+        return np.concatenate([rgb, sigma], axis=-1).astype(F32)
+    hd = np.concatenate([h, q(np.asarray(dir_enc, F32))], axis=-1)
     h8 = leaky_relu(hd @ q(layers[8][0]) + layers[8][1], alpha)          # stays fp32 for the VALU head
     rgb = h8 @ layers[9][0] + layers[9][1]
     sigma = hd @ q(layers[10][0]) + layers[10][1]
