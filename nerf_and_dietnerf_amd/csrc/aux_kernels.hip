@@ -271,7 +271,10 @@ void launch_sample_pdf(const float* weights, const float* z, long long N, int S,
 // butterfly (same terms as a left-to-right loop, another association: a few ulps).  Same result on every run and
 // for every batching of the rays.  The first version walked one ray per LANE: 64 wavefronts for a 4096-ray batch and
 // a 3 KiB stride between the lanes of a load.
+// SIGMA_ONLY (the coarse pass of a render, whose only output is the weights): raw is the compact (N*S,) sigma vector of
+// mlp_f16x3_sig_kernel, only `weights` is written, and the weights are the same bits as the full kernel's.
 // ------------------------------------------------------------------------------------------------
+template <bool SIGMA_ONLY>
 __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict__ raw, const float* __restrict__ z,
                                                         long long N, int S, float* __restrict__ rgb,
                                                         float* __restrict__ weights, float* __restrict__ cumprod,
@@ -286,7 +289,8 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     for (int s0 = 0; s0 < S; s0 += 64) {
         const int s = s0 + lane;
         const bool in = s < S;
-        const float4 o = in ? rw[s] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 o = SIGMA_ONLY ? make_float4(0.f, 0.f, 0.f, in ? raw[r * S + s] : 0.f)
+                                    : in ? rw[s] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float zc = in ? zr[s] : 0.f;
         const float delta = s + 1 < S ? zr[s + 1] - zc : 1e9f;
         const float sigma = fmaxf(o.w, 0.f);
@@ -308,6 +312,11 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
             T = Ts * (lane == 0 ? 1.0f : oms);
         }
         const float w = a * T;
+        if constexpr (SIGMA_ONLY) {
+            if (in) weights[r * S + s] = w;
+            carry = __shfl(T * om, 63);
+            continue;
+        }
         c0 += w * r0; c1 += w * r1; c2 += w * r2; dep += w * zc;
         if (in) {
             const long long m = r * S + s;
@@ -318,6 +327,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
         }
         carry = __shfl(T * om, 63);
     }
+    if constexpr (SIGMA_ONLY) return;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o); c2 += __shfl_xor(c2, o); dep += __shfl_xor(dep, o);
@@ -331,8 +341,14 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
 void launch_composite(const float* raw, const float* z, long long N, int S, float* rgb, float* weights,
                       float* cumprod, float* alpha, float* rgb_samples, float* depth, hipStream_t stream) {
     if (N <= 0) return;
-    hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, raw, z, N, S,
+    hipLaunchKernelGGL(composite_kernel<false>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, raw, z, N, S,
                        rgb, weights, cumprod, alpha, rgb_samples, depth);
+}
+
+void launch_composite_weights(const float* sigma, const float* z, long long N, int S, float* weights, hipStream_t stream) {
+    if (N <= 0) return;
+    hipLaunchKernelGGL(composite_kernel<true>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, sigma, z, N, S,
+                       nullptr, weights, nullptr, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -67,6 +67,11 @@ constexpr int kHChunksHid = (8 * kHQpuHid) / kHCQ;                   // 8
 constexpr int kHChunksSkip = (8 * kHQpuSkip + kHCQ - 1) / kHCQ;      // 10
 constexpr int kHChunksLast = (kHTilesLast * kHQpuLast + kHCQ - 1) / kHCQ;   // 6
 constexpr int kHStreamChunks = kHChunksPE + 6 * kHChunksHid + kHChunksSkip + kHChunksLast;   // 66
+// sigma-only stream of the coarse render pass (BODY_SIG: layer 8's sigma tile alone, its rgb tiles and head dropped): the
+// same chunks up to layer 7, then the sigma tile's 18 k-steps in 2 chunks
+constexpr int kHChunksSig = (kHQpuLast + kHCQ - 1) / kHCQ;                                   // 2
+constexpr int kHStreamChunksSig = kHStreamChunks - kHChunksLast + kHChunksSig;               // 62
+static_assert(kHStreamChunksSig * (size_t)kHChunkBytes == kStreamBytesF16Sig, "sigma-only stream size mismatch");
 // single-pass mode: its own stream with the hi fragments only (one quad per k-step)
 constexpr int kFChunksPE = (8 * kHStepsPE + kHCQ - 1) / kHCQ;                          // 1
 constexpr int kFChunksHid = (8 * kHStepsHid) / kHCQ;                                   // 4
@@ -103,7 +108,7 @@ constexpr int kXConstBHead = 2848;    // b_r, b_g, b_b, (unused)
 constexpr int kXConstWsig = 2864;     // [256] the sigma head's weights as floats (the trainer's backward adds its rank-1 term on the VALU)
 constexpr int kXConstFloats = 3120;
 static_assert(kXConstFloats <= kConstFloats, "xyz-only constants must fit the shared LDS carve");
-enum { BODY_HIDSIG = 4, BODY_LAST0 = 5 };
+enum { BODY_HIDSIG = 4, BODY_LAST0 = 5, BODY_SIG = 6 };
 static_assert(kHConstFloats <= kConstFloats, "f16x3 constants must fit the shared LDS carve");
 
 // Stash / gradient-buffer stores of the fused trainer kernels: streamed out once, read back gigabytes later by the

@@ -12,6 +12,10 @@
 //   * the weight stream holds an fp16 hi fragment and an fp16 lo fragment per (tile, k-step);
 //   * the sigma head (280 -> 1) rides the MFMA as a 5th output tile of layer 8 (its inputs only
 //     exist as fp16 hi/lo fragments); the rgb head (128 -> 3) stays on the VALU in fp32.
+// The coarse pass of a render reads nothing but the weights, which depend on sigma alone: mlp_f16x3_sig_kernel (SIGONLY)
+// ends in BODY_SIG, layer 8's sigma tile by itself (same bias, same 18 k-steps in the same pass order, same register
+// as the full kernel's tile 4, so sigma is bit-identical), skips the four rgb tiles and the rgb head, and writes sigma
+// alone: raw is then a compact (M,) vector.
 // Measured accuracy (tests/test_gpu_parity.py): final RGB within 1e-4 of the fp32 oracle.
 #include "mlp_f16_frag.h"
 
@@ -59,9 +63,9 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                                              frag4 (&xh)[16], frag4 (&xl)[16], frag4 (&nh)[14], frag4 (&nl)[14],
                                              const frag4 (&peh)[kHStepsPE], const frag4 (&pel)[kHStepsPE], const frag4 (&dh)[2],
                                              const frag4 (&dl)[2], float (&xc)[64], float& sigma_raw) {
-    constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_HIDSIG ? 9 : BODY == BODY_LAST0 ? 4 : 8;
+    constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_SIG ? 1 : BODY == BODY_HIDSIG ? 9 : BODY == BODY_LAST0 ? 4 : 8;
     constexpr int NSTEP = BODY == BODY_PE ? kHStepsPE : (BODY == BODY_HID || BODY == BODY_HIDSIG || BODY == BODY_LAST0) ? kHStepsHid
-                          : BODY == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;
+                          : BODY == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;   // BODY_LAST, BODY_SIG: [h7, dir]
     constexpr int SIG0 = BODY == BODY_HIDSIG ? 1 : 0;      // tiles before the first hidden tile (the leading sigma tile)
     constexpr int TPS = FAST ? 1 : 2;        // quads (A fragments) per k-step: hi [, lo]
     constexpr int QPU = TPS * NSTEP;
@@ -307,7 +311,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             // contiguous in the constant region) into the accumulator it will use -- free since 2 tiles
             if constexpr (n == (NSTEP >= 12 ? 10 : 0)) {
                 if constexpr (u + 1 < NU) load_bias(bias_off_bytes + (u + 1) * 128, nxt);
-                else if constexpr (BODY != BODY_LAST && BODY != BODY_LAST0) load_bias(bias_off_bytes + NU * 128, nxt);
+                else if constexpr (BODY != BODY_LAST && BODY != BODY_LAST0 && BODY != BODY_SIG) load_bias(bias_off_bytes + NU * 128, nxt);
             }
             // layer 0 has only 3 k-steps per tile: its epilogues go in one block per tile
             if constexpr (BODY == BODY_PE && u > 0 && n == 0) {
@@ -349,8 +353,10 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             if (mk_cur_ptr) stream_store(mk_cur_ptr, mk_cur);      // the 128-wide layer's record is complete
         }
     }
-    if constexpr (BODY == BODY_LAST) {
-        // sigma row: feature row 0 of tile 4 = register 0 of lane half 0; raw, no activation (NeRF.py:336)
+    if constexpr (BODY == BODY_LAST || BODY == BODY_SIG) {
+        // sigma row: feature row 0 of tile 4 (BODY_SIG: its only tile) = register 0 of lane half 0; raw, no activation
+        // (NeRF.py:336).  Both bodies keep that tile in accs[0].
+        static_assert(((NU - 1 + ROT) & 3) == 0, "the sigma tile's accumulator");
         sigma_raw = accs[(NU - 1) & 3][0];
         if constexpr (STASH) { if (mk_cur_ptr) stream_store(mk_cur_ptr, mk_cur); }   // layer 8 (128 features): all four tiles are finished
     }
@@ -376,8 +382,9 @@ __device__ __forceinline__ void split8(const float (&v)[8], frag4& hi, frag4& lo
     }
 }
 
-template <bool FAST, bool STASH = false, bool XYZ = false>
+template <bool FAST, bool STASH = false, bool XYZ = false, bool SIGONLY = false>
 __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
+    static_assert(!SIGONLY || (!FAST && !STASH && !XYZ), "the sigma-only variant is a render kernel of the 3-pass network");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -393,13 +400,18 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     const long long ntiles = (a.M + 127) / 128;
     if ((long long)blockIdx.x >= ntiles) return;
 
-    for (int i = tid; i < (XYZ ? kXConstFloats : kHConstFloats) / 4; i += 256)
-        reinterpret_cast<f32x4*>(smem + kLdsConst)[i] = reinterpret_cast<const f32x4*>(a.wconst)[i];
+    // SIGONLY: layer 7's last tile preloads the next body's bias from kHConstBias8 (the layers' biases are contiguous), and
+    // the next body is the sigma tile: its 32-float block (kHConstBiasSig) is copied there instead
+    for (int i = tid; i < (XYZ ? kXConstFloats : kHConstFloats) / 4; i += 256) {
+        const bool sig = SIGONLY && i >= kHConstBias8 / 4 && i < (kHConstBias8 + 32) / 4;
+        reinterpret_cast<f32x4*>(smem + kLdsConst)[i] =
+            reinterpret_cast<const f32x4*>(a.wconst)[sig ? i + (kHConstBiasSig - kHConstBias8) / 4 : i];
+    }
 
     Pipe p;
     p.ck = 0;
     p.src_next = 0;
-    p.n_chunks = XYZ ? (FAST ? kXFStreamChunks : kXStreamChunks) : (FAST ? kFStreamChunks : kHStreamChunks);
+    p.n_chunks = XYZ ? (FAST ? kXFStreamChunks : kXStreamChunks) : SIGONLY ? kHStreamChunksSig : (FAST ? kFStreamChunks : kHStreamChunks);
     p.wbase = reinterpret_cast<const char*>(a.wstream);
     p.voff = wave * (kHCQ / 4 * kQuadBytes) + lane * 16;
     p.wave_lds = wave * (kHCQ / 4 * kQuadBytes);
@@ -545,6 +557,9 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
             mk_prev_ptr = mk_cur_ptr; mk_cur_ptr = mk_of(9);
             mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
             layer_body_h<BODY_LAST0, true, FAST, STASH, 1>(p, lane16, cb_h, kXConstBias9 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+        } else if constexpr (SIGONLY) {
+            layer_body_h<BODY_SIG, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+            STAMP(t1); acc_t[4] += t1 - t0;
         } else {
             st_prev = st_cur;
             st_cur = st_of(8);
@@ -552,6 +567,14 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
             mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
             layer_body_h<BODY_LAST, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
             STAMP(t1); acc_t[4] += t1 - t0;
+        }
+        if constexpr (SIGONLY) {
+            if (valid && h == 0) {
+                a.raw[m] = sigma_raw;
+                if (a.nonfinite && !(fabsf(sigma_raw) <= 3.0e38f)) atomicAdd(a.nonfinite, 1ull);
+            }
+            STAMP(t0); acc_t[5] += t0 - t1; acc_t[6] += 1;
+            continue;
         }
         // rgb head (128 -> 3) on the VALU in fp32
         float o0 = 0.f, o1 = 0.f, o2 = 0.f;
@@ -598,6 +621,9 @@ __global__ __launch_bounds__(256, 1) void mlp_f16_kernel(const MlpArgs a) { mlp_
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_stash_kernel(const MlpArgs a) { mlp_f16_body<false, true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16_stash_kernel(const MlpArgs a) { mlp_f16_body<true, true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_xyz_kernel(const MlpArgs a) { mlp_f16_body<false, false, true>(a); }
+#if NERF_PE_LX == 5
+__global__ __launch_bounds__(256, 1) void mlp_f16x3_sig_kernel(const MlpArgs a) { mlp_f16_body<false, false, false, true>(a); }
+#endif
 __global__ __launch_bounds__(256, 1) void mlp_f16_xyz_kernel(const MlpArgs a) { mlp_f16_body<true, false, true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_xyz_stash_kernel(const MlpArgs a) { mlp_f16_body<false, true, true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16_xyz_stash_kernel(const MlpArgs a) { mlp_f16_body<true, true, true>(a); }
@@ -628,6 +654,15 @@ void launch_mlp_f16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool si
     else hipLaunchKernelGGL(mlp_f16x3_kernel, dim3(grid), dim3(256), kLdsTotal, stream, a);
 }
 
+#if NERF_PE_LX == 5
+void launch_mlp_f16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream) {
+    if (a.M <= 0) return;
+    const long long ntiles = (a.M + 127) / 128;
+    const int grid = (int)(ntiles < (long long)num_cus ? ntiles : (long long)num_cus);
+    hipLaunchKernelGGL(mlp_f16x3_sig_kernel, dim3(grid), dim3(256), kLdsTotal, stream, a);
+}
+#endif
+
 #if defined(NERF_STAMPS) && NERF_PE_LX == 5
 extern "C" void nerf_debug_read_stamps_h(unsigned long long* out) {
     (void)hipDeviceSynchronize();
@@ -652,6 +687,10 @@ void mlp_f16x3_set_attributes() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_f16_xyz_stash_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+#if NERF_PE_LX == 5
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_f16x3_sig_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -713,8 +752,9 @@ struct HLayer { const float* k; const float* b; int in, out; };
 
 // The packing as a pure index map: EmitW(pos_hi, pos_lo (-1 in the hi-only stream), src) for every 16-bit slot pair of
 // the stream, EmitC(pos, src) for every float of the constant region; src = index into the blob, -1 = zero padding.
+// sig_only: the sigma-only stream (3-pass, n_angles 1 or 2): layer 8 is BODY_SIG instead of BODY_LAST; same constants.
 template <class EmitW, class EmitC>
-static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c) {
+static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c, bool sig_only = false) {
     const int kd = 256 + 8 * (n_angles + 1);
     const bool xyz_only = n_angles == 0;
     // Keras creation order; xyz-only (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
@@ -732,7 +772,7 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
     }
     size_t chunk = 0;
     auto emit_body = [&](int layer, int body) {
-        const int NU = body == BODY_LAST ? kHTilesLast : body == BODY_HIDSIG ? 9 : body == BODY_LAST0 ? 4 : 8;
+        const int NU = body == BODY_LAST ? kHTilesLast : body == BODY_SIG ? 1 : body == BODY_HIDSIG ? 9 : body == BODY_LAST0 ? 4 : 8;
         const int NSTEP = body == BODY_PE ? kHStepsPE : (body == BODY_HID || body == BODY_HIDSIG || body == BODY_LAST0) ? kHStepsHid
                           : body == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;
         const long long b0 = (long long)chunk * (kHChunkBytes / 2);
@@ -753,7 +793,8 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
                         }
                         long long src = -1;
                         if (row >= 0) {
-                            if (body == BODY_LAST && u == kHTilesLast - 1) src = i == 0 ? L[10].k + row : -1;   // sigma row
+                            if ((body == BODY_LAST && u == kHTilesLast - 1) || body == BODY_SIG)
+                                src = i == 0 ? L[10].k + row : -1;                                                 // sigma row
                             else if (body == BODY_HIDSIG && u == 0) src = i == 0 ? L[11].k + row : -1;           // leading sigma row
                             else if (body == BODY_HIDSIG) src = L[layer].k + (long long)row * L[layer].out + 32 * (u - 1) + i;
                             else src = L[layer].k + (long long)row * L[layer].out + 32 * u + i;
@@ -785,7 +826,7 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
         for (int f = 0; f < 256; ++f) emit_c(kXConstWsig + f, L[11].k + f);
         return;
     }
-    emit_body(8, BODY_LAST);
+    emit_body(8, sig_only ? BODY_SIG : BODY_LAST);
     for (int f = 0; f < 128; ++f) emit_c(kHConstBias8 + f, L[8].b + f);
     emit_c(kHConstBiasSig + 0, L[10].b);
     for (int c = 0; c < 3; ++c)
@@ -793,9 +834,10 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c)
     for (int c = 0; c < 3; ++c) emit_c(kHConstBHead + c, L[9].b + c);
 }
 
-static void pack_weights_f16_impl(const float* blob, int n_angles, void* stream_out, float* const_out, bool hi_only) {
-    memset(stream_out, 0, n_angles == 0 ? (hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz)
-                                        : (hi_only ? kStreamBytesF16Hi : kStreamBytesF16));
+static void pack_weights_f16_impl(const float* blob, int n_angles, void* stream_out, float* const_out, bool hi_only,
+                                  bool sig_only = false) {
+    memset(stream_out, 0, sig_only ? kStreamBytesF16Sig : n_angles == 0 ? (hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz)
+                                                                        : (hi_only ? kStreamBytesF16Hi : kStreamBytesF16));
     memset(const_out, 0, kConstBytes);
     uint16_t* base = reinterpret_cast<uint16_t*>(stream_out);
     pack_f16_map(n_angles, hi_only,
@@ -805,7 +847,7 @@ static void pack_weights_f16_impl(const float* blob, int n_angles, void* stream_
                      base[ph] = hi;
                      if (pl >= 0) base[pl] = f32_to_f16(w - f16_to_f32(hi));
                  },
-                 [&](long long pos, long long src) { const_out[pos] = blob[src]; });
+                 [&](long long pos, long long src) { const_out[pos] = blob[src]; }, sig_only);
 }
 
 // gather tables of the 3-pass stream for the device-side re-pack (the trainer's forward runs on this kernel and its
@@ -862,5 +904,21 @@ void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float
 void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out) {
     pack_weights_f16_impl(blob, n_angles, stream_out, const_out, true);
 }
+#if NERF_PE_LX == 5
+void pack_weights_f16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out) {
+    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false, true);
+}
+// gather table of the sigma-only stream (kStreamBytesF16Sig / 2 entries); its constants are build_f16x3_gather's
+void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx) {
+    memset(stream_idx, 0, (kStreamBytesF16Sig / 2) * sizeof(int32_t));
+    pack_f16_map(n_angles, false,
+                 [&](long long ph, long long pl, long long src) {
+                     if (src < 0) return;
+                     stream_idx[ph] = (int32_t)(2 * (src + 1));
+                     stream_idx[pl] = (int32_t)(2 * (src + 1) + 1);
+                 },
+                 [](long long, long long) {}, true);
+}
+#endif
 
 }  // namespace nerf

@@ -193,6 +193,12 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
     pack_weights_f16(blob, c->cfg.n_angles, sth1.data(), csh.data());       // same constants as the 3-pass stream
     if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16Hi));
     HIP_OK(hipMemcpy(n.stream_h1, sth1.data(), kStreamBytesF16Hi, hipMemcpyHostToDevice));
+    if (which == NERF_NET_COARSE) {      // the coarse pass of a render reads the weights only: sigma-only stream (dev_render)
+        std::vector<uint16_t> sths(kStreamBytesF16Sig / 2);
+        pack_weights_f16x3_sig(blob, c->cfg.n_angles, sths.data(), csh.data());
+        if (!n.stream_hs) HIP_OK(hipMalloc((void**)&n.stream_hs, kStreamBytesF16Sig));
+        HIP_OK(hipMemcpy(n.stream_hs, sths.data(), kStreamBytesF16Sig, hipMemcpyHostToDevice));
+    }
     const size_t nf = nerf_blob_size(&c->cfg);
     if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf);
     n.loaded = true;
@@ -219,14 +225,23 @@ int check_cfg(const nerf_config* cfg) {
     return 0;
 }
 
+// can network `which` run the sigma-only kernel (launch_mlp_f16x3_sig)?  f16x3 precision, the kLx build, n_angles 1 or 2
+bool sigma_only_ok(const nerf_ctx* c, int which) {
+    return c->cfg.precision == NERF_PRECISION_F16X3 && c->cfg.n_pos_enc_xyz <= kLx && c->cfg.n_angles != 0 &&
+           c->net[which].stream_hs != nullptr;
+}
+
 // record the MLP launch between two events when timing is on
+// sigma_only (sigma_only_ok): raw receives sigma alone, (M,) floats
 int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const float* z, float* raw, long long M,
-            int S, int mode) {
+            int S, int mode, bool sigma_only = false) {
     if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
     if (int r = train_flush_weights(c, which)) return r;   // re-pack the operand streams after optimizer steps
+    if (sigma_only && !sigma_only_ok(c, which)) return fail("internal: network %d has no sigma-only kernel", which);
     const bool f16 = c->cfg.precision == NERF_PRECISION_F16X3 || c->cfg.precision == NERF_PRECISION_F16;
     MlpArgs a{};
-    a.wstream = c->cfg.precision == NERF_PRECISION_F16 ? (const float*)c->net[which].stream_h1
+    a.wstream = sigma_only ? (const float*)c->net[which].stream_hs
+                : c->cfg.precision == NERF_PRECISION_F16 ? (const float*)c->net[which].stream_h1
                 : f16 ? (const float*)c->net[which].stream_h : c->net[which].stream;
     a.wconst = f16 ? c->net[which].cst_h : c->net[which].cst;
     a.in_a = in_a; a.in_b = in_b; a.z = z; a.raw = raw; a.M = M; a.S = S; a.mode = mode;
@@ -248,7 +263,8 @@ int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const 
     // single-pass mode: two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the
     // one-tile kernel; the xyz-only network has the one-tile variant only
     static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
-    if (c->cfg.n_pos_enc_xyz > kLx) {
+    if (sigma_only) launch_mlp_f16x3_sig(a, c->num_cus, c->stream);
+    else if (c->cfg.n_pos_enc_xyz > kLx) {
         // wide-PE network: the 3-pass or the one-tile single-pass kernel of the wide-PE build (no fp32 kernel, check_cfg)
         if (!f16) return fail("n_pos_enc_dim_xyz %d: no exact-fp32 kernel (precision f16x3 or f16)", c->cfg.n_pos_enc_xyz);
         wide::launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
@@ -329,8 +345,20 @@ int copy_back_batch(nerf_ctx* c, const nerf_outputs* host, const nerf_outputs* d
 }
 
 // render_rays on device pointers
+// A coarse pass whose only output is the weights (the coarse pass of NeRF.render) runs the sigma-only network and the
+// weights-only composite where sigma_only_ok: the weights depend on sigma alone and come out bit-identical.
 int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, const float* z, long long N, int S,
                     const nerf_outputs& outs) {
+    const bool weights_only = outs.weights && !outs.rgb && !outs.cumprod && !outs.alpha && !outs.rgb_samples && !outs.z &&
+                              !outs.depth;
+    if (which == NERF_NET_COARSE && weights_only && sigma_only_ok(c, which)) {
+        if (int r = ensure(c, c->b_raw, (size_t)N * S * sizeof(float))) return r;
+        float* sigma = (float*)c->b_raw.p;
+        if (int r = run_mlp(c, which, o, d, z, sigma, N * S, S, 0, true)) return r;
+        launch_composite_weights(sigma, z, N, S, outs.weights, c->stream);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
     if (int r = ensure(c, c->b_raw, (size_t)N * S * 4 * sizeof(float))) return r;
     float* raw = (float*)c->b_raw.p;
     if (int r = run_mlp(c, which, o, d, z, raw, N * S, S, 0)) return r;
@@ -354,7 +382,7 @@ int dev_render(nerf_ctx* c, const float* o, const float* d, long long N, int Sc,
     if (int r = ensure(c, c->b_wc, (size_t)N * Sc * sizeof(float))) return r;
     nerf_outputs co{};
     co.weights = (float*)c->b_wc.p;
-    if (int r = dev_render_rays(c, NERF_NET_COARSE, o, d, zc, N, Sc, co)) return r;
+    if (int r = dev_render_rays(c, NERF_NET_COARSE, o, d, zc, N, Sc, co)) return r;   // weights only: the sigma-only path
     const int St = Sc + Sf;
     if (int r = ensure(c, c->b_zf, (size_t)N * St * sizeof(float))) return r;
     float* zf = (float*)c->b_zf.p;
@@ -426,6 +454,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
         if (n.cst) (void)hipFree(n.cst);
         if (n.stream_h) (void)hipFree(n.stream_h);
         if (n.stream_h1) (void)hipFree(n.stream_h1);
+        if (n.stream_hs) (void)hipFree(n.stream_hs);
         if (n.cst_h) (void)hipFree(n.cst_h);
     }
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }

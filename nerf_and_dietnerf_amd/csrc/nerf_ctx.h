@@ -30,6 +30,7 @@ struct NetWeights {
     float* cst = nullptr;        // kConstBytes
     void* stream_h = nullptr;    // kStreamBytesF16   (fp16 hi/lo fragment stream)
     void* stream_h1 = nullptr;   // kStreamBytesF16Hi (fp16 hi-only stream of the single-pass mode)
+    void* stream_hs = nullptr;   // kStreamBytesF16Sig (sigma-only 3-pass stream: the coarse network of a (kLx, n_angles 1|2) config)
     float* cst_h = nullptr;      // kConstBytes
     bool loaded = false;
     std::vector<float> host_blob;   // last blob handed to nerf_load_weights (Keras order): seed of the trainer

@@ -47,6 +47,7 @@ constexpr size_t kStreamBytes = size_t(kStreamChunks) * kChunkBytes;
 constexpr size_t kStreamBytesXyzF32 = size_t(142) * kChunkBytes;   // the xyz-only network's fp32 stream (12 Dense layers, mlp_fp32.hip)
 constexpr size_t kStreamBytesF16 = size_t(66) * 32 * kQuadBytes;   // f16x3 stream: 66 chunks of 32 KiB (mlp_f16x3.hip)
 constexpr size_t kStreamBytesF16Hi = size_t(33) * 32 * kQuadBytes; // single-pass fp16 stream: hi fragments only
+constexpr size_t kStreamBytesF16Sig = size_t(62) * 32 * kQuadBytes; // f16x3 sigma-only stream (coarse render pass)
 constexpr size_t kStreamBytesF16Xyz = size_t(73) * 32 * kQuadBytes;    // the xyz-only network's streams (12 Dense layers)
 constexpr size_t kStreamBytesF16HiXyz = size_t(37) * 32 * kQuadBytes;
 
@@ -108,6 +109,11 @@ void mlp_f16x3_set_attributes();
 // stream_out: kStreamBytesF16 / kStreamBytesF16Hi bytes (kStreamBytesF16Xyz / kStreamBytesF16HiXyz when n_angles == 0)
 void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
 void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
+// sigma-only coarse render (3-pass, n_angles 1 or 2, the kLx build only): a.raw receives sigma alone, (M,) floats; its
+// stream (kStreamBytesF16Sig) ends in layer 8's sigma tile, its constants are pack_weights_f16x3's
+void launch_mlp_f16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream);
+void pack_weights_f16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
+void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx /* kStreamBytesF16Sig / 2 */);
 
 // mlp_f16x3_wide.hip -- the same entry points for networks with n_pos_enc_dim_xyz 6..10: kernels that encode kLxWide octaves,
 // packers / gather tables for the (kLxWide, kLd) blob layout (same stream sizes).  No exact-fp32 render kernel exists for them.
@@ -180,6 +186,8 @@ void launch_sample_pdf(const float* weights, const float* z, long long N, int S,
                        hipStream_t stream);
 void launch_composite(const float* raw, const float* z, long long N, int S, float* rgb, float* weights,
                       float* cumprod, float* alpha, float* rgb_samples, float* depth, hipStream_t stream);
+// the weights alone, from a compact (N*S,) sigma vector (launch_mlp_f16x3_sig's output): bit-identical to launch_composite's
+void launch_composite_weights(const float* sigma, const float* z, long long N, int S, float* weights, hipStream_t stream);
 void launch_posenc(const float* x, long long M, int n_enc, int passthrough, float* out, hipStream_t stream);
 
 }  // namespace nerf

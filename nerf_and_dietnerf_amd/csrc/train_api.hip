@@ -108,8 +108,9 @@ struct TrainState {
     // path's three operand streams re-packed from the trained blob: on the DEVICE, by gather tables built once from the host
     // packers (round 4; the device -> host -> pack x 3 -> device round trip this replaces cost ~30 ms and two synchronisations
     // per render).  rt_h / rt_h1: build_f16x3_gather (3-pass / hi-only stream), rt_ch their constants; rt_f / rt_cf: the fp32
-    // stream and constants (pack_weights_fp32 only moves values: the table is the packed INDEX blob).
-    int32_t *rt_h = nullptr, *rt_h1 = nullptr, *rt_ch = nullptr, *rt_f = nullptr, *rt_cf = nullptr;
+    // stream and constants (pack_weights_fp32 only moves values: the table is the packed INDEX blob).  rt_hs: the coarse
+    // network's sigma-only stream (build_f16x3_sig_gather; constants rt_ch), where the render path has one.
+    int32_t *rt_h = nullptr, *rt_h1 = nullptr, *rt_ch = nullptr, *rt_f = nullptr, *rt_cf = nullptr, *rt_hs = nullptr;
     std::vector<RenderSlot> slots;  // nerf_train_render_forward / _backward
 };
 
@@ -1085,7 +1086,7 @@ void train_free(nerf_ctx* c) {
         if (n.fcst) (void)hipFree(n.fcst);
         if (n.bstream) (void)hipFree(n.bstream);
     }
-    for (int32_t* p : {t->rt_h, t->rt_h1, t->rt_ch, t->rt_f, t->rt_cf})
+    for (int32_t* p : {t->rt_h, t->rt_h1, t->rt_ch, t->rt_f, t->rt_cf, t->rt_hs})
         if (p) (void)hipFree(p);
     if (t->sidx) (void)hipFree(t->sidx);
     if (t->cidx) (void)hipFree(t->cidx);
@@ -1151,6 +1152,12 @@ static int ensure_render_tables(nerf_ctx* c, TrainState* t) {
     std::vector<int32_t> f(nf), cfi(kConstFloats);
     for (size_t i = 0; i < nf; ++i) f[i] = (int32_t)sf[i];
     for (size_t i = 0; i < (size_t)kConstFloats; ++i) cfi[i] = (int32_t)cf[i];
+    if (na != 0) {
+        std::vector<int32_t> hs(kStreamBytesF16Sig / 2);
+        build_f16x3_sig_gather(na, hs.data());
+        aim_gather(c->cfg, hs.data(), hs.size(), true);
+        if (int r = up(hs, &t->rt_hs)) return r;
+    }
     if (int r = up(h1, &t->rt_h1)) return r;
     if (int r = up(ch, &t->rt_ch)) return r;
     if (int r = up(f, &t->rt_f)) return r;
@@ -1172,6 +1179,10 @@ int train_flush_weights(nerf_ctx* c, int which, bool to_host) {
         const int na = c->cfg.n_angles;
         launch_repack_f16x3(n.blob, t->rt_h, nw.stream_h, t->rt_ch, nw.cst_h, f16_stream_bytes(na, false), c->stream);
         launch_repack_f16x3(n.blob, t->rt_h1, nw.stream_h1, t->rt_ch, nw.cst_h, f16_stream_bytes(na, true), c->stream);
+        if (nw.stream_hs) {
+            if (!t->rt_hs) return fail("internal: no gather table for the sigma-only stream");
+            launch_repack_f16x3(n.blob, t->rt_hs, nw.stream_hs, t->rt_ch, nw.cst_h, kStreamBytesF16Sig, c->stream);
+        }
         if (t->rt_f) {
             launch_gather_blob(n.blob, t->rt_f, nw.stream, (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4, c->stream);
             launch_gather_blob(n.blob, t->rt_cf, nw.cst, kConstFloats, c->stream);
