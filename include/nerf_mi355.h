@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NERF_ABI_VERSION 5
+#define NERF_ABI_VERSION 6
 
 enum { NERF_NET_COARSE = 0, NERF_NET_FINE = 1 };
 enum { NERF_MEM_HOST = 0, NERF_MEM_DEVICE = 1 };
@@ -37,14 +37,17 @@ enum { NERF_MEM_HOST = 0, NERF_MEM_DEVICE = 1 };
 enum {
     NERF_PRECISION_FP32 = 0,   /* v_mfma_f32_32x32x2_f32: exact fp32 fma chains (parity mode)      */
     NERF_PRECISION_F16X3 = 1,  /* 3-pass split-fp16 MFMA (hi*hi + hi*lo + lo*hi), fp32 accumulate */
-    NERF_PRECISION_F16 = 2     /* 1-pass fp16 MFMA, fp32 accumulate, activations rounded to fp16 between layers: the
+    NERF_PRECISION_F16 = 2,    /* 1-pass fp16 MFMA, fp32 accumulate, activations rounded to fp16 between layers: the
                                   numerics class of the reference's production policy (mixed_float16,
                                   src/ExecutionRun.py:220-221); NOT the fp32 parity mode */
+    NERF_PRECISION_BF16X3 = 3  /* 3-pass split-bf16 MFMA (hi*hi + hi*lo + lo*hi), fp32 accumulate: ~16 significant bits per
+                                  operand (fp32-class results, 1e-4 RGB) with fp32's exponent range -- nothing saturates at
+                                  65504.  Render path only: the trainer's kernels do not depend on the ctx precision */
 };
 
 /* Network + frustum description: the 9 net/render keys of src/ConfigurationKeys.py:64-111. */
 typedef struct nerf_config {
-    int32_t n_pos_enc_xyz;    /* n_pos_enc_dim_xyz   (5)   accepted: 1..10; 6..10 with precision f16x3 / f16 only */
+    int32_t n_pos_enc_xyz;    /* n_pos_enc_dim_xyz   (5)   accepted: 1..10; 6..10 with precision f16x3 / bf16x3 / f16 only */
     int32_t n_pos_enc_dir;    /* n_pos_enc_view_dir  (4)   accepted: 1..4 */
     int32_t n_angles;         /* n_angles_for_model  (2)   accepted: 0 (xyz-only network), 1, 2 */
     int32_t hidden_dim;       /* hidden_layer_dim    (256) accepted: 256 only */
@@ -174,8 +177,10 @@ int nerf_render_image_sharded_outputs(nerf_ctx* ctx, const float* c2w, float fie
 /* ---- status ------------------------------------------------------------------------------ */
 /* Synchronises and returns (then clears) the number of sample rows whose network output was not finite
  * since the last read.  NERF_PRECISION_F16X3 needs |activations| < 65504 (fp16 range); a non-zero count
- * there means: switch this model to NERF_PRECISION_FP32.  The reference has no such check (TF propagates
- * NaN silently). */
+ * there means: switch this model to NERF_PRECISION_BF16X3 (fp32's range: about 3.4e38; the only fp32-class mode of
+ * a network with n_pos_enc_dim_xyz 6..10) or to NERF_PRECISION_FP32.  NERF_PRECISION_BF16X3 counts as well: there a
+ * non-zero count means the fp32 network itself overflows or holds NaN weights.  The reference has no such check (TF
+ * propagates NaN silently). */
 int nerf_ctx_read_nonfinite(nerf_ctx* ctx, int64_t* rows);
 
 /* ---- training ---------------------------------------------------

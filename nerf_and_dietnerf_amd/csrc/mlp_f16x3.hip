@@ -17,15 +17,52 @@
 // as the full kernel's tile 4, so sigma is bit-identical), skips the four rgb tiles and the rgb head, and writes sigma
 // alone: raw is then a compact (M,) vector.
 // Measured accuracy (tests/test_gpu_parity.py): final RGB within 1e-4 of the fp32 oracle.
+//
+// NERF_BF16 (mlp_bf16x3.hip, mlp_bf16x3_wide.hip) builds the 3-pass render kernels of this source a second time with bf16
+// elements (NERF_PRECISION_BF16X3): x = hi + lo with hi = the top 16 bits of the fp32 value (exact in bf16, no conversion)
+// and lo = x - hi rounded to bf16, the same three passes on v_mfma_f32_32x32x16_bf16 -- same lane map, k-step, C/D layout,
+// fragment order, ring and epilogue schedule; ~16 significant bits per operand and fp32's exponent range (nothing
+// saturates at 65504).  Only the view-direction, xyz-only and sigma-only render kernels exist in that build (no
+// single-pass, no stash variant); the device-side re-pack of its streams reads the fp16 build's gather tables (same slots).
 #include "mlp_f16_frag.h"
 
 #include <math.h>
 #include <string.h>
 
-#if NERF_PE_LX == 5
+#if defined(NERF_BF16) && NERF_PE_LX == 5
+namespace nerf::bf16 {     // the bf16 build (mlp_bf16x3.hip): the 3-pass render kernels with bf16 elements
+#elif defined(NERF_BF16)
+namespace nerf::bf16::wide {   // ... and its wide-PE build (mlp_bf16x3_wide.hip)
+#elif NERF_PE_LX == 5
 namespace nerf {
 #else
 namespace nerf::wide {     // the wide-PE build (mlp_f16x3_wide.hip): same kernels with 10 xyz octaves
+#endif
+
+// ---- element format of the 3-pass kernels: fp16, or bf16 under NERF_BF16 ----
+#ifdef NERF_BF16
+typedef __bf16 e8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+#define NERF_MFMA_E16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
+// hi = the top 16 bits (8 significant bits, exact in bf16), lo = y - hi (exact in fp32, |lo| < 2^-7 |y|)
+__device__ __forceinline__ void split_e(float y, float& hi_f, float& lo_f) {
+    hi_f = __uint_as_float(__float_as_uint(y) & 0xFFFF0000u);
+    lo_f = y - hi_f;
+}
+// two hi parts -> one dword: their upper halves, one v_perm_b32, no conversion
+__device__ __forceinline__ uint32_t pack_hi(float a, float b) {
+    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+}
+__device__ __forceinline__ uint32_t pack_lo(float a, float b) {   // RNE; v_cvt_pk_bf16_f32
+    const bf2 t = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(uint32_t, t);
+}
+#else
+typedef h8 e8;
+#define NERF_MFMA_E16 __builtin_amdgcn_mfma_f32_32x32x16_f16
+__device__ __forceinline__ void split_e(float y, float& hi_f, float& lo_f) { split_trunc(y, hi_f, lo_f); }
+__device__ __forceinline__ uint32_t pack_hi(float a, float b) { return pack_h2(a, b); }
+__device__ __forceinline__ uint32_t pack_lo(float a, float b) { return pack_h2(a, b); }
 #endif
 
 #ifdef NERF_STAMPS
@@ -159,9 +196,9 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             ph = pack_h2(y0, y1);                                         // round to fp16, no lo part
         } else {
             float h0, l0, h1, l1;
-            split_trunc(y0, h0, l0);
-            split_trunc(y1, h1, l1);
-            ph = pack_h2(h0, h1); pl = pack_h2(l0, l1);                   // whole-register writes
+            split_e(y0, h0, l0);
+            split_e(y1, h1, l1);
+            ph = pack_hi(h0, h1); pl = pack_lo(l0, l1);                   // whole-register writes
         }
         if constexpr (STASH) {
             if constexpr (FAST) stash4h(utc, rc, ph, decltype(pend_sel)::value ? st_prev : st_cur);
@@ -246,8 +283,8 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                     issue_read(std::integral_constant<int, Qn>{});
                 }
             });
-            const h8 a_hi = __builtin_bit_cast(h8, araw[0]);
-            const h8 a_lo = __builtin_bit_cast(h8, araw[FAST ? 0 : 1]);
+            const e8 a_hi = __builtin_bit_cast(e8, araw[0]);
+            const e8 a_lo = __builtin_bit_cast(e8, araw[FAST ? 0 : 1]);
             (void)a_lo;
             frag4 bh_, bl_;
             if constexpr (BODY == BODY_PE) { bh_ = peh[n]; bl_ = pel[n]; }
@@ -259,7 +296,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                 if constexpr (n < kHStepsHid) { bh_ = xh[n]; bl_ = xl[n]; }
                 else { bh_ = dh[n - kHStepsHid]; bl_ = dl[n - kHStepsHid]; }
             }
-            const h8 b_hi = __builtin_bit_cast(h8, bh_), b_lo = __builtin_bit_cast(h8, bl_);
+            const e8 b_hi = __builtin_bit_cast(e8, bh_), b_lo = __builtin_bit_cast(e8, bl_);
             // Deferred epilogue: within a layer ONE accumulator register of the previous tile per k-step over
             // all 16 steps (fragment dwords are packed on odd steps); the previous LAYER's tile 7 goes a pair per
             // step over steps 0..7 because its fragments are read from step 14 on.
@@ -270,10 +307,10 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             // the leading sigma tile (row 0 = the raw density, no activation, src/NeRF.py:283) is complete after tile 0
             if constexpr (BODY == BODY_HIDSIG && u == 1 && n == 0) sigma_raw = prv[0];
             if constexpr (!FAST) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc, 0, 0, 0);
+                acc = NERF_MFMA_E16(a_hi, b_lo, acc, 0, 0, 0);
+                acc = NERF_MFMA_E16(a_lo, b_hi, acc, 0, 0, 0);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc, 0, 0, 0);
+            acc = NERF_MFMA_E16(a_hi, b_hi, acc, 0, 0, 0);
             if constexpr (kPend && kPackedEpi) {
                 constexpr int er = 2 * n;
                 store_pair_p(std::integral_constant<int, 7>{}, std::integral_constant<int, er>{}, act_pair(prv[er], prv[er + 1]), std::true_type{}, std::true_type{});
@@ -375,10 +412,10 @@ __device__ __forceinline__ void split8(const float (&v)[8], frag4& hi, frag4& lo
             continue;
         }
         float h0, l0, h1, l1;
-        split_trunc(v[e], h0, l0);
-        split_trunc(v[e + 1], h1, l1);
-        hi[e >> 1] = pack_h2(h0, h1);
-        lo[e >> 1] = pack_h2(l0, l1);
+        split_e(v[e], h0, l0);
+        split_e(v[e + 1], h1, l1);
+        hi[e >> 1] = pack_hi(h0, h1);
+        lo[e >> 1] = pack_lo(l0, l1);
     }
 }
 
@@ -616,6 +653,39 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+#ifdef NERF_BF16
+__global__ __launch_bounds__(256, 1) void mlp_bf16x3_kernel(const MlpArgs a) { mlp_f16_body<false>(a); }
+__global__ __launch_bounds__(256, 1) void mlp_bf16x3_xyz_kernel(const MlpArgs a) { mlp_f16_body<false, false, true>(a); }
+#if NERF_PE_LX == 5
+__global__ __launch_bounds__(256, 1) void mlp_bf16x3_sig_kernel(const MlpArgs a) { mlp_f16_body<false, false, false, true>(a); }
+#endif
+
+static int bf_grid(const MlpArgs& a, int num_cus) {
+    const long long ntiles = (a.M + 127) / 128;
+    return (int)(ntiles < (long long)num_cus ? ntiles : (long long)num_cus);
+}
+void launch_mlp_bf16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only) {
+    if (a.M <= 0) return;
+    if (xyz_only) hipLaunchKernelGGL(mlp_bf16x3_xyz_kernel, dim3(bf_grid(a, num_cus)), dim3(256), kLdsTotal, stream, a);
+    else hipLaunchKernelGGL(mlp_bf16x3_kernel, dim3(bf_grid(a, num_cus)), dim3(256), kLdsTotal, stream, a);
+}
+#if NERF_PE_LX == 5
+void launch_mlp_bf16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream) {
+    if (a.M <= 0) return;
+    hipLaunchKernelGGL(mlp_bf16x3_sig_kernel, dim3(bf_grid(a, num_cus)), dim3(256), kLdsTotal, stream, a);
+}
+#endif
+void mlp_bf16x3_set_attributes() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bf16x3_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bf16x3_xyz_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+#if NERF_PE_LX == 5
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bf16x3_sig_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+#endif
+}
+#else    // !NERF_BF16: the fp16 kernels
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_kernel(const MlpArgs a) { mlp_f16_body<false>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16_kernel(const MlpArgs a) { mlp_f16_body<true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_stash_kernel(const MlpArgs a) { mlp_f16_body<false, true>(a); }
@@ -692,6 +762,7 @@ void mlp_f16x3_set_attributes() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
 #endif
 }
+#endif   // NERF_BF16
 
 // ------------------------------------------------------------------------------------------------
 // Host-side packing: blob (Keras get_weights() order) -> fp16 hi/lo fragment stream + fp32 constants
@@ -730,6 +801,24 @@ float f16_to_f32(uint16_t hbits) {
     memcpy(&f, &x, 4);
     return f;
 }
+#ifdef NERF_BF16
+// fp32 -> bf16 round-to-nearest-even (v_cvt_pk_bf16_f32) and back
+uint16_t f32_to_e16(float f) {
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x40u);   // nan stays nan
+    return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
+}
+float e16_to_f32(uint16_t b) {
+    const uint32_t x = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &x, 4);
+    return f;
+}
+#else
+uint16_t f32_to_e16(float f) { return f32_to_f16(f); }
+float e16_to_f32(uint16_t hbits) { return f16_to_f32(hbits); }
+#endif
 int h_pe_row(int v, int h) {   // slot v (0..23) of lane half h -> row of the (33, .) kernel; -1 = pad
     if (v < 3 * kPeLx) { const int c = v / kPeLx, k = v % kPeLx; return c * (1 + 2 * kPeLx) + 1 + 2 * k + h; }
     if (kPeLx != 5) {              // wide-PE build: slots 0..31 of the (63, .) kernel; raw x, y in half 0, z in half 1
@@ -843,13 +932,44 @@ static void pack_weights_f16_impl(const float* blob, int n_angles, void* stream_
     pack_f16_map(n_angles, hi_only,
                  [&](long long ph, long long pl, long long src) {
                      const float w = src < 0 ? 0.f : blob[src];
-                     const uint16_t hi = f32_to_f16(w);
+                     const uint16_t hi = f32_to_e16(w);
                      base[ph] = hi;
-                     if (pl >= 0) base[pl] = f32_to_f16(w - f16_to_f32(hi));
+                     if (pl >= 0) base[pl] = f32_to_e16(w - e16_to_f32(hi));
                  },
                  [&](long long pos, long long src) { const_out[pos] = blob[src]; }, sig_only);
 }
 
+#if defined(NERF_BF16) && NERF_PE_LX == 5
+// device-side re-pack of a bf16 hi/lo stream from a blob: the fp16 build's gather table of the same stream (same slots,
+// build_f16x3_gather / build_f16x3_sig_gather), elements rounded as the host packer above rounds them
+__global__ void repack_bf16x3_kernel(const float* __restrict__ blob, const int32_t* __restrict__ stream_idx,
+                                     uint16_t* __restrict__ stream, size_t n_slots) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots) return;
+    const int32_t t = stream_idx[i];
+    uint16_t out = 0;
+    if (t != 0) {
+        const float w = blob[(t >> 1) - 1];
+        const __bf16 hi = (__bf16)w;                             // RNE, as the host packer
+        const __bf16 v = (t & 1) ? (__bf16)(w - (float)hi) : hi;
+        out = __builtin_bit_cast(uint16_t, v);
+    }
+    stream[i] = out;
+}
+void launch_repack_bf16x3(const float* blob, const int32_t* stream_idx, void* stream, size_t stream_bytes, hipStream_t s) {
+    const size_t n = stream_bytes / 2;
+    hipLaunchKernelGGL(repack_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blob, stream_idx,
+                       reinterpret_cast<uint16_t*>(stream), n);
+}
+void pack_weights_bf16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out) {
+    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false, true);
+}
+#endif
+#ifdef NERF_BF16
+void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out) {
+    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false);
+}
+#else    // !NERF_BF16
 // gather tables of the 3-pass stream for the device-side re-pack (the trainer's forward runs on this kernel and its
 // weights change every step): stream_idx[slot] = 2 * (src + 1) + is_lo, const_idx[float] = src + 1; 0 = padding
 size_t f16_stream_bytes(int n_angles, bool hi_only) {
@@ -920,5 +1040,6 @@ void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx) {
                  [](long long, long long) {}, true);
 }
 #endif
+#endif   // NERF_BF16
 
-}  // namespace nerf
+}  // namespace nerf (:: wide, :: bf16, :: bf16::wide)

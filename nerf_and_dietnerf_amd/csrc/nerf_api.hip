@@ -138,11 +138,16 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
         std::vector<float> cst(kConstFloats);
         wide::pack_weights_f16x3(blob, c->cfg.n_angles, s3.data(), cst.data());
         wide::pack_weights_f16(blob, c->cfg.n_angles, s1.data(), cst.data());
+        std::vector<uint16_t> sb(b3 / 2);
+        std::vector<float> cb(kConstFloats);
+        bf16::wide::pack_weights_bf16x3(blob, c->cfg.n_angles, sb.data(), cb.data());       // (cb == cst: fp32 constants)
+        if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, b3));
         if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, b3));
         if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, b1));
         if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
         HIP_OK(hipStreamSynchronize(c->stream));
         HIP_OK(hipMemcpy(n.stream_h, s3.data(), b3, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(n.stream_b, sb.data(), b3, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.stream_h1, s1.data(), b1, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.cst_h, cst.data(), kConstBytes, hipMemcpyHostToDevice));
         const size_t nfw = nerf_blob_size(&c->cfg);
@@ -158,6 +163,10 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
         pack_weights_f16x3(blob, 0, sx.data(), cx.data());
         pack_weights_f16(blob, 0, sx1.data(), cx.data());
         pack_weights_fp32(blob, 0, sf.data(), cf.data());
+        std::vector<uint16_t> sbx(kStreamBytesF16Xyz / 2);
+        std::vector<float> cbx(kConstFloats);
+        bf16::pack_weights_bf16x3(blob, 0, sbx.data(), cbx.data());                         // (cbx == cx: fp32 constants)
+        if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, kStreamBytesF16Xyz));
         if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, kStreamBytesF16Xyz));
         if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16HiXyz));
         if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
@@ -167,6 +176,7 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
         HIP_OK(hipMemcpy(n.stream, sf.data(), kStreamBytesXyzF32, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.cst, cf.data(), kConstBytes, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.stream_h, sx.data(), kStreamBytesF16Xyz, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(n.stream_b, sbx.data(), kStreamBytesF16Xyz, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.stream_h1, sx1.data(), kStreamBytesF16HiXyz, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(n.cst_h, cx.data(), kConstBytes, hipMemcpyHostToDevice));
         const size_t nf0 = nerf_blob_size(&c->cfg);
@@ -193,11 +203,18 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
     pack_weights_f16(blob, c->cfg.n_angles, sth1.data(), csh.data());       // same constants as the 3-pass stream
     if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16Hi));
     HIP_OK(hipMemcpy(n.stream_h1, sth1.data(), kStreamBytesF16Hi, hipMemcpyHostToDevice));
+    // the bf16 hi/lo stream of NERF_PRECISION_BF16X3 (same geometry; its constants are the fp32 ones of cst_h)
+    bf16::pack_weights_bf16x3(blob, c->cfg.n_angles, sth.data(), csh.data());
+    if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, kStreamBytesF16));
+    HIP_OK(hipMemcpy(n.stream_b, sth.data(), kStreamBytesF16, hipMemcpyHostToDevice));
     if (which == NERF_NET_COARSE) {      // the coarse pass of a render reads the weights only: sigma-only stream (dev_render)
         std::vector<uint16_t> sths(kStreamBytesF16Sig / 2);
         pack_weights_f16x3_sig(blob, c->cfg.n_angles, sths.data(), csh.data());
         if (!n.stream_hs) HIP_OK(hipMalloc((void**)&n.stream_hs, kStreamBytesF16Sig));
         HIP_OK(hipMemcpy(n.stream_hs, sths.data(), kStreamBytesF16Sig, hipMemcpyHostToDevice));
+        bf16::pack_weights_bf16x3_sig(blob, c->cfg.n_angles, sths.data(), csh.data());
+        if (!n.stream_bs) HIP_OK(hipMalloc((void**)&n.stream_bs, kStreamBytesF16Sig));
+        HIP_OK(hipMemcpy(n.stream_bs, sths.data(), kStreamBytesF16Sig, hipMemcpyHostToDevice));
     }
     const size_t nf = nerf_blob_size(&c->cfg);
     if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf);
@@ -219,16 +236,18 @@ int check_cfg(const nerf_config* cfg) {
                     "(got %d %d %d %d)", kLxWide, kLd, kHidden, kLast, cfg->n_pos_enc_xyz, cfg->n_pos_enc_dir, cfg->hidden_dim,
                     cfg->last_hidden_dim);
     if (cfg->precision != NERF_PRECISION_FP32 && cfg->precision != NERF_PRECISION_F16X3 &&
-        cfg->precision != NERF_PRECISION_F16)
-        return fail("unknown precision %d (NERF_PRECISION_FP32 = 0, NERF_PRECISION_F16X3 = 1, NERF_PRECISION_F16 = 2)",
-                    cfg->precision);
+        cfg->precision != NERF_PRECISION_F16 && cfg->precision != NERF_PRECISION_BF16X3)
+        return fail("unknown precision %d (NERF_PRECISION_FP32 = 0, NERF_PRECISION_F16X3 = 1, NERF_PRECISION_F16 = 2, "
+                    "NERF_PRECISION_BF16X3 = 3)", cfg->precision);
     return 0;
 }
 
-// can network `which` run the sigma-only kernel (launch_mlp_f16x3_sig)?  f16x3 precision, the kLx build, n_angles 1 or 2
+// can network `which` run the sigma-only kernel (launch_mlp_f16x3_sig / launch_mlp_bf16x3_sig)?  f16x3 or bf16x3
+// precision, the kLx build, n_angles 1 or 2
 bool sigma_only_ok(const nerf_ctx* c, int which) {
-    return c->cfg.precision == NERF_PRECISION_F16X3 && c->cfg.n_pos_enc_xyz <= kLx && c->cfg.n_angles != 0 &&
-           c->net[which].stream_hs != nullptr;
+    if (c->cfg.n_pos_enc_xyz > kLx || c->cfg.n_angles == 0) return false;
+    if (c->cfg.precision == NERF_PRECISION_BF16X3) return c->net[which].stream_bs != nullptr;
+    return c->cfg.precision == NERF_PRECISION_F16X3 && c->net[which].stream_hs != nullptr;
 }
 
 // record the MLP launch between two events when timing is on
@@ -238,9 +257,11 @@ int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const 
     if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
     if (int r = train_flush_weights(c, which)) return r;   // re-pack the operand streams after optimizer steps
     if (sigma_only && !sigma_only_ok(c, which)) return fail("internal: network %d has no sigma-only kernel", which);
-    const bool f16 = c->cfg.precision == NERF_PRECISION_F16X3 || c->cfg.precision == NERF_PRECISION_F16;
+    const bool bf = c->cfg.precision == NERF_PRECISION_BF16X3;
+    const bool f16 = c->cfg.precision == NERF_PRECISION_F16X3 || c->cfg.precision == NERF_PRECISION_F16 || bf;   // 16-bit streams, cst_h
     MlpArgs a{};
-    a.wstream = sigma_only ? (const float*)c->net[which].stream_hs
+    a.wstream = bf ? (const float*)(sigma_only ? c->net[which].stream_bs : c->net[which].stream_b)
+                : sigma_only ? (const float*)c->net[which].stream_hs
                 : c->cfg.precision == NERF_PRECISION_F16 ? (const float*)c->net[which].stream_h1
                 : f16 ? (const float*)c->net[which].stream_h : c->net[which].stream;
     a.wconst = f16 ? c->net[which].cst_h : c->net[which].cst;
@@ -263,10 +284,16 @@ int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const 
     // single-pass mode: two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the
     // one-tile kernel; the xyz-only network has the one-tile variant only
     static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
-    if (sigma_only) launch_mlp_f16x3_sig(a, c->num_cus, c->stream);
+    if (bf) {
+        // 3-pass split-bf16 kernels (mlp_bf16x3.hip; Lx 6..10: mlp_bf16x3_wide.hip)
+        if (!a.wstream) return fail("internal: network %d has no bf16 stream", which);
+        if (sigma_only) bf16::launch_mlp_bf16x3_sig(a, c->num_cus, c->stream);
+        else if (c->cfg.n_pos_enc_xyz > kLx) bf16::wide::launch_mlp_bf16x3(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
+        else bf16::launch_mlp_bf16x3(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
+    } else if (sigma_only) launch_mlp_f16x3_sig(a, c->num_cus, c->stream);
     else if (c->cfg.n_pos_enc_xyz > kLx) {
         // wide-PE network: the 3-pass or the one-tile single-pass kernel of the wide-PE build (no fp32 kernel, check_cfg)
-        if (!f16) return fail("n_pos_enc_dim_xyz %d: no exact-fp32 kernel (precision f16x3 or f16)", c->cfg.n_pos_enc_xyz);
+        if (!f16) return fail("n_pos_enc_dim_xyz %d: no exact-fp32 kernel (precision f16x3, bf16x3 or f16)", c->cfg.n_pos_enc_xyz);
         wide::launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
     } else if (c->cfg.precision == NERF_PRECISION_F16 && c->cfg.n_angles != 0 && !one_tile) launch_mlp_f16_2t(a, c->num_cus, c->stream);
     else if (f16) launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
@@ -407,7 +434,7 @@ int nerf_ctx_create(const nerf_config* cfg, nerf_ctx** out) {
     *out = nullptr;
     if (int r = check_cfg(cfg)) return r;
     if (cfg->n_pos_enc_xyz > kLx && cfg->precision == NERF_PRECISION_FP32)
-        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the fp16-core kernels only: precision f16x3 or f16, not fp32",
+        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
                     cfg->n_pos_enc_xyz, kLx);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -435,6 +462,8 @@ int nerf_ctx_create(const nerf_config* cfg, nerf_ctx** out) {
     mlp_fp32_set_attributes();
     mlp_f16x3_set_attributes();
     wide::mlp_f16x3_set_attributes();
+    bf16::mlp_bf16x3_set_attributes();
+    bf16::wide::mlp_bf16x3_set_attributes();
     mlp_bwd_f16x3_set_attributes();
     mlp_f16_2t_set_attributes();
     *out = c;
@@ -455,6 +484,8 @@ void nerf_ctx_destroy(nerf_ctx* c) {
         if (n.stream_h) (void)hipFree(n.stream_h);
         if (n.stream_h1) (void)hipFree(n.stream_h1);
         if (n.stream_hs) (void)hipFree(n.stream_hs);
+        if (n.stream_b) (void)hipFree(n.stream_b);
+        if (n.stream_bs) (void)hipFree(n.stream_bs);
         if (n.cst_h) (void)hipFree(n.cst_h);
     }
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -488,10 +519,11 @@ int nerf_ctx_set_bounds(nerf_ctx* c, float near_b, float far_b) {
 
 int nerf_ctx_set_precision(nerf_ctx* c, int precision) {
     if (!c) return fail("ctx is NULL");
-    if (precision != NERF_PRECISION_FP32 && precision != NERF_PRECISION_F16X3 && precision != NERF_PRECISION_F16)
+    if (precision != NERF_PRECISION_FP32 && precision != NERF_PRECISION_F16X3 && precision != NERF_PRECISION_F16 &&
+        precision != NERF_PRECISION_BF16X3)
         return fail("unknown precision %d", precision);
     if (c->cfg.n_pos_enc_xyz > kLx && precision == NERF_PRECISION_FP32)
-        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the fp16-core kernels only: precision f16x3 or f16, not fp32",
+        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
                     c->cfg.n_pos_enc_xyz, kLx);
     HIP_OK(hipStreamSynchronize(c->stream));
     c->cfg.precision = precision;

@@ -126,6 +126,23 @@ void mlp_f16x3_set_attributes();
 void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out);
 void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out);
 }  // namespace wide
+// mlp_bf16x3.hip / mlp_bf16x3_wide.hip -- the bf16 build of mlp_f16x3.hip's 3-pass RENDER kernels (NERF_PRECISION_BF16X3):
+// bf16 hi/lo streams of the same geometry (kStreamBytesF16 / kStreamBytesF16Xyz / kStreamBytesF16Sig), the constants of
+// pack_weights_f16x3.  No single-pass and no stash variant.  The device re-pack reads build_f16x3_gather's /
+// build_f16x3_sig_gather's stream tables (same slots) and rounds to bf16.
+namespace bf16 {
+void launch_mlp_bf16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only = false);
+void launch_mlp_bf16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream);      // the kLx build only, as the fp16 one
+void mlp_bf16x3_set_attributes();
+void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
+void pack_weights_bf16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
+void launch_repack_bf16x3(const float* blob, const int32_t* stream_idx, void* stream, size_t stream_bytes, hipStream_t s);
+namespace wide {
+void launch_mlp_bf16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only = false);
+void mlp_bf16x3_set_attributes();
+void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out);
+}  // namespace wide
+}  // namespace bf16
 // the octaves of the blob layout the kernels of an (lx, .) network are packed for: kLx, or kLxWide for lx > kLx
 inline int pe_layout_lx(int lx) { return lx > kLx ? kLxWide : kLx; }
 

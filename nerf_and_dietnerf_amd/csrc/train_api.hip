@@ -1179,9 +1179,12 @@ int train_flush_weights(nerf_ctx* c, int which, bool to_host) {
         const int na = c->cfg.n_angles;
         launch_repack_f16x3(n.blob, t->rt_h, nw.stream_h, t->rt_ch, nw.cst_h, f16_stream_bytes(na, false), c->stream);
         launch_repack_f16x3(n.blob, t->rt_h1, nw.stream_h1, t->rt_ch, nw.cst_h, f16_stream_bytes(na, true), c->stream);
+        // the bf16 hi/lo streams (NERF_PRECISION_BF16X3): the same slots as the fp16 3-pass streams, hence the same tables
+        if (nw.stream_b) bf16::launch_repack_bf16x3(n.blob, t->rt_h, nw.stream_b, f16_stream_bytes(na, false), c->stream);
         if (nw.stream_hs) {
             if (!t->rt_hs) return fail("internal: no gather table for the sigma-only stream");
             launch_repack_f16x3(n.blob, t->rt_hs, nw.stream_hs, t->rt_ch, nw.cst_h, kStreamBytesF16Sig, c->stream);
+            if (nw.stream_bs) bf16::launch_repack_bf16x3(n.blob, t->rt_hs, nw.stream_bs, kStreamBytesF16Sig, c->stream);
         }
         if (t->rt_f) {
             launch_gather_blob(n.blob, t->rt_f, nw.stream, (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4, c->stream);

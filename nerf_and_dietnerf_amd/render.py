@@ -42,7 +42,7 @@ N_COLOR_CHANNELS = 3
 # "auto": render in f16x3 (fp32-class results at 3x the exact-fp32 rate), watch the library's non-finite counter, and fall
 # back to exact fp32 for a weight set whose activations leave the fp16 range (Context._auto_call)
 _PRECISIONS = {"fp32": NERF_PRECISION_FP32, "f16x3": NERF_PRECISION_F16X3, "f16": _lib.NERF_PRECISION_F16,
-               "auto": NERF_PRECISION_F16X3}
+               "bf16x3": _lib.NERF_PRECISION_BF16X3, "auto": NERF_PRECISION_F16X3}
 
 
 # --------------------------------------------------------------------------------------------
@@ -202,9 +202,11 @@ class Context:
 
     def __init__(self, *, n_pos_enc_xyz=5, n_pos_enc_dir=4, n_angles=2, hidden_dim=256, last_hidden_dim=128,
                  leaky_relu_alpha=0.05, near=2.0, far=6.0, precision="auto", device=0):
-        """``precision``: "auto" (default: f16x3 with the exact-fp32 fallback below), "fp32" (exact fp32 MFMA: the parity
-        mode), "f16x3" (3-pass split-fp16 MFMA, fp32-class results while |activations| < 65504), "f16" (single-pass fp16:
-        the numerics class of the reference's mixed_float16 policy)."""
+        """``precision``: "auto" (default: f16x3 with the fallback below -- to exact fp32, or to bf16x3 for a network with
+        n_pos_enc_xyz 6..10, which has no exact-fp32 kernel), "fp32" (exact fp32 MFMA: the parity mode), "f16x3" (3-pass
+        split-fp16 MFMA, fp32-class results while |activations| < 65504), "bf16x3" (3-pass split-bf16 MFMA: fp32-class
+        results, 1e-4 RGB, with fp32's exponent range; render path only), "f16" (single-pass fp16: the numerics class of
+        the reference's mixed_float16 policy)."""
         self.lib = _lib.load()
         if n_angles not in (0, 1, 2):
             raise Exception(f"{N_ANGLES_FOR_MODEL} should be 1 or 2.")   # src/UtilsCV.py:138
@@ -218,7 +220,7 @@ class Context:
         self._stream = None
         self.comm_world = 0          # ranks of this ctx's in-library communicator (0 = none)
         self.precision = precision
-        self._auto_fp32 = False      # "auto": this weight set overflowed fp16 once -> exact fp32 until the weights change
+        self._auto_fp32 = False      # "auto": this weight set overflowed fp16 once -> exact fp32 (n_pos_enc_xyz 6..10: bf16x3) until the weights change
         self._auto_unchecked = False  # "auto": device-resident calls since the last look at the counter
         self.auto_fallbacks = 0      # "auto": calls that were re-rendered in exact fp32
         self._slot_fine = {}         # train_render_forward slots that ran a fine pass
@@ -254,12 +256,13 @@ class Context:
         self.cfg.near_boundary, self.cfg.far_boundary = near, far
 
     def set_precision(self, precision: str) -> None:
-        """"auto", "fp32" (exact fp32 MFMA), "f16x3" (3-pass split-fp16 MFMA, fp32 accumulate) or "f16"."""
+        """"auto", "fp32" (exact fp32 MFMA), "f16x3" (3-pass split-fp16 MFMA, fp32 accumulate), "bf16x3" (3-pass split-bf16
+        MFMA, fp32 accumulate: fp32's range) or "f16".  Works at any time: every mode's operand streams stay resident."""
         _lib.check(self.lib.nerf_ctx_set_precision(self.h, _PRECISIONS[precision]))
         self.cfg.precision = _PRECISIONS[precision]
         self.precision, self._auto_fp32, self._auto_unchecked = precision, False, False
 
-    # ---- precision="auto": f16x3 by default, exact fp32 for a weight set that needs it ----
+    # ---- precision="auto": f16x3 by default, exact fp32 (n_pos_enc_xyz 6..10: bf16x3) for a weight set that needs it ----
     def _auto_new_weights(self) -> None:
         """The fallback is per weight set (src/NeRF.py:190-246 renders whatever the model holds): new weights try f16x3 again."""
         if self.precision == "auto" and self._auto_fp32:
@@ -267,15 +270,17 @@ class Context:
             self.cfg.precision, self._auto_fp32 = NERF_PRECISION_F16X3, False
 
     def _auto_to_fp32(self) -> None:
-        _lib.check(self.lib.nerf_ctx_set_precision(self.h, NERF_PRECISION_FP32))
-        self.cfg.precision, self._auto_fp32, self._auto_unchecked = NERF_PRECISION_FP32, True, False
+        # the wide-PE networks (n_pos_enc_xyz 6..10) have no exact-fp32 kernel: their fallback is the bf16x3 mode
+        to = NERF_PRECISION_FP32 if self.cfg.n_pos_enc_xyz <= 5 else _lib.NERF_PRECISION_BF16X3
+        _lib.check(self.lib.nerf_ctx_set_precision(self.h, to))
+        self.cfg.precision, self._auto_fp32, self._auto_unchecked = to, True, False
 
     def _auto_call(self, call, mem):
         """Run ``call`` (one path function that evaluates a network).  Under precision="auto" a host-memory call -- which
         is synchronous on return anyway -- then reads the library's non-finite counter (a device counter the fused kernels
         add to: one 8-byte copy, no extra synchronisation); a non-zero count means activations left the fp16 range in the
-        f16x3 kernels, so the call is repeated in exact fp32 (same draws: same seed) and the context stays there until
-        its weights change.  Device-resident calls are asynchronous and are NOT checked one by one (that would drain the
+        f16x3 kernels, so the call is repeated in exact fp32 (bf16x3 for n_pos_enc_xyz 6..10; same draws: same seed) and the
+        context stays there until its weights change.  Device-resident calls are asynchronous and are NOT checked one by one (that would drain the
         queue per call): ``auto_check()`` looks at the counter when the caller synchronises (video.render_video does)."""
         out = call()
         if self.precision != "auto" or self._auto_fp32:
@@ -314,7 +319,7 @@ class Context:
 
     def read_nonfinite(self) -> int:
         """Rows with a non-finite network output since the last call (synchronises).  Non-zero in the
-        f16x3 mode means activations left the fp16 range: use precision="fp32" for this model."""
+        f16x3 mode means activations left the fp16 range: use precision="bf16x3" or "fp32" for this model."""
         n = C.c_int64()
         _lib.check(self.lib.nerf_ctx_read_nonfinite(self.h, C.byref(n)))
         return n.value
@@ -704,7 +709,10 @@ class NetHandle:
 
 
 class NeRF:
-    """Mirror of the reference model class (src/NeRF.py:22-246): render path and train_step."""
+    """Mirror of the reference model class (src/NeRF.py:22-246): render path and train_step.
+
+    ``precision`` is the render path's arithmetic (``Context``): "auto" (default), "fp32", "f16x3", "bf16x3" (3-pass
+    split-bf16 MFMA: fp32-class results with fp32's exponent range) or "f16".  train_step does not depend on it."""
 
     def __init__(self, net_config: Dict, render_config: Dict, near_boundary: float, far_boundary: float,
                  device: int = 0, precision: str = "auto"):
