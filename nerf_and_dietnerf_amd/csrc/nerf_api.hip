@@ -130,91 +130,26 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
         for (size_t i = 0; i < idx.size(); ++i) spread[i] = idx[i] ? blob_in[idx[i] - 1] : 0.f;
         blob = spread.data();
     }
-    if (L != kLx) {
-        // wide-PE network: the two fp16 streams (3-pass, hi-only) and their constants; there is no exact-fp32 kernel
-        const bool xyz = c->cfg.n_angles == 0;
-        const size_t b3 = xyz ? kStreamBytesF16Xyz : kStreamBytesF16, b1 = xyz ? kStreamBytesF16HiXyz : kStreamBytesF16Hi;
-        std::vector<uint16_t> s3(b3 / 2), s1(b1 / 2);
-        std::vector<float> cst(kConstFloats);
-        wide::pack_weights_f16x3(blob, c->cfg.n_angles, s3.data(), cst.data());
-        wide::pack_weights_f16(blob, c->cfg.n_angles, s1.data(), cst.data());
-        std::vector<uint16_t> sb(b3 / 2);
-        std::vector<float> cb(kConstFloats);
-        bf16::wide::pack_weights_bf16x3(blob, c->cfg.n_angles, sb.data(), cb.data());       // (cb == cst: fp32 constants)
-        if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, b3));
-        if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, b3));
-        if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, b1));
-        if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipMemcpy(n.stream_h, s3.data(), b3, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.stream_b, sb.data(), b3, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.stream_h1, s1.data(), b1, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.cst_h, cst.data(), kConstBytes, hipMemcpyHostToDevice));
-        const size_t nfw = nerf_blob_size(&c->cfg);
-        if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nfw);
-        n.loaded = true;
-        return 0;
+    // pack and upload every stream the table lists for this network; the stream is drained once, before the first copy (a
+    // running kernel may still read the old weights), and the copies block: the host buffers die with this call
+    StreamDesc d[kStreamKinds];
+    render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, which, d);
+    std::vector<float> cst[kConstBlocks];
+    bool drained = false;
+    for (int k = 0; k < kStreamKinds; ++k) {
+        if (!d[k].bytes) continue;
+        std::vector<char> host(d[k].bytes);
+        cst[d[k].cst].resize(kConstFloats);
+        d[k].pack(blob, c->cfg.n_angles, host.data(), cst[d[k].cst].data());
+        if (!n.stream[k]) HIP_OK(hipMalloc(&n.stream[k], d[k].bytes));
+        if (!drained) HIP_OK(hipStreamSynchronize(c->stream));
+        drained = true;
+        HIP_OK(hipMemcpy(n.stream[k], host.data(), d[k].bytes, hipMemcpyHostToDevice));
     }
-    if (c->cfg.n_angles == 0) {
-        // xyz-only network: all three arithmetic modes run on the fused kernels' xyz-only variants, each with its own
-        // stream and constant layout
-        std::vector<uint16_t> sx(kStreamBytesF16Xyz / 2), sx1(kStreamBytesF16HiXyz / 2);
-        std::vector<float> cx(kConstFloats), sf(kStreamBytesXyzF32 / 4), cf(kConstFloats);
-        pack_weights_f16x3(blob, 0, sx.data(), cx.data());
-        pack_weights_f16(blob, 0, sx1.data(), cx.data());
-        pack_weights_fp32(blob, 0, sf.data(), cf.data());
-        std::vector<uint16_t> sbx(kStreamBytesF16Xyz / 2);
-        std::vector<float> cbx(kConstFloats);
-        bf16::pack_weights_bf16x3(blob, 0, sbx.data(), cbx.data());                         // (cbx == cx: fp32 constants)
-        if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, kStreamBytesF16Xyz));
-        if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, kStreamBytesF16Xyz));
-        if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16HiXyz));
-        if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
-        if (!n.stream) HIP_OK(hipMalloc((void**)&n.stream, kStreamBytesXyzF32));
-        if (!n.cst) HIP_OK(hipMalloc((void**)&n.cst, kConstBytes));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipMemcpy(n.stream, sf.data(), kStreamBytesXyzF32, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.cst, cf.data(), kConstBytes, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.stream_h, sx.data(), kStreamBytesF16Xyz, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.stream_b, sbx.data(), kStreamBytesF16Xyz, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.stream_h1, sx1.data(), kStreamBytesF16HiXyz, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(n.cst_h, cx.data(), kConstBytes, hipMemcpyHostToDevice));
-        const size_t nf0 = nerf_blob_size(&c->cfg);
-        if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf0);
-        n.loaded = true;
-        return 0;
-    }
-    std::vector<float> st(kStreamBytes / 4), cs(kConstFloats);
-    pack_weights_fp32(blob, c->cfg.n_angles, st.data(), cs.data());
-    if (!n.stream) HIP_OK(hipMalloc((void**)&n.stream, kStreamBytes));
-    if (!n.cst) HIP_OK(hipMalloc((void**)&n.cst, kConstBytes));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(n.stream, st.data(), kStreamBytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(n.cst, cs.data(), kConstBytes, hipMemcpyHostToDevice));
-    // both operand formats are kept resident (2 x 2.1 MB per network) so precision can be switched per call
-    std::vector<uint16_t> sth(kStreamBytesF16 / 2);
-    std::vector<float> csh(kConstFloats);
-    pack_weights_f16x3(blob, c->cfg.n_angles, sth.data(), csh.data());
-    if (!n.stream_h) HIP_OK(hipMalloc((void**)&n.stream_h, kStreamBytesF16));
-    if (!n.cst_h) HIP_OK(hipMalloc((void**)&n.cst_h, kConstBytes));
-    HIP_OK(hipMemcpy(n.stream_h, sth.data(), kStreamBytesF16, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(n.cst_h, csh.data(), kConstBytes, hipMemcpyHostToDevice));
-    std::vector<uint16_t> sth1(kStreamBytesF16Hi / 2);
-    pack_weights_f16(blob, c->cfg.n_angles, sth1.data(), csh.data());       // same constants as the 3-pass stream
-    if (!n.stream_h1) HIP_OK(hipMalloc((void**)&n.stream_h1, kStreamBytesF16Hi));
-    HIP_OK(hipMemcpy(n.stream_h1, sth1.data(), kStreamBytesF16Hi, hipMemcpyHostToDevice));
-    // the bf16 hi/lo stream of NERF_PRECISION_BF16X3 (same geometry; its constants are the fp32 ones of cst_h)
-    bf16::pack_weights_bf16x3(blob, c->cfg.n_angles, sth.data(), csh.data());
-    if (!n.stream_b) HIP_OK(hipMalloc((void**)&n.stream_b, kStreamBytesF16));
-    HIP_OK(hipMemcpy(n.stream_b, sth.data(), kStreamBytesF16, hipMemcpyHostToDevice));
-    if (which == NERF_NET_COARSE) {      // the coarse pass of a render reads the weights only: sigma-only stream (dev_render)
-        std::vector<uint16_t> sths(kStreamBytesF16Sig / 2);
-        pack_weights_f16x3_sig(blob, c->cfg.n_angles, sths.data(), csh.data());
-        if (!n.stream_hs) HIP_OK(hipMalloc((void**)&n.stream_hs, kStreamBytesF16Sig));
-        HIP_OK(hipMemcpy(n.stream_hs, sths.data(), kStreamBytesF16Sig, hipMemcpyHostToDevice));
-        bf16::pack_weights_bf16x3_sig(blob, c->cfg.n_angles, sths.data(), csh.data());
-        if (!n.stream_bs) HIP_OK(hipMalloc((void**)&n.stream_bs, kStreamBytesF16Sig));
-        HIP_OK(hipMemcpy(n.stream_bs, sths.data(), kStreamBytesF16Sig, hipMemcpyHostToDevice));
+    for (int b = 0; b < kConstBlocks; ++b) {
+        if (cst[b].empty()) continue;
+        if (!n.cst[b]) HIP_OK(hipMalloc((void**)&n.cst[b], kConstBytes));
+        HIP_OK(hipMemcpy(n.cst[b], cst[b].data(), kConstBytes, hipMemcpyHostToDevice));
     }
     const size_t nf = nerf_blob_size(&c->cfg);
     if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf);
@@ -226,6 +161,49 @@ int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
 
 namespace {
 
+// The kernel that renders a network of `cfg` in `precision`: its operand stream, its constant block and its launcher.
+// want_sigma asks for the sigma-only kernel (f16x3 / bf16x3, the kLx build, n_angles 1 or 2; the coarse network alone keeps its
+// stream); sigma_only says whether that is what came back: raw then receives sigma alone, (M,) floats.
+struct RenderKernel {
+    StreamKind stream;
+    ConstBlock cst;
+    void (*launch)(const MlpArgs& a, int num_cus, hipStream_t s, bool xyz_only);
+    bool sigma_only;
+};
+// -> 0; 1: the config has no kernel of that precision; 2: no such precision (nerf_last_error() says which, either way)
+int pick_render_kernel(const nerf_config& cfg, int precision, bool want_sigma, RenderKernel* k) {
+    const bool wide_pe = cfg.n_pos_enc_xyz > kLx, sig = want_sigma && !wide_pe && cfg.n_angles != 0;
+    switch (precision) {
+    case NERF_PRECISION_FP32:
+        if (wide_pe)
+            return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
+                        cfg.n_pos_enc_xyz, kLx);
+        *k = {kFp32, kConstFp32, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_fp32(a, n, s, x); }, false};
+        return 0;
+    case NERF_PRECISION_F16X3:
+        if (sig) *k = {kF16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { launch_mlp_f16x3_sig(a, n, s); }, true};
+        else if (wide_pe) *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { wide::launch_mlp_f16x3(a, n, s, false, x); }, false};
+        else *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_f16x3(a, n, s, false, x); }, false};
+        return 0;
+    case NERF_PRECISION_F16: {
+        // two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the one-tile kernel;
+        // the xyz-only network and the wide-PE build have the one-tile variant only
+        static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
+        if (wide_pe) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { wide::launch_mlp_f16x3(a, n, s, true, x); }, false};
+        else if (cfg.n_angles != 0 && !one_tile) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { launch_mlp_f16_2t(a, n, s); }, false};
+        else *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_f16x3(a, n, s, true, x); }, false};
+        return 0;
+    }
+    case NERF_PRECISION_BF16X3:
+        if (sig) *k = {kBf16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { bf16::launch_mlp_bf16x3_sig(a, n, s); }, true};
+        else if (wide_pe) *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { bf16::wide::launch_mlp_bf16x3(a, n, s, x); }, false};
+        else *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { bf16::launch_mlp_bf16x3(a, n, s, x); }, false};
+        return 0;
+    }
+    fail("unknown precision %d", precision);
+    return 2;
+}
+
 int check_cfg(const nerf_config* cfg) {
     if (!cfg) return fail("nerf_config is NULL");
     if (cfg->n_angles != 2 && cfg->n_angles != 1 && cfg->n_angles != 0)
@@ -235,36 +213,22 @@ int check_cfg(const nerf_config* cfg) {
         return fail("supported networks: n_pos_enc_dim_xyz 1..%d, n_pos_enc_view_dir 1..%d, hidden %d, last hidden %d "
                     "(got %d %d %d %d)", kLxWide, kLd, kHidden, kLast, cfg->n_pos_enc_xyz, cfg->n_pos_enc_dir, cfg->hidden_dim,
                     cfg->last_hidden_dim);
-    if (cfg->precision != NERF_PRECISION_FP32 && cfg->precision != NERF_PRECISION_F16X3 &&
-        cfg->precision != NERF_PRECISION_F16 && cfg->precision != NERF_PRECISION_BF16X3)
+    RenderKernel k;      // a precision this config has no kernel for is nerf_ctx_create's to refuse: a blob still has a size
+    if (pick_render_kernel(*cfg, cfg->precision, false, &k) == 2)
         return fail("unknown precision %d (NERF_PRECISION_FP32 = 0, NERF_PRECISION_F16X3 = 1, NERF_PRECISION_F16 = 2, "
                     "NERF_PRECISION_BF16X3 = 3)", cfg->precision);
     return 0;
 }
 
-// can network `which` run the sigma-only kernel (launch_mlp_f16x3_sig / launch_mlp_bf16x3_sig)?  f16x3 or bf16x3
-// precision, the kLx build, n_angles 1 or 2
-bool sigma_only_ok(const nerf_ctx* c, int which) {
-    if (c->cfg.n_pos_enc_xyz > kLx || c->cfg.n_angles == 0) return false;
-    if (c->cfg.precision == NERF_PRECISION_BF16X3) return c->net[which].stream_bs != nullptr;
-    return c->cfg.precision == NERF_PRECISION_F16X3 && c->net[which].stream_hs != nullptr;
-}
-
 // record the MLP launch between two events when timing is on
-// sigma_only (sigma_only_ok): raw receives sigma alone, (M,) floats
-int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const float* z, float* raw, long long M,
-            int S, int mode, bool sigma_only = false) {
+int run_mlp(nerf_ctx* c, int which, const RenderKernel& k, const float* in_a, const float* in_b, const float* z, float* raw,
+            long long M, int S, int mode) {
     if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
     if (int r = train_flush_weights(c, which)) return r;   // re-pack the operand streams after optimizer steps
-    if (sigma_only && !sigma_only_ok(c, which)) return fail("internal: network %d has no sigma-only kernel", which);
-    const bool bf = c->cfg.precision == NERF_PRECISION_BF16X3;
-    const bool f16 = c->cfg.precision == NERF_PRECISION_F16X3 || c->cfg.precision == NERF_PRECISION_F16 || bf;   // 16-bit streams, cst_h
     MlpArgs a{};
-    a.wstream = bf ? (const float*)(sigma_only ? c->net[which].stream_bs : c->net[which].stream_b)
-                : sigma_only ? (const float*)c->net[which].stream_hs
-                : c->cfg.precision == NERF_PRECISION_F16 ? (const float*)c->net[which].stream_h1
-                : f16 ? (const float*)c->net[which].stream_h : c->net[which].stream;
-    a.wconst = f16 ? c->net[which].cst_h : c->net[which].cst;
+    a.wstream = (const float*)c->net[which].stream[k.stream];
+    a.wconst = c->net[which].cst[k.cst];
+    if (!a.wstream || !a.wconst) return fail("internal: network %d keeps no stream of kind %d", which, (int)k.stream);
     a.in_a = in_a; a.in_b = in_b; a.z = z; a.raw = raw; a.M = M; a.S = S; a.mode = mode;
     a.nonfinite = c->nonfinite;
     a.alpha = c->cfg.leaky_relu_alpha;
@@ -281,23 +245,7 @@ int run_mlp(nerf_ctx* c, int which, const float* in_a, const float* in_b, const 
         c->timed_rows += M;
         HIP_OK(hipEventRecord(e0, c->stream));
     }
-    // single-pass mode: two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the
-    // one-tile kernel; the xyz-only network has the one-tile variant only
-    static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
-    if (bf) {
-        // 3-pass split-bf16 kernels (mlp_bf16x3.hip; Lx 6..10: mlp_bf16x3_wide.hip)
-        if (!a.wstream) return fail("internal: network %d has no bf16 stream", which);
-        if (sigma_only) bf16::launch_mlp_bf16x3_sig(a, c->num_cus, c->stream);
-        else if (c->cfg.n_pos_enc_xyz > kLx) bf16::wide::launch_mlp_bf16x3(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
-        else bf16::launch_mlp_bf16x3(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
-    } else if (sigma_only) launch_mlp_f16x3_sig(a, c->num_cus, c->stream);
-    else if (c->cfg.n_pos_enc_xyz > kLx) {
-        // wide-PE network: the 3-pass or the one-tile single-pass kernel of the wide-PE build (no fp32 kernel, check_cfg)
-        if (!f16) return fail("n_pos_enc_dim_xyz %d: no exact-fp32 kernel (precision f16x3, bf16x3 or f16)", c->cfg.n_pos_enc_xyz);
-        wide::launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
-    } else if (c->cfg.precision == NERF_PRECISION_F16 && c->cfg.n_angles != 0 && !one_tile) launch_mlp_f16_2t(a, c->num_cus, c->stream);
-    else if (f16) launch_mlp_f16x3(a, c->num_cus, c->stream, c->cfg.precision == NERF_PRECISION_F16, c->cfg.n_angles == 0);
-    else launch_mlp_fp32(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
+    k.launch(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
     if (c->timing) HIP_OK(hipEventRecord(e1, c->stream));
     HIP_OK(hipGetLastError());
     return 0;
@@ -373,22 +321,24 @@ int copy_back_batch(nerf_ctx* c, const nerf_outputs* host, const nerf_outputs* d
 
 // render_rays on device pointers
 // A coarse pass whose only output is the weights (the coarse pass of NeRF.render) runs the sigma-only network and the
-// weights-only composite where sigma_only_ok: the weights depend on sigma alone and come out bit-identical.
+// weights-only composite where pick_render_kernel has one: the weights depend on sigma alone and come out bit-identical.
 int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, const float* z, long long N, int S,
                     const nerf_outputs& outs) {
     const bool weights_only = outs.weights && !outs.rgb && !outs.cumprod && !outs.alpha && !outs.rgb_samples && !outs.z &&
                               !outs.depth;
-    if (which == NERF_NET_COARSE && weights_only && sigma_only_ok(c, which)) {
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, which == NERF_NET_COARSE && weights_only, &k)) return 1;
+    if (k.sigma_only) {
         if (int r = ensure(c, c->b_raw, (size_t)N * S * sizeof(float))) return r;
         float* sigma = (float*)c->b_raw.p;
-        if (int r = run_mlp(c, which, o, d, z, sigma, N * S, S, 0, true)) return r;
+        if (int r = run_mlp(c, which, k, o, d, z, sigma, N * S, S, 0)) return r;
         launch_composite_weights(sigma, z, N, S, outs.weights, c->stream);
         HIP_OK(hipGetLastError());
         return 0;
     }
     if (int r = ensure(c, c->b_raw, (size_t)N * S * 4 * sizeof(float))) return r;
     float* raw = (float*)c->b_raw.p;
-    if (int r = run_mlp(c, which, o, d, z, raw, N * S, S, 0)) return r;
+    if (int r = run_mlp(c, which, k, o, d, z, raw, N * S, S, 0)) return r;
     launch_composite(raw, z, N, S, outs.rgb, outs.weights, outs.cumprod, outs.alpha, outs.rgb_samples, outs.depth,
                      c->stream);
     if (outs.z && outs.z != z)
@@ -433,9 +383,8 @@ int nerf_ctx_create(const nerf_config* cfg, nerf_ctx** out) {
     if (!out) return fail("out is NULL");
     *out = nullptr;
     if (int r = check_cfg(cfg)) return r;
-    if (cfg->n_pos_enc_xyz > kLx && cfg->precision == NERF_PRECISION_FP32)
-        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
-                    cfg->n_pos_enc_xyz, kLx);
+    RenderKernel k;
+    if (pick_render_kernel(*cfg, cfg->precision, false, &k)) return 1;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)
@@ -479,14 +428,8 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);
     for (auto& n : c->net) {
-        if (n.stream) (void)hipFree(n.stream);
-        if (n.cst) (void)hipFree(n.cst);
-        if (n.stream_h) (void)hipFree(n.stream_h);
-        if (n.stream_h1) (void)hipFree(n.stream_h1);
-        if (n.stream_hs) (void)hipFree(n.stream_hs);
-        if (n.stream_b) (void)hipFree(n.stream_b);
-        if (n.stream_bs) (void)hipFree(n.stream_bs);
-        if (n.cst_h) (void)hipFree(n.cst_h);
+        for (void* p : n.stream) if (p) (void)hipFree(p);
+        for (float* p : n.cst) if (p) (void)hipFree(p);
     }
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -519,12 +462,8 @@ int nerf_ctx_set_bounds(nerf_ctx* c, float near_b, float far_b) {
 
 int nerf_ctx_set_precision(nerf_ctx* c, int precision) {
     if (!c) return fail("ctx is NULL");
-    if (precision != NERF_PRECISION_FP32 && precision != NERF_PRECISION_F16X3 && precision != NERF_PRECISION_F16 &&
-        precision != NERF_PRECISION_BF16X3)
-        return fail("unknown precision %d", precision);
-    if (c->cfg.n_pos_enc_xyz > kLx && precision == NERF_PRECISION_FP32)
-        return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
-                    c->cfg.n_pos_enc_xyz, kLx);
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, precision, false, &k)) return 1;
     HIP_OK(hipStreamSynchronize(c->stream));
     c->cfg.precision = precision;
     return 0;
@@ -643,7 +582,9 @@ int nerf_model_predict(nerf_ctx* c, int which, const float* xyz, const float* vi
         if (int r = ensure(c, c->b_raw, (size_t)M * 16)) return r;
         dx = (const float*)c->b_in0.p; dv = view_dirs ? (const float*)c->b_in1.p : nullptr; dr = (float*)c->b_raw.p;
     }
-    if (int r = run_mlp(c, which, dx, dv, nullptr, dr, M, 1, 1)) return r;
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    if (int r = run_mlp(c, which, k, dx, dv, nullptr, dr, M, 1, 1)) return r;
     if (mem == NERF_MEM_HOST) {
         HIP_OK(hipMemcpyAsync(raw, dr, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));

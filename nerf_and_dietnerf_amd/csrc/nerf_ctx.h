@@ -26,14 +26,8 @@ struct DevBuf {
 };
 
 struct NetWeights {
-    float* stream = nullptr;     // kStreamBytes      (fp32 MFMA operand stream)
-    float* cst = nullptr;        // kConstBytes
-    void* stream_h = nullptr;    // kStreamBytesF16   (fp16 hi/lo fragment stream)
-    void* stream_h1 = nullptr;   // kStreamBytesF16Hi (fp16 hi-only stream of the single-pass mode)
-    void* stream_hs = nullptr;   // kStreamBytesF16Sig (sigma-only 3-pass stream: the coarse network of a (kLx, n_angles 1|2) config)
-    float* cst_h = nullptr;      // kConstBytes
-    void* stream_b = nullptr;    // bf16 hi/lo fragment stream of NERF_PRECISION_BF16X3 (size and slots of stream_h; constants: cst_h)
-    void* stream_bs = nullptr;   // ... and its sigma-only stream, where stream_hs exists
+    void* stream[kStreamKinds] = {};   // the operand streams render_streams() lists for this network (null: not kept)
+    float* cst[kConstBlocks] = {};     // kConstBytes each
     bool loaded = false;
     std::vector<float> host_blob;   // last blob handed to nerf_load_weights (Keras order): seed of the trainer
 };

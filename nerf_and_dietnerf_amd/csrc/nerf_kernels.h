@@ -146,6 +146,39 @@ void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, floa
 // the octaves of the blob layout the kernels of an (lx, .) network are packed for: kLx, or kLxWide for lx > kLx
 inline int pe_layout_lx(int lx) { return lx > kLx ? kLxWide : kLx; }
 
+// ---- the render path's resident operand streams, stated once ----
+// Upload (nerf_api.hip), kernel choice (pick_render_kernel), the device re-pack after optimizer steps (train_api.hip) and
+// the host-sanitizer tool (tools/pack_asan_test.cpp) all walk render_streams(); none of them names a stream on its own.
+enum StreamKind { kF16x3, kF16Hi, kBf16x3, kF16x3Sig, kBf16x3Sig, kFp32, kStreamKinds };   // in re-pack order
+enum ConstBlock { kConstFp32, kConst16, kConstBlocks };   // pack_weights_fp32's constants / the ones every 16-bit packer writes
+struct StreamDesc {
+    size_t bytes;        // 0: this network does not keep the stream
+    void (*pack)(const float* blob, int n_angles, void* stream_out /*bytes*/, float* const_out /*kConstFloats*/);
+    ConstBlock cst;      // the constant block the packer fills
+    StreamKind table;    // the kind whose gather table the device re-pack reads (the bf16 kinds: their fp16 twins', same slots)
+    bool bf16;           // ... and whether it rounds to bf16 (launch_repack_bf16x3) or to fp16 (launch_repack_f16x3)
+};
+// the streams network `which` (0 = coarse, 1 = fine) of an (lx, n_angles) config keeps.  Wide-PE networks (lx > kLx) have no
+// fp32 and no sigma-only streams; xyz-only networks the ...Xyz sizes and no sigma-only streams; sigma-only: the coarse network
+inline void render_streams(int lx, int n_angles, int which, StreamDesc d[kStreamKinds]) {
+    const bool wd = lx > kLx, xyz = n_angles == 0;
+    const size_t b3 = xyz ? kStreamBytesF16Xyz : kStreamBytesF16, b1 = xyz ? kStreamBytesF16HiXyz : kStreamBytesF16Hi;
+    const size_t bs = !wd && !xyz && which == 0 ? kStreamBytesF16Sig : 0, bf = wd ? 0 : xyz ? kStreamBytesXyzF32 : kStreamBytes;
+    d[kF16x3] = {b3, wd ? wide::pack_weights_f16x3 : pack_weights_f16x3, kConst16, kF16x3, false};
+    d[kF16Hi] = {b1, wd ? wide::pack_weights_f16 : pack_weights_f16, kConst16, kF16Hi, false};
+    d[kBf16x3] = {b3, wd ? bf16::wide::pack_weights_bf16x3 : bf16::pack_weights_bf16x3, kConst16, kF16x3, true};
+    d[kF16x3Sig] = {bs, pack_weights_f16x3_sig, kConst16, kF16x3Sig, false};
+    d[kBf16x3Sig] = {bs, bf16::pack_weights_bf16x3_sig, kConst16, kF16x3Sig, true};
+    d[kFp32] = {bf, [](const float* b, int na, void* s, float* c) { pack_weights_fp32(b, na, (float*)s, c); }, kConstFp32, kFp32, false};
+}
+// gather table (bytes / 2 entries) of a 16-bit kind that is its own table source; -> whether const_idx (kConstFloats entries,
+// the kConst16 block's: the same from every kind) was written too.  The fp32 kind's table is its packer run on an index blob.
+inline bool build_stream_gather(int lx, int n_angles, StreamKind k, int32_t* stream_idx, int32_t* const_idx) {
+    if (k == kF16x3Sig) { build_f16x3_sig_gather(n_angles, stream_idx); return false; }
+    (lx > kLx ? wide::build_f16x3_gather : build_f16x3_gather)(n_angles, k == kF16Hi, stream_idx, const_idx);
+    return true;
+}
+
 // mlp_f16_2t.hip -- single-pass fp16 render kernel with two 32-sample tiles per wave (same hi-only stream / constants)
 void launch_mlp_f16_2t(const MlpArgs& a, int num_cus, hipStream_t stream);
 void mlp_f16_2t_set_attributes();

@@ -105,12 +105,13 @@ struct TrainState {
     DevBuf macc;                    // running sums of the step metrics (4 doubles: loss, psnr_coarse, psnr_fine, steps)
     DevBuf gsave[2];                // ... under mixed_float16 with accumulate = 1: the (unscaled) gradients already there
     // A render between optimizer steps (DietNeRF's consistency render every 13th step, the epoch plots) needs the render
-    // path's three operand streams re-packed from the trained blob: on the DEVICE, by gather tables built once from the host
-    // packers (round 4; the device -> host -> pack x 3 -> device round trip this replaces cost ~30 ms and two synchronisations
-    // per render).  rt_h / rt_h1: build_f16x3_gather (3-pass / hi-only stream), rt_ch their constants; rt_f / rt_cf: the fp32
-    // stream and constants (pack_weights_fp32 only moves values: the table is the packed INDEX blob).  rt_hs: the coarse
-    // network's sigma-only stream (build_f16x3_sig_gather; constants rt_ch), where the render path has one.
-    int32_t *rt_h = nullptr, *rt_h1 = nullptr, *rt_ch = nullptr, *rt_f = nullptr, *rt_cf = nullptr, *rt_hs = nullptr;
+    // path's operand streams (nerf_kernels.h::render_streams) re-packed from the trained blob: on the DEVICE, by gather tables
+    // built once from the host packers (round 4; the device -> host -> pack x 3 -> device round trip this replaces cost ~30 ms
+    // and two synchronisations per render).  rt[k]: the table of stream kind k where k is its own table source (StreamDesc::
+    // table), rt_cst[b]: the table of constant block b.
+    int32_t* rt[kStreamKinds] = {};
+    int32_t* rt_cst[kConstBlocks] = {};
+    bool rt_built = false;
     std::vector<RenderSlot> slots;  // nerf_train_render_forward / _backward
 };
 
@@ -1086,8 +1087,8 @@ void train_free(nerf_ctx* c) {
         if (n.fcst) (void)hipFree(n.fcst);
         if (n.bstream) (void)hipFree(n.bstream);
     }
-    for (int32_t* p : {t->rt_h, t->rt_h1, t->rt_ch, t->rt_f, t->rt_cf, t->rt_hs})
-        if (p) (void)hipFree(p);
+    for (int32_t* p : t->rt) if (p) (void)hipFree(p);
+    for (int32_t* p : t->rt_cst) if (p) (void)hipFree(p);
     if (t->sidx) (void)hipFree(t->sidx);
     if (t->cidx) (void)hipFree(t->cidx);
     for (int32_t* bi : t->bidx) if (bi) (void)hipFree(bi);
@@ -1116,56 +1117,51 @@ int train_on_load(nerf_ctx* c, int which) {
     return relayout_net(c, n);
 }
 
-// gather tables of the render path's operand streams (see TrainState::rt_*)
+// gather tables of the render path's operand streams (see TrainState::rt): one for every kind either network keeps
 static int ensure_render_tables(nerf_ctx* c, TrainState* t) {
-    if (t->rt_h) return 0;
-    const int na = c->cfg.n_angles;
+    if (t->rt_built) return 0;
+    const int na = c->cfg.n_angles, lx = c->cfg.n_pos_enc_xyz;
     auto up = [&](const std::vector<int32_t>& v, int32_t** dst) -> int {
-        HIP_OK(hipMalloc((void**)dst, v.size() * sizeof(int32_t)));
+        if (!*dst) HIP_OK(hipMalloc((void**)dst, v.size() * sizeof(int32_t)));
         HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         return 0;
     };
-    std::vector<int32_t> h(f16_stream_bytes(na, false) / 2), h1(f16_stream_bytes(na, true) / 2), ch(kConstFloats),
-        ch1(kConstFloats);
-    const bool wide_pe = c->cfg.n_pos_enc_xyz > kLx;
-    (wide_pe ? wide::build_f16x3_gather : build_f16x3_gather)(na, false, h.data(), ch.data());
-    (wide_pe ? wide::build_f16x3_gather : build_f16x3_gather)(na, true, h1.data(), ch1.data());
-    if (ch != ch1) return fail("internal: the two fp16 streams disagree about their constants");
-    aim_gather(c->cfg, h.data(), h.size(), true);
-    aim_gather(c->cfg, h1.data(), h1.size(), true);
-    aim_gather(c->cfg, ch.data(), ch.size(), false);
-    if (wide_pe) {                           // no exact-fp32 render kernel (and no fp32 stream) for a wide-PE network
-        if (int r = up(h1, &t->rt_h1)) return r;
-        if (int r = up(ch, &t->rt_ch)) return r;
-        return up(h, &t->rt_h);
+    StreamDesc d[2][kStreamKinds];
+    for (int w = 0; w < 2; ++w) render_streams(lx, na, w, d[w]);
+    std::vector<int32_t> c16;                // the 16-bit kinds' constant table: every builder must give the same one
+    for (int k = 0; k < kStreamKinds; ++k) {
+        const size_t bytes = std::max(d[0][k].bytes, d[1][k].bytes);
+        if (!bytes || d[0][k].table != k) continue;
+        std::vector<int32_t> si(bytes / (k == kFp32 ? 4 : 2)), ci(kConstFloats);
+        if (k == kFp32) {
+            // pack a blob whose entry i holds i + 1 (exact in fp32: the blob has 5e5 entries) -- what lands in a slot is the
+            // 1-based index of the weight that belongs there, 0 where the packer pads.  The packer takes the (kLx, kLd)
+            // layout: its entry i holds the 1-based index of the trained blob's weight there, 0 for an octave row it does not have
+            std::vector<int32_t> wide(blob_floats(kLx, kLd, na));
+            for (size_t i = 0; i < wide.size(); ++i) wide[i] = (int32_t)(i + 1);
+            aim_gather(c->cfg, wide.data(), wide.size(), false);
+            std::vector<float> idx(wide.begin(), wide.end()), sf(si.size()), cf(kConstFloats);
+            d[0][k].pack(idx.data(), na, sf.data(), cf.data());
+            si.assign(sf.begin(), sf.end());
+            ci.assign(cf.begin(), cf.end());
+            if (int r = up(ci, &t->rt_cst[kConstFp32])) return r;
+        } else {
+            const bool has_cst = build_stream_gather(lx, na, (StreamKind)k, si.data(), ci.data());
+            aim_gather(c->cfg, si.data(), si.size(), true);
+            if (has_cst && !c16.empty() && ci != c16) return fail("internal: the two fp16 streams disagree about their constants");
+            if (has_cst && c16.empty()) {
+                c16 = ci;
+                aim_gather(c->cfg, ci.data(), ci.size(), false);
+                if (int r = up(ci, &t->rt_cst[kConst16])) return r;
+            }
+        }
+        if (int r = up(si, &t->rt[k])) return r;
     }
-    // fp32 stream: pack a blob whose entry i holds i + 1 (exact in fp32: the blob has 5e5 entries) -- what lands in a slot
-    // is the 1-based index of the weight that belongs there, 0 where the packer pads.  The packer takes the (kLx, kLd)
-    // layout: its entry i holds the 1-based index of the trained blob's weight there, 0 for an octave row it does not have
-    const size_t nf = (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4;
-    std::vector<int32_t> wide(blob_floats(kLx, kLd, na));
-    for (size_t i = 0; i < wide.size(); ++i) wide[i] = (int32_t)(i + 1);
-    aim_gather(c->cfg, wide.data(), wide.size(), false);
-    std::vector<float> idx(wide.size()), sf(nf), cf(kConstFloats);
-    for (size_t i = 0; i < wide.size(); ++i) idx[i] = (float)wide[i];
-    pack_weights_fp32(idx.data(), na, sf.data(), cf.data());
-    std::vector<int32_t> f(nf), cfi(kConstFloats);
-    for (size_t i = 0; i < nf; ++i) f[i] = (int32_t)sf[i];
-    for (size_t i = 0; i < (size_t)kConstFloats; ++i) cfi[i] = (int32_t)cf[i];
-    if (na != 0) {
-        std::vector<int32_t> hs(kStreamBytesF16Sig / 2);
-        build_f16x3_sig_gather(na, hs.data());
-        aim_gather(c->cfg, hs.data(), hs.size(), true);
-        if (int r = up(hs, &t->rt_hs)) return r;
-    }
-    if (int r = up(h1, &t->rt_h1)) return r;
-    if (int r = up(ch, &t->rt_ch)) return r;
-    if (int r = up(f, &t->rt_f)) return r;
-    if (int r = up(cfi, &t->rt_cf)) return r;
-    return up(h, &t->rt_h);                  // last: rt_h != nullptr means all five (wide-PE: three) exist
+    t->rt_built = true;
+    return 0;
 }
 
-// The render path's view of a network that is being trained.  After optimizer steps its three operand streams are
+// The render path's view of a network that is being trained.  After optimizer steps its operand streams are
 // re-packed from the trained blob on the device (enqueued on the ctx stream: a render between steps does not synchronise);
 // to_host additionally brings NetWeights::host_blob up to date (nerf_train_end, a restarting nerf_train_begin: the next
 // trainer starts from it).
@@ -1176,19 +1172,17 @@ int train_flush_weights(nerf_ctx* c, int which, bool to_host) {
     NetWeights& nw = c->net[which];
     if (n.render_dirty) {
         if (int r = ensure_render_tables(c, t)) return r;
-        const int na = c->cfg.n_angles;
-        launch_repack_f16x3(n.blob, t->rt_h, nw.stream_h, t->rt_ch, nw.cst_h, f16_stream_bytes(na, false), c->stream);
-        launch_repack_f16x3(n.blob, t->rt_h1, nw.stream_h1, t->rt_ch, nw.cst_h, f16_stream_bytes(na, true), c->stream);
-        // the bf16 hi/lo streams (NERF_PRECISION_BF16X3): the same slots as the fp16 3-pass streams, hence the same tables
-        if (nw.stream_b) bf16::launch_repack_bf16x3(n.blob, t->rt_h, nw.stream_b, f16_stream_bytes(na, false), c->stream);
-        if (nw.stream_hs) {
-            if (!t->rt_hs) return fail("internal: no gather table for the sigma-only stream");
-            launch_repack_f16x3(n.blob, t->rt_hs, nw.stream_hs, t->rt_ch, nw.cst_h, kStreamBytesF16Sig, c->stream);
-            if (nw.stream_bs) bf16::launch_repack_bf16x3(n.blob, t->rt_hs, nw.stream_bs, kStreamBytesF16Sig, c->stream);
-        }
-        if (t->rt_f) {
-            launch_gather_blob(n.blob, t->rt_f, nw.stream, (na == 0 ? kStreamBytesXyzF32 : kStreamBytes) / 4, c->stream);
-            launch_gather_blob(n.blob, t->rt_cf, nw.cst, kConstFloats, c->stream);
+        StreamDesc d[kStreamKinds];
+        render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, which, d);
+        for (int k = 0; k < kStreamKinds; ++k) {
+            if (!d[k].bytes) continue;
+            const int32_t *tab = t->rt[d[k].table], *ctab = t->rt_cst[d[k].cst];
+            if (!tab || !ctab || !nw.stream[k]) return fail("internal: no gather table for stream kind %d of network %d", k, which);
+            if (k == kFp32) {                // pack_weights_fp32 only moves values: plain gathers of stream and constants
+                launch_gather_blob(n.blob, tab, (float*)nw.stream[k], d[k].bytes / 4, c->stream);
+                launch_gather_blob(n.blob, ctab, nw.cst[d[k].cst], kConstFloats, c->stream);
+            } else if (d[k].bf16) bf16::launch_repack_bf16x3(n.blob, tab, nw.stream[k], d[k].bytes, c->stream);   // (constants: its fp16 twin's)
+            else launch_repack_f16x3(n.blob, tab, nw.stream[k], ctab, nw.cst[d[k].cst], d[k].bytes, c->stream);
         }
         HIP_OK(hipGetLastError());
         n.render_dirty = false;

@@ -225,6 +225,52 @@ def test_render_after_train_steps_matches_fresh_context(oracle, lx, ld, na, mixe
             fresh.close()
 
 
+@pytest.mark.parametrize("lx,na", [(5, 2), (5, 0), (7, 2), (7, 0)])
+def test_every_resident_stream_follows_reloads_and_train_steps(oracle, lx, na):
+    """One context, switched through every precision its config has a kernel for (fp32 only at Lx <= 5), renders the same
+    bits as a fresh context created in that precision: (a) after the first load_weights, (b) after a second load_weights
+    onto the streams already allocated, (c) after three train_steps (the device re-pack of every stream) and after a
+    load_weights under the running trainer.  67 rays x (12 coarse, 12 + 20 fine) samples: 804 and 2144 rows, a ragged last
+    128-row tile in both passes.  The four configs are the four classes csrc/nerf_kernels.h::render_streams tells apart."""
+    n, sc, sf = 67, 12, 20
+    o, d, rng = B.rays(n, seed=21)
+    tgt = rng.random((n, 3), dtype=np.float32)
+    u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
+    precisions = (["fp32"] if lx <= 5 else []) + ["f16x3", "f16", "bf16x3"]
+
+    def check(ctx, pair, label):
+        for p in precisions:
+            ctx.set_precision(p)
+            got = ctx.render(o, d, sc, sf, u_c, u_f)
+            fresh = _context(pair, lx, 4, na, precision=p)
+            try:
+                want = fresh.render(o, d, sc, sf, u_c, u_f)
+            finally:
+                fresh.close()
+            for i, (a, b) in enumerate(zip(got, want)):
+                np.testing.assert_array_equal(a, b, err_msg=f"{label}, {p}, output {i}")
+
+    first, second, third = (B.blobs(lx, 4, na, seed=s) for s in (11, 31, 51))
+    ctx = _context(first, lx, 4, na, precision=precisions[0])
+    try:
+        check(ctx, first, "(a) first load")
+        for which, blob in enumerate(second):
+            ctx.load_weights(which, blob)
+        check(ctx, second, "(b) second load")
+        ctx.train_begin(5e-4)
+        for _ in range(3):
+            ctx.train_step(o, d, tgt, sc, sf, u_c, u_f)
+        trained = (ctx.get_weights(0), ctx.get_weights(1))
+        assert np.count_nonzero(trained[0] != second[0]) > 0 and np.count_nonzero(trained[1] != second[1]) > 0
+        check(ctx, trained, "(c) after three train steps")
+        for which, blob in enumerate(third):
+            ctx.load_weights(which, blob)
+        check(ctx, third, "(c) load under the running trainer")
+        ctx.train_end()
+    finally:
+        ctx.close()
+
+
 # ---- 6. precision="auto" on a wide network ----
 def test_auto_falls_back_to_bf16x3_on_a_wide_network(oracle, golden_ckpt):
     """Lx 10 has no exact-fp32 kernel: under precision="auto" a weight set that leaves the fp16 range is re-rendered in
