@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* 6 also covers the forward-facing-scene entries added after it (nerf_ctx_set_sampling, nerf_ctx_set_ray_space,
+ * nerf_rays_to_ndc; marked "ABI 6+" below): they are additive -- no existing entry, struct or default changes -- so the
+ * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
 enum { NERF_NET_COARSE = 0, NERF_NET_FINE = 1 };
@@ -43,6 +46,18 @@ enum {
     NERF_PRECISION_BF16X3 = 3  /* 3-pass split-bf16 MFMA (hi*hi + hi*lo + lo*hi), fp32 accumulate: ~16 significant bits per
                                   operand (fp32-class results, 1e-4 RGB) with fp32's exponent range -- nothing saturates at
                                   65504.  Render path only: the trainer's kernels do not depend on the ctx precision */
+};
+
+/* ABI 6+: where the coarse depths of a ray fall (nerf_ctx_set_sampling) */
+enum {
+    NERF_SAMPLING_LINEAR = 0,  /* stratified, uniform in depth between near and far: get_z_values, src/UtilsCV.py:565-581 */
+    NERF_SAMPLING_LINDISP = 1  /* stratified, uniform in DISPARITY 1/z ("lindisp"): half of the samples lie nearer than
+                                  2 near far / (near + far); for scenes whose content runs from ~1 unit to (almost) infinity */
+};
+/* ABI 6+: the space of the rays nerf_render_image generates from a camera (nerf_ctx_set_ray_space) */
+enum {
+    NERF_RAYS_WORLD = 0,       /* world-space pinhole rays: get_rays_directions, src/UtilsCV.py:467-499 */
+    NERF_RAYS_NDC = 1          /* the same rays re-parameterised in normalised device coordinates (see nerf_rays_to_ndc) */
 };
 
 /* Network + frustum description: the 9 net/render keys of src/ConfigurationKeys.py:64-111. */
@@ -91,6 +106,19 @@ int nerf_ctx_set_stream(nerf_ctx* ctx, void* hip_stream);
 /* change the frustum (near/far) or precision after creation */
 int nerf_ctx_set_bounds(nerf_ctx* ctx, float near_boundary, float far_boundary);
 int nerf_ctx_set_precision(nerf_ctx* ctx, int precision);
+/* ABI 6+, forward-facing scenes.  A new ctx is NERF_SAMPLING_LINEAR / NERF_RAYS_WORLD: the reference's behaviour.
+ * nerf_ctx_set_sampling: NERF_SAMPLING_LINDISP draws the coarse depths of EVERY call that draws them (nerf_get_z_values,
+ * nerf_render, nerf_render_image and the sharded calls, nerf_train_step / _gradients, nerf_train_render_*) as
+ *   z = 1 / (1/near + (1/far - 1/near) (s + u) / S),   near <= z < far,
+ * with the draws u the linear mode would use.  It needs near_boundary > 0: the setter, and later any of those calls
+ * (the bounds may change in between), fail with "lindisp needs near_boundary > 0".
+ * nerf_ctx_set_ray_space: NERF_RAYS_NDC makes the calls that generate rays from a camera -- nerf_render_image,
+ * nerf_render_image_sharded, nerf_render_image_sharded_outputs -- pass them through the transform of nerf_rays_to_ndc
+ * (same fov, this ndc_near_plane > 0) before they render.  In NDC the scene lies between 0 and 1 along every ray: the
+ * caller sets that with nerf_ctx_set_bounds(ctx, 0, 1).  Calls that take rays (nerf_render, the trainer) render what they
+ * are given; nerf_get_rays_directions stays world-space.  ndc_near_plane is ignored for NERF_RAYS_WORLD. */
+int nerf_ctx_set_sampling(nerf_ctx* ctx, int mode);
+int nerf_ctx_set_ray_space(nerf_ctx* ctx, int space, float ndc_near_plane);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of
@@ -102,8 +130,21 @@ int nerf_load_weights(nerf_ctx* ctx, int which, const float* blob, size_t n_floa
 /* get_rays_directions, src/UtilsCV.py:467-499.  c2w row-major (4,4) HOST; dirs (H*W,4). */
 int nerf_get_rays_directions(nerf_ctx* ctx, const float* c2w, float fov, int32_t H, int32_t W,
                              float* dirs, int mem);
+/* ABI 6+: world rays -> NDC rays, for callers that bring their own rays (nerf_render, the trainer, a ray dataset).  The
+ * reference carries this transform as dead code only.  Cameras look down -z; the near plane is z = -ndc_near_plane; fov is
+ * the field of view the rays were generated with: get_rays_directions uses ONE tangent for both axes and no aspect term,
+ * so both NDC scale factors are k = 1 / tan(fov / 2).  With tn = -(n + o_z) / d_z and p = o + tn d (the origin moved onto
+ * the near plane):
+ *   o' = (-k p_x / p_z, -k p_y / p_z, 1 + 2n / p_z)                                     -- o'_z = -1
+ *   d' = (-k (d_x / d_z - p_x / p_z), -k (d_y / d_z - p_y / p_z), -2n / p_z)            -- (o' + d')_z = +1: infinity
+ * w components are copied.  [n, infinity) along the world ray becomes [0, 1) along the NDC ray.  A ray with d_z == 0
+ * comes out non-finite (not guarded).  rays (N,4) in, (N,4) out; in place is allowed as out_orig == rays_orig AND
+ * out_dirs == rays_dirs.  The fused kernels take the view direction from the direction they are given: under NDC that is
+ * d', not the world direction (no difference for n_angles 0). */
+int nerf_rays_to_ndc(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float fov,
+                     float ndc_near_plane, float* out_orig, float* out_dirs, int mem);
 /* get_z_values(near,far,N,1,S)[:,0,:], src/UtilsCV.py:565-581.  u (N,S) uniform draws or NULL
- * (= on-device Philox keyed by seed and global ray index ray_base+r).  z (N,S). */
+ * (= on-device Philox keyed by seed and global ray index ray_base+r).  z (N,S).  Follows nerf_ctx_set_sampling. */
 int nerf_get_z_values(nerf_ctx* ctx, int64_t N, int32_t S, const float* u, uint64_t seed,
                       int64_t ray_base, float* z, int mem);
 /* get_z_vals_from_prob_dist_func, src/UtilsCV.py:502-539.  weights,z (N,S); u (N,Sf) or NULL;

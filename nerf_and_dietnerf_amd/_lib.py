@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("NERF_MI355_LIB") or os.path.join(_HERE, "lib", "libne
 NERF_NET_COARSE, NERF_NET_FINE = 0, 1
 NERF_MEM_HOST, NERF_MEM_DEVICE = 0, 1
 NERF_PRECISION_FP32, NERF_PRECISION_F16X3, NERF_PRECISION_F16, NERF_PRECISION_BF16X3 = 0, 1, 2, 3
+NERF_SAMPLING_LINEAR, NERF_SAMPLING_LINDISP = 0, 1
+NERF_RAYS_WORLD, NERF_RAYS_NDC = 0, 1
 NERF_ABI_VERSION = 6
 
 
@@ -49,9 +51,12 @@ SYMBOLS = [
     ("nerf_ctx_set_stream", C.c_int, [_P, _P]),
     ("nerf_ctx_set_bounds", C.c_int, [_P, _F, _F]),
     ("nerf_ctx_set_precision", C.c_int, [_P, C.c_int]),
+    ("nerf_ctx_set_sampling", C.c_int, [_P, C.c_int]),
+    ("nerf_ctx_set_ray_space", C.c_int, [_P, C.c_int, _F]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     ("nerf_get_rays_directions", C.c_int, [_P, _P, _F, _I32, _I32, _P, C.c_int]),
+    ("nerf_rays_to_ndc", C.c_int, [_P, _P, _P, _I64, _F, _F, _P, _P, C.c_int]),
     ("nerf_get_z_values", C.c_int, [_P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),
     ("nerf_sample_pdf", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _U64, _I64, _P, _P, C.c_int]),
     ("nerf_positional_encoding", C.c_int, [_P, _P, _I64, _I32, _I32, _P, C.c_int]),

@@ -36,6 +36,8 @@ N_EPOCHS, OPTIMIZER_LR, TEST_IMG_IDX = "n_epochs", "optimizer_lr", "test_img_idx
 N_RAYS_IN_BATCH_TRAIN = "n_rays_in_batch_train"
 BLENDER, COLMAP = "blender", "colmap"
 MIXED_FLOAT16 = "mixed_float16"
+# optional keys of the ``render`` section the reference does not have (forward-facing scenes; render.py reads them)
+LINDISP, USE_NDC, NDC_NEAR_PLANE = "lindisp", "use_ndc", "ndc_near_plane"
 ESTIMATE = "estimate"              # get_nerf(estimated_intersection=...): run the scene analysis, as the reference does
 
 
@@ -85,7 +87,9 @@ def get_nerf(config: Dict, near_boundary: float, far_boundary: float, *, images=
     ``save_location`` holds them.  ``policy``: the reference always trains under "mixed_float16" (:220-221); "float32" selects
     the fp32-class trainer.  ``estimated_intersection``: ESTIMATE (default) runs the reference's scene analysis on ALL camera
     poses (:249-251: the point the optical axes meet in, used only if the rig is spherical); an explicit point, or None
-    for the non-spherical pose sampling (src/DietNeRF.py:254-260), overrides it."""
+    for the non-spherical pose sampling (src/DietNeRF.py:254-260), overrides it.
+    The whole ``render`` section goes to the model, so a YAML that carries ``lindisp`` / ``use_ndc`` / ``ndc_near_plane`` gets
+    disparity sampling / NDC rays (with ``use_ndc`` the caller passes the NDC bounds 0 and 1 as near / far)."""
     from .dietnerf import DietNeRF
     from .render import NeRF
     net, render, training = config[NEURAL_NET], config[RENDER], config[TRAINING]

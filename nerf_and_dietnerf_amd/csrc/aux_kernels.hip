@@ -4,6 +4,9 @@
 //   sample_pdf    get_z_vals_from_prob_dist_func src/UtilsCV.py:502-539 (+ sort(concat), src/NeRF.py:132)
 //   composite     ray_marching                   src/UtilsNeuralRadianceField.py:88-115 (+ depth, ExecutionRun.py:346)
 //   posenc        positional_encoding_for_*      src/UtilsNeuralRadianceField.py:52-85 (standalone; tests/tools)
+// and two the reference does not have ("Ray and sampling space"):
+//   rays_to_ndc   world rays -> NDC rays of a forward-facing scene
+//   z_values, disparity-linear mode
 //
 // All HBM-bound fp32/int32 work.  Evaluation order is the canonical one of oracle/nerf_oracle.py:
 // sums / cumsum / cumprod run left to right along the sample axis and products are NOT contracted
@@ -51,16 +54,53 @@ __global__ void raygen_kernel(const RaygenArgs a) {
     if (a.orig) reinterpret_cast<float4*>(a.orig)[t] = make_float4(a.c[3], a.c[7], a.c[11], a.c[15]);
 }
 
+// tf.tan(field_of_view / 2) (UtilsCV.py:488): tan of fp32(fov/2), evaluated in double and rounded once
+static float raygen_tan_half(float fov) { return (float)tan((double)(fov * 0.5f)); }
+
 void launch_raygen(const float c2w_host[16], float fov, int H, int W, long long ray_begin,
                    long long ray_count, float* orig, float* dirs, hipStream_t stream) {
     if (ray_count <= 0) return;
     RaygenArgs a;
     for (int i = 0; i < 16; ++i) a.c[i] = c2w_host[i];
-    // tf.tan(field_of_view / 2) (UtilsCV.py:488): tan of fp32(fov/2), evaluated in double and rounded once
-    a.tan_half = (float)tan((double)(fov * 0.5f));
+    a.tan_half = raygen_tan_half(fov);
     a.H = H; a.W = W; a.ray_begin = ray_begin; a.ray_count = ray_count; a.orig = orig; a.dirs = dirs;
     const int bs = 256;
     hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((ray_count + bs - 1) / bs)), dim3(bs), 0, stream, a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rays_to_ndc: one thread per ray.  Cameras look down -z; n = distance of the near plane z = -n; k = 1 / tan_half is the
+// NDC scale of BOTH axes (the raygen above has one tangent and no aspect term).
+//   tn = -(n + o_z) / d_z;  p = o + tn d              (the origin moved onto the near plane: p_z = -n)
+//   o' = (-k p_x / p_z, -k p_y / p_z, 1 + 2n / p_z)   (o'_z = -1)
+//   d' = (-k (d_x / d_z - p_x / p_z), -k (d_y / d_z - p_y / p_z), -2n / p_z)   (o' + d' is the point at infinity: z = +1)
+// w is copied.  d_z = 0 (a ray parallel to the near plane) gives non-finite rays: not guarded.  In place (out == in) is
+// fine: a thread reads its own ray before it writes it.
+// ------------------------------------------------------------------------------------------------
+__global__ void rays_to_ndc_kernel(const float* orig, const float* dirs, long long N, float n, float two_n, float k,
+                                   float* out_orig, float* out_dirs) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N) return;
+    const float4 o = reinterpret_cast<const float4*>(orig)[t];
+    const float4 d = reinterpret_cast<const float4*>(dirs)[t];
+    const float tn = -__fdiv_rn(__fadd_rn(n, o.z), d.z);
+    const float px = __fadd_rn(o.x, __fmul_rn(tn, d.x));
+    const float py = __fadd_rn(o.y, __fmul_rn(tn, d.y));
+    const float pz = __fadd_rn(o.z, __fmul_rn(tn, d.z));
+    const float rx = __fdiv_rn(px, pz), ry = __fdiv_rn(py, pz), e = __fdiv_rn(two_n, pz);
+    const float sx = __fdiv_rn(d.x, d.z), sy = __fdiv_rn(d.y, d.z);
+    reinterpret_cast<float4*>(out_orig)[t] = make_float4(-__fmul_rn(k, rx), -__fmul_rn(k, ry), __fadd_rn(1.0f, e), o.w);
+    reinterpret_cast<float4*>(out_dirs)[t] =
+        make_float4(-__fmul_rn(k, __fsub_rn(sx, rx)), -__fmul_rn(k, __fsub_rn(sy, ry)), -e, d.w);
+}
+
+void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float fov, float near_plane, float* out_orig,
+                        float* out_dirs, hipStream_t stream) {
+    if (N <= 0) return;
+    const float k = (float)(1.0 / (double)raygen_tan_half(fov));   // the raygen's own (rounded) tangent, inverted once
+    const int bs = 256;
+    hipLaunchKernelGGL(rays_to_ndc_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream, orig, dirs, N,
+                       near_plane, 2.0f * near_plane, k, out_orig, out_dirs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -81,13 +121,41 @@ __global__ void z_values_kernel(float start, float stop, float delta, float span
     z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, span), (float)S));
 }
 
-void launch_z_values(float near_b, float far_b, long long N, int S, const float* u, uint64_t seed,
+// Disparity-linear mode: the strata are uniform in 1/z.  t = (s + u) / S,  z = 1 / (inv_near + (inv_far - inv_near) t),
+// u the same draw as above.  inv_near = 1/near and dinv = 1/far - 1/near come from the host (double, rounded once).  s + u
+// can round up to s + 1 (u = 1 - 2^-24): it is held at the largest float below, so t stays inside its stratum and t < 1;
+// the result is held in [near, far) (far_below = the largest float below far), which the roundings of the last stratum
+// could otherwise touch.
+__global__ void z_values_lindisp_kernel(float near_b, float far_below, float inv_near, float dinv, long long N, int S,
+                                        const float* __restrict__ u, uint64_t seed, long long ray_base,
+                                        float* __restrict__ z) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= N * S) return;
+    const long long r = m / S;
+    const int s = (int)(m - r * S);
+    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
+    const float top = (float)(s + 1);
+    float v = __fadd_rn((float)s, uu);
+    if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
+    const float t = __fdiv_rn(v, (float)S);
+    const float zz = __fdiv_rn(1.0f, __fadd_rn(inv_near, __fmul_rn(dinv, t)));
+    z[m] = fminf(fmaxf(zz, near_b), far_below);
+}
+
+void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
                      long long ray_base, float* z, hipStream_t stream) {
     if (N <= 0) return;
-    const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
-    const float span = (float)((double)far_b - (double)near_b);
     const long long total = N * S;
     const int bs = 256;
+    if (lindisp) {   // near_b > 0: the callers refuse anything else
+        const float inv_near = (float)(1.0 / (double)near_b);
+        const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
+        hipLaunchKernelGGL(z_values_lindisp_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream, near_b,
+                           nextafterf(far_b, near_b), inv_near, dinv, N, S, u, seed, ray_base, z);
+        return;
+    }
+    const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
+    const float span = (float)((double)far_b - (double)near_b);
     hipLaunchKernelGGL(z_values_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream, near_b,
                        far_b, delta, span, N, S, u, seed, ray_base, z);
 }

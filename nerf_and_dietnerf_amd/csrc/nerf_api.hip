@@ -57,6 +57,12 @@ int enter(nerf_ctx* c) {
     return 0;
 }
 
+int sampling_ok(const nerf_ctx* c) {
+    // 1/near: checked where depths are drawn as well as in the setter, since nerf_ctx_set_bounds may come after it
+    if (c->sampling == NERF_SAMPLING_LINDISP && !(c->cfg.near_boundary > 0.f)) return fail("lindisp needs near_boundary > 0");
+    return 0;
+}
+
 // The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
 static int layer_dims(int lx, int ld, int n_angles, int dims[12][2]) {
     const int xd = 3 + 6 * lx;                                  // src/NeRF.py:312
@@ -351,9 +357,11 @@ int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, cons
 int dev_render(nerf_ctx* c, const float* o, const float* d, long long N, int Sc, int Sf, const float* u_c,
                const float* u_f, uint64_t seed, long long ray_base, const nerf_outputs& outs) {
     const bool fine = Sf > 0 && c->net[NERF_NET_FINE].loaded;
+    if (int r = sampling_ok(c)) return r;
     if (int r = ensure(c, c->b_zc, (size_t)N * Sc * sizeof(float))) return r;
     float* zc = (float*)c->b_zc.p;
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, u_c, seed, ray_base, zc, c->stream);
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, Sc, u_c, seed, ray_base,
+                    zc, c->stream);
     if (!fine) return dev_render_rays(c, NERF_NET_COARSE, o, d, zc, N, Sc, outs);
     if (Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
     if (int r = ensure(c, c->b_wc, (size_t)N * Sc * sizeof(float))) return r;
@@ -460,6 +468,25 @@ int nerf_ctx_set_bounds(nerf_ctx* c, float near_b, float far_b) {
     return 0;
 }
 
+int nerf_ctx_set_sampling(nerf_ctx* c, int mode) {
+    if (!c) return fail("ctx is NULL");
+    if (mode != NERF_SAMPLING_LINEAR && mode != NERF_SAMPLING_LINDISP)
+        return fail("unknown sampling mode %d (NERF_SAMPLING_LINEAR = 0, NERF_SAMPLING_LINDISP = 1)", mode);
+    if (mode == NERF_SAMPLING_LINDISP && !(c->cfg.near_boundary > 0.f)) return fail("lindisp needs near_boundary > 0");
+    c->sampling = mode;
+    return 0;
+}
+
+int nerf_ctx_set_ray_space(nerf_ctx* c, int space, float ndc_near_plane) {
+    if (!c) return fail("ctx is NULL");
+    if (space != NERF_RAYS_WORLD && space != NERF_RAYS_NDC)
+        return fail("unknown ray space %d (NERF_RAYS_WORLD = 0, NERF_RAYS_NDC = 1)", space);
+    if (space == NERF_RAYS_NDC && !(ndc_near_plane > 0.f)) return fail("ndc_near_plane must be > 0 (got %g)", ndc_near_plane);
+    c->ray_space = space;
+    if (space == NERF_RAYS_NDC) c->ndc_near_plane = ndc_near_plane;
+    return 0;
+}
+
 int nerf_ctx_set_precision(nerf_ctx* c, int precision) {
     if (!c) return fail("ctx is NULL");
     RenderKernel k;
@@ -497,11 +524,38 @@ int nerf_get_rays_directions(nerf_ctx* c, const float* c2w, float fov, int32_t H
     return 0;
 }
 
+int nerf_rays_to_ndc(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float fov, float ndc_near_plane,
+                     float* out_orig, float* out_dirs, int mem) {
+    ENTER(c);
+    if (!rays_orig || !rays_dirs || !out_orig || !out_dirs) return fail("NULL argument");
+    if (N < 0) return fail("bad shape N=%lld", (long long)N);
+    if (!(ndc_near_plane > 0.f)) return fail("ndc_near_plane must be > 0 (got %g)", ndc_near_plane);
+    if ((out_orig == rays_orig) != (out_dirs == rays_dirs) || out_orig == rays_dirs || out_dirs == rays_orig || out_orig == out_dirs)
+        return fail("nerf_rays_to_ndc works in place only as out_orig == rays_orig AND out_dirs == rays_dirs");
+    if (N == 0) return 0;
+    const float *o = rays_orig, *d = rays_dirs;
+    float *oo = out_orig, *od = out_dirs;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
+        o = oo = (float*)c->b_orig.p; d = od = (float*)c->b_dirs.p;
+    }
+    launch_rays_to_ndc(o, d, N, fov, ndc_near_plane, oo, od, c->stream);
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(out_orig, oo, (size_t)N * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(out_dirs, od, (size_t)N * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
 int nerf_get_z_values(nerf_ctx* c, int64_t N, int32_t S, const float* u, uint64_t seed, int64_t ray_base, float* z,
                       int mem) {
     ENTER(c);
     if (!c || !z) return fail("NULL argument");
     if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
+    if (int r = sampling_ok(c)) return r;
     const float* du = u;
     float* dz = z;
     if (mem == NERF_MEM_HOST) {
@@ -509,7 +563,8 @@ int nerf_get_z_values(nerf_ctx* c, int64_t N, int32_t S, const float* u, uint64_
         if (int r = ensure(c, c->b_zc, (size_t)N * S * 4)) return r;
         dz = (float*)c->b_zc.p;
     }
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, S, du, seed, ray_base, dz, c->stream);
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, S, du, seed, ray_base,
+                    dz, c->stream);
     HIP_OK(hipGetLastError());
     if (mem == NERF_MEM_HOST) {
         HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
@@ -671,6 +726,7 @@ int nerf_render_image(nerf_ctx* c, const float* c2w, float fov, int32_t H, int32
     const int S = fine ? Sc + Sf : Sc;
     if (fine && sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024) return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget", Sc, Sf);
     const long long N = ray_count;
+    if (int r = sampling_ok(c)) return r;
     if (batch == 0) {
         batch = 1 << 18;
         // host destinations with per-sample outputs (up to 5.4 KB per ray): four batches per slab so that the device-to-host
@@ -682,6 +738,9 @@ int nerf_render_image(nerf_ctx* c, const float* c2w, float fov, int32_t H, int32
     if (int r = ensure(c, c->b_orig, (size_t)N * 16)) return r;
     if (int r = ensure(c, c->b_dirs, (size_t)N * 16)) return r;
     launch_raygen(c2w, fov, H, W, ray_begin, N, (float*)c->b_orig.p, (float*)c->b_dirs.p, c->stream);
+    if (c->ray_space == NERF_RAYS_NDC)   // in place: what nerf_rays_to_ndc makes of these rays, bit for bit
+        launch_rays_to_ndc((const float*)c->b_orig.p, (const float*)c->b_dirs.p, N, fov, c->ndc_near_plane, (float*)c->b_orig.p,
+                           (float*)c->b_dirs.p, c->stream);
     const float *duc = u_c, *duf = u_f;
     nerf_outputs dev = *outs;
     if (mem == NERF_MEM_HOST) {

@@ -39,6 +39,9 @@ struct CommState;    // comm_api.hip
 
 struct nerf_ctx {
     nerf_config cfg;
+    int sampling = NERF_SAMPLING_LINEAR;       // coarse depths: nerf_ctx_set_sampling
+    int ray_space = NERF_RAYS_WORLD;           // rays nerf_render_image generates: nerf_ctx_set_ray_space
+    float ndc_near_plane = 1.0f;
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -64,6 +67,7 @@ int ensure(nerf_ctx* c, DevBuf& b, size_t bytes);   // grow-only device buffer
 int h2d(nerf_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int enter(nerf_ctx* c);                             // NULL check + hipSetDevice
 #define ENTER(c) do { if (int r__ = nerf::enter(c)) return r__; } while (0)
+int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's bounds suit its sampling mode (lindisp: near > 0)
 
 void train_free(nerf_ctx* c);                       // train_api.hip: releases c->train (called by nerf_ctx_destroy)
 void comm_free(nerf_ctx* c);                        // comm_api.hip: releases c->comm (called by nerf_ctx_destroy)

@@ -228,7 +228,11 @@ void launch_repack_bwd(const float* blob, const int32_t* idx, void* stream, hipS
 void launch_raygen(const float c2w_host[16], float fov, int H, int W,
                    long long ray_begin, long long ray_count, float* orig /*nullable*/, float* dirs,
                    hipStream_t stream);
-void launch_z_values(float near_b, float far_b, long long N, int S, const float* u, uint64_t seed,
+// world rays -> NDC rays (near plane z = -near_plane, both scale factors 1 / tan(fov / 2) as the raygen's); out may be in
+void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float fov, float near_plane, float* out_orig,
+                        float* out_dirs, hipStream_t stream);
+// lindisp: strata uniform in 1/z (needs near_b > 0) instead of in z
+void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
                      long long ray_base, float* z, hipStream_t stream);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,

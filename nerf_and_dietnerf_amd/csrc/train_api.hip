@@ -713,6 +713,7 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
     if (!rays_o || !rays_d || !target) return fail("NULL argument");
     bool fine;
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
+    if (int r = sampling_ok(c)) return r;
     const size_t f = sizeof(float);
     const float *o, *d, *tg, *uc, *uf;
     if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
@@ -744,7 +745,8 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
 
     // coarse forward (src/NeRF.py:146-151)
     TPass& pc = t->pass[0];
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, uc, seed, 0, (float*)pc.z.p, c->stream);
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, Sc, uc, seed, 0,
+                    (float*)pc.z.p, c->stream);
     if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
     const bool through_sampler = fine && t->cfg.sampler_gradient != 0;
     if (fine) {
@@ -803,12 +805,14 @@ int render_forward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const Pa
                         const float* d, const float* uc, const float* uf, uint64_t seed, long long ray_base) {
     const long long N = dc.N;
     const int Sc = dc.S, Sf = df.S - dc.S;                           // the fine pass renders the Sc + Sf merged samples
+    if (int q = sampling_ok(c)) return q;
     int r = ensure_pass(c, t->pass[0], dc);
     if (fine) r |= ensure_pass(c, t->pass[1], df);
     r |= ensure(c, t->z_new, (fine ? N * (long long)Sf : 1) * sizeof(float));
     if (r) return r;
     TPass& pc = t->pass[0];
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, N, Sc, uc, seed, ray_base, (float*)pc.z.p, c->stream);
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, Sc, uc, seed, ray_base,
+                    (float*)pc.z.p, c->stream);
     if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
     if (!fine) return 0;
     launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,

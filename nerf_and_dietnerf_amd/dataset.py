@@ -18,7 +18,9 @@ import numpy as np
 
 
 def c2w_to_rays_prepare_ds(c2w, field_of_view: float, img, ctx):
-    """One image -> (rays_orig (h*w,4), rays_dirs (h*w,4), real_rgb_pixels (h*w,3)) as CUDA tensors."""
+    """One image -> (rays_orig (h*w,4), rays_dirs (h*w,4), real_rgb_pixels (h*w,3)) as CUDA tensors.  On a context in NDC
+    ray space (render_config ``use_ndc``; Context.set_ray_space) the rays are transformed on the device, with the
+    context's near plane, before they are returned: the trainer then sees what render_image renders."""
     import torch
     dev = torch.device("cuda", ctx.cfg.device)
     img_t = torch.as_tensor(np.asarray(img, np.float32) if not hasattr(img, "is_cuda") else img,
@@ -28,6 +30,8 @@ def c2w_to_rays_prepare_ds(c2w, field_of_view: float, img, ctx):
                             dtype=torch.float32, device=dev)
     dirs = ctx.get_rays_directions(h, w, float(field_of_view), c2w_t).reshape(-1, 4)
     orig = c2w_t[:, 3].expand(dirs.shape[0], 4).contiguous()          # broadcast of c2w[..., :, 3]
+    if getattr(ctx, "ray_space", "world") == "ndc":
+        orig, dirs = ctx.rays_to_ndc(orig, dirs, float(field_of_view), ctx.ndc_near_plane)
     return orig, dirs, img_t.reshape(-1, 3)
 
 

@@ -186,6 +186,8 @@ class DietNeRF(NeRF):
         pose_t = torch.as_tensor(pose, dtype=torch.float32, device=self._dev)
         dirs = ctx.get_rays_directions(s, s, self.fov, pose_t).reshape(-1, 4)[begin:begin + count].contiguous()
         orig = pose_t[:, 3].expand(count, 4).contiguous()
+        if getattr(ctx, "ray_space", "world") == "ndc":   # the tape renders the rays render_image renders (render_config use_ndc)
+            orig, dirs = ctx.rays_to_ndc(orig, dirs, self.fov, ctx.ndc_near_plane)
         batch = int(self.batch_size_train)
         slab = None
         if self.keep_activations:

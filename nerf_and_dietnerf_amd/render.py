@@ -35,6 +35,10 @@ HIDDEN_LAYER_DIM = "hidden_layer_dim"
 LAST_HIDDEN_LAYER_DIM = "last_hidden_layer_dim"
 N_RAYS_IN_BATCH_RENDER = "n_rays_in_batch_render"
 N_RAYS_IN_BATCH_TRAIN = "n_rays_in_batch_train"
+# render_config keys the reference does not have: forward-facing scenes ("Ray and sampling space")
+LINDISP = "lindisp"                  # bool, default False: coarse depths uniform in disparity
+USE_NDC = "use_ndc"                  # bool, default False: rays in normalised device coordinates
+NDC_NEAR_PLANE = "ndc_near_plane"    # float, default 1.0: distance of the NDC near plane (with use_ndc)
 
 N_COORDINATES = 3
 N_COLOR_CHANNELS = 3
@@ -43,6 +47,8 @@ N_COLOR_CHANNELS = 3
 # back to exact fp32 for a weight set whose activations leave the fp16 range (Context._auto_call)
 _PRECISIONS = {"fp32": NERF_PRECISION_FP32, "f16x3": NERF_PRECISION_F16X3, "f16": _lib.NERF_PRECISION_F16,
                "bf16x3": _lib.NERF_PRECISION_BF16X3, "auto": NERF_PRECISION_F16X3}
+_SAMPLINGS = {"linear": _lib.NERF_SAMPLING_LINEAR, "lindisp": _lib.NERF_SAMPLING_LINDISP}
+_RAY_SPACES = {"world": _lib.NERF_RAYS_WORLD, "ndc": _lib.NERF_RAYS_NDC}
 
 
 # --------------------------------------------------------------------------------------------
@@ -224,6 +230,7 @@ class Context:
         self._auto_unchecked = False  # "auto": device-resident calls since the last look at the counter
         self.auto_fallbacks = 0      # "auto": calls that were re-rendered in exact fp32
         self._slot_fine = {}         # train_render_forward slots that ran a fine pass
+        self.sampling, self.ray_space, self.ndc_near_plane = "linear", "world", 1.0   # what nerf_ctx_create leaves
 
     def close(self):
         if getattr(self, "h", None):
@@ -254,6 +261,45 @@ class Context:
     def set_bounds(self, near: float, far: float) -> None:
         _lib.check(self.lib.nerf_ctx_set_bounds(self.h, near, far))
         self.cfg.near_boundary, self.cfg.far_boundary = near, far
+
+    def set_sampling(self, mode: str) -> None:
+        """"linear" (default: coarse depths stratified uniformly in depth, src/UtilsCV.py:565-581) or "lindisp" (uniformly in
+        disparity 1/z; needs near > 0).  Every call that draws coarse depths follows it: get_z_values, render, render_image,
+        the trainer."""
+        if mode not in _SAMPLINGS:
+            raise ValueError(f"unknown sampling mode {mode!r}: expected one of {sorted(_SAMPLINGS)}")
+        # the library's own check (it repeats it wherever depths are drawn: the bounds may change later), made here first so
+        # that a configuration error does not need a device call to show
+        if mode == "lindisp" and not self.cfg.near_boundary > 0:
+            raise RuntimeError("lindisp needs near_boundary > 0")
+        _lib.check(self.lib.nerf_ctx_set_sampling(self.h, _SAMPLINGS[mode]))
+        self.sampling = mode
+
+    def set_ray_space(self, space: str, ndc_near_plane: float = 1.0) -> None:
+        """"world" (default) or "ndc": render_image / render_image_sharded then pass the camera's rays through
+        ``rays_to_ndc(..., fov, ndc_near_plane)`` before rendering; set the bounds to (0, 1) for it.  Calls that take rays render
+        what they are given, and get_rays_directions stays world-space."""
+        if space not in _RAY_SPACES:
+            raise ValueError(f"unknown ray space {space!r}: expected one of {sorted(_RAY_SPACES)}")
+        _lib.check(self.lib.nerf_ctx_set_ray_space(self.h, _RAY_SPACES[space], float(ndc_near_plane)))
+        self.ray_space = space
+        if space == "ndc":
+            self.ndc_near_plane = float(ndc_near_plane)
+
+    def rays_to_ndc(self, rays_orig, rays_dirs, fov, ndc_near_plane: float = 1.0):
+        """World rays (..., 4) of cameras looking down -z -> (rays_orig, rays_dirs) in NDC, same shape and kind (numpy or
+        torch-device arrays, as get_rays_directions); ``fov`` is the field of view the rays were generated with
+        (include/nerf_mi355.h: nerf_rays_to_ndc has the formulas)."""
+        arr = self._arrays(rays_orig, rays_dirs)
+        shape = tuple(rays_orig.shape)
+        if shape != tuple(rays_dirs.shape) or not shape or shape[-1] != 4:
+            raise ValueError(f"rays must be two (..., 4) arrays of one shape, got {shape} and {tuple(rays_dirs.shape)}")
+        n = int(np.prod(shape[:-1], dtype=np.int64))
+        po, pd = arr.inp(_reshape(rays_orig, (n, 4)), (n, 4)), arr.inp(_reshape(rays_dirs, (n, 4)), (n, 4))
+        oo, poo = arr.out(shape)
+        od, pod = arr.out(shape)
+        _lib.check(self.lib.nerf_rays_to_ndc(self.h, po, pd, n, float(fov), float(ndc_near_plane), poo, pod, arr.mem))
+        return oo, od
 
     def set_precision(self, precision: str) -> None:
         """"auto", "fp32" (exact fp32 MFMA), "f16x3" (3-pass split-fp16 MFMA, fp32 accumulate), "bf16x3" (3-pass split-bf16
@@ -732,6 +778,14 @@ class NeRF:
         self.n_pos_enc_view_dir = net_config[N_POS_ENC_VIEW_DIR]
         self.n_angles_for_model = net_config[N_ANGLES_FOR_MODEL]
         self.seed = 0
+        # forward-facing scenes: absent keys leave the context as nerf_ctx_create made it (linear depths, world rays)
+        self.lindisp = bool(render_config.get(LINDISP, False))
+        self.use_ndc = bool(render_config.get(USE_NDC, False))
+        self.ndc_near_plane = float(render_config.get(NDC_NEAR_PLANE, 1.0))
+        if self.lindisp:
+            self.ctx.set_sampling("lindisp")
+        if self.use_ndc:
+            self.ctx.set_ray_space("ndc", self.ndc_near_plane)
 
     def set_weights(self, coarse, fine=None) -> None:
         self._blobs = [coarse, fine]

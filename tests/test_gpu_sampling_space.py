@@ -1,0 +1,458 @@
+"""Forward-facing scenes on the device: disparity-linear coarse depths (nerf_ctx_set_sampling) and NDC rays
+(nerf_rays_to_ndc, nerf_ctx_set_ray_space) through every layer that follows them -- get_z_values, render, render_image and
+its sharded form, the trainer and the ray dataset.  The float64 formulas, their float32 restatements and the derived error
+bars live in tests/sampling_space_ref.py; the CPU oracle is used unchanged, through the entries it has for given rays and
+depths.  Every test here needs the three entry points this adds to the ABI.
+
+One case of the plan cannot exist as written: disparity sampling refuses near <= 0 (1 / near), and NDC bounds are (0, 1).
+test_parity_end_to_end therefore asserts that refusal for "use_ndc + lindisp at bounds (0, 1)" and runs the end-to-end
+comparison for use_ndc at (0, 1) with linear depths (the NDC configuration) and for use_ndc + lindisp at (2^-4, 1), the same
+case with the near bound lifted off zero."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import sampling_space_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
+       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
+IMAGES = [(8, 8), (16, 24), (24, 16)]            # (h, w): 8 x 8, 24 x 16 and 16 x 24 pixels
+NDC_NEAR = 0.5                                   # the rig's own near bound is 0.56 (tests/golden/alexander50_epoch095.npz)
+LINDISP_MESSAGE = "lindisp needs near_boundary > 0"
+
+
+@pytest.fixture(scope="module")
+def rig():
+    return R.forward_facing_poses()
+
+
+@pytest.fixture(scope="module")
+def blobs():
+    import nerf_and_dietnerf_amd as N
+    return N.glorot_blob(0), N.glorot_blob(1)
+
+
+def _ctx(blobs=None, near=2.0, far=6.0, precision="fp32", **kw):
+    import nerf_and_dietnerf_amd as N
+    ctx = N.Context(near=near, far=far, precision=precision, **kw)
+    if blobs is not None:
+        ctx.load_weights(0, blobs[0])
+        ctx.load_weights(1, blobs[1])
+    return ctx
+
+
+# ---- 1. lindisp depths ---------------------------------------------------------------------------------------------------
+def _draws(rng, n, s):
+    """Random draws with a row of u = 0 and a row of u = nextafter(1, 0) (for one ray: three separate sets)."""
+    if n == 1:
+        return [rng.random((1, s), dtype=np.float32), np.zeros((1, s), np.float32), np.full((1, s), R.U_BELOW_ONE, np.float32)]
+    u = rng.random((n, s), dtype=np.float32)
+    u[0], u[-1] = 0.0, R.U_BELOW_ONE
+    return [u]
+
+
+@pytest.mark.parametrize("near,far", [(1.0, 8.0), (0.5, 64.0)])
+def test_lindisp_depths_against_float64(near, far, capsys):
+    """|dz| / z <= 6 * 2^-24 * far / near (sampling_space_ref.lindisp_bar has the derivation), near <= z < far, strictly
+    increasing along s -- for N in {1, 77, 4096} x S in {1, 2, 64, 257}, with u = 0 and u = nextafter(1, 0) among the draws."""
+    ctx = _ctx(near=near, far=far)
+    ctx.set_sampling("lindisp")
+    rng = np.random.default_rng(11)
+    worst = 0.0
+    for n in (1, 77, 4096):
+        for s in (1, 2, 64, 257):
+            for u in _draws(rng, n, s):
+                z = ctx.get_z_values(near, far, 1, n, s, uniform_values=u).reshape(n, s)
+                ref = R.lindisp_f64(near, far, u)
+                worst = max(worst, float((np.abs(z - ref) / ref).max()))
+                assert np.all(np.abs(z - ref) <= R.lindisp_bar(near, far) * ref), (n, s)
+                assert np.all(z >= near) and np.all(z < far), (n, s)
+                assert np.all(np.diff(z, axis=1) > 0), (n, s)
+    with capsys.disabled():
+        print(f"\n[lindisp {near} .. {far}] max |dz| / z = {worst:.3e} (bar {R.lindisp_bar(near, far):.3e})", end="")
+    ctx.close()
+
+
+def test_lindisp_device_draws_repeat_and_follow_the_global_ray_index(oracle):
+    """u = None: Philox(seed, ray_base + r) -- two calls agree bit for bit, a call from ray_base = b equals rows b.. of a call
+    from 0, and the depths are the formula's on the oracle's restatement of the same draws."""
+    near, far, n, s, b = 1.0, 8.0, 77, 64, 31
+    ctx = _ctx(near=near, far=far)
+    ctx.set_sampling("lindisp")
+    z0 = ctx.get_z_values(near, far, 1, n, s, seed=9).reshape(n, s)
+    np.testing.assert_array_equal(z0, ctx.get_z_values(near, far, 1, n, s, seed=9).reshape(n, s))
+    zb = ctx.get_z_values(near, far, 1, 20, s, seed=9, ray_base=b).reshape(20, s)
+    np.testing.assert_array_equal(zb, z0[b:b + 20])
+    assert not np.array_equal(z0, ctx.get_z_values(near, far, 1, n, s, seed=10).reshape(n, s))
+    ref = R.lindisp_f64(near, far, oracle.philox_uniform(9, np.arange(n, dtype=np.uint64), s, 0))
+    assert np.all(np.abs(z0 - ref) <= R.lindisp_bar(near, far) * ref)
+    ctx.close()
+
+
+def test_lindisp_refuses_a_near_bound_that_is_not_positive(blobs):
+    """The library's own check: in the setter, and -- the bounds may change after it -- in every call that draws depths."""
+    import nerf_and_dietnerf_amd as N
+    ctx = _ctx(blobs, near=1.0, far=8.0)
+    ctx.set_sampling("lindisp")
+    ctx.set_bounds(0.0, 1.0)
+    o = np.zeros((4, 4), np.float32)
+    d = np.tile(np.array([0, 0, -1, 0], np.float32), (4, 1))
+    c2w = np.eye(4, dtype=np.float32)
+    for call in (lambda: ctx.get_z_values(0.0, 1.0, 1, 4, 8),
+                 lambda: ctx.render(o, d, 8, 8),
+                 lambda: ctx.render_image(c2w, 0.5, 2, 2, 0, 8, 8),
+                 lambda: N._lib.check(ctx.lib.nerf_ctx_set_sampling(ctx.h, N._lib.NERF_SAMPLING_LINDISP))):
+        with pytest.raises(RuntimeError, match=LINDISP_MESSAGE):
+            call()
+    ctx.train_begin(5e-4)
+    with pytest.raises(RuntimeError, match=LINDISP_MESSAGE):
+        ctx.train_gradients(o, d, np.zeros((4, 3), np.float32), 8, 8)
+    with pytest.raises(RuntimeError, match=LINDISP_MESSAGE):
+        ctx.train_render_gradients(o, d, np.zeros((4, 3), np.float32), 8, 8)
+    ctx.set_sampling("linear")                                   # the linear mode takes these bounds
+    assert np.isfinite(ctx.render(o, d, 8, 8)[0]).all()
+    ctx.close()
+
+
+# ---- 2. the default state is today's behaviour ---------------------------------------------------------------------------
+def test_linear_after_lindisp_is_bit_identical_to_a_fresh_context(oracle, rig, golden_ckpt):
+    poses, fov = rig
+    o, d = R.world_rays(oracle, poses[0], fov, 7, 11)            # 77 rays
+    near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
+    w = (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
+    tgt = np.random.default_rng(2).random((77, 3), dtype=np.float32)
+    got = []
+    for toggled in (False, True):
+        ctx = _ctx(w, near=near, far=far)
+        if toggled:
+            ctx.set_sampling("lindisp")
+            lin = ctx.get_z_values(near, far, 1, 77, 16, seed=4)
+            ctx.set_sampling("linear")
+            ctx.set_ray_space("ndc", NDC_NEAR)
+            ctx.set_ray_space("world")
+        z = ctx.get_z_values(near, far, 1, 77, 16, seed=4)
+        if toggled:
+            assert not np.array_equal(z, lin)                    # the mode did change the depths while it was on
+        outs = ctx.render(o, d, 16, 24, seed=4)
+        img = ctx.render_image(poses[0], fov, 7, 11, 0, 16, 24, seed=4)
+        ctx.train_begin(5e-4)
+        m = ctx.train_step(o, d, tgt, 16, 24, seed=4)
+        got.append([z] + list(outs) + list(img) + [ctx.get_weights(0), ctx.get_weights(1), np.array([m[k] for k in sorted(m)])])
+        ctx.train_end()
+        ctx.close()
+    for a, b in zip(*got):
+        np.testing.assert_array_equal(a, b)
+
+
+# ---- 3. the NDC transform ------------------------------------------------------------------------------------------------
+def _check_ndc(o, d, oo, dd, fov, n):
+    ro, rd, p = R.rays_to_ndc_f64(o, d, fov, n)
+    bars = R.ndc_bars(o, d, fov, n)
+    assert R.within(oo[:, :2], ro[:, :2], bars["oxy"]) and R.within(oo[:, 2], ro[:, 2], bars["oz"])
+    assert R.within(dd[:, :2], rd[:, :2], bars["dxy"]) and R.within(dd[:, 2], rd[:, 2], bars["dz"])
+    assert np.all(oo[:, 3] == o[:, 3]) and np.all(dd[:, 3] == d[:, 3])
+    # o'_z = -1 and (o' + d')_z = +1, to the bars of those components
+    assert R.within(oo[:, 2], -1.0, bars["oz"])
+    assert np.all(np.abs(oo[:, 2].astype(np.float64) + dd[:, 2] - 1.0) <= (bars["oz"] + 2 * bars["dz"]) * R.U)
+    # the NDC point at t' = 1 - p_z / (p_z + t d_z) is the perspective projection of the world point p + t d
+    k = float(R.ndc_scale(fov))
+    d64 = d[:, :3].astype(np.float64)
+    for t in (0.1, 1.0, 10.0, 1000.0):
+        pt = p + t * d64
+        proj = np.stack([-k * pt[:, 0] / pt[:, 2], -k * pt[:, 1] / pt[:, 2], 1.0 + 2 * float(np.float32(n)) / pt[:, 2]], axis=1)
+        tp = (1.0 - p[:, 2] / (p[:, 2] + t * d64[:, 2]))[:, None]
+        got = oo[:, :3].astype(np.float64) + tp * dd[:, :3].astype(np.float64)       # t' <= 1: the two bars add
+        scale = np.maximum(1.0, np.maximum(np.abs(ro[:, :3]), np.abs(rd[:, :3])))
+        lim = np.array([bars["oxy"] + bars["dxy"]] * 2 + [bars["oz"] + bars["dz"]]) * R.U * scale
+        assert np.all(np.abs(got - proj) <= lim), t
+    return bars
+
+
+def test_rays_to_ndc_against_float64(oracle, rig, capsys):
+    """The three most -z-facing cameras of the golden LLFF rig x the three image shapes, plus 1, 77 and 4096 rays drawn from
+    them: every component within its derived bar of the float64 formulas (sampling_space_ref.ndc_bars), the defining
+    properties, in place == out of place and host memory == device memory, bit for bit."""
+    import torch
+    import nerf_and_dietnerf_amd as N
+    poses, fov = rig
+    ctx = _ctx()
+    sets = [R.world_rays(oracle, c2w, fov, h, w) for c2w, (h, w) in zip(poses, IMAGES)]
+    sets += [R.world_rays(oracle, c2w, fov, h, w) for c2w, (h, w) in zip(poses[::-1], IMAGES)]
+    every_o, every_d = (np.concatenate([s[i] for s in sets]) for i in range(2))
+    pick = np.random.default_rng(5).integers(0, every_o.shape[0], 4096)
+    sets += [(every_o[pick[:n]], every_d[pick[:n]]) for n in (1, 77, 4096)]
+    for o, d in sets:
+        # device: get_rays_directions output where the set is one image, as the dataset uses it
+        oo, dd = ctx.rays_to_ndc(o, d, fov, NDC_NEAR)
+        assert oo.shape == o.shape and dd.shape == d.shape
+        bars = _check_ndc(o, d, oo, dd, fov, NDC_NEAR)
+        ot, dt = torch.as_tensor(o).cuda(), torch.as_tensor(d).cuda()
+        od, ddv = ctx.rays_to_ndc(ot, dt, fov, NDC_NEAR)
+        assert od.is_cuda and ddv.is_cuda
+        np.testing.assert_array_equal(od.cpu().numpy(), oo)
+        np.testing.assert_array_equal(ddv.cpu().numpy(), dd)
+        # in place, on device memory, through the C entry point itself
+        oi, di = ot.clone(), dt.clone()
+        torch.cuda.synchronize()
+        N._lib.check(ctx.lib.nerf_rays_to_ndc(ctx.h, oi.data_ptr(), di.data_ptr(), o.shape[0], fov, NDC_NEAR, oi.data_ptr(),
+                                              di.data_ptr(), N._lib.NERF_MEM_DEVICE))
+        ctx.synchronize()
+        np.testing.assert_array_equal(oi.cpu().numpy(), oo)
+        np.testing.assert_array_equal(di.cpu().numpy(), dd)
+    with capsys.disabled():
+        print(f"\n[rays_to_ndc] bars of the last set, in units of 2^-24 max(1, |value|): " +
+              ", ".join(f"{k} {v:.1f}" for k, v in bars.items()), end="")
+    # the library's raygen and the oracle's agree bit for bit (existing tests pin it); its output is what the dataset feeds
+    h, w = IMAGES[1]
+    dirs = ctx.get_rays_directions(h, w, fov, poses[1]).reshape(-1, 4)
+    np.testing.assert_array_equal(dirs, sets[1][1])
+    # half in place is refused
+    o, d = sets[0]
+    buf = np.empty_like(o)
+    assert ctx.lib.nerf_rays_to_ndc(ctx.h, o.ctypes.data, d.ctypes.data, o.shape[0], fov, NDC_NEAR, o.ctypes.data,
+                                    buf.ctypes.data, N._lib.NERF_MEM_HOST) != 0
+    ctx.close()
+
+
+# ---- 4. render_image in NDC mode -----------------------------------------------------------------------------------------
+def test_render_image_in_ndc_mode_is_raygen_ndc_render(oracle, rig, blobs):
+    """render_image on an NDC context == get_rays_directions -> rays_to_ndc -> render on a world context, bit for bit, with the
+    same (seed, global ray index): the whole image, a slab, and two batch sizes."""
+    poses, fov = rig
+    (h, w), sc, sf, seed = IMAGES[1], 16, 24, 5
+    ndc = _ctx(blobs, near=0.0, far=1.0)
+    ndc.set_ray_space("ndc", NDC_NEAR)
+    plain = _ctx(blobs, near=0.0, far=1.0)
+    for c2w in poses:
+        dirs = plain.get_rays_directions(h, w, fov, c2w).reshape(-1, 4)
+        orig = np.tile(c2w[:, 3], (h * w, 1)).astype(np.float32)
+        o, d = plain.rays_to_ndc(orig, dirs, fov, NDC_NEAR)
+        want = plain.render(o, d, sc, sf, seed=seed, want_depth=True)
+        for batch in (0, 100):
+            got = ndc.render_image(c2w, fov, h, w, batch, sc, sf, seed=seed, want_depth=True)
+            for a, b in zip(got, want):
+                np.testing.assert_array_equal(a.reshape(b.shape), b)
+        begin, count = 37, 101
+        want_slab = plain.render(o[begin:begin + count], d[begin:begin + count], sc, sf, seed=seed, ray_base=begin, want_depth=True)
+        for batch in (0, 64):
+            got = ndc.render_image(c2w, fov, h, w, batch, sc, sf, seed=seed, ray_begin=begin, ray_count=count, want_depth=True)
+            for a, b in zip(got, want_slab):
+                np.testing.assert_array_equal(a, b)
+        for a, b in zip(want_slab, want):
+            np.testing.assert_array_equal(a, b[begin:begin + count])
+    # world mode again: the transform is gone
+    ndc.set_ray_space("world")
+    np.testing.assert_array_equal(ndc.render_image(poses[0], fov, h, w, 0, sc, sf, seed=seed)[0],
+                                  plain.render_image(poses[0], fov, h, w, 0, sc, sf, seed=seed)[0])
+    ndc.close()
+    plain.close()
+
+
+# ---- 5. parity end to end ------------------------------------------------------------------------------------------------
+_PARITY = {}
+
+
+def _parity_reference(oracle, rig, blobs, lindisp, near, far):
+    """The unmodified CPU oracle on the test-side NDC rays and the test-side coarse depths (computed once per configuration)."""
+    key = (lindisp, near, far)
+    if key not in _PARITY:
+        poses, fov = rig
+        h, w = IMAGES[1]
+        rng = np.random.default_rng(21)
+        u_c, u_f = rng.random((h * w, 64), dtype=np.float32), rng.random((h * w, 128), dtype=np.float32)
+        o, d = R.rays_to_ndc_f32(*R.world_rays(oracle, poses[1], fov, h, w), fov, NDC_NEAR)
+        z_c = R.lindisp_f32(near, far, u_c) if lindisp else oracle.get_z_values(near, far, u_c)
+        coarse, fine = oracle.unpack_blob(blobs[0]), oracle.unpack_blob(blobs[1])
+        res = oracle.render_rays(coarse, o, d, z_c)
+        z_f = oracle.get_z_vals_from_prob_dist_func(res[1], z_c, u_f)
+        z = np.sort(np.concatenate([z_f, z_c], axis=-1), axis=-1)
+        _PARITY[key] = (u_c, u_f, oracle.render_rays(fine, o, d, z)[0], z)
+    return _PARITY[key]
+
+
+@pytest.mark.parametrize("precision", ["fp32", "f16x3", "bf16x3"])
+def test_parity_end_to_end(oracle, rig, blobs, precision, capsys):
+    """NeRF(render_config: use_ndc [+ lindisp]).render_image at 64 + 128 samples on a 24 x 16 image with Glorot weights and
+    explicit draws: final RGB within the project's 1e-4 bar (tests/test_gpu_parity.py) of the unmodified CPU oracle.
+    use_ndc + lindisp at the NDC bounds (0, 1) is refused (1 / near); it runs at (2^-4, 1)."""
+    import nerf_and_dietnerf_amd as N
+    poses, fov = rig
+    h, w = IMAGES[1]
+    rc = {"n_render_samples_coarse": 64, "n_render_samples_fine": 128, "use_ndc": True, "ndc_near_plane": NDC_NEAR}
+    with pytest.raises(RuntimeError, match=LINDISP_MESSAGE):
+        N.NeRF(NET, dict(rc, lindisp=True), 0.0, 1.0, precision=precision)
+    for lindisp, near, far in ((False, 0.0, 1.0), (True, 2.0 ** -4, 1.0)):
+        u_c, u_f, ref, ref_z = _parity_reference(oracle, rig, blobs, lindisp, near, far)
+        model = N.NeRF(NET, dict(rc, lindisp=lindisp), near, far, precision=precision)
+        model.set_weights(*blobs)
+        out = model.render_image(poses[1], fov, h, w, u_coarse=u_c, u_fine=u_f)
+        err = float(np.abs(out[0].reshape(-1, 3) - ref).max())
+        with capsys.disabled():
+            print(f"\n[{precision}, use_ndc{' + lindisp' if lindisp else ''}, bounds {near} .. {far}] max-abs RGB error vs the "
+                  f"oracle {err:.3e}; max |dz| {np.abs(out[5].reshape(ref_z.shape) - ref_z).max():.3e}", end="")
+        assert np.isfinite(out[0]).all() and err <= 1e-4
+        assert model.ctx.read_nonfinite() == 0
+        model.ctx.close()
+
+
+# ---- 6. training follows the mode ----------------------------------------------------------------------------------------
+def _relerr(a, b):
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+def _cos(a, b):
+    a, b = a.astype(np.float64), b.astype(np.float64)
+    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
+
+
+@pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
+def test_train_gradients_follow_the_sampling_mode(oracle, rig, golden_ckpt, policy, capsys):
+    """One train_gradients call in lindisp mode with draws u against one in linear mode with the draws
+    u' = (z_lindisp - linspace[s]) S / (far - near), which put the linear mode's depths on the same values up to rounding.
+    Bars of tests/test_gpu_train.py, float32 policy against its oracle at the reference's leaky_relu_alpha = 0.05: loss
+    within 2e-6 relative (:86; :126 has 2e-3 under mixed_float16), both gradient blobs within 5e-2 of max|g| with cosine
+    > 0.999 (:89-91)."""
+    poses, fov = rig
+    near, far, n, sc, sf = 1.0, 8.0, 48, 16, 24
+    rng = np.random.default_rng(3)
+    o, d = R.world_rays(oracle, poses[2], fov, 8, 8)
+    idx = rng.choice(64, n, replace=False)
+    o, d = o[idx], np.ascontiguousarray(d[idx])
+    u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
+    tgt = rng.random((n, 3), dtype=np.float32)
+    mixed = policy == "mixed_float16"
+    res = {}
+    for mode in ("lindisp", "linear"):
+        ctx = _ctx((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), near=near, far=far)
+        ctx.set_sampling(mode)
+        if mode == "lindisp":
+            z_ld = ctx.get_z_values(near, far, 1, n, sc, uniform_values=u_c).reshape(n, sc)
+            u = u_c
+        else:
+            u = ((z_ld.astype(np.float64) - oracle.linspace_f32(near, far, sc)[None, :]) * sc / (far - near)).astype(np.float32)
+            z_lin = ctx.get_z_values(near, far, 1, n, sc, uniform_values=u).reshape(n, sc)
+            assert np.abs(z_lin - z_ld).max() <= 4 * R.U * far          # the same depths, to rounding
+        ctx.train_begin(5e-4, mixed_float16=mixed)
+        res[mode] = ctx.train_gradients(o, d, tgt, sc, sf, u, u_f)
+        ctx.train_end()
+        ctx.close()
+    (m0, gc0, gf0), (m1, gc1, gf1) = res["lindisp"], res["linear"]
+    with capsys.disabled():
+        print(f"\n[{policy}] lindisp vs linear on the same depths: loss {m0['loss']:.7f} / {m1['loss']:.7f}, gradients "
+              f"{_relerr(gc0, gc1):.2e} (coarse), {_relerr(gf0, gf1):.2e} (fine) of max|g|", end="")
+    assert np.isfinite(gc0).all() and np.isfinite(gf0).all()
+    assert abs(m0["loss"] - m1["loss"]) <= (2e-3 if mixed else 2e-6) * m1["loss"]
+    assert _relerr(gc0, gc1) <= 5e-2 and _cos(gc0, gc1) > 0.999
+    assert _relerr(gf0, gf1) <= 5e-2 and _cos(gf0, gf1) > 0.999
+    # and the mode matters: linear depths on the lindisp draws are another problem
+    ctx = _ctx((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), near=near, far=far)
+    ctx.train_begin(5e-4, mixed_float16=mixed)
+    m2 = ctx.train_gradients(o, d, tgt, sc, sf, u_c, u_f)[0]
+    assert abs(m2["loss"] - m0["loss"]) > 1e-4 * m0["loss"]
+    ctx.close()
+
+
+def test_use_ndc_dataset_holds_the_ndc_rays(rig):
+    """prepare_ds on a use_ndc model's context: two 8 x 8 images -> exactly the rays rays_to_ndc returns for them."""
+    import torch
+    import nerf_and_dietnerf_amd as N
+    poses, fov = rig
+    images = np.random.default_rng(8).random((2, 8, 8, 3), dtype=np.float32)
+    model = N.NeRF(NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 8, "use_ndc": True, "ndc_near_plane": NDC_NEAR},
+                   0.0, 1.0, precision="fp32")
+    assert model.ctx.ray_space == "ndc" and model.ctx.sampling == "linear"
+    ds = N.prepare_ds(32, poses[:2], images, fov, model.ctx)
+    want_o, want_d = [], []
+    for c2w in poses[:2]:
+        dirs = model.ctx.get_rays_directions(8, 8, fov, c2w).reshape(-1, 4)
+        o, d = model.ctx.rays_to_ndc(np.tile(c2w[:, 3], (64, 1)).astype(np.float32), dirs, fov, NDC_NEAR)
+        want_o.append(o)
+        want_d.append(d)
+    assert ds.n_rays == 128 and ds.orig.is_cuda
+    np.testing.assert_array_equal(ds.orig.cpu().numpy(), np.concatenate(want_o))
+    np.testing.assert_array_equal(ds.dirs.cpu().numpy(), np.concatenate(want_d))
+    np.testing.assert_array_equal(ds.rgb.cpu().numpy(), images.reshape(-1, 3))
+    # a world context keeps world rays
+    model.ctx.set_ray_space("world")
+    ds_w = N.prepare_ds(32, poses[:2], images, fov, model.ctx)
+    assert torch.equal(ds_w.orig[:64], torch.as_tensor(poses[0][:, 3]).cuda().expand(64, 4))
+    model.ctx.close()
+
+
+# ---- 7. sharded render ---------------------------------------------------------------------------------------------------
+def _rank_main(rank, world, p, id_path, q):
+    try:
+        import time
+        import nerf_and_dietnerf_amd as N
+        ctx = N.Context(near=0.0, far=1.0, precision="fp32")
+        ctx.load_weights(0, p["blobs"][0])
+        ctx.load_weights(1, p["blobs"][1])
+        ctx.set_ray_space("ndc", NDC_NEAR)
+        if rank == 0:
+            with open(id_path + ".tmp", "wb") as f:
+                f.write(N.Context.comm_unique_id())
+            os.replace(id_path + ".tmp", id_path)
+        t0 = time.time()
+        while not os.path.exists(id_path):
+            time.sleep(0.02)
+            if time.time() - t0 > 120:
+                raise TimeoutError("rank 0 never published the communicator id")
+        with open(id_path, "rb") as f:
+            ctx.comm_init(f.read(), rank, world)
+        h, w = p["hw"]
+        img = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5)
+        six = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5, outputs="all")
+        with open("/proc/self/maps") as f:
+            assert "libstub_rccl.so" in f.read()
+        ctx.comm_destroy()
+        q.put((rank, (img, six[5])))
+    except BaseException as e:
+        import traceback
+        q.put((rank, RuntimeError(f"rank {rank}: {e}\n{traceback.format_exc()}")))
+        raise
+
+
+def test_sharded_render_in_ndc_mode(rig, blobs, tmp_path):
+    """nerf_render_image_sharded over two ranks (the test-only RCCL stand-in, tests/stub_rccl.c) on NDC contexts == the one-rank
+    image, bit for bit: the slabs go through the same raygen -> rays_to_ndc as nerf_render_image."""
+    import torch.multiprocessing as mp
+    poses, fov = rig
+    h, w = 7, 13                                                  # 91 rays: the second slab is one ray short
+    stub = tmp_path / "libstub_rccl.so"
+    subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "stub_rccl.c"),
+                    "-o", str(stub), "-L/opt/rocm/lib", "-lamdhip64", "-lrt"], check=True)
+    one = _ctx(blobs, near=0.0, far=1.0)
+    one.set_ray_space("ndc", NDC_NEAR)
+    want = one.render_image(poses[0], fov, h, w, 0, 16, 24, seed=5)
+    world_img = _ctx(blobs, near=0.0, far=1.0).render_image(poses[0], fov, h, w, 0, 16, 24, seed=5)[0]
+    assert not np.array_equal(want[0], world_img)                 # NDC mode is not a no-op
+    one.close()
+    p = dict(blobs=blobs, c2w=poses[0], fov=fov, hw=(h, w))
+    mpc = mp.get_context("spawn")
+    q = mpc.Queue()
+    id_path = str(tmp_path / "comm_id")
+    old = os.environ.get("NERF_RCCL_LIB")
+    os.environ["NERF_RCCL_LIB"] = str(stub)                        # inherited by the ranks
+    try:
+        procs = [mpc.Process(target=_rank_main, args=(r, 2, p, id_path, q)) for r in range(2)]
+        for pr in procs:
+            pr.start()
+    finally:
+        if old is None:
+            os.environ.pop("NERF_RCCL_LIB", None)
+        else:
+            os.environ["NERF_RCCL_LIB"] = old
+    res = [q.get(timeout=300) for _ in procs]
+    for pr in procs:
+        pr.join(timeout=60)
+    for _, r in res:
+        if isinstance(r, BaseException):
+            raise r
+    for _, (img, z) in res:
+        np.testing.assert_array_equal(img, want[0])
+        np.testing.assert_array_equal(z, want[5])
