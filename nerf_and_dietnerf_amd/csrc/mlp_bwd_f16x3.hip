@@ -8,8 +8,8 @@
 //     D7  = (W8[hidden rows] . G9 + W10[hidden rows] * d_sigma) * LeakyReLU'(h8)
 //     D_l-1 = (W_l . D_l) * LeakyReLU'(h_l)          l = 7 .. 1   (layer 4: its 256 hidden rows)
 //     dXa = W4[xyz rows] . D4,  dXb = W0 . D0        (gradient w.r.t. the xyz encoding; only for the sampler term)
-// where D_l is the gradient w.r.t. the pre-activation of layer l.  It replaces the layer-by-layer gemm_abt_h launches
-// (train_kernels.hip) whose every operand made a round trip through HBM.
+// where D_l is the gradient w.r.t. the pre-activation of layer l.  It replaced layer-by-layer data-gradient GEMM launches
+// whose every operand made a round trip through HBM (the reference trainer still runs that way, in exact fp32: gemm_abt).
 //
 // Same skeleton as the forward kernel: one wave per SIMD, 32 samples per wave with the sample on the lane,
 // D^T = W . D_next^T on v_mfma_f32_32x32x16_f16 in three passes over hi/lo split operands (fp32-class results), the
@@ -22,7 +22,8 @@
 //     its own power-of-two scale, renewed per layer from the largest entry of that sample's operand, so that the packed
 //     operand peaks between 2^5 and 2^12 for every row independently (the layer-wise GEMM could only scale whole
 //     buffers); scaling a column of B scales that column of the product, so the epilogue undoes it exactly;
-//   * every D_l is also written in fp32 (true scale) for the weight-gradient GEMMs, with max|D_l| for their scaling.
+//   * every D_l is also written for the weight-gradient GEMMs, with max|D_l| for their scaling: as the packed (hi, lo)
+//     operand itself plus its row factor (pair16, 3-pass kernels) or as fp16 values (single-pass kernels).
 #include "mlp_f16_frag.h"
 
 #include <string.h>
@@ -180,7 +181,8 @@ __device__ __forceinline__ void bwd_body(Pipe& p, uint32_t lane16, float alpha, 
         o[0] = q0; o[1] = q1; o[2] = q2; o[3] = v;
         stream_store(reinterpret_cast<f32x4*>(base + (decltype(fragc)::value ? 32 : 1) * (c0 + 8 * (r >> 2))), o);
     };
-    // register r of hidden tile ht: mask, write the true value, scale + split + pack into the next operand
+    // register r of hidden tile ht: mask, scale + split + pack into the next operand, store D (the packed pair itself, or
+    // its fp16 true-scale value under the single-pass policy)
     // alpha folded into the four scales once per body (pinned: left to itself hipcc re-multiplies per value rather than
     // hold the registers)
     auto pinned = [](float v) { asm volatile("" : "+v"(v)); return v; };
@@ -219,19 +221,15 @@ __device__ __forceinline__ void bwd_body(Pipe& p, uint32_t lane16, float alpha, 
             const float ws = *reinterpret_cast<const float*>(smem_ + cb_h + (kXConstWsig + 32 * ht + 8 * (r >> 2) + (r & 3)) * 4);
             acc_v = fmaf(ws, decltype(sig_sel)::value == 1 ? dsig_cur : dsig_prev, acc_in);
         }
-        // t = acc * LeakyReLU' / scale-in (the true value), pk = acc * LeakyReLU' * scale-out (the next operand): LeakyReLU'
-        // is folded into the two power-of-two scales (exact), one selected factor each -- bfe + 2 bfi + 2 mul where
-        // and + compare + select + three multiplications were 6 VALU ops per value (single-pass: t comes from the packed
-        // pair, see ratio_h2: bfe + bfi + mul per value)
+        // pk = acc * LeakyReLU' * scale-out (the next operand): LeakyReLU' is folded into the power-of-two scale (exact), one
+        // selected factor -- bfe + bfi + mul per value.  No true-scale value is formed on the 3-pass path (D is stored as the
+        // packed pair); single-pass: the fp16 true-scale value comes from the packed pair, see ratio_h2
         const int neg = mask_ones<mask_bit(ht, r)>(mk[ht >> 1]);
+        // TODO: drop inv_s / ainv_s and the callers' pinned ainv_* products.  The true-scale factors have no reader since the
+        // gradient buffers hold the packed operand; they stay for now because removing the pinned products changes the
+        // kernels' instruction streams, which then have to be measured again.
+        (void)inv_s; (void)ainv_s;
         float pk;
-        if constexpr (!FAST && !kPair16) {
-            const float t = acc_v * mask_select(neg, ainv_s, inv_s);
-            if constexpr ((r & 3) == 0) q0 = t;
-            else if constexpr ((r & 3) == 1) q1 = t;
-            else if constexpr ((r & 3) == 2) q2 = t;
-            else store4(dst, 32 * ht, r, t, std::true_type{});
-        }
         // (pk = t * (rho / inv) would save the second select, but a sample whose gradient underflows has inv = 0 and
         // rho / inv = Inf: 0 * Inf poisoned the weight gradients -- measured, reverted)
         pk = acc_v * mask_select(neg, arho_s, rho_s);
@@ -267,17 +265,15 @@ __device__ __forceinline__ void bwd_body(Pipe& p, uint32_t lane16, float alpha, 
                 const uint32_t ph = pack_h2(h0, h1), pl = pack_h2(l0, l1);
                 if constexpr (decltype(to_x)::value) { xh[n][d] = ph; xl[n][d] = pl; }
                 else { nh[n][d] = ph; nl[n][d] = pl; }
-                // pair16 gradient buffers (nerf_kernels.h::kPair16): D is stored as this very operand pair -- the row's power-of-
+                // pair16 gradient buffers (nerf_kernels.h::MlpBwdArgs::rs_ptr): D is stored as this very operand pair -- the row's power-of-
                 // two scale stays on it, its inverse goes to rs_ptr once per row and buffer -- in the slot of its fp32 value:
                 // {hi01, hi23, lo01, lo23} per four features.  No true-scale value is formed at all (a select and a multiply
                 // per value less than the fp32 buffers needed).
-                if constexpr (kPair16) {
-                    if constexpr ((r & 3) == 1) { q0 = __uint_as_float(ph); q1 = __uint_as_float(pl); }
-                    else {
-                        frag4 o;
-                        o[0] = __float_as_uint(q0); o[1] = ph; o[2] = __float_as_uint(q1); o[3] = pl;
-                        stream_store(reinterpret_cast<frag4*>(dst + 32 * (32 * ht + 8 * (r >> 2))), o);
-                    }
+                if constexpr ((r & 3) == 1) { q0 = __uint_as_float(ph); q1 = __uint_as_float(pl); }
+                else {
+                    frag4 o;
+                    o[0] = __float_as_uint(q0); o[1] = ph; o[2] = __float_as_uint(q1); o[3] = pl;
+                    stream_store(reinterpret_cast<frag4*>(dst + 32 * (32 * ht + 8 * (r >> 2))), o);
                 }
             }
         }
@@ -499,11 +495,9 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a) {
                     g9[n * 8 + g * 4 + e] = v;
                     mt = fmaxf(mt, fabsf(v));
                 }
-                if constexpr (FAST)
+                if constexpr (FAST)      // (3-pass: G9 is stored below, in pair16 form)
                     stream_store(reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.d_ptr[NMQ - 1]) + off128 + 32 * (32 * t + 16 * s + 8 * g)),
                                  make_uint2(pack_h2(o[0], o[1]), pack_h2(o[2], o[3])));
-                else if constexpr (!kPair16)
-                    stream_store(reinterpret_cast<f32x4*>(a.d_ptr[NMQ - 1] + off128 + 32 * (32 * t + 16 * s + 8 * g)), o);
             }
         }
         mt = max_with_other_half(mt);
@@ -530,7 +524,7 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a) {
                 nh[n][e >> 1] = pack_h2(h0, h1);
                 nl[n][e >> 1] = pack_h2(l0, l1);
             }
-            if constexpr (!FAST && kPair16) {      // G9 in pair16 form: the operand fragments are its rows (scale sig, row factor 1 / sig)
+            if constexpr (!FAST) {      // G9 in pair16 form: the operand fragments are its rows (scale sig, row factor 1 / sig)
                 const int t = n >> 1, s = n & 1;
                 stream_store(reinterpret_cast<frag4*>(a.d_ptr[NMQ - 1] + off128 + 32 * (32 * t + 16 * s)), frag4{nh[n][0], nh[n][1], nl[n][0], nl[n][1]});
                 stream_store(reinterpret_cast<frag4*>(a.d_ptr[NMQ - 1] + off128 + 32 * (32 * t + 16 * s + 8)), frag4{nh[n][2], nh[n][3], nl[n][2], nl[n][3]});
@@ -538,7 +532,7 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a) {
         }
         // row factor of a pair16 gradient buffer: the upper half of a power of two's fp32 bits (one 2-byte store per row)
         auto store_rs = [&](int buf, float r) {
-            if constexpr (!FAST && kPair16) {
+            if constexpr (!FAST) {
                 if (h == 0) a.rs_ptr[buf][m] = (uint16_t)(__float_as_uint(r) >> 16);
             }
         };
@@ -617,23 +611,21 @@ __device__ __forceinline__ void mlp_bwd_body(const MlpBwdArgs& a) {
                 for (int e = 0; e < 4; ++e) {
                     const int bit = mask_bit(7, r + e);
                     // pair16: in the scale of D0's other tiles (rho of the last body); true D = that * inv_sig
-                    const float v = last[r + e] * (((mk_cur[3] >> bit) & 1u) ? alpha : 1.0f) * (!FAST && kPair16 ? L.rho_prev : L.inv_prev);
+                    const float v = last[r + e] * (((mk_cur[3] >> bit) & 1u) ? alpha : 1.0f) * (FAST ? L.inv_prev : L.rho_prev);
                     o[e] = v;
                     tmax = fmaxf(tmax, fabsf(v));
                 }
-                if constexpr (!FAST && kPair16) {
+                if constexpr (!FAST) {
                     float h0, l0, h1, l1, h2_, l2, h3, l3;
                     split_trunc(o[0], h0, l0); split_trunc(o[1], h1, l1); split_trunc(o[2], h2_, l2); split_trunc(o[3], h3, l3);
                     stream_store(reinterpret_cast<frag4*>(d_cur + 32 * (32 * 7 + 8 * (r >> 2))),
                                  frag4{pack_h2(h0, h1), pack_h2(h2_, h3), pack_h2(l0, l1), pack_h2(l2, l3)});
-                } else if constexpr (FAST)
+                } else
                     stream_store(reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(d_cur) + 32 * (32 * 7 + 8 * (r >> 2))),
                                  make_uint2(pack_h2(o[0], o[1]), pack_h2(o[2], o[3])));
-                else
-                    stream_store(reinterpret_cast<f32x4*>(d_cur + 32 * (32 * 7 + 8 * (r >> 2))), o);
             }
             // max|D0| of this sample: the already packed part (in the next operand's scale) and the flushed tile
-            if constexpr (!FAST && kPair16) tmax *= L.inv_sig;
+            if constexpr (!FAST) tmax *= L.inv_sig;
             tmax = fmaxf(tmax, L.mrun * L.inv_sig);
             lds_gmax_update<FAST>(NMQ - 1, __float_as_uint(max_with_other_half(tmax)));
         }

@@ -1,9 +1,12 @@
 // train_api.hip -- C ABI of the training path (include/nerf_mi355.h, "training" section):
 //   NeRF.train_step            src/NeRF.py:136-178   (loss, gradients of both networks, optimizer step, metrics)
 //   Adam(optimizer_lr)         src/ExecutionRun.py:226 (Keras-2.7 defaults beta_1=.9 beta_2=.999 epsilon=1e-7)
-// Orchestration only: every arithmetic step is a HIP kernel of train_kernels.hip / aux_kernels.hip on the
-// context's stream.  Master weights, gradients and Adam moments live on the device as flat blobs in Keras
-// get_weights() order; padded [K x N] / [N x K] copies feed the GEMMs and are rebuilt after every update.
+// Orchestration only: every arithmetic step is a HIP kernel of train_kernels.hip / aux_kernels.hip / the fused MLP
+// kernels on the context's stream.  Master weights, gradients and Adam moments live on the device as flat blobs in Keras
+// get_weights() order; what the kernels read (the fused trainer's two operand streams, the reference trainer's padded
+// [K x N] / [N x K] matrices) is rebuilt from the blob after every update.
+// Two trainers (TrainState::reference): the fused one (default; stash forward, mlp_bwd_f16x3, batched weight gradients
+// on fragment-major buffers) and the layer-wise exact-fp32 one (NERF_TRAIN_FORWARD=gemm), kept as an independent reference.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,15 +24,15 @@ namespace nerf {
 struct TLayer {
     int K_real, N_real, Kp, Np, rowmap;
     size_t w_off, b_off;           // offsets into the blob
-    float *W, *WT, *bias;          // padded copies (device)
-    uint16_t *Whi, *Wlo;           // W split into fp16 hi / lo planes (data gradient on the fp16 cores)
+    float *W, *WT, *bias;          // padded copies (device; the reference trainer's, TNet::mats)
 };
 
 struct TNet {
     bool present = false;
     bool render_dirty = false;     // optimizer steps not yet packed into the render path's operand streams
     bool host_stale = false;       // ... and not yet copied to NetWeights::host_blob (the seed of the next trainer)
-    float *blob = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr, *mats = nullptr;
+    float *blob = nullptr, *grad = nullptr, *m = nullptr, *v = nullptr;
+    float* mats = nullptr;         // reference trainer: W, WT and bias of every layer (TLayer)
     void* fstream = nullptr;       // fused forward (f16x3 stash kernel): operand stream + constants, re-packed on device
     float* fcst = nullptr;
     void* bstream = nullptr;       // fused backward (mlp_bwd_f16x3): transposed operand stream, re-packed on device
@@ -43,7 +46,7 @@ struct TPass {                      // activations of one pass, kept from forwar
     // fused backward: LeakyReLU' bit records of layers 0..8 (32 B per row and layer, written by the stash forward),
     // the pre-activation gradients D[0..7] (Mp x 256) and G9 = D[8] (Mp x 128), the two encoding-gradient parts
     DevBuf masks, D[10], dxa, dxb;     // D[8], D[9]: see MlpBwdArgs::d_ptr (the xyz-only network has ten gradient buffers)
-    DevBuf rs;                         // pair16 gradient buffers (float32 policy): 10 x Mp row factors (MlpBwdArgs::rs_ptr)
+    DevBuf rs;                         // pair16 gradient buffers (fused trainer, float32 policy): 10 x Mp row factors (MlpBwdArgs::rs_ptr)
 };
 
 // nerf_train_render_forward / _backward (ABI 5): the activations of one ray batch of NeRF.render(), kept from a forward to
@@ -64,19 +67,22 @@ constexpr int kMaxRenderSlots = 4096;
 
 struct TrainState {
     nerf_train_config cfg;
-    bool training = false;          // set by nerf_train_begin
-    bool fused_forward = false;     // forward pass on the fused split-fp16 kernel with activation stash (n_angles > 0)
-    int32_t *sidx = nullptr, *cidx = nullptr;   // device gather tables of the fused kernel's stream / constants
-    bool fused_backward = false;    // data gradients by the fused chain kernel (needs the fused forward's mask records)
-    bool frag = false;              // fused forward + backward: activation / gradient buffers are fragment-major (frag_index)
-    bool pair16 = false;            // ... and, under the float32 policy, the gradient buffers hold fp16 (hi, lo) pairs in their fp32 slots (nerf_kernels.h::kPair16)
+    // The layer-wise exact-fp32 trainer (NERF_TRAIN_FORWARD=gemm): gemm_abt forward and data gradients, gemm_atb weight
+    // gradients, row-major fp32 buffers -- an independent reference for the tests.  Otherwise (default) the fused trainer:
+    // the f16x3 stash forward, the mlp_bwd_f16x3 chain and the batched weight-gradient GEMMs on the fp16 matrix cores, all
+    // on fragment-major buffers (frag_layout.h::frag_index) that hold fp32 activations and "pair16" gradients (fp16 (hi, lo)
+    // pairs in the fp32 slots, MlpBwdArgs::rs_ptr) under the float32 policy, fp16 values under mixed_float16.
+    bool reference = false;
+    int32_t *sidx = nullptr, *cidx = nullptr;   // device gather tables of the fused forward's stream / constants
     int32_t* bidx[2] = {nullptr, nullptr};      // gather tables of the backward stream: [0] plain, [1] with encoding tiles
     long long step = 0;
     size_t nblob = 0;
     TNet net[2];
     TPass pass[2];
-    DevBuf Ga, Gb, G9, Graw, dA0, partial, d_rgb, d_wext, d_zf, tgt, o, d, u_c, u_f, scal, gmax;
-    DevBuf dsig;                    // (Mp) column 3 of Graw as a vector, written by the fused backward chain (GemmAtb::sig_g)
+    DevBuf Graw, partial, d_rgb, d_wext, d_zf, tgt, o, d, u_c, u_f, scal;
+    DevBuf Ga, Gb, G9, dA0;         // reference trainer: ping-pong gradient buffers (Mp x 256), the rgb branch's (Mp x 128), dL/d(xyz_enc)
+    DevBuf gmax;                    // fused trainer: 2 passes x 16 x 64 max|D| slots (MlpBwdArgs::gmax -> GemmAtb::gmax)
+    DevBuf dsig;                    // ... (Mp) column 3 of Graw as a vector, written by the backward chain (GemmAtb::sig_g)
     // The fine pass's batched weight-gradient launch on a second stream, beside the sampler / compositing backward and the coarse
     // pass's backward chain (default; NERF_TRAIN_OVERLAP=0 keeps one stream).  Its slab sums live in their own buffer, each pass
     // has its own max|D| slots, and the main stream joins before anything reads the fine network's gradient blob.  Both big
@@ -87,12 +93,6 @@ struct TrainState {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool side_pending = false;
     DevBuf partial_side;
-    bool wgrad_f16 = false;         // weight gradients on the fp16 matrix cores (gemm_atb_h), else exact fp32 MFMA
-    bool dgrad_f16 = false;         // data gradients on the fp16 matrix cores (gemm_abt_h)
-    bool wgrad_wide = true;         // 256 x 256 tile for the 256-wide layers' weight gradients
-    // elements per row of the 256-wide / 128-wide activation and gradient buffers (padded pitches were measured against
-    // L2-channel hot-spotting in round 2 and lost; the fused path's buffers are fragment-major now, frag_layout.h)
-    int ldh = 256, ldh9 = 128;
     bool acc_grads = false;         // the running backward pass ADDS to the gradient blobs (nerf_train_render_gradients)
     // ray loss = loss_w[0] * MSE(coarse) + loss_w[1] * MSE(fine) (nerf_train_set_loss_weights): 1, 1 is NeRF.train_step
     // (src/NeRF.py:151,157); DietNeRF's ray loss counts the coarse term twice (src/DietNeRF.py:160-170)
@@ -176,19 +176,19 @@ void aim_gather(const nerf_config& cfg, int32_t* idx, size_t n, bool f16) {
 }
 
 int relayout_net(nerf_ctx* c, TNet& n) {
-    if (n.fstream)
-        launch_repack_f16x3(n.blob, c->train->sidx, n.fstream, c->train->cidx, n.fcst,
-                            f16_stream_bytes(c->cfg.n_angles, c->train->mixed), c->stream);
-    if (n.bstream) launch_repack_bwd(n.blob, c->train->bidx[n.bdx ? 1 : 0], n.bstream, c->stream);
-    // the padded W / W^T / hi-lo planes feed the layer-wise GEMMs only (NERF_TRAIN_* switches); the fused forward + backward
-    // read the two re-packed streams above and nothing else (22 launches per step that nobody read)
-    if (c->train->frag) { HIP_OK(hipGetLastError()); return 0; }
+    const TrainState* t = c->train;
+    if (!t->reference) {     // the fused kernels read their two re-packed streams and nothing else
+        launch_repack_f16x3(n.blob, t->sidx, n.fstream, t->cidx, n.fcst, f16_stream_bytes(c->cfg.n_angles, t->mixed), c->stream);
+        launch_repack_bwd(n.blob, t->bidx[n.bdx ? 1 : 0], n.bstream, c->stream);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
     for (int l = 0; l < n.n_layers; ++l) {
         const TLayer& L = n.L[l];
         RelayoutArgs a;
         a.w = n.blob + L.w_off; a.b = n.blob + L.b_off;
         a.K_real = L.K_real; a.N_real = L.N_real; a.Kp = L.Kp; a.Np = L.Np; a.rowmap = L.rowmap;
-        a.W = L.W; a.WT = L.WT; a.bias = L.bias; a.Whi = L.Whi; a.Wlo = L.Wlo;
+        a.W = L.W; a.WT = L.WT; a.bias = L.bias;
         launch_relayout(a, c->stream);
     }
     HIP_OK(hipGetLastError());
@@ -206,9 +206,8 @@ int alloc_optimizer(nerf_ctx* c, TrainState* t, TNet& n) {
     return 0;
 }
 
-// fused-forward operands of one network (and, once, the gather tables they are re-packed with)
+// the fused trainer's operand streams of one network (and, once, the gather tables they are re-packed with)
 int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
-    if (!t->fused_forward) return 0;
     if (!t->sidx) {
         std::vector<int32_t> si(f16_stream_bytes(c->cfg.n_angles, t->mixed) / 2), ci(kConstFloats);
         if (c->cfg.n_pos_enc_xyz > kLx) wide::build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
@@ -222,19 +221,17 @@ int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
     }
     if (!n.fstream) HIP_OK(hipMalloc(&n.fstream, kStreamBytesF16Xyz));     // the largest of the four streams
     if (!n.fcst) HIP_OK(hipMalloc((void**)&n.fcst, kConstBytes));
-    if (t->fused_backward && t->training) {
-        // the fine network's chain also produces the gradient w.r.t. the xyz encoding when the sampler is differentiated
-        n.bdx = (&n == &t->net[1]) && t->cfg.sampler_gradient != 0;
-        int32_t*& bi = t->bidx[n.bdx ? 1 : 0];
-        if (!bi) {
-            std::vector<int32_t> idx(kBwdStreamBytes / 2);
-            build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data(), 3 + 6 * pe_layout_lx(c->cfg.n_pos_enc_xyz));
-            aim_gather(c->cfg, idx.data(), idx.size(), true);
-            HIP_OK(hipMalloc((void**)&bi, idx.size() * sizeof(int32_t)));
-            HIP_OK(hipMemcpy(bi, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        if (!n.bstream) HIP_OK(hipMalloc(&n.bstream, kBwdStreamBytes));
+    // the fine network's chain also produces the gradient w.r.t. the xyz encoding when the sampler is differentiated
+    n.bdx = (&n == &t->net[1]) && t->cfg.sampler_gradient != 0;
+    int32_t*& bi = t->bidx[n.bdx ? 1 : 0];
+    if (!bi) {
+        std::vector<int32_t> idx(kBwdStreamBytes / 2);
+        build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data(), 3 + 6 * pe_layout_lx(c->cfg.n_pos_enc_xyz));
+        aim_gather(c->cfg, idx.data(), idx.size(), true);
+        HIP_OK(hipMalloc((void**)&bi, idx.size() * sizeof(int32_t)));
+        HIP_OK(hipMemcpy(bi, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    if (!n.bstream) HIP_OK(hipMalloc(&n.bstream, kBwdStreamBytes));
     return 0;
 }
 
@@ -243,25 +240,24 @@ int init_net(nerf_ctx* c, TrainState* t, int which) {
     n.n_layers = layer_table(c->cfg, n.L);
     const size_t nb = t->nblob * sizeof(float);
     HIP_OK(hipMalloc((void**)&n.blob, nb));
-    if (t->training)
-        if (int r = alloc_optimizer(c, t, n)) return r;
-    size_t mats = 0;
-    for (int l = 0; l < n.n_layers; ++l) mats += 3 * (size_t)n.L[l].Kp * n.L[l].Np + n.L[l].Np;   // W, WT, (Whi + Wlo), bias
-    HIP_OK(hipMalloc((void**)&n.mats, mats * sizeof(float)));
-    float* p = n.mats;
-    for (int l = 0; l < n.n_layers; ++l) {
-        TLayer& L = n.L[l];
-        L.W = p; p += (size_t)L.Kp * L.Np;
-        L.WT = p; p += (size_t)L.Kp * L.Np;
-        L.Whi = reinterpret_cast<uint16_t*>(p);
-        L.Wlo = L.Whi + (size_t)L.Kp * L.Np;
-        p += (size_t)L.Kp * L.Np;          // two half planes = one float plane
-        L.bias = p; p += L.Np;
-    }
+    if (int r = alloc_optimizer(c, t, n)) return r;
     HIP_OK(hipMemcpyAsync(n.blob, c->net[which].host_blob.data(), nb, hipMemcpyHostToDevice, c->stream));
     n.present = true;
     n.render_dirty = n.host_stale = false;
-    if (int r = ensure_fused(c, t, n)) return r;
+    if (!t->reference) {
+        if (int r = ensure_fused(c, t, n)) return r;
+    } else {
+        size_t mats = 0;
+        for (int l = 0; l < n.n_layers; ++l) mats += 2 * (size_t)n.L[l].Kp * n.L[l].Np + n.L[l].Np;   // W, WT, bias
+        HIP_OK(hipMalloc((void**)&n.mats, mats * sizeof(float)));
+        float* p = n.mats;
+        for (int l = 0; l < n.n_layers; ++l) {
+            TLayer& L = n.L[l];
+            L.W = p; p += (size_t)L.Kp * L.Np;
+            L.WT = p; p += (size_t)L.Kp * L.Np;
+            L.bias = p; p += L.Np;
+        }
+    }
     return relayout_net(c, n);
 }
 
@@ -271,33 +267,33 @@ struct PassDims { long long N; int S; long long M, Mp; };
 PassDims pass_dims(long long N, int S) { return {N, S, N * S, (N * S + 127) / 128 * 128}; }
 
 int ensure_pass(nerf_ctx* c, TPass& p, const PassDims& d) {
+    const TrainState* t = c->train;
     const size_t f = sizeof(float);
     // the mixed_float16 policy keeps activations and pre-activation gradients in fp16 (same element pitches, half the
     // bytes); the buffers are grow-only and are released by train_free before a trainer of the other policy starts
-    const size_t ea = c->train && c->train->mixed && c->train->training ? 2 : f;
+    const size_t ea = t->mixed ? 2 : f;
     int r = 0;
     r |= ensure(c, p.C4, d.Mp * kLdC4 * ea);
     r |= ensure(c, p.C8, d.Mp * kLdC8 * ea);
     DevBuf* hs[] = {&p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7};
-    const int ldh = c->train ? c->train->ldh : 256, ldh9 = c->train ? c->train->ldh9 : 128;
-    for (DevBuf* h : hs) r |= ensure(c, *h, d.Mp * ldh * ea);
-    r |= ensure(c, p.H9, d.Mp * ldh9 * ea);
-    if (c->cfg.n_angles == 0) r |= ensure(c, p.H8b, d.Mp * 256 * f);      // (fp32-sized: also the layer-wise path's)
+    for (DevBuf* h : hs) r |= ensure(c, *h, d.Mp * 256 * ea);
+    r |= ensure(c, p.H9, d.Mp * 128 * ea);
+    const bool xyz = c->cfg.n_angles == 0;
+    if (xyz) r |= ensure(c, p.H8b, d.Mp * 256 * f);      // (fp32-sized under either policy)
     r |= ensure(c, p.raw, d.Mp * 4 * f);
     r |= ensure(c, p.T, d.M * f);
     r |= ensure(c, p.w, d.M * f);
     r |= ensure(c, p.rgb, d.N * 3 * f);
     r |= ensure(c, p.z, d.M * f);
-    if (c->train && c->train->fused_backward && c->train->training) {
-        const bool xyz = c->cfg.n_angles == 0;
-        r |= ensure(c, p.masks, (size_t)(xyz ? 10 : 9) * d.Mp * 32);
-        for (int l = 0; l < 8; ++l) r |= ensure(c, p.D[l], d.Mp * ldh * ea);
-        r |= ensure(c, p.D[8], d.Mp * (xyz ? ldh : ldh9) * ea);
-        if (xyz) r |= ensure(c, p.D[9], d.Mp * ldh9 * ea);
-        r |= ensure(c, p.dxa, d.Mp * kBwdXyzLd * f);
-        r |= ensure(c, p.dxb, d.Mp * kBwdXyzLd * f);
-        if (c->train->pair16) r |= ensure(c, p.rs, (size_t)10 * d.Mp * sizeof(uint16_t));
-    }
+    if (t->reference) return r;
+    // the fused backward chain's side: mask records, one gradient buffer per layer, the two encoding-gradient parts
+    r |= ensure(c, p.masks, (size_t)(xyz ? 10 : 9) * d.Mp * 32);
+    for (int l = 0; l < 8; ++l) r |= ensure(c, p.D[l], d.Mp * 256 * ea);
+    r |= ensure(c, p.D[8], d.Mp * (xyz ? 256 : 128) * ea);
+    if (xyz) r |= ensure(c, p.D[9], d.Mp * 128 * ea);
+    r |= ensure(c, p.dxa, d.Mp * kBwdXyzLd * f);
+    r |= ensure(c, p.dxb, d.Mp * kBwdXyzLd * f);
+    if (!t->mixed) r |= ensure(c, p.rs, (size_t)10 * d.Mp * sizeof(uint16_t));
     return r;
 }
 
@@ -310,7 +306,7 @@ void fwd_layer(nerf_ctx* c, const TLayer& L, const float* A, int lda, float* Out
     launch_gemm_abt(linear_head ? EPI_FWD_LINEAR : EPI_FWD_LEAKY, linear_head, g, c->stream);
 }
 
-// the Dense stack over Mp encoded rows (C4 / C8 hold the encodings) -> raw_out (Mp x 4)
+// the reference trainer's Dense stack over Mp encoded rows (C4 / C8 hold the encodings) -> raw_out (Mp x 4)
 void forward_layers(nerf_ctx* c, TNet& n, TPass& p, long long Mp, float* raw) {
     float *C4 = (float*)p.C4.p, *C8 = (float*)p.C8.p;
     float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
@@ -341,11 +337,14 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
     TPass& p = t->pass[which];
     float *raw = (float*)p.raw.p, *z = (float*)p.z.p;
     launch_train_encode(o, dirs, z, 0, d.M, d.S, d.Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, 0,
-                        (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed, t->frag);
-    if (t->frag && !n.fstream) return fail("internal: fused training forward without its weight stream");
-    if (t->fused_forward && n.fstream) {
-        // the render path's fused PE + MLP kernel (3-pass split fp16, fp32-class results) with every activation also
-        // written to the buffers the backward GEMMs read: 4x the rate of the layer-wise forward
+                        (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed, !t->reference);
+    if (t->reference) {
+        forward_layers(c, n, p, d.Mp, raw);
+    } else {
+        if (!n.fstream) return fail("internal: fused training forward without its weight stream");
+        // the render path's fused PE + MLP kernel (3-pass split fp16, fp32-class results; one pass under mixed_float16) with
+        // every activation also written to the buffers the weight-gradient GEMMs read, and the LeakyReLU' bit records the
+        // backward chain reads: 4x the rate of the layer-wise forward
         MlpArgs a{};
         a.wstream = (const float*)n.fstream; a.wconst = n.fcst;
         a.in_a = o; a.in_b = dirs; a.z = z; a.raw = raw; a.nonfinite = c->nonfinite;
@@ -354,7 +353,7 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
         float* dst[10] = {(float*)p.H1.p, (float*)p.H2.p, (float*)p.H3.p, (float*)p.C4.p, (float*)p.H5.p,
                           (float*)p.H6.p, (float*)p.H7.p, (float*)p.C8.p, xyz ? (float*)p.H8b.p : (float*)p.H9.p,
                           xyz ? (float*)p.H9.p : nullptr};
-        const int ld[10] = {t->ldh, t->ldh, t->ldh, kLdC4, t->ldh, t->ldh, t->ldh, kLdC8, xyz ? t->ldh : t->ldh9, t->ldh9};
+        const int ld[10] = {256, 256, 256, kLdC4, 256, 256, 256, kLdC8, xyz ? 256 : 128, 128};
         for (int i = 0; i < (xyz ? 10 : 9); ++i) {
             a.st_ptr[i] = dst[i]; a.st_ld[i] = ld[i];
             a.mask_ptr[i] = p.masks.p ? (uint32_t*)p.masks.p + (size_t)i * d.Mp * 8 : nullptr;
@@ -364,8 +363,6 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
 #endif
         if (c->cfg.n_pos_enc_xyz > kLx) wide::launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
         else launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
-    } else {
-        forward_layers(c, n, p, d.Mp, raw);
     }
     launch_composite(raw, z, d.N, d.S, (float*)p.rgb.p, (float*)p.w.p, (float*)p.T.p, nullptr, nullptr, nullptr,
                      c->stream);
@@ -380,7 +377,6 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
 struct WgradQueue {
     GemmAtbBatch gemm{};
     ReduceBatch red{};
-    bool open = false;
 };
 
 // floats of partial sums a batched launch needs: the layout loop of wgrad_flush, for the slab count it would choose
@@ -399,7 +395,6 @@ int join_side(nerf_ctx* c, TrainState* t) {       // the main stream waits for t
 }
 
 int wgrad_flush(nerf_ctx* c, TrainState* t, WgradQueue& q, long long Mp, bool on_side = false) {
-    q.open = false;
     if (q.gemm.n == 0) return 0;
     hipStream_t st = c->stream;
     DevBuf* pb = &t->partial;
@@ -437,9 +432,8 @@ int wgrad_flush(nerf_ctx* c, TrainState* t, WgradQueue& q, long long Mp, bool on
         q.red.e[e].splits = splits;
         off += (size_t)splits * (g.Kp + 1) * g.Nw;
     }
-    if (t->mixed) launch_gemm_atb_f16_batch(q.gemm, st, true);
-    else if (q.gemm.e[0].g_rs) launch_gemm_atb_p_batch(q.gemm, st, true);     // (one format per trainer: all entries agree)
-    else launch_gemm_atb_h_batch(q.gemm, st, true);
+    if (t->mixed) launch_gemm_atb_f16_batch(q.gemm, st);
+    else launch_gemm_atb_p_batch(q.gemm, st);
     launch_reduce_grad_batch(q.red, st);
     q.gemm.n = q.red.n = 0;
     if (on_side) {
@@ -449,75 +443,92 @@ int wgrad_flush(nerf_ctx* c, TrainState* t, WgradQueue& q, long long Mp, bool on
     return 0;
 }
 
-// -> true if the GEMM also produced the weight gradient of head `sig_layer` (else the caller launches that head by itself)
-bool wgrad(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* G, int ldg, int Ncols,
-           int n_src_off, long long Mp, const unsigned* gmax = nullptr, WgradQueue* q = nullptr,
-           const uint16_t* g_rs = nullptr /* pair16: G's row factors */,
-           int sig_layer = -1 /* this GEMM also produces the weight gradient of head `sig_layer` (input = A) from t->dsig */) {
+// One weight-gradient launch of layer l and its reduction into the gradient blob: the GEMM's operands, the row slabs (about
+// `want_splits` of them, whole multiples of `row_quantum` rows), the slab sums' destination
+struct Wgrad { GemmAtb g; ReduceArgs r; int splits; };
+
+Wgrad wgrad_args(TrainState* t, TNet& n, int l, const float* A, int lda, const float* G, int ldg, int Ncols, int n_src_off,
+                 long long Mp, int want_splits, int row_quantum) {
     const TLayer& L = n.L[l];
-    GemmAtb g{};
+    Wgrad w{};
+    GemmAtb& g = w.g;
     g.A = A; g.lda = lda; g.K = L.Kp; g.G = G; g.ldg = ldg; g.N = Ncols;
     g.partial = (float*)t->partial.p; g.Kp = L.Kp; g.Nw = Ncols; g.M = Mp;
-    // the heads' (K x 4) results come from a VALU kernel that wants many small slabs; the GEMMs use kTrainSplits
-    const bool f16 = (t->wgrad_f16 && gmax && Ncols >= 128) || (t->mixed && Ncols >= 128);
-    const bool wide = f16 && t->wgrad_wide && Ncols >= 256;
     g.a_f16 = t->mixed ? 1 : 0;
-    g.frag = t->frag ? 1 : 0;
-    g.g_rs = f16 && !t->mixed ? g_rs : nullptr;
-    const int want_splits = Ncols == 4 ? 1024 : wide ? kTrainSplitsWide : kTrainSplits;
     long long rps = (Mp + want_splits - 1) / want_splits;
-    rps = t->frag ? (rps + 31) / 32 * 32 : (rps + 15) / 16 * 16;     // fragment-major operands: whole 32-row blocks
+    rps = (rps + row_quantum - 1) / row_quantum * row_quantum;
     g.rows_per_split = (int)rps;
-    g.gmax = gmax;
-    ReduceArgs r{};
-    r.Kp = L.Kp; r.Nw = Ncols;
+    w.splits = (int)((Mp + rps - 1) / rps);
+    ReduceArgs& r = w.r;
+    r.partial = g.partial; r.Kp = L.Kp; r.Nw = Ncols; r.splits = w.splits;
     r.grad_w = n.grad + L.w_off; r.grad_b = n.grad + L.b_off;
     r.K_real = L.K_real; r.N_real = L.N_real; r.n_src_off = n_src_off; r.rowmap = L.rowmap;
     r.accumulate = t->acc_grads ? 1 : 0;
-    if (q && q->open && wide && reduce_grad_is_wide(r) && q->gemm.n < kWgradBatchMax) {
-        q->gemm.e[q->gemm.n++] = g;               // slabs and partial regions are laid out by wgrad_flush
-        q->red.e[q->red.n++] = r;
-        return false;
+    return w;
+}
+
+// The reference trainer: exact fp32 MFMA (the heads: the VALU kernel) over row-major operands, 16-row slab quantum
+void wgrad_reference(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* G, int ldg, int Ncols,
+                     int n_src_off, long long Mp) {
+    // the heads' (K x 4) results come from a VALU kernel that wants many small slabs; their inputs are H9 (128 wide) and
+    // C8 (kLdC8 wide, its first 256 columns for the xyz-only network's sigma head): whole, 16-byte-aligned column quads,
+    // at most 256 of them, as head_wgrad_rows_kernel requires
+    static_assert(kLdC8 % 4 == 0 && kLdC8 <= 1024, "head_wgrad_rows_kernel: Kp % 4 == 0, Kp <= 1024, lda % 4 == 0");
+    const Wgrad w = wgrad_args(t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp, Ncols == 4 ? 1024 : kTrainSplits, 16);
+    if (Ncols == 4) launch_head_wgrad(w.g, false, c->stream);
+    else launch_gemm_atb(w.g, c->stream);
+    launch_reduce_grad(w.r, c->stream);
+}
+
+// The fused trainer's three forms (fragment-major operands: slabs of whole 32-row blocks).  D: layer l's pre-activation
+// gradient from the backward chain, rs / gmax: its row factors (pair16, float32 policy; else null) and max|D| slots.
+// A 256-wide layer joins the pass's batched launch.  wgrad_flush owns the slab layout of a queued entry: it sets
+// rows_per_split, partial and splits of both halves for the batch as a whole, whatever wgrad_args put there.
+int wgrad_queue(TrainState* t, TNet& n, int l, const float* A, int lda, const float* D, const uint16_t* rs,
+                const unsigned* gmax, long long Mp, WgradQueue& q) {
+    if (q.gemm.n >= kWgradBatchMax) return fail("internal: more 256-wide layers than a batched weight-gradient launch holds");
+    Wgrad w = wgrad_args(t, n, l, A, lda, D, 256, 256, 0, Mp, kTrainSplitsWide, 32);
+    w.g.g_rs = rs; w.g.gmax = gmax;
+    q.gemm.e[q.gemm.n++] = w.g;
+    q.red.e[q.red.n++] = w.r;
+    return 0;
+}
+
+// The 128-wide layer (8; 9 in the xyz-only network) on the 128 tile.  sig_layer >= 0: the GEMM also produces the weight gradient
+// of that head (the sigma head: its input is A = C8, its gradient t->dsig) -- it stages C8 anyway, no second pass over that buffer;
+// the head's slab sums land behind this GEMM's.
+void wgrad_tile128(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* D, const uint16_t* rs,
+                   const unsigned* gmax, long long Mp, int sig_layer = -1) {
+    Wgrad w = wgrad_args(t, n, l, A, lda, D, 128, 128, 0, Mp, kTrainSplits, 32);
+    w.g.g_rs = rs; w.g.gmax = gmax;
+    if (sig_layer >= 0) {
+        w.g.sig_g = (const float*)t->dsig.p;
+        w.g.sig_partial = w.g.partial + (size_t)w.splits * (w.g.Kp + 1) * w.g.Nw;
     }
-    const int n_splits = (int)((Mp + rps - 1) / rps);
-    // the sigma head rides in this GEMM (gemm_atb_p / gemm_atb_f16, 128-wide tile): its slab sums land behind this GEMM's
-    const bool sig = sig_layer >= 0 && t->frag && !wide && Ncols == 128 && (t->mixed || g.g_rs) && t->dsig.p;
-    if (sig) {
-        g.sig_g = (const float*)t->dsig.p;
-        g.sig_partial = g.partial + (size_t)n_splits * (g.Kp + 1) * g.Nw;
-    }
-    if (Ncols == 4) launch_head_wgrad(g, c->stream);
-    else if (t->mixed) launch_gemm_atb_f16(g, c->stream, wide);
-    else if (g.g_rs) launch_gemm_atb_p(g, c->stream, wide);
-    else if (f16) launch_gemm_atb_h(g, c->stream, wide);
-    else launch_gemm_atb(g, c->stream);
-    r.partial = g.partial; r.splits = n_splits;
-    launch_reduce_grad(r, c->stream);
-    if (sig) {
+    if (t->mixed) launch_gemm_atb_f16(w.g, c->stream);
+    else launch_gemm_atb_p(w.g, c->stream);
+    launch_reduce_grad(w.r, c->stream);
+    if (sig_layer >= 0) {
         const TLayer& Ls = n.L[sig_layer];
-        ReduceArgs rs{};
-        rs.partial = g.sig_partial; rs.Kp = g.Kp; rs.Nw = 1; rs.splits = n_splits;
-        rs.grad_w = n.grad + Ls.w_off; rs.grad_b = n.grad + Ls.b_off;
-        rs.K_real = Ls.K_real; rs.N_real = 1; rs.n_src_off = 0; rs.rowmap = Ls.rowmap;
-        rs.accumulate = t->acc_grads ? 1 : 0;
-        launch_reduce_grad(rs, c->stream);
+        ReduceArgs sig_r{};
+        sig_r.partial = w.g.sig_partial; sig_r.Kp = w.g.Kp; sig_r.Nw = 1; sig_r.splits = w.splits;
+        sig_r.grad_w = n.grad + Ls.w_off; sig_r.grad_b = n.grad + Ls.b_off;
+        sig_r.K_real = Ls.K_real; sig_r.N_real = 1; sig_r.n_src_off = 0; sig_r.rowmap = Ls.rowmap;
+        sig_r.accumulate = t->acc_grads ? 1 : 0;
+        launch_reduce_grad(sig_r, c->stream);
     }
-    return sig;
+}
+
+// A head (4-wide G = column n_src_off.. of Graw, row-major) on the VALU kernel, which wants many small slabs
+void wgrad_head(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, int n_src_off, long long Mp) {
+    const Wgrad w = wgrad_args(t, n, l, A, lda, (const float*)t->Graw.p, 4, 4, n_src_off, Mp, 1024, 32);
+    launch_head_wgrad(w.g, true, c->stream);
+    launch_reduce_grad(w.r, c->stream);
 }
 
 void dgrad(nerf_ctx* c, const float* G, int ldg, int Kg, const float* Wrows, int ldb, int Nout, const float* H, int ldh,
-           float* Out, int ldo, long long Mp, unsigned* gmax_out, const float* r1a = nullptr, const float* r1b = nullptr,
-           const TLayer* split = nullptr, const unsigned* gmax_in = nullptr) {
+           float* Out, int ldo, long long Mp, const float* r1a = nullptr, const float* r1b = nullptr) {
     GemmAbt g{};
-    g.gmax = gmax_out;
-    if (split && gmax_in && Nout % 128 == 0 && Kg % 32 == 0) {     // fp16 matrix cores: W comes pre-split (rows 0.. of W)
-        g.A = G; g.lda = ldg; g.ldb = ldb; g.Out = Out; g.ldo = ldo;
-        g.M = Mp; g.N = Nout; g.K = Kg; g.H = H; g.ldh = ldh; g.r1a = r1a; g.r1a_ld = 4; g.r1b = r1b;
-        g.n_valid = Nout; g.alpha = c->cfg.leaky_relu_alpha;
-        g.Bhi = split->Whi; g.Blo = split->Wlo; g.gmax_in = gmax_in;
-        launch_gemm_abt_h(g, c->stream);
-        return;
-    }
     g.A = G; g.lda = ldg; g.Bt = Wrows; g.ldb = ldb; g.Out = Out; g.ldo = ldo;
     g.M = Mp; g.N = Nout; g.K = Kg; g.H = H; g.ldh = ldh; g.r1a = r1a; g.r1a_ld = 4; g.r1b = r1b;
     g.n_valid = Nout; g.alpha = c->cfg.leaky_relu_alpha;
@@ -531,10 +542,79 @@ void dgrad_xyz(nerf_ctx* c, const float* G, const float* Wrows, float* dA0, long
     launch_gemm_abt(EPI_BWD_PLAIN, true, g, c->stream);
 }
 
-// Graw (Mp x 4, padding rows zero) must be filled; writes n.grad; with d_z != NULL adds dL/dz through the
-// sample positions (d_z must already hold the compositing part).
-int backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs,
-                  float* d_z) {
+// The two backward passes below: Graw (Mp x 4, padding rows zero) must be filled; they write n.grad; with d_z != NULL they
+// add dL/dz through the sample positions (d_z must already hold the compositing part).
+
+// The fused trainer: ONE kernel for the whole data-gradient chain (mlp_bwd_f16x3.hip: the gradient stays on the lane from
+// layer to layer; every D_l is written once, with max|D_l| in the pass's gmax slots), then the weight gradients from the
+// stashed activations and the D_l.
+int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z) {
+    TNet& n = t->net[which];
+    TPass& p = t->pass[which];
+    const long long Mp = d.Mp;
+    float *C4 = (float*)p.C4.p, *C8 = (float*)p.C8.p;
+    float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
+          *H6 = (float*)p.H6.p, *H7 = (float*)p.H7.p, *H9 = (float*)p.H9.p;
+    // gm + 64 k: bits of max|D| of the gradient buffer the chain produces k-th in this pass (scale of gemm_atb_p's operand;
+    // gemm_atb_f16 reads none: no reset under mixed_float16)
+    unsigned* gm = t->gmax.p ? (unsigned*)t->gmax.p + (size_t)which * 16 * 64 : nullptr;   // per pass
+    if (!(n.bstream && n.fcst && p.masks.p && gm))
+        return fail("internal: fused training backward without its stream / mask records");
+    if (!t->mixed) HIP_OK(hipMemsetAsync(gm, 0, 16 * 64 * sizeof(unsigned), c->stream));
+    MlpBwdArgs b{};
+    b.wstream = n.bstream; b.wconst = n.fcst; b.graw = (const float*)t->Graw.p; b.gmax = gm; b.Mp = Mp;
+    b.alpha = c->cfg.leaky_relu_alpha;
+    b.ld = 256; b.ld9 = 128;
+    const bool xyz = n.n_layers == 12;
+    const int nrec = xyz ? 10 : 9;                   // mask records / gradient buffers; gmax group k <-> d_ptr[nrec - 1 - k]
+    for (int l = 0; l < nrec; ++l) {
+        b.mask_ptr[l] = (const uint32_t*)p.masks.p + (size_t)l * Mp * 8;
+        b.d_ptr[l] = (float*)p.D[l].p;
+        b.rs_ptr[l] = t->mixed ? nullptr : (uint16_t*)p.rs.p + (size_t)l * Mp;     // row factors of d_ptr[l] (pair16)
+    }
+    b.dx_ptr[0] = (float*)p.dxa.p; b.dx_ptr[1] = (float*)p.dxb.p;
+    b.dsig = xyz ? nullptr : (float*)t->dsig.p;
+    launch_mlp_bwd_f16x3(b, n.bdx, t->mixed, c->num_cus, c->stream, xyz);
+    WgradQueue wq;
+    // layer l's gradient buffer is d_ptr[l], its gmax group nrec - 1 - l
+    auto queue = [&](int l, const float* A, int lda) {
+        return wgrad_queue(t, n, l, A, lda, b.d_ptr[l], b.rs_ptr[l], gm + 64 * (nrec - 1 - l), Mp, wq);
+    };
+    if (xyz) {
+        // get_network_only_xyz (src/NeRF.py:248-288): 10 = the rgb head on h9, 11 = the sigma head on h8 (the first 256
+        // columns of C8), 9 = 256 -> 128 on the extra layer's output, 8 = that extra 256 -> 256 layer on h8
+        wgrad_head(c, t, n, 10, H9, 128, 0, Mp);
+        wgrad_head(c, t, n, 11, C8, kLdC8, 3, Mp);
+        wgrad_tile128(c, t, n, 9, (const float*)p.H8b.p, 256, b.d_ptr[9], b.rs_ptr[9], gm, Mp);
+        if (int r = queue(8, C8, kLdC8)) return r;
+    } else {
+        wgrad_head(c, t, n, 9, H9, 128, 0, Mp);
+        // the sigma head (layer 10: input C8 = [h8 | dir_enc], gradient column 3 of Graw) rides in layer 8's GEMM
+        wgrad_tile128(c, t, n, 8, C8, kLdC8, b.d_ptr[8], b.rs_ptr[8], gm, Mp, 10);
+    }
+    // (the xyz encoding's columns 256.. of C4: in the fragment-major buffer a column offset c is 32 c ELEMENTS --
+    // half the byte offset under the fp16 policy)
+    const size_t xyz_off = (size_t)32 * 256;
+    const float* c4_xyz = t->mixed ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(C4) + xyz_off) : C4 + xyz_off;
+    const float* in[8] = {c4_xyz, H1, H2, H3, C4, H5, H6, H7};       // input of layer l
+    for (int l = 7; l >= 0; --l)
+        if (int r = queue(l, in[l], l == 0 || l == 4 ? kLdC4 : 256)) return r;
+    // the fine pass's batched launch can run beside the coarse pass's backward (which reads none of its operands)
+    if (int r = wgrad_flush(c, t, wq, Mp, t->overlap && which == 1 && !t->acc_grads)) return r;
+    if (d_z) {
+        if (!n.bdx) return fail("internal: the sampler term needs the backward stream with encoding tiles");
+        // the chain's encoding tiles are laid out for kLx (wide-PE: kLxWide) octaves; the ones the network lacks carry
+        // zero gradient
+        launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
+                      d_z, c->stream, true);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// The reference trainer: layer by layer, the data gradient (gemm_abt, LeakyReLU' mask from the stored activation) ping-pongs
+// between Ga and Gb, each layer's weight gradient follows from its stored input
+int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     const long long Mp = d.Mp;
@@ -544,110 +624,43 @@ int backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, cons
     float *Ga = (float*)t->Ga.p, *Gb = (float*)t->Gb.p, *G9 = (float*)t->G9.p, *Graw = (float*)t->Graw.p,
           *dA0 = (float*)t->dA0.p;
     const bool dx = d_z != nullptr;
-    // gm[k]: bits of max|G| of the gradient buffer produced k-th in this pass (scale of the split-fp16 weight gradient)
-    // exact-fp32 weight gradients need no scale (but the fused chain always reports its maxima)
-    unsigned* gm = t->wgrad_f16 || t->fused_backward ? (unsigned*)t->gmax.p + (size_t)which * 16 * 64 : nullptr;   // per pass
-    // (the max|D| slots feed the split-fp16 weight gradients' scale; gemm_atb_f16 reads none: no reset under mixed_float16)
-    if (gm && !t->mixed) HIP_OK(hipMemsetAsync(gm, 0, 16 * 64 * sizeof(unsigned), c->stream));
-    auto GM = [&](int k) -> unsigned* { return gm ? gm + 64 * k : nullptr; };
-    auto DS = [&](int l) -> const TLayer* { return t->dgrad_f16 && gm ? &n.L[l] : nullptr; };   // pre-split W of layer l
-    if (t->frag && !(n.bstream && n.fcst && p.masks.p && gm))
-        return fail("internal: fused training backward without its stream / mask records");
-    if (t->fused_backward && n.bstream && n.fcst && p.masks.p && gm) {
-        // ONE kernel for the whole data-gradient chain (mlp_bwd_f16x3.hip): the gradient stays on the lane from layer to
-        // layer; every D_l is written once for the weight-gradient GEMMs below, with max|D_l| in the same gmax slots
-        MlpBwdArgs b{};
-        b.wstream = n.bstream; b.wconst = n.fcst; b.graw = Graw; b.gmax = gm; b.Mp = Mp; b.alpha = c->cfg.leaky_relu_alpha;
-        b.ld = t->ldh; b.ld9 = t->ldh9;
-        const int ldh = t->ldh, ldh9 = t->ldh9;
-        const bool xyz = n.n_layers == 12;
-        const int nrec = xyz ? 10 : 9;                   // mask records / gradient buffers; gmax group k <-> d_ptr[nrec - 1 - k]
-        for (int l = 0; l < nrec; ++l) {
-            b.mask_ptr[l] = (const uint32_t*)p.masks.p + (size_t)l * Mp * 8;
-            b.d_ptr[l] = (float*)p.D[l].p;
-            b.rs_ptr[l] = t->pair16 ? (uint16_t*)p.rs.p + (size_t)l * Mp : nullptr;
-        }
-        b.dx_ptr[0] = (float*)p.dxa.p; b.dx_ptr[1] = (float*)p.dxb.p;
-        b.dsig = xyz ? nullptr : (float*)t->dsig.p;
-        launch_mlp_bwd_f16x3(b, n.bdx, t->mixed, c->num_cus, c->stream, xyz);
-        WgradQueue wq;
-        auto RS = [&](int l) -> const uint16_t* { return t->pair16 ? b.rs_ptr[l] : nullptr; };   // row factors of d_ptr[l]
-        if (xyz) {
-            // get_network_only_xyz (src/NeRF.py:248-288): 10 = the rgb head on h9, 11 = the sigma head on h8 (the first 256
-            // columns of C8), 9 = 256 -> 128 on the extra layer's output, 8 = that extra 256 -> 256 layer on h8
-            float* H8b = (float*)p.H8b.p;
-            wgrad(c, t, n, 10, H9, ldh9, Graw, 4, 4, 0, Mp);
-            wgrad(c, t, n, 11, C8, kLdC8, Graw, 4, 4, 3, Mp);
-            wgrad(c, t, n, 9, H8b, ldh, b.d_ptr[9], ldh9, 128, 0, Mp, GM(0), nullptr, RS(9));
-            wq.open = t->wgrad_wide;
-            wgrad(c, t, n, 8, C8, kLdC8, b.d_ptr[8], ldh, 256, 0, Mp, GM(1), &wq, RS(8));
-        } else {
-            wgrad(c, t, n, 9, H9, ldh9, Graw, 4, 4, 0, Mp);
-            // the sigma head (layer 10: input C8 = [h8 | dir_enc], gradient column 3 of Graw) rides in layer 8's GEMM, which
-            // stages C8 anyway -- no second pass over that buffer
-            if (!wgrad(c, t, n, 8, C8, kLdC8, b.d_ptr[8], ldh9, 128, 0, Mp, GM(0), nullptr, RS(8), 10))
-                wgrad(c, t, n, 10, C8, kLdC8, Graw, 4, 4, 3, Mp);      // (a build without the by-product path: -DNERF_PAIR16=0, float32 policy)
-            wq.open = t->wgrad_wide;
-        }
-        const int g0 = xyz ? 1 : 0;                      // gmax group of D_l is g0 + 8 - l
-        wgrad(c, t, n, 7, H7, ldh, b.d_ptr[7], ldh, 256, 0, Mp, GM(g0 + 1), &wq, RS(7));
-        wgrad(c, t, n, 6, H6, ldh, b.d_ptr[6], ldh, 256, 0, Mp, GM(g0 + 2), &wq, RS(6));
-        wgrad(c, t, n, 5, H5, ldh, b.d_ptr[5], ldh, 256, 0, Mp, GM(g0 + 3), &wq, RS(5));
-        wgrad(c, t, n, 4, C4, kLdC4, b.d_ptr[4], ldh, 256, 0, Mp, GM(g0 + 4), &wq, RS(4));
-        wgrad(c, t, n, 3, H3, ldh, b.d_ptr[3], ldh, 256, 0, Mp, GM(g0 + 5), &wq, RS(3));
-        wgrad(c, t, n, 2, H2, ldh, b.d_ptr[2], ldh, 256, 0, Mp, GM(g0 + 6), &wq, RS(2));
-        wgrad(c, t, n, 1, H1, ldh, b.d_ptr[1], ldh, 256, 0, Mp, GM(g0 + 7), &wq, RS(1));
-        // (the xyz encoding's columns 256.. of C4: in the fragment-major buffer a column offset c is 32 c ELEMENTS --
-        // half the byte offset under the fp16 policy)
-        const size_t xyz_off = (size_t)32 * 256;
-        const float* c4_xyz = t->mixed ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(C4) + xyz_off) : C4 + xyz_off;
-        wgrad(c, t, n, 0, c4_xyz, kLdC4, b.d_ptr[0], ldh, 256, 0, Mp, GM(g0 + 8), &wq, RS(0));
-        // the fine pass's batched launch can run beside the coarse pass's backward (which reads none of its operands)
-        if (int r = wgrad_flush(c, t, wq, Mp, t->overlap && which == 1 && !t->acc_grads)) return r;
-        if (dx) {
-            if (!n.bdx) return fail("internal: the sampler term needs the backward stream with encoding tiles");
-            // the chain's encoding tiles are laid out for kLx (wide-PE: kLxWide) octaves; the ones the network lacks carry
-            // zero gradient
-            launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
-                          d_z, c->stream, true);
-        }
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
+    auto wgrad = [&](int l, const float* A, int lda, const float* G, int ldg, int Ncols, int n_src_off = 0) {
+        wgrad_reference(c, t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp);
+    };
     if (n.n_layers == 11) {
-        wgrad(c, t, n, 9, H9, 128, Graw, 4, 4, 0, Mp);
-        wgrad(c, t, n, 10, C8, kLdC8, Graw, 4, 4, 3, Mp);
-        launch_head_bwd(Graw, n.L[9].W, H9, Mp, c->cfg.leaky_relu_alpha, G9, GM(0), c->stream);
-        wgrad(c, t, n, 8, C8, kLdC8, G9, 128, 128, 0, Mp, GM(0));
+        wgrad(9, H9, 128, Graw, 4, 4);
+        wgrad(10, C8, kLdC8, Graw, 4, 4, 3);
+        launch_head_bwd(Graw, n.L[9].W, H9, Mp, c->cfg.leaky_relu_alpha, G9, c->stream);
+        wgrad(8, C8, kLdC8, G9, 128, 128);
         // dL/dh8 = G9 . W8[hidden rows]^T + Graw[:,3] * W10[hidden rows]   (WT10 row 0 = the sigma head's column)
-        dgrad(c, G9, 128, 128, n.L[8].W, 128, 256, C8, kLdC8, Ga, 256, Mp, GM(1), Graw + 3, n.L[10].WT, DS(8), GM(0));
+        dgrad(c, G9, 128, 128, n.L[8].W, 128, 256, C8, kLdC8, Ga, 256, Mp, Graw + 3, n.L[10].WT);
     } else {
         float* H8b = (float*)p.H8b.p;
-        wgrad(c, t, n, 10, H9, 128, Graw, 4, 4, 0, Mp);
-        wgrad(c, t, n, 11, C8, kLdC8, Graw, 4, 4, 3, Mp);
-        launch_head_bwd(Graw, n.L[10].W, H9, Mp, c->cfg.leaky_relu_alpha, G9, GM(0), c->stream);
-        wgrad(c, t, n, 9, H8b, 256, G9, 128, 128, 0, Mp, GM(0));
-        dgrad(c, G9, 128, 128, n.L[9].W, 128, 256, H8b, 256, Gb, 256, Mp, GM(9), nullptr, nullptr, DS(9), GM(0));    // -> pre-activation grad of h8b
-        wgrad(c, t, n, 8, C8, kLdC8, Gb, 256, 256, 0, Mp, GM(9));
+        wgrad(10, H9, 128, Graw, 4, 4);
+        wgrad(11, C8, kLdC8, Graw, 4, 4, 3);
+        launch_head_bwd(Graw, n.L[10].W, H9, Mp, c->cfg.leaky_relu_alpha, G9, c->stream);
+        wgrad(9, H8b, 256, G9, 128, 128);
+        dgrad(c, G9, 128, 128, n.L[9].W, 128, 256, H8b, 256, Gb, 256, Mp);    // -> pre-activation grad of h8b
+        wgrad(8, C8, kLdC8, Gb, 256, 256);
         // dL/dh8 = Gb . W8^T + Graw[:,3] * W11   (WT11 row 0 = the sigma head's column)
-        dgrad(c, Gb, 256, 256, n.L[8].W, 256, 256, C8, kLdC8, Ga, 256, Mp, GM(1), Graw + 3, n.L[11].WT, DS(8), GM(9));
+        dgrad(c, Gb, 256, 256, n.L[8].W, 256, 256, C8, kLdC8, Ga, 256, Mp, Graw + 3, n.L[11].WT);
     }
-    wgrad(c, t, n, 7, H7, 256, Ga, 256, 256, 0, Mp, GM(1));
-    dgrad(c, Ga, 256, 256, n.L[7].W, 256, 256, H7, 256, Gb, 256, Mp, GM(2), nullptr, nullptr, DS(7), GM(1));
-    wgrad(c, t, n, 6, H6, 256, Gb, 256, 256, 0, Mp, GM(2));
-    dgrad(c, Gb, 256, 256, n.L[6].W, 256, 256, H6, 256, Ga, 256, Mp, GM(3), nullptr, nullptr, DS(6), GM(2));
-    wgrad(c, t, n, 5, H5, 256, Ga, 256, 256, 0, Mp, GM(3));
-    dgrad(c, Ga, 256, 256, n.L[5].W, 256, 256, H5, 256, Gb, 256, Mp, GM(4), nullptr, nullptr, DS(5), GM(3));
-    wgrad(c, t, n, 4, C4, kLdC4, Gb, 256, 256, 0, Mp, GM(4));
-    dgrad(c, Gb, 256, 256, n.L[4].W, 256, 256, C4, kLdC4, Ga, 256, Mp, GM(5), nullptr, nullptr, DS(4), GM(4));
+    wgrad(7, H7, 256, Ga, 256, 256);
+    dgrad(c, Ga, 256, 256, n.L[7].W, 256, 256, H7, 256, Gb, 256, Mp);
+    wgrad(6, H6, 256, Gb, 256, 256);
+    dgrad(c, Gb, 256, 256, n.L[6].W, 256, 256, H6, 256, Ga, 256, Mp);
+    wgrad(5, H5, 256, Ga, 256, 256);
+    dgrad(c, Ga, 256, 256, n.L[5].W, 256, 256, H5, 256, Gb, 256, Mp);
+    wgrad(4, C4, kLdC4, Gb, 256, 256);
+    dgrad(c, Gb, 256, 256, n.L[4].W, 256, 256, C4, kLdC4, Ga, 256, Mp);
     if (dx) dgrad_xyz(c, Gb, n.L[4].W + (size_t)256 * 256, dA0, Mp, false);     // skip connection's xyz rows
-    wgrad(c, t, n, 3, H3, 256, Ga, 256, 256, 0, Mp, GM(5));
-    dgrad(c, Ga, 256, 256, n.L[3].W, 256, 256, H3, 256, Gb, 256, Mp, GM(6), nullptr, nullptr, DS(3), GM(5));
-    wgrad(c, t, n, 2, H2, 256, Gb, 256, 256, 0, Mp, GM(6));
-    dgrad(c, Gb, 256, 256, n.L[2].W, 256, 256, H2, 256, Ga, 256, Mp, GM(7), nullptr, nullptr, DS(2), GM(6));
-    wgrad(c, t, n, 1, H1, 256, Ga, 256, 256, 0, Mp, GM(7));
-    dgrad(c, Ga, 256, 256, n.L[1].W, 256, 256, H1, 256, Gb, 256, Mp, GM(8), nullptr, nullptr, DS(1), GM(7));
-    wgrad(c, t, n, 0, C4 + 256, kLdC4, Gb, 256, 256, 0, Mp, GM(8));
+    wgrad(3, H3, 256, Ga, 256, 256);
+    dgrad(c, Ga, 256, 256, n.L[3].W, 256, 256, H3, 256, Gb, 256, Mp);
+    wgrad(2, H2, 256, Gb, 256, 256);
+    dgrad(c, Gb, 256, 256, n.L[2].W, 256, 256, H2, 256, Ga, 256, Mp);
+    wgrad(1, H1, 256, Ga, 256, 256);
+    dgrad(c, Ga, 256, 256, n.L[1].W, 256, 256, H1, 256, Gb, 256, Mp);
+    wgrad(0, C4 + 256, kLdC4, Gb, 256, 256);
     if (dx) {
         dgrad_xyz(c, Gb, n.L[0].W, dA0, Mp, true);
         launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, d_z, c->stream);
@@ -665,7 +678,8 @@ int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDim
     HIP_OK(hipMemsetAsync(Graw + pd.M * 4, 0, (pd.Mp - pd.M) * 4 * sizeof(float), c->stream));
     launch_composite_bwd((const float*)p.raw.p, (const float*)p.z.p, (const float*)p.T.p, pd.N, pd.S, d_rgb, d_wext, Graw,
                          d_z, c->stream);
-    return backward_pass(c, t, which, pd, o, dirs, d_z);
+    return t->reference ? backward_reference(c, t, which, pd, o, dirs, d_z)
+                        : backward_fused(c, t, which, pd, o, dirs, d_z);
 }
 
 // the sample counts of a training call; *fine: whether the fine pass runs
@@ -686,15 +700,18 @@ int check_samples(const TrainState* t, long long N, int Sc, int Sf, bool* fine) 
 // the buffers every backward needs, for passes of up to Mmax (padded) rows and a coarse pass of Mc rows
 int ensure_bwd_workspace(nerf_ctx* c, TrainState* t, long long Mmax, long long Mc) {
     const size_t f = sizeof(float);
-    int r = ensure(c, t->Ga, Mmax * 256 * f);
-    r |= ensure(c, t->Gb, Mmax * 256 * f);
-    r |= ensure(c, t->G9, Mmax * 128 * f);
-    r |= ensure(c, t->Graw, Mmax * 4 * f);
-    r |= ensure(c, t->dsig, Mmax * f);
-    r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
+    int r = ensure(c, t->Graw, Mmax * 4 * f);
     r |= ensure(c, t->partial, (size_t)2 * kTrainSplitsWide * (kLdC4 + 1) * 256 * f);   // also holds a pass's batched slabs
     r |= ensure(c, t->d_wext, Mc * f);
-    r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
+    if (t->reference) {     // the layer-wise data gradients' buffers (the fused chain keeps its own per pass: TPass::D, dxa, dxb)
+        r |= ensure(c, t->Ga, Mmax * 256 * f);
+        r |= ensure(c, t->Gb, Mmax * 256 * f);
+        r |= ensure(c, t->G9, Mmax * 128 * f);
+        r |= ensure(c, t->dA0, Mmax * kXyzPad * f);
+    } else {
+        r |= ensure(c, t->dsig, Mmax * f);
+        r |= ensure(c, t->gmax, 2 * 16 * 64 * sizeof(unsigned));
+    }
     return r;
 }
 
@@ -709,7 +726,7 @@ int stage_in(nerf_ctx* c, DevBuf& b, const float* src, size_t bytes, int mem, co
 int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const float* target, int64_t N, int Sc,
                    int Sf, const float* u_c, const float* u_f, uint64_t seed, int mem) {
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d || !target) return fail("NULL argument");
     bool fine;
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
@@ -911,7 +928,7 @@ static void swap_grad_members(TPass& a, TPass& b) {
     std::swap(a.dxb, b.dxb);
     std::swap(a.rs, b.rs);
 }
-// the slot's stash becomes TrainState::pass (which forward_pass / backward_pass work on), keeping the working gradient buffers
+// the slot's stash becomes TrainState::pass (which forward_pass / the backward passes work on), keeping the working gradient buffers
 static void slot_swap_in(TrainState* t, RenderSlot& s) {
     for (int w = 0; w < 2; ++w) {
         std::swap(t->pass[w], s.pass[w]);
@@ -952,7 +969,7 @@ int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d,
                           int Sf, const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, bool accumulate,
                           int mem) {
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d || !d_rgb_in) return fail("NULL argument");
     bool fine;
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
@@ -973,7 +990,7 @@ int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d,
 int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float* rays_d, int64_t N, int Sc, int Sf,
                         const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, int mem) {
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d) return fail("NULL argument");
     if (slot < 0 || slot >= kMaxRenderSlots) return fail("slot %d out of range (0..%d)", slot, kMaxRenderSlots - 1);
     bool fine;
@@ -1008,7 +1025,7 @@ int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float*
 
 int render_backward_impl(nerf_ctx* c, int slot, const float* d_rgb_in, bool accumulate, int mem) {
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     if (!d_rgb_in) return fail("NULL argument");
     if (slot < 0 || (size_t)slot >= t->slots.size() || !t->slots[slot].valid)
         return fail("slot %d holds no forward pass (nerf_train_render_forward first; a backward pass consumes it, and so does "
@@ -1209,20 +1226,16 @@ int nerf_train_begin(nerf_ctx* c, const nerf_train_config* cfg) {
     if (!cfg) return fail("nerf_train_config is NULL");
     if (!(cfg->learning_rate > 0.f)) return fail("learning_rate must be positive");
     if (!c->net[0].loaded) return fail("load the coarse network's weights before nerf_train_begin");
-    if (c->train && c->train->training) {
+    if (c->train) {
         // a trainer restarted without nerf_train_end goes on from the TRAINED weights ("the weights currently loaded")
         for (int w = 0; w < 2; ++w)
             if (int r = train_flush_weights(c, w, true)) return r;
         train_free(c);
     }
-    TrainState* t = c->train;           // an inference-only state (xyz-only network) is promoted in place
-    if (!t) {
-        t = new TrainState();
-        t->nblob = nerf_blob_size(&c->cfg);
-        c->train = t;
-    }
+    TrainState* t = new TrainState();
+    t->nblob = nerf_blob_size(&c->cfg);
+    c->train = t;
     t->cfg = *cfg;
-    t->training = true;
     t->loss_w[0] = t->loss_w[1] = 1.f;
     t->mixed = cfg->mixed_float16 != 0;
     {
@@ -1237,46 +1250,19 @@ int nerf_train_begin(nerf_ctx* c, const nerf_train_config* cfg) {
         if (int r = ensure(c, t->opt, sizeof(OptState))) { train_free(c); return r; }
         HIP_OK(hipMemcpy(t->opt.p, &h, sizeof(OptState), hipMemcpyHostToDevice));
     }
-    // forward on the fused kernel unless the network has no fused kernel (xyz-only) or NERF_TRAIN_FORWARD=gemm asks
-    // for the layer-wise fp32 GEMM forward (exact fp32 products instead of the 3-pass split)
+    // the fused trainer unless NERF_TRAIN_FORWARD=gemm asks for the layer-wise exact-fp32 one (TrainState::reference)
     const char* fw = getenv("NERF_TRAIN_FORWARD");
-    t->fused_forward = !(fw && strcmp(fw, "gemm") == 0);
-    // weight gradients on the fp16 matrix cores (split operands, fp32-class) unless NERF_TRAIN_WGRAD=fp32
-    const char* wg = getenv("NERF_TRAIN_WGRAD");
-    t->wgrad_f16 = !(wg && strcmp(wg, "fp32") == 0);
-    const char* ww = getenv("NERF_TRAIN_WGRAD_TILE");
-    t->wgrad_wide = !(ww && strcmp(ww, "128") == 0);
-    const char* dg = getenv("NERF_TRAIN_DGRAD");
-    t->dgrad_f16 = t->wgrad_f16 && !(dg && strcmp(dg, "fp32") == 0);     // needs the max tracking of the f16 path
-    // data gradients by the fused chain kernel (the stash forward's counterpart) unless NERF_TRAIN_BACKWARD=layers asks
-    // for the layer-by-layer GEMMs; it reads the forward's mask records, so it needs the fused forward
-    const char* bw = getenv("NERF_TRAIN_BACKWARD");
-    t->fused_backward = t->fused_forward && t->dgrad_f16 && !(bw && strcmp(bw, "layers") == 0);
+    t->reference = fw && strcmp(fw, "gemm") == 0;
     // the fine pass's batched weight-gradient launch on a second stream (see TrainState::overlap) unless NERF_TRAIN_OVERLAP=0
     const char* ov = getenv("NERF_TRAIN_OVERLAP");
     t->overlap = !(ov && strcmp(ov, "0") == 0);
-    t->ldh = 256; t->ldh9 = 128;
-    // the fused forward writes fragment-major buffers that only the fused backward and the weight-gradient kernels read:
-    // both fused or neither (NERF_TRAIN_BACKWARD=layers, NERF_TRAIN_WGRAD / NERF_TRAIN_DGRAD=fp32 select the layer-wise
-    // GEMM forward as well)
-    if (!t->fused_backward) t->fused_forward = false;
-    t->frag = t->fused_forward && t->fused_backward;
-    t->pair16 = kPair16 && t->frag && !t->mixed;
-    if (t->mixed && !(t->fused_forward && t->fused_backward)) {
+    if (t->mixed && t->reference) {
         train_free(c);
-        return fail("mixed_float16 training runs on the fused forward / backward kernels: unset NERF_TRAIN_FORWARD / "
-                    "NERF_TRAIN_BACKWARD / NERF_TRAIN_DGRAD / NERF_TRAIN_WGRAD");
+        return fail("mixed_float16 training runs on the fused trainer only: unset NERF_TRAIN_FORWARD");
     }
-    for (int w = 0; w < 2; ++w) {
-        if (!c->net[w].loaded) continue;
-        if (!t->net[w].present) {
+    for (int w = 0; w < 2; ++w)
+        if (c->net[w].loaded)
             if (int r = init_net(c, t, w)) { train_free(c); return r; }
-        } else {
-            if (int r = alloc_optimizer(c, t, t->net[w])) { train_free(c); return r; }
-            if (int r = ensure_fused(c, t, t->net[w])) { train_free(c); return r; }
-            if (int r = relayout_net(c, t->net[w])) { train_free(c); return r; }
-        }
-    }
     return 0;
 }
 
@@ -1290,7 +1276,7 @@ int nerf_train_end(nerf_ctx* c) {
 }
 
 int nerf_train_loss_scale(nerf_ctx* c, float* loss_scale, int64_t* steps_applied, int64_t* steps_skipped) {
-    if (!c || !c->train || !c->train->training) return fail("nerf_train_begin has not been called");
+    if (!c || !c->train) return fail("nerf_train_begin has not been called");
     OptState h;
     HIP_OK(hipMemcpyAsync(&h, c->train->opt.p, sizeof(OptState), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -1303,7 +1289,7 @@ int nerf_train_loss_scale(nerf_ctx* c, float* loss_scale, int64_t* steps_applied
 int nerf_train_read_metric_sums(nerf_ctx* c, double* sums, int64_t* steps) {
     ENTER(c);
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     double h[4] = {0, 0, 0, 0};
     if (t->macc.p) {
         HIP_OK(hipMemcpyAsync(h, t->macc.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -1316,14 +1302,14 @@ int nerf_train_read_metric_sums(nerf_ctx* c, double* sums, int64_t* steps) {
 }
 
 int nerf_train_set_learning_rate(nerf_ctx* c, float lr) {
-    if (!c || !c->train || !c->train->training) return fail("nerf_train_begin has not been called");
+    if (!c || !c->train) return fail("nerf_train_begin has not been called");
     if (!(lr > 0.f)) return fail("learning_rate must be positive");
     c->train->cfg.learning_rate = lr;
     return 0;
 }
 
 int nerf_train_set_loss_weights(nerf_ctx* c, float coarse_mse_weight, float fine_mse_weight) {
-    if (!c || !c->train || !c->train->training) return fail("nerf_train_begin has not been called");
+    if (!c || !c->train) return fail("nerf_train_begin has not been called");
     if (!(coarse_mse_weight >= 0.f) || !(fine_mse_weight >= 0.f) || !(coarse_mse_weight <= 3.0e38f) ||
         !(fine_mse_weight <= 3.0e38f))
         return fail("loss weights must be finite and non-negative (got %g, %g)", coarse_mse_weight, fine_mse_weight);
@@ -1387,7 +1373,7 @@ int nerf_train_render_release(nerf_ctx* c) {
 int nerf_train_apply(nerf_ctx* c, const float* grad_coarse, const float* grad_fine, int mem) {
     ENTER(c);
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (grad_coarse) HIP_OK(hipMemcpyAsync(t->net[0].grad, grad_coarse, t->nblob * sizeof(float), kind, c->stream));
     if (grad_fine) {
@@ -1423,7 +1409,7 @@ int nerf_train_step(nerf_ctx* c, const float* rays_orig, const float* rays_dirs,
 int nerf_train_get_gradients(nerf_ctx* c, int which, float* blob, size_t n_floats, int mem) {
     ENTER(c);
     TrainState* t = c->train;
-    if (!t || !t->training) return fail("nerf_train_begin has not been called");
+    if (!t) return fail("nerf_train_begin has not been called");
     if (!blob) return fail("blob is NULL");
     if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail("which must be 0 (coarse) or 1 (fine)");
     if (!t->net[which].present) return fail("network %d has no weights loaded", which);

@@ -1,5 +1,6 @@
-// train_kernels.h -- internal declarations of the training path (NeRF.train_step, src/NeRF.py:136-178):
-// layer-wise fp32 MFMA GEMMs over activations kept in HBM + the per-ray backward kernels.  gfx950 only.
+// train_kernels.h -- internal declarations of the training path (NeRF.train_step, src/NeRF.py:136-178): the fused
+// trainer's weight-gradient GEMMs on the fp16 matrix cores (fragment-major operands), the reference trainer's layer-wise
+// exact-fp32 MFMA GEMMs over row-major activations, and the per-ray backward / optimizer kernels both share.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,26 +34,20 @@ struct GemmAbt {
     int n_valid;                // columns actually stored
     int accumulate;             // BWD_PLAIN: Out += result
     float alpha;
-    unsigned* gmax;             // BWD_MASK optional: atomicMax of the bits of max|Out| (for the split-fp16 weight gradient)
-    // split-fp16 variant (launch_gemm_abt_h): Bt pre-split into fp16 hi / lo planes of the same shape; max|A| slots
-    const uint16_t* Bhi; const uint16_t* Blo;
-    const unsigned* gmax_in;
 };
 void launch_gemm_abt(int epi, bool narrow, const GemmAbt& g, hipStream_t s);
-// the data-gradient GEMM (EPI_BWD_MASK, 128-wide tiles) on the fp16 matrix cores: A (a gradient buffer, scaled by a power
-// of two from gmax_in) is split while it is staged, Bt comes pre-split; three MFMA passes, fp32 accumulation
-void launch_gemm_abt_h(const GemmAbt& g, hipStream_t s);
 
 // partial[split][k][n] = sum over the split's rows of A[m][k] * G[m][n]; row Kp of every split = column sums of G
 struct GemmAtb {
     const float* A; int lda; int K;     // K = columns of A used (multiple of 4)
     const float* G; int ldg; int N;     // N = columns of G used (multiple of 4)
     float* partial; int Kp; int Nw;     // partial: [splits][Kp + 1][Nw]
-    long long M; int rows_per_split;    // multiple of 16
-    const unsigned* gmax;               // split-fp16 variant: bits of max|G| (written by G's producer); G is scaled to fp16 range
+    long long M; int rows_per_split;    // multiple of 16 (gemm_atb, row-major operands) / of 32 (the fused trainer's kernels)
+    const unsigned* gmax;               // gemm_atb_p: bits of max|G| (written by G's producer, MlpBwdArgs::gmax); G is scaled to fp16 range
     int a_f16;                          // head_wgrad: A holds fp16 elements (lda in halfs); gemm_atb_f16: both operands do
-    int frag;                           // A and G (not the heads' 4-wide G) are fragment-major (frag_layout.h::frag_index); rows_per_split % 32 == 0
-    // pair16 gradient operand of the fused float32-policy trainer (gemm_atb_p, train_kernels.hip; nerf_kernels.h::kPair16):
+    // The fused trainer's kernels (gemm_atb_p, gemm_atb_f16, head_wgrad with frag) take A and G (not the heads' 4-wide G)
+    // fragment-major (frag_layout.h::frag_index); gemm_atb and the reference trainer's head_wgrad take them row-major.
+    // pair16 gradient operand of the fused float32-policy trainer (gemm_atb_p, train_kernels.hip; MlpBwdArgs::rs_ptr):
     // G's fp32 slots hold the backward chain's packed operand as fp16 (hi, lo) pairs -- the 16 bytes of four consecutive
     // features of a row are {hi01, hi23, lo01, lo23} -- carrying one power-of-two scale per row:
     // true G = (hi + lo) * g_rs[row] (g_rs: upper half of the factor's fp32 bits).  A stays fp32.
@@ -66,17 +61,18 @@ struct GemmAtb {
 };
 constexpr int kWgradBatchMax = 10;   // GEMMs per batched weight-gradient launch (the eight 256-wide layers of a pass fit)
 struct GemmAtbBatch { int n; int wg_end[kWgradBatchMax]; GemmAtb e[kWgradBatchMax]; };
-void launch_gemm_atb(const GemmAtb& g, hipStream_t s);
-// same contract on the fp16 matrix cores: both operands split hi + lo (22 bits) on the fly while they are staged into LDS,
-// three MFMA passes, fp32 accumulation; G is pre-scaled by a power of two so that its largest entry sits at 2^14
-void launch_gemm_atb_h(const GemmAtb& g, hipStream_t s, bool wide = false);   // wide: 256 x 256 tile, 512 threads
-void launch_gemm_atb_h_batch(GemmAtbBatch& b, hipStream_t s, bool wide);      // all entries in ONE launch (fills wg_end)
-void launch_gemm_atb_p(const GemmAtb& g, hipStream_t s, bool wide = false);   // pair16 operands (g.g_rs), same contract
-void launch_gemm_atb_p_batch(GemmAtbBatch& b, hipStream_t s, bool wide);
-void launch_head_wgrad(const GemmAtb& g, hipStream_t s);   // N = 4 (the heads): VALU kernel, same partial layout
-// mixed_float16 policy: A and G are fp16 rows (lda / ldg in halfs), one MFMA pass, no scaling (G carries the loss scale)
-void launch_gemm_atb_f16(const GemmAtb& g, hipStream_t s, bool wide = false);
-void launch_gemm_atb_f16_batch(GemmAtbBatch& b, hipStream_t s, bool wide);
+void launch_gemm_atb(const GemmAtb& g, hipStream_t s);     // exact fp32 MFMA, row-major operands (the reference trainer)
+// same contract on the fp16 matrix cores, fragment-major operands (the fused trainer).  One GEMM on the 128 x 128 tile
+// (256 threads; with g.sig_g the sigma head rides along), or a batch in ONE launch on the 256 x 256 tile (512 threads; fills
+// wg_end):
+// float32 policy: A fp32, split hi + lo (22 bits) while it is staged, G pair16 (g.g_rs); three MFMA passes, fp32 accumulation
+void launch_gemm_atb_p(const GemmAtb& g, hipStream_t s);
+void launch_gemm_atb_p_batch(GemmAtbBatch& b, hipStream_t s);
+// mixed_float16 policy: A and G are fp16 (lda / ldg in halfs), one MFMA pass, no scaling (G carries the loss scale)
+void launch_gemm_atb_f16(const GemmAtb& g, hipStream_t s);
+void launch_gemm_atb_f16_batch(GemmAtbBatch& b, hipStream_t s);
+// N = 4 (the heads): VALU kernel, same partial layout; frag: A is fragment-major (fp32, or fp16 with g.a_f16), else row-major fp32
+void launch_head_wgrad(const GemmAtb& g, bool frag, hipStream_t s);
 
 // grad[blob layout] = sum over splits of partial (deterministic order)
 struct ReduceArgs {
@@ -95,7 +91,6 @@ void launch_reduce_grad_batch(const ReduceBatch& b, hipStream_t s);  // one laun
 struct RelayoutArgs {
     const float* w; const float* b; int K_real, N_real, Kp, Np, rowmap;
     float* W; float* WT; float* bias;
-    uint16_t* Whi; uint16_t* Wlo;       // W split into fp16 hi / lo planes (same [Kp x Np] layout)
 };
 void launch_relayout(const RelayoutArgs& a, hipStream_t s);
 
@@ -134,7 +129,7 @@ void launch_opt_tick(OptState* st, float beta1, float beta2, hipStream_t s);   /
 void launch_composite_bwd(const float* raw, const float* z, const float* T, long long N, int S, const float* d_rgb,
                           const float* d_w_ext, float* Graw, float* d_z, hipStream_t s);
 void launch_head_bwd(const float* Graw, const float* W9 /*[128][Np9] row-major, Np9 = 32*/, const float* H9,
-                     long long M, float alpha, float* G9, unsigned* gmax, hipStream_t s);
+                     long long M, float alpha, float* G9, hipStream_t s);
 // lx: octaves of the encoding-gradient rows' layout ([x, sin0, cos0, ...] per component, 1 + 2 lx columns each; 1..10)
 void launch_pe_bwd(const float* dA0, const float* dA0b /* added to dA0, or null */, const float* o, const float* d,
                    const float* z, long long N, int S, int lx, float* d_z, hipStream_t s,

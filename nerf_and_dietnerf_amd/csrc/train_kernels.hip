@@ -177,7 +177,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NERF_ABT
     abt_compute<WTM, WTN, LDA, LDB>(As[buf], Bs[buf], wm * WTM * 32, wn * WTN * 32, li, lh, acc);
 
     // C/D layout of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    float vmax = 0.f;
 #pragma unroll
     for (int a = 0; a < WTM; ++a)
 #pragma unroll
@@ -198,23 +197,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, NERF_ABT
                 } else if (EPI == EPI_BWD_MASK) {
                     if (g.r1a) v = fmaf(g.r1a[m * g.r1a_ld], r1b, v);
                     v = hmask[a][b][r] > 0.f ? v : g.alpha * v;
-                    vmax = fmaxf(vmax, fabsf(v));
                 } else {
                     if (g.accumulate) v += g.Out[m * g.ldo + n];
                 }
                 if (n < g.n_valid) g.Out[m * g.ldo + n] = v;
             }
         }
-    if (EPI == EPI_BWD_MASK && g.gmax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        // 64 slots per buffer and a plain read first: same-address atomics from 32 k waves would serialise in L2
-        if (lane == 0) {
-            unsigned* slot = g.gmax + (blockIdx.x & 63);
-            const unsigned vb = __float_as_uint(vmax);               // non-negative floats order like their bits
-            if (vb > *slot) atomicMax(slot, vb);
-        }
-    }
 }
 
 template <int EPI>
@@ -358,14 +346,7 @@ void launch_gemm_atb(const GemmAtb& g, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// gemm_atb_h: the weight-gradient GEMM on the fp16 matrix cores.  Both operands are split x = hi + lo (two fp16 values,
-// 22 significant bits) while they are staged, and each product is formed in three passes hi*lo + lo*hi + hi*hi of
-// v_mfma_f32_32x32x16_f16 with fp32 accumulation -- the arithmetic of the render path's f16x3 kernel.  Gradients are tiny
-// (1e-5 and below), so G is multiplied by a power of two that puts its largest entry (tracked by its producer with an
-// atomicMax) at 2^14; the partial sums are divided by it again.  Staging: 128 threads per operand, each a 4 rows x 4
-// columns block (four global float4 loads), transposed in registers so that the 16 sample rows of a column land
-// contiguously: the MFMA operand of lane (column, half) is one ds_read_b128.  LDS: [plane][column][16 rows] fp16, 48-byte
-// column stride (conflict-free for the 64 x 16-byte operand reads).
+// The weight-gradient GEMMs of the fused trainer (gemm_atb_p, gemm_atb_f16) on the fp16 matrix cores: shared pieces
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
@@ -394,191 +375,6 @@ __device__ __forceinline__ int batch_entry(const GemmAtbBatch& b, int& lin) {
     return e;
 }
 
-template <int W>
-__global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 128 ? 3 : 2))) void gemm_atb_h_kernel(const GemmAtbBatch bat) {
-    int lin = blockIdx.x;
-    const GemmAtb& g = bat.e[batch_entry(bat, lin)];
-    constexpr int kPl = W * kHColStride;          // bytes per plane
-    constexpr int WNW = W / 64;                   // waves along n (2 or 4); two along k
-    constexpr int KTL = W / 64;                   // 32-row k tiles per wave (2 or 4); two n tiles per wave
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][4 * kPl];    // planes: A hi, A lo, G hi, G lo
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wk = wave / WNW, wn = wave % WNW;
-    const int li = lane & 31, lh = lane >> 5;
-    const int kt_n = (g.Kp + W - 1) / W, nt_n = (g.Nw + W - 1) / W, T = kt_n * nt_n;
-    const int n_splits = (int)((g.M + g.rows_per_split - 1) / g.rows_per_split);
-    if (lin >= T * n_splits) return;              // padding workgroups of a batch entry (its range is a multiple of 8)
-    const int grp = lin / (8 * T), rem = lin % (8 * T);
-    int split = grp * 8 + rem % 8, tile = rem / 8;
-    if (grp * 8 + 8 > n_splits) {
-        const int r2 = lin - grp * 8 * T, left = n_splits - grp * 8;
-        split = grp * 8 + r2 % left;
-        tile = r2 / left;
-    }
-    const int kb = (tile % kt_n) * W, nb = (tile / kt_n) * W;
-    const bool first_ktile = tile % kt_n == 0;
-    const long long ms = (long long)split * g.rows_per_split;
-    const long long me = ms + g.rows_per_split < g.M ? ms + g.rows_per_split : g.M;
-    // power-of-two scale of G: largest entry -> [2^14, 2^15)
-    unsigned mb = g.gmax ? g.gmax[lane] : 0u;                  // 64 slots per buffer (see the producers)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned other = __shfl_xor(mb, o); mb = other > mb ? other : mb; }
-    int sexp = mb ? 127 + 14 - ((int)((mb >> 23) & 0xFF) - 127) : 127;
-    sexp = sexp < 1 ? 1 : sexp > 254 ? 254 : sexp;
-    const float gscale = __uint_as_float((unsigned)sexp << 23), ginv = 1.0f / gscale;
-    // staging role of this thread: operand (A: t < W, G: t >= W), rows 4 rg .. 4 rg + 3, columns 4 cg .. 4 cg + 3
-    const bool isG = t >= W;
-    const int b = t & (W - 1), rg = b & 3, cg = b >> 2;
-    const int ld = isG ? g.ldg : g.lda;
-    const bool on = isG ? (nb + 4 * cg < g.N) : (kb + 4 * cg < g.K);
-    // threads whose columns lie outside the matrix read column block 0 (valid memory) and park zeros
-    const int col0 = on ? (isG ? nb : kb) + 4 * cg : 0;
-    // fragment-major operands (frag_layout.h::frag_index): the thread's 4 rows x 4 columns are 16 consecutive floats
-    const int rs = g.frag ? 4 : ld;                                   // floats between two of its rows
-    const float* src = (isG ? g.G : g.A) + (g.frag ? frag_index(ms + 4 * rg, col0, ld) : (ms + 4 * rg) * ld + col0);
-    const float mul = isG ? gscale : 1.0f;
-    const int wbase = (isG ? 2 : 0) * kPl + 4 * cg * kHColStride + rg * 8;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    f32x16 acc[KTL][2];
-#pragma unroll
-    for (int a = 0; a < KTL; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
-    float cs0 = 0.f, cs1 = 0.f, cs2 = 0.f, cs3 = 0.f;      // column sums of the raw G block (bias gradient)
-
-    // Register stages of operand rows (NERF_ATBH_STAGES, default 3): with one 512-thread workgroup per CU a 16-row step
-    // lasts ~800 cycles, less than a global load's latency; loads are issued NS - 2 barriers ahead of their use.  The
-    // loop is branch-free (see gemm_atb_f16_kernel: loads inside conditional blocks made the compiler wait for vmcnt(0)
-    // before every LDS store); steps past the end read the last rows again and are zeroed when they are parked.
-#ifndef NERF_ATBH_STAGES
-#define NERF_ATBH_STAGES 3
-#endif
-    constexpr int NS = NERF_ATBH_STAGES;
-    float4 R[NS][4];
-    const long long steps = ms < me ? (me - ms) / 16 : 0;
-    auto fetch = [&](float4 (&r)[4], long long st) {
-        const long long sc = st < steps ? st : steps - 1;
-        const float* q_ = src + (g.frag ? (size_t)(sc >> 1) * 32 * ld + (sc & 1) * 64 : (size_t)sc * 16 * ld);
-        r[0] = *reinterpret_cast<const float4*>(q_);
-        r[1] = *reinterpret_cast<const float4*>(q_ + rs);
-        r[2] = *reinterpret_cast<const float4*>(q_ + 2 * (size_t)rs);
-        r[3] = *reinterpret_cast<const float4*>(q_ + 3 * (size_t)rs);
-    };
-    auto col = [&](int jcol, float c0, float c1, float c2, float c3, int buf) {
-        uint32_t h01, l01, h23, l23;
-        split_pack2(c0 * mul, c1 * mul, h01, l01);
-        split_pack2(c2 * mul, c3 * mul, h23, l23);
-        unsigned char* w_ = &lds[buf][wbase + jcol * kHColStride];
-        *reinterpret_cast<uint2*>(w_) = make_uint2(h01, h23);
-        *reinterpret_cast<uint2*>(w_ + kPl) = make_uint2(l01, l23);
-    };
-    auto park = [&](const float4 (&r_)[4], long long st, int buf) {
-        const bool live = on && st < steps;
-        float4 r[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = live ? r_[e] : zero4;
-        cs0 += (r[0].x + r[1].x) + (r[2].x + r[3].x); cs1 += (r[0].y + r[1].y) + (r[2].y + r[3].y);
-        cs2 += (r[0].z + r[1].z) + (r[2].z + r[3].z); cs3 += (r[0].w + r[1].w) + (r[2].w + r[3].w);
-        col(0, r[0].x, r[1].x, r[2].x, r[3].x, buf);
-        col(1, r[0].y, r[1].y, r[2].y, r[3].y, buf);
-        col(2, r[0].z, r[1].z, r[2].z, r[3].z, buf);
-        col(3, r[0].w, r[1].w, r[2].w, r[3].w, buf);
-    };
-
-    auto compute = [&](int buf) {
-        const unsigned char* base = lds[buf];
-        h8v ah[KTL], al[KTL], gh[2], gl[2];
-#pragma unroll
-        for (int q = 0; q < KTL; ++q) {
-            const int ca = (wk * (W / 2) + q * 32 + li) * kHColStride + 16 * lh;
-            ah[q] = *reinterpret_cast<const h8v*>(base + ca);
-            al[q] = *reinterpret_cast<const h8v*>(base + kPl + ca);
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int cgd = (wn * 64 + q * 32 + li) * kHColStride + 16 * lh;
-            gh[q] = *reinterpret_cast<const h8v*>(base + 2 * kPl + cgd);
-            gl[q] = *reinterpret_cast<const h8v*>(base + 3 * kPl + cgd);
-        }
-#pragma unroll
-        for (int a = 0; a < KTL; ++a)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], gl[c], acc[a][c], 0, 0, 0);
-                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[a], gh[c], acc[a][c], 0, 0, 0);
-                acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], gh[c], acc[a][c], 0, 0, 0);
-            }
-    };
-
-#ifndef NERF_ATB_STAGGER
-#define NERF_ATB_STAGGER 1
-#endif
-    const bool late_half = NERF_ATB_STAGGER && W == 256 && __builtin_amdgcn_readfirstlane(wave) >= 4;
-    if (steps > 0) {
-#pragma unroll
-        for (int q = 0; q < NS - 1; ++q) fetch(R[q], q);
-        park(R[0], 0, 0);
-        __syncthreads();
-        int buf = 0;
-        // step st: registers in slot st % NS; unrolled by NS for static register indices (the last round may run past the
-        // end: those steps park zeros).
-        // Stagger (NERF_ATB_STAGGER): waves w and w + 4 of a 512-thread workgroup share a SIMD and, running the same
-        // program between the same barriers, did their MFMAs together and their staging (vector work) together.  The
-        // second half parks FIRST and computes after -- park writes buffer buf ^ 1, compute reads buffer buf, both orders
-        // are legal between two barriers -- so one partner's MFMAs run beside the other's split / pack / LDS stores
-        // (MI355X_MICROARCH.md, "try a stagger").  Two copies of the whole loop, chosen once per wave: the choice inside
-        // the loop body cost 400 spilled registers.
-        auto main_loop = [&](auto late_c) {
-            for (long long base_st = 1; base_st < steps; base_st += NS) {
-#pragma unroll
-                for (int i = 0; i < NS; ++i) {
-                    const long long st = base_st + i;
-                    fetch(R[(1 + i + NS - 2) % NS], st + NS - 2);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (decltype(late_c)::value) {
-                        park(R[(1 + i) % NS], st, buf ^ 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        compute(buf);
-                    } else {
-                        compute(buf);
-                        __builtin_amdgcn_sched_barrier(0);
-                        park(R[(1 + i) % NS], st, buf ^ 1);
-                    }
-                    __syncthreads();
-                    buf ^= 1;
-                }
-            }
-        };
-        if (late_half) main_loop(std::true_type{});
-        else main_loop(std::false_type{});
-        compute(buf);
-    }
-
-    float* part = g.partial + (size_t)split * (g.Kp + 1) * g.Nw;
-#pragma unroll
-    for (int a = 0; a < KTL; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n = nb + wn * 64 + c * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int k = kb + wk * (W / 2) + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (k < g.Kp && n < g.Nw) part[(size_t)k * g.Nw + n] = acc[a][c][r] * ginv;
-            }
-        }
-    // bias gradient: column sums of the raw (unscaled) G rows of this slab; the four row groups of a column block are
-    // four neighbouring lanes
-    cs0 += __shfl_xor(cs0, 1); cs1 += __shfl_xor(cs1, 1); cs2 += __shfl_xor(cs2, 1); cs3 += __shfl_xor(cs3, 1);
-    cs0 += __shfl_xor(cs0, 2); cs1 += __shfl_xor(cs1, 2); cs2 += __shfl_xor(cs2, 2); cs3 += __shfl_xor(cs3, 2);
-    if (first_ktile && isG && rg == 0 && nb + 4 * cg < g.Nw) {
-        float* prow = part + (size_t)g.Kp * g.Nw + nb + 4 * cg;
-        prow[0] = cs0; prow[1] = cs1; prow[2] = cs2; prow[3] = cs3;
-    }
-}
-
 // workgroup ranges of a batch: entry e gets tiles x splits workgroups, rounded up to a multiple of 8 so that every entry
 // starts on XCD 0 (the tile order inside an entry is XCD-aware)
 static int batch_ranges(GemmAtbBatch& b, int W) {
@@ -593,44 +389,44 @@ static int batch_ranges(GemmAtbBatch& b, int W) {
     return end;
 }
 
-void launch_gemm_atb_h_batch(GemmAtbBatch& b, hipStream_t s, bool wide) {
-    if (b.n <= 0) return;
-    const int wgs = batch_ranges(b, wide ? 256 : 128);
-    if (wide) hipLaunchKernelGGL(gemm_atb_h_kernel<256>, dim3((unsigned)wgs), dim3(512), 0, s, b);
-    else hipLaunchKernelGGL(gemm_atb_h_kernel<128>, dim3((unsigned)wgs), dim3(256), 0, s, b);
-}
-
-void launch_gemm_atb_h(const GemmAtb& g, hipStream_t s, bool wide) {
-    GemmAtbBatch b{};
-    b.n = 1; b.e[0] = g;
-    launch_gemm_atb_h_batch(b, s, wide);
-}
-
 // ------------------------------------------------------------------------------------------------
-// gemm_atb_p: gemm_atb_h for a gradient operand that ARRIVES split ("pair16" buffers, float32 policy of the fused
-// trainer, nerf_kernels.h::kPair16).  The backward chain holds every pre-activation gradient as an fp16 (hi, lo) pair --
-// it is the next layer's MFMA operand -- and stores that pair in the value's fp32 slot: the 16 bytes of four consecutive
-// features of a row are {hi01, hi23, lo01, lo23} (packed halfs); same buffers, same addresses, same loads.
-//   A (activations): fp32 rows, split hi + lo while they are staged exactly as in gemm_atb_h (a pair16 stash was built
+// gemm_atb_p: the weight-gradient GEMM of the fused float32-policy trainer on the fp16 matrix cores.  Both operands are
+// x = hi + lo (two fp16 values, 22 significant bits), and each product is formed in three passes hi*lo + lo*hi + hi*hi of
+// v_mfma_f32_32x32x16_f16 with fp32 accumulation -- the arithmetic of the render path's f16x3 kernel.  Gradients are tiny
+// (1e-5 and below), so G is multiplied by a power of two taken from its largest entry (tracked by its producer with an
+// atomicMax, GemmAtb::gmax); the partial sums are divided by it again.  Staging: W threads per operand, each a 4 rows x 4
+// columns block (64 consecutive bytes of the fragment-major buffer), transposed in registers so that the 16 sample rows of
+// a column land contiguously: the MFMA operand of lane (column, half) is one ds_read_b128.  LDS: [plane][column][16 rows]
+// fp16, 48-byte column stride (conflict-free for the 64 x 16-byte operand reads).
+//   The gradient operand ARRIVES split ("pair16" buffers, nerf_kernels.h::MlpBwdArgs::rs_ptr).  The backward chain holds
+// every pre-activation gradient as an fp16 (hi, lo) pair -- it is the next layer's MFMA operand -- and stores that pair in
+// the value's fp32 slot: the 16 bytes of four consecutive features of a row are {hi01, hi23, lo01, lo23} (packed halfs).
+//   A (activations): fp32 rows, split hi + lo while they are staged (split_pack2; a pair16 stash was built
 // too and measured out: the forward had to assemble its store tuple with moves and spilled, +5 % on that kernel).
 //   G: the chain's packed operand D' = D * 2^s_row, one power of two PER SAMPLE ROW (mlp_bwd_f16x3.hip: every row's
 // operand peaks between 2^5 and 2^12 whatever its gradient is), with 2^-s_row stored per row as the upper half of its
 // fp32 bits (g_rs, 2 B per row and buffer).  The contraction runs over rows, so the row factor is applied while staging:
-// f_row = 2^-s_row * gscale (gscale: the buffer's true max|D| -> [2^8, 2^9), from the producer's gmax slots as before),
+// f_row = 2^-s_row * gscale (gscale: the buffer's true max|D| -> [2^8, 2^9), from the producer's gmax slots),
 // packed to fp16 pairs and multiplied onto the transposed (row, row + 1) pairs with v_pk_mul_f16 -- exact unless the
 // product drops below 2^-14 (absolute error 2^-25 against a buffer maximum of 2^8: 2^-33 of max|D|); rows whose factor
 // underflows fp16 altogether (peak below 2^-20 of the largest row's) are dropped, which an fp32 sum over the rows does to
-// them as well.  The target 2^8 instead of gemm_atb_h's 2^14 leaves room for a row whose outputs collapsed against its
+// them as well.  The target 2^8 (not the 2^14 an unscaled fp32 operand could take) leaves room for a row whose outputs collapsed against its
 // operand's peak (factor up to 2^15 / its peak); beyond that the factor is clamped (finite, wrong by the clamp -- needs
 // a row-wise gain below 2^-11 in one layer).  Rows past the slab's end take factor 0.  The bias gradient (column sums of
 // true G) is v_dot2c_f32_f16 of the scaled pairs with (1, 1).  G's staging is ~3.5 vector instructions per element
 // (byte permutes, v_pk_mul, v_dot2c) where the fp32 rows took ~6 (scale, and, subtract, conversions, column sums).
-// Waves are specialised by operand (A: waves 0 .. W/64 - 1, G: the rest): two copies of the loop, chosen once per wave --
-// for W = 256 these are the SIMD partners of gemm_atb_h's stagger (the G half stages first, then computes).
+// Waves are specialised by operand (A: waves 0 .. W/64 - 1, G: the rest): two copies of the loop, chosen once per wave.
+// Stagger (NERF_ATB_STAGGER, W = 256): waves w and w + 4 of a 512-thread workgroup share a SIMD and, running the same
+// program between the same barriers, did their MFMAs together and their staging (vector work) together.  The second half
+// (here: the G waves) parks FIRST and computes after -- park writes buffer buf ^ 1, compute reads buffer buf, both orders
+// are legal between two barriers -- so one partner's MFMAs run beside the other's split / pack / LDS stores.
 // What this kernel is bound by (profiles/r4_diagnostic_ab.txt): not its staging work -- with ONE MFMA pass instead of three
 // (timing-only build) the batched launch streams at 5.96 TB/s, with three at 4.95: per 16-row step ~2000 cycles of
 // barrier + LDS operand reads + staging do not overlap the 1536 MFMA cycles of the SIMD's two waves.
 // ------------------------------------------------------------------------------------------------
+#ifndef NERF_ATB_STAGGER
+#define NERF_ATB_STAGGER 1
+#endif
 // SIG: the entry carries the sigma head's weight gradient as a by-product (GemmAtb::sig_g; W = 128, one n tile)
 template <int W, bool SIG = false>
 __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 128 ? 3 : 2))) void gemm_atb_p_kernel(const GemmAtbBatch bat) {
@@ -709,7 +505,7 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
         unsigned char* w_ = &lds[buf][wbase];
         constexpr uint32_t kLoSel = 0x05040100u, kHiSel = 0x07060302u;
         if constexpr (!decltype(role_g)::value) {
-            // A: fp32 activations, split hi + lo here exactly as gemm_atb_h does (rows past the slab's end are re-read rows:
+            // A: fp32 activations, split hi + lo here (rows past the slab's end are re-read rows:
             // finite, and they meet a zero factor on the G side)
             auto cola = [&](int j, float c0, float c1, float c2, float c3) {
                 uint32_t h01, l01, h23, l23;
@@ -787,8 +583,8 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
 
     if (steps > 0) {
         // Two copies of the whole pipeline, chosen once per wave (the choice inside the loop body cost hundreds of spilled
-        // registers in gemm_atb_h).  The G waves of the 256-wide tile stage FIRST and compute after (gemm_atb_h's stagger of
-        // the SIMD partners w / w + 4: park writes buffer buf ^ 1, compute reads buf, both orders are legal between barriers).
+        // registers).  The G waves of the 256-wide tile stage FIRST and compute after (the stagger of the SIMD partners
+        // w / w + 4, see above).
         auto run = [&](auto role_g) {
             constexpr bool late = decltype(role_g)::value && NERF_ATB_STAGGER && W == 256;
 #pragma unroll
@@ -856,18 +652,18 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
     }
 }
 
-void launch_gemm_atb_p_batch(GemmAtbBatch& b, hipStream_t s, bool wide) {
+void launch_gemm_atb_p_batch(GemmAtbBatch& b, hipStream_t s) {
     if (b.n <= 0) return;
-    const int wgs = batch_ranges(b, wide ? 256 : 128);
-    if (wide) hipLaunchKernelGGL(gemm_atb_p_kernel<256>, dim3((unsigned)wgs), dim3(512), 0, s, b);
-    else if (b.n == 1 && b.e[0].sig_g && b.e[0].Nw <= 128) hipLaunchKernelGGL((gemm_atb_p_kernel<128, true>), dim3((unsigned)wgs), dim3(256), 0, s, b);
-    else hipLaunchKernelGGL(gemm_atb_p_kernel<128>, dim3((unsigned)wgs), dim3(256), 0, s, b);
+    const int wgs = batch_ranges(b, 256);
+    hipLaunchKernelGGL(gemm_atb_p_kernel<256>, dim3((unsigned)wgs), dim3(512), 0, s, b);
 }
 
-void launch_gemm_atb_p(const GemmAtb& g, hipStream_t s, bool wide) {
+void launch_gemm_atb_p(const GemmAtb& g, hipStream_t s) {
     GemmAtbBatch b{};
     b.n = 1; b.e[0] = g;
-    launch_gemm_atb_p_batch(b, s, wide);
+    const int wgs = batch_ranges(b, 128);
+    if (g.sig_g && g.Nw <= 128) hipLaunchKernelGGL((gemm_atb_p_kernel<128, true>), dim3((unsigned)wgs), dim3(256), 0, s, b);
+    else hipLaunchKernelGGL(gemm_atb_p_kernel<128>, dim3((unsigned)wgs), dim3(256), 0, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -875,13 +671,13 @@ void launch_gemm_atb_p(const GemmAtb& g, hipStream_t s, bool wide) {
 // gradients) arrive as fp16 rows from the single-pass stash forward / backward chain: half the bytes of the fp32 buffers
 // (this GEMM is bound by reading them), no hi/lo split and no conversion while staging -- a 4 x 4 block of halfs is
 // transposed with byte permutes -- and ONE v_mfma_f32_32x32x16_f16 pass per product, fp32 accumulation.  Same tiling,
-// LDS layout ([plane][column][16 rows], 48-byte column stride), partial-sum layout and bias row as gemm_atb_h.  A
+// LDS layout ([plane][column][16 rows], 48-byte column stride), partial-sum layout and bias row as gemm_atb_p.  A
 // gradient that left the fp16 range arrives as Inf and makes the partial sums non-finite: the loss-scale logic skips
 // that step (src/NeRF.py:159-163 under LossScaleOptimizer).
 // ------------------------------------------------------------------------------------------------
 // SIG: the entry carries the sigma head's weight gradient as a by-product (GemmAtb::sig_g; W = 128, one n tile): fp16 A x fp32
 // d_sigma, accumulated in fp32 (v_fma_mix_f32: no conversion instructions)
-template <int W, bool FRAG, bool SIG = false>
+template <int W, bool SIG = false>
 __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 128 && !SIG ? 3 : 2))) void gemm_atb_f16_kernel(const GemmAtbBatch bat) {
     int lin = blockIdx.x;
     const GemmAtb& g = bat.e[batch_entry(bat, lin)];
@@ -918,11 +714,9 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
     const int col = on ? (isG ? nb : kb) + 4 * cg : 0;
     float sg0 = 0.f, sg1 = 0.f, sg2 = 0.f, sg3 = 0.f, sgb = 0.f;   // SIG, A threads: sum_rows A[row][col j] * d_sigma[row]; sum of d_sigma
     const float* sigp = SIG ? g.sig_g + ms + 4 * rg : nullptr;
-    // fragment-major operands (frag_layout.h::frag_index): the thread's 4 rows x 4 columns are 16 consecutive elements
-    // -- with FRAG known at compile time they are fetched as two 16-byte loads instead of four 8-byte ones
-    const int rs = FRAG ? 4 : ld;                                     // elements between two of its rows
-    const uint16_t* src = reinterpret_cast<const uint16_t*>(isG ? g.G : g.A) +
-                          (FRAG ? frag_index(ms + 4 * rg, col, ld) : (ms + 4 * rg) * ld + col);
+    // fragment-major operands (frag_layout.h::frag_index): the thread's 4 rows x 4 columns are 16 consecutive elements,
+    // fetched as two 16-byte loads
+    const uint16_t* src = reinterpret_cast<const uint16_t*>(isG ? g.G : g.A) + frag_index(ms + 4 * rg, col, ld);
     const int wbase = (isG ? 1 : 0) * kPl + 4 * cg * kHColStride + rg * 8;
 
     f32x16 acc[KTL][2];
@@ -955,17 +749,10 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
     long long steps = 0;
     auto fetch1 = [&](uint2 (&r)[4], long long st) {
         const long long sc = st < steps ? st : steps - 1;
-        const uint16_t* q_ = src + (FRAG ? (size_t)(sc >> 1) * 32 * ld + (sc & 1) * 64 : (size_t)sc * 16 * ld);
-        if constexpr (FRAG) {
-            const uint4 lo = *reinterpret_cast<const uint4*>(q_), hi = *reinterpret_cast<const uint4*>(q_ + 8);
-            r[0] = make_uint2(lo.x, lo.y); r[1] = make_uint2(lo.z, lo.w);
-            r[2] = make_uint2(hi.x, hi.y); r[3] = make_uint2(hi.z, hi.w);
-        } else {
-            r[0] = *reinterpret_cast<const uint2*>(q_);
-            r[1] = *reinterpret_cast<const uint2*>(q_ + rs);
-            r[2] = *reinterpret_cast<const uint2*>(q_ + 2 * (size_t)rs);
-            r[3] = *reinterpret_cast<const uint2*>(q_ + 3 * (size_t)rs);
-        }
+        const uint16_t* q_ = src + (size_t)(sc >> 1) * 32 * ld + (sc & 1) * 64;
+        const uint4 lo = *reinterpret_cast<const uint4*>(q_), hi = *reinterpret_cast<const uint4*>(q_ + 8);
+        r[0] = make_uint2(lo.x, lo.y); r[1] = make_uint2(lo.z, lo.w);
+        r[2] = make_uint2(hi.x, hi.y); r[3] = make_uint2(hi.z, hi.w);
     };
     auto fetch = [&](uint2 (&r)[PB][4], float4 (&sgv)[PB], long long pj) {
 #pragma unroll
@@ -1046,7 +833,7 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
         __syncthreads();
         int buf = 0;
         // group st: registers in slot st % NS; unrolled by NS for static register indices.  The last round may run past
-        // the end: those groups park zeros.  (Stagger of the SIMD partners: see gemm_atb_h_kernel.)
+        // the end: those groups park zeros.  (Stagger of the SIMD partners: see gemm_atb_p.)
         auto main_loop = [&](auto late_c) {
             for (long long base_st = 1; base_st < groups; base_st += NS) {
 #pragma unroll
@@ -1106,230 +893,27 @@ __global__ __launch_bounds__(2 * W) __attribute__((amdgpu_waves_per_eu(2, W == 1
     }
 }
 
-void launch_gemm_atb_f16_batch(GemmAtbBatch& b, hipStream_t s, bool wide) {
+void launch_gemm_atb_f16_batch(GemmAtbBatch& b, hipStream_t s) {
     if (b.n <= 0) return;
-    const int wgs = batch_ranges(b, wide ? 256 : 128);
-    const bool frag = b.e[0].frag != 0;           // one layout per trainer: all entries agree
-    if (wide) {
-        if (frag) hipLaunchKernelGGL((gemm_atb_f16_kernel<256, true>), dim3((unsigned)wgs), dim3(512), 0, s, b);
-        else hipLaunchKernelGGL((gemm_atb_f16_kernel<256, false>), dim3((unsigned)wgs), dim3(512), 0, s, b);
-    } else {
-        if (frag && b.n == 1 && b.e[0].sig_g && b.e[0].Nw <= 128) hipLaunchKernelGGL((gemm_atb_f16_kernel<128, true, true>), dim3((unsigned)wgs), dim3(256), 0, s, b);
-        else if (frag) hipLaunchKernelGGL((gemm_atb_f16_kernel<128, true>), dim3((unsigned)wgs), dim3(256), 0, s, b);
-        else hipLaunchKernelGGL((gemm_atb_f16_kernel<128, false>), dim3((unsigned)wgs), dim3(256), 0, s, b);
-    }
+    const int wgs = batch_ranges(b, 256);
+    hipLaunchKernelGGL(gemm_atb_f16_kernel<256>, dim3((unsigned)wgs), dim3(512), 0, s, b);
 }
 
-void launch_gemm_atb_f16(const GemmAtb& g, hipStream_t s, bool wide) {
+void launch_gemm_atb_f16(const GemmAtb& g, hipStream_t s) {
     GemmAtbBatch b{};
     b.n = 1; b.e[0] = g;
-    launch_gemm_atb_f16_batch(b, s, wide);
-}
-
-// ------------------------------------------------------------------------------------------------
-// gemm_abt_h: the data-gradient GEMM  G_prev = (G . W^T [+ rank-1]) * LeakyReLU'(H)  on the fp16 matrix cores, same
-// arithmetic as gemm_atb_h: G is scaled to the fp16 range (its max comes from its producer) and split hi + lo while it is
-// staged (rows are k-contiguous: no transpose), W comes pre-split from the relayout kernel; three passes of
-// v_mfma_f32_32x32x16_f16, fp32 accumulation, then the usual epilogue on acc / scale.  k-step 32, 80-byte LDS rows.
-// ------------------------------------------------------------------------------------------------
-constexpr int kAbhStride = 80;
-constexpr int kAbhPlane = 128 * kAbhStride;     // 10 240 B: 128 rows x (32 halfs + pad)
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_abt_h_kernel(const GemmAbt g) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][4 * kAbhPlane];   // planes: A hi, A lo, B hi, B lo
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int li = lane & 31, lh = lane >> 5;
-    const int n_tiles = g.N / 128;
-    const long long lin = blockIdx.x, grp = lin / (8 * n_tiles), rem = lin % (8 * n_tiles);
-    long long m_tile = grp * 8 + rem % 8;
-    int n_tile = (int)(rem / 8);
-    const long long m_tiles = g.M / 128;
-    if (grp * 8 + 8 > m_tiles) {
-        const long long base = grp * 8 * n_tiles, r2 = lin - base, left = m_tiles - grp * 8;
-        m_tile = grp * 8 + r2 % left;
-        n_tile = (int)(r2 / left);
-    }
-    const long long m0 = m_tile * 128;
-    const int n0 = n_tile * 128;
-    unsigned mb = g.gmax_in ? g.gmax_in[lane] : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned other = __shfl_xor(mb, o); mb = other > mb ? other : mb; }
-    int sexp = mb ? 127 + 14 - ((int)((mb >> 23) & 0xFF) - 127) : 127;
-    sexp = sexp < 1 ? 1 : sexp > 254 ? 254 : sexp;
-    const float gscale = __uint_as_float((unsigned)sexp << 23), ginv = 1.0f / gscale;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
-
-    float hmask[2][2][16];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n = n0 + (wn * 2 + c) * 32 + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long m = m0 + (wm * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                hmask[a][c][r] = g.H[m * g.ldh + n];
-            }
-        }
-
-    // staging slots: A tile 128 rows x 32 k fp32 = 1024 float4 (4 per thread); B planes 128 rows x 32 halfs = 512 x 16 B each
-    const int arow = t >> 3, akq = t & 7;            // + 32 i rows
-    const float* ap = g.A + (m0 + arow) * g.lda + 4 * akq;
-    const size_t a32 = (size_t)32 * g.lda;
-    const int brow = t >> 2, bq = t & 3;             // + 64 i rows
-    const uint16_t* bph = g.Bhi + (size_t)(n0 + brow) * g.ldb + 8 * bq;
-    const uint16_t* bpl = g.Blo + (size_t)(n0 + brow) * g.ldb + 8 * bq;
-    const size_t b64 = (size_t)64 * g.ldb;
-    float4 ra0, ra1, ra2, ra3;
-    uint4 bh0, bh1, bl0, bl1;
-#define ABH_FETCH(K0)                                                                         \
-    ra0 = *reinterpret_cast<const float4*>(ap + (K0));                                        \
-    ra1 = *reinterpret_cast<const float4*>(ap + a32 + (K0));                                  \
-    ra2 = *reinterpret_cast<const float4*>(ap + 2 * a32 + (K0));                              \
-    ra3 = *reinterpret_cast<const float4*>(ap + 3 * a32 + (K0));                              \
-    bh0 = *reinterpret_cast<const uint4*>(bph + (K0));                                        \
-    bh1 = *reinterpret_cast<const uint4*>(bph + b64 + (K0));                                  \
-    bl0 = *reinterpret_cast<const uint4*>(bpl + (K0));                                        \
-    bl1 = *reinterpret_cast<const uint4*>(bpl + b64 + (K0));
-#define ABH_A(R, I, BUF)                                                                      \
-    {                                                                                         \
-        uint32_t h01, l01, h23, l23;                                                          \
-        split_pack2((R).x * gscale, (R).y * gscale, h01, l01);                                \
-        split_pack2((R).z * gscale, (R).w * gscale, h23, l23);                                \
-        unsigned char* w_ = &lds[BUF][(arow + 32 * (I)) * kAbhStride + akq * 8];              \
-        *reinterpret_cast<uint2*>(w_) = make_uint2(h01, h23);                                 \
-        *reinterpret_cast<uint2*>(w_ + kAbhPlane) = make_uint2(l01, l23);                     \
-    }
-#define ABH_PARK(BUF)                                                                         \
-    ABH_A(ra0, 0, BUF) ABH_A(ra1, 1, BUF) ABH_A(ra2, 2, BUF) ABH_A(ra3, 3, BUF)               \
-    *reinterpret_cast<uint4*>(&lds[BUF][2 * kAbhPlane + brow * kAbhStride + bq * 16]) = bh0;  \
-    *reinterpret_cast<uint4*>(&lds[BUF][2 * kAbhPlane + (brow + 64) * kAbhStride + bq * 16]) = bh1; \
-    *reinterpret_cast<uint4*>(&lds[BUF][3 * kAbhPlane + brow * kAbhStride + bq * 16]) = bl0;  \
-    *reinterpret_cast<uint4*>(&lds[BUF][3 * kAbhPlane + (brow + 64) * kAbhStride + bq * 16]) = bl1;
-
-    auto compute = [&](int buf) {
-        const unsigned char* base = lds[buf];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            h8v ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int ra = (wm * 64 + q * 32 + li) * kAbhStride + ks * 32 + 16 * lh;
-                const int rb = (wn * 64 + q * 32 + li) * kAbhStride + ks * 32 + 16 * lh;
-                ah[q] = *reinterpret_cast<const h8v*>(base + ra);
-                al[q] = *reinterpret_cast<const h8v*>(base + kAbhPlane + ra);
-                bh[q] = *reinterpret_cast<const h8v*>(base + 2 * kAbhPlane + rb);
-                bl[q] = *reinterpret_cast<const h8v*>(base + 3 * kAbhPlane + rb);
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bl[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[a], bh[c], acc[a][c], 0, 0, 0);
-                    acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bh[c], acc[a][c], 0, 0, 0);
-                }
-        }
-    };
-
-    ABH_FETCH(0)
-    ABH_PARK(0)
-    __syncthreads();
-    int buf = 0;
-    for (int k0 = 32; k0 < g.K; k0 += 32) {
-        ABH_FETCH(k0)
-        __builtin_amdgcn_sched_barrier(0);
-        compute(buf);
-        __builtin_amdgcn_sched_barrier(0);
-        ABH_PARK(buf ^ 1)
-        __syncthreads();
-        buf ^= 1;
-    }
-    compute(buf);
-#undef ABH_FETCH
-#undef ABH_A
-#undef ABH_PARK
-
-    float vmax = 0.f;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int n = n0 + (wn * 2 + c) * 32 + li;
-            const float r1b = g.r1a ? g.r1b[n] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long m = m0 + (wm * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                float v = acc[a][c][r] * ginv;
-                if (g.r1a) v = fmaf(g.r1a[m * g.r1a_ld], r1b, v);
-                v = hmask[a][c][r] > 0.f ? v : g.alpha * v;
-                vmax = fmaxf(vmax, fabsf(v));
-                g.Out[m * g.ldo + n] = v;
-            }
-        }
-    if (g.gmax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        if (lane == 0) {
-            unsigned* slot = g.gmax + (blockIdx.x & 63);
-            const unsigned vb = __float_as_uint(vmax);
-            if (vb > *slot) atomicMax(slot, vb);
-        }
-    }
-}
-
-void launch_gemm_abt_h(const GemmAbt& g, hipStream_t s) {
-    if (g.M <= 0) return;
-    hipLaunchKernelGGL(gemm_abt_h_kernel, dim3((unsigned)((g.M / 128) * (g.N / 128))), dim3(256), 0, s, g);
+    const int wgs = batch_ranges(b, 128);
+    if (g.sig_g && g.Nw <= 128) hipLaunchKernelGGL((gemm_atb_f16_kernel<128, true>), dim3((unsigned)wgs), dim3(256), 0, s, b);
+    else hipLaunchKernelGGL(gemm_atb_f16_kernel<128>, dim3((unsigned)wgs), dim3(256), 0, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------
 // head_wgrad: weight gradients of the two heads (N = 4 columns of Graw): a (K x 4) result needs no matrix core.  One
-// workgroup per row slab, one thread per column of A; writes the same partial layout as gemm_atb (row Kp = column sums).
+// workgroup per row slab; writes the same partial layout as gemm_atb (row Kp = column sums).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void head_wgrad_kernel(const GemmAtb g) {
-    const int split = blockIdx.x, t = threadIdx.x;
-    const long long ms = (long long)split * g.rows_per_split;
-    const long long me = ms + g.rows_per_split < g.M ? ms + g.rows_per_split : g.M;
-    float* part = g.partial + (size_t)split * (g.Kp + 1) * g.Nw;
-    for (int k = t; k < g.Kp + 1; k += 256) {
-        const bool ones = k == g.Kp;                       // the extra row: column sums of G
-        const bool valid = ones || k < g.K;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if (valid)
-            for (long long m = ms; m < me; m += 8) {       // slabs are multiples of 16 rows: 8 loads in flight
-                float av[8];
-                float4 gv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    gv[q] = *reinterpret_cast<const float4*>(g.G + (m + q) * g.ldg);
-                    av[q] = ones ? 1.0f : g.a_f16 ? (float)reinterpret_cast<const _Float16*>(g.A)[(m + q) * g.lda + k]
-                                                  : g.A[(m + q) * g.lda + k];
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    a0 = fmaf(av[q], gv[q].x, a0); a1 = fmaf(av[q], gv[q].y, a1);
-                    a2 = fmaf(av[q], gv[q].z, a2); a3 = fmaf(av[q], gv[q].w, a3);
-                }
-            }
-        float* o = part + (size_t)k * g.Nw;
-        o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3;
-    }
-}
-
-// fp16 activations (mixed_float16 policy).  A row of A is read as a whole by neighbouring threads (8 bytes = four columns
-// each): K / 4 column quads x RL row lanes per workgroup, four rows in flight per thread, the row lanes' partial sums
-// combined through LDS in a fixed order.  (The first version, one thread per column pair striding down the rows with
-// 4-byte loads, ran at 1.1 TB/s.)
-template <bool F16>      // F16: A holds fp16 elements (mixed_float16 policy); else fp32 (16-byte loads of four columns)
+// Row-major fp32 A (the reference trainer).  A row of A is read as a whole by neighbouring threads (16 bytes = four columns
+// each): Kp / 4 column quads (at most 80: Kp <= 320 here) x RL row lanes per workgroup, four rows in flight per thread, the
+// row lanes' partial sums combined through LDS in a fixed order.
 __global__ __launch_bounds__(256) void head_wgrad_rows_kernel(const GemmAtb g) {
     __shared__ float red[256][17];                          // [thread][16 sums + 1 pad]
     __shared__ float gsum[256][4];
@@ -1337,7 +921,6 @@ __global__ __launch_bounds__(256) void head_wgrad_rows_kernel(const GemmAtb g) {
     const long long ms = (long long)split * g.rows_per_split;
     const long long me = ms + g.rows_per_split < g.M ? ms + g.rows_per_split : g.M;
     float* part = g.partial + (size_t)split * (g.Kp + 1) * g.Nw;
-    const uint16_t* A = reinterpret_cast<const uint16_t*>(g.A);
     const int KQ = g.Kp / 4;                               // column quads (Kp is a multiple of 4; <= 80)
     const int RL = 256 / KQ;                               // row lanes
     const int cq = t % KQ, rl = t / KQ;
@@ -1351,7 +934,6 @@ __global__ __launch_bounds__(256) void head_wgrad_rows_kernel(const GemmAtb g) {
     float gs[4] = {0.f, 0.f, 0.f, 0.f};
     if (active) {
         for (long long m = ms + rl; m < me; m += 4LL * RL) {
-            uint2 av[4];
             float4 af[4];
             float4 gv[4];
 #pragma unroll
@@ -1359,18 +941,11 @@ __global__ __launch_bounds__(256) void head_wgrad_rows_kernel(const GemmAtb g) {
                 const long long mm = m + (long long)u * RL;
                 const bool in = mm < me;
                 gv[u] = in ? *reinterpret_cast<const float4*>(g.G + mm * g.ldg) : make_float4(0.f, 0.f, 0.f, 0.f);
-                if constexpr (F16) av[u] = in && live ? *reinterpret_cast<const uint2*>(A + mm * g.lda + 4 * cq) : make_uint2(0u, 0u);
-                else af[u] = in && live ? *reinterpret_cast<const float4*>(g.A + mm * g.lda + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
+                af[u] = in && live ? *reinterpret_cast<const float4*>(g.A + mm * g.lda + 4 * cq) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                float x[4];
-                if constexpr (F16) {
-                    const h2v lo = __builtin_bit_cast(h2v, av[u].x), hi = __builtin_bit_cast(h2v, av[u].y);
-                    x[0] = (float)lo[0]; x[1] = (float)lo[1]; x[2] = (float)hi[0]; x[3] = (float)hi[1];
-                } else {
-                    x[0] = af[u].x; x[1] = af[u].y; x[2] = af[u].z; x[3] = af[u].w;
-                }
+                const float x[4] = {af[u].x, af[u].y, af[u].z, af[u].w};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     a[c][0] = fmaf(x[c], gv[u].x, a[c][0]); a[c][1] = fmaf(x[c], gv[u].y, a[c][1]);
@@ -1481,22 +1056,14 @@ __global__ __launch_bounds__(256) void head_wgrad_frag_kernel(const GemmAtb g) {
     }
 }
 
-void launch_head_wgrad(const GemmAtb& g, hipStream_t s) {
-    if (g.frag) {
-        const int fsplits = (int)((g.M + g.rows_per_split - 1) / g.rows_per_split);
-        if (g.a_f16) hipLaunchKernelGGL(head_wgrad_frag_kernel<true>, dim3((unsigned)fsplits), dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(head_wgrad_frag_kernel<false>, dim3((unsigned)fsplits), dim3(256), 0, s, g);
-        return;
-    }
-    const int splits = (int)((g.M + g.rows_per_split - 1) / g.rows_per_split);
-    // rows read as a whole by neighbouring threads (needs at most 256 column quads; Kp <= 320 here); the column-strided
-    // head_wgrad_kernel stays for wider matrices
-    if (g.Kp % 4 == 0 && g.Kp <= 1024 && g.lda % 4 == 0) {
-        if (g.a_f16) hipLaunchKernelGGL(head_wgrad_rows_kernel<true>, dim3((unsigned)splits), dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(head_wgrad_rows_kernel<false>, dim3((unsigned)splits), dim3(256), 0, s, g);
-        return;
-    }
-    hipLaunchKernelGGL(head_wgrad_kernel, dim3((unsigned)splits), dim3(256), 0, s, g);
+// The row-major kernel needs whole column quads in 16-byte-aligned rows and at most 256 of them (one thread each, the
+// bounds of its LDS reduction): Kp % 4 == 0, Kp <= 1024, lda % 4 == 0.  The layer table's heads have Kp = lda = 128 / 256 /
+// kLdC8 (train_api.hip::wgrad_reference holds the table to it at compile time).
+void launch_head_wgrad(const GemmAtb& g, bool frag, hipStream_t s) {
+    const dim3 grid((unsigned)((g.M + g.rows_per_split - 1) / g.rows_per_split));
+    if (!frag) hipLaunchKernelGGL(head_wgrad_rows_kernel, grid, dim3(256), 0, s, g);
+    else if (g.a_f16) hipLaunchKernelGGL(head_wgrad_frag_kernel<true>, grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(head_wgrad_frag_kernel<false>, grid, dim3(256), 0, s, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1615,12 +1182,6 @@ __global__ void relayout_kernel(const RelayoutArgs a) {
     const float v = valid ? a.w[(size_t)kb * a.N_real + n] : 0.f;
     a.W[(size_t)kt * a.Np + n] = v;
     a.WT[(size_t)n * a.Kp + kt] = v;
-    if (a.Whi) {
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        a.Whi[(size_t)kt * a.Np + n] = __builtin_bit_cast(uint16_t, hi);
-        a.Wlo[(size_t)kt * a.Np + n] = __builtin_bit_cast(uint16_t, lo);
-    }
     if (kt == 0) a.bias[n] = n < a.N_real ? a.b[n] : 0.f;
 }
 
@@ -1987,7 +1548,7 @@ void launch_composite_bwd(const float* raw, const float* z, const float* T, long
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ Graw, const float* __restrict__ W9,
                                                        const float* __restrict__ H9, long long M, float alpha,
-                                                       float* __restrict__ G9, unsigned* __restrict__ gmax) {
+                                                       float* __restrict__ G9) {
     __shared__ float w[128 * 3];
     for (int i = threadIdx.x; i < 128 * 3; i += 256) w[i] = W9[(i / 3) * 32 + (i % 3)];
     __syncthreads();
@@ -2007,27 +1568,13 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     }
     out.x = ov[0]; out.y = ov[1]; out.z = ov[2]; out.w = ov[3];
     *reinterpret_cast<float4*>(G9 + m * 128 + j) = out;
-    if (gmax) {      // uniform per launch.  One slot check per workgroup: 65 k workgroups each polling per wave was 0.7 ms
-        __shared__ float wmax[4];
-        float vmax = fmaxf(fmaxf(fabsf(ov[0]), fabsf(ov[1])), fmaxf(fabsf(ov[2]), fabsf(ov[3])));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = vmax;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const float m4 = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-            unsigned* slot = gmax + (blockIdx.x & 63);
-            const unsigned vb = __float_as_uint(m4);
-            if (vb > *slot) atomicMax(slot, vb);
-        }
-    }
 }
 
 void launch_head_bwd(const float* Graw, const float* W9, const float* H9, long long M, float alpha, float* G9,
-                     unsigned* gmax, hipStream_t s) {
+                     hipStream_t s) {
     if (M <= 0) return;
     hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)((M * 32 + 255) / 256)), dim3(256), 0, s, Graw, W9, H9, M, alpha,
-                       G9, gmax);
+                       G9);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -224,14 +224,12 @@ def test_training_gradients_float32_policy(oracle, lx, ld, na, capsys):
 
 @pytest.mark.parametrize("lx,ld,na", [(3, 2, 2), (2, 4, 0), (10, 2, 2)])
 def test_layerwise_exact_fp32_trainer(oracle, lx, ld, na, monkeypatch):
-    """The layer-wise exact-fp32 trainer behind NERF_TRAIN_FORWARD / _WGRAD / _DGRAD (GEMMs over the encoded inputs in the
+    """The layer-wise exact-fp32 reference trainer behind NERF_TRAIN_FORWARD=gemm (GEMMs over the encoded inputs in the
     network's own column layout, the encoding backward on the compact layout) at alpha 1 with the sampler term: 2e-4 of
     max|g| against float64 autograd."""
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
-    monkeypatch.setenv("NERF_TRAIN_WGRAD", "fp32")
-    monkeypatch.setenv("NERF_TRAIN_DGRAD", "fp32")
     p = _train_problem(oracle, seed=7)
     kw = _kw(lx, ld, na)
     bc, bf = _blobs(lx, ld, na, seed=27)

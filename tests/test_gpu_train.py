@@ -984,7 +984,7 @@ def test_gradients_at_the_reference_sample_counts(oracle, golden_ckpt, alpha, ca
 
 def test_fp16_core_trainer_equals_exact_fp32_trainer_at_full_size(oracle, golden_ckpt, capsys, monkeypatch):
     """The default trainer forms every product on the fp16 matrix cores with split operands; the exact-fp32 MFMA path
-    stays behind NERF_TRAIN_FORWARD / NERF_TRAIN_WGRAD / NERF_TRAIN_DGRAD.  On a batch far too large for the CPU oracle
+    stays behind NERF_TRAIN_FORWARD=gemm, which selects the whole layer-wise reference trainer.  On a batch far too large for the CPU oracle
     (1024 rays x (64 + 128) samples) the two must give the same loss and the same gradients to fp32-class accuracy.
     Compared with the sampler term off: through the sampler a single LeakyReLU sign flip in the fine pass (the two
     forwards differ by ~1e-6, and ~1e2 of 3e7 pre-activations per layer sit that close to zero) moves one ray's whole
@@ -997,11 +997,8 @@ def test_fp16_core_trainer_equals_exact_fp32_trainer_at_full_size(oracle, golden
         for mode in ("fp32", "f16"):
             if mode == "fp32":
                 monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
-                monkeypatch.setenv("NERF_TRAIN_WGRAD", "fp32")
-                monkeypatch.setenv("NERF_TRAIN_DGRAD", "fp32")
             else:
-                for k in ("NERF_TRAIN_FORWARD", "NERF_TRAIN_WGRAD", "NERF_TRAIN_DGRAD"):
-                    monkeypatch.delenv(k, raising=False)
+                monkeypatch.delenv("NERF_TRAIN_FORWARD", raising=False)
             ctx = _ctx(p)
             ctx.train_begin(5e-4, sampler_gradient=sg)
             res[(sg, mode)] = ctx.train_gradients(o, d, tgt, 64, 128, seed=3)

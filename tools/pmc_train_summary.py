@@ -12,11 +12,9 @@ import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))     # the batch's output folder, as in tools/gpu_profile_batch.sh
 KINDS = (("mlp_f16x3_stash_kernel", "fused forward with activation stash (3-pass split fp16)"),
-         ("gemm_abt_h_kernel", "gemm_abt_h data gradient (3-pass split fp16)"),
-         ("gemm_atb_h_kernel", "gemm_atb_h weight gradient (3-pass split fp16)"),
-         ("gemm_abt_kernel<2, 2, 2, 2, 0>", "gemm_abt forward, exact fp32 (xyz-only network / NERF_TRAIN_FORWARD=gemm)"),
-         ("gemm_abt_kernel<2, 2, 2, 2, 2>", "gemm_abt data gradient, exact fp32 (NERF_TRAIN_DGRAD=fp32)"),
-         ("gemm_atb_kernel", "gemm_atb weight gradient, exact fp32 (NERF_TRAIN_WGRAD=fp32)"))
+         ("gemm_abt_kernel<2, 2, 2, 2, 0>", "gemm_abt forward, exact fp32 (reference trainer, NERF_TRAIN_FORWARD=gemm)"),
+         ("gemm_abt_kernel<2, 2, 2, 2, 2>", "gemm_abt data gradient, exact fp32 (reference trainer)"),
+         ("gemm_atb_kernel", "gemm_atb weight gradient, exact fp32 (reference trainer)"))
 
 
 def main():
