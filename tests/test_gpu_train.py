@@ -14,7 +14,29 @@ import math
 import numpy as np
 import pytest
 
+import grad_blocks as GB
+
 pytestmark = pytest.mark.gpu
+
+# Block by block (tests/grad_blocks.py): next to every blob-wide comparison below, each kernel, each bias and each row group
+# with its own code path in the trainer is compared against ITS OWN max -- the blob-wide max only sees the loudest tensors.
+BLOCKS = GB.blocks(5, 4, 2)
+
+
+# One LeakyReLU mask flip, block by block (alpha = 0.05).  A pre-activation z of layer L (row r, unit j) that the fp32 forward
+# puts on the other side of zero than float64 (|z| ~ 1e-6) turns LeakyReLU' there from 1 into alpha or back.  Layers above L
+# do not notice (the activation moves by (1 - alpha) |z|); layer L's kernel and bias change in column j by that row's term
+# times (1 - alpha) or (1 / alpha - 1), and every layer below L receives the changed delta through W_L^T.  The signature is
+# therefore: every block of layers 0..L off by a similar relative amount ~ |one row's term| / ||block|| (1e-4..5e-3 with the
+# ~700..2000 sample rows of these problems), every block above L at the fp32 floor.  Where float32 autograd has NO flip on
+# the same inputs, 16 x its figure is no yardstick for those layers: the test names L, the blocks of layers 0..L keep the
+# blob-wide bar (5e-2 of the blob max), and every block above L is asserted at the oracle-derived bar.
+
+
+def _f32(fn, *a, **kw):
+    """The same oracle call in float32: the reference's own rounding, the yardstick of the block-wise bars."""
+    import torch
+    return fn(*a, dtype=torch.float32, **kw)
 
 
 def _rays(oracle, n, seed=0, hw=8):
@@ -51,8 +73,9 @@ def _cos(a, b):
     return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
 
 
-def test_gradients_coarse_only(oracle, golden_ckpt):
-    """No fine network (n_render_samples_fine == 0, src/NeRF.py:36-39,153): loss = coarse MSE alone."""
+def test_gradients_coarse_only(oracle, golden_ckpt, capsys):
+    """No fine network (n_render_samples_fine == 0, src/NeRF.py:36-39,153): loss = coarse MSE alone.  No sampler term either:
+    every block of the coarse gradient at the alpha = 0.05 bar (relative L2, 16 x the float32 oracle's)."""
     from oracle import train_oracle as T
     p = _problem(oracle, golden_ckpt)
     ctx = _ctx(p, fine=False)
@@ -63,19 +86,24 @@ def test_gradients_coarse_only(oracle, golden_ckpt):
     assert abs(m["loss"] - r["loss"]) <= 1e-6 * r["loss"] + 1e-7
     assert abs(m["psnr_coarse"] - r["psnr_coarse"]) <= 1e-4
     assert _relerr(gc, r["grad_coarse"]) <= 1e-2 and _cos(gc, r["grad_coarse"]) > 0.9999
+    r32 = _f32(T.train_gradients, p["bc"], None, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], None)
+    with capsys.disabled():
+        GB.check_fp32_masks(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, "[coarse only, alpha 0.05] coarse")
     ctx.close()
 
 
 @pytest.mark.parametrize("alpha", [1.0, 0.05])
 @pytest.mark.parametrize("sampler_gradient", [False, True])
-def test_gradients_coarse_and_fine(oracle, golden_ckpt, sampler_gradient, alpha):
+def test_gradients_coarse_and_fine(oracle, golden_ckpt, sampler_gradient, alpha, capsys):
     """alpha = 1 makes the network smooth (LeakyReLU = identity): every GEMM, the heads, compositing, positional
     encoding and sampler backward are then checked at 2e-4 of max|g| (measured 1e-5..4e-5, the fp32 floor: the
     float32 oracle differs from the float64 one by 2.4e-5..2.8e-5 here).  alpha = 0.05 (the reference's value) adds
     the LeakyReLU' masks, where single fp32-vs-float64 sign flips of near-zero pre-activations move a gradient
     entry by ~1/rows of its value, and one flip in the fine pass moves one ray's sampler gradient, i.e. ~1/N of
     the coarse gradient (N = 48 rays here: 2e-2 measured): bar 5e-2 of max|g| and cosine > 0.999 -- a wrong mask
-    would be an O(1) error."""
+    would be an O(1) error.
+    Block by block: alpha = 1 at 2e-4 of each block's own max; alpha = 0.05 by relative L2 at 16 x the float32 oracle's, on
+    the fine network and -- where the sampler term, which one fine-pass flip moves by ~1/N, is off -- on the coarse one."""
     from oracle import train_oracle as T
     p = _problem(oracle, golden_ckpt)
     ctx = _ctx(p, leaky_relu_alpha=alpha)
@@ -89,6 +117,17 @@ def test_gradients_coarse_and_fine(oracle, golden_ckpt, sampler_gradient, alpha)
     tol, cos_min = (2e-4, 0.9999999) if alpha == 1.0 else (5e-2, 0.999)
     assert _relerr(gc, r["grad_coarse"]) <= tol and _cos(gc, r["grad_coarse"]) > cos_min
     assert _relerr(gf, r["grad_fine"]) <= tol and _cos(gf, r["grad_fine"]) > cos_min
+    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+               sampler_grad=sampler_gradient, alpha=alpha)
+    tag = f"[48 x (16+24), alpha {alpha:g}, sampler term {'on' if sampler_gradient else 'off'}]"
+    with capsys.disabled():
+        if alpha == 1.0:
+            GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, tol, tag + " coarse")
+            GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, tol, tag + " fine")
+        else:
+            if not sampler_gradient:
+                GB.check_fp32_masks(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, tag + " coarse")
+            GB.check_fp32_masks(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, tag + " fine")
     # the reference's sampler term is a large part of the coarse gradient: make sure it is really there
     if sampler_gradient and alpha != 1.0:
         r0 = T.train_gradients(p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
@@ -126,10 +165,18 @@ def test_gradients_with_a_wide_dynamic_range_between_rays(oracle, golden_ckpt, p
     assert abs(m["loss"] - r["loss"]) <= (2e-3 if mixed else 2e-6) * r["loss"]
     tol = 2e-2 if mixed else 2e-4
     assert ec <= tol and ef <= tol, (ec, ef)
+    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], tgt, p["near"], p["far"], p["u_c"], p["u_f"], alpha=1.0,
+               fp16_loss_scale=32768.0 if mixed else None)
+    with capsys.disabled():
+        for net, g in (("coarse", gc), ("fine", gf)):
+            if mixed:
+                GB.check_mixed(g, r["grad_" + net], r32["grad_" + net], BLOCKS, f"[{policy}, wide range] {net}")
+            else:
+                GB.check_fp32_smooth(g, r["grad_" + net], r32["grad_" + net], BLOCKS, tol, f"[{policy}, wide range] {net}")
     ctx.close()
 
 
-def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt):
+def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt, capsys):
     """u = NULL: jitter and inverse-CDF draws from the on-device Philox (same counters in the forward sampler
     and in its backward); N*S not a multiple of the 128-row GEMM tile; n_angles = 1 network."""
     from oracle import train_oracle as T
@@ -154,6 +201,14 @@ def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt):
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     assert _relerr(gc, r["grad_coarse"]) <= 5e-2 and _cos(gc, r["grad_coarse"]) > 0.999
     assert _relerr(gf, r["grad_fine"]) <= 5e-2 and _cos(gf, r["grad_fine"]) > 0.999
+    # Block by block (fine network, alpha 0.05, relative L2 at 16 x the float32 oracle's largest = 3.7e-3): one mask flip in
+    # layer 0 (see the note at the top of this file) -- k0 4.3e-3, b0 3.9e-3, every block of layers 1..10 under the bar -- so
+    # k0 and b0 keep the blob-wide 5e-2 and the other 26 blocks, the sigma head and the row groups included, are asserted.
+    r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=1)
+    blks = GB.blocks(5, 4, 1)
+    with capsys.disabled():
+        GB.check_fp32_masks(gf, r["grad_fine"], r32["grad_fine"], blks, "[37 x (11+19), device RNG, n_angles 1] fine",
+                            named=GB.layers_up_to(blks, 0))
     ctx.close()
 
 
@@ -391,6 +446,8 @@ def test_data_parallel_gradients_equal_full_batch(oracle, golden_ckpt):
         pr.join(timeout=60)
     for rank, gc, gf, w in res:
         assert _relerr(gc, gc_full) <= 1e-5 and _relerr(gf, gf_full) <= 1e-5, rank
+        GB.check_equal(gc, gc_full, BLOCKS, 1e-5, f"rank {rank}, coarse")
+        GB.check_equal(gf, gf_full, BLOCKS, 1e-5, f"rank {rank}, fine")
     np.testing.assert_array_equal(res[0][3], res[1][3])
 
 
@@ -411,6 +468,7 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
     near, far = 0.5, 2.5
     bc, bf = N.glorot_blob(21, n_angles=0), N.glorot_blob(22, n_angles=0)
     bc[-1] = bf[-1] = 1.5
+    blks = GB.blocks(5, 4, 0)
     # (6 rays at the reference's 64 + 128 samples: nearly transparent rays whose colour gradient vanishes while the density
     # gradient does not -- the case that overflowed the fp16 packing of the sigma term before its scale was fixed)
     for n, sc, sf, seed in ((40, 12, 20, 6), (6, 64, 128, 7)):
@@ -439,6 +497,11 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
                 assert _cos(gc, r["grad_coarse"]) > 0.99 and _cos(gf, r["grad_fine"]) > 0.999
                 if alpha == 1.0:        # the arithmetic, mask-free: measured 8.6e-4 / 4.0e-4
                     assert qc <= 5e-3 and qf <= 5e-3 and cc > 0.99999 and cf > 0.99999
+                    e32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha,
+                               fp16_loss_scale=32768.0)
+                    with capsys.disabled():
+                        for net, g in (("coarse", gc), ("fine", gf)):
+                            GB.check_mixed(g, r16["grad_" + net], e32["grad_" + net], blks, f"[xyz-only, mixed, {n} rays] {net}")
                 else:                   # + LeakyReLU sign flips of near-zero pre-activations (fp32 vs float64 accumulation of
                     # the same fp16 products; one flip in the fine pass moves a whole ray's sampler term: 1 / rays)
                     assert qc <= 1.5e-1 and qf <= 5e-2 and cc > 0.995 and cf > 0.999
@@ -449,6 +512,17 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
                 assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
                 assert ec <= tol and _cos(gc, r["grad_coarse"]) > cmin
                 assert ef <= tol and _cos(gf, r["grad_fine"]) > cmin
+                r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha)
+                with capsys.disabled():
+                    tag = f"[xyz-only, float32, {n} rays, alpha {alpha:g}]"
+                    if alpha == 1.0:
+                        GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], blks, tol, tag + " coarse")
+                        GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], blks, tol, tag + " fine")
+                    else:               # the sampler term is on: the fine network.  40 rays: float32 autograd has no mask flip
+                        # (1.7e-5, bar 2.6e-4), the GPU forward has one in layer 3 (note at the top of this file): b2 5.4e-4,
+                        # b1 5.2e-4, k0..k3 4.6e-4..5.1e-4, b0 4.9e-4, b3 4.8e-4, every block of layers 4..11 under the bar
+                        named = GB.layers_up_to(blks, 3) if n == 40 else ()
+                        GB.check_fp32_masks(gf, r["grad_fine"], r32["grad_fine"], blks, tag + " fine", named=named)
             if alpha == 0.05 and n == 40:
                 losses = [ctx.train_step(o, d, tgt, sc, sf, u_c, u_f)["loss"] for _ in range(20)]
                 assert np.isfinite(losses).all() and losses[-1] < 0.7 * losses[0]
@@ -673,6 +747,8 @@ def test_train_edge_shapes_and_transparent_scene(oracle, golden_ckpt, n, sc, sf)
             assert _relerr(gc, r["grad_coarse"]) <= 5e-2
         else:
             assert np.abs(gc).max() <= 1e-9
+        if not r["grad_coarse"].any():          # the transparent network: zero on purpose, and exactly zero block by block
+            GB.assert_blocks(gc, r["grad_coarse"], BLOCKS, 0.0, label="transparent coarse network", exact_zero=True)
         first = ctx.train_step(o, d, tgt, sc, sf, u_c, u_f)["loss"]
         assert np.isfinite(first)
         ctx.close()
@@ -792,6 +868,10 @@ def test_mixed_float16_policy_gradients_and_loss_scaling(oracle, golden_ckpt, ca
         assert ef <= 2e-2 and cf > 0.9999 and ec <= 2e-1 and cc > 0.999
         assert qc <= 2e-2 and qf <= 2e-3                 # measured 6.5e-3 / 5.0e-4
         assert abs(m["loss"] - r16["loss"]) <= 2e-5 * r16["loss"]
+        e32 = _f32(T.train_gradients, *args, sampler_grad=True, alpha=1.0, fp16_loss_scale=scale)
+        with capsys.disabled():
+            GB.check_mixed(gc, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, f"[mixed_float16, scale {scale:g}] coarse")
+            GB.check_mixed(gf, r16["grad_fine"], e32["grad_fine"], BLOCKS, f"[mixed_float16, scale {scale:g}] fine")
         ctx.close()
     # The same comparison at the reference's alpha = 0.05 and with the sampler term off (classic NeRF).  Against float64
     # the fp16 class shows as 1.5e-2 (sampler off) / 3.4e-1 (sampler on: the inverse-CDF interpolation's 1e5 gain, its
@@ -815,6 +895,11 @@ def test_mixed_float16_policy_gradients_and_loss_scaling(oracle, golden_ckpt, ca
         # measured at alpha 0.05 with the sampler term: coarse 2.5e-3, fine 9.8e-3 (a few LeakyReLU sign flips of near-zero
         # pre-activations: fp32 against float64 accumulation of the same fp16 products)
         assert qc <= 2e-2 and qf <= 3e-2 and _cos(gc0, r16["grad_coarse"]) > 0.9999 and _cos(gf0, r16["grad_fine"]) > 0.9999
+        if alpha == 1.0:                   # (the block-wise mixed bar is an alpha = 1 bar: no mask flips)
+            e32 = _f32(T.train_gradients, *args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=32768.0)
+            with capsys.disabled():
+                GB.check_mixed(gc0, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, "[mixed_float16, sampler term off] coarse")
+                GB.check_mixed(gf0, r16["grad_fine"], e32["grad_fine"], BLOCKS, "[mixed_float16, sampler term off] fine")
     # a power-of-two loss scale changes nothing but which gradient entries leave fp16's normal range in the half-width
     # buffers: between two sane scales the unscaled gradients agree to fp16 class
     np.testing.assert_allclose(grads[32768.0][1], grads[4096.0][1], rtol=0, atol=2e-2 * np.abs(grads[4096.0][1]).max())
@@ -862,11 +947,17 @@ def test_backward_through_render(oracle, golden_ckpt, sampler_gradient, capsys):
         print(f"\n[backward through render(), 40 rays x (55 + 55), sampler term {'on' if sampler_gradient else 'off'}] "
               f"fine gradient vs float64 autograd {ef:.2e} of max|g|, cosine {cf:.7f}", end="")
     assert ef <= 2e-4 and cf > 0.9999999
+    r32 = _f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
+               sampler_grad=sampler_gradient, alpha=1.0)
+    with capsys.disabled():
+        GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, 2e-4, "[backward through render()] fine")
     if sampler_gradient:
         ec, cc = _relerr(gc, r["grad_coarse"]), _cos(gc, r["grad_coarse"])
         with capsys.disabled():
             print(f"; coarse (through the sampler only) {ec:.2e}, cosine {cc:.7f}")
         assert ec <= 2e-4 and cc > 0.9999999
+        with capsys.disabled():          # (render() does not read the coarse colour branch: those blocks are exactly zero)
+            GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, 2e-4, "[backward through render()] coarse")
     else:
         assert not gc.any() and not r["grad_coarse"].any()      # render() does not depend on the coarse weights then
     # sum with the ray loss, as the reference does before its single Adam step (src/DietNeRF.py:140-153)
@@ -955,6 +1046,17 @@ def test_gradients_at_ragged_shapes(oracle, golden_ckpt, shape, capsys):
               f"max|g| coarse {ec:.2e}, fine {ef:.2e}; cosine {cc:.7f}, {cf:.7f}")
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     assert ec <= 5e-4 and cc > 0.999999 and ef <= 5e-4 and cf > 0.999999
+    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+               sampler_grad=True, alpha=1.0)
+    # 130 x (2 + 3): two coarse samples per ray in almost empty space leave the coarse sigma head's four blocks at 1e-11 of
+    # the blob max (under the floor, above the cap of two).  Lifting the sigma bias until they resolve makes the problem so
+    # ill-conditioned that float32 autograd itself misses blocks by 1.1e-3, so those four blocks are left to the blob-wide
+    # assert here and to test_small_blocks_survive_a_dominant_batch (130 x (5 + 3), sigma bias lifted); every other coarse
+    # block and the whole fine network (its dead sigma head: exactly zero) are compared.
+    coarse_blocks = BLOCKS if sc > 2 else [b for b in BLOCKS if b[0] not in ("k10", "k10[hidden]", "k10[dir]", "b10")]
+    with capsys.disabled():
+        GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], coarse_blocks, 5e-4, f"[{n} x ({sc}+{sf})] coarse")
+        GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, 5e-4, f"[{n} x ({sc}+{sf})] fine")
     ctx.close()
 
 
@@ -979,7 +1081,55 @@ def test_gradients_at_the_reference_sample_counts(oracle, golden_ckpt, alpha, ca
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     tol, cos_min = (2e-4, 0.9999999) if alpha == 1.0 else (5e-2, 0.999)
     assert ec <= tol and cc > cos_min and ef <= tol and cf > cos_min
+    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+               sampler_grad=True, alpha=alpha)
+    with capsys.disabled():
+        if alpha == 1.0:
+            GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, tol, "[32 x (64+128), alpha 1] coarse")
+            GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, tol, "[32 x (64+128), alpha 1] fine")
+        else:
+            GB.check_fp32_masks(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, "[32 x (64+128), alpha 0.05] fine")
     ctx.close()
+
+
+@pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
+@pytest.mark.parametrize("n_angles", [2, 1, 0])
+def test_small_blocks_survive_a_dominant_batch(oracle, n_angles, policy, capsys):
+    """130 rays x (5 + 3) samples: 650 / 390 sample rows, i.e. two row slabs of the weight-gradient GEMMs of which the second
+    is mostly empty, and split slabs that hold no row at all -- the shape at which the sigma head's partial (it rides in layer
+    8's GEMM) and the bias rows of EMPTY splits reach the reduction.  Every block of both gradients against the oracle at
+    alpha = 1 (float32 policy: 2e-4 of the block's own max vs float64 autograd; mixed_float16: 4 x the fp16 emulation's own
+    float32-vs-float64 distance, at least 2e-2, vs the emulation), for all three network variants, with the sigma bias
+    lifted as in test_gradients_device_rng_and_odd_sizes so that the sigma head's gradient is not trivially zero."""
+    from oracle import train_oracle as T
+    import nerf_and_dietnerf_amd as N
+    mixed = policy == "mixed_float16"
+    n, sc, sf = 130, 5, 3
+    o, d, rng = _rays(oracle, n, 17, hw=16)
+    tgt = rng.random((n, 3), dtype=np.float32)
+    u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
+    bc, bf = N.glorot_blob(51, n_angles=n_angles), N.glorot_blob(52, n_angles=n_angles)
+    bc[-1] = bf[-1] = 2.0
+    near, far = 0.5, 2.5
+    blks = GB.blocks(5, 4, n_angles)
+    ctx = N.Context(near=near, far=far, n_angles=n_angles, leaky_relu_alpha=1.0)
+    ctx.load_weights(0, bc)
+    ctx.load_weights(1, bf)
+    ctx.train_begin(1e-3, mixed_float16=mixed)
+    m, gc, gf = ctx.train_gradients(o, d, tgt, sc, sf, u_c, u_f)
+    ctx.close()
+    kw = dict(n_angles=n_angles, alpha=1.0, fp16_loss_scale=32768.0 if mixed else None)
+    r = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, **kw)
+    r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, **kw)
+    assert np.isfinite(gc).all() and np.isfinite(gf).all()
+    assert abs(m["loss"] - r["loss"]) <= (1e-4 if mixed else 2e-6) * r["loss"]
+    with capsys.disabled():
+        for net, g in (("coarse", gc), ("fine", gf)):
+            tag = f"[130 x (5+3), n_angles {n_angles}, {policy}] {net}"
+            if mixed:
+                GB.check_mixed(g, r["grad_" + net], r32["grad_" + net], blks, tag)
+            else:
+                GB.check_fp32_smooth(g, r["grad_" + net], r32["grad_" + net], blks, 2e-4, tag)
 
 
 def test_fp16_core_trainer_equals_exact_fp32_trainer_at_full_size(oracle, golden_ckpt, capsys, monkeypatch):
@@ -1052,6 +1202,12 @@ def test_gradients_of_a_large_batch_equal_the_mean_of_its_halves(oracle, golden_
     tol = 2e-5 if policy == "mixed_float16" else 2e-6
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
     assert abs(float(m["loss"]) - loss) <= 1e-6 * loss and ec <= tol and ef <= tol
+    with capsys.disabled():
+        for net, g, a in (("coarse", gc, acc_c), ("fine", gf, acc_f)):
+            errs = GB.block_errors(g, a, BLOCKS)
+            print(f"\n    [{policy}, 8192 rays vs halves] {net}: {GB.summary(errs)}", end="")
+    GB.check_equal(gc, acc_c, BLOCKS, tol, "coarse")
+    GB.check_equal(gf, acc_f, BLOCKS, tol, "fine")
     ctx.close()
 
 
@@ -1121,6 +1277,13 @@ def test_backward_through_render_and_mixed_policy_for_the_other_network_variants
     assert ec <= 2e-4 and ef <= 2e-4
     # (the coarse gradient runs through the sampler's gains: measured 1.2e-2 on this problem, 8.6e-4 on the one above)
     assert abs(m["loss"] - r16["loss"]) <= 1e-4 * r16["loss"] and qc <= 3e-2 and qf <= 5e-3
+    blks = GB.blocks(5, 4, n_angles)
+    r32 = _f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, **kw)
+    e32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
+    with capsys.disabled():
+        for net, g, h in (("coarse", gc, hc), ("fine", gf, hf)):
+            GB.check_fp32_smooth(g, r["grad_" + net], r32["grad_" + net], blks, 2e-4, f"[n_angles {n_angles}, render()] {net}")
+            GB.check_mixed(h, r16["grad_" + net], e32["grad_" + net], blks, f"[n_angles {n_angles}, mixed train step] {net}")
 
 
 @pytest.mark.parametrize("sampler_gradient", [True, False])
@@ -1150,10 +1313,16 @@ def test_backward_through_render_mixed_policy(oracle, golden_ckpt, sampler_gradi
         line = (f"\n[backward through render(), mixed_float16, loss scale {scale:g}, sampler term "
                 f"{'on' if sampler_gradient else 'off'}] fine vs the fp16-emulating oracle {qf:.2e} of max|g|, cosine {cf:.6f}")
         assert qf <= 5e-3 and cf > 0.9999
+        e32 = _f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
+                   sampler_grad=sampler_gradient, alpha=1.0, fp16_loss_scale=scale)
+        with capsys.disabled():
+            GB.check_mixed(gf, r16["grad_fine"], e32["grad_fine"], BLOCKS, f"[render(), mixed, scale {scale:g}] fine")
         if sampler_gradient:
             qc, cc = _relerr(gc, r16["grad_coarse"]), _cos(gc, r16["grad_coarse"])
             line += f"; coarse (through the sampler only) {qc:.2e}, cosine {cc:.6f}"
             assert qc <= 3e-2 and cc > 0.999
+            with capsys.disabled():
+                GB.check_mixed(gc, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, f"[render(), mixed, scale {scale:g}] coarse")
         else:
             assert not gc.any()
         with capsys.disabled():
@@ -1241,6 +1410,11 @@ def test_backward_through_render_mixed_policy_other_variants(oracle, n_angles, c
               f"{qc:.2e}, fine {qf:.2e} of max|g|", end="")
     assert np.abs(rgb - r16["rgb"]).max() <= 2e-3
     assert qc <= 3e-2 and qf <= 5e-3
+    e32 = _f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
+    with capsys.disabled():
+        for net, g in (("coarse", gc), ("fine", gf)):
+            GB.check_mixed(g, r16["grad_" + net], e32["grad_" + net], GB.blocks(5, 4, n_angles),
+                           f"[n_angles {n_angles}, render(), mixed] {net}")
     ctx.train_apply()
     assert ctx.train_loss_scale() == (32768.0, 1, 0)
     ctx.close()
@@ -1288,6 +1462,8 @@ def test_render_forward_backward_slots_equal_the_one_call_path(oracle, golden_ck
         np.testing.assert_array_equal(ctx.train_render_forward(3, pb["o"], pb["d"], 55, 55, **kw_b), rgb_b)
         ctx.train_render_backward(0, da, accumulate=True, want_blobs=False)
         gc, gf = ctx.train_render_backward(3, db, accumulate=True)
+        GB.check_equal(gc, gc_ref, GB.blocks(5, 4, n_angles), 0, "slot path, coarse")         # (names the block that differs)
+        GB.check_equal(gf, gf_ref, GB.blocks(5, 4, n_angles), 0, "slot path, fine")
         np.testing.assert_array_equal(gc, gc_ref)
         np.testing.assert_array_equal(gf, gf_ref)
         with pytest.raises(RuntimeError, match="holds no forward"):
