@@ -30,7 +30,8 @@ extern "C" {
 #endif
 
 /* 6 also covers the forward-facing-scene entries added after it (nerf_ctx_set_sampling, nerf_ctx_set_ray_space,
- * nerf_rays_to_ndc; marked "ABI 6+" below): they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_rays_to_ndc) and the scene-box entries (nerf_ctx_set_scene_box, nerf_ray_box_bounds, nerf_get_z_values_rays), all
+ * marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -119,6 +120,29 @@ int nerf_ctx_set_precision(nerf_ctx* ctx, int precision);
  * are given; nerf_get_rays_directions stays world-space.  ndc_near_plane is ignored for NERF_RAYS_WORLD. */
 int nerf_ctx_set_sampling(nerf_ctx* ctx, int mode);
 int nerf_ctx_set_ray_space(nerf_ctx* ctx, int space, float ndc_near_plane);
+/* ABI 6+, scene box: an optional axis-aligned box lo[3] < hi[3] gives every ray its own depth range.  A new ctx has none
+ * (NULL, NULL turns it off again), and without one nothing changes.  The box lives in the space of the rays the depth
+ * kernel is given: world rays, or NDC rays under NERF_RAYS_NDC (nerf_render_image applies it AFTER the transform).
+ * For a ray (o, d) depths are the parameter t of o + t d, as everywhere here; d is not normalised.  In float32, every
+ * operation rounded on its own:
+ *   1. per axis a with d_a != 0: t0 = (lo_a - o_a) / d_a, t1 = (hi_a - o_a) / d_a, axis interval [min(t0,t1), max(t0,t1)];
+ *   2. per axis with d_a == 0 (either sign of zero): no constraint if lo_a <= o_a <= hi_a, otherwise the ray MISSES
+ *      (a branch: a ray that runs along a face of the box is inside);
+ *   3. tn = the largest lower end, tf = the smallest upper end, a = max(tn, near), b = min(tf, far);
+ *   4. the ray HITS if no axis said "misses" and b > a; it is NARROWED if it hits and (a > near or b < far);
+ *   5. a narrowed ray draws its coarse depths with the sampling mode's own formula on [a, b], constants computed per ray:
+ *      linear   z = linspace(a, b, S)[s] + (u (b - a)) / S  (first and last linspace entries exactly a and b; as with
+ *               near / far the last stratum may pass b, by up to (b - a) / S),
+ *      lindisp  z = 1 / (1/a + (1/b - 1/a) (s + u) / S), held in [a, b)  (a >= near > 0 keeps it legal);
+ *   6. a ray that is not narrowed -- it misses, or the box contains its whole [near, far] -- draws exactly the depths of a
+ *      ctx without a box, bit for bit.  A miss is not an error and produces no special value.
+ * Every call that draws coarse depths and has rays follows the box: nerf_get_z_values_rays, nerf_render,
+ * nerf_render_image and both sharded calls, nerf_train_step / nerf_train_gradients, nerf_train_render_gradients and
+ * nerf_train_render_forward (a slot records the depths it drew: its backward pass uses them whatever the box is by then).
+ * nerf_get_z_values has no rays and nerf_render_rays takes the depths from its caller: both ignore the box.  Fine
+ * sampling, compositing, the networks and the backward pass consume the depths and are unchanged.
+ * The setter refuses non-finite values and lo_a >= hi_a ("scene box needs finite lo < hi on every axis"). */
+int nerf_ctx_set_scene_box(nerf_ctx* ctx, const float* lo3, const float* hi3);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of
@@ -144,9 +168,18 @@ int nerf_get_rays_directions(nerf_ctx* ctx, const float* c2w, float fov, int32_t
 int nerf_rays_to_ndc(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float fov,
                      float ndc_near_plane, float* out_orig, float* out_dirs, int mem);
 /* get_z_values(near,far,N,1,S)[:,0,:], src/UtilsCV.py:565-581.  u (N,S) uniform draws or NULL
- * (= on-device Philox keyed by seed and global ray index ray_base+r).  z (N,S).  Follows nerf_ctx_set_sampling. */
+ * (= on-device Philox keyed by seed and global ray index ray_base+r).  z (N,S).  Follows nerf_ctx_set_sampling.  It has
+ * no rays, so it IGNORES the scene box: nerf_get_z_values_rays is the call that follows it. */
 int nerf_get_z_values(nerf_ctx* ctx, int64_t N, int32_t S, const float* u, uint64_t seed,
                       int64_t ray_base, float* z, int mem);
+/* ABI 6+: nerf_get_z_values for callers that have rays (N,4): the coarse depths nerf_render and the trainer draw for them,
+ * following the sampling mode AND the scene box (without a box: exactly nerf_get_z_values). */
+int nerf_get_z_values_rays(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, int32_t S,
+                           const float* u, uint64_t seed, int64_t ray_base, float* z, int mem);
+/* ABI 6+: steps 1-4 of nerf_ctx_set_scene_box for N rays, from the device function the depth kernels call.
+ * bounds (N,2): (a, b) of a narrowed ray, (near, far) of any other; narrowed (N) int32 0 / 1, or NULL.  Fails without a box. */
+int nerf_ray_box_bounds(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
+                        int32_t* narrowed, int mem);
 /* get_z_vals_from_prob_dist_func, src/UtilsCV.py:502-539.  weights,z (N,S); u (N,Sf) or NULL;
  * z_new (N,Sf) sorted.  If z_merged != NULL also writes sort(concat(z_new,z)) (N,S+Sf)
  * (src/NeRF.py:132). */

@@ -53,11 +53,14 @@ SYMBOLS = [
     ("nerf_ctx_set_precision", C.c_int, [_P, C.c_int]),
     ("nerf_ctx_set_sampling", C.c_int, [_P, C.c_int]),
     ("nerf_ctx_set_ray_space", C.c_int, [_P, C.c_int, _F]),
+    ("nerf_ctx_set_scene_box", C.c_int, [_P, _P, _P]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     ("nerf_get_rays_directions", C.c_int, [_P, _P, _F, _I32, _I32, _P, C.c_int]),
     ("nerf_rays_to_ndc", C.c_int, [_P, _P, _P, _I64, _F, _F, _P, _P, C.c_int]),
     ("nerf_get_z_values", C.c_int, [_P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),
+    ("nerf_get_z_values_rays", C.c_int, [_P, _P, _P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),
+    ("nerf_ray_box_bounds", C.c_int, [_P, _P, _P, _I64, _P, _P, C.c_int]),
     ("nerf_sample_pdf", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _U64, _I64, _P, _P, C.c_int]),
     ("nerf_positional_encoding", C.c_int, [_P, _P, _I64, _I32, _I32, _P, C.c_int]),
     ("nerf_model_predict", C.c_int, [_P, C.c_int, _P, _P, _I64, _P, C.c_int]),

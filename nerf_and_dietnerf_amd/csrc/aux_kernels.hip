@@ -7,6 +7,8 @@
 // and two the reference does not have ("Ray and sampling space"):
 //   rays_to_ndc   world rays -> NDC rays of a forward-facing scene
 //   z_values, disparity-linear mode
+//   scene box     ray_box_interval: the part of [near, far] a ray spends inside an axis-aligned box; the box variants of
+//                 the two depth kernels draw on it, ray_box_bounds returns it
 //
 // All HBM-bound fp32/int32 work.  Evaluation order is the canonical one of oracle/nerf_oracle.py:
 // sums / cumsum / cumprod run left to right along the sample axis and products are NOT contracted
@@ -142,11 +144,141 @@ __global__ void z_values_lindisp_kernel(float near_b, float far_below, float inv
     z[m] = fminf(fmaxf(zz, near_b), far_below);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Scene box: the interval of a ray (o, d) inside an axis-aligned box lo < hi, clipped to
+// [near, far].  Depths are the parameter t of o + t d; d is not normalised.  float32, every operation rounded on its own:
+//   1. per axis with d_a != 0: t0 = (lo_a - o_a) / d_a, t1 = (hi_a - o_a) / d_a, axis interval [min, max]
+//   2. per axis with d_a == 0 (either zero): no constraint if lo_a <= o_a <= hi_a, otherwise the ray misses -- a branch,
+//      not the NaN of 0 / 0, which would turn "on the face" into a miss
+//   3. tn = largest lower end, tf = smallest upper end; a = max(tn, near), b = min(tf, far)
+//   4. hit: no axis missed and b > a.  NARROWED: hit and (a > near or b < far)
+// min / max are written as comparisons: nothing hangs on how fminf / fmaxf treat NaN or the sign of zero (non-finite rays
+// are not guarded, as in rays_to_ndc).  -> narrowed; a, b are meant to be used only then.
+// A narrowed ray draws its depths on [a, b] with constants of its own; any other ray -- a miss, or a box that contains
+// its whole [near, far] -- keeps the host's constants and so the depths of a context without a box, bit for bit.
+// This one function decides for the depth kernels and for nerf_ray_box_bounds.
+// ------------------------------------------------------------------------------------------------
+struct BoxArgs {
+    float lo[3], hi[3];
+    float near_b, far_b;
+};
+
+__device__ __forceinline__ bool ray_box_interval(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
+    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+    float tn = -__builtin_huge_valf(), tf = __builtin_huge_valf();
+    bool miss = false;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        if (dd[ax] == 0.0f) {
+            if (!(bx.lo[ax] <= oo[ax] && oo[ax] <= bx.hi[ax])) miss = true;
+            continue;
+        }
+        const float t0 = __fdiv_rn(__fsub_rn(bx.lo[ax], oo[ax]), dd[ax]);
+        const float t1 = __fdiv_rn(__fsub_rn(bx.hi[ax], oo[ax]), dd[ax]);
+        const bool first = t0 < t1;
+        const float low = first ? t0 : t1, high = first ? t1 : t0;
+        if (low > tn) tn = low;
+        if (high < tf) tf = high;
+    }
+    *a = tn > bx.near_b ? tn : bx.near_b;
+    *b = tf < bx.far_b ? tf : bx.far_b;
+    const bool hit = !miss && *b > *a;
+    return hit && (*a > bx.near_b || *b < bx.far_b);
+}
+
+// nerf_ray_box_bounds: one thread per ray.  bounds (N,2) = (a, b) of a narrowed ray, (near, far) of any other.
+__global__ void ray_box_bounds_kernel(const BoxArgs bx, const float* __restrict__ orig, const float* __restrict__ dirs,
+                                      long long N, float* __restrict__ bounds, int* __restrict__ narrowed) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    float a, b;
+    const bool nar = ray_box_interval(bx, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b);
+    reinterpret_cast<float2*>(bounds)[r] = nar ? make_float2(a, b) : make_float2(bx.near_b, bx.far_b);
+    if (narrowed) narrowed[r] = nar ? 1 : 0;
+}
+
+// The depth kernels with a box: one thread per sample, like the two above, whose formulas these repeat.  c0..c3 are the
+// constants launch_z_values gives the kernel without a box -- linear: start, stop, delta, span; lindisp: near, far_below,
+// inv_near, dinv -- and a narrowed ray replaces them with its own, computed in float32 from (a, b):
+//   linear:  start = a, stop = b, span = b - a, delta = span / (S - 1) (0 for S == 1); the last stratum may pass b by span / S
+//   lindisp: near = a, far_below = the float below b, inv_near = 1 / a, dinv = 1 / b - inv_near   (a >= near > 0)
+// Every thread of a ray reads the ray's 32 bytes and takes the decision again: S threads, one cache line, no bounds buffer
+// and no launch in front of this one.
+template <bool LINDISP>
+__global__ void z_values_box_kernel(const BoxArgs bx, float c0, float c1, float c2, float c3,
+                                    const float* __restrict__ orig, const float* __restrict__ dirs, long long N, int S,
+                                    const float* __restrict__ u, uint64_t seed, long long ray_base,
+                                    float* __restrict__ z) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= N * S) return;
+    const long long r = m / S;
+    const int s = (int)(m - r * S);
+    float a, b;
+    if (ray_box_interval(bx, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b)) {
+        c0 = a;
+        if constexpr (LINDISP) {
+            c1 = __int_as_float(__float_as_int(b) - 1);           // b > a > 0
+            c2 = __fdiv_rn(1.0f, a);
+            c3 = __fsub_rn(__fdiv_rn(1.0f, b), c2);
+        } else {
+            c1 = b;
+            c3 = __fsub_rn(b, a);
+            c2 = S > 1 ? __fdiv_rn(c3, (float)(S - 1)) : 0.f;
+        }
+    }
+    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
+    if constexpr (LINDISP) {
+        const float top = (float)(s + 1);
+        float v = __fadd_rn((float)s, uu);
+        if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
+        const float t = __fdiv_rn(v, (float)S);
+        const float zz = __fdiv_rn(1.0f, __fadd_rn(c2, __fmul_rn(c3, t)));
+        z[m] = fminf(fmaxf(zz, c0), c1);
+    } else {
+        float lin = __fadd_rn(c0, __fmul_rn(c2, (float)s));
+        if (s == 0) lin = c0;
+        if (s == S - 1 && S > 1) lin = c1;
+        z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, c3), (float)S));
+    }
+}
+
+static BoxArgs box_args(const SceneBox& box, float near_b, float far_b) {
+    BoxArgs bx;
+    for (int i = 0; i < 3; ++i) { bx.lo[i] = box.lo[i]; bx.hi[i] = box.hi[i]; }
+    bx.near_b = near_b; bx.far_b = far_b;
+    return bx;
+}
+
+void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,
+                           float* bounds, int* narrowed, hipStream_t stream) {
+    if (N <= 0) return;
+    const int bs = 256;
+    hipLaunchKernelGGL(ray_box_bounds_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream,
+                       box_args(box, near_b, far_b), orig, dirs, N, bounds, narrowed);
+}
+
 void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
-                     long long ray_base, float* z, hipStream_t stream) {
+                     long long ray_base, float* z, hipStream_t stream, const float* orig, const float* dirs,
+                     const SceneBox* box) {
     if (N <= 0) return;
     const long long total = N * S;
     const int bs = 256;
+    if (box && orig && dirs) {   // the same host constants as below, for the rays the box does not narrow
+        const BoxArgs bx = box_args(*box, near_b, far_b);
+        const dim3 grid((unsigned)((total + bs - 1) / bs));
+        if (lindisp) {
+            const float inv_near = (float)(1.0 / (double)near_b);
+            const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
+            hipLaunchKernelGGL(z_values_box_kernel<true>, grid, dim3(bs), 0, stream, bx, near_b, nextafterf(far_b, near_b),
+                               inv_near, dinv, orig, dirs, N, S, u, seed, ray_base, z);
+            return;
+        }
+        const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
+        const float span = (float)((double)far_b - (double)near_b);
+        hipLaunchKernelGGL(z_values_box_kernel<false>, grid, dim3(bs), 0, stream, bx, near_b, far_b, delta, span, orig, dirs,
+                           N, S, u, seed, ray_base, z);
+        return;
+    }
     if (lindisp) {   // near_b > 0: the callers refuse anything else
         const float inv_near = (float)(1.0 / (double)near_b);
         const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);

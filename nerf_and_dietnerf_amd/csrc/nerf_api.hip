@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -61,6 +62,12 @@ int sampling_ok(const nerf_ctx* c) {
     // 1/near: checked where depths are drawn as well as in the setter, since nerf_ctx_set_bounds may come after it
     if (c->sampling == NERF_SAMPLING_LINDISP && !(c->cfg.near_boundary > 0.f)) return fail("lindisp needs near_boundary > 0");
     return 0;
+}
+
+void draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
+                   long long ray_base, float* z) {
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, S, u, seed, ray_base, z,
+                    c->stream, o, d, c->box_on ? &c->box : nullptr);
 }
 
 // The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
@@ -360,8 +367,7 @@ int dev_render(nerf_ctx* c, const float* o, const float* d, long long N, int Sc,
     if (int r = sampling_ok(c)) return r;
     if (int r = ensure(c, c->b_zc, (size_t)N * Sc * sizeof(float))) return r;
     float* zc = (float*)c->b_zc.p;
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, Sc, u_c, seed, ray_base,
-                    zc, c->stream);
+    draw_z_values(c, o, d, N, Sc, u_c, seed, ray_base, zc);
     if (!fine) return dev_render_rays(c, NERF_NET_COARSE, o, d, zc, N, Sc, outs);
     if (Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
     if (int r = ensure(c, c->b_wc, (size_t)N * Sc * sizeof(float))) return r;
@@ -487,6 +493,18 @@ int nerf_ctx_set_ray_space(nerf_ctx* c, int space, float ndc_near_plane) {
     return 0;
 }
 
+int nerf_ctx_set_scene_box(nerf_ctx* c, const float* lo3, const float* hi3) {
+    if (!c) return fail("ctx is NULL");
+    if (!lo3 && !hi3) { c->box_on = false; return 0; }
+    if (!lo3 || !hi3) return fail("scene box: lo and hi are both given, or both NULL (box off)");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
+            return fail("scene box needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", a, lo3[a], hi3[a]);
+    for (int a = 0; a < 3; ++a) { c->box.lo[a] = lo3[a]; c->box.hi[a] = hi3[a]; }
+    c->box_on = true;
+    return 0;
+}
+
 int nerf_ctx_set_precision(nerf_ctx* c, int precision) {
     if (!c) return fail("ctx is NULL");
     RenderKernel k;
@@ -568,6 +586,57 @@ int nerf_get_z_values(nerf_ctx* c, int64_t N, int32_t S, const float* u, uint64_
     HIP_OK(hipGetLastError());
     if (mem == NERF_MEM_HOST) {
         HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int nerf_get_z_values_rays(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, int32_t S, const float* u,
+                           uint64_t seed, int64_t ray_base, float* z, int mem) {
+    ENTER(c);
+    if (!rays_orig || !rays_dirs || !z) return fail("NULL argument");
+    if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
+    if (int r = sampling_ok(c)) return r;
+    const float *o = rays_orig, *d = rays_dirs, *du = u;
+    float* dz = z;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
+        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p;
+        if (u) { if (int r = h2d(c, c->b_u0, u, (size_t)N * S * 4)) return r; du = (const float*)c->b_u0.p; }
+        if (int r = ensure(c, c->b_zc, (size_t)N * S * 4)) return r;
+        dz = (float*)c->b_zc.p;
+    }
+    draw_z_values(c, o, d, N, S, du, seed, ray_base, dz);
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int nerf_ray_box_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds, int32_t* narrowed,
+                        int mem) {
+    ENTER(c);
+    if (!rays_orig || !rays_dirs || !bounds) return fail("NULL argument");
+    if (N < 0) return fail("bad shape N=%lld", (long long)N);
+    if (!c->box_on) return fail("no scene box is set (nerf_ctx_set_scene_box)");
+    const float *o = rays_orig, *d = rays_dirs;
+    float* db = bounds;
+    int32_t* dn = narrowed;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
+        if (int r = ensure(c, c->b_in0, (size_t)N * 8)) return r;
+        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; db = (float*)c->b_in0.p;
+        if (narrowed) { if (int r = ensure(c, c->b_in1, (size_t)N * 4)) return r; dn = (int32_t*)c->b_in1.p; }
+    }
+    launch_ray_box_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, db, dn, c->stream);
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(bounds, db, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (narrowed) HIP_OK(hipMemcpyAsync(narrowed, dn, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
     return 0;

@@ -42,6 +42,8 @@ struct nerf_ctx {
     int sampling = NERF_SAMPLING_LINEAR;       // coarse depths: nerf_ctx_set_sampling
     int ray_space = NERF_RAYS_WORLD;           // rays nerf_render_image generates: nerf_ctx_set_ray_space
     float ndc_near_plane = 1.0f;
+    bool box_on = false;                       // scene box, in the space of the rays the depth kernel sees: nerf_ctx_set_scene_box
+    nerf::SceneBox box = {};
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -68,6 +70,9 @@ int h2d(nerf_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int enter(nerf_ctx* c);                             // NULL check + hipSetDevice
 #define ENTER(c) do { if (int r__ = nerf::enter(c)) return r__; } while (0)
 int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's bounds suit its sampling mode (lindisp: near > 0)
+// The coarse depths of N rays as this ctx draws them (bounds, sampling mode, scene box): every call site that has rays
+void draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
+                   long long ray_base, float* z);   // nerf_api.hip; device pointers, enqueued on the ctx stream
 
 void train_free(nerf_ctx* c);                       // train_api.hip: releases c->train (called by nerf_ctx_destroy)
 void comm_free(nerf_ctx* c);                        // comm_api.hip: releases c->comm (called by nerf_ctx_destroy)

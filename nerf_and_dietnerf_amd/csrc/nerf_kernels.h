@@ -227,9 +227,16 @@ void launch_raygen(const float c2w_host[16], float fov, int H, int W,
 // world rays -> NDC rays (near plane z = -near_plane, both scale factors 1 / tan(fov / 2) as the raygen's); out may be in
 void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float fov, float near_plane, float* out_orig,
                         float* out_dirs, hipStream_t stream);
-// lindisp: strata uniform in 1/z (needs near_b > 0) instead of in z
+// lindisp: strata uniform in 1/z (needs near_b > 0) instead of in z.  With rays (N,4) AND a box, every ray the box narrows
+// draws on its own interval (aux_kernels.hip: ray_box_interval); without either, the kernels and arguments of a context
+// that has no box.
+struct SceneBox { float lo[3], hi[3]; };
 void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
-                     long long ray_base, float* z, hipStream_t stream);
+                     long long ray_base, float* z, hipStream_t stream, const float* orig = nullptr,
+                     const float* dirs = nullptr, const SceneBox* box = nullptr);
+// bounds (N,2): (a, b) of a narrowed ray, (near_b, far_b) of any other; narrowed (N) 0 / 1, nullable
+void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,
+                           float* bounds, int* narrowed, hipStream_t stream);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                        uint64_t seed, long long ray_base, float* z_new, float* z_merged,

@@ -20,7 +20,9 @@ import numpy as np
 def c2w_to_rays_prepare_ds(c2w, field_of_view: float, img, ctx):
     """One image -> (rays_orig (h*w,4), rays_dirs (h*w,4), real_rgb_pixels (h*w,3)) as CUDA tensors.  On a context in NDC
     ray space (render_config ``use_ndc``; Context.set_ray_space) the rays are transformed on the device, with the
-    context's near plane, before they are returned: the trainer then sees what render_image renders."""
+    context's near plane, before they are returned: the trainer then sees what render_image renders.  These are the rays
+    a scene box (render_config ``scene_box``; Context.set_scene_box) is defined on: the trainer clips each to the box when it
+    draws depths, nothing is stored here."""
     import torch
     dev = torch.device("cuda", ctx.cfg.device)
     img_t = torch.as_tensor(np.asarray(img, np.float32) if not hasattr(img, "is_cuda") else img,

@@ -188,6 +188,7 @@ class DietNeRF(NeRF):
         orig = pose_t[:, 3].expand(count, 4).contiguous()
         if getattr(ctx, "ray_space", "world") == "ndc":   # the tape renders the rays render_image renders (render_config use_ndc)
             orig, dirs = ctx.rays_to_ndc(orig, dirs, self.fov, ctx.ndc_near_plane)
+        # (render_config scene_box: the context holds the box, so the tape's forward draws the depths render_image draws)
         batch = int(self.batch_size_train)
         slab = None
         if self.keep_activations:

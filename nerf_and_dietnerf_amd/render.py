@@ -39,6 +39,7 @@ N_RAYS_IN_BATCH_TRAIN = "n_rays_in_batch_train"
 LINDISP = "lindisp"                  # bool, default False: coarse depths uniform in disparity
 USE_NDC = "use_ndc"                  # bool, default False: rays in normalised device coordinates
 NDC_NEAR_PLANE = "ndc_near_plane"    # float, default 1.0: distance of the NDC near plane (with use_ndc)
+SCENE_BOX = "scene_box"              # [[x, y, z], [x, y, z]] (lo, hi), default absent: per-ray depth range from a scene box
 
 N_COORDINATES = 3
 N_COLOR_CHANNELS = 3
@@ -231,6 +232,7 @@ class Context:
         self.auto_fallbacks = 0      # "auto": calls that were re-rendered in exact fp32
         self._slot_fine = {}         # train_render_forward slots that ran a fine pass
         self.sampling, self.ray_space, self.ndc_near_plane = "linear", "world", 1.0   # what nerf_ctx_create leaves
+        self.scene_box = None        # ((lo), (hi)) of set_scene_box
 
     def close(self):
         if getattr(self, "h", None):
@@ -300,6 +302,54 @@ class Context:
         od, pod = arr.out(shape)
         _lib.check(self.lib.nerf_rays_to_ndc(self.h, po, pd, n, float(fov), float(ndc_near_plane), poo, pod, arr.mem))
         return oo, od
+
+    def set_scene_box(self, lo, hi=None) -> None:
+        """An axis-aligned box ``lo[3] < hi[3]`` in the space of the rays the depth kernel sees (world rays, or NDC rays on an
+        "ndc" context): every call that draws coarse depths AND has rays -- get_z_values_for_rays, render, render_image and
+        its sharded form, the trainer -- then samples a ray on the part of [near, far] that lies inside the box; a ray that
+        misses the box, or whose whole [near, far] lies inside, keeps the depths of a context without a box (include/nerf_mi355.h:
+        nerf_ctx_set_scene_box has the rule).  ``set_scene_box(None)`` turns it off.  get_z_values has no rays and ignores it."""
+        if lo is None and hi is None:
+            _lib.check(self.lib.nerf_ctx_set_scene_box(self.h, None, None))
+            self.scene_box = None
+            return
+        if lo is None or hi is None:
+            raise ValueError("scene box: give both corners, or None to turn it off")
+        lo_a, hi_a = np.asarray(lo, np.float32).ravel(), np.asarray(hi, np.float32).ravel()
+        if lo_a.shape != (3,) or hi_a.shape != (3,):
+            raise ValueError(f"scene box corners must have 3 components each, got {lo_a.shape[0]} and {hi_a.shape[0]}")
+        # the library's own rule, checked here first so that a configuration error does not need a device call to show
+        if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
+            raise RuntimeError(f"scene box needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
+        _lib.check(self.lib.nerf_ctx_set_scene_box(self.h, lo_a.ctypes.data, hi_a.ctypes.data))
+        self.scene_box = (tuple(float(v) for v in lo_a), tuple(float(v) for v in hi_a))
+
+    def ray_box_bounds(self, rays_orig, rays_dirs):
+        """Rays (N,4) -> (bounds (N,2) float32, narrowed (N,) int32) under the context's box and bounds: (a, b) of a ray the
+        box narrows, (near, far) of any other (nerf_ray_box_bounds: the device function the depth kernels call)."""
+        arr = self._arrays(rays_orig, rays_dirs)
+        n = int(rays_orig.shape[0])
+        po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
+        bounds, pb = arr.out((n, 2))
+        if arr.torch is not None:
+            narrowed = arr.torch.empty((n,), dtype=arr.torch.int32, device=arr.device)
+            pn = narrowed.data_ptr()
+        else:
+            narrowed = np.empty((n,), np.int32)
+            pn = narrowed.ctypes.data
+        _lib.check(self.lib.nerf_ray_box_bounds(self.h, po, pd, n, pb, pn, arr.mem))
+        return bounds, narrowed
+
+    def get_z_values_for_rays(self, rays_orig, rays_dirs, n_samples, uniform_values=None, seed=0, ray_base=0):
+        """The coarse depths (N, n_samples) render and the trainer draw for these rays (N,4) at the context's bounds: get_z_values
+        for callers that have rays -- it follows the sampling mode and the scene box."""
+        arr = self._arrays(rays_orig, rays_dirs, uniform_values)
+        n = int(rays_orig.shape[0])
+        po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
+        pu = arr.inp(uniform_values, (n, n_samples))
+        out, p = arr.out((n, n_samples))
+        _lib.check(self.lib.nerf_get_z_values_rays(self.h, po, pd, n, n_samples, pu, seed, ray_base, p, arr.mem))
+        return out
 
     def set_precision(self, precision: str) -> None:
         """"auto", "fp32" (exact fp32 MFMA), "f16x3" (3-pass split-fp16 MFMA, fp32 accumulate), "bf16x3" (3-pass split-bf16
@@ -786,6 +836,12 @@ class NeRF:
             self.ctx.set_sampling("lindisp")
         if self.use_ndc:
             self.ctx.set_ray_space("ndc", self.ndc_near_plane)
+        # scene box: an absent key (or None) leaves the context without one
+        self.scene_box = render_config.get(SCENE_BOX)
+        if self.scene_box is not None:
+            if len(self.scene_box) != 2:
+                raise ValueError(f"{SCENE_BOX} must be [[x, y, z], [x, y, z]] (lo, hi), got {self.scene_box!r}")
+            self.ctx.set_scene_box(self.scene_box[0], self.scene_box[1])
 
     def set_weights(self, coarse, fine=None) -> None:
         self._blobs = [coarse, fine]
