@@ -93,11 +93,15 @@ __device__ unsigned long long g_stamps_h[16];
 // for its signs).
 // ROT rotates the four accumulators: tile u works in accs[(u + ROT) & 3] and a PENDING tile is looked for in
 // accs[(ROT + 3) & 3]; every body but BODY_LAST0 (which follows the 9-tile BODY_HIDSIG) uses ROT = 0.
-template <int BODY, bool PENDING, bool FAST, bool STASH = false, int ROT = 0>
+// PP (ping-pong, the 3-pass render kernels): consecutive layers swap the two fragment sets instead of copying the new
+// activations back -- the caller passes (x, n) to one layer and (n, x) to the next, tiles 0..6 land in the other set's
+// fragments 0..13 and the PENDING tile 7 in its fragments 14..15, which the following layer reads as its own xh/xl[14..15].
+// No fragment is ever copied; every value is computed by the same instructions in the same order.
+template <int BODY, bool PENDING, bool FAST, bool STASH = false, int ROT = 0, bool PP = false>
 __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t cb_h, int bias_off_bytes,
                                              float alpha, float* st_prev, float* st_cur, frag4* mk_prev_ptr,
                                              frag4* mk_cur_ptr, frag4& mk_prev, frag4& mk_cur, f32x16 (&accs)[4],
-                                             frag4 (&xh)[16], frag4 (&xl)[16], frag4 (&nh)[14], frag4 (&nl)[14],
+                                             frag4 (&xh)[16], frag4 (&xl)[16], frag4 (&nh)[PP ? 16 : 14], frag4 (&nl)[PP ? 16 : 14],
                                              const frag4 (&peh)[kHStepsPE], const frag4 (&pel)[kHStepsPE], const frag4 (&dh)[2],
                                              const frag4 (&dl)[2], float (&xc)[64], float& sigma_raw) {
     constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_SIG ? 1 : BODY == BODY_HIDSIG ? 9 : BODY == BODY_LAST0 ? 4 : 8;
@@ -199,6 +203,9 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             split_e(y0, h0, l0);
             split_e(y1, h1, l1);
             ph = pack_hi(h0, h1); pl = pack_lo(l0, l1);                   // whole-register writes
+            // PP: nothing in this body reads the new fragments, and left to itself hipcc keeps the fp32 values and sinks
+            // every split and pack to the end of the layer; pinned here they stay under the k-step they were dealt to
+            if constexpr (PP && BODY != BODY_PE) asm volatile("" : "+v"(ph), "+v"(pl));
         }
         if constexpr (STASH) {
             if constexpr (FAST) stash4h(utc, rc, ph, decltype(pend_sel)::value ? st_prev : st_cur);
@@ -319,7 +326,16 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                     store_pair_p(std::integral_constant<int, et>{}, std::integral_constant<int, n - 1>{}, act_pair(prv[n - 1], prv[n]), std::false_type{}, std::false_type{});
             } else if constexpr (kPend) {
                 constexpr int er = 2 * n;
-                const float y0 = act(prv[er]), y1 = act(prv[er + 1]);
+                float y0, y1;
+                if constexpr (PP) {
+                    // the PENDING tile is complete before the body starts and hipcc hoists its alpha * acc in front of the
+                    // first MFMA; read the pair here, in the k-step that packs it
+                    float v0 = prv[er], v1 = prv[er + 1];
+                    asm volatile("" : "+v"(v0), "+v"(v1));
+                    y0 = act(v0); y1 = act(v1);
+                } else {
+                    y0 = act(prv[er]); y1 = act(prv[er + 1]);
+                }
                 store_pair(std::integral_constant<int, 7>{}, std::integral_constant<int, er>{}, y0, y1, std::true_type{}, std::true_type{});
             } else if constexpr (kPrevS) {
                 const float y = act(prv[n]);
@@ -341,8 +357,8 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             if constexpr (u == 0 && PENDING) {
                 if constexpr (STASH && n == 8) { if (mk_prev_ptr) stream_store(mk_prev_ptr, mk_prev); }   // that layer's mask word is complete
                 // previous layer's tile 6 sits complete in nh/nl[12..13]; its k-steps are long retired
-                if constexpr (n == 8) { xh[12] = nh[12]; xl[12] = nl[12]; }
-                if constexpr (n == 9) { xh[13] = nh[13]; xl[13] = nl[13]; }
+                if constexpr (!PP && n == 8) { xh[12] = nh[12]; xl[12] = nl[12]; }
+                if constexpr (!PP && n == 9) { xh[13] = nh[13]; xl[13] = nl[13]; }
             }
             // preload the bias of the NEXT tile (or of the next layer's tile 0: the layers' biases are
             // contiguous in the constant region) into the accumulator it will use -- free since 2 tiles
@@ -361,13 +377,13 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                         return;
                     }
                     const float z0 = act(prv[r]), z1 = act(prv[r + 1]);
-                    if constexpr (u - 1 <= 5) store_pair(std::integral_constant<int, u - 1>{}, std::integral_constant<int, r>{}, z0, z1, std::true_type{}, std::false_type{});
+                    if constexpr (u - 1 <= 5 || PP) store_pair(std::integral_constant<int, u - 1>{}, std::integral_constant<int, r>{}, z0, z1, std::true_type{}, std::false_type{});
                     else store_pair(std::integral_constant<int, u - 1>{}, std::integral_constant<int, r>{}, z0, z1, std::false_type{}, std::false_type{});
                 });
             }
             // last tile of an in-place layer: fragment m-1 of x-in died with k-step m-1; tiles 0..5 of
             // the new activations (fragments 0..11) are complete by now
-            if constexpr ((BODY == BODY_HID || BODY == BODY_SKIP || BODY == BODY_HIDSIG) && u == NU - 1) {
+            if constexpr (!PP && (BODY == BODY_HID || BODY == BODY_SKIP || BODY == BODY_HIDSIG) && u == NU - 1) {
                 constexpr int m = BODY == BODY_SKIP ? n - kHStepsPE : n;
                 if constexpr (m >= 1 && m - 1 < 12) { xh[m - 1] = nh[m - 1]; xl[m - 1] = nl[m - 1]; }
             }
@@ -422,6 +438,14 @@ __device__ __forceinline__ void split8(const float (&v)[8], frag4& hi, frag4& lo
 template <bool FAST, bool STASH = false, bool XYZ = false, bool SIGONLY = false>
 __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     static_assert(!SIGONLY || (!FAST && !STASH && !XYZ), "the sigma-only variant is a render kernel of the 3-pass network");
+    // the fp16 3-pass render kernels with view directions (mlp_f16x3_kernel, mlp_f16x3_sig_kernel) ping-pong their fragment
+    // sets across layers (layer_body_h's PP); every other instantiation and build keeps the copy-back schedule
+#if defined(NERF_BF16) || NERF_PE_LX != 5
+    constexpr bool kPPBuild = false;
+#else
+    constexpr bool kPPBuild = true;
+#endif
+    constexpr bool kPP = kPPBuild && !FAST && !STASH && !XYZ;     // (dependent in every build: the untaken calls are discarded)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -466,7 +490,7 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    frag4 xh[16], xl[16], nh[14], nl[14], peh[kHStepsPE], pel[kHStepsPE], dh[2], dl[2];
+    frag4 xh[16], xl[16], nh[kPP ? 16 : 14], nl[kPP ? 16 : 14], peh[kHStepsPE], pel[kHStepsPE], dh[2], dl[2];
     f32x16 accs[4];
     float xc[64];
     float sigma_raw = 0.f;
@@ -567,20 +591,38 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
         float* st_prev = nullptr;
         float* st_cur = st_of(0);
         STAMP(t1); acc_t[0] += t1 - t0;
-        layer_body_h<BODY_PE, false, FAST, STASH>(p, lane16, cb_h, (kHConstBias + 0 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+        layer_body_h<BODY_PE, false, FAST, STASH, 0, kPP>(p, lane16, cb_h, (kHConstBias + 0 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
         STAMP(t0); acc_t[1] += t0 - t1;
+        if constexpr (kPP) {
+            // layers 1..7 in pairs: an odd layer reads x and writes n, the even one after it (the skip layer among them)
+            // reads n and writes x; layer 7 leaves its output in n, where layer 8 reads it
 #pragma unroll 1
-        for (int l = 1; l <= 7; ++l) {
-            st_prev = st_cur;
-            st_cur = st_of(l);
-            mk_prev_ptr = mk_cur_ptr; mk_cur_ptr = mk_of(l);
-            mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
-            if (l == 4) {
-                layer_body_h<BODY_SKIP, true, FAST, STASH>(p, lane16, cb_h, (kHConstBias + 4 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
-                STAMP(t1); acc_t[3] += t1 - t0; t0 = t1;
-            } else {
-                layer_body_h<BODY_HID, true, FAST, STASH>(p, lane16, cb_h, (kHConstBias + l * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+            for (int l = 1;; l += 2) {
+                layer_body_h<BODY_HID, true, FAST, STASH, 0, true>(p, lane16, cb_h, (kHConstBias + l * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
                 STAMP(t1); acc_t[2] += t1 - t0; t0 = t1;
+                if (l == 7) break;
+                if (l == 3) {
+                    layer_body_h<BODY_SKIP, true, FAST, STASH, 0, true>(p, lane16, cb_h, (kHConstBias + 4 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
+                    STAMP(t1); acc_t[3] += t1 - t0; t0 = t1;
+                } else {
+                    layer_body_h<BODY_HID, true, FAST, STASH, 0, true>(p, lane16, cb_h, (kHConstBias + (l + 1) * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
+                    STAMP(t1); acc_t[2] += t1 - t0; t0 = t1;
+                }
+            }
+        } else {
+#pragma unroll 1
+            for (int l = 1; l <= 7; ++l) {
+                st_prev = st_cur;
+                st_cur = st_of(l);
+                mk_prev_ptr = mk_cur_ptr; mk_cur_ptr = mk_of(l);
+                mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
+                if (l == 4) {
+                    layer_body_h<BODY_SKIP, true, FAST, STASH>(p, lane16, cb_h, (kHConstBias + 4 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+                    STAMP(t1); acc_t[3] += t1 - t0; t0 = t1;
+                } else {
+                    layer_body_h<BODY_HID, true, FAST, STASH>(p, lane16, cb_h, (kHConstBias + l * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+                    STAMP(t1); acc_t[2] += t1 - t0; t0 = t1;
+                }
             }
         }
         if constexpr (XYZ) {
@@ -595,14 +637,16 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
             mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
             layer_body_h<BODY_LAST0, true, FAST, STASH, 1>(p, lane16, cb_h, kXConstBias9 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
         } else if constexpr (SIGONLY) {
-            layer_body_h<BODY_SIG, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+            if constexpr (kPP) layer_body_h<BODY_SIG, true, FAST, STASH, 0, true>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
+            else layer_body_h<BODY_SIG, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
             STAMP(t1); acc_t[4] += t1 - t0;
         } else {
             st_prev = st_cur;
             st_cur = st_of(8);
             mk_prev_ptr = mk_cur_ptr; mk_cur_ptr = mk_of(8);
             mk_prev = mk_cur; mk_cur = frag4{0u, 0u, 0u, 0u};
-            layer_body_h<BODY_LAST, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+            if constexpr (kPP) layer_body_h<BODY_LAST, true, FAST, STASH, 0, true>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
+            else layer_body_h<BODY_LAST, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
             STAMP(t1); acc_t[4] += t1 - t0;
         }
         if constexpr (SIGONLY) {
