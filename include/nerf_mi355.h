@@ -40,7 +40,15 @@ enum { NERF_MEM_HOST = 0, NERF_MEM_DEVICE = 1 };
 /* arithmetic of the 256-wide contractions; everything else is always fp32 */
 enum {
     NERF_PRECISION_FP32 = 0,   /* v_mfma_f32_32x32x2_f32: exact fp32 fma chains (parity mode)      */
-    NERF_PRECISION_F16X3 = 1,  /* 3-pass split-fp16 MFMA (hi*hi + hi*lo + lo*hi), fp32 accumulate */
+    NERF_PRECISION_F16X3 = 1,  /* 3-pass split-fp16 MFMA (hi*hi + hi*lo + lo*hi), fp32 accumulate.  fp32-class between two
+                                  limits: |activations| < 65504 (beyond: non-finite rows, counted by nerf_ctx_read_nonfinite),
+                                  and NOT TOO SMALL -- the lo half of an activation is an fp16 subnormal (absolute step
+                                  2^-24) below |y| = 2^-4 and hi itself below 2^-14, so the mode loses bits as a layer's
+                                  activations shrink, with every value finite and NOTHING COUNTED.  Measured on the shipped
+                                  checkpoint (layer-1 activations: mean 0.14, max 1.8) with that layer scaled by 2^k: raw
+                                  outputs 1.7e-6 of the fp32 network at k = 0, 1.1e-5 at -4, 2.3e-4 at -8, 2.5e-3 at -12;
+                                  final RGB leaves 1e-4 at k = -9 (mean |y| 2.7e-4, max 3.5e-3).  NERF_PRECISION_BF16X3 is
+                                  the mode for such weights (8.9e-6 / 1.3e-5 at every k).  DESIGN.md section 4.1b */
     NERF_PRECISION_F16 = 2,    /* 1-pass fp16 MFMA, fp32 accumulate, activations rounded to fp16 between layers: the
                                   numerics class of the reference's production policy (mixed_float16,
                                   src/ExecutionRun.py:220-221); NOT the fp32 parity mode */
@@ -254,7 +262,12 @@ int nerf_render_image_sharded_outputs(nerf_ctx* ctx, const float* c2w, float fie
  * there means: switch this model to NERF_PRECISION_BF16X3 (fp32's range: about 3.4e38; the only fp32-class mode of
  * a network with n_pos_enc_dim_xyz 6..10) or to NERF_PRECISION_FP32.  NERF_PRECISION_BF16X3 counts as well: there a
  * non-zero count means the fp32 network itself overflows or holds NaN weights.  The reference has no such check (TF
- * propagates NaN silently). */
+ * propagates NaN silently).
+ * There is NO watch for the opposite limit of NERF_PRECISION_F16X3: activations far below 2^-4 lose their lo half to
+ * fp16 subnormals and the result degrades with every value finite (figures at the enum above; final RGB of the shipped
+ * checkpoint leaves 1e-4 once a layer's activations are 2^-9 of their trained size).  A zero count therefore says "no
+ * overflow", not "fp32-class"; weights with very small hidden activations belong in NERF_PRECISION_BF16X3, whose error does
+ * not depend on the scale. */
 int nerf_ctx_read_nonfinite(nerf_ctx* ctx, int64_t* rows);
 
 /* ---- training ---------------------------------------------------
