@@ -30,8 +30,9 @@ extern "C" {
 #endif
 
 /* 6 also covers the forward-facing-scene entries added after it (nerf_ctx_set_sampling, nerf_ctx_set_ray_space,
- * nerf_rays_to_ndc) and the scene-box entries (nerf_ctx_set_scene_box, nerf_ray_box_bounds, nerf_get_z_values_rays), all
- * marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_rays_to_ndc), the scene-box entries (nerf_ctx_set_scene_box, nerf_ray_box_bounds, nerf_get_z_values_rays) and the
+ * occupancy-grid entries (nerf_ctx_set_occupancy_grid, nerf_ctx_get_occupancy_grid, nerf_occupancy_bake,
+ * nerf_ray_occupancy_bounds), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -151,6 +152,41 @@ int nerf_ctx_set_ray_space(nerf_ctx* ctx, int space, float ndc_near_plane);
  * sampling, compositing, the networks and the backward pass consume the depths and are unchanged.
  * The setter refuses non-finite values and lo_a >= hi_a ("scene box needs finite lo < hi on every axis"). */
 int nerf_ctx_set_scene_box(nerf_ctx* ctx, const float* lo3, const float* hi3);
+/* ABI 6+, occupancy grid: R x R x R bits over the scene box say where the network has density; a ray is then sampled from
+ * the first occupied cell it enters to the last one it leaves, at the same sample count.  Off by default.  A grid needs a
+ * box ("an occupancy grid needs a scene box"), and setting, changing or clearing the box drops the grid.  R is a multiple
+ * of 4 in [4, 256]; cell (ix, iy, iz) is bit ix + R (iy + R iz) of a little-endian uint32 array of R^3 / 32 words.
+ * The ray rule, in float32, every operation rounded on its own (no FMA):
+ *   1. (a0, b0) = steps 1-3 of the box rule (the ray clipped to the box and to near / far).  No hit (an axis said
+ *      "misses", or not b0 > a0): the ray is untouched, state 0.
+ *   2. cell_a = (hi_a - lo_a) / R; the start cell per axis is clamp(floor(((o_a + a0 d_a) - lo_a) / cell_a), 0, R - 1).
+ *   3. plane k of an axis lies at t = ((lo_a + cell_a k) - o_a) / d_a, recomputed from k at every step, never accumulated;
+ *      the first plane of an axis is k = cell + 1 for d_a > 0, k = cell for d_a < 0; an axis with d_a == 0 never steps.
+ *   4. Amanatides-Woo walk from t = a0: the next axis is the one with the smallest plane parameter tm (ties: the lowest
+ *      axis index, strict <); the current cell's segment is [t, te], te = tm held in [t, b0]; an occupied cell sets a' = t
+ *      the first time and b' = te every time; the walk stops when tm reaches b0 (not tm < b0), when the stepped index
+ *      leaves the grid, or after 3R + 3 steps; otherwise t = te and the walk goes on in the next cell.
+ *   5. if an occupied cell was met, b' > a' (as the box rule asks b > a of a hit: cells touched in one point do not
+ *      count) and a' > a0 or b' < b0 (as the box rule asks a > near or b < far of "narrowed": a grid that is full along the
+ *      ray is the box alone), the ray is NARROWED BY THE GRID to [a', b'], state 2, and draws its depths by the box rule's
+ *      step 5 on that interval (linear and lindisp alike; a' >= near > 0 keeps lindisp legal).
+ *   6. otherwise the ray keeps exactly what a ctx with the box alone gives it, bit for bit: state 1 and (a0, b0) if the box
+ *      narrows it, state 0 and (near, far) if not.  Nothing is ever left unsampled.
+ * Every call listed under the scene box follows the grid; a training slot keeps the depths it drew.  nerf_ray_box_bounds
+ * and nerf_get_z_values keep their meaning.  The library never rebuilds a grid on its own: it is the caller's snapshot of
+ * the network, and training on with a stale grid is the caller's choice.
+ * set: `bits` is a HOST pointer to R^3 / 32 words (copied before the call returns); NULL, 0 clears the grid.
+ * get: writes *R = 0 when there is no grid; bits (HOST, R^3 / 32 words) may be NULL to ask for R only. */
+int nerf_ctx_set_occupancy_grid(nerf_ctx* ctx, const uint32_t* bits, int32_t R);
+int nerf_ctx_get_occupancy_grid(nerf_ctx* ctx, uint32_t* bits, int32_t* R);
+/* ABI 6+: bake the grid from network `which` (0 coarse / 1 fine) in the ctx's precision: a cell is occupied if sigma (raw
+ * column 3 of nerf_model_predict, the same kernels) exceeds sigma_threshold at any of its samples_per_cell points (1..8):
+ * point 0 is the float32 centre lo_a + cell_a (i_a + 0.5), further points are Philox-jittered inside the cell (seed).  The
+ * set is then grown by `dilate` cells (0..2, 26-neighbourhood).  *n_occupied (nullable) = the occupied cells afterwards.
+ * Fails without a box, if the network is not loaded, if sigma_threshold is not finite and > 0, if samples_per_cell is
+ * outside 1..8; a bake that fails leaves the ctx without a grid. */
+int nerf_occupancy_bake(nerf_ctx* ctx, int which, int32_t R, float sigma_threshold, int32_t samples_per_cell, int32_t dilate,
+                        uint64_t seed, int64_t* n_occupied);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of
@@ -188,6 +224,11 @@ int nerf_get_z_values_rays(nerf_ctx* ctx, const float* rays_orig, const float* r
  * bounds (N,2): (a, b) of a narrowed ray, (near, far) of any other; narrowed (N) int32 0 / 1, or NULL.  Fails without a box. */
 int nerf_ray_box_bounds(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
                         int32_t* narrowed, int mem);
+/* ABI 6+: the occupancy-grid rule for N rays, from the device function the depth kernels call.  bounds (N,2): (a', b') of
+ * a ray the grid narrows, (a0, b0) of one only the box narrows, (near, far) of any other; state (N) int32 2 / 1 / 0, or
+ * NULL.  Fails without a grid. */
+int nerf_ray_occupancy_bounds(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
+                              int32_t* state, int mem);
 /* get_z_vals_from_prob_dist_func, src/UtilsCV.py:502-539.  weights,z (N,S); u (N,Sf) or NULL;
  * z_new (N,Sf) sorted.  If z_merged != NULL also writes sort(concat(z_new,z)) (N,S+Sf)
  * (src/NeRF.py:132). */

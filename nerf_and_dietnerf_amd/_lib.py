@@ -54,6 +54,9 @@ SYMBOLS = [
     ("nerf_ctx_set_sampling", C.c_int, [_P, C.c_int]),
     ("nerf_ctx_set_ray_space", C.c_int, [_P, C.c_int, _F]),
     ("nerf_ctx_set_scene_box", C.c_int, [_P, _P, _P]),
+    ("nerf_ctx_set_occupancy_grid", C.c_int, [_P, _P, _I32]),
+    ("nerf_ctx_get_occupancy_grid", C.c_int, [_P, _P, _P]),
+    ("nerf_occupancy_bake", C.c_int, [_P, C.c_int, _I32, _F, _I32, _I32, _U64, _P]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     ("nerf_get_rays_directions", C.c_int, [_P, _P, _F, _I32, _I32, _P, C.c_int]),
@@ -61,6 +64,7 @@ SYMBOLS = [
     ("nerf_get_z_values", C.c_int, [_P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),
     ("nerf_get_z_values_rays", C.c_int, [_P, _P, _P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),
     ("nerf_ray_box_bounds", C.c_int, [_P, _P, _P, _I64, _P, _P, C.c_int]),
+    ("nerf_ray_occupancy_bounds", C.c_int, [_P, _P, _P, _I64, _P, _P, C.c_int]),
     ("nerf_sample_pdf", C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _U64, _I64, _P, _P, C.c_int]),
     ("nerf_positional_encoding", C.c_int, [_P, _P, _I64, _I32, _I32, _P, C.c_int]),
     ("nerf_model_predict", C.c_int, [_P, C.c_int, _P, _P, _I64, _P, C.c_int]),

@@ -39,6 +39,7 @@ MIXED_FLOAT16 = "mixed_float16"
 # optional keys of the ``render`` section the reference does not have (forward-facing scenes; render.py reads them)
 LINDISP, USE_NDC, NDC_NEAR_PLANE = "lindisp", "use_ndc", "ndc_near_plane"
 SCENE_BOX = "scene_box"            # [[x, y, z], [x, y, z]]: per-ray depth range from a scene bounding box
+OCCUPANCY_GRID = "occupancy_grid"  # {resolution, sigma_threshold, samples_per_cell, dilate, update_every, warmup_epochs}; needs scene_box
 ESTIMATE = "estimate"              # get_nerf(estimated_intersection=...): run the scene analysis, as the reference does
 
 
@@ -91,7 +92,8 @@ def get_nerf(config: Dict, near_boundary: float, far_boundary: float, *, images=
     for the non-spherical pose sampling (src/DietNeRF.py:254-260), overrides it.
     The whole ``render`` section goes to the model, so a YAML that carries ``lindisp`` / ``use_ndc`` / ``ndc_near_plane`` gets
     disparity sampling / NDC rays (with ``use_ndc`` the caller passes the NDC bounds 0 and 1 as near / far), and one that
-    carries ``scene_box: [[x, y, z], [x, y, z]]`` samples every ray inside that box (NeRF and DietNeRF alike)."""
+    carries ``scene_box: [[x, y, z], [x, y, z]]`` samples every ray inside that box (NeRF and DietNeRF alike); with
+    ``occupancy_grid: {resolution, sigma_threshold, ...}`` beside it, inside the occupied cells of a grid baked from the network."""
     from .dietnerf import DietNeRF
     from .render import NeRF
     net, render, training = config[NEURAL_NET], config[RENDER], config[TRAINING]

@@ -163,7 +163,8 @@ struct BoxArgs {
     float near_b, far_b;
 };
 
-__device__ __forceinline__ bool ray_box_interval(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
+// steps 1-3 and the first half of 4: -> hit; (a, b) = the ray clipped to the box and to near / far
+__device__ __forceinline__ bool ray_box_hit(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
     const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
     float tn = -__builtin_huge_valf(), tf = __builtin_huge_valf();
     bool miss = false;
@@ -182,7 +183,11 @@ __device__ __forceinline__ bool ray_box_interval(const BoxArgs& bx, const float4
     }
     *a = tn > bx.near_b ? tn : bx.near_b;
     *b = tf < bx.far_b ? tf : bx.far_b;
-    const bool hit = !miss && *b > *a;
+    return !miss && *b > *a;
+}
+
+__device__ __forceinline__ bool ray_box_interval(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
+    const bool hit = ray_box_hit(bx, o, d, a, b);
     return hit && (*a > bx.near_b || *b < bx.far_b);
 }
 
@@ -290,6 +295,250 @@ void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S
     const float span = (float)((double)far_b - (double)near_b);
     hipLaunchKernelGGL(z_values_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream, near_b,
                        far_b, delta, span, N, S, u, seed, ray_base, z);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Occupancy grid (include/nerf_mi355.h: nerf_ctx_set_occupancy_grid has the rule): R x R x R bits
+// over the scene box, cell (ix, iy, iz) = bit ix + R (iy + R iz) of a little-endian uint32 array.  ray_grid_interval walks a
+// ray through the cells of its box interval [a0, b0] (Amanatides-Woo) and returns the stretch from the first occupied cell
+// it enters to the last one it leaves.  float32, every operation rounded on its own; a plane's parameter is recomputed from
+// its index at every step, never accumulated.  -> 0: the ray keeps (near, far); 1: the box alone narrows it to (a0, b0);
+// 2: the grid narrows it to (a, b).  A ray that meets no occupied cell (or meets occupied cells only in a point: b > a is
+// asked for, as the box rule asks it of a hit), or whose occupied stretch is all of [a0, b0], is left to the box rule: nothing
+// is ever left unsampled, and a full grid is the box alone, bit for bit.
+// The cell index is held in [0, R) wherever the bits are read.
+// ------------------------------------------------------------------------------------------------
+struct GridArgs {
+    BoxArgs bx;
+    const uint32_t* bits;
+    int R;
+};
+
+__device__ __forceinline__ float grid_plane(float lo, float cell, int k, float o, float d) {
+    return __fdiv_rn(__fsub_rn(__fadd_rn(lo, __fmul_rn(cell, (float)k)), o), d);
+}
+
+__device__ __forceinline__ int ray_grid_interval(const GridArgs& g, const float4 o, const float4 d, float* a, float* b) {
+    const BoxArgs& bx = g.bx;
+    const int R = g.R;
+    // steps 1-3 of the box rule, from the function the box kernels decide with: a hit that the box does not narrow still
+    // walks the grid
+    float a0, b0;
+    const bool hit = ray_box_hit(bx, o, d, &a0, &b0);
+    const bool box_narrowed = hit && (a0 > bx.near_b || b0 < bx.far_b);
+    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+    *a = bx.near_b; *b = bx.far_b;
+    if (!hit) return 0;
+    float cell[3], tp[3];
+    int idx[3], step[3], plane[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        cell[ax] = __fdiv_rn(__fsub_rn(bx.hi[ax], bx.lo[ax]), (float)R);
+        const float p = __fadd_rn(oo[ax], __fmul_rn(a0, dd[ax]));
+        const float f = floorf(__fdiv_rn(__fsub_rn(p, bx.lo[ax]), cell[ax]));
+        idx[ax] = f >= 0.0f ? (f <= (float)(R - 1) ? (int)f : R - 1) : 0;      // NaN -> 0
+        step[ax] = dd[ax] > 0.0f ? 1 : -1;
+        plane[ax] = idx[ax] + (dd[ax] > 0.0f ? 1 : 0);
+        tp[ax] = dd[ax] == 0.0f ? __builtin_huge_valf() : grid_plane(bx.lo[ax], cell[ax], plane[ax], oo[ax], dd[ax]);
+    }
+    float t = a0, ga = 0.f, gb = 0.f;
+    bool found = false;
+    const int max_steps = 3 * R + 3;
+    for (int it = 0; it < max_steps; ++it) {
+        int ax = 0;
+        float tm = tp[0];
+        if (tp[1] < tm) { ax = 1; tm = tp[1]; }
+        if (tp[2] < tm) { ax = 2; tm = tp[2]; }
+        float te = tm;
+        if (te > b0) te = b0;
+        if (te < t) te = t;
+        const int bit = idx[0] + R * (idx[1] + R * idx[2]);       // < R^3 <= 2^24
+        if ((g.bits[bit >> 5] >> (bit & 31)) & 1u) {
+            if (!found) { ga = t; found = true; }
+            gb = te;
+        }
+        if (!(tm < b0)) break;
+        // the stepped axis, written without a dynamic index into the per-axis arrays (they stay in registers)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k == ax) {
+                idx[k] += step[k];
+                plane[k] += step[k];
+                tp[k] = grid_plane(bx.lo[k], cell[k], plane[k], oo[k], dd[k]);
+            }
+        if (idx[0] < 0 || idx[0] >= R || idx[1] < 0 || idx[1] >= R || idx[2] < 0 || idx[2] >= R) break;
+        t = te;
+    }
+    if (found && gb > ga && (ga > a0 || gb < b0)) { *a = ga; *b = gb; return 2; }
+    if (box_narrowed) { *a = a0; *b = b0; return 1; }
+    return 0;
+}
+
+// One thread per ray: bounds (N,2), state (N).  The walk takes up to 3R + 3 steps, so unlike the box decision it is made
+// once per ray, here, and z_values_bounds_kernel reads the result.
+__global__ void ray_grid_bounds_kernel(const GridArgs g, const float* __restrict__ orig, const float* __restrict__ dirs,
+                                       long long N, float* __restrict__ bounds, int* __restrict__ state) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    float a, b;
+    const int st = ray_grid_interval(g, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b);
+    reinterpret_cast<float2*>(bounds)[r] = make_float2(a, b);
+    if (state) state[r] = st;
+}
+
+// The depth kernels on given bounds: one thread per sample.  c0..c3 are the host constants of z_values_box_kernel; a ray of
+// state 1 or 2 replaces them with its own, by that kernel's formulas, so a state-1 ray has the bits the box kernel gives it
+// and a state-0 ray those of a context without a box.
+template <bool LINDISP>
+__global__ void z_values_bounds_kernel(float c0, float c1, float c2, float c3, const float* __restrict__ bounds,
+                                       const int* __restrict__ state, long long N, int S, const float* __restrict__ u,
+                                       uint64_t seed, long long ray_base, float* __restrict__ z) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= N * S) return;
+    const long long r = m / S;
+    const int s = (int)(m - r * S);
+    if (state[r] != 0) {
+        const float2 ab = reinterpret_cast<const float2*>(bounds)[r];
+        const float a = ab.x, b = ab.y;
+        c0 = a;
+        if constexpr (LINDISP) {
+            c1 = __int_as_float(__float_as_int(b) - 1);           // b > a > 0
+            c2 = __fdiv_rn(1.0f, a);
+            c3 = __fsub_rn(__fdiv_rn(1.0f, b), c2);
+        } else {
+            c1 = b;
+            c3 = __fsub_rn(b, a);
+            c2 = S > 1 ? __fdiv_rn(c3, (float)(S - 1)) : 0.f;
+        }
+    }
+    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
+    if constexpr (LINDISP) {
+        const float top = (float)(s + 1);
+        float v = __fadd_rn((float)s, uu);
+        if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
+        const float t = __fdiv_rn(v, (float)S);
+        const float zz = __fdiv_rn(1.0f, __fadd_rn(c2, __fmul_rn(c3, t)));
+        z[m] = fminf(fmaxf(zz, c0), c1);
+    } else {
+        float lin = __fadd_rn(c0, __fmul_rn(c2, (float)s));
+        if (s == 0) lin = c0;
+        if (s == S - 1 && S > 1) lin = c1;
+        z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, c3), (float)S));
+    }
+}
+
+void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, const uint32_t* bits, int R, const float* orig,
+                            const float* dirs, long long N, float* bounds, int* state, hipStream_t stream) {
+    if (N <= 0) return;
+    GridArgs g;
+    g.bx = box_args(box, near_b, far_b);
+    g.bits = bits; g.R = R;
+    const int bs = 256;
+    hipLaunchKernelGGL(ray_grid_bounds_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream, g, orig, dirs, N,
+                       bounds, state);
+}
+
+void launch_z_values_bounds(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
+                            long long ray_base, float* z, const float* bounds, const int* state, hipStream_t stream) {
+    if (N <= 0) return;
+    const int bs = 256;
+    const dim3 grid((unsigned)((N * S + bs - 1) / bs));
+    if (lindisp) {   // the host constants of launch_z_values
+        const float inv_near = (float)(1.0 / (double)near_b);
+        const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
+        hipLaunchKernelGGL(z_values_bounds_kernel<true>, grid, dim3(bs), 0, stream, near_b, nextafterf(far_b, near_b), inv_near,
+                           dinv, bounds, state, N, S, u, seed, ray_base, z);
+        return;
+    }
+    const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
+    const float span = (float)((double)far_b - (double)near_b);
+    hipLaunchKernelGGL(z_values_bounds_kernel<false>, grid, dim3(bs), 0, stream, near_b, far_b, delta, span, bounds, state, N,
+                       S, u, seed, ray_base, z);
+}
+
+// ---- baking: cell sample points -> the network's sigma (the MLP kernels, nerf_api.hip) -> bits -> dilation ----
+// Cells are numbered as their bits are.  A chunk is a run of whole 64-cell groups [cell_begin, cell_begin + n_cells), so a
+// wavefront's ballot is two whole words.  Point j of a cell: j == 0 the centre lo + cell (i + 0.5), j > 0 lo + cell (i + u)
+// with u = Philox(seed, cell number, 3 j + axis), stream 2 (the depth draws use 0 and 1).  The view direction is the unit
+// vector (0, 0, 1): sigma does not depend on it.
+__global__ void grid_points_kernel(const BoxArgs bx, int R, long long cell_begin, long long n_points, int spc, uint64_t seed,
+                                   float* __restrict__ xyz, float* __restrict__ view) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_points) return;
+    const long long cell = cell_begin + p / spc;
+    const int j = (int)(p % spc);
+    const int i[3] = {(int)(cell % R), (int)((cell / R) % R), (int)(cell / ((long long)R * R))};
+    float x[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const float w = __fdiv_rn(__fsub_rn(bx.hi[ax], bx.lo[ax]), (float)R);
+        const float f = j == 0 ? 0.5f : philox_uniform(seed, (uint64_t)cell, 3 * j + ax, 2u);
+        x[ax] = __fadd_rn(bx.lo[ax], __fmul_rn(w, __fadd_rn((float)i[ax], f)));
+    }
+    xyz[3 * p + 0] = x[0]; xyz[3 * p + 1] = x[1]; xyz[3 * p + 2] = x[2];
+    if (view) { view[3 * p + 0] = 0.f; view[3 * p + 1] = 0.f; view[3 * p + 2] = 1.f; }
+}
+
+// raw (n_cells * spc, 4): column 3 is sigma.  One thread per cell; lanes 0 and 32 of a wavefront store its two words.
+__global__ void grid_threshold_kernel(const float* __restrict__ raw, long long cell_begin, long long n_cells, int spc,
+                                      float threshold, uint32_t* __restrict__ bits) {
+    const long long cl = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool occ = false;
+    if (cl < n_cells) {
+        float m = raw[4 * (cl * spc) + 3];
+        for (int j = 1; j < spc; ++j) {
+            const float v = raw[4 * (cl * spc + j) + 3];
+            if (v > m) m = v;
+        }
+        occ = m > threshold;      // NaN: empty
+    }
+    const unsigned long long vote = __ballot(occ);
+    const int lane = threadIdx.x & 63;
+    if (cl < n_cells && (lane & 31) == 0) bits[(cell_begin + cl) >> 5] = (uint32_t)(vote >> lane);
+}
+
+// dst = src grown by one cell in the 26-neighbourhood.  One thread per cell, R^3 a multiple of 64.
+__global__ void grid_dilate_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int R) {
+    const long long cells = (long long)R * R * R;
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool occ = false;
+    if (c < cells) {
+        const int ix = (int)(c % R), iy = (int)((c / R) % R), iz = (int)(c / ((long long)R * R));
+        for (int dz = -1; dz <= 1; ++dz)
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int x = ix + dx, y = iy + dy, zc = iz + dz;
+                    if (x < 0 || x >= R || y < 0 || y >= R || zc < 0 || zc >= R) continue;
+                    const int bit = x + R * (y + R * zc);
+                    occ = occ || ((src[bit >> 5] >> (bit & 31)) & 1u);
+                }
+    }
+    const unsigned long long vote = __ballot(occ);
+    const int lane = threadIdx.x & 63;
+    if (c < cells && (lane & 31) == 0) dst[c >> 5] = (uint32_t)(vote >> lane);
+}
+
+void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,
+                        float* xyz, float* view, hipStream_t stream) {
+    const long long n_points = n_cells * spc;
+    if (n_points <= 0) return;
+    const int bs = 256;
+    hipLaunchKernelGGL(grid_points_kernel, dim3((unsigned)((n_points + bs - 1) / bs)), dim3(bs), 0, stream,
+                       box_args(box, 0.f, 0.f), R, cell_begin, n_points, spc, seed, xyz, view);
+}
+
+void launch_grid_threshold(const float* raw, long long cell_begin, long long n_cells, int spc, float threshold,
+                           uint32_t* bits, hipStream_t stream) {
+    if (n_cells <= 0) return;
+    const int bs = 256;
+    hipLaunchKernelGGL(grid_threshold_kernel, dim3((unsigned)((n_cells + bs - 1) / bs)), dim3(bs), 0, stream, raw, cell_begin,
+                       n_cells, spc, threshold, bits);
+}
+
+void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t stream) {
+    const long long cells = (long long)R * R * R;
+    const int bs = 256;
+    hipLaunchKernelGGL(grid_dilate_kernel, dim3((unsigned)((cells + bs - 1) / bs)), dim3(bs), 0, stream, src, dst, R);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -64,10 +64,22 @@ int sampling_ok(const nerf_ctx* c) {
     return 0;
 }
 
-void draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
-                   long long ray_base, float* z) {
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, S, u, seed, ray_base, z,
-                    c->stream, o, d, c->box_on ? &c->box : nullptr);
+int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
+                  long long ray_base, float* z) {
+    const bool lindisp = c->sampling == NERF_SAMPLING_LINDISP;
+    if (c->box_on && c->grid_R > 0 && o && d && N > 0) {
+        // the walk through the grid is made once per ray, into the ctx's own scratch; the depth kernel reads the result
+        if (int r = ensure(c, c->b_gbounds, (size_t)N * 8)) return r;
+        if (int r = ensure(c, c->b_gstate, (size_t)N * 4)) return r;
+        launch_ray_grid_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, (const uint32_t*)c->b_grid[c->grid_cur].p,
+                               c->grid_R, o, d, N, (float*)c->b_gbounds.p, (int*)c->b_gstate.p, c->stream);
+        launch_z_values_bounds(c->cfg.near_boundary, c->cfg.far_boundary, lindisp, N, S, u, seed, ray_base, z,
+                               (const float*)c->b_gbounds.p, (const int*)c->b_gstate.p, c->stream);
+        return 0;
+    }
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, lindisp, N, S, u, seed, ray_base, z, c->stream, o, d,
+                    c->box_on ? &c->box : nullptr);
+    return 0;
 }
 
 // The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
@@ -367,7 +379,7 @@ int dev_render(nerf_ctx* c, const float* o, const float* d, long long N, int Sc,
     if (int r = sampling_ok(c)) return r;
     if (int r = ensure(c, c->b_zc, (size_t)N * Sc * sizeof(float))) return r;
     float* zc = (float*)c->b_zc.p;
-    draw_z_values(c, o, d, N, Sc, u_c, seed, ray_base, zc);
+    if (int r = draw_z_values(c, o, d, N, Sc, u_c, seed, ray_base, zc)) return r;
     if (!fine) return dev_render_rays(c, NERF_NET_COARSE, o, d, zc, N, Sc, outs);
     if (Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
     if (int r = ensure(c, c->b_wc, (size_t)N * Sc * sizeof(float))) return r;
@@ -438,7 +450,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     (void)hipSetDevice(c->cfg.device);
     (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->b_orig, &c->b_dirs, &c->b_zc, &c->b_zf, &c->b_raw, &c->b_wc, &c->b_u0, &c->b_u1,
-                      &c->b_in0, &c->b_in1, &c->b_in2};
+                      &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);
     for (auto& n : c->net) {
@@ -495,13 +507,98 @@ int nerf_ctx_set_ray_space(nerf_ctx* c, int space, float ndc_near_plane) {
 
 int nerf_ctx_set_scene_box(nerf_ctx* c, const float* lo3, const float* hi3) {
     if (!c) return fail("ctx is NULL");
-    if (!lo3 && !hi3) { c->box_on = false; return 0; }
+    if (!lo3 && !hi3) { c->box_on = false; c->grid_R = 0; return 0; }   // the grid lives on the box: it goes with it
     if (!lo3 || !hi3) return fail("scene box: lo and hi are both given, or both NULL (box off)");
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
             return fail("scene box needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", a, lo3[a], hi3[a]);
     for (int a = 0; a < 3; ++a) { c->box.lo[a] = lo3[a]; c->box.hi[a] = hi3[a]; }
     c->box_on = true;
+    c->grid_R = 0;
+    return 0;
+}
+
+// ---- occupancy grid ----
+static int grid_resolution_ok(int R) {
+    if (R < 4 || R > 256 || R % 4) return fail("occupancy grid resolution must be a multiple of 4 in [4, 256] (got %d)", R);
+    return 0;
+}
+static const char* kGridNeedsBox = "an occupancy grid needs a scene box (nerf_ctx_set_scene_box)";
+
+int nerf_ctx_set_occupancy_grid(nerf_ctx* c, const uint32_t* bits, int32_t R) {
+    ENTER(c);
+    if (!bits && R == 0) { c->grid_R = 0; return 0; }
+    if (!bits) return fail("occupancy grid: bits is NULL (NULL, 0 clears the grid)");
+    if (!c->box_on) return fail("%s", kGridNeedsBox);
+    if (int r = grid_resolution_ok(R)) return r;
+    const size_t bytes = (size_t)R * R * R / 8;
+    c->grid_R = 0;
+    if (int r = ensure(c, c->b_grid[0], bytes)) return r;
+    HIP_OK(hipMemcpyAsync(c->b_grid[0].p, bits, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));          // the caller's array is free again
+    c->grid_cur = 0;
+    c->grid_R = R;
+    return 0;
+}
+
+int nerf_ctx_get_occupancy_grid(nerf_ctx* c, uint32_t* bits, int32_t* R) {
+    ENTER(c);
+    if (!R) return fail("NULL argument");
+    *R = c->grid_R;
+    if (!bits || c->grid_R == 0) return 0;
+    const size_t bytes = (size_t)c->grid_R * c->grid_R * c->grid_R / 8;
+    HIP_OK(hipMemcpyAsync(bits, c->b_grid[c->grid_cur].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int nerf_occupancy_bake(nerf_ctx* c, int which, int32_t R, float sigma_threshold, int32_t samples_per_cell, int32_t dilate,
+                        uint64_t seed, int64_t* n_occupied) {
+    ENTER(c);
+    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
+    if (!c->box_on) return fail("%s", kGridNeedsBox);
+    if (int r = grid_resolution_ok(R)) return r;
+    if (!std::isfinite(sigma_threshold) || !(sigma_threshold > 0.f))
+        return fail("occupancy grid: sigma_threshold must be finite and > 0 (got %g)", sigma_threshold);
+    if (samples_per_cell < 1 || samples_per_cell > 8)
+        return fail("occupancy grid: samples_per_cell must be in 1..8 (got %d)", samples_per_cell);
+    if (dilate < 0 || dilate > 2) return fail("occupancy grid: dilate must be 0, 1 or 2 (got %d)", dilate);
+    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    const long long cells = (long long)R * R * R;                 // a multiple of 64
+    const size_t bytes = (size_t)cells / 8;
+    c->grid_R = 0;                                                // a bake that fails leaves no grid behind
+    if (int r = ensure(c, c->b_grid[0], bytes)) return r;
+    if (int r = ensure(c, c->b_grid[1], bytes)) return r;
+    // chunks of whole 64-cell groups, at most 2^20 points each, through the device-resident model_predict path
+    const long long chunk_cells = std::min(cells, (((long long)1 << 20) / samples_per_cell) & ~63LL);
+    const size_t pts = (size_t)chunk_cells * samples_per_cell;
+    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
+    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
+    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
+    float *xyz = (float*)c->b_in0.p, *view = (float*)c->b_in1.p, *raw = (float*)c->b_raw.p;
+    int cur = 0;
+    for (long long begin = 0; begin < cells; begin += chunk_cells) {
+        const long long n = std::min(chunk_cells, cells - begin);
+        launch_grid_points(c->box, R, begin, n, samples_per_cell, seed, xyz, view, c->stream);
+        if (int r = run_mlp(c, which, k, xyz, c->cfg.n_angles != 0 ? view : nullptr, nullptr, raw, n * samples_per_cell, 1, 1))
+            return r;
+        launch_grid_threshold(raw, begin, n, samples_per_cell, sigma_threshold, (uint32_t*)c->b_grid[cur].p, c->stream);
+    }
+    for (int i = 0; i < dilate; ++i, cur ^= 1)
+        launch_grid_dilate((const uint32_t*)c->b_grid[cur].p, (uint32_t*)c->b_grid[cur ^ 1].p, R, c->stream);
+    HIP_OK(hipGetLastError());
+    if (n_occupied) {
+        std::vector<uint32_t> host(bytes / 4);
+        HIP_OK(hipMemcpyAsync(host.data(), c->b_grid[cur].p, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        long long count = 0;
+        for (uint32_t w : host) count += __builtin_popcount(w);
+        *n_occupied = count;
+    }
+    c->grid_cur = cur;
+    c->grid_R = R;
     return 0;
 }
 
@@ -607,7 +704,7 @@ int nerf_get_z_values_rays(nerf_ctx* c, const float* rays_orig, const float* ray
         if (int r = ensure(c, c->b_zc, (size_t)N * S * 4)) return r;
         dz = (float*)c->b_zc.p;
     }
-    draw_z_values(c, o, d, N, S, du, seed, ray_base, dz);
+    if (int r = draw_z_values(c, o, d, N, S, du, seed, ray_base, dz)) return r;
     HIP_OK(hipGetLastError());
     if (mem == NERF_MEM_HOST) {
         HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
@@ -637,6 +734,33 @@ int nerf_ray_box_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_d
     if (mem == NERF_MEM_HOST) {
         HIP_OK(hipMemcpyAsync(bounds, db, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
         if (narrowed) HIP_OK(hipMemcpyAsync(narrowed, dn, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int nerf_ray_occupancy_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
+                              int32_t* state, int mem) {
+    ENTER(c);
+    if (!rays_orig || !rays_dirs || !bounds) return fail("NULL argument");
+    if (N < 0) return fail("bad shape N=%lld", (long long)N);
+    if (!c->box_on || c->grid_R == 0) return fail("no occupancy grid is set (nerf_ctx_set_occupancy_grid, nerf_occupancy_bake)");
+    const float *o = rays_orig, *d = rays_dirs;
+    float* db = bounds;
+    int32_t* ds = state;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
+        if (int r = ensure(c, c->b_in0, (size_t)N * 8)) return r;
+        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; db = (float*)c->b_in0.p;
+        if (state) { if (int r = ensure(c, c->b_in1, (size_t)N * 4)) return r; ds = (int32_t*)c->b_in1.p; }
+    }
+    launch_ray_grid_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R,
+                           o, d, N, db, ds, c->stream);
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(bounds, db, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+        if (state) HIP_OK(hipMemcpyAsync(state, ds, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
     return 0;

@@ -44,6 +44,10 @@ struct nerf_ctx {
     float ndc_near_plane = 1.0f;
     bool box_on = false;                       // scene box, in the space of the rays the depth kernel sees: nerf_ctx_set_scene_box
     nerf::SceneBox box = {};
+    int grid_R = 0;                            // occupancy grid over the box (0: none): nerf_ctx_set_occupancy_grid / nerf_occupancy_bake
+    int grid_cur = 0;                          // which of b_grid holds it; the other is the dilation's second array
+    nerf::DevBuf b_grid[2];                    // grid_R^3 / 32 words each
+    nerf::DevBuf b_gbounds, b_gstate;          // per-ray (a, b) and state of draw_z_values under a grid (grow-only)
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -70,8 +74,9 @@ int h2d(nerf_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int enter(nerf_ctx* c);                             // NULL check + hipSetDevice
 #define ENTER(c) do { if (int r__ = nerf::enter(c)) return r__; } while (0)
 int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's bounds suit its sampling mode (lindisp: near > 0)
-// The coarse depths of N rays as this ctx draws them (bounds, sampling mode, scene box): every call site that has rays
-void draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
+// The coarse depths of N rays as this ctx draws them (bounds, sampling mode, scene box, occupancy grid): every call site that
+// has rays.  Without a grid it launches what it always launched and cannot fail; with one it may grow two scratch buffers.
+int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
                    long long ray_base, float* z);   // nerf_api.hip; device pointers, enqueued on the ctx stream
 
 void train_free(nerf_ctx* c);                       // train_api.hip: releases c->train (called by nerf_ctx_destroy)

@@ -237,6 +237,20 @@ void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S
 // bounds (N,2): (a, b) of a narrowed ray, (near_b, far_b) of any other; narrowed (N) 0 / 1, nullable
 void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,
                            float* bounds, int* narrowed, hipStream_t stream);
+// Occupancy grid (aux_kernels.hip: ray_grid_interval): bits = R^3 / 32 device words over the box, cell (ix, iy, iz) = bit
+// ix + R (iy + R iz).  bounds (N,2) and state (N; 0 untouched / 1 box only / 2 grid; nullable) of every ray, walked once ...
+void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, const uint32_t* bits, int R, const float* orig,
+                            const float* dirs, long long N, float* bounds, int* state, hipStream_t stream);
+// ... and launch_z_values on them: a ray of state 0 draws with the host's constants, any other on its own (a, b)
+void launch_z_values_bounds(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
+                            long long ray_base, float* z, const float* bounds, const int* state, hipStream_t stream);
+// baking: the sample points (n_cells * spc, 3) of cells [cell_begin, cell_begin + n_cells) and as many unit view directions
+// (nullable); raw (n_cells * spc, 4) -> their bits; one step of 26-neighbour growth.  cell_begin, n_cells: multiples of 64
+void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,
+                        float* xyz, float* view, hipStream_t stream);
+void launch_grid_threshold(const float* raw, long long cell_begin, long long n_cells, int spc, float threshold,
+                           uint32_t* bits, hipStream_t stream);
+void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t stream);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                        uint64_t seed, long long ray_base, float* z_new, float* z_merged,

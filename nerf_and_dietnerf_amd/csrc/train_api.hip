@@ -762,7 +762,7 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
 
     // coarse forward (src/NeRF.py:146-151)
     TPass& pc = t->pass[0];
-    draw_z_values(c, o, d, N, Sc, uc, seed, 0, (float*)pc.z.p);
+    if (int q = draw_z_values(c, o, d, N, Sc, uc, seed, 0, (float*)pc.z.p)) return q;
     if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
     const bool through_sampler = fine && t->cfg.sampler_gradient != 0;
     if (fine) {
@@ -827,7 +827,7 @@ int render_forward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const Pa
     r |= ensure(c, t->z_new, (fine ? N * (long long)Sf : 1) * sizeof(float));
     if (r) return r;
     TPass& pc = t->pass[0];
-    draw_z_values(c, o, d, N, Sc, uc, seed, ray_base, (float*)pc.z.p);
+    if (int q = draw_z_values(c, o, d, N, Sc, uc, seed, ray_base, (float*)pc.z.p)) return q;
     if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
     if (!fine) return 0;
     launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,

@@ -21,8 +21,8 @@ def c2w_to_rays_prepare_ds(c2w, field_of_view: float, img, ctx):
     """One image -> (rays_orig (h*w,4), rays_dirs (h*w,4), real_rgb_pixels (h*w,3)) as CUDA tensors.  On a context in NDC
     ray space (render_config ``use_ndc``; Context.set_ray_space) the rays are transformed on the device, with the
     context's near plane, before they are returned: the trainer then sees what render_image renders.  These are the rays
-    a scene box (render_config ``scene_box``; Context.set_scene_box) is defined on: the trainer clips each to the box when it
-    draws depths, nothing is stored here."""
+    a scene box (render_config ``scene_box``; Context.set_scene_box) is defined on: the trainer clips each to the box -- and to
+    the occupancy grid, when the context has one -- when it draws depths, nothing is stored here."""
     import torch
     dev = torch.device("cuda", ctx.cfg.device)
     img_t = torch.as_tensor(np.asarray(img, np.float32) if not hasattr(img, "is_cuda") else img,
@@ -90,14 +90,21 @@ def fit(model, ds: RayDataset, epochs: int = 1, steps_per_epoch: Optional[int] =
 
     The loop never waits for a step: ``train_step(..., want_metrics=False)`` only enqueues, the library adds every step's
     loss / psnr_coarse / psnr_fine to running sums on the device, and the sums are read once per epoch (and every
-    ``log_every`` steps when a progress line is asked for) -- so an epoch runs at the step rate ``bench.py`` reports."""
+    ``log_every`` steps when a progress line is asked for) -- so an epoch runs at the step rate ``bench.py`` reports.
+
+    With render_config ``occupancy_grid`` the model's grid follows its schedule at the start of every epoch
+    (NeRF.occupancy_grid_epoch: off during ``warmup_epochs``, baked again every ``update_every`` epochs after them); within
+    an epoch the grid is the snapshot taken at its start."""
     ctx = model.ctx
     ctx.train_read_metric_sums()                     # start from clean sums
     extra = getattr(model, "train_read_extra_metric_sums", None)    # DietNeRF: cosine_similarity_loss, kept by the model
     if extra:
         extra()
     history = []
+    grid_epoch = getattr(model, "occupancy_grid_epoch", None)
     for _ in range(epochs):
+        if grid_epoch:
+            grid_epoch()
         sums: Dict[str, float] = {}
         n = 0
 

@@ -40,6 +40,11 @@ LINDISP = "lindisp"                  # bool, default False: coarse depths unifor
 USE_NDC = "use_ndc"                  # bool, default False: rays in normalised device coordinates
 NDC_NEAR_PLANE = "ndc_near_plane"    # float, default 1.0: distance of the NDC near plane (with use_ndc)
 SCENE_BOX = "scene_box"              # [[x, y, z], [x, y, z]] (lo, hi), default absent: per-ray depth range from a scene box
+OCCUPANCY_GRID = "occupancy_grid"    # dict of the keys below, default absent: sample each ray where the network has density
+GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL = "resolution", "sigma_threshold", "samples_per_cell"
+GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS = "dilate", "update_every", "warmup_epochs"
+_GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS)
+GRID_NEEDS_BOX = "an occupancy grid needs a scene box"
 
 N_COORDINATES = 3
 N_COLOR_CHANNELS = 3
@@ -55,6 +60,35 @@ _RAY_SPACES = {"world": _lib.NERF_RAYS_WORLD, "ndc": _lib.NERF_RAYS_NDC}
 # --------------------------------------------------------------------------------------------
 # array plumbing: numpy (host) or torch.cuda (device)
 # --------------------------------------------------------------------------------------------
+def check_grid_resolution(resolution) -> int:
+    """The library's rule for R (a multiple of 4 in [4, 256]), checked before any device call."""
+    r = int(resolution)
+    if r != resolution or r < 4 or r > 256 or r % 4:
+        raise ValueError(f"occupancy grid resolution must be a multiple of 4 in [4, 256] (got {resolution!r})")
+    return r
+
+
+def pack_occupancy_grid(grid) -> np.ndarray:
+    """(R, R, R) bool array indexed [ix, iy, iz] -> R^3 / 32 little-endian uint32 words, cell (ix, iy, iz) = bit
+    ix + R (iy + R iz)."""
+    g = np.asarray(grid)
+    if g.ndim != 3 or g.shape[0] != g.shape[1] or g.shape[0] != g.shape[2]:
+        raise ValueError(f"an occupancy grid is an (R, R, R) array, got shape {g.shape}")
+    check_grid_resolution(g.shape[0])
+    flat = np.ascontiguousarray(g.astype(bool).transpose(2, 1, 0)).ravel()          # ix runs fastest
+    return np.packbits(flat, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def unpack_occupancy_grid(words, resolution=None) -> np.ndarray:
+    """The inverse of pack_occupancy_grid; ``resolution`` defaults to the R with R^3 = 32 * len(words)."""
+    w = np.ascontiguousarray(np.asarray(words).ravel(), dtype="<u4")
+    r = int(round((32 * w.size) ** (1.0 / 3.0))) if resolution is None else int(resolution)
+    check_grid_resolution(r)
+    if r ** 3 != 32 * w.size:
+        raise ValueError(f"{w.size} words are no R^3 / 32 for R = {r}")
+    return np.unpackbits(w.view(np.uint8), bitorder="little").astype(bool).reshape(r, r, r).transpose(2, 1, 0).copy()
+
+
 def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
@@ -233,6 +267,7 @@ class Context:
         self._slot_fine = {}         # train_render_forward slots that ran a fine pass
         self.sampling, self.ray_space, self.ndc_near_plane = "linear", "world", 1.0   # what nerf_ctx_create leaves
         self.scene_box = None        # ((lo), (hi)) of set_scene_box
+        self.grid_resolution = 0     # R of the occupancy grid (0: none)
 
     def close(self):
         if getattr(self, "h", None):
@@ -311,7 +346,7 @@ class Context:
         nerf_ctx_set_scene_box has the rule).  ``set_scene_box(None)`` turns it off.  get_z_values has no rays and ignores it."""
         if lo is None and hi is None:
             _lib.check(self.lib.nerf_ctx_set_scene_box(self.h, None, None))
-            self.scene_box = None
+            self.scene_box, self.grid_resolution = None, 0      # the grid lives on the box
             return
         if lo is None or hi is None:
             raise ValueError("scene box: give both corners, or None to turn it off")
@@ -323,6 +358,83 @@ class Context:
             raise RuntimeError(f"scene box needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
         _lib.check(self.lib.nerf_ctx_set_scene_box(self.h, lo_a.ctypes.data, hi_a.ctypes.data))
         self.scene_box = (tuple(float(v) for v in lo_a), tuple(float(v) for v in hi_a))
+        self.grid_resolution = 0     # a new box drops the grid
+
+    # ---- occupancy grid: R x R x R bits over the scene box (include/nerf_mi355.h: nerf_ctx_set_occupancy_grid has the rule) ----
+    def set_occupancy_grid(self, grid) -> None:
+        """``grid``: an (R, R, R) bool array indexed [ix, iy, iz], or the R^3 / 32 packed uint32 words (1-D), or None to clear
+        it.  With a grid every call that follows the scene box samples a ray from the first occupied cell it enters to the
+        last one it leaves; a ray that meets none keeps what the box alone gives it.  Needs a scene box; a new box drops it.
+        The grid is a snapshot: nothing here or in the library ever rebuilds it, so after the weights change (training) it is
+        stale until the caller sets or bakes it again -- training with a stale grid is the caller's choice."""
+        if grid is None:
+            _lib.check(self.lib.nerf_ctx_set_occupancy_grid(self.h, None, 0))
+            self.grid_resolution = 0
+            return
+        if self.scene_box is None:
+            raise RuntimeError(f"{GRID_NEEDS_BOX} (set_scene_box)")
+        g = np.asarray(grid)
+        if g.ndim == 3:
+            words, r = pack_occupancy_grid(g), g.shape[0]
+        elif g.ndim == 1 and g.dtype.kind in "ui":
+            words = np.ascontiguousarray(g, dtype=np.uint32)
+            r = check_grid_resolution(int(round((32 * words.size) ** (1.0 / 3.0))))
+            if r ** 3 != 32 * words.size:
+                raise ValueError(f"{words.size} words are no R^3 / 32 for a multiple of 4 in [4, 256]")
+        else:
+            raise ValueError(f"an occupancy grid is an (R, R, R) bool array or a 1-D array of packed uint32 words, got "
+                             f"{g.dtype} of shape {g.shape}")
+        _lib.check(self.lib.nerf_ctx_set_occupancy_grid(self.h, words.ctypes.data, r))
+        self.grid_resolution = r
+
+    def occupancy_grid(self):
+        """The context's grid as an (R, R, R) bool array indexed [ix, iy, iz], or None."""
+        r = C.c_int32(0)
+        _lib.check(self.lib.nerf_ctx_get_occupancy_grid(self.h, None, C.addressof(r)))
+        if r.value == 0:
+            return None
+        words = np.empty(r.value ** 3 // 32, np.uint32)
+        _lib.check(self.lib.nerf_ctx_get_occupancy_grid(self.h, words.ctypes.data, C.addressof(r)))
+        return unpack_occupancy_grid(words, r.value)
+
+    def bake_occupancy_grid(self, which, resolution, sigma_threshold, samples_per_cell=1, dilate=1, seed=0) -> int:
+        """Bake the grid from network ``which`` (0 coarse, 1 fine) as it is NOW, in the context's precision: a cell is occupied
+        if the network's sigma exceeds ``sigma_threshold`` at its centre or at one of its ``samples_per_cell - 1`` jittered
+        points; the set is grown by ``dilate`` cells (0..2).  Returns the occupied count.  See set_occupancy_grid: the grid
+        is never rebuilt implicitly."""
+        if self.scene_box is None:
+            raise RuntimeError(f"{GRID_NEEDS_BOX} (set_scene_box)")
+        r = check_grid_resolution(resolution)
+        thr = float(sigma_threshold)
+        if not (np.isfinite(thr) and thr > 0):
+            raise ValueError(f"occupancy grid: sigma_threshold must be finite and > 0 (got {sigma_threshold!r})")
+        if not 1 <= int(samples_per_cell) <= 8:
+            raise ValueError(f"occupancy grid: samples_per_cell must be in 1..8 (got {samples_per_cell!r})")
+        if int(dilate) not in (0, 1, 2):
+            raise ValueError(f"occupancy grid: dilate must be 0, 1 or 2 (got {dilate!r})")
+        count = C.c_int64(0)
+        self.grid_resolution = 0
+        _lib.check(self.lib.nerf_occupancy_bake(self.h, int(which), r, thr, int(samples_per_cell), int(dilate), int(seed),
+                                                C.addressof(count)))
+        self.grid_resolution = r
+        return int(count.value)
+
+    def ray_occupancy_bounds(self, rays_orig, rays_dirs):
+        """Rays (N,4) -> (bounds (N,2) float32, state (N,) int32) under the context's box, grid and bounds: state 2 and the
+        grid's interval, state 1 and the box's for a ray only the box narrows, state 0 and (near, far) for any other
+        (nerf_ray_occupancy_bounds: the device function behind the depth kernels)."""
+        arr = self._arrays(rays_orig, rays_dirs)
+        n = int(rays_orig.shape[0])
+        po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
+        bounds, pb = arr.out((n, 2))
+        if arr.torch is not None:
+            state = arr.torch.empty((n,), dtype=arr.torch.int32, device=arr.device)
+            ps = state.data_ptr()
+        else:
+            state = np.empty((n,), np.int32)
+            ps = state.ctypes.data
+        _lib.check(self.lib.nerf_ray_occupancy_bounds(self.h, po, pd, n, pb, ps, arr.mem))
+        return bounds, state
 
     def ray_box_bounds(self, rays_orig, rays_dirs):
         """Rays (N,4) -> (bounds (N,2) float32, narrowed (N,) int32) under the context's box and bounds: (a, b) of a ray the
@@ -842,6 +954,62 @@ class NeRF:
             if len(self.scene_box) != 2:
                 raise ValueError(f"{SCENE_BOX} must be [[x, y, z], [x, y, z]] (lo, hi), got {self.scene_box!r}")
             self.ctx.set_scene_box(self.scene_box[0], self.scene_box[1])
+        # occupancy grid: an absent key (or None) leaves everything as it was
+        self.grid_config = self._grid_config(render_config.get(OCCUPANCY_GRID), self.scene_box)
+        self._grid_epochs = 0        # epochs fit() has run: the grid's schedule counts them
+
+    @staticmethod
+    def _grid_config(cfg, scene_box):
+        """render_config["occupancy_grid"] checked and completed with its defaults, or None."""
+        if cfg is None:
+            return None
+        if scene_box is None:
+            raise ValueError(f"{OCCUPANCY_GRID}: {GRID_NEEDS_BOX} (render_config[{SCENE_BOX!r}])")
+        unknown = sorted(set(cfg) - set(_GRID_KEYS))
+        if unknown:
+            raise ValueError(f"{OCCUPANCY_GRID}: unknown keys {unknown}; expected {list(_GRID_KEYS)}")
+        for key in (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD):
+            if key not in cfg:
+                raise ValueError(f"{OCCUPANCY_GRID} needs {key!r}")
+        out = {GRID_RESOLUTION: check_grid_resolution(cfg[GRID_RESOLUTION]), GRID_SIGMA_THRESHOLD: float(cfg[GRID_SIGMA_THRESHOLD]),
+               GRID_SAMPLES_PER_CELL: int(cfg.get(GRID_SAMPLES_PER_CELL, 1)), GRID_DILATE: int(cfg.get(GRID_DILATE, 1)),
+               GRID_UPDATE_EVERY: int(cfg.get(GRID_UPDATE_EVERY, 1)), GRID_WARMUP_EPOCHS: int(cfg.get(GRID_WARMUP_EPOCHS, 0))}
+        if not (np.isfinite(out[GRID_SIGMA_THRESHOLD]) and out[GRID_SIGMA_THRESHOLD] > 0):
+            raise ValueError(f"{OCCUPANCY_GRID}: sigma_threshold must be finite and > 0 (got {cfg[GRID_SIGMA_THRESHOLD]!r})")
+        if not 1 <= out[GRID_SAMPLES_PER_CELL] <= 8:
+            raise ValueError(f"{OCCUPANCY_GRID}: samples_per_cell must be in 1..8 (got {cfg[GRID_SAMPLES_PER_CELL]!r})")
+        if out[GRID_DILATE] not in (0, 1, 2):
+            raise ValueError(f"{OCCUPANCY_GRID}: dilate must be 0, 1 or 2 (got {cfg[GRID_DILATE]!r})")
+        if out[GRID_UPDATE_EVERY] < 1 or out[GRID_WARMUP_EPOCHS] < 0:
+            raise ValueError(f"{OCCUPANCY_GRID}: update_every must be >= 1 and warmup_epochs >= 0")
+        return out
+
+    def update_occupancy_grid(self, seed: int = 0) -> Optional[int]:
+        """Bake the configured grid (render_config["occupancy_grid"]) from the fine network when it is loaded, otherwise the
+        coarse one; returns the occupied count, or None without the key.  load_weights calls it, and dataset.fit calls it
+        every ``update_every`` epochs once ``warmup_epochs`` have passed (before that the grid is off).  Nowhere else is the
+        grid rebuilt: after set_weights or train_step calls of the caller's own it is stale until this is called again, and
+        training with a stale grid is the caller's choice."""
+        g = self.grid_config
+        if g is None:
+            return None
+        which = NERF_NET_FINE if self.model_fine is not None and self.ctx.loaded[NERF_NET_FINE] else NERF_NET_COARSE
+        return self.ctx.bake_occupancy_grid(which, g[GRID_RESOLUTION], g[GRID_SIGMA_THRESHOLD], g[GRID_SAMPLES_PER_CELL],
+                                            g[GRID_DILATE], seed)
+
+    def occupancy_grid_epoch(self) -> None:
+        """dataset.fit's hook, at the start of every epoch: the grid is off during the warm-up epochs and baked again every
+        ``update_every`` epochs after them."""
+        g = self.grid_config
+        if g is None:
+            return
+        done = self._grid_epochs - g[GRID_WARMUP_EPOCHS]
+        self._grid_epochs += 1
+        if done < 0:
+            if self.ctx.grid_resolution:
+                self.ctx.set_occupancy_grid(None)
+        elif done % g[GRID_UPDATE_EVERY] == 0:
+            self.update_occupancy_grid()
 
     def set_weights(self, coarse, fine=None) -> None:
         self._blobs = [coarse, fine]
@@ -855,6 +1023,7 @@ class NeRF:
         from .keras_h5 import load_nerf_checkpoint
         coarse, fine = load_nerf_checkpoint(str(path))
         self.set_weights(coarse, fine)
+        self.update_occupancy_grid()     # render_config["occupancy_grid"]: a loaded checkpoint is rendered with its own grid
 
     def save_weights(self, path) -> None:
         """Keras ``model.save_weights(path)`` (src/UtilsFiles.py:153-164): the current (trained) weights as a
