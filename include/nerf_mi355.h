@@ -32,7 +32,8 @@ extern "C" {
 /* 6 also covers the forward-facing-scene entries added after it (nerf_ctx_set_sampling, nerf_ctx_set_ray_space,
  * nerf_rays_to_ndc), the scene-box entries (nerf_ctx_set_scene_box, nerf_ray_box_bounds, nerf_get_z_values_rays) and the
  * occupancy-grid entries (nerf_ctx_set_occupancy_grid, nerf_ctx_get_occupancy_grid, nerf_occupancy_bake,
- * nerf_ray_occupancy_bounds), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_ray_occupancy_bounds) and the mesh entries (nerf_density_lattice, nerf_isosurface, nerf_isosurface_fetch,
+ * nerf_mesh_colors), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -187,6 +188,48 @@ int nerf_ctx_get_occupancy_grid(nerf_ctx* ctx, uint32_t* bits, int32_t* R);
  * outside 1..8; a bake that fails leaves the ctx without a grid. */
 int nerf_occupancy_bake(nerf_ctx* ctx, int which, int32_t R, float sigma_threshold, int32_t samples_per_cell, int32_t dilate,
                         uint64_t seed, int64_t* n_occupied);
+
+/* ---- ABI 6+, a triangle mesh out of the density field ---------------------------------------------------------------------
+ * nerf_density_lattice: raw sigma (column 3 of nerf_model_predict before the ReLU, the same kernels, the ctx's precision) of
+ * network `which` at the n^3 lattice points of the scene box, n in 2..512.  Point (ix, iy, iz) is element
+ * ix + n (iy + n iz) of sigma (n, n, n); its position is p_a = lo_a + step_a * float(i_a), step_a = (hi_a - lo_a) / float(n - 1),
+ * in float32, every operation rounded on its own (no FMA).  view_dir3 (HOST, 3 floats) is the view direction of every point,
+ * NULL = (0, 0, 1) as in the bake; it is ignored for n_angles == 0.  The points go through the network in chunks of at most
+ * 2^20.  Fails without a box ("a density lattice needs a scene box"), if the network is not loaded, or if n is outside 2..512. */
+int nerf_density_lattice(nerf_ctx* ctx, int which, int32_t n, const float* view_dir3, float* sigma, int mem);
+/* nerf_isosurface: the surface s = iso of a volume s (n, n, n), n in 2..512, laid out and placed as above on the box lo3 < hi3
+ * (HOST, explicit: the volume need not come from a network), as an indexed triangle mesh by marching tetrahedra on the
+ * 6-tetrahedra split of every cube along its (0,0,0)-(1,1,1) diagonal.  Neighbouring cubes agree on every face diagonal, so
+ * the mesh is closed wherever the surface does not leave the lattice.  The result is canonical (no atomics, no hashing):
+ *   Inside.    A point is inside iff s > iso; NaN is outside.  iso must be finite.
+ *   Edges.     Every tetrahedron edge runs from a lattice point p to p + e, e one of 7 types, in this order:
+ *              100, 010, 001, 110, 011, 101, 111 (x, y, z offsets).
+ *   Vertices.  An edge whose ends differ in "inside" carries exactly one vertex; vertices are numbered in increasing order of
+ *              key = 7 * pointindex(p) + type.  Position, per axis: p0 + t (p1 - p0) with p0, p1 the positions of p and p + e
+ *              and t = (iso - s0) / (s1 - s0), s0 = s(p); float32, separate operations; a t that is not finite is 0.5.
+ *   Triangles. Cubes are visited in order cx + (n - 1) (cy + (n - 1) cz), the tetrahedra of a cube in lexicographic order of
+ *              the axis permutation (a, b, c): 012, 021, 102, 120, 201, 210; corners c0 = cube base, c1 = c0 + e_a,
+ *              c2 = c1 + e_b, c3 = c2 + e_c.  One or three corners inside: one triangle on the three edges at the odd corner,
+ *              in corner order.  Two inside (I0, I1) and two outside (O0, O1), each pair in corner order: the quad
+ *              (I0O0, I0O1, I1O1, I1O0).  The polygon is oriented counter-clockwise seen from the outside (normal from inside
+ *              to outside), decided from the case and the permutation's parity alone, never from positions: where a lattice
+ *              value equals iso, vertices coincide and triangles have zero area.  It is then rotated so that its lowest
+ *              vertex id comes first and emitted as (q0, q1, q2) and, for a quad, (q0, q2, q3).
+ *   Normals.   Gradient at a lattice point, per axis: (s[i + 1] - s[i - 1]) / (2 step_a), at the faces the one-sided
+ *              difference over step_a.  At a vertex g = g0 + t (g1 - g0); the normal is -g / |g|,
+ *              |g| = sqrt((gx gx + gy gy) + gz gz), or (0, 0, 0) when |g| is 0 or not finite.
+ * The counts are not known in advance, so there are two calls: the first builds the mesh in the ctx's arena and returns the
+ * counts (both always fit int32 for n <= 512; a count that did not would fail the call), the second copies it out: vertices
+ * (V, 3) float32, normals (V, 3) float32 or NULL, triangles (T, 3) int32; `mem` says where the call's own arrays live.  The
+ * mesh stays until the next first call (which replaces it, and leaves none if it fails) or nerf_ctx_destroy; a fetch without
+ * one fails ("no pending mesh").  With 0 vertices the fetch succeeds and writes nothing. */
+int nerf_isosurface(nerf_ctx* ctx, const float* sigma, int32_t n, const float* lo3, const float* hi3, float iso,
+                    int64_t* n_vertices, int64_t* n_triangles, int mem);
+int nerf_isosurface_fetch(nerf_ctx* ctx, float* vertices, float* normals, int32_t* triangles, int mem);
+/* nerf_mesh_colors: network `which` at V vertices, seen against their normals -- view direction -normal, a ray that sees the
+ * surface travels against its normal; a zero normal uses (0, 0, 1) -- through the sigmoid nerf_ray_marching applies for
+ * rgb_samples.  vertices, normals, rgb: (V, 3).  The directions are ignored for n_angles == 0. */
+int nerf_mesh_colors(nerf_ctx* ctx, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of

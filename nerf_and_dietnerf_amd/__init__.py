@@ -27,6 +27,7 @@ from .video import (get_c2w_matrices_between_2_c2w, get_c2w_matrices_between_2_c
                     get_rotation_matrix_from_source_to_dest_mats, interpolation_type_slerp_for_c2w,
                     slerp_rotation_matrix, get_l_to_r_c2w_matrices, get_sphere_matrices, get_sphere_matrix, histogram_equalize_depth,
                     render_video)
+from .mesh import read_ply, write_ply
 from .weights import blob_size, glorot_blob, layer_shapes
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -57,6 +57,10 @@ SYMBOLS = [
     ("nerf_ctx_set_occupancy_grid", C.c_int, [_P, _P, _I32]),
     ("nerf_ctx_get_occupancy_grid", C.c_int, [_P, _P, _P]),
     ("nerf_occupancy_bake", C.c_int, [_P, C.c_int, _I32, _F, _I32, _I32, _U64, _P]),
+    ("nerf_density_lattice", C.c_int, [_P, C.c_int, _I32, _P, _P, C.c_int]),
+    ("nerf_isosurface", C.c_int, [_P, _P, _I32, _P, _P, _F, C.POINTER(_I64), C.POINTER(_I64), C.c_int]),
+    ("nerf_isosurface_fetch", C.c_int, [_P, _P, _P, _P, C.c_int]),
+    ("nerf_mesh_colors", C.c_int, [_P, C.c_int, _P, _P, _I64, _P, C.c_int]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     ("nerf_get_rays_directions", C.c_int, [_P, _P, _F, _I32, _I32, _P, C.c_int]),

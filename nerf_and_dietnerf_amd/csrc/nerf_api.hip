@@ -450,7 +450,9 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     (void)hipSetDevice(c->cfg.device);
     (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->b_orig, &c->b_dirs, &c->b_zc, &c->b_zf, &c->b_raw, &c->b_wc, &c->b_u0, &c->b_u1,
-                      &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate};
+                      &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate,
+                      &c->b_mesh_v, &c->b_mesh_n, &c->b_mesh_t, &c->b_mesh_sigma, &c->b_mesh_mask, &c->b_mesh_first,
+                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);
     for (auto& n : c->net) {
@@ -599,6 +601,85 @@ int nerf_occupancy_bake(nerf_ctx* c, int which, int32_t R, float sigma_threshold
     }
     c->grid_cur = cur;
     c->grid_R = R;
+    return 0;
+}
+
+// ---- mesh extraction: the network on the lattice and at the vertices (the isosurface itself: mesh_kernels.hip) ----
+static constexpr long long kMeshChunk = 1LL << 20;   // points per pass through the network, as the bake
+
+int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_dir3, float* sigma, int mem) {
+    ENTER(c);
+    if (!sigma) return fail("NULL argument");
+    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
+    if (!c->box_on) return fail("a density lattice needs a scene box (nerf_ctx_set_scene_box)");
+    if (n < 2 || n > 512) return fail("density lattice: n must be in 2..512 (got %d)", n);
+    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    const float up[3] = {0.f, 0.f, 1.f};
+    const float* vd = view_dir3 ? view_dir3 : up;
+    const long long points = (long long)n * n * n;
+    const size_t pts = (size_t)std::min(points, kMeshChunk);
+    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
+    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
+    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
+    float* out = sigma;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = ensure(c, c->b_lattice, (size_t)points * 4)) return r;
+        out = (float*)c->b_lattice.p;
+    }
+    float *xyz = (float*)c->b_in0.p, *view = c->cfg.n_angles != 0 ? (float*)c->b_in1.p : nullptr, *raw = (float*)c->b_raw.p;
+    for (long long begin = 0; begin < points; begin += kMeshChunk) {
+        const long long m = std::min(kMeshChunk, points - begin);
+        launch_lattice_points(c->box, n, begin, m, vd, xyz, view, c->stream);
+        if (int r = run_mlp(c, which, k, xyz, view, nullptr, raw, m, 1, 1)) return r;
+        launch_raw_sigma(raw, m, out + begin, c->stream);
+    }
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(sigma, out, (size_t)points * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem) {
+    ENTER(c);
+    if (V < 0) return fail("bad V");
+    if (V == 0) return 0;
+    if (!vertices || !normals || !rgb) return fail("NULL argument");
+    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
+    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    const size_t pts = (size_t)std::min((long long)V, kMeshChunk);
+    const bool host = mem == NERF_MEM_HOST;
+    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
+    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
+    if (host) {
+        if (int r = ensure(c, c->b_in0, pts * 12)) return r;
+        if (int r = ensure(c, c->b_in2, pts * 12)) return r;
+        if (int r = ensure(c, c->b_out[0], pts * 12)) return r;
+    }
+    float *view = (float*)c->b_in1.p, *raw = (float*)c->b_raw.p;
+    for (long long begin = 0; begin < V; begin += kMeshChunk) {
+        const long long m = std::min(kMeshChunk, (long long)V - begin);
+        const float *xyz = vertices + 3 * begin, *nrm = normals + 3 * begin;
+        float* out = rgb + 3 * begin;
+        if (host) {
+            HIP_OK(hipMemcpyAsync(c->b_in0.p, xyz, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
+            HIP_OK(hipMemcpyAsync(c->b_in2.p, nrm, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
+            xyz = (const float*)c->b_in0.p; nrm = (const float*)c->b_in2.p; out = (float*)c->b_out[0].p;
+        }
+        launch_mesh_view(nrm, m, view, c->stream);
+        if (int r = run_mlp(c, which, k, xyz, c->cfg.n_angles != 0 ? view : nullptr, nullptr, raw, m, 1, 1)) return r;
+        launch_raw_rgb(raw, m, out, c->stream);
+        HIP_OK(hipGetLastError());
+        if (host) {
+            HIP_OK(hipMemcpyAsync(rgb + 3 * begin, out, (size_t)m * 12, hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));
+        }
+    }
     return 0;
 }
 

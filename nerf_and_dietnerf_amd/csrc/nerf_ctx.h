@@ -48,6 +48,12 @@ struct nerf_ctx {
     int grid_cur = 0;                          // which of b_grid holds it; the other is the dilation's second array
     nerf::DevBuf b_grid[2];                    // grid_R^3 / 32 words each
     nerf::DevBuf b_gbounds, b_gstate;          // per-ray (a, b) and state of draw_z_values under a grid (grow-only)
+    // mesh extraction (mesh_kernels.hip): the pending mesh of nerf_isosurface and its scratch, all grow-only
+    bool mesh_on = false;
+    long long mesh_V = 0, mesh_T = 0;
+    nerf::DevBuf b_mesh_v, b_mesh_n, b_mesh_t;                             // vertices, normals, triangles
+    nerf::DevBuf b_mesh_sigma, b_mesh_mask, b_mesh_first, b_mesh_count, b_mesh_tfirst, b_mesh_sums;
+    nerf::DevBuf b_lattice;                    // nerf_density_lattice(NERF_MEM_HOST): the volume before it leaves
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;

@@ -251,6 +251,14 @@ void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long l
 void launch_grid_threshold(const float* raw, long long cell_begin, long long n_cells, int spc, float threshold,
                            uint32_t* bits, hipStream_t stream);
 void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t stream);
+// mesh_kernels.hip: points [begin, begin + count) of the n^3 lattice over the box (x fastest) and as many copies of view_dir
+// (view nullable); column 3 of raw (count, 4); the view directions -normal ((0, 0, 1) for a zero normal); the sigmoid of
+// columns 0..2 of raw (count, 4)
+void launch_lattice_points(const SceneBox& box, int n, long long begin, long long count, const float view_dir[3], float* xyz,
+                           float* view, hipStream_t stream);
+void launch_raw_sigma(const float* raw, long long count, float* sigma, hipStream_t stream);
+void launch_mesh_view(const float* normals, long long count, float* view, hipStream_t stream);
+void launch_raw_rgb(const float* raw, long long count, float* rgb, hipStream_t stream);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                        uint64_t seed, long long ray_base, float* z_new, float* z_merged,

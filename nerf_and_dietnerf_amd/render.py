@@ -419,6 +419,78 @@ class Context:
         self.grid_resolution = r
         return int(count.value)
 
+    # ---- mesh extraction: density lattice -> isosurface -> vertex colours (include/nerf_mi355.h: nerf_isosurface has the rule) ----
+    def density_lattice(self, which, n, view_dir=None, device_out=False):
+        """Raw sigma of network ``which`` (0 coarse, 1 fine) at the n^3 lattice points of the scene box, n in 2..512, in the
+        context's precision: an (n, n, n) float32 array indexed [iz, iy, ix] (x fastest), the sigma column of model_predict at
+        the points lo + step * i, step = (hi - lo) / (n - 1).  ``view_dir``: three numbers, the view direction of every point
+        (default (0, 0, 1), the bake's; ignored for n_angles == 0).  The result is a numpy array, or a torch-device tensor if
+        ``view_dir`` is one or ``device_out`` is set."""
+        if self.scene_box is None:
+            raise RuntimeError("a density lattice needs a scene box (set_scene_box)")
+        n = int(n)
+        if not 2 <= n <= 512:
+            raise ValueError(f"density lattice: n must be in 2..512 (got {n})")
+        if device_out and not (_is_torch(view_dir) and view_dir.is_cuda):
+            import torch
+            arr = self._arrays(torch.empty(1, device=torch.device("cuda", self.cfg.device)))   # torch's current stream
+        else:
+            arr = self._arrays(view_dir)
+        pv = None
+        if view_dir is not None:
+            vd = np.ascontiguousarray(view_dir.detach().cpu().numpy() if _is_torch(view_dir) else view_dir, dtype=np.float32).ravel()
+            if vd.shape != (3,):
+                raise ValueError(f"view_dir must have 3 components, got {vd.shape[0]}")
+            pv = vd.ctypes.data
+
+        def run():
+            out, p = arr.out((n, n, n))
+            _lib.check(self.lib.nerf_density_lattice(self.h, int(which), n, pv, p, arr.mem))
+            return out
+        return self._auto_call(run, arr.mem)
+
+    def isosurface(self, sigma, lo, hi, iso, normals=True):
+        """The surface sigma = iso of an (n, n, n) volume indexed [iz, iy, ix] over the box (lo, hi), n in 2..512, by marching
+        tetrahedra on the device -> (vertices (V, 3) float32, triangles (T, 3) int32, normals (V, 3) float32 or None), numpy or
+        torch-device arrays as ``sigma`` is.  Inside is sigma > iso; triangles are counter-clockwise seen from the outside and
+        normals point from inside to outside (-gradient).  The numbering is canonical (nerf_isosurface has the rule)."""
+        arr = self._arrays(sigma)
+        shape = tuple(sigma.shape)
+        if len(shape) != 3 or shape[0] != shape[1] or shape[0] != shape[2]:
+            raise ValueError(f"sigma must be an (n, n, n) array, got {shape}")
+        n = shape[0]
+        ps = arr.inp(sigma, shape)
+        lo_a, hi_a = np.asarray(lo, np.float32).ravel(), np.asarray(hi, np.float32).ravel()
+        if lo_a.shape != (3,) or hi_a.shape != (3,):
+            raise ValueError(f"box corners must have 3 components each, got {lo_a.shape[0]} and {hi_a.shape[0]}")
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.nerf_isosurface(self.h, ps, n, lo_a.ctypes.data, hi_a.ctypes.data, float(iso), C.byref(nv),
+                                            C.byref(nt), arr.mem))
+        v, t = int(nv.value), int(nt.value)
+        vertices, pvx = arr.out((v, 3))
+        nrm, pn = arr.out((v, 3)) if normals else (None, None)
+        if arr.torch is not None:
+            triangles = arr.torch.empty((t, 3), dtype=arr.torch.int32, device=arr.device)
+            pt = triangles.data_ptr()
+        else:
+            triangles = np.empty((t, 3), np.int32)
+            pt = triangles.ctypes.data
+        _lib.check(self.lib.nerf_isosurface_fetch(self.h, pvx, pn, pt, arr.mem))
+        return vertices, triangles, nrm
+
+    def mesh_colors(self, which, vertices, normals):
+        """Network ``which`` at the vertices (V, 3), each seen against its normal (view direction -normal; (0, 0, 1) for a
+        zero normal): (V, 3) colours in [0, 1], the sigmoid ray_marching applies.  numpy or torch-device arrays."""
+        arr = self._arrays(vertices, normals)
+        v = int(vertices.shape[0])
+        pvx, pn = arr.inp(vertices, (v, 3)), arr.inp(normals, (v, 3))
+
+        def run():
+            out, p = arr.out((v, 3))
+            _lib.check(self.lib.nerf_mesh_colors(self.h, int(which), pvx, pn, v, p, arr.mem))
+            return out
+        return self._auto_call(run, arr.mem)
+
     def ray_occupancy_bounds(self, rays_orig, rays_dirs):
         """Rays (N,4) -> (bounds (N,2) float32, state (N,) int32) under the context's box, grid and bounds: state 2 and the
         grid's interval, state 1 and the box's for a ray only the box narrows, state 0 and (near, far) for any other
@@ -996,6 +1068,38 @@ class NeRF:
         which = NERF_NET_FINE if self.model_fine is not None and self.ctx.loaded[NERF_NET_FINE] else NERF_NET_COARSE
         return self.ctx.bake_occupancy_grid(which, g[GRID_RESOLUTION], g[GRID_SIGMA_THRESHOLD], g[GRID_SAMPLES_PER_CELL],
                                             g[GRID_DILATE], seed)
+
+    def extract_mesh(self, resolution: int = 128, sigma_threshold: float = 50.0, which: Optional[int] = None, colors: bool = True,
+                     path=None) -> Dict[str, np.ndarray]:
+        """The scene as a triangle mesh: the density of network ``which`` (None: the fine network if it is loaded, else the
+        coarse one) on a ``resolution``^3 lattice over render_config["scene_box"], its isosurface at ``sigma_threshold``
+        (raw sigma, the unit of the occupancy grid's threshold), and per-vertex colours seen against the normals.  Returns
+        numpy arrays: "vertices" (V, 3) float32, "normals" (V, 3) float32 (unit, pointing out of the density; zero where the
+        gradient vanishes), "triangles" (T, 3) int32 (counter-clockwise from outside) and, with ``colors``, "colors" (V, 3)
+        float32 in [0, 1].  ``path``: also write a binary little-endian PLY there (mesh.write_ply).  The mesh is closed
+        except where the surface leaves the box."""
+        if self.scene_box is None:
+            raise ValueError(f"extract_mesh needs render_config[{SCENE_BOX!r}]")
+        if which is None:
+            which = NERF_NET_FINE if self.model_fine is not None and self.ctx.loaded[NERF_NET_FINE] else NERF_NET_COARSE
+        try:
+            import torch
+            on_device = torch.cuda.is_available()
+        except ImportError:
+            on_device = False
+        sigma = self.ctx.density_lattice(which, resolution, device_out=on_device)      # the volume stays on the device
+        vertices, triangles, normals = self.ctx.isosurface(sigma, self.scene_box[0], self.scene_box[1], sigma_threshold)
+        rgb = self.ctx.mesh_colors(which, vertices, normals) if colors else None
+        if on_device and self.ctx.auto_check():          # precision "auto": the f16x3 pass overflowed, the context is in fp32 now
+            return self.extract_mesh(resolution, sigma_threshold, which, colors, path)
+        host = (lambda x: x.cpu().numpy()) if on_device else (lambda x: x)
+        mesh = {"vertices": host(vertices), "normals": host(normals), "triangles": host(triangles)}
+        if colors:
+            mesh["colors"] = host(rgb)
+        if path is not None:
+            from .mesh import write_ply
+            write_ply(path, mesh["vertices"], mesh["triangles"], mesh["normals"], mesh.get("colors"))
+        return mesh
 
     def occupancy_grid_epoch(self) -> None:
         """dataset.fit's hook, at the start of every epoch: the grid is off during the warm-up epochs and baked again every
