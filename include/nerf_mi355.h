@@ -272,6 +272,31 @@ int nerf_ray_box_bounds(nerf_ctx* ctx, const float* rays_orig, const float* rays
  * NULL.  Fails without a grid. */
 int nerf_ray_occupancy_bounds(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
                               int32_t* state, int mem);
+/* ABI 6+, sample culling: under an occupancy grid, the samples of a render pass that lie in EMPTY cells skip the network.
+ * Off by default.  The flag may be set with or without a grid and acts only while the ctx holds one; dropping the grid (a new
+ * box, nerf_ctx_set_occupancy_grid(NULL, 0)) leaves the flag as it is.  The rule for sample (ray, s), in float32, every
+ * operation rounded on its own (no FMA), comparisons instead of fmin / fmax:
+ *   1. p_a = o_a + d_a z, multiply then add: the point the network kernels form themselves.
+ *   2. inside = lo_a <= p_a <= hi_a on all three axes; a NaN compares false, so the sample is not inside.
+ *   3. i_a = clamp(floor((p_a - lo_a) / cell_a), 0, R - 1), cell_a = (hi_a - lo_a) / R (step 2 of the grid rule): a point on
+ *      the hi face belongs to cell R - 1, a point on an interior cell face to the upper cell.
+ *   4. the sample is CULLED iff inside and bit i_x + R (i_y + R i_z) is 0.  Every other sample is KEPT: the grid knows
+ *      nothing outside the box, and a ray that misses the box renders as before, bit for bit.
+ * A culled sample has the raw network output (0, 0, 0, 0): alpha and weight exactly 0, the transmittance untouched,
+ * rgb_samples = sigmoid(0).  The kept samples run through the same network kernels as compacted rows in ascending sample
+ * index (no atomics: the result does not depend on the launch).  The host reads the row count of every pass (one 4-byte copy
+ * and a stream synchronise per network pass), so a culled render call is not asynchronous.  A culled pass counts its rows in
+ * 32 bits: a nerf_render_rays / nerf_render call with N * S above 2^31 - 1 samples in one pass fails under the flag where it
+ * would run without it (nerf_render_image batches its rays and stays far below).
+ * nerf_render_rays, nerf_render, nerf_render_image and the sharded calls follow the flag.  nerf_train_* (one-call and slot
+ * paths, so DietNeRF's consistency render too) IGNORE it: no backward pass through the compaction exists. */
+int nerf_ctx_set_sample_culling(nerf_ctx* ctx, int on);
+/* The verdict of that rule for N rays x S depths z (N,S), from the device function the render path calls: keep (N,S) int32,
+ * 1 kept / 0 culled.  Fails without a grid. */
+int nerf_sample_occupancy(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, const float* z, int64_t N, int32_t S,
+                          int32_t* keep, int mem);
+/* Samples seen and samples kept, summed over all culled network passes since the last call (either may be NULL); clears both. */
+int nerf_ctx_read_culling(nerf_ctx* ctx, int64_t* samples, int64_t* kept);
 /* get_z_vals_from_prob_dist_func, src/UtilsCV.py:502-539.  weights,z (N,S); u (N,Sf) or NULL;
  * z_new (N,Sf) sorted.  If z_merged != NULL also writes sort(concat(z_new,z)) (N,S+Sf)
  * (src/NeRF.py:132). */
@@ -475,6 +500,12 @@ int nerf_get_weights(nerf_ctx* ctx, int which, float* blob, size_t n_floats, int
  * since the last read, and resets the counters. */
 int nerf_ctx_enable_timing(nerf_ctx* ctx, int on);
 int nerf_ctx_read_timing(nerf_ctx* ctx, double* mlp_ms, int64_t* n_launches, int64_t* n_rows);
+/* With timing on, the culled passes' own stages by stream events, summed since the last call (synchronises, then clears):
+ * ms4[0] verdict + scan, [1] the host's read of the row count (copy, synchronise, growing the compact buffers), [2] gather,
+ * [3] expand; the network itself is nerf_ctx_read_timing's.  *n_passes (nullable) = the culled passes counted.
+ * nerf_ctx_read_timing and nerf_ctx_enable_timing clear these events as well, so a caller who never asks for them keeps
+ * nothing: to have both, call this one first. */
+int nerf_ctx_read_culling_timing(nerf_ctx* ctx, double* ms4, int64_t* n_passes);
 
 #ifdef __cplusplus
 }

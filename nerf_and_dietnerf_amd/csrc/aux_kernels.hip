@@ -307,6 +307,9 @@ void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S
 // asked for, as the box rule asks it of a hit), or whose occupied stretch is all of [a0, b0], is left to the box rule: nothing
 // is ever left unsampled, and a full grid is the box alone, bit for bit.
 // The cell index is held in [0, R) wherever the bits are read.
+// The verdict on a single sample under the same grid (step 2's cell of the sample's own point) is sample_kept, in
+// cull_kernels.hip beside the kernels that call it: device functions do not cross translation units in this build, so the
+// cell index the two share is nerf_device.h's grid_cell_index.
 // ------------------------------------------------------------------------------------------------
 struct GridArgs {
     BoxArgs bx;
@@ -335,8 +338,7 @@ __device__ __forceinline__ int ray_grid_interval(const GridArgs& g, const float4
     for (int ax = 0; ax < 3; ++ax) {
         cell[ax] = __fdiv_rn(__fsub_rn(bx.hi[ax], bx.lo[ax]), (float)R);
         const float p = __fadd_rn(oo[ax], __fmul_rn(a0, dd[ax]));
-        const float f = floorf(__fdiv_rn(__fsub_rn(p, bx.lo[ax]), cell[ax]));
-        idx[ax] = f >= 0.0f ? (f <= (float)(R - 1) ? (int)f : R - 1) : 0;      // NaN -> 0
+        idx[ax] = grid_cell_index(p, bx.lo[ax], cell[ax], R);                   // NaN -> 0
         step[ax] = dd[ax] > 0.0f ? 1 : -1;
         plane[ax] = idx[ax] + (dd[ax] > 0.0f ? 1 : 0);
         tp[ax] = dd[ax] == 0.0f ? __builtin_huge_valf() : grid_plane(bx.lo[ax], cell[ax], plane[ax], oo[ax], dd[ax]);

@@ -396,6 +396,12 @@ int read_total(nerf_ctx* c, const uint32_t* dev, const char* what, long long* ou
 
 }  // namespace
 
+// the scan above for the other translation units (cull_kernels.hip's bit mask): POPC items
+size_t scan_sums_words(long long N) { return (size_t)((N + kScanTile - 1) / kScanTile); }
+void launch_scan_popc(const uint8_t* in, long long N, uint32_t* sums, uint32_t* out, uint32_t* total_dev, hipStream_t stream) {
+    launch_scan<true>(in, N, sums, out, total_dev, stream);
+}
+
 void launch_lattice_points(const SceneBox& box, int n, long long begin, long long count, const float view_dir[3], float* xyz,
                            float* view, hipStream_t stream) {
     if (count <= 0) return;

@@ -344,6 +344,76 @@ int copy_back_batch(nerf_ctx* c, const nerf_outputs* host, const nerf_outputs* d
     return 0;
 }
 
+// with timing on: the next event of the culled passes' pool (six per pass, read by nerf_ctx_read_culling_timing)
+int cull_stamp(nerf_ctx* c) {
+    if (!c->timing) return 0;
+    if (c->cull_ev_used == c->cull_ev.size()) {
+        hipEvent_t e;
+        HIP_OK(hipEventCreate(&e));
+        c->cull_ev.push_back(e);
+    }
+    HIP_OK(hipEventRecord(c->cull_ev[c->cull_ev_used++], c->stream));
+    return 0;
+}
+
+// network_pass under sample culling (cull_kernels.hip): verdict bits -> scan -> the row count M, read
+// by the host because the fused kernels take it by value -> the kept samples' points as M mode-1 rows -> the same kernel
+// pick_render_kernel gives the unculled pass -> the full raw (or sigma) buffer with zeros for the culled samples.
+int culled_mlp(nerf_ctx* c, int which, const RenderKernel& k, const float* o, const float* d, const float* z, long long N, int S,
+               float* raw) {
+    const long long total = N * S;
+    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);      // run_mlp's, also when M == 0
+    if (total > (long long)INT32_MAX) return fail("sample culling: %lld samples in one pass do not fit int32", total);
+    const long long words = (total + 63) / 64, mask_bytes = words * 8;
+    const size_t tiles = scan_sums_words(mask_bytes);
+    if (int r = ensure(c, c->b_cmask, (size_t)mask_bytes)) return r;
+    if (int r = ensure(c, c->b_cfirst, (size_t)mask_bytes * 4)) return r;
+    if (int r = ensure(c, c->b_csums, (tiles + 1) * 4)) return r;
+    if (!c->cull_rows) HIP_OK(hipHostMalloc((void**)&c->cull_rows, sizeof(uint32_t), hipHostMallocDefault));
+    const uint8_t* mask = (const uint8_t*)c->b_cmask.p;
+    uint32_t *first = (uint32_t*)c->b_cfirst.p, *sums = (uint32_t*)c->b_csums.p;
+    if (int r = cull_stamp(c)) return r;
+    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, d, z, N, S, (uint64_t*)c->b_cmask.p,
+                       nullptr, c->stream);
+    launch_scan_popc(mask, mask_bytes, sums, first, sums + tiles, c->stream);
+    HIP_OK(hipGetLastError());
+    if (int r = cull_stamp(c)) return r;
+    HIP_OK(hipMemcpyAsync(c->cull_rows, sums + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const long long M = *c->cull_rows;
+    if (M > total) return fail("internal: sample culling kept %lld of %lld samples", M, total);
+    c->cull_samples += total;
+    c->cull_kept += M;
+    const size_t row = k.sigma_only ? 4 : 16;
+    const bool with_dirs = c->cfg.n_angles != 0;
+    if (M > 0) {      // the compact buffers follow M, not N * S
+        if (int r = ensure(c, c->b_cxyz, (size_t)M * 12)) return r;
+        if (with_dirs) if (int r = ensure(c, c->b_cdirs, (size_t)M * 12)) return r;
+        if (int r = ensure(c, c->b_craw, (size_t)M * row)) return r;
+    }
+    if (int r = cull_stamp(c)) return r;
+    if (M > 0) {
+        float *xyz = (float*)c->b_cxyz.p, *view = with_dirs ? (float*)c->b_cdirs.p : nullptr;
+        launch_sample_gather(o, d, z, N, S, mask, first, xyz, view, c->stream);
+        if (int r = cull_stamp(c)) return r;
+        if (int r = run_mlp(c, which, k, xyz, view, nullptr, (float*)c->b_craw.p, M, 1, 1)) return r;
+    } else if (int r = cull_stamp(c)) return r;
+    if (int r = cull_stamp(c)) return r;
+    launch_raw_expand((const float*)c->b_craw.p, total, k.sigma_only, mask, first, raw, c->stream);
+    return cull_stamp(c);
+}
+
+// The network pass of dev_render_rays: raw (N*S, 4) -- sigma_only: (N*S,) -- of every sample.  Under sample culling (on, and
+// the ctx holds a grid) it is culled_mlp's; otherwise the one mode-0 launch it always was.
+int network_pass(nerf_ctx* c, int which, const RenderKernel& k, const float* o, const float* d, const float* z, long long N, int S,
+                 float* raw) {
+    if (!(c->cull_on && c->box_on && c->grid_R > 0 && N > 0)) return run_mlp(c, which, k, o, d, z, raw, N * S, S, 0);
+    const size_t ev0 = c->cull_ev_used;
+    const int r = culled_mlp(c, which, k, o, d, z, N, S, raw);
+    if (r) c->cull_ev_used = ev0;                                  // the stage events count whole passes only
+    return r;
+}
+
 // render_rays on device pointers
 // A coarse pass whose only output is the weights (the coarse pass of NeRF.render) runs the sigma-only network and the
 // weights-only composite where pick_render_kernel has one: the weights depend on sigma alone and come out bit-identical.
@@ -356,14 +426,14 @@ int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, cons
     if (k.sigma_only) {
         if (int r = ensure(c, c->b_raw, (size_t)N * S * sizeof(float))) return r;
         float* sigma = (float*)c->b_raw.p;
-        if (int r = run_mlp(c, which, k, o, d, z, sigma, N * S, S, 0)) return r;
+        if (int r = network_pass(c, which, k, o, d, z, N, S, sigma)) return r;
         launch_composite_weights(sigma, z, N, S, outs.weights, c->stream);
         HIP_OK(hipGetLastError());
         return 0;
     }
     if (int r = ensure(c, c->b_raw, (size_t)N * S * 4 * sizeof(float))) return r;
     float* raw = (float*)c->b_raw.p;
-    if (int r = run_mlp(c, which, k, o, d, z, raw, N * S, S, 0)) return r;
+    if (int r = network_pass(c, which, k, o, d, z, N, S, raw)) return r;
     launch_composite(raw, z, N, S, outs.rgb, outs.weights, outs.cumprod, outs.alpha, outs.rgb_samples, outs.depth,
                      c->stream);
     if (outs.z && outs.z != z)
@@ -452,7 +522,8 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     DevBuf* bufs[] = {&c->b_orig, &c->b_dirs, &c->b_zc, &c->b_zf, &c->b_raw, &c->b_wc, &c->b_u0, &c->b_u1,
                       &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate,
                       &c->b_mesh_v, &c->b_mesh_n, &c->b_mesh_t, &c->b_mesh_sigma, &c->b_mesh_mask, &c->b_mesh_first,
-                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice};
+                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice, &c->b_cmask, &c->b_cfirst,
+                      &c->b_csums, &c->b_cxyz, &c->b_cdirs, &c->b_craw};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);
     for (auto& n : c->net) {
@@ -462,6 +533,8 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (hipEvent_t e : c->copy_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->cull_ev) (void)hipEventDestroy(e);
+    if (c->cull_rows) (void)hipHostFree(c->cull_rows);
     comm_free(c);
     train_free(c);
     if (c->nonfinite) (void)hipFree(c->nonfinite);
@@ -847,6 +920,66 @@ int nerf_ray_occupancy_bounds(nerf_ctx* c, const float* rays_orig, const float* 
     return 0;
 }
 
+// ---- sample culling (cull_kernels.hip) ----
+int nerf_ctx_set_sample_culling(nerf_ctx* c, int on) {
+    if (!c) return fail("ctx is NULL");
+    c->cull_on = on != 0;
+    return 0;
+}
+
+int nerf_sample_occupancy(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, const float* z, int64_t N, int32_t S,
+                          int32_t* keep, int mem) {
+    ENTER(c);
+    if (!rays_orig || !rays_dirs || !z || !keep) return fail("NULL argument");
+    if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
+    if (!c->box_on || c->grid_R == 0) return fail("no occupancy grid is set (nerf_ctx_set_occupancy_grid, nerf_occupancy_bake)");
+    if (N == 0) return 0;
+    const float *o = rays_orig, *d = rays_dirs, *dz = z;
+    int32_t* dk = keep;
+    if (mem == NERF_MEM_HOST) {
+        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
+        if (int r = h2d(c, c->b_zc, z, (size_t)N * S * 4)) return r;
+        if (int r = ensure(c, c->b_in0, (size_t)N * S * 4)) return r;
+        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; dz = (const float*)c->b_zc.p; dk = (int32_t*)c->b_in0.p;
+    }
+    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, d, dz, N, S, nullptr, dk, c->stream);
+    HIP_OK(hipGetLastError());
+    if (mem == NERF_MEM_HOST) {
+        HIP_OK(hipMemcpyAsync(keep, dk, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int nerf_ctx_read_culling(nerf_ctx* c, int64_t* samples, int64_t* kept) {
+    if (!c) return fail("ctx is NULL");
+    if (samples) *samples = c->cull_samples;
+    if (kept) *kept = c->cull_kept;
+    c->cull_samples = c->cull_kept = 0;
+    return 0;
+}
+
+int nerf_ctx_read_culling_timing(nerf_ctx* c, double* ms4, int64_t* n_passes) {
+    if (!c) return fail("ctx is NULL");
+    HIP_OK(hipStreamSynchronize(c->stream));
+    double tot[4] = {0, 0, 0, 0};
+    const size_t passes = c->cull_ev_used / 6;
+    for (size_t p = 0; p < passes; ++p) {
+        const hipEvent_t* e = &c->cull_ev[6 * p];
+        const int pair[4][2] = {{0, 1}, {1, 2}, {2, 3}, {4, 5}};
+        for (int i = 0; i < 4; ++i) {
+            float ms = 0;
+            HIP_OK(hipEventElapsedTime(&ms, e[pair[i][0]], e[pair[i][1]]));
+            tot[i] += ms;
+        }
+    }
+    if (ms4) for (int i = 0; i < 4; ++i) ms4[i] = tot[i];
+    if (n_passes) *n_passes = (int64_t)passes;
+    c->cull_ev_used = 0;
+    return 0;
+}
+
 int nerf_sample_pdf(nerf_ctx* c, const float* weights, const float* z, int64_t N, int32_t S, int32_t Sf,
                     const float* u, uint64_t seed, int64_t ray_base, float* z_new, float* z_merged, int mem) {
     ENTER(c);
@@ -1079,6 +1212,7 @@ int nerf_ctx_enable_timing(nerf_ctx* c, int on) {
     HIP_OK(hipStreamSynchronize(c->stream));
     c->timing = on != 0;
     c->ev_used = 0;
+    c->cull_ev_used = 0;
     c->timed_rows = 0;
     return 0;
 }
@@ -1097,6 +1231,7 @@ int nerf_ctx_read_timing(nerf_ctx* c, double* mlp_ms, int64_t* n_launches, int64
     if (n_rows) *n_rows = c->timed_rows;
     c->ev_used = 0;
     c->timed_rows = 0;
+    c->cull_ev_used = 0;      // the culled passes' stage events belong to the same span: nerf_ctx_read_culling_timing comes first
     return 0;
 }
 

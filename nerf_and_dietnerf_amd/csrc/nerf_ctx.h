@@ -48,6 +48,14 @@ struct nerf_ctx {
     int grid_cur = 0;                          // which of b_grid holds it; the other is the dilation's second array
     nerf::DevBuf b_grid[2];                    // grid_R^3 / 32 words each
     nerf::DevBuf b_gbounds, b_gstate;          // per-ray (a, b) and state of draw_z_values under a grid (grow-only)
+    // sample culling (cull_kernels.hip): nerf_ctx_set_sample_culling; it acts only while the ctx holds a grid
+    bool cull_on = false;
+    long long cull_samples = 0, cull_kept = 0; // totals over the culled passes since nerf_ctx_read_culling
+    uint32_t* cull_rows = nullptr;             // page-locked word the row count M of a pass is copied to
+    nerf::DevBuf b_cmask, b_cfirst, b_csums;   // verdict bits, slot per mask byte, the scan's tile sums + total (grow-only)
+    nerf::DevBuf b_cxyz, b_cdirs, b_craw;      // the M compact rows: points, directions, raw (sized after M is known)
+    std::vector<hipEvent_t> cull_ev;           // with timing on, six per culled pass: verdict+scan | read M | gather | (MLP) | expand
+    size_t cull_ev_used = 0;
     // mesh extraction (mesh_kernels.hip): the pending mesh of nerf_isosurface and its scratch, all grow-only
     bool mesh_on = false;
     long long mesh_V = 0, mesh_T = 0;

@@ -96,4 +96,14 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ray, int
     return bits_to_uniform(e == 0 ? r.x : e == 1 ? r.y : e == 2 ? r.z : r.w);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Occupancy grid: the cell of coordinate p on one axis of an R-cell grid that starts at lo with cells of width cell,
+// clamp(floor((p - lo) / cell), 0, R - 1) in float32, every operation rounded on its own; a NaN gives 0.  The one statement of
+// step 2 of the grid rule: ray_grid_interval (aux_kernels.hip) and sample_kept (cull_kernels.hip) both call it.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int grid_cell_index(float p, float lo, float cell, int R) {
+    const float f = floorf(__fdiv_rn(__fsub_rn(p, lo), cell));
+    return f >= 0.0f ? (f <= (float)(R - 1) ? (int)f : R - 1) : 0;
+}
+
 }  // namespace nerf

@@ -259,6 +259,20 @@ void launch_lattice_points(const SceneBox& box, int n, long long begin, long lon
 void launch_raw_sigma(const float* raw, long long count, float* sigma, hipStream_t stream);
 void launch_mesh_view(const float* normals, long long count, float* view, hipStream_t stream);
 void launch_raw_rgb(const float* raw, long long count, float* rgb, hipStream_t stream);
+// mesh_kernels.hip's exclusive scan for bit-mask items: out[i] = set bits of in[0..i), *total_dev = set bits of all N bytes;
+// sums: scratch of scan_sums_words(N) words.  No atomics: the result does not depend on the launch.
+size_t scan_sums_words(long long N);
+void launch_scan_popc(const uint8_t* in, long long N, uint32_t* sums, uint32_t* out, uint32_t* total_dev, hipStream_t stream);
+// cull_kernels.hip (sample culling under an occupancy grid: sample_kept has the rule).  mask: ceil(N S / 64) 64-bit words, bit
+// t = sample t is kept (nullable); verdict (N S) int32 1 / 0 (nullable).  first: launch_scan_popc of the mask's bytes.
+// gather: the kept samples' points (M,3) and ray directions (M,3; nullable) in ascending sample index; expand: raw (total,4)
+// -- sigma_only: (total,) -- from the M compact rows, zeros for a culled sample.
+void launch_sample_keep(const SceneBox& box, const uint32_t* bits, int R, const float* orig, const float* dirs, const float* z,
+                        long long N, int S, uint64_t* mask, int* verdict, hipStream_t stream);
+void launch_sample_gather(const float* orig, const float* dirs, const float* z, long long N, int S, const uint8_t* mask,
+                          const uint32_t* first, float* xyz, float* view, hipStream_t stream);
+void launch_raw_expand(const float* compact, long long total, bool sigma_only, const uint8_t* mask, const uint32_t* first,
+                       float* raw, hipStream_t stream);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                        uint64_t seed, long long ray_base, float* z_new, float* z_merged,

@@ -43,7 +43,9 @@ SCENE_BOX = "scene_box"              # [[x, y, z], [x, y, z]] (lo, hi), default 
 OCCUPANCY_GRID = "occupancy_grid"    # dict of the keys below, default absent: sample each ray where the network has density
 GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL = "resolution", "sigma_threshold", "samples_per_cell"
 GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS = "dilate", "update_every", "warmup_epochs"
-_GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS)
+GRID_CULL_SAMPLES = "cull_samples"    # bool, default False: samples in empty cells skip the network (Context.set_sample_culling)
+_GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS,
+              GRID_CULL_SAMPLES)
 GRID_NEEDS_BOX = "an occupancy grid needs a scene box"
 
 N_COORDINATES = 3
@@ -268,6 +270,7 @@ class Context:
         self.sampling, self.ray_space, self.ndc_near_plane = "linear", "world", 1.0   # what nerf_ctx_create leaves
         self.scene_box = None        # ((lo), (hi)) of set_scene_box
         self.grid_resolution = 0     # R of the occupancy grid (0: none)
+        self.sample_culling = False  # set_sample_culling
 
     def close(self):
         if getattr(self, "h", None):
@@ -507,6 +510,43 @@ class Context:
             ps = state.ctypes.data
         _lib.check(self.lib.nerf_ray_occupancy_bounds(self.h, po, pd, n, pb, ps, arr.mem))
         return bounds, state
+
+    # ---- sample culling under the grid (include/nerf_mi355.h: nerf_ctx_set_sample_culling has the rule) ----
+    def set_sample_culling(self, on) -> None:
+        """With a grid, the samples of a render pass that lie in empty cells skip the network and count as raw output
+        (0, 0, 0, 0); samples outside the box are kept.  Off by default; it may be set with or without a grid and acts only
+        while the context holds one.  render_rays, render, render_image and the sharded calls follow it; the trainer (and so
+        DietNeRF's consistency render) ignores it.  A culled call reads a row count per network pass: it synchronises."""
+        _lib.check(self.lib.nerf_ctx_set_sample_culling(self.h, int(bool(on))))
+        self.sample_culling = bool(on)
+
+    def sample_occupancy(self, rays_orig, rays_dirs, z_values):
+        """Rays (N,4), depths (N,S) -> the culling verdict (N,S) int32, 1 kept / 0 culled, under the context's box and grid
+        (nerf_sample_occupancy: the device function behind the render path)."""
+        arr = self._arrays(rays_orig, rays_dirs, z_values)
+        n, s = int(z_values.shape[0]), int(z_values.shape[1])
+        po, pd, pz = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4)), arr.inp(z_values, (n, s))
+        if arr.torch is not None:
+            keep = arr.torch.empty((n, s), dtype=arr.torch.int32, device=arr.device)
+            pk = keep.data_ptr()
+        else:
+            keep = np.empty((n, s), np.int32)
+            pk = keep.ctypes.data
+        _lib.check(self.lib.nerf_sample_occupancy(self.h, po, pd, pz, n, s, pk, arr.mem))
+        return keep
+
+    def read_culling(self) -> Tuple[int, int]:
+        """(samples, kept) summed over all culled network passes since the last call; clears both."""
+        samples, kept = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.nerf_ctx_read_culling(self.h, C.byref(samples), C.byref(kept)))
+        return samples.value, kept.value
+
+    def read_culling_timing(self) -> Tuple[Tuple[float, float, float, float], int]:
+        """With enable_timing: ((verdict + scan, host read of the row count, gather, expand) in ms, culled passes) since the
+        last call (synchronises); the network itself is read_timing's.  Call it BEFORE read_timing, which clears these too."""
+        ms, n = (C.c_double * 4)(), C.c_int64()
+        _lib.check(self.lib.nerf_ctx_read_culling_timing(self.h, ms, C.byref(n)))
+        return tuple(ms), n.value
 
     def ray_box_bounds(self, rays_orig, rays_dirs):
         """Rays (N,4) -> (bounds (N,2) float32, narrowed (N,) int32) under the context's box and bounds: (a, b) of a ray the
@@ -1029,6 +1069,8 @@ class NeRF:
         # occupancy grid: an absent key (or None) leaves everything as it was
         self.grid_config = self._grid_config(render_config.get(OCCUPANCY_GRID), self.scene_box)
         self._grid_epochs = 0        # epochs fit() has run: the grid's schedule counts them
+        if self.grid_config is not None and self.grid_config.get(GRID_CULL_SAMPLES, False):
+            self.ctx.set_sample_culling(True)
 
     @staticmethod
     def _grid_config(cfg, scene_box):
@@ -1054,6 +1096,10 @@ class NeRF:
             raise ValueError(f"{OCCUPANCY_GRID}: dilate must be 0, 1 or 2 (got {cfg[GRID_DILATE]!r})")
         if out[GRID_UPDATE_EVERY] < 1 or out[GRID_WARMUP_EPOCHS] < 0:
             raise ValueError(f"{OCCUPANCY_GRID}: update_every must be >= 1 and warmup_epochs >= 0")
+        if GRID_CULL_SAMPLES in cfg:       # without the key the config is what it was
+            if not isinstance(cfg[GRID_CULL_SAMPLES], (bool, np.bool_)):
+                raise ValueError(f"{OCCUPANCY_GRID}: {GRID_CULL_SAMPLES} must be a bool (got {cfg[GRID_CULL_SAMPLES]!r})")
+            out[GRID_CULL_SAMPLES] = bool(cfg[GRID_CULL_SAMPLES])
         return out
 
     def update_occupancy_grid(self, seed: int = 0) -> Optional[int]:
