@@ -289,8 +289,36 @@ int nerf_ray_occupancy_bounds(nerf_ctx* ctx, const float* rays_orig, const float
  * 32 bits: a nerf_render_rays / nerf_render call with N * S above 2^31 - 1 samples in one pass fails under the flag where it
  * would run without it (nerf_render_image batches its rays and stays far below).
  * nerf_render_rays, nerf_render, nerf_render_image and the sharded calls follow the flag.  nerf_train_* (one-call and slot
- * paths, so DietNeRF's consistency render too) IGNORE it: no backward pass through the compaction exists. */
+ * paths, so DietNeRF's consistency render too) IGNORE it: the trainer has a switch of its own,
+ * nerf_ctx_set_train_sample_culling. */
 int nerf_ctx_set_sample_culling(nerf_ctx* ctx, int on);
+/* ABI 6+, sample culling in the TRAINER: a separate switch, off by default, independent of nerf_ctx_set_sample_culling (which
+ * the trainer keeps ignoring).  It may be set with or without a grid and with or without a running trainer, acts only while
+ * the ctx holds a grid, survives the grid being dropped, and nerf_train_begin does not reset it.  Under it the network passes
+ * of every training entry point -- nerf_train_step (the data-parallel step included: ranks may keep different row counts, only
+ * the gradient blobs are reduced), nerf_train_gradients, nerf_train_render_gradients, nerf_train_render_forward / _backward
+ * and so DietNeRF's consistency render -- run on the kept samples only, forward and backward:
+ *   - The verdict for a sample is exactly steps 1-4 of nerf_ctx_set_sample_culling, from the same device function, evaluated
+ *     on the depths the pass actually runs on: the coarse depths; in nerf_train_step / nerf_train_gradients the Sf new fine
+ *     depths; in the render-gradient paths the Sc + Sf merged depths.
+ *   - A culled sample has the raw network output (0, 0, 0, 0) as a CONSTANT: it is never a network row, forward or backward,
+ *     contributes nothing to any weight gradient and nothing to dL/dz through the network input.  The verdict is piecewise
+ *     constant in z and carries no gradient.
+ *   - Compositing and its backward pass run on all N * S samples as without the flag; the compositing's own dL/dz terms
+ *     (through the deltas) stay.
+ *   - The kept samples are compacted rows in ascending sample index (no atomics).  Rows are independent in every kernel
+ *     involved, so under a grid that is full the losses and gradients are bit-identical to the flag being off.
+ *   - A pass keeps its compaction record (verdict bits, scan offsets, row count) with its activations: the backward half uses
+ *     exactly the rows the forward half made, and a slot of nerf_train_render_forward keeps the record as it keeps its depths
+ *     -- its backward pass does not depend on what the flag or the grid are by then.
+ *   - A pass that keeps no row launches no network kernel and contributes exact zeros to that network's gradient (stored or
+ *     accumulated as the call asks); loss, metrics, the mixed_float16 verdict and Adam behave as for any finite step.
+ *   - Culled cells receive NO gradient: density can reappear there only through a re-bake of the grid with dilation.
+ * The host reads the row count of every network pass (one 4-byte copy and a stream synchronise per pass, two per step with a
+ * fine network): a culled training call is NOT asynchronous -- "the step never waits for the GPU" holds only with the flag
+ * off.  Row counts are 32-bit: a pass with N * S above 2^31 - 1 samples fails under the flag with the render path's message.
+ * Passes run this way add to the counters of nerf_ctx_read_culling (samples seen, rows run). */
+int nerf_ctx_set_train_sample_culling(nerf_ctx* ctx, int on);
 /* The verdict of that rule for N rays x S depths z (N,S), from the device function the render path calls: keep (N,S) int32,
  * 1 kept / 0 culled.  Fails without a grid. */
 int nerf_sample_occupancy(nerf_ctx* ctx, const float* rays_orig, const float* rays_dirs, const float* z, int64_t N, int32_t S,

@@ -70,6 +70,7 @@ SYMBOLS = [
     ("nerf_ray_box_bounds", C.c_int, [_P, _P, _P, _I64, _P, _P, C.c_int]),
     ("nerf_ray_occupancy_bounds", C.c_int, [_P, _P, _P, _I64, _P, _P, C.c_int]),
     ("nerf_ctx_set_sample_culling", C.c_int, [_P, C.c_int]),
+    ("nerf_ctx_set_train_sample_culling", C.c_int, [_P, C.c_int]),
     ("nerf_sample_occupancy", C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, C.c_int]),
     ("nerf_ctx_read_culling", C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     ("nerf_ctx_read_culling_timing", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),

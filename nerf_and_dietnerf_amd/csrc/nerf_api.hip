@@ -927,6 +927,12 @@ int nerf_ctx_set_sample_culling(nerf_ctx* c, int on) {
     return 0;
 }
 
+int nerf_ctx_set_train_sample_culling(nerf_ctx* c, int on) {      // the trainer's switch: train_api.hip (compact_pass)
+    if (!c) return fail("ctx is NULL");
+    c->train_cull_on = on != 0;
+    return 0;
+}
+
 int nerf_sample_occupancy(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, const float* z, int64_t N, int32_t S,
                           int32_t* keep, int mem) {
     ENTER(c);

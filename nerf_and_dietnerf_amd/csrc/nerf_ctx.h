@@ -50,6 +50,7 @@ struct nerf_ctx {
     nerf::DevBuf b_gbounds, b_gstate;          // per-ray (a, b) and state of draw_z_values under a grid (grow-only)
     // sample culling (cull_kernels.hip): nerf_ctx_set_sample_culling; it acts only while the ctx holds a grid
     bool cull_on = false;
+    bool train_cull_on = false;                // nerf_ctx_set_train_sample_culling: the trainer's switch (train_api.hip: compact_pass)
     long long cull_samples = 0, cull_kept = 0; // totals over the culled passes since nerf_ctx_read_culling
     uint32_t* cull_rows = nullptr;             // page-locked word the row count M of a pass is copied to
     nerf::DevBuf b_cmask, b_cfirst, b_csums;   // verdict bits, slot per mask byte, the scan's tile sums + total (grow-only)

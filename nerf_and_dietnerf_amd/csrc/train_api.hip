@@ -47,6 +47,10 @@ struct TPass {                      // activations of one pass, kept from forwar
     // the pre-activation gradients D[0..7] (Mp x 256) and G9 = D[8] (Mp x 128), the two encoding-gradient parts
     DevBuf masks, D[10], dxa, dxb;     // D[8], D[9]: see MlpBwdArgs::d_ptr (the xyz-only network has ten gradient buffers)
     DevBuf rs;                         // pair16 gradient buffers (fused trainer, float32 policy): 10 x Mp row factors (MlpBwdArgs::rs_ptr)
+    // The compaction record of a pass run under nerf_ctx_set_train_sample_culling (stash side: it travels with a RenderSlot):
+    // the verdict bits, launch_scan_popc's slot per mask byte and the row count.  rows < 0: the pass ran every sample.
+    DevBuf cmask, cfirst;
+    long long rows = -1;
 };
 
 // nerf_train_render_forward / _backward (ABI 5): the activations of one ray batch of NeRF.render(), kept from a forward to
@@ -81,6 +85,7 @@ struct TrainState {
     TPass pass[2];
     DevBuf Graw, partial, d_rgb, d_wext, d_zf, tgt, o, d, u_c, u_f, scal;
     DevBuf Ga, Gb, G9, dA0;         // reference trainer: ping-pong gradient buffers (Mp x 256), the rgb branch's (Mp x 128), dL/d(xyz_enc)
+    DevBuf Gc;                      // a culled pass: the kept rows of Graw (padded rows x 4, padding rows zero)
     DevBuf gmax;                    // fused trainer: 2 passes x 16 x 64 max|D| slots (MlpBwdArgs::gmax -> GemmAtb::gmax)
     DevBuf dsig;                    // ... (Mp) column 3 of Graw as a vector, written by the backward chain (GemmAtb::sig_g)
     // The fine pass's batched weight-gradient launch on a second stream, beside the sampler / compositing backward and the coarse
@@ -148,7 +153,7 @@ void free_buf(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0
 
 void free_pass(TPass& p) {
     for (DevBuf* b : {&p.C4, &p.C8, &p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7, &p.H8b, &p.H9, &p.raw, &p.T, &p.w, &p.rgb,
-                      &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs})
+                      &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs, &p.cmask, &p.cfirst})
         free_buf(*b);
     for (DevBuf& b : p.D) free_buf(b);
 }
@@ -332,14 +337,69 @@ void forward_layers(nerf_ctx* c, TNet& n, TPass& p, long long Mp, float* raw) {
     }
 }
 
+// the rows the network kernels of a pass run on: every sample, or the kept ones of a culled pass (TPass::rows)
+long long padded_rows(long long M) { return (M + 127) / 128 * 128; }
+long long net_rows_padded(const TPass& p, const PassDims& d) { return p.rows < 0 ? d.Mp : padded_rows(p.rows); }
+
+// nerf_ctx_set_train_sample_culling acts only while the ctx holds a grid
+bool train_culling(const nerf_ctx* c) { return c->train_cull_on && c->box_on && c->grid_R > 0; }
+
+// The compaction of a culled pass (include/nerf_mi355.h: nerf_ctx_set_train_sample_culling): verdict bits of the pass's depths ->
+// scan -> the row count, read by the host because every kernel downstream takes it by value -> the kept samples' points and
+// directions as compact rows in c->b_cxyz / b_cdirs.  The record (TPass::cmask, cfirst, rows) stays with the stash.
+int compact_pass(nerf_ctx* c, TPass& p, const PassDims& d, const float* o, const float* dirs) {
+    const long long total = d.M;
+    if (total > (long long)INT32_MAX) return fail("sample culling: %lld samples in one pass do not fit int32", total);
+    const long long words = (total + 63) / 64, mask_bytes = words * 8;
+    const size_t tiles = scan_sums_words(mask_bytes);
+    if (int r = ensure(c, p.cmask, (size_t)mask_bytes)) return r;
+    if (int r = ensure(c, p.cfirst, (size_t)mask_bytes * 4)) return r;
+    if (int r = ensure(c, c->b_csums, (tiles + 1) * 4)) return r;
+    if (!c->cull_rows) HIP_OK(hipHostMalloc((void**)&c->cull_rows, sizeof(uint32_t), hipHostMallocDefault));
+    const uint8_t* mask = (const uint8_t*)p.cmask.p;
+    uint32_t *first = (uint32_t*)p.cfirst.p, *sums = (uint32_t*)c->b_csums.p;
+    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, dirs, (const float*)p.z.p, d.N, d.S,
+                       (uint64_t*)p.cmask.p, nullptr, c->stream);
+    launch_scan_popc(mask, mask_bytes, sums, first, sums + tiles, c->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(c->cull_rows, sums + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const long long M = *c->cull_rows;
+    if (M > total) return fail("internal: sample culling kept %lld of %lld samples", M, total);
+    p.rows = M;
+    c->cull_samples += total;
+    c->cull_kept += M;
+    if (M == 0) return 0;
+    const bool with_dirs = c->cfg.n_angles != 0;
+    if (int r = ensure(c, c->b_cxyz, (size_t)M * 12)) return r;
+    if (with_dirs) if (int r = ensure(c, c->b_cdirs, (size_t)M * 12)) return r;
+    if (int r = ensure(c, c->b_craw, (size_t)padded_rows(M) * 16)) return r;
+    launch_sample_gather(o, dirs, (const float*)p.z.p, d.N, d.S, mask, first, (float*)c->b_cxyz.p,
+                         with_dirs ? (float*)c->b_cdirs.p : nullptr, c->stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     float *raw = (float*)p.raw.p, *z = (float*)p.z.p;
-    launch_train_encode(o, dirs, z, 0, d.M, d.S, d.Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, 0,
-                        (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed, !t->reference);
-    if (t->reference) {
-        forward_layers(c, n, p, d.Mp, raw);
+    p.rows = -1;
+    const bool culled = train_culling(c);
+    if (culled) if (int r = compact_pass(c, p, d, o, dirs)) return r;
+    // a culled pass: the network runs in point mode on the compact rows and writes their raw rows to c->b_craw; with no row
+    // kept it does not run at all
+    const long long M = culled ? p.rows : d.M, Mp = net_rows_padded(p, d);
+    const float* in_a = culled ? (const float*)c->b_cxyz.p : o;
+    const float* in_b = culled ? (c->cfg.n_angles != 0 ? (const float*)c->b_cdirs.p : nullptr) : dirs;
+    float* net_raw = culled ? (float*)c->b_craw.p : raw;
+    if (M > 0)
+        launch_train_encode(in_a, in_b, culled ? nullptr : z, 0, M, culled ? 1 : d.S, Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz,
+                            c->cfg.n_pos_enc_dir, culled ? 1 : 0, (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed,
+                            !t->reference);
+    if (M == 0) {
+    } else if (t->reference) {
+        forward_layers(c, n, p, Mp, net_raw);
     } else {
         if (!n.fstream) return fail("internal: fused training forward without its weight stream");
         // the render path's fused PE + MLP kernel (3-pass split fp16, fp32-class results; one pass under mixed_float16) with
@@ -347,8 +407,8 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
         // backward chain reads: 4x the rate of the layer-wise forward
         MlpArgs a{};
         a.wstream = (const float*)n.fstream; a.wconst = n.fcst;
-        a.in_a = o; a.in_b = dirs; a.z = z; a.raw = raw; a.nonfinite = c->nonfinite;
-        a.M = d.M; a.S = d.S; a.mode = 0; a.alpha = c->cfg.leaky_relu_alpha;
+        a.in_a = in_a; a.in_b = in_b; a.z = culled ? nullptr : z; a.raw = net_raw; a.nonfinite = c->nonfinite;
+        a.M = M; a.S = culled ? 1 : d.S; a.mode = culled ? 1 : 0; a.alpha = c->cfg.leaky_relu_alpha;
         const bool xyz = c->cfg.n_angles == 0;
         float* dst[10] = {(float*)p.H1.p, (float*)p.H2.p, (float*)p.H3.p, (float*)p.C4.p, (float*)p.H5.p,
                           (float*)p.H6.p, (float*)p.H7.p, (float*)p.C8.p, xyz ? (float*)p.H8b.p : (float*)p.H9.p,
@@ -356,14 +416,16 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
         const int ld[10] = {256, 256, 256, kLdC4, 256, 256, 256, kLdC8, xyz ? 256 : 128, 128};
         for (int i = 0; i < (xyz ? 10 : 9); ++i) {
             a.st_ptr[i] = dst[i]; a.st_ld[i] = ld[i];
-            a.mask_ptr[i] = p.masks.p ? (uint32_t*)p.masks.p + (size_t)i * d.Mp * 8 : nullptr;
+            a.mask_ptr[i] = p.masks.p ? (uint32_t*)p.masks.p + (size_t)i * Mp * 8 : nullptr;
         }
 #ifdef NERF_DIAG_STASH_WRAP   // diagnostic BUILD only (make EXTRA=-DNERF_DIAG_STASH_WRAP): timing without HBM stores, wrong results
-        a.diag_wrap = d.Mp >= 8192;
+        a.diag_wrap = Mp >= 8192;
 #endif
         if (c->cfg.n_pos_enc_xyz > kLx) wide::launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
         else launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
     }
+    if (culled)     // the full raw buffer, zeros for the culled samples: the compositing runs on all N S samples
+        launch_raw_expand(net_raw, d.M, false, (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, raw, c->stream);
     launch_composite(raw, z, d.N, d.S, (float*)p.rgb.p, (float*)p.w.p, (float*)p.T.p, nullptr, nullptr, nullptr,
                      c->stream);
     HIP_OK(hipGetLastError());
@@ -520,8 +582,9 @@ void wgrad_tile128(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, i
 }
 
 // A head (4-wide G = column n_src_off.. of Graw, row-major) on the VALU kernel, which wants many small slabs
-void wgrad_head(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, int n_src_off, long long Mp) {
-    const Wgrad w = wgrad_args(t, n, l, A, lda, (const float*)t->Graw.p, 4, 4, n_src_off, Mp, 1024, 32);
+void wgrad_head(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* Graw, int n_src_off,
+                long long Mp) {
+    const Wgrad w = wgrad_args(t, n, l, A, lda, Graw, 4, 4, n_src_off, Mp, 1024, 32);
     launch_head_wgrad(w.g, true, c->stream);
     launch_reduce_grad(w.r, c->stream);
 }
@@ -543,7 +606,8 @@ void dgrad_xyz(nerf_ctx* c, const float* G, const float* Wrows, float* dA0, long
 }
 
 // The two backward passes below: Graw (Mp x 4, padding rows zero) must be filled; they write n.grad; with d_z != NULL they
-// add dL/dz through the sample positions (d_z must already hold the compositing part).
+// add dL/dz through the sample positions (d_z must already hold the compositing part).  For a culled pass (TPass::rows >= 0)
+// Mp is the kept rows' padded count, Graw is TrainState::Gc and d_z gets its addition at the kept samples only.
 
 // The fused trainer: ONE kernel for the whole data-gradient chain (mlp_bwd_f16x3.hip: the gradient stays on the lane from
 // layer to layer; every D_l is written once, with max|D_l| in the pass's gmax slots), then the weight gradients from the
@@ -551,7 +615,8 @@ void dgrad_xyz(nerf_ctx* c, const float* G, const float* Wrows, float* dA0, long
 int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
-    const long long Mp = d.Mp;
+    const long long Mp = net_rows_padded(p, d);
+    const float* Graw = (const float*)(p.rows < 0 ? t->Graw.p : t->Gc.p);
     float *C4 = (float*)p.C4.p, *C8 = (float*)p.C8.p;
     float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
           *H6 = (float*)p.H6.p, *H7 = (float*)p.H7.p, *H9 = (float*)p.H9.p;
@@ -562,7 +627,7 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
         return fail("internal: fused training backward without its stream / mask records");
     if (!t->mixed) HIP_OK(hipMemsetAsync(gm, 0, 16 * 64 * sizeof(unsigned), c->stream));
     MlpBwdArgs b{};
-    b.wstream = n.bstream; b.wconst = n.fcst; b.graw = (const float*)t->Graw.p; b.gmax = gm; b.Mp = Mp;
+    b.wstream = n.bstream; b.wconst = n.fcst; b.graw = Graw; b.gmax = gm; b.Mp = Mp;
     b.alpha = c->cfg.leaky_relu_alpha;
     b.ld = 256; b.ld9 = 128;
     const bool xyz = n.n_layers == 12;
@@ -583,12 +648,12 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
     if (xyz) {
         // get_network_only_xyz (src/NeRF.py:248-288): 10 = the rgb head on h9, 11 = the sigma head on h8 (the first 256
         // columns of C8), 9 = 256 -> 128 on the extra layer's output, 8 = that extra 256 -> 256 layer on h8
-        wgrad_head(c, t, n, 10, H9, 128, 0, Mp);
-        wgrad_head(c, t, n, 11, C8, kLdC8, 3, Mp);
+        wgrad_head(c, t, n, 10, H9, 128, Graw, 0, Mp);
+        wgrad_head(c, t, n, 11, C8, kLdC8, Graw, 3, Mp);
         wgrad_tile128(c, t, n, 9, (const float*)p.H8b.p, 256, b.d_ptr[9], b.rs_ptr[9], gm, Mp);
         if (int r = queue(8, C8, kLdC8)) return r;
     } else {
-        wgrad_head(c, t, n, 9, H9, 128, 0, Mp);
+        wgrad_head(c, t, n, 9, H9, 128, Graw, 0, Mp);
         // the sigma head (layer 10: input C8 = [h8 | dir_enc], gradient column 3 of Graw) rides in layer 8's GEMM
         wgrad_tile128(c, t, n, 8, C8, kLdC8, b.d_ptr[8], b.rs_ptr[8], gm, Mp, 10);
     }
@@ -605,8 +670,13 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
         if (!n.bdx) return fail("internal: the sampler term needs the backward stream with encoding tiles");
         // the chain's encoding tiles are laid out for kLx (wide-PE: kLxWide) octaves; the ones the network lacks carry
         // zero gradient
-        launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
-                      d_z, c->stream, true);
+        if (p.rows < 0)
+            launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
+                          d_z, c->stream, true);
+        else
+            launch_pe_bwd_compact(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S,
+                                  pe_layout_lx(c->cfg.n_pos_enc_xyz), (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p,
+                                  d_z, c->stream, true);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -617,12 +687,12 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
 int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
-    const long long Mp = d.Mp;
+    const long long Mp = net_rows_padded(p, d);
     float *C4 = (float*)p.C4.p, *C8 = (float*)p.C8.p;
     float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
           *H6 = (float*)p.H6.p, *H7 = (float*)p.H7.p, *H9 = (float*)p.H9.p;
-    float *Ga = (float*)t->Ga.p, *Gb = (float*)t->Gb.p, *G9 = (float*)t->G9.p, *Graw = (float*)t->Graw.p,
-          *dA0 = (float*)t->dA0.p;
+    float *Ga = (float*)t->Ga.p, *Gb = (float*)t->Gb.p, *G9 = (float*)t->G9.p,
+          *Graw = (float*)(p.rows < 0 ? t->Graw.p : t->Gc.p), *dA0 = (float*)t->dA0.p;
     const bool dx = d_z != nullptr;
     auto wgrad = [&](int l, const float* A, int lda, const float* G, int ldg, int Ncols, int n_src_off = 0) {
         wgrad_reference(c, t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp);
@@ -663,7 +733,11 @@ int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d,
     wgrad(0, C4 + 256, kLdC4, Gb, 256, 256);
     if (dx) {
         dgrad_xyz(c, Gb, n.L[0].W, dA0, Mp, true);
-        launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, d_z, c->stream);
+        if (p.rows < 0)
+            launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, d_z, c->stream);
+        else
+            launch_pe_bwd_compact(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz,
+                                  (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, d_z, c->stream);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -678,6 +752,18 @@ int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDim
     HIP_OK(hipMemsetAsync(Graw + pd.M * 4, 0, (pd.Mp - pd.M) * 4 * sizeof(float), c->stream));
     launch_composite_bwd((const float*)p.raw.p, (const float*)p.z.p, (const float*)p.T.p, pd.N, pd.S, d_rgb, d_wext, Graw,
                          d_z, c->stream);
+    if (p.rows == 0) {
+        // a culled pass that kept no row: no network kernel ran forward, none runs backward; the pass contributes exact zeros
+        // to the network's gradient (stored, or added: nothing to do) and nothing to d_z beyond the compositing's own terms
+        if (!t->acc_grads) HIP_OK(hipMemsetAsync(t->net[which].grad, 0, t->nblob * sizeof(float), c->stream));
+        return 0;
+    }
+    if (p.rows > 0) {
+        const long long Mp = padded_rows(p.rows);
+        if (int r = ensure(c, t->Gc, (size_t)Mp * 4 * sizeof(float))) return r;
+        launch_graw_gather(Graw, pd.M, p.rows, Mp, (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, (float*)t->Gc.p,
+                           c->stream);
+    }
     return t->reference ? backward_reference(c, t, which, pd, o, dirs, d_z)
                         : backward_fused(c, t, which, pd, o, dirs, d_z);
 }
@@ -1117,7 +1203,7 @@ void train_free(nerf_ctx* c) {
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
     if (t->ev_join) (void)hipEventDestroy(t->ev_join);
     free_buf(t->partial_side);
-    DevBuf* bs[] = {&t->Ga, &t->Gb, &t->G9, &t->Graw, &t->dsig, &t->dA0, &t->partial, &t->d_rgb, &t->d_wext, &t->d_zf, &t->tgt,
+    DevBuf* bs[] = {&t->Gc, &t->Ga, &t->Gb, &t->G9, &t->Graw, &t->dsig, &t->dA0, &t->partial, &t->d_rgb, &t->d_wext, &t->d_zf, &t->tgt,
                     &t->o, &t->d, &t->u_c, &t->u_f, &t->scal, &t->gmax, &t->z_new, &t->d_zm, &t->zero_rgb, &t->opt,
                     &t->gsave[0], &t->gsave[1], &t->macc};
     for (DevBuf* b : bs) free_buf(*b);

@@ -90,11 +90,13 @@ def fit(model, ds: RayDataset, epochs: int = 1, steps_per_epoch: Optional[int] =
 
     The loop never waits for a step: ``train_step(..., want_metrics=False)`` only enqueues, the library adds every step's
     loss / psnr_coarse / psnr_fine to running sums on the device, and the sums are read once per epoch (and every
-    ``log_every`` steps when a progress line is asked for) -- so an epoch runs at the step rate ``bench.py`` reports.
+    ``log_every`` steps when a progress line is asked for) -- so an epoch runs at the step rate ``bench.py`` reports.  (With
+    ``"cull_train_samples"`` and a grid every step reads its passes' row counts and so does wait: Context.set_train_sample_culling.)
 
     With render_config ``occupancy_grid`` the model's grid follows its schedule at the start of every epoch
     (NeRF.occupancy_grid_epoch: off during ``warmup_epochs``, baked again every ``update_every`` epochs after them); within
-    an epoch the grid is the snapshot taken at its start."""
+    an epoch the grid is the snapshot taken at its start.  Under ``"cull_train_samples"`` that snapshot also decides which
+    samples train: a culled cell receives no gradient until a re-bake (with ``dilate``) brings it back."""
     ctx = model.ctx
     ctx.train_read_metric_sums()                     # start from clean sums
     extra = getattr(model, "train_read_extra_metric_sums", None)    # DietNeRF: cosine_similarity_loss, kept by the model

@@ -44,8 +44,9 @@ OCCUPANCY_GRID = "occupancy_grid"    # dict of the keys below, default absent: s
 GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL = "resolution", "sigma_threshold", "samples_per_cell"
 GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS = "dilate", "update_every", "warmup_epochs"
 GRID_CULL_SAMPLES = "cull_samples"    # bool, default False: samples in empty cells skip the network (Context.set_sample_culling)
+GRID_CULL_TRAIN_SAMPLES = "cull_train_samples"    # bool, default False: the same in the trainer (Context.set_train_sample_culling)
 _GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS,
-              GRID_CULL_SAMPLES)
+              GRID_CULL_SAMPLES, GRID_CULL_TRAIN_SAMPLES)
 GRID_NEEDS_BOX = "an occupancy grid needs a scene box"
 
 N_COORDINATES = 3
@@ -271,6 +272,7 @@ class Context:
         self.scene_box = None        # ((lo), (hi)) of set_scene_box
         self.grid_resolution = 0     # R of the occupancy grid (0: none)
         self.sample_culling = False  # set_sample_culling
+        self._train_sample_culling = False  # set_train_sample_culling
 
     def close(self):
         if getattr(self, "h", None):
@@ -519,6 +521,21 @@ class Context:
         DietNeRF's consistency render) ignores it.  A culled call reads a row count per network pass: it synchronises."""
         _lib.check(self.lib.nerf_ctx_set_sample_culling(self.h, int(bool(on))))
         self.sample_culling = bool(on)
+
+    def set_train_sample_culling(self, on) -> None:
+        """The trainer's own switch (nerf_ctx_set_train_sample_culling has the rule): with a grid, the samples of a training
+        pass that lie in empty cells are never network rows, forward or backward, and count as the constant raw output
+        (0, 0, 0, 0); culled cells receive no gradient.  Off by default, independent of set_sample_culling; it may be set with
+        or without a grid or a running trainer and acts only while the context holds a grid.  train_step, train_gradients,
+        train_render_gradients and train_render_forward / _backward follow it.  A culled training call reads a row count per
+        network pass: it synchronises."""
+        _lib.check(self.lib.nerf_ctx_set_train_sample_culling(self.h, int(bool(on))))
+        self._train_sample_culling = bool(on)
+
+    @property
+    def train_sample_culling(self) -> bool:
+        """Whether set_train_sample_culling is on."""
+        return self._train_sample_culling
 
     def sample_occupancy(self, rays_orig, rays_dirs, z_values):
         """Rays (N,4), depths (N,S) -> the culling verdict (N,S) int32, 1 kept / 0 culled, under the context's box and grid
@@ -1071,6 +1088,8 @@ class NeRF:
         self._grid_epochs = 0        # epochs fit() has run: the grid's schedule counts them
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_SAMPLES, False):
             self.ctx.set_sample_culling(True)
+        if self.grid_config is not None and self.grid_config.get(GRID_CULL_TRAIN_SAMPLES, False):
+            self.ctx.set_train_sample_culling(True)
 
     @staticmethod
     def _grid_config(cfg, scene_box):
@@ -1100,6 +1119,10 @@ class NeRF:
             if not isinstance(cfg[GRID_CULL_SAMPLES], (bool, np.bool_)):
                 raise ValueError(f"{OCCUPANCY_GRID}: {GRID_CULL_SAMPLES} must be a bool (got {cfg[GRID_CULL_SAMPLES]!r})")
             out[GRID_CULL_SAMPLES] = bool(cfg[GRID_CULL_SAMPLES])
+        if GRID_CULL_TRAIN_SAMPLES in cfg:
+            if not isinstance(cfg[GRID_CULL_TRAIN_SAMPLES], (bool, np.bool_)):
+                raise ValueError(f"{OCCUPANCY_GRID}: {GRID_CULL_TRAIN_SAMPLES} must be a bool (got {cfg[GRID_CULL_TRAIN_SAMPLES]!r})")
+            out[GRID_CULL_TRAIN_SAMPLES] = bool(cfg[GRID_CULL_TRAIN_SAMPLES])
         return out
 
     def update_occupancy_grid(self, seed: int = 0) -> Optional[int]:
