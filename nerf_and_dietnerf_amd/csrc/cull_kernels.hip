@@ -5,19 +5,18 @@
 // network pass, and raw_expand_kernel spreads the M raw rows back over all N * S samples with zeros for the culled ones.
 //
 // The trainer under nerf_ctx_set_train_sample_culling (train_api.hip) uses the same kernels for its forward half; its backward
-// half adds graw_gather_kernel (the kept rows of dL/d(raw), padded to whole 128-row tiles with zero rows) and
-// pe_bwd_compact_kernel (train_kernels.hip's pe_bwd_kernel reading the encoding gradient of sample t at its compact row).
+// half adds graw_gather_kernel (the kept rows of dL/d(raw), padded to whole 128-row tiles with zero rows) and hands the mask
+// and the slots to train_kernels.hip's pe_bwd_kernel, which then reads the encoding gradient of sample t at its compact row.
 //
-// Canonical like the mesh: no atomics, the rows are in ascending sample index.  The fused MLP kernels are not touched: they
-// take M by value, so the host reads it (nerf_api.hip: culled_mlp).
+// Canonical like the mesh: no atomics, the rows are in ascending sample index (nerf_device.h: sample_slot).  The fused MLP
+// kernels are not touched: they take M by value, so the host reads it (nerf_api.hip: compact_samples, the one routine both
+// paths call).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "frag_layout.h"
 #include "nerf_device.h"
 #include "nerf_kernels.h"
-#include "train_kernels.h"
 
 namespace nerf {
 namespace {
@@ -83,15 +82,6 @@ __global__ __launch_bounds__(kBs) void sample_keep_kernel(const CullArgs g, cons
     if (mask && (threadIdx.x & 63) == 0 && t < total) mask[t >> 6] = m;
 }
 
-// slot of kept sample t among the kept samples: the scan's offset of its mask byte + the kept samples before it in the byte
-__device__ __forceinline__ bool sample_slot(const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first, long long t,
-                                            size_t* slot) {
-    const unsigned byte = mask[t >> 3], k = (unsigned)(t & 7);
-    if (!((byte >> k) & 1u)) return false;
-    *slot = (size_t)first[t >> 3] + __popc(byte & ((1u << k) - 1u));
-    return true;
-}
-
 // One thread per sample: a kept sample writes its point (step 1's operations) and its ray's direction to its slot.
 __global__ __launch_bounds__(kBs) void sample_gather_kernel(const float* __restrict__ orig, const float* __restrict__ dirs,
                                                             const float* __restrict__ z, long long total, int S,
@@ -138,54 +128,6 @@ __global__ __launch_bounds__(kBs) void graw_gather_kernel(const float* __restric
     }
 }
 
-// pe_bwd_kernel (train_kernels.hip) for a culled pass: one thread per SAMPLE; a kept sample reads its encoding gradient at its
-// compact row and adds dL/dp . d to d_z at its own index, a culled one leaves d_z alone.  The arithmetic is that kernel's,
-// operation for operation (the build does not contract), so under a full grid (slot == t) d_z comes out bit-identical.
-template <int LX>      // octaves of the gradient rows' layout
-__global__ __launch_bounds__(kBs) void pe_bwd_compact_kernel(const float* __restrict__ dA0, const float* __restrict__ dA0b,
-                                                             const float* __restrict__ o, const float* __restrict__ d,
-                                                             const float* __restrict__ z, long long total, int S,
-                                                             const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first,
-                                                             float* __restrict__ d_z, int frag) {
-    const long long t = (long long)blockIdx.x * kBs + threadIdx.x;
-    if (t >= total) return;
-    size_t slot;
-    if (!sample_slot(mask, first, t, &slot)) return;
-    const long long m = (long long)slot;
-    const long long r = t / S;
-    const float zz = z[t];
-    const float kPi = 3.1415927410125732f;
-    const float4 oo = reinterpret_cast<const float4*>(o)[r], dd = reinterpret_cast<const float4*>(d)[r];
-    const float p[3] = {__fadd_rn(oo.x, __fmul_rn(dd.x, zz)), __fadd_rn(oo.y, __fmul_rn(dd.y, zz)),
-                        __fadd_rn(oo.z, __fmul_rn(dd.z, zz))};
-    const float dv[3] = {dd.x, dd.y, dd.z};
-    constexpr int Q = (3 * (1 + 2 * LX) + 3) / 4;    // float4s covering the 3 + 6 LX encoding columns (rows are 64 floats)
-    static_assert(4 * Q <= kXyzPad, "the encoding columns fit a gradient row");
-    float g[4 * Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const long long e = frag ? frag_index(m, 4 * q, kXyzPad) : m * kXyzPad + 4 * q;
-        float4 v = *reinterpret_cast<const float4*>(dA0 + e);
-        if (dA0b) { const float4 w = *reinterpret_cast<const float4*>(dA0b + e); v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
-        g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        constexpr int XC = 1 + 2 * LX;
-        float dp = g[c * XC];
-#pragma unroll
-        for (int k = 0; k < LX; ++k) {
-            const float f = kPi * (float)(1 << k);
-            const float th = __fmul_rn(p[c], f);
-            const float sn = sin_shifted(th, 0), cs = sin_shifted(th, 1);
-            dp += (cs * g[c * XC + 1 + 2 * k] - sn * g[c * XC + 2 + 2 * k]) * f;
-        }
-        acc += dp * dv[c];
-    }
-    d_z[t] += acc;
-}
-
 }  // namespace
 
 void launch_sample_keep(const SceneBox& box, const uint32_t* bits, int R, const float* orig, const float* dirs, const float* z,
@@ -218,21 +160,6 @@ void launch_graw_gather(const float* graw, long long total, long long M, long lo
     const long long items = total + (Mp - M);
     if (items <= 0) return;
     hipLaunchKernelGGL(graw_gather_kernel, dim3(blocks_for(items)), dim3(kBs), 0, stream, graw, total, M, Mp, mask, first, compact);
-}
-
-void launch_pe_bwd_compact(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N, int S,
-                           int lx, const uint8_t* mask, const uint32_t* first, float* d_z, hipStream_t s, bool frag) {
-    const long long total = N * S;
-    if (total <= 0) return;
-    const dim3 grid(blocks_for(total)), block(kBs);
-    const int fr = frag ? 1 : 0;
-#define NERF_PE_BWD_COMPACT(L) \
-    case L: hipLaunchKernelGGL(pe_bwd_compact_kernel<L>, grid, block, 0, s, dA0, dA0b, o, d, z, total, S, mask, first, d_z, fr); break;
-    switch (lx < 1 ? 1 : lx > 10 ? 10 : lx) {
-        NERF_PE_BWD_COMPACT(1) NERF_PE_BWD_COMPACT(2) NERF_PE_BWD_COMPACT(3) NERF_PE_BWD_COMPACT(4) NERF_PE_BWD_COMPACT(5)
-        NERF_PE_BWD_COMPACT(6) NERF_PE_BWD_COMPACT(7) NERF_PE_BWD_COMPACT(8) NERF_PE_BWD_COMPACT(9) NERF_PE_BWD_COMPACT(10)
-    }
-#undef NERF_PE_BWD_COMPACT
 }
 
 }  // namespace nerf

@@ -82,6 +82,58 @@ int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int 
     return 0;
 }
 
+// with timing on: the next event of the culled render passes' pool (six per pass, read by nerf_ctx_read_culling_timing)
+static int cull_stamp(nerf_ctx* c, bool stamp = true) {
+    if (!stamp || !c->timing) return 0;
+    if (c->cull_ev_used == c->cull_ev.size()) {
+        hipEvent_t e;
+        HIP_OK(hipEventCreate(&e));
+        c->cull_ev.push_back(e);
+    }
+    HIP_OK(hipEventRecord(c->cull_ev[c->cull_ev_used++], c->stream));
+    return 0;
+}
+
+// Verdict bits -> scan -> the row count M, read by the host because every kernel downstream takes it by value -> the kept
+// samples' points and directions as compact rows.  Four stage events: before the verdicts, after the scan, after the read and
+// the growth of the compact buffers, after the gather.
+int compact_samples(nerf_ctx* c, SampleCompaction& rec, const float* o, const float* d, const float* z, long long N, int S,
+                    bool stamp) {
+    const long long total = N * S;
+    if (total > (long long)INT32_MAX) return fail("sample culling: %lld samples in one pass do not fit int32", total);
+    const long long words = (total + 63) / 64, mask_bytes = words * 8;
+    const size_t tiles = scan_sums_words(mask_bytes);
+    if (int r = ensure(c, rec.mask, (size_t)mask_bytes)) return r;
+    if (int r = ensure(c, rec.first, (size_t)mask_bytes * 4)) return r;
+    if (int r = ensure(c, c->b_csums, (tiles + 1) * 4)) return r;
+    if (!c->cull_rows) HIP_OK(hipHostMalloc((void**)&c->cull_rows, sizeof(uint32_t), hipHostMallocDefault));
+    const uint8_t* mask = (const uint8_t*)rec.mask.p;
+    uint32_t *first = (uint32_t*)rec.first.p, *sums = (uint32_t*)c->b_csums.p;
+    if (int r = cull_stamp(c, stamp)) return r;
+    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, d, z, N, S, (uint64_t*)rec.mask.p,
+                       nullptr, c->stream);
+    launch_scan_popc(mask, mask_bytes, sums, first, sums + tiles, c->stream);
+    HIP_OK(hipGetLastError());
+    if (int r = cull_stamp(c, stamp)) return r;
+    HIP_OK(hipMemcpyAsync(c->cull_rows, sums + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const long long M = *c->cull_rows;
+    if (M > total) return fail("internal: sample culling kept %lld of %lld samples", M, total);
+    rec.rows = M;
+    c->cull_samples += total;
+    c->cull_kept += M;
+    const bool with_dirs = c->cfg.n_angles != 0;
+    if (M > 0) {      // the compact buffers follow M, not N * S
+        if (int r = ensure(c, c->b_cxyz, (size_t)M * 12)) return r;
+        if (with_dirs) if (int r = ensure(c, c->b_cdirs, (size_t)M * 12)) return r;
+    }
+    if (int r = cull_stamp(c, stamp)) return r;
+    if (M > 0)
+        launch_sample_gather(o, d, z, N, S, mask, first, (float*)c->b_cxyz.p, with_dirs ? (float*)c->b_cdirs.p : nullptr, c->stream);
+    HIP_OK(hipGetLastError());
+    return cull_stamp(c, stamp);
+}
+
 // The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
 static int layer_dims(int lx, int ld, int n_angles, int dims[12][2]) {
     const int xd = 3 + 6 * lx;                                  // src/NeRF.py:312
@@ -344,62 +396,21 @@ int copy_back_batch(nerf_ctx* c, const nerf_outputs* host, const nerf_outputs* d
     return 0;
 }
 
-// with timing on: the next event of the culled passes' pool (six per pass, read by nerf_ctx_read_culling_timing)
-int cull_stamp(nerf_ctx* c) {
-    if (!c->timing) return 0;
-    if (c->cull_ev_used == c->cull_ev.size()) {
-        hipEvent_t e;
-        HIP_OK(hipEventCreate(&e));
-        c->cull_ev.push_back(e);
-    }
-    HIP_OK(hipEventRecord(c->cull_ev[c->cull_ev_used++], c->stream));
-    return 0;
-}
-
-// network_pass under sample culling (cull_kernels.hip): verdict bits -> scan -> the row count M, read
-// by the host because the fused kernels take it by value -> the kept samples' points as M mode-1 rows -> the same kernel
-// pick_render_kernel gives the unculled pass -> the full raw (or sigma) buffer with zeros for the culled samples.
+// network_pass under sample culling (cull_kernels.hip): compact_samples -> the kept samples' points as M mode-1 rows of the same
+// kernel pick_render_kernel gives the unculled pass -> the full raw (or sigma) buffer with zeros for the culled samples.
 int culled_mlp(nerf_ctx* c, int which, const RenderKernel& k, const float* o, const float* d, const float* z, long long N, int S,
                float* raw) {
-    const long long total = N * S;
     if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);      // run_mlp's, also when M == 0
-    if (total > (long long)INT32_MAX) return fail("sample culling: %lld samples in one pass do not fit int32", total);
-    const long long words = (total + 63) / 64, mask_bytes = words * 8;
-    const size_t tiles = scan_sums_words(mask_bytes);
-    if (int r = ensure(c, c->b_cmask, (size_t)mask_bytes)) return r;
-    if (int r = ensure(c, c->b_cfirst, (size_t)mask_bytes * 4)) return r;
-    if (int r = ensure(c, c->b_csums, (tiles + 1) * 4)) return r;
-    if (!c->cull_rows) HIP_OK(hipHostMalloc((void**)&c->cull_rows, sizeof(uint32_t), hipHostMallocDefault));
-    const uint8_t* mask = (const uint8_t*)c->b_cmask.p;
-    uint32_t *first = (uint32_t*)c->b_cfirst.p, *sums = (uint32_t*)c->b_csums.p;
-    if (int r = cull_stamp(c)) return r;
-    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, d, z, N, S, (uint64_t*)c->b_cmask.p,
-                       nullptr, c->stream);
-    launch_scan_popc(mask, mask_bytes, sums, first, sums + tiles, c->stream);
-    HIP_OK(hipGetLastError());
-    if (int r = cull_stamp(c)) return r;
-    HIP_OK(hipMemcpyAsync(c->cull_rows, sums + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    const long long M = *c->cull_rows;
-    if (M > total) return fail("internal: sample culling kept %lld of %lld samples", M, total);
-    c->cull_samples += total;
-    c->cull_kept += M;
-    const size_t row = k.sigma_only ? 4 : 16;
-    const bool with_dirs = c->cfg.n_angles != 0;
-    if (M > 0) {      // the compact buffers follow M, not N * S
-        if (int r = ensure(c, c->b_cxyz, (size_t)M * 12)) return r;
-        if (with_dirs) if (int r = ensure(c, c->b_cdirs, (size_t)M * 12)) return r;
-        if (int r = ensure(c, c->b_craw, (size_t)M * row)) return r;
+    if (int r = compact_samples(c, c->cull, o, d, z, N, S, true)) return r;
+    const long long M = c->cull.rows;
+    if (M > 0) {
+        if (int r = ensure(c, c->b_craw, (size_t)M * (k.sigma_only ? 4 : 16))) return r;
+        const float* view = c->cfg.n_angles != 0 ? (const float*)c->b_cdirs.p : nullptr;
+        if (int r = run_mlp(c, which, k, (const float*)c->b_cxyz.p, view, nullptr, (float*)c->b_craw.p, M, 1, 1)) return r;
     }
     if (int r = cull_stamp(c)) return r;
-    if (M > 0) {
-        float *xyz = (float*)c->b_cxyz.p, *view = with_dirs ? (float*)c->b_cdirs.p : nullptr;
-        launch_sample_gather(o, d, z, N, S, mask, first, xyz, view, c->stream);
-        if (int r = cull_stamp(c)) return r;
-        if (int r = run_mlp(c, which, k, xyz, view, nullptr, (float*)c->b_craw.p, M, 1, 1)) return r;
-    } else if (int r = cull_stamp(c)) return r;
-    if (int r = cull_stamp(c)) return r;
-    launch_raw_expand((const float*)c->b_craw.p, total, k.sigma_only, mask, first, raw, c->stream);
+    launch_raw_expand((const float*)c->b_craw.p, N * S, k.sigma_only, (const uint8_t*)c->cull.mask.p,
+                      (const uint32_t*)c->cull.first.p, raw, c->stream);
     return cull_stamp(c);
 }
 
@@ -407,7 +418,7 @@ int culled_mlp(nerf_ctx* c, int which, const RenderKernel& k, const float* o, co
 // the ctx holds a grid) it is culled_mlp's; otherwise the one mode-0 launch it always was.
 int network_pass(nerf_ctx* c, int which, const RenderKernel& k, const float* o, const float* d, const float* z, long long N, int S,
                  float* raw) {
-    if (!(c->cull_on && c->box_on && c->grid_R > 0 && N > 0)) return run_mlp(c, which, k, o, d, z, raw, N * S, S, 0);
+    if (!(culling_acts(c, c->cull_on) && N > 0)) return run_mlp(c, which, k, o, d, z, raw, N * S, S, 0);
     const size_t ev0 = c->cull_ev_used;
     const int r = culled_mlp(c, which, k, o, d, z, N, S, raw);
     if (r) c->cull_ev_used = ev0;                                  // the stage events count whole passes only
@@ -522,7 +533,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     DevBuf* bufs[] = {&c->b_orig, &c->b_dirs, &c->b_zc, &c->b_zf, &c->b_raw, &c->b_wc, &c->b_u0, &c->b_u1,
                       &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate,
                       &c->b_mesh_v, &c->b_mesh_n, &c->b_mesh_t, &c->b_mesh_sigma, &c->b_mesh_mask, &c->b_mesh_first,
-                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice, &c->b_cmask, &c->b_cfirst,
+                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice, &c->cull.mask, &c->cull.first,
                       &c->b_csums, &c->b_cxyz, &c->b_cdirs, &c->b_craw};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);
@@ -927,7 +938,7 @@ int nerf_ctx_set_sample_culling(nerf_ctx* c, int on) {
     return 0;
 }
 
-int nerf_ctx_set_train_sample_culling(nerf_ctx* c, int on) {      // the trainer's switch: train_api.hip (compact_pass)
+int nerf_ctx_set_train_sample_culling(nerf_ctx* c, int on) {      // the trainer's switch: train_api.hip (forward_pass)
     if (!c) return fail("ctx is NULL");
     c->train_cull_on = on != 0;
     return 0;

@@ -32,6 +32,10 @@ struct NetWeights {
     std::vector<float> host_blob;   // last blob handed to nerf_load_weights (Keras order): seed of the trainer
 };
 
+// The record of one culled pass (cull_kernels.hip): verdict bits, the scan's slot per mask byte (both grow-only), the row count.
+// The render path keeps one on the ctx, the trainer one per TPass: a slot's backward pass reads it long after its forward pass.
+struct SampleCompaction { DevBuf mask, first; long long rows = -1; };   // rows < 0: no compaction, every sample ran
+
 struct TrainState;   // train_api.hip
 struct CommState;    // comm_api.hip
 
@@ -48,14 +52,15 @@ struct nerf_ctx {
     int grid_cur = 0;                          // which of b_grid holds it; the other is the dilation's second array
     nerf::DevBuf b_grid[2];                    // grid_R^3 / 32 words each
     nerf::DevBuf b_gbounds, b_gstate;          // per-ray (a, b) and state of draw_z_values under a grid (grow-only)
-    // sample culling (cull_kernels.hip): nerf_ctx_set_sample_culling; it acts only while the ctx holds a grid
-    bool cull_on = false;
-    bool train_cull_on = false;                // nerf_ctx_set_train_sample_culling: the trainer's switch (train_api.hip: compact_pass)
+    // sample culling (cull_kernels.hip): a switch acts only while the ctx holds a grid (culling_acts)
+    bool cull_on = false;                      // nerf_ctx_set_sample_culling: the render path's switch
+    bool train_cull_on = false;                // nerf_ctx_set_train_sample_culling: the trainer's switch
     long long cull_samples = 0, cull_kept = 0; // totals over the culled passes since nerf_ctx_read_culling
     uint32_t* cull_rows = nullptr;             // page-locked word the row count M of a pass is copied to
-    nerf::DevBuf b_cmask, b_cfirst, b_csums;   // verdict bits, slot per mask byte, the scan's tile sums + total (grow-only)
+    nerf::SampleCompaction cull;               // the render path's record (the trainer's: TPass::cull)
+    nerf::DevBuf b_csums;                      // the scan's tile sums + total; this and the next line: scratch of one forward pass
     nerf::DevBuf b_cxyz, b_cdirs, b_craw;      // the M compact rows: points, directions, raw (sized after M is known)
-    std::vector<hipEvent_t> cull_ev;           // with timing on, six per culled pass: verdict+scan | read M | gather | (MLP) | expand
+    std::vector<hipEvent_t> cull_ev;           // with timing on, six per culled RENDER pass: verdict+scan | read M | gather | (MLP) | expand
     size_t cull_ev_used = 0;
     // mesh extraction (mesh_kernels.hip): the pending mesh of nerf_isosurface and its scratch, all grow-only
     bool mesh_on = false;
@@ -93,6 +98,14 @@ int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's b
 // has rays.  Without a grid it launches what it always launched and cannot fail; with one it may grow two scratch buffers.
 int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
                    long long ray_base, float* z);   // nerf_api.hip; device pointers, enqueued on the ctx stream
+
+// a culling switch (cull_on, train_cull_on) acts only while the ctx holds a grid
+inline bool culling_acts(const nerf_ctx* c, bool flag) { return flag && c->box_on && c->grid_R > 0; }
+// nerf_api.hip: the compaction of one pass's N * S samples under the grid, for the render path and the trainer alike.  On
+// success rec.rows = M, the cull_samples / cull_kept counters have advanced and, for M > 0, the kept samples' points (and
+// directions, when the network has them) are the M rows of c->b_cxyz / b_cdirs.  stamp: record the render path's stage events.
+int compact_samples(nerf_ctx* c, SampleCompaction& rec, const float* o, const float* d, const float* z, long long N, int S,
+                    bool stamp);
 
 void train_free(nerf_ctx* c);                       // train_api.hip: releases c->train (called by nerf_ctx_destroy)
 void comm_free(nerf_ctx* c);                        // comm_api.hip: releases c->comm (called by nerf_ctx_destroy)

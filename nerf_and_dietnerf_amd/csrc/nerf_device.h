@@ -106,4 +106,14 @@ __device__ __forceinline__ int grid_cell_index(float p, float lo, float cell, in
     return f >= 0.0f ? (f <= (float)(R - 1) ? (int)f : R - 1) : 0;
 }
 
+// Sample culling (cull_kernels.hip): whether sample t is kept, and its slot among the kept samples -- the scan's offset of its
+// mask byte + the kept samples before it in the byte
+__device__ __forceinline__ bool sample_slot(const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first, long long t,
+                                            size_t* slot) {
+    const unsigned byte = mask[t >> 3], k = (unsigned)(t & 7);
+    if (!((byte >> k) & 1u)) return false;
+    *slot = (size_t)first[t >> 3] + __popc(byte & ((1u << k) - 1u));
+    return true;
+}
+
 }  // namespace nerf

@@ -274,13 +274,9 @@ void launch_sample_gather(const float* orig, const float* dirs, const float* z, 
 void launch_raw_expand(const float* compact, long long total, bool sigma_only, const uint8_t* mask, const uint32_t* first,
                        float* raw, hipStream_t stream);
 // ... and the backward half of a culled training pass (nerf_ctx_set_train_sample_culling).  graw_gather: the kept rows of
-// graw (total,4) as compact (Mp,4), rows M.. zero.  pe_bwd_compact: train_kernels.h::launch_pe_bwd with the encoding gradient of
-// sample t at its compact row (row-major or fragment-major, lx 1..10); adds to d_z (N S) at the kept samples only.
+// graw (total,4) as compact (Mp,4), rows M.. zero.  (The encoding backward is train_kernels.h::launch_pe_bwd given mask, first.)
 void launch_graw_gather(const float* graw, long long total, long long M, long long Mp, const uint8_t* mask, const uint32_t* first,
                         float* compact, hipStream_t stream);
-void launch_pe_bwd_compact(const float* dA0, const float* dA0b /* added to dA0, or null */, const float* o, const float* d,
-                           const float* z, long long N, int S, int lx, const uint8_t* mask, const uint32_t* first, float* d_z,
-                           hipStream_t s, bool frag = false);
 size_t sample_pdf_lds_bytes(int S, int Sf);
 void launch_sample_pdf(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                        uint64_t seed, long long ray_base, float* z_new, float* z_merged,

@@ -47,10 +47,9 @@ struct TPass {                      // activations of one pass, kept from forwar
     // the pre-activation gradients D[0..7] (Mp x 256) and G9 = D[8] (Mp x 128), the two encoding-gradient parts
     DevBuf masks, D[10], dxa, dxb;     // D[8], D[9]: see MlpBwdArgs::d_ptr (the xyz-only network has ten gradient buffers)
     DevBuf rs;                         // pair16 gradient buffers (fused trainer, float32 policy): 10 x Mp row factors (MlpBwdArgs::rs_ptr)
-    // The compaction record of a pass run under nerf_ctx_set_train_sample_culling (stash side: it travels with a RenderSlot):
-    // the verdict bits, launch_scan_popc's slot per mask byte and the row count.  rows < 0: the pass ran every sample.
-    DevBuf cmask, cfirst;
-    long long rows = -1;
+    // The record of a pass run under nerf_ctx_set_train_sample_culling (stash side: it travels with a RenderSlot, so a slot's
+    // backward pass does not depend on what the ctx culled, or was told, after its forward pass)
+    SampleCompaction cull;
 };
 
 // nerf_train_render_forward / _backward (ABI 5): the activations of one ray batch of NeRF.render(), kept from a forward to
@@ -153,7 +152,7 @@ void free_buf(DevBuf& b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0
 
 void free_pass(TPass& p) {
     for (DevBuf* b : {&p.C4, &p.C8, &p.H1, &p.H2, &p.H3, &p.H5, &p.H6, &p.H7, &p.H8b, &p.H9, &p.raw, &p.T, &p.w, &p.rgb,
-                      &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs, &p.cmask, &p.cfirst})
+                      &p.z, &p.masks, &p.dxa, &p.dxb, &p.rs, &p.cull.mask, &p.cull.first})
         free_buf(*b);
     for (DevBuf& b : p.D) free_buf(b);
 }
@@ -269,7 +268,8 @@ int init_net(nerf_ctx* c, TrainState* t, int which) {
 // ---- one pass: forward ---------------------------------------------------------------------------
 struct PassDims { long long N; int S; long long M, Mp; };
 
-PassDims pass_dims(long long N, int S) { return {N, S, N * S, (N * S + 127) / 128 * 128}; }
+long long padded_rows(long long M) { return (M + 127) / 128 * 128; }      // the network kernels work on whole 128-row tiles
+PassDims pass_dims(long long N, int S) { return {N, S, N * S, padded_rows(N * S)}; }
 
 int ensure_pass(nerf_ctx* c, TPass& p, const PassDims& d) {
     const TrainState* t = c->train;
@@ -337,69 +337,34 @@ void forward_layers(nerf_ctx* c, TNet& n, TPass& p, long long Mp, float* raw) {
     }
 }
 
-// the rows the network kernels of a pass run on: every sample, or the kept ones of a culled pass (TPass::rows)
-long long padded_rows(long long M) { return (M + 127) / 128 * 128; }
-long long net_rows_padded(const TPass& p, const PassDims& d) { return p.rows < 0 ? d.Mp : padded_rows(p.rows); }
-
-// nerf_ctx_set_train_sample_culling acts only while the ctx holds a grid
-bool train_culling(const nerf_ctx* c) { return c->train_cull_on && c->box_on && c->grid_R > 0; }
-
-// The compaction of a culled pass (include/nerf_mi355.h: nerf_ctx_set_train_sample_culling): verdict bits of the pass's depths ->
-// scan -> the row count, read by the host because every kernel downstream takes it by value -> the kept samples' points and
-// directions as compact rows in c->b_cxyz / b_cdirs.  The record (TPass::cmask, cfirst, rows) stays with the stash.
-int compact_pass(nerf_ctx* c, TPass& p, const PassDims& d, const float* o, const float* dirs) {
-    const long long total = d.M;
-    if (total > (long long)INT32_MAX) return fail("sample culling: %lld samples in one pass do not fit int32", total);
-    const long long words = (total + 63) / 64, mask_bytes = words * 8;
-    const size_t tiles = scan_sums_words(mask_bytes);
-    if (int r = ensure(c, p.cmask, (size_t)mask_bytes)) return r;
-    if (int r = ensure(c, p.cfirst, (size_t)mask_bytes * 4)) return r;
-    if (int r = ensure(c, c->b_csums, (tiles + 1) * 4)) return r;
-    if (!c->cull_rows) HIP_OK(hipHostMalloc((void**)&c->cull_rows, sizeof(uint32_t), hipHostMallocDefault));
-    const uint8_t* mask = (const uint8_t*)p.cmask.p;
-    uint32_t *first = (uint32_t*)p.cfirst.p, *sums = (uint32_t*)c->b_csums.p;
-    launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, dirs, (const float*)p.z.p, d.N, d.S,
-                       (uint64_t*)p.cmask.p, nullptr, c->stream);
-    launch_scan_popc(mask, mask_bytes, sums, first, sums + tiles, c->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(c->cull_rows, sums + tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    const long long M = *c->cull_rows;
-    if (M > total) return fail("internal: sample culling kept %lld of %lld samples", M, total);
-    p.rows = M;
-    c->cull_samples += total;
-    c->cull_kept += M;
-    if (M == 0) return 0;
-    const bool with_dirs = c->cfg.n_angles != 0;
-    if (int r = ensure(c, c->b_cxyz, (size_t)M * 12)) return r;
-    if (with_dirs) if (int r = ensure(c, c->b_cdirs, (size_t)M * 12)) return r;
-    if (int r = ensure(c, c->b_craw, (size_t)padded_rows(M) * 16)) return r;
-    launch_sample_gather(o, dirs, (const float*)p.z.p, d.N, d.S, mask, first, (float*)c->b_cxyz.p,
-                         with_dirs ? (float*)c->b_cdirs.p : nullptr, c->stream);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
+// the rows the network kernels of a pass run on: every sample, or the kept ones of a culled pass (TPass::cull)
+long long net_rows_padded(const TPass& p, const PassDims& d) { return p.cull.rows < 0 ? d.Mp : padded_rows(p.cull.rows); }
+// ... and the pass's record as launch_pe_bwd takes it: nulls for a pass that ran every sample
+const uint8_t* cull_mask(const TPass& p) { return p.cull.rows < 0 ? nullptr : (const uint8_t*)p.cull.mask.p; }
+const uint32_t* cull_first(const TPass& p) { return p.cull.rows < 0 ? nullptr : (const uint32_t*)p.cull.first.p; }
 
 int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     float *raw = (float*)p.raw.p, *z = (float*)p.z.p;
-    p.rows = -1;
-    const bool culled = train_culling(c);
-    if (culled) if (int r = compact_pass(c, p, d, o, dirs)) return r;
-    // a culled pass: the network runs in point mode on the compact rows and writes their raw rows to c->b_craw; with no row
-    // kept it does not run at all
-    const long long M = culled ? p.rows : d.M, Mp = net_rows_padded(p, d);
-    const float* in_a = culled ? (const float*)c->b_cxyz.p : o;
-    const float* in_b = culled ? (c->cfg.n_angles != 0 ? (const float*)c->b_cdirs.p : nullptr) : dirs;
-    float* net_raw = culled ? (float*)c->b_craw.p : raw;
-    if (M > 0)
-        launch_train_encode(in_a, in_b, culled ? nullptr : z, 0, M, culled ? 1 : d.S, Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz,
-                            c->cfg.n_pos_enc_dir, culled ? 1 : 0, (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed,
-                            !t->reference);
-    if (M == 0) {
+    // what the network runs on: the pass's rays and depths (mode 0), or ...
+    struct { const float *in_a, *in_b, *z; int S, mode; long long M, Mp; float* raw; } in = {o, dirs, z, d.S, 0, d.M, d.Mp, raw};
+    p.cull.rows = -1;
+    if (culling_acts(c, c->train_cull_on)) {
+        // ... a culled pass: point mode on the compact rows, their raw rows to c->b_craw; with no row kept it does not run at all
+        if (int r = compact_samples(c, p.cull, o, dirs, z, d.N, d.S, false)) return r;
+        const long long M = p.cull.rows, Mp = padded_rows(M);
+        if (int r = ensure(c, c->b_craw, (size_t)Mp * 16)) return r;
+        in = {(const float*)c->b_cxyz.p, c->cfg.n_angles != 0 ? (const float*)c->b_cdirs.p : nullptr, nullptr, 1, 1, M, Mp,
+              (float*)c->b_craw.p};
+    }
+    const long long Mp = in.Mp;
+    if (in.M > 0)
+        launch_train_encode(in.in_a, in.in_b, in.z, 0, in.M, in.S, Mp, c->cfg.n_angles, c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir,
+                            in.mode, (float*)p.C4.p, (float*)p.C8.p, c->stream, t->mixed, !t->reference);
+    if (in.M == 0) {
     } else if (t->reference) {
-        forward_layers(c, n, p, Mp, net_raw);
+        forward_layers(c, n, p, Mp, in.raw);
     } else {
         if (!n.fstream) return fail("internal: fused training forward without its weight stream");
         // the render path's fused PE + MLP kernel (3-pass split fp16, fp32-class results; one pass under mixed_float16) with
@@ -407,8 +372,8 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
         // backward chain reads: 4x the rate of the layer-wise forward
         MlpArgs a{};
         a.wstream = (const float*)n.fstream; a.wconst = n.fcst;
-        a.in_a = in_a; a.in_b = in_b; a.z = culled ? nullptr : z; a.raw = net_raw; a.nonfinite = c->nonfinite;
-        a.M = M; a.S = culled ? 1 : d.S; a.mode = culled ? 1 : 0; a.alpha = c->cfg.leaky_relu_alpha;
+        a.in_a = in.in_a; a.in_b = in.in_b; a.z = in.z; a.raw = in.raw; a.nonfinite = c->nonfinite;
+        a.M = in.M; a.S = in.S; a.mode = in.mode; a.alpha = c->cfg.leaky_relu_alpha;
         const bool xyz = c->cfg.n_angles == 0;
         float* dst[10] = {(float*)p.H1.p, (float*)p.H2.p, (float*)p.H3.p, (float*)p.C4.p, (float*)p.H5.p,
                           (float*)p.H6.p, (float*)p.H7.p, (float*)p.C8.p, xyz ? (float*)p.H8b.p : (float*)p.H9.p,
@@ -424,8 +389,8 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
         if (c->cfg.n_pos_enc_xyz > kLx) wide::launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
         else launch_mlp_f16x3_stash(a, c->num_cus, c->stream, t->mixed, xyz);
     }
-    if (culled)     // the full raw buffer, zeros for the culled samples: the compositing runs on all N S samples
-        launch_raw_expand(net_raw, d.M, false, (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, raw, c->stream);
+    if (p.cull.rows >= 0)     // the full raw buffer, zeros for the culled samples: the compositing runs on all N S samples
+        launch_raw_expand(in.raw, d.M, false, cull_mask(p), cull_first(p), raw, c->stream);
     launch_composite(raw, z, d.N, d.S, (float*)p.rgb.p, (float*)p.w.p, (float*)p.T.p, nullptr, nullptr, nullptr,
                      c->stream);
     HIP_OK(hipGetLastError());
@@ -606,7 +571,7 @@ void dgrad_xyz(nerf_ctx* c, const float* G, const float* Wrows, float* dA0, long
 }
 
 // The two backward passes below: Graw (Mp x 4, padding rows zero) must be filled; they write n.grad; with d_z != NULL they
-// add dL/dz through the sample positions (d_z must already hold the compositing part).  For a culled pass (TPass::rows >= 0)
+// add dL/dz through the sample positions (d_z must already hold the compositing part).  For a culled pass (TPass::cull.rows >= 0)
 // Mp is the kept rows' padded count, Graw is TrainState::Gc and d_z gets its addition at the kept samples only.
 
 // The fused trainer: ONE kernel for the whole data-gradient chain (mlp_bwd_f16x3.hip: the gradient stays on the lane from
@@ -616,7 +581,7 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     const long long Mp = net_rows_padded(p, d);
-    const float* Graw = (const float*)(p.rows < 0 ? t->Graw.p : t->Gc.p);
+    const float* Graw = (const float*)(p.cull.rows < 0 ? t->Graw.p : t->Gc.p);
     float *C4 = (float*)p.C4.p, *C8 = (float*)p.C8.p;
     float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
           *H6 = (float*)p.H6.p, *H7 = (float*)p.H7.p, *H9 = (float*)p.H9.p;
@@ -670,13 +635,8 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
         if (!n.bdx) return fail("internal: the sampler term needs the backward stream with encoding tiles");
         // the chain's encoding tiles are laid out for kLx (wide-PE: kLxWide) octaves; the ones the network lacks carry
         // zero gradient
-        if (p.rows < 0)
-            launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
-                          d_z, c->stream, true);
-        else
-            launch_pe_bwd_compact(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S,
-                                  pe_layout_lx(c->cfg.n_pos_enc_xyz), (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p,
-                                  d_z, c->stream, true);
+        launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
+                      cull_mask(p), cull_first(p), d_z, c->stream, true);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -692,7 +652,7 @@ int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d,
     float *H1 = (float*)p.H1.p, *H2 = (float*)p.H2.p, *H3 = (float*)p.H3.p, *H5 = (float*)p.H5.p,
           *H6 = (float*)p.H6.p, *H7 = (float*)p.H7.p, *H9 = (float*)p.H9.p;
     float *Ga = (float*)t->Ga.p, *Gb = (float*)t->Gb.p, *G9 = (float*)t->G9.p,
-          *Graw = (float*)(p.rows < 0 ? t->Graw.p : t->Gc.p), *dA0 = (float*)t->dA0.p;
+          *Graw = (float*)(p.cull.rows < 0 ? t->Graw.p : t->Gc.p), *dA0 = (float*)t->dA0.p;
     const bool dx = d_z != nullptr;
     auto wgrad = [&](int l, const float* A, int lda, const float* G, int ldg, int Ncols, int n_src_off = 0) {
         wgrad_reference(c, t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp);
@@ -733,11 +693,8 @@ int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d,
     wgrad(0, C4 + 256, kLdC4, Gb, 256, 256);
     if (dx) {
         dgrad_xyz(c, Gb, n.L[0].W, dA0, Mp, true);
-        if (p.rows < 0)
-            launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, d_z, c->stream);
-        else
-            launch_pe_bwd_compact(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz,
-                                  (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, d_z, c->stream);
+        launch_pe_bwd(dA0, nullptr, o, dirs, (const float*)p.z.p, d.N, d.S, c->cfg.n_pos_enc_xyz, cull_mask(p), cull_first(p),
+                      d_z, c->stream);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -752,17 +709,16 @@ int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDim
     HIP_OK(hipMemsetAsync(Graw + pd.M * 4, 0, (pd.Mp - pd.M) * 4 * sizeof(float), c->stream));
     launch_composite_bwd((const float*)p.raw.p, (const float*)p.z.p, (const float*)p.T.p, pd.N, pd.S, d_rgb, d_wext, Graw,
                          d_z, c->stream);
-    if (p.rows == 0) {
+    if (p.cull.rows == 0) {
         // a culled pass that kept no row: no network kernel ran forward, none runs backward; the pass contributes exact zeros
         // to the network's gradient (stored, or added: nothing to do) and nothing to d_z beyond the compositing's own terms
         if (!t->acc_grads) HIP_OK(hipMemsetAsync(t->net[which].grad, 0, t->nblob * sizeof(float), c->stream));
         return 0;
     }
-    if (p.rows > 0) {
-        const long long Mp = padded_rows(p.rows);
+    if (p.cull.rows > 0) {
+        const long long Mp = padded_rows(p.cull.rows);
         if (int r = ensure(c, t->Gc, (size_t)Mp * 4 * sizeof(float))) return r;
-        launch_graw_gather(Graw, pd.M, p.rows, Mp, (const uint8_t*)p.cmask.p, (const uint32_t*)p.cfirst.p, (float*)t->Gc.p,
-                           c->stream);
+        launch_graw_gather(Graw, pd.M, p.cull.rows, Mp, cull_mask(p), cull_first(p), (float*)t->Gc.p, c->stream);
     }
     return t->reference ? backward_reference(c, t, which, pd, o, dirs, d_z)
                         : backward_fused(c, t, which, pd, o, dirs, d_z);

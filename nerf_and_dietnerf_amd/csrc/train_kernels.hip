@@ -1578,16 +1578,25 @@ void launch_head_bwd(const float* Graw, const float* W9, const float* H9, long l
 }
 
 // ------------------------------------------------------------------------------------------------
-// positional-encoding backward + sample_along_rays backward: d_z[m] += sum_c dL/dp_c * dir_c
+// positional-encoding backward + sample_along_rays backward: d_z[t] += sum_c dL/dp_c * dir_c, one thread per sample t.
+// Its encoding gradient is row m = t; for a culled pass (mask / first non-null: SampleCompaction) row m = the slot of a
+// kept sample (nerf_device.h::sample_slot), and a culled sample leaves d_z alone.
 // ------------------------------------------------------------------------------------------------
 template <int LX>      // octaves of the gradient rows' layout
 __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __restrict__ dA0b /* second part to add, or null */,
                               const float* __restrict__ o, const float* __restrict__ d,
-                              const float* __restrict__ z, long long M, int S, float* __restrict__ d_z, int frag) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const long long r = m / S;
-    const float zz = z[m];
+                              const float* __restrict__ z, long long total, int S, const uint8_t* __restrict__ mask,
+                              const uint32_t* __restrict__ first, float* __restrict__ d_z, int frag) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    long long m = t;
+    if (mask) {
+        size_t slot;
+        if (!sample_slot(mask, first, t, &slot)) return;
+        m = (long long)slot;
+    }
+    const long long r = t / S;
+    const float zz = z[t];
     const float kPi = 3.1415927410125732f;
     const float4 oo = reinterpret_cast<const float4*>(o)[r], dd = reinterpret_cast<const float4*>(d)[r];
     const float p[3] = {__fadd_rn(oo.x, __fmul_rn(dd.x, zz)), __fadd_rn(oo.y, __fmul_rn(dd.y, zz)),
@@ -1597,6 +1606,7 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
     // frag: the (Mp, 64) rows are fragment-major (frag_layout.h::frag_index; written by the fused backward chain):
     // neighbouring threads read neighbouring 16-byte slots
     constexpr int Q = (3 * (1 + 2 * LX) + 3) / 4;    // float4s covering the 3 + 6 LX encoding columns (rows are 64 floats)
+    static_assert(4 * Q <= kXyzPad, "the encoding columns fit a gradient row");
     float g[4 * Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {                  // 33 floats (LX 5) read as 9 float4, 63 (LX 10) as 16: no overrun
@@ -1619,7 +1629,7 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
         }
         acc += dp * dv[c];
     }
-    d_z[m] += acc;
+    d_z[t] += acc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1649,23 +1659,18 @@ void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm
 }
 
 void launch_pe_bwd(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N, int S,
-                   int lx, float* d_z, hipStream_t s, bool frag) {
-    const long long M = N * S;
-    if (M <= 0) return;
-    const dim3 grid((unsigned)((M + 255) / 256)), block(256);
+                   int lx, const uint8_t* mask, const uint32_t* first, float* d_z, hipStream_t s, bool frag) {
+    const long long total = N * S;
+    if (total <= 0) return;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     const int fr = frag ? 1 : 0;
-    switch (lx) {
-        case 1: hipLaunchKernelGGL(pe_bwd_kernel<1>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 2: hipLaunchKernelGGL(pe_bwd_kernel<2>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 3: hipLaunchKernelGGL(pe_bwd_kernel<3>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 4: hipLaunchKernelGGL(pe_bwd_kernel<4>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 5: hipLaunchKernelGGL(pe_bwd_kernel<5>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 6: hipLaunchKernelGGL(pe_bwd_kernel<6>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 7: hipLaunchKernelGGL(pe_bwd_kernel<7>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 8: hipLaunchKernelGGL(pe_bwd_kernel<8>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        case 9: hipLaunchKernelGGL(pe_bwd_kernel<9>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
-        default: hipLaunchKernelGGL(pe_bwd_kernel<10>, grid, block, 0, s, dA0, dA0b, o, d, z, M, S, d_z, fr); break;
+#define NERF_PE_BWD(L) \
+    case L: hipLaunchKernelGGL(pe_bwd_kernel<L>, grid, block, 0, s, dA0, dA0b, o, d, z, total, S, mask, first, d_z, fr); break;
+    switch (lx) {      // check_cfg: 1..10
+        NERF_PE_BWD(1) NERF_PE_BWD(2) NERF_PE_BWD(3) NERF_PE_BWD(4) NERF_PE_BWD(5)
+        NERF_PE_BWD(6) NERF_PE_BWD(7) NERF_PE_BWD(8) NERF_PE_BWD(9) NERF_PE_BWD(10)
     }
+#undef NERF_PE_BWD
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -313,6 +313,52 @@ def test_render_gradients_and_slots_under_a_half_full_grid(oracle, golden_ckpt, 
     c.close()
 
 
+def test_a_culled_render_between_forward_and_backward_leaves_the_slot_alone(oracle, golden_ckpt):
+    """The render path and the trainer run the same compaction routine, each into a record of its own: a culled render under
+    another grid between a slot's forward and its backward pass overwrites the context's record and the shared scratch, and the
+    slot's backward pass still equals the one call bit for bit."""
+    n, sc, sf = 130, 8, 16
+    p = scene(oracle, golden_ckpt, n, sc, sf, SEED_RENDER["float32"])
+    c = _ctx(p, HALF_GRID, True)
+    c.train_begin(5e-4)
+    rgb, gc, gf = c.train_render_gradients(p["o"], p["d"], p["d_rgb"], sc, sf, p["u_c"], p["u_f"])
+    c.read_culling()
+    np.testing.assert_array_equal(c.train_render_forward(0, p["o"], p["d"], sc, sf, p["u_c"], p["u_f"]), rgb)
+    samples, kept = c.read_culling()
+    assert samples == n * (2 * sc + sf) and 0 < kept < samples            # the slot does hold a record
+    c.set_sample_culling(True)
+    c.set_occupancy_grid(~HALF_GRID)
+    assert np.isfinite(c.render(p["o"], p["d"], sc, sf, p["u_c"], p["u_f"])[0]).all()
+    samples, kept_render = c.read_culling()
+    assert 0 < kept_render < samples and kept_render != kept              # the render did compact, to other rows
+    sc_, sf_ = c.train_render_backward(0, p["d_rgb"])
+    assert c.read_culling() == (0, 0)
+    assert gc.any() and gf.any()
+    _same_bits([sc_, sf_], [gc, gf])
+    c.close()
+
+
+def test_stage_events_belong_to_render_passes_only(oracle, golden_ckpt):
+    """With timing on, a culled render pass records its six stage events and a culled training pass records none."""
+    n, sc, sf = 130, 8, 16
+    p = scene(oracle, golden_ckpt, n, sc, sf, 2)
+    c = _ctx(p, HALF_GRID, True)
+    c.set_sample_culling(True)
+    c.train_begin(5e-4)
+    c.enable_timing(True)
+    c.read_culling_timing()
+    c.read_culling()
+    c.render(p["o"], p["d"], sc, sf, p["u_c"], p["u_f"])
+    samples, kept = c.read_culling()
+    assert 0 < kept < samples
+    assert c.read_culling_timing()[1] == 2                                # the coarse pass and the fine pass
+    c.train_gradients(p["o"], p["d"], p["tgt"], sc, sf, p["u_c"], p["u_f"], want_blobs=False)
+    samples, kept = c.read_culling()
+    assert samples == n * (sc + sf) and 0 < kept < samples                # two culled training passes ...
+    assert c.read_culling_timing()[1] == 0                                # ... and no stage event
+    c.close()
+
+
 # ---- 5. nothing kept ---------------------------------------------------------------------------------------------------------
 def _rays_inside(oracle, golden_ckpt, c, n, sc):
     """As tests/test_gpu_culling.py::test_nothing_kept: the rays that hit the box.  The trainer draws its own depths; uniform in
