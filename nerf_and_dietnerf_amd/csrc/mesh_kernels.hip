@@ -441,11 +441,9 @@ int nerf_isosurface(nerf_ctx* c, const float* sigma, int32_t n, const float* lo3
     if (!std::isfinite(iso)) return fail("isosurface: iso must be finite (got %g)", iso);
     c->mesh_on = false;                                        // a call that fails leaves no mesh behind
     const long long points = (long long)n * n * n, cubes = (long long)(n - 1) * (n - 1) * (n - 1);
-    const float* s = sigma;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_mesh_sigma, sigma, (size_t)points * 4)) return r;
-        s = (const float*)c->b_mesh_sigma.p;
-    }
+    Staging st(c, mem);      // (no outputs: the mesh stays in the ctx until nerf_isosurface_fetch)
+    const float* s = st.in(c->b_mesh_sigma, sigma, (size_t)points * 4);
+    if (st.err) return st.err;
     const size_t tiles = (size_t)((points + kScanTile - 1) / kScanTile);
     if (int r = ensure(c, c->b_mesh_mask, (size_t)points)) return r;
     if (int r = ensure(c, c->b_mesh_first, (size_t)points * 4)) return r;
@@ -477,7 +475,7 @@ int nerf_isosurface(nerf_ctx* c, const float* sigma, int32_t n, const float* lo3
                            tfirst, (int*)c->b_mesh_t.p);
     }
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
+    if (int r = st.finish()) return r;
     c->mesh_V = V; c->mesh_T = T;
     c->mesh_on = true;
     *n_vertices = V; *n_triangles = T;
@@ -488,12 +486,11 @@ int nerf_isosurface_fetch(nerf_ctx* c, float* vertices, float* normals, int32_t*
     ENTER(c);
     if (!c->mesh_on) return fail("no pending mesh: call nerf_isosurface first");
     if ((c->mesh_V > 0 && !vertices) || (c->mesh_T > 0 && !triangles)) return fail("NULL argument");
-    const hipMemcpyKind kind = mem == NERF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (c->mesh_V > 0) {
-        HIP_OK(hipMemcpyAsync(vertices, c->b_mesh_v.p, (size_t)c->mesh_V * 12, kind, c->stream));
-        if (normals) HIP_OK(hipMemcpyAsync(normals, c->b_mesh_n.p, (size_t)c->mesh_V * 12, kind, c->stream));
+        if (int r = copy_to_caller(c, vertices, c->b_mesh_v.p, (size_t)c->mesh_V * 12, mem)) return r;
+        if (normals) if (int r = copy_to_caller(c, normals, c->b_mesh_n.p, (size_t)c->mesh_V * 12, mem)) return r;
     }
-    if (c->mesh_T > 0) HIP_OK(hipMemcpyAsync(triangles, c->b_mesh_t.p, (size_t)c->mesh_T * 12, kind, c->stream));
+    if (c->mesh_T > 0) if (int r = copy_to_caller(c, triangles, c->b_mesh_t.p, (size_t)c->mesh_T * 12, mem)) return r;
     if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -52,6 +52,39 @@ int h2d(nerf_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     return 0;
 }
 
+int copy_to_caller(nerf_ctx* c, void* dst, const void* src_dev, size_t bytes, int mem) {
+    HIP_OK(hipMemcpyAsync(dst, src_dev, bytes, mem == NERF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+int copy_from_caller(nerf_ctx* c, void* dst_dev, const void* src, size_t bytes, int mem) {
+    HIP_OK(hipMemcpyAsync(dst_dev, src, bytes, mem == NERF_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+Staging::Staging(nerf_ctx* c, int mem) : c(c), host(mem == NERF_MEM_HOST) {}
+
+void* Staging::stage(DevBuf& b, void* caller, size_t bytes, bool upload) {
+    if (!caller || err) return nullptr;
+    if (!host) return caller;
+    if (upload) {
+        err = h2d(c, b, caller, bytes);
+    } else if (n_back == (int)(sizeof back / sizeof back[0])) {
+        err = fail("internal: more than %d staged outputs in one call", n_back);
+    } else if (!(err = ensure(c, b, bytes))) {
+        back[n_back].dst = caller; back[n_back].src = b.p; back[n_back].bytes = bytes;
+        ++n_back;
+    }
+    return err ? nullptr : b.p;
+}
+
+int Staging::finish() {
+    if (!host) return 0;
+    for (int i = 0; i < n_back; ++i) HIP_OK(hipMemcpyAsync(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int enter(nerf_ctx* c) {
     if (!c) return fail("ctx is NULL");
     HIP_OK(hipSetDevice(c->cfg.device));
@@ -342,30 +375,15 @@ float** out_ptrs(nerf_outputs& o, int i) {
     }
 }
 
-// For host-memory calls: device twins of the requested outputs.
-int make_dev_outputs(nerf_ctx* c, const nerf_outputs* host, long long N, int S, nerf_outputs* dev) {
+// The device pointers of the requested outputs: member i of a host caller's nerf_outputs is staged on b_out[i].
+nerf_outputs stage_outputs(nerf_ctx* c, Staging& st, const nerf_outputs& outs, long long N, int S) {
     const OutSizes sz = out_sizes(S);
-    nerf_outputs h = host ? *host : nerf_outputs{};
-    *dev = nerf_outputs{};
+    nerf_outputs dev = outs;
     for (int i = 0; i < 7; ++i) {
-        if (!*out_ptrs(h, i)) continue;
-        if (int r = ensure(c, c->b_out[i], sz.per_ray[i] * N * sizeof(float))) return r;
-        *out_ptrs(*dev, i) = (float*)c->b_out[i].p;
+        float** p = out_ptrs(dev, i);
+        *p = st.out(c->b_out[i], *p, sz.per_ray[i] * N * sizeof(float));
     }
-    return 0;
-}
-int copy_back_outputs(nerf_ctx* c, const nerf_outputs* host, const nerf_outputs* dev, long long N, int S) {
-    const OutSizes sz = out_sizes(S);
-    nerf_outputs h = host ? *host : nerf_outputs{};
-    nerf_outputs d = *dev;
-    for (int i = 0; i < 7; ++i) {
-        float* hp = *out_ptrs(h, i);
-        if (!hp) continue;
-        HIP_OK(hipMemcpyAsync(hp, *out_ptrs(d, i), sz.per_ray[i] * N * sizeof(float), hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return dev;
 }
 
 // Host-memory render_image: the rows [off, off + n) of every requested output leave for the host on the ctx's COPY stream
@@ -707,11 +725,9 @@ int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_di
     if (int r = ensure(c, c->b_in0, pts * 12)) return r;
     if (int r = ensure(c, c->b_in1, pts * 12)) return r;
     if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    float* out = sigma;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = ensure(c, c->b_lattice, (size_t)points * 4)) return r;
-        out = (float*)c->b_lattice.p;
-    }
+    Staging st(c, mem);
+    float* out = st.out(c->b_lattice, sigma, (size_t)points * 4);
+    if (st.err) return st.err;
     float *xyz = (float*)c->b_in0.p, *view = c->cfg.n_angles != 0 ? (float*)c->b_in1.p : nullptr, *raw = (float*)c->b_raw.p;
     for (long long begin = 0; begin < points; begin += kMeshChunk) {
         const long long m = std::min(kMeshChunk, points - begin);
@@ -720,11 +736,7 @@ int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_di
         launch_raw_sigma(raw, m, out + begin, c->stream);
     }
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(sigma, out, (size_t)points * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem) {
@@ -737,32 +749,21 @@ int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float*
     RenderKernel k;
     if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
     const size_t pts = (size_t)std::min((long long)V, kMeshChunk);
-    const bool host = mem == NERF_MEM_HOST;
     if (int r = ensure(c, c->b_in1, pts * 12)) return r;
     if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    if (host) {
-        if (int r = ensure(c, c->b_in0, pts * 12)) return r;
-        if (int r = ensure(c, c->b_in2, pts * 12)) return r;
-        if (int r = ensure(c, c->b_out[0], pts * 12)) return r;
-    }
     float *view = (float*)c->b_in1.p, *raw = (float*)c->b_raw.p;
-    for (long long begin = 0; begin < V; begin += kMeshChunk) {
+    for (long long begin = 0; begin < V; begin += kMeshChunk) {      // a host caller's chunk is staged, and leaves, by itself
         const long long m = std::min(kMeshChunk, (long long)V - begin);
-        const float *xyz = vertices + 3 * begin, *nrm = normals + 3 * begin;
-        float* out = rgb + 3 * begin;
-        if (host) {
-            HIP_OK(hipMemcpyAsync(c->b_in0.p, xyz, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
-            HIP_OK(hipMemcpyAsync(c->b_in2.p, nrm, (size_t)m * 12, hipMemcpyHostToDevice, c->stream));
-            xyz = (const float*)c->b_in0.p; nrm = (const float*)c->b_in2.p; out = (float*)c->b_out[0].p;
-        }
+        Staging st(c, mem);
+        const float* xyz = st.in(c->b_in0, vertices + 3 * begin, (size_t)m * 12);
+        const float* nrm = st.in(c->b_in2, normals + 3 * begin, (size_t)m * 12);
+        float* out = st.out(c->b_out[0], rgb + 3 * begin, (size_t)m * 12);
+        if (st.err) return st.err;
         launch_mesh_view(nrm, m, view, c->stream);
         if (int r = run_mlp(c, which, k, xyz, c->cfg.n_angles != 0 ? view : nullptr, nullptr, raw, m, 1, 1)) return r;
         launch_raw_rgb(raw, m, out, c->stream);
         HIP_OK(hipGetLastError());
-        if (host) {
-            HIP_OK(hipMemcpyAsync(rgb + 3 * begin, out, (size_t)m * 12, hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-        }
+        if (int r = st.finish()) return r;
     }
     return 0;
 }
@@ -790,18 +791,12 @@ int nerf_get_rays_directions(nerf_ctx* c, const float* c2w, float fov, int32_t H
     if (!c || !c2w || !dirs) return fail("NULL argument");
     if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
     const long long N = (long long)H * W;
-    float* d = dirs;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = ensure(c, c->b_dirs, N * 16)) return r;
-        d = (float*)c->b_dirs.p;
-    }
+    Staging st(c, mem);
+    float* d = st.out(c->b_dirs, dirs, N * 16);
+    if (st.err) return st.err;
     launch_raygen(c2w, fov, H, W, 0, N, nullptr, d, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(dirs, d, N * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_rays_to_ndc(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float fov, float ndc_near_plane,
@@ -813,21 +808,15 @@ int nerf_rays_to_ndc(nerf_ctx* c, const float* rays_orig, const float* rays_dirs
     if ((out_orig == rays_orig) != (out_dirs == rays_dirs) || out_orig == rays_dirs || out_dirs == rays_orig || out_orig == out_dirs)
         return fail("nerf_rays_to_ndc works in place only as out_orig == rays_orig AND out_dirs == rays_dirs");
     if (N == 0) return 0;
-    const float *o = rays_orig, *d = rays_dirs;
-    float *oo = out_orig, *od = out_dirs;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
-        o = oo = (float*)c->b_orig.p; d = od = (float*)c->b_dirs.p;
-    }
+    Staging st(c, mem);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    float* oo = st.out(c->b_orig, out_orig, (size_t)N * 16);      // (a host caller's rays are converted in their staging buffers)
+    float* od = st.out(c->b_dirs, out_dirs, (size_t)N * 16);
+    if (st.err) return st.err;
     launch_rays_to_ndc(o, d, N, fov, ndc_near_plane, oo, od, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(out_orig, oo, (size_t)N * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(out_dirs, od, (size_t)N * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_get_z_values(nerf_ctx* c, int64_t N, int32_t S, const float* u, uint64_t seed, int64_t ray_base, float* z,
@@ -836,21 +825,14 @@ int nerf_get_z_values(nerf_ctx* c, int64_t N, int32_t S, const float* u, uint64_
     if (!c || !z) return fail("NULL argument");
     if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
     if (int r = sampling_ok(c)) return r;
-    const float* du = u;
-    float* dz = z;
-    if (mem == NERF_MEM_HOST) {
-        if (u) { if (int r = h2d(c, c->b_u0, u, (size_t)N * S * 4)) return r; du = (const float*)c->b_u0.p; }
-        if (int r = ensure(c, c->b_zc, (size_t)N * S * 4)) return r;
-        dz = (float*)c->b_zc.p;
-    }
+    Staging st(c, mem);
+    const float* du = st.in(c->b_u0, u, (size_t)N * S * 4);
+    float* dz = st.out(c->b_zc, z, (size_t)N * S * 4);
+    if (st.err) return st.err;
     launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, S, du, seed, ray_base,
                     dz, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_get_z_values_rays(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, int32_t S, const float* u,
@@ -859,23 +841,15 @@ int nerf_get_z_values_rays(nerf_ctx* c, const float* rays_orig, const float* ray
     if (!rays_orig || !rays_dirs || !z) return fail("NULL argument");
     if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
     if (int r = sampling_ok(c)) return r;
-    const float *o = rays_orig, *d = rays_dirs, *du = u;
-    float* dz = z;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
-        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p;
-        if (u) { if (int r = h2d(c, c->b_u0, u, (size_t)N * S * 4)) return r; du = (const float*)c->b_u0.p; }
-        if (int r = ensure(c, c->b_zc, (size_t)N * S * 4)) return r;
-        dz = (float*)c->b_zc.p;
-    }
+    Staging st(c, mem);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    const float* du = st.in(c->b_u0, u, (size_t)N * S * 4);
+    float* dz = st.out(c->b_zc, z, (size_t)N * S * 4);
+    if (st.err) return st.err;
     if (int r = draw_z_values(c, o, d, N, S, du, seed, ray_base, dz)) return r;
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(z, dz, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_ray_box_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds, int32_t* narrowed,
@@ -884,24 +858,15 @@ int nerf_ray_box_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_d
     if (!rays_orig || !rays_dirs || !bounds) return fail("NULL argument");
     if (N < 0) return fail("bad shape N=%lld", (long long)N);
     if (!c->box_on) return fail("no scene box is set (nerf_ctx_set_scene_box)");
-    const float *o = rays_orig, *d = rays_dirs;
-    float* db = bounds;
-    int32_t* dn = narrowed;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
-        if (int r = ensure(c, c->b_in0, (size_t)N * 8)) return r;
-        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; db = (float*)c->b_in0.p;
-        if (narrowed) { if (int r = ensure(c, c->b_in1, (size_t)N * 4)) return r; dn = (int32_t*)c->b_in1.p; }
-    }
+    Staging st(c, mem);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    float* db = st.out(c->b_in0, bounds, (size_t)N * 8);
+    int32_t* dn = st.out(c->b_in1, narrowed, (size_t)N * 4);
+    if (st.err) return st.err;
     launch_ray_box_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, db, dn, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(bounds, db, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-        if (narrowed) HIP_OK(hipMemcpyAsync(narrowed, dn, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_ray_occupancy_bounds(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, int64_t N, float* bounds,
@@ -910,25 +875,16 @@ int nerf_ray_occupancy_bounds(nerf_ctx* c, const float* rays_orig, const float* 
     if (!rays_orig || !rays_dirs || !bounds) return fail("NULL argument");
     if (N < 0) return fail("bad shape N=%lld", (long long)N);
     if (!c->box_on || c->grid_R == 0) return fail("no occupancy grid is set (nerf_ctx_set_occupancy_grid, nerf_occupancy_bake)");
-    const float *o = rays_orig, *d = rays_dirs;
-    float* db = bounds;
-    int32_t* ds = state;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
-        if (int r = ensure(c, c->b_in0, (size_t)N * 8)) return r;
-        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; db = (float*)c->b_in0.p;
-        if (state) { if (int r = ensure(c, c->b_in1, (size_t)N * 4)) return r; ds = (int32_t*)c->b_in1.p; }
-    }
+    Staging st(c, mem);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    float* db = st.out(c->b_in0, bounds, (size_t)N * 8);
+    int32_t* ds = st.out(c->b_in1, state, (size_t)N * 4);
+    if (st.err) return st.err;
     launch_ray_grid_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R,
                            o, d, N, db, ds, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(bounds, db, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-        if (state) HIP_OK(hipMemcpyAsync(state, ds, (size_t)N * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 // ---- sample culling (cull_kernels.hip) ----
@@ -951,22 +907,15 @@ int nerf_sample_occupancy(nerf_ctx* c, const float* rays_orig, const float* rays
     if (N < 0 || S <= 0) return fail("bad shape N=%lld S=%d", (long long)N, S);
     if (!c->box_on || c->grid_R == 0) return fail("no occupancy grid is set (nerf_ctx_set_occupancy_grid, nerf_occupancy_bake)");
     if (N == 0) return 0;
-    const float *o = rays_orig, *d = rays_dirs, *dz = z;
-    int32_t* dk = keep;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_orig, rays_orig, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_dirs, rays_dirs, (size_t)N * 16)) return r;
-        if (int r = h2d(c, c->b_zc, z, (size_t)N * S * 4)) return r;
-        if (int r = ensure(c, c->b_in0, (size_t)N * S * 4)) return r;
-        o = (const float*)c->b_orig.p; d = (const float*)c->b_dirs.p; dz = (const float*)c->b_zc.p; dk = (int32_t*)c->b_in0.p;
-    }
+    Staging st(c, mem);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    const float* dz = st.in(c->b_zc, z, (size_t)N * S * 4);
+    int32_t* dk = st.out(c->b_in0, keep, (size_t)N * S * 4);
+    if (st.err) return st.err;
     launch_sample_keep(c->box, (const uint32_t*)c->b_grid[c->grid_cur].p, c->grid_R, o, d, dz, N, S, nullptr, dk, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(keep, dk, (size_t)N * S * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_ctx_read_culling(nerf_ctx* c, int64_t* samples, int64_t* kept) {
@@ -1003,24 +952,16 @@ int nerf_sample_pdf(nerf_ctx* c, const float* weights, const float* z, int64_t N
     if (!c || !weights || !z) return fail("NULL argument");
     if (N < 0 || S < 2 || Sf <= 0) return fail("bad shape N=%lld S=%d Sf=%d (need S>=2, Sf>=1)", (long long)N, S, Sf);
     if (sample_pdf_lds_bytes(S, Sf) > 64 * 1024) return fail("S=%d Sf=%d exceeds the sampler's LDS budget", S, Sf);
-    const float *dw = weights, *dz = z, *du = u;
-    float *dn = z_new, *dm = z_merged;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_in0, weights, (size_t)N * S * 4)) return r;
-        if (int r = h2d(c, c->b_in1, z, (size_t)N * S * 4)) return r;
-        dw = (const float*)c->b_in0.p; dz = (const float*)c->b_in1.p;
-        if (u) { if (int r = h2d(c, c->b_u1, u, (size_t)N * Sf * 4)) return r; du = (const float*)c->b_u1.p; }
-        if (z_new) { if (int r = ensure(c, c->b_in2, (size_t)N * Sf * 4)) return r; dn = (float*)c->b_in2.p; }
-        if (z_merged) { if (int r = ensure(c, c->b_zf, (size_t)N * (S + Sf) * 4)) return r; dm = (float*)c->b_zf.p; }
-    }
+    Staging st(c, mem);
+    const float* dw = st.in(c->b_in0, weights, (size_t)N * S * 4);
+    const float* dz = st.in(c->b_in1, z, (size_t)N * S * 4);
+    const float* du = st.in(c->b_u1, u, (size_t)N * Sf * 4);
+    float* dn = st.out(c->b_in2, z_new, (size_t)N * Sf * 4);
+    float* dm = st.out(c->b_zf, z_merged, (size_t)N * (S + Sf) * 4);
+    if (st.err) return st.err;
     launch_sample_pdf(dw, dz, N, S, Sf, du, seed, ray_base, dn, dm, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        if (z_new) HIP_OK(hipMemcpyAsync(z_new, dn, (size_t)N * Sf * 4, hipMemcpyDeviceToHost, c->stream));
-        if (z_merged) HIP_OK(hipMemcpyAsync(z_merged, dm, (size_t)N * (S + Sf) * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_positional_encoding(nerf_ctx* c, const float* x, int64_t M, int32_t n_enc, int32_t passthrough, float* out,
@@ -1029,20 +970,13 @@ int nerf_positional_encoding(nerf_ctx* c, const float* x, int64_t M, int32_t n_e
     if (!c || !x || !out) return fail("NULL argument");
     if (M < 0 || n_enc < 0 || n_enc > 16) return fail("bad shape M=%lld n_enc=%d", (long long)M, n_enc);
     const size_t per = 3 * ((passthrough ? 1 : 0) + 2 * (size_t)n_enc);
-    const float* dx = x;
-    float* dout = out;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_in0, x, (size_t)M * 12)) return r;
-        if (int r = ensure(c, c->b_in1, (size_t)M * per * 4)) return r;
-        dx = (const float*)c->b_in0.p; dout = (float*)c->b_in1.p;
-    }
+    Staging st(c, mem);
+    const float* dx = st.in(c->b_in0, x, (size_t)M * 12);
+    float* dout = st.out(c->b_in1, out, (size_t)M * per * 4);
+    if (st.err) return st.err;
     launch_posenc(dx, M, n_enc, passthrough, dout, c->stream);
     HIP_OK(hipGetLastError());
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(out, dout, (size_t)M * per * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_model_predict(nerf_ctx* c, int which, const float* xyz, const float* view_dirs, int64_t M, float* raw,
@@ -1052,23 +986,15 @@ int nerf_model_predict(nerf_ctx* c, int which, const float* xyz, const float* vi
     if (!c || !xyz || !raw || (!view_dirs && c->cfg.n_angles != 0)) return fail("NULL argument");
     if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
     if (M < 0) return fail("bad M");
-    const float *dx = xyz, *dv = view_dirs;
-    float* dr = raw;
-    if (mem == NERF_MEM_HOST) {
-        if (int r = h2d(c, c->b_in0, xyz, (size_t)M * 12)) return r;
-        if (view_dirs)
-            if (int r = h2d(c, c->b_in1, view_dirs, (size_t)M * 12)) return r;
-        if (int r = ensure(c, c->b_raw, (size_t)M * 16)) return r;
-        dx = (const float*)c->b_in0.p; dv = view_dirs ? (const float*)c->b_in1.p : nullptr; dr = (float*)c->b_raw.p;
-    }
+    Staging st(c, mem);
+    const float* dx = st.in(c->b_in0, xyz, (size_t)M * 12);
+    const float* dv = st.in(c->b_in1, view_dirs, (size_t)M * 12);
+    float* dr = st.out(c->b_raw, raw, (size_t)M * 16);
+    if (st.err) return st.err;
     RenderKernel k;
     if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
     if (int r = run_mlp(c, which, k, dx, dv, nullptr, dr, M, 1, 1)) return r;
-    if (mem == NERF_MEM_HOST) {
-        HIP_OK(hipMemcpyAsync(raw, dr, (size_t)M * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return st.finish();
 }
 
 int nerf_ray_marching(nerf_ctx* c, const float* raw, const float* z, int64_t N, int32_t S, const nerf_outputs* outs,
@@ -1076,23 +1002,15 @@ int nerf_ray_marching(nerf_ctx* c, const float* raw, const float* z, int64_t N, 
     ENTER(c);
     if (!c || !raw || !z || !outs) return fail("NULL argument");
     if (N < 0 || S <= 0) return fail("bad shape");
-    if (mem == NERF_MEM_DEVICE) {
-        launch_composite(raw, z, N, S, outs->rgb, outs->weights, outs->cumprod, outs->alpha, outs->rgb_samples,
-                         outs->depth, c->stream);
-        if (outs->z && outs->z != z)
-            HIP_OK(hipMemcpyAsync(outs->z, z, (size_t)N * S * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    if (int r = h2d(c, c->b_raw, raw, (size_t)N * S * 16)) return r;
-    if (int r = h2d(c, c->b_zc, z, (size_t)N * S * 4)) return r;
-    nerf_outputs dev;
-    if (int r = make_dev_outputs(c, outs, N, S, &dev)) return r;
-    launch_composite((const float*)c->b_raw.p, (const float*)c->b_zc.p, N, S, dev.rgb, dev.weights, dev.cumprod,
-                     dev.alpha, dev.rgb_samples, dev.depth, c->stream);
-    if (dev.z) HIP_OK(hipMemcpyAsync(dev.z, c->b_zc.p, (size_t)N * S * 4, hipMemcpyDeviceToDevice, c->stream));
+    Staging st(c, mem);
+    const float* dr = st.in(c->b_raw, raw, (size_t)N * S * 16);
+    const float* dz = st.in(c->b_zc, z, (size_t)N * S * 4);
+    const nerf_outputs dev = stage_outputs(c, st, *outs, N, S);
+    if (st.err) return st.err;
+    launch_composite(dr, dz, N, S, dev.rgb, dev.weights, dev.cumprod, dev.alpha, dev.rgb_samples, dev.depth, c->stream);
+    if (dev.z && dev.z != dz) HIP_OK(hipMemcpyAsync(dev.z, dz, (size_t)N * S * 4, hipMemcpyDeviceToDevice, c->stream));
     HIP_OK(hipGetLastError());
-    return copy_back_outputs(c, outs, &dev, N, S);
+    return st.finish();
 }
 
 int nerf_render_rays(nerf_ctx* c, int which, const float* o, const float* d, const float* z, int64_t N, int32_t S,
@@ -1101,16 +1019,14 @@ int nerf_render_rays(nerf_ctx* c, int which, const float* o, const float* d, con
     if (!c || !o || !d || !z || !outs) return fail("NULL argument");
     if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
     if (N < 0 || S <= 0) return fail("bad shape");
-    if (mem == NERF_MEM_DEVICE) return dev_render_rays(c, which, o, d, z, N, S, *outs);
-    if (int r = h2d(c, c->b_orig, o, (size_t)N * 16)) return r;
-    if (int r = h2d(c, c->b_dirs, d, (size_t)N * 16)) return r;
-    if (int r = h2d(c, c->b_zc, z, (size_t)N * S * 4)) return r;
-    nerf_outputs dev;
-    if (int r = make_dev_outputs(c, outs, N, S, &dev)) return r;
-    if (int r = dev_render_rays(c, which, (const float*)c->b_orig.p, (const float*)c->b_dirs.p,
-                                (const float*)c->b_zc.p, N, S, dev))
-        return r;
-    return copy_back_outputs(c, outs, &dev, N, S);
+    Staging st(c, mem);
+    const float* so = st.in(c->b_orig, o, (size_t)N * 16);
+    const float* sd = st.in(c->b_dirs, d, (size_t)N * 16);
+    const float* sz = st.in(c->b_zc, z, (size_t)N * S * 4);
+    const nerf_outputs dev = stage_outputs(c, st, *outs, N, S);
+    if (st.err) return st.err;
+    if (int r = dev_render_rays(c, which, so, sd, sz, N, S, dev)) return r;
+    return st.finish();
 }
 
 int nerf_render(nerf_ctx* c, const float* o, const float* d, int64_t N, int32_t Sc, int32_t Sf, const float* u_c,
@@ -1121,18 +1037,15 @@ int nerf_render(nerf_ctx* c, const float* o, const float* d, int64_t N, int32_t 
     const bool fine = Sf > 0 && c->net[NERF_NET_FINE].loaded;
     const int S = fine ? Sc + Sf : Sc;
     if (fine && sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024) return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget", Sc, Sf);
-    if (mem == NERF_MEM_DEVICE) return dev_render(c, o, d, N, Sc, Sf, u_c, u_f, seed, ray_base, *outs);
-    if (int r = h2d(c, c->b_orig, o, (size_t)N * 16)) return r;
-    if (int r = h2d(c, c->b_dirs, d, (size_t)N * 16)) return r;
-    const float *duc = nullptr, *duf = nullptr;
-    if (u_c) { if (int r = h2d(c, c->b_u0, u_c, (size_t)N * Sc * 4)) return r; duc = (const float*)c->b_u0.p; }
-    if (u_f && fine) { if (int r = h2d(c, c->b_u1, u_f, (size_t)N * Sf * 4)) return r; duf = (const float*)c->b_u1.p; }
-    nerf_outputs dev;
-    if (int r = make_dev_outputs(c, outs, N, S, &dev)) return r;
-    if (int r = dev_render(c, (const float*)c->b_orig.p, (const float*)c->b_dirs.p, N, Sc, Sf, duc, duf, seed,
-                           ray_base, dev))
-        return r;
-    return copy_back_outputs(c, outs, &dev, N, S);
+    Staging st(c, mem);
+    const float* so = st.in(c->b_orig, o, (size_t)N * 16);
+    const float* sd = st.in(c->b_dirs, d, (size_t)N * 16);
+    const float* duc = st.in(c->b_u0, u_c, (size_t)N * Sc * 4);
+    const float* duf = st.in(c->b_u1, fine ? u_f : nullptr, (size_t)N * Sf * 4);      // (without a fine pass nothing reads u_f)
+    const nerf_outputs dev = stage_outputs(c, st, *outs, N, S);
+    if (st.err) return st.err;
+    if (int r = dev_render(c, so, sd, N, Sc, Sf, duc, duf, seed, ray_base, dev)) return r;
+    return st.finish();
 }
 
 int nerf_render_image(nerf_ctx* c, const float* c2w, float fov, int32_t H, int32_t W, int64_t ray_begin,
@@ -1170,7 +1083,9 @@ int nerf_render_image(nerf_ctx* c, const float* c2w, float fov, int32_t H, int32
     if (mem == NERF_MEM_HOST) {
         if (u_c) { if (int r = h2d(c, c->b_u0, u_c + ray_begin * Sc, (size_t)N * Sc * 4)) return r; duc = (const float*)c->b_u0.p; }
         if (u_f && fine) { if (int r = h2d(c, c->b_u1, u_f + ray_begin * Sf, (size_t)N * Sf * 4)) return r; duf = (const float*)c->b_u1.p; }
-        if (int r = make_dev_outputs(c, outs, N, S, &dev)) return r;
+        Staging st(c, mem);      // never finished: the outputs leave batch by batch on the copy stream (copy_back_batch)
+        dev = stage_outputs(c, st, *outs, N, S);
+        if (st.err) return st.err;
     } else {
         if (u_c) duc = u_c + ray_begin * Sc;
         if (u_f) duf = u_f + ray_begin * Sf;

@@ -74,7 +74,11 @@ struct nerf_ctx {
     hipStream_t copy_stream = nullptr;         // device-to-host copies of nerf_render_image(NERF_MEM_HOST), beside the kernels
     std::vector<hipEvent_t> copy_ev;           // "batch k is done" events the copy stream waits on (ring)
     nerf::NetWeights net[2];
-    // scratch arena (grow-only)
+    // scratch arena (grow-only).  Staging (nerf::Staging, host-memory calls): b_orig, b_dirs (rays), b_u0, b_u1 (draws), b_in0,
+    // b_in1, b_in2 (other arguments), b_out[i] (member i of nerf_outputs); an entry also stages in b_zc, b_zf or b_raw where the
+    // passes it runs leave that buffer alone.  The passes (draw_z_values, dev_render, dev_render_rays, run_mlp's callers, the
+    // bake): b_zc, b_zf, b_raw, b_wc here, b_g* and b_c* above; the bake, the lattice and the vertex colours also generate their
+    // points into b_in0 / b_in1.
     nerf::DevBuf b_orig, b_dirs, b_zc, b_zf, b_raw, b_wc, b_u0, b_u1, b_in0, b_in1, b_in2;
     nerf::DevBuf b_out[7];
     // timing
@@ -92,6 +96,32 @@ namespace nerf {
 int ensure(nerf_ctx* c, DevBuf& b, size_t bytes);   // grow-only device buffer
 int h2d(nerf_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int enter(nerf_ctx* c);                             // NULL check + hipSetDevice
+// library buffer -> caller's buffer (device to host, or device to device, by `mem`) and caller's buffer -> library buffer, on the
+// ctx stream; neither synchronises: a host caller's entry point does, once
+int copy_to_caller(nerf_ctx* c, void* dst, const void* src_dev, size_t bytes, int mem);
+int copy_from_caller(nerf_ctx* c, void* dst_dev, const void* src, size_t bytes, int mem);
+
+// The pointer arguments of one entry point that takes `int mem`: made at its top, finished at its end.  For a device caller
+// in() and out() hand the caller's pointer back and finish() does nothing (the call stays asynchronous); for a host caller in()
+// uploads into `b`, out() grows `b` and remembers the copy back, finish() enqueues those copies in the order they were
+// registered and synchronises once.  A NULL argument gives NULL.  The caller names the buffer: which arena buffers a pass
+// leaves alone is the entry point's knowledge (see the arena in nerf_ctx).  An output registered on the buffer its input was
+// staged into shares it (nerf_rays_to_ndc in place).  A failure is kept in `err` and makes every later in() / out() a no-op
+// that gives NULL: check it once, before the launches; a call that returns before finish() copies nothing back.
+struct Staging {
+    Staging(nerf_ctx* c, int mem);
+    template <class T> const T* in(DevBuf& b, const T* src, size_t bytes) { return (const T*)stage(b, (void*)src, bytes, true); }
+    template <class T> T* out(DevBuf& b, T* dst, size_t bytes) { return (T*)stage(b, dst, bytes, false); }
+    int finish();
+    int err = 0;
+
+private:
+    void* stage(DevBuf& b, void* caller, size_t bytes, bool upload);
+    nerf_ctx* c;
+    bool host;
+    struct { void* dst; const void* src; size_t bytes; } back[7];   // (nerf_outputs has the most outputs of any entry: seven)
+    int n_back = 0;
+};
 #define ENTER(c) do { if (int r__ = nerf::enter(c)) return r__; } while (0)
 int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's bounds suit its sampling mode (lindisp: near > 0)
 // The coarse depths of N rays as this ctx draws them (bounds, sampling mode, scene box, occupancy grid): every call site that

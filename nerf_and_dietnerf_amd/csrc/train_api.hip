@@ -757,14 +757,6 @@ int ensure_bwd_workspace(nerf_ctx* c, TrainState* t, long long Mmax, long long M
     return r;
 }
 
-int stage_in(nerf_ctx* c, DevBuf& b, const float* src, size_t bytes, int mem, const float** out) {
-    if (!src) { *out = nullptr; return 0; }
-    if (mem == NERF_MEM_DEVICE) { *out = src; return 0; }
-    if (int r = h2d(c, b, src, bytes)) return r;
-    *out = (const float*)b.p;
-    return 0;
-}
-
 int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const float* target, int64_t N, int Sc,
                    int Sf, const float* u_c, const float* u_f, uint64_t seed, int mem) {
     TrainState* t = c->train;
@@ -774,12 +766,13 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
     if (int r = sampling_ok(c)) return r;
     const size_t f = sizeof(float);
-    const float *o, *d, *tg, *uc, *uf;
-    if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
-    if (int r = stage_in(c, t->d, rays_d, N * 4 * f, mem, &d)) return r;
-    if (int r = stage_in(c, t->tgt, target, N * 3 * f, mem, &tg)) return r;
-    if (int r = stage_in(c, t->u_c, u_c, (size_t)N * Sc * f, mem, &uc)) return r;
-    if (int r = stage_in(c, t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f, mem, &uf)) return r;
+    Staging st(c, mem);      // inputs only: the outputs are the trainer's own buffers, and leave through copy_out
+    const float* o = st.in(t->o, rays_o, N * 4 * f);
+    const float* d = st.in(t->d, rays_d, N * 4 * f);
+    const float* tg = st.in(t->tgt, target, N * 3 * f);
+    const float* uc = st.in(t->u_c, u_c, (size_t)N * Sc * f);
+    const float* uf = st.in(t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f);
+    if (st.err) return st.err;
 
     const PassDims dc = pass_dims(N, Sc), df = pass_dims(N, Sf);     // the fine pass renders the Sf new samples only
     int r = ensure_pass(c, t->pass[0], dc);
@@ -1014,12 +1007,13 @@ int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d,
     bool fine;
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
     const size_t f = sizeof(float);
-    const float *o, *d, *dr, *uc, *uf;
-    if (int r = stage_in(c, t->o, rays_o, N * 4 * f, mem, &o)) return r;
-    if (int r = stage_in(c, t->d, rays_d, N * 4 * f, mem, &d)) return r;
-    if (int r = stage_in(c, t->tgt, d_rgb_in, N * 3 * f, mem, &dr)) return r;
-    if (int r = stage_in(c, t->u_c, u_c, (size_t)N * Sc * f, mem, &uc)) return r;
-    if (int r = stage_in(c, t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f, mem, &uf)) return r;
+    Staging st(c, mem);
+    const float* o = st.in(t->o, rays_o, N * 4 * f);
+    const float* d = st.in(t->d, rays_d, N * 4 * f);
+    const float* dr = st.in(t->tgt, d_rgb_in, N * 3 * f);
+    const float* uc = st.in(t->u_c, u_c, (size_t)N * Sc * f);
+    const float* uf = st.in(t->u_f, fine ? u_f : nullptr, (size_t)N * (fine ? Sf : 0) * f);
+    if (st.err) return st.err;
     const PassDims dc = pass_dims(N, Sc), df = pass_dims(N, Sc + Sf);
     if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate)) return r;
     SlotLease lease(c, t);                        // (no slot: the activations stay in TrainState::pass)
@@ -1041,10 +1035,8 @@ int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float*
     const size_t f = sizeof(float);
     // the slot keeps its own copies of the rays and draws: the caller's buffers need not outlive this call
     auto keep = [&](DevBuf& b, const float* src, size_t bytes) -> int {
-        if (mem == NERF_MEM_HOST) return h2d(c, b, src, bytes);
         if (int r = ensure(c, b, bytes)) return r;
-        HIP_OK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-        return 0;
+        return copy_from_caller(c, b.p, src, bytes, mem);
     };
     if (int r = keep(s.o, rays_o, N * 4 * f)) return r;
     if (int r = keep(s.d, rays_d, N * 4 * f)) return r;
@@ -1073,8 +1065,9 @@ int render_backward_impl(nerf_ctx* c, int slot, const float* d_rgb_in, bool accu
     RenderSlot& s = t->slots[slot];
     const bool fine = s.Sf > 0;
     const PassDims dc = pass_dims(s.N, s.Sc), df = pass_dims(s.N, s.Sc + s.Sf);
-    const float* dr;
-    if (int r = stage_in(c, t->tgt, d_rgb_in, s.N * 3 * sizeof(float), mem, &dr)) return r;
+    Staging st(c, mem);
+    const float* dr = st.in(t->tgt, d_rgb_in, s.N * 3 * sizeof(float));
+    if (st.err) return st.err;
     if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate)) return r;
     s.valid = false;                              // consumed, whatever happens below
     SlotLease lease(c, t, &s);
@@ -1088,13 +1081,12 @@ int render_backward_impl(nerf_ctx* c, int slot, const float* d_rgb_in, bool accu
 int copy_out(nerf_ctx* c, int mem, int Sf, float* grad_coarse, float* grad_fine, float* rgb_out = nullptr,
              const void* rgb = nullptr, long long N = 0) {
     const TrainState* t = c->train;
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const size_t nb = t->nblob * sizeof(float);
-    if (rgb_out) HIP_OK(hipMemcpyAsync(rgb_out, rgb, N * 3 * sizeof(float), kind, c->stream));
-    if (grad_coarse) HIP_OK(hipMemcpyAsync(grad_coarse, t->net[0].grad, nb, kind, c->stream));
+    if (rgb_out) if (int r = copy_to_caller(c, rgb_out, rgb, N * 3 * sizeof(float), mem)) return r;
+    if (grad_coarse) if (int r = copy_to_caller(c, grad_coarse, t->net[0].grad, nb, mem)) return r;
     if (grad_fine) {
         if (!(Sf > 0 && t->net[1].present)) return fail("grad_fine requested but no fine pass ran (Sf = %d)", Sf);
-        HIP_OK(hipMemcpyAsync(grad_fine, t->net[1].grad, nb, kind, c->stream));
+        if (int r = copy_to_caller(c, grad_fine, t->net[1].grad, nb, mem)) return r;
     }
     if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
@@ -1414,11 +1406,10 @@ int nerf_train_apply(nerf_ctx* c, const float* grad_coarse, const float* grad_fi
     ENTER(c);
     TrainState* t = c->train;
     if (!t) return fail("nerf_train_begin has not been called");
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (grad_coarse) HIP_OK(hipMemcpyAsync(t->net[0].grad, grad_coarse, t->nblob * sizeof(float), kind, c->stream));
+    if (grad_coarse) if (int r = copy_from_caller(c, t->net[0].grad, grad_coarse, t->nblob * sizeof(float), mem)) return r;
     if (grad_fine) {
         if (!t->net[1].present) return fail("grad_fine given but no fine network is loaded");
-        HIP_OK(hipMemcpyAsync(t->net[1].grad, grad_fine, t->nblob * sizeof(float), kind, c->stream));
+        if (int r = copy_from_caller(c, t->net[1].grad, grad_fine, t->nblob * sizeof(float), mem)) return r;
     }
     if (mem == NERF_MEM_HOST && (grad_coarse || grad_fine)) HIP_OK(hipStreamSynchronize(c->stream));
     // LossScaleOptimizer.apply_gradients: test what is about to be applied (the caller's all-reduced blobs, or the ctx's
@@ -1454,8 +1445,7 @@ int nerf_train_get_gradients(nerf_ctx* c, int which, float* blob, size_t n_float
     if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail("which must be 0 (coarse) or 1 (fine)");
     if (!t->net[which].present) return fail("network %d has no weights loaded", which);
     if (n_floats != t->nblob) return fail("gradient blob has %zu floats, expected %zu", n_floats, t->nblob);
-    const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIP_OK(hipMemcpyAsync(blob, t->net[which].grad, t->nblob * sizeof(float), kind, c->stream));
+    if (int r = copy_to_caller(c, blob, t->net[which].grad, t->nblob * sizeof(float), mem)) return r;
     if (mem == NERF_MEM_HOST) HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1469,8 +1459,7 @@ int nerf_get_weights(nerf_ctx* c, int which, float* blob, size_t n_floats, int m
     if (n_floats != want) return fail("weight blob has %zu floats, expected %zu", n_floats, want);
     TrainState* t = c->train;
     if (t && t->net[which].present) {
-        const hipMemcpyKind kind = mem == NERF_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIP_OK(hipMemcpyAsync(blob, t->net[which].blob, want * sizeof(float), kind, c->stream));
+        if (int r = copy_to_caller(c, blob, t->net[which].blob, want * sizeof(float), mem)) return r;
         HIP_OK(hipStreamSynchronize(c->stream));
         return 0;
     }

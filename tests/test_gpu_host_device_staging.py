@@ -1,0 +1,292 @@
+"""Host memory in and out against device memory in and out, bit for bit, for every entry point of the C ABI that stages its
+arguments through nerf::Staging (csrc/nerf_ctx.h): each Context method is called once with numpy arrays and once with the same
+data as torch-device tensors, on ONE context, and every returned array must hold the same bits.  The ray counts run 63 (less
+than a wavefront) -> 143 (a 128-row tile and a tail) -> 63 over the whole module, so every staging buffer first grows and is then
+reused with stale contents past the end of the smaller call."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+BOX = ((-1.5, -1.5, -2.2), (1.5, 1.5, 0.5))
+GRID = np.random.default_rng(8).random((8, 8, 8)) < 0.5      # about half full
+SC, SF, ROWS, LATTICE = 8, 8, 130, 5
+IMAGES = {63: (9, 7), 143: (13, 11)}
+
+
+@pytest.fixture(scope="module")
+def ctx(golden_ckpt):
+    import nerf_and_dietnerf_amd as N
+    c = N.Context(near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]), precision="f16x3")
+    c.load_weights(0, golden_ckpt["blob_coarse"])
+    c.load_weights(1, golden_ckpt["blob_fine"])
+    c.set_scene_box(*BOX)
+    c.set_occupancy_grid(GRID)
+    yield c
+    c.close()
+
+
+def scene(oracle, golden_ckpt, n):
+    """The n rays of an IMAGES[n] picture of the golden test camera (it stands inside the box), the last five moved above the box
+    and turned round (they miss it), and seeded inputs for every entry that takes these rays."""
+    h, w = IMAGES[n]
+    c2w, fov = np.asarray(golden_ckpt["c2w_test"], np.float32), float(golden_ckpt["fov"])
+    near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
+    d = np.ascontiguousarray(oracle.get_rays_directions(h, w, fov, c2w).reshape(-1, 4), np.float32)
+    d[-5:, :3] *= -1.0
+    o = np.ascontiguousarray(np.broadcast_to(c2w[:, 3], d.shape), np.float32)
+    o[-5:, 2] += 3.0
+    rng = np.random.default_rng(n)
+    return dict(n=n, h=h, w=w, c2w=c2w, fov=fov, near=near, far=far, o=o, d=d,
+                u_c=rng.random((n, SC), dtype=np.float32), u_f=rng.random((n, SF), dtype=np.float32),
+                z=np.sort(rng.uniform(near, far, (n, SC)).astype(np.float32), axis=1),
+                weights=rng.random((n, SC), dtype=np.float32) + np.float32(1e-3),
+                raw=rng.standard_normal((n, SC, 4)).astype(np.float32),
+                tgt=rng.random((n, 3), dtype=np.float32), d_rgb=(rng.standard_normal((n, 3)) * 0.1).astype(np.float32))
+
+
+# module-scoped and parametrised: pytest runs every test below at 63 rays, then every test at 143, then every test at 63 again
+@pytest.fixture(scope="module", params=[63, 143, 63], ids=["63", "143", "63-again"])
+def p(request, oracle, golden_ckpt):
+    return scene(oracle, golden_ckpt, request.param)
+
+
+@pytest.fixture(scope="module")
+def trainer(ctx):
+    ctx.train_begin(5e-4)      # the float32 policy
+    yield ctx
+    ctx.train_end()
+
+
+def _host(a):
+    return a
+
+
+def _device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _bits(a):
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(case):
+    """case(put) makes one call with its array arguments passed through ``put`` and returns an array, or a tuple of arrays,
+    Nones and plain values: the host call's against the device call's.  -> the host call's results."""
+    host, dev = case(_host), case(_device)
+    host, dev = (r if isinstance(r, (tuple, list)) else (r,) for r in (host, dev))
+    assert len(host) == len(dev)
+    for i, (a, b) in enumerate(zip(host, dev)):
+        if a is None or isinstance(a, (dict, int, float)):
+            assert a == b, i
+            continue
+        assert isinstance(a, np.ndarray) and b.is_cuda, i
+        b = b.cpu().numpy()
+        assert a.dtype == b.dtype and a.shape == b.shape, (i, a.dtype, b.dtype, a.shape, b.shape)
+        np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=f"output {i}")
+    return host
+
+
+# ---- rays and depths -------------------------------------------------------------------------------------------------------------
+def test_get_rays_directions(ctx, p):
+    (d,) = same(lambda put: ctx.get_rays_directions(p["h"], p["w"], p["fov"], put(p["c2w"])))
+    assert d.shape == (p["h"], p["w"], 4)
+
+
+def test_rays_to_ndc(ctx, p):
+    same(lambda put: ctx.rays_to_ndc(put(p["o"]), put(p["d"]), p["fov"], 1.0))
+
+
+def test_rays_to_ndc_in_place(ctx, p):
+    """The C entry with out == in (the binding never does that): the staged pair shares its buffers."""
+    from nerf_and_dietnerf_amd import _lib
+
+    def case(put):
+        o, d = put(p["o"].copy()), put(p["d"].copy())
+        arr = ctx._arrays(o, d)
+        po, pd = arr.inp(o, (p["n"], 4)), arr.inp(d, (p["n"], 4))
+        _lib.check(ctx.lib.nerf_rays_to_ndc(ctx.h, po, pd, p["n"], p["fov"], 1.0, po, pd, arr.mem))
+        return arr.keep[0], arr.keep[1]
+    in_place = same(case)
+    for a, b in zip(in_place, ctx.rays_to_ndc(p["o"], p["d"], p["fov"], 1.0)):
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+
+
+def test_get_z_values(ctx, p):
+    same(lambda put: ctx.get_z_values(p["near"], p["far"], p["h"], p["w"], SC, put(p["u_c"])))
+
+
+def test_get_z_values_without_u(ctx, p):
+    """Philox draws: the binding goes to the device only for a device ``u``, so this is the C entry itself."""
+    from nerf_and_dietnerf_amd import _lib
+
+    def case(put):
+        arr = ctx._arrays(put(p["o"]))
+        z, pz = arr.out((p["n"], SC))
+        _lib.check(ctx.lib.nerf_get_z_values(ctx.h, p["n"], SC, None, 7, 3, pz, arr.mem))
+        return z
+    same(case)
+
+
+@pytest.mark.parametrize("with_u", [True, False], ids=["u", "philox"])
+def test_get_z_values_for_rays(ctx, p, with_u):
+    same(lambda put: ctx.get_z_values_for_rays(put(p["o"]), put(p["d"]), SC, put(p["u_c"]) if with_u else None, seed=7))
+
+
+def test_ray_box_bounds(ctx, p):
+    bounds, narrowed = same(lambda put: ctx.ray_box_bounds(put(p["o"]), put(p["d"])))
+    assert set(np.unique(narrowed)) == {0, 1}                   # both kinds of ray
+
+
+def test_ray_box_bounds_without_narrowed(ctx, p):
+    """The optional output absent: the C entry with narrowed = NULL."""
+    from nerf_and_dietnerf_amd import _lib
+
+    def case(put):
+        o, d = put(p["o"]), put(p["d"])
+        arr = ctx._arrays(o, d)
+        bounds, pb = arr.out((p["n"], 2))
+        _lib.check(ctx.lib.nerf_ray_box_bounds(ctx.h, arr.inp(o), arr.inp(d), p["n"], pb, None, arr.mem))
+        return bounds
+    (bounds,) = same(case)
+    np.testing.assert_array_equal(_bits(bounds), _bits(ctx.ray_box_bounds(p["o"], p["d"])[0]))
+
+
+def test_ray_occupancy_bounds(ctx, p):
+    bounds, state = same(lambda put: ctx.ray_occupancy_bounds(put(p["o"]), put(p["d"])))
+    assert len(np.unique(state)) >= 2                           # both kinds of ray
+
+
+def test_sample_occupancy(ctx, p):
+    (keep,) = same(lambda put: ctx.sample_occupancy(put(p["o"]), put(p["d"]), put(p["z"])))
+    assert set(np.unique(keep)) == {0, 1}
+
+
+@pytest.mark.parametrize("with_u", [True, False], ids=["u", "philox"])
+def test_get_z_vals_from_prob_dist_func(ctx, p, with_u):
+    same(lambda put: ctx.get_z_vals_from_prob_dist_func(put(p["weights"]), put(p["z"]), SF, put(p["u_f"]) if with_u else None,
+                                                        seed=7, return_merged=True))
+
+
+def test_sample_pdf_with_z_new_alone(ctx, p):
+    """The optional output absent: the C entry with z_merged = NULL (what the binding does without return_merged), and the
+    other way round, z_new = NULL, which only the C entry offers."""
+    from nerf_and_dietnerf_amd import _lib
+    n = p["n"]
+    same(lambda put: ctx.get_z_vals_from_prob_dist_func(put(p["weights"]), put(p["z"]), SF, put(p["u_f"])))
+
+    def case(put):
+        w, z, u = put(p["weights"]), put(p["z"]), put(p["u_f"])
+        arr = ctx._arrays(w, z, u)
+        merged, pm = arr.out((n, SC + SF))
+        _lib.check(ctx.lib.nerf_sample_pdf(ctx.h, arr.inp(w), arr.inp(z), n, SC, SF, arr.inp(u), 0, 0, None, pm, arr.mem))
+        return merged
+    same(case)
+
+
+# ---- the network -----------------------------------------------------------------------------------------------------------------
+def _points():
+    rng = np.random.default_rng(130)
+    xyz = rng.uniform(-1.0, 1.0, (ROWS, 3)).astype(np.float32)
+    view = rng.standard_normal((ROWS, 3)).astype(np.float32)
+    return xyz, view / np.linalg.norm(view, axis=1, keepdims=True).astype(np.float32)
+
+
+@pytest.mark.parametrize("n_enc, passthrough", [(5, True), (4, False)])
+def test_positional_encoding(ctx, p, n_enc, passthrough):
+    xyz, _ = _points()
+    same(lambda put: ctx.positional_encoding(put(xyz), n_enc, passthrough))
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_model_predict(ctx, p, which):
+    xyz, view = _points()
+    (raw,) = same(lambda put: ctx.model_predict(which, put(xyz), put(view)))
+    assert np.isfinite(raw).all() and raw.any()
+
+
+def test_ray_marching(ctx, p):
+    same(lambda put: ctx.ray_marching(put(p["raw"]), put(p["z"])))
+
+
+@pytest.mark.parametrize("culling", [False, True], ids=["plain", "culled"])
+def test_render_rays(ctx, p, culling):
+    ctx.set_sample_culling(culling)
+    try:
+        res = same(lambda put: ctx.render_rays(1, put(p["o"]), put(p["d"]), put(p["z"])))
+    finally:
+        ctx.set_sample_culling(False)
+    assert np.isfinite(res[0]).all()
+
+
+@pytest.mark.parametrize("with_u", [True, False], ids=["u", "philox"])
+def test_render(ctx, p, with_u):
+    res = same(lambda put: ctx.render(put(p["o"]), put(p["d"]), SC, SF, put(p["u_c"]) if with_u else None,
+                                      put(p["u_f"]) if with_u else None, seed=7, want_depth=True))
+    assert len(res) == 7 and np.isfinite(res[0]).all()
+
+
+def test_render_with_some_outputs_absent(ctx, p):
+    """nerf_render with rgb and depth alone, then weights alone: the other members of nerf_outputs are NULL."""
+    from nerf_and_dietnerf_amd import _lib
+    from nerf_and_dietnerf_amd._lib import NerfOutputs
+    n = p["n"]
+
+    def case(put, members):
+        o, d = put(p["o"]), put(p["d"])
+        arr = ctx._arrays(o, d)
+        shapes = {"rgb": (n, 3), "weights": (n, SC + SF), "depth": (n,)}
+        outs, res = NerfOutputs(), []
+        for m in members:
+            a, ptr = arr.out(shapes[m])
+            setattr(outs, m, ptr)
+            res.append(a)
+        _lib.check(ctx.lib.nerf_render(ctx.h, arr.inp(o), arr.inp(d), n, SC, SF, None, None, 7, 0, C.byref(outs), arr.mem))
+        return tuple(res)
+    full = ctx.render(p["o"], p["d"], SC, SF, seed=7, want_depth=True)
+    rgb, depth = same(lambda put: case(put, ("rgb", "depth")))
+    (weights,) = same(lambda put: case(put, ("weights",)))
+    for a, b in ((rgb, full[0]), (weights, full[1]), (depth, full[6])):
+        np.testing.assert_array_equal(_bits(a), _bits(b))
+
+
+# ---- mesh extraction -------------------------------------------------------------------------------------------------------------
+def test_density_lattice_isosurface_mesh_colors(ctx, p):
+    import torch
+    (sigma,) = same(lambda put: ctx.density_lattice(1, LATTICE, device_out=put is _device))
+    (seen,) = same(lambda put: ctx.density_lattice(0, LATTICE, view_dir=put(np.array([0.6, 0.0, 0.8], np.float32))))
+    assert sigma.shape == (LATTICE,) * 3 and np.isfinite(sigma).all()
+    iso = float(np.median(sigma))
+    assert sigma.min() < iso < sigma.max()
+    v, t, nrm = same(lambda put: ctx.isosurface(put(sigma), *BOX, iso))
+    assert len(v) > 0 and len(t) > 0 and t.dtype == np.int32
+    same(lambda put: ctx.isosurface(put(sigma), *BOX, iso, normals=False))      # the optional output of the fetch absent
+    (rgb,) = same(lambda put: ctx.mesh_colors(1, put(v), put(nrm)))
+    assert rgb.shape == v.shape and np.isfinite(rgb).all()
+    torch.cuda.synchronize()
+
+
+# ---- the trainer (float32 policy) ------------------------------------------------------------------------------------------------
+def test_train_gradients(trainer, p):
+    m, gc, gf = same(lambda put: trainer.train_gradients(put(p["o"]), put(p["d"]), put(p["tgt"]), SC, SF, put(p["u_c"]),
+                                                         put(p["u_f"])))
+    assert np.isfinite(gc).all() and gc.any() and gf.any() and np.isfinite(m["loss"])
+
+
+def test_train_render_gradients(trainer, p):
+    rgb, gc, gf = same(lambda put: trainer.train_render_gradients(put(p["o"]), put(p["d"]), put(p["d_rgb"]), SC, SF,
+                                                                  put(p["u_c"]), put(p["u_f"])))
+    assert np.isfinite(rgb).all() and gc.any() and gf.any()
+
+
+def test_train_render_forward_backward(trainer, p):
+    def case(put):
+        rgb = trainer.train_render_forward(0, put(p["o"]), put(p["d"]), SC, SF, put(p["u_c"]), put(p["u_f"]))
+        gc, gf = trainer.train_render_backward(0, put(p["d_rgb"]))
+        return rgb, gc, gf
+    rgb, gc, gf = same(case)
+    assert np.isfinite(rgb).all() and gc.any() and gf.any()
+    trainer.train_render_release()
