@@ -33,7 +33,8 @@ extern "C" {
  * nerf_rays_to_ndc), the scene-box entries (nerf_ctx_set_scene_box, nerf_ray_box_bounds, nerf_get_z_values_rays) and the
  * occupancy-grid entries (nerf_ctx_set_occupancy_grid, nerf_ctx_get_occupancy_grid, nerf_occupancy_bake,
  * nerf_ray_occupancy_bounds) and the mesh entries (nerf_density_lattice, nerf_isosurface, nerf_isosurface_fetch,
- * nerf_mesh_colors), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_mesh_colors) and the distortion-loss entries (nerf_train_set_distortion_weights, nerf_train_read_distortion_sums,
+ * nerf_distortion_loss), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -447,6 +448,34 @@ int nerf_train_set_learning_rate(nerf_ctx* ctx, float learning_rate);
  * MSE(fine) is what its tape differentiates -- (2, 1) here.  The weights act on the gradients and on the `loss` metric
  * (and its running sum); psnr_coarse / psnr_fine stay the plain per-pass values.  Finite, >= 0. */
 int nerf_train_set_loss_weights(nerf_ctx* ctx, float coarse_mse_weight, float fine_mse_weight);
+/* ABI 6+, distortion loss (mip-NeRF 360): a per-ray regulariser on the compositing weights of a pass, which pulls a ray's
+ * weight into one compact interval and pushes weight spread along the ray ("floaters") to zero.  For a ray with depths
+ * z_0 <= ... <= z_{S-1} and compositing weights w_i (the `weights` output of the pass), with the ctx's bounds
+ * (nerf_ctx_set_bounds; 0 and 1 for NDC rays):
+ *     t_i = (z_i - near) / (far - near),  t_S = 1;  sample i owns [t_i, t_{i+1}] (the last one, whose compositing interval
+ *     is 1e9, owns [t_{S-1}, 1]);  m_i = (t_i + t_{i+1}) / 2,  d_i = t_{i+1} - t_i
+ *     L_ray = sum_i sum_j w_i w_j |m_i - m_j|  +  (1/3) sum_i w_i^2 d_i          L = mean of L_ray over the batch's rays
+ * and the objective of nerf_train_step / nerf_train_gradients becomes
+ *     coarse_mse_weight * MSE(coarse) + fine_mse_weight * MSE(fine) + coarse * L(coarse pass) + fine * L(fine pass).
+ * Finite, >= 0; (0, 0) -- the state nerf_train_begin leaves -- runs no kernel of it, and losses, gradients and step time are
+ * those of a library without it, bit for bit.  The gradient reaches the network through dL/dw of the compositing and, for
+ * the fine pass under sampler_gradient = 1, through dL/dz of the fine depths into the sampler and the coarse network (the
+ * coarse depths are data).  Under mixed_float16 it carries the loss scale like every other gradient.  The `loss` metric and
+ * its running sum stay the weighted MSE sum; L has running sums of its own, below.  A data-parallel step takes the mean over
+ * each rank's shard before the blobs are averaged.  The regulariser belongs to the ray loss ONLY: the backward passes
+ * through NeRF.render() that take a caller's d_rgb (nerf_train_render_gradients, nerf_train_render_forward /
+ * nerf_train_render_backward) do not apply it.  Needs far > near at the next gradient computation. */
+int nerf_train_set_distortion_weights(nerf_ctx* ctx, float coarse, float fine);
+/* ABI 6+: every nerf_train_step / nerf_train_gradients with a non-zero distortion weight for a pass adds that pass's
+ * UNWEIGHTED L to a running sum on the device; this call synchronises, returns the sums and the number of such gradient
+ * computations since the last read, and clears them (either pointer may be NULL).  A pass whose weight is 0 adds nothing. */
+int nerf_train_read_distortion_sums(nerf_ctx* ctx, double* sums /* [2]: L coarse, L fine */, int64_t* steps);
+/* ABI 6+: the bare operator on caller data, beside nerf_ray_marching and nerf_sample_pdf: weights, z (N,S), z sorted along
+ * each ray -> loss_per_ray (N) = L_ray, d_weights (N,S) = dL_ray/dw, d_z (N,S) = dL_ray/dz -- unscaled, per ray, no 1/N; any
+ * output pointer may be NULL.  One ray per wavefront, no atomics: the same inputs give the same bits on every run.  Needs
+ * S >= 1 and far > near. */
+int nerf_distortion_loss(nerf_ctx* ctx, const float* weights, const float* z, int64_t N, int32_t S, float* loss_per_ray,
+                         float* d_weights, float* d_z, int mem);
 /* mixed_float16 policy: the current loss scale, the optimizer steps applied and the steps skipped so far (1 / n / 0
  * under the fp32 policy).  Any pointer may be NULL. */
 int nerf_train_loss_scale(nerf_ctx* ctx, float* loss_scale, int64_t* steps_applied, int64_t* steps_skipped);

@@ -95,6 +95,9 @@ SYMBOLS = [
     ("nerf_train_end", C.c_int, [_P]),
     ("nerf_train_set_learning_rate", C.c_int, [_P, _F]),
     ("nerf_train_set_loss_weights", C.c_int, [_P, _F, _F]),
+    ("nerf_train_set_distortion_weights", C.c_int, [_P, _F, _F]),
+    ("nerf_train_read_distortion_sums", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),
+    ("nerf_distortion_loss", C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, C.c_int]),
     ("nerf_train_loss_scale", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(_I64), C.POINTER(_I64)]),
     ("nerf_train_read_metric_sums", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),
     ("nerf_train_step", C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _U64, _P, C.c_int]),

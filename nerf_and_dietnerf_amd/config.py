@@ -40,6 +40,7 @@ MIXED_FLOAT16 = "mixed_float16"
 LINDISP, USE_NDC, NDC_NEAR_PLANE = "lindisp", "use_ndc", "ndc_near_plane"
 SCENE_BOX = "scene_box"            # [[x, y, z], [x, y, z]]: per-ray depth range from a scene bounding box
 OCCUPANCY_GRID = "occupancy_grid"  # {resolution, sigma_threshold, samples_per_cell, dilate, update_every, warmup_epochs, cull_samples, cull_train_samples}; needs scene_box
+DISTORTION_LOSS = "distortion_loss"  # number or [coarse, fine]: weights of the distortion regulariser on the compositing weights
 ESTIMATE = "estimate"              # get_nerf(estimated_intersection=...): run the scene analysis, as the reference does
 
 

@@ -101,6 +101,12 @@ struct TrainState {
     // ray loss = loss_w[0] * MSE(coarse) + loss_w[1] * MSE(fine) (nerf_train_set_loss_weights): 1, 1 is NeRF.train_step
     // (src/NeRF.py:151,157); DietNeRF's ray loss counts the coarse term twice (src/DietNeRF.py:160-170)
     float loss_w[2] = {1.f, 1.f};
+    // ... + dist_w[0] * L(coarse weights) + dist_w[1] * L(fine weights), L the batch mean of the distortion loss
+    // (distortion_kernels.hip; nerf_train_set_distortion_weights).  0, 0: no kernel of it runs and none of its buffers exists.
+    float dist_w[2] = {0.f, 0.f};
+    DevBuf d_wdist;                 // the fine pass's dL/dw from the regulariser (N x Sf): that pass's d_w_ext
+    DevBuf dist_ray;                // the per-ray losses of the pass at hand (N)
+    DevBuf dacc;                    // running sums (3 doubles: L coarse, L fine, gradient computations under the regulariser)
     // mixed_float16 policy (src/ExecutionRun.py:220-221, src/NeRF.py:159-163): single-pass fp16 forward / data gradients
     // and the dynamic loss scale of Keras' LossScaleOptimizer
     bool mixed = false;
@@ -786,7 +792,29 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
         if (!rm) HIP_OK(hipMemsetAsync(t->macc.p, 0, 4 * sizeof(double), c->stream));
         r |= rm;
     }
+    // the distortion regulariser of a pass (TrainState::dist_w): its buffers exist only once a weight is non-zero
+    const bool dist_c = t->dist_w[0] > 0.f, dist_f = fine && t->dist_w[1] > 0.f;
+    if (dist_c || dist_f) {
+        if (!(c->cfg.far_boundary > c->cfg.near_boundary))
+            return fail("the distortion loss needs far_boundary > near_boundary (got %g, %g)", c->cfg.near_boundary,
+                        c->cfg.far_boundary);
+        r |= ensure(c, t->dist_ray, N * f);
+        if (dist_f) r |= ensure(c, t->d_wdist, df.M * f);
+        if (!t->dacc.p) {
+            const int rd = ensure(c, t->dacc, 3 * sizeof(double));
+            if (!rd) HIP_OK(hipMemsetAsync(t->dacc.p, 0, 3 * sizeof(double), c->stream));
+            r |= rd;
+        }
+    }
     if (r) return r;
+    // factor * (st->scale) * dL/dw of pass `which` -> d_w (stored, or added to the sampler's), its mean loss -> the running sums
+    auto distortion = [&](int which, const PassDims& pd, float* d_w, bool add_w, bool count_step) {
+        const TPass& p = t->pass[which];
+        launch_distortion((const float*)p.w.p, (const float*)p.z.p, pd.N, pd.S, c->cfg.near_boundary, c->cfg.far_boundary,
+                          (const OptState*)t->opt.p, t->dist_w[which] / (float)pd.N, (float*)t->dist_ray.p, d_w, add_w, nullptr,
+                          false, c->stream);
+        launch_distortion_mean((const float*)t->dist_ray.p, pd.N, which, count_step, (double*)t->dacc.p, c->stream);
+    };
     float* scal = (float*)t->scal.p;
     float* d_rgb = (float*)t->d_rgb.p;
     // the finiteness flag collects over ONE gradient computation: gradients that were computed and never applied
@@ -808,14 +836,22 @@ int gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d, const 
         if (int q = forward_pass(c, t, 1, df, o, d)) return q;
         launch_mse((const float*)pf.rgb.p, tg, N, (const OptState*)t->opt.p, t->loss_w[1], d_rgb, scal + 1, c->stream);
         float* d_zf = through_sampler ? (float*)t->d_zf.p : nullptr;
-        if (int q = composite_backward_pass(c, t, 1, df, o, d, d_rgb, nullptr, d_zf)) return q;
+        if (dist_f) distortion(1, df, (float*)t->d_wdist.p, false, true);
+        if (int q = composite_backward_pass(c, t, 1, df, o, d, d_rgb, dist_f ? (const float*)t->d_wdist.p : nullptr, d_zf))
+            return q;
+        // the regulariser's own dL/dz joins the pass's d_z AFTER the compositing backward, which stores there (the fine depths
+        // have a consumer only under sampler_gradient; the coarse depths are data)
+        if (dist_f && d_zf)
+            launch_distortion((const float*)pf.w.p, (const float*)pf.z.p, N, Sf, c->cfg.near_boundary, c->cfg.far_boundary,
+                              (const OptState*)t->opt.p, t->dist_w[1] / (float)N, nullptr, nullptr, false, d_zf, true, c->stream);
         if (through_sampler)
             launch_sample_pdf_bwd((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, 0, d_zf,
                                   (float*)t->d_wext.p, c->stream);
     }
     launch_mse((const float*)pc.rgb.p, tg, N, (const OptState*)t->opt.p, t->loss_w[0], d_rgb, scal + 0, c->stream);
-    if (int q = composite_backward_pass(c, t, 0, dc, o, d, d_rgb, through_sampler ? (const float*)t->d_wext.p : nullptr,
-                                        nullptr))
+    if (dist_c) distortion(0, dc, (float*)t->d_wext.p, through_sampler, !dist_f);
+    if (int q = composite_backward_pass(c, t, 0, dc, o, d, d_rgb,
+                                        through_sampler || dist_c ? (const float*)t->d_wext.p : nullptr, nullptr))
         return q;
     if (int q = join_side(c, t)) return q;
     if (t->mixed) {
@@ -1153,7 +1189,7 @@ void train_free(nerf_ctx* c) {
     free_buf(t->partial_side);
     DevBuf* bs[] = {&t->Gc, &t->Ga, &t->Gb, &t->G9, &t->Graw, &t->dsig, &t->dA0, &t->partial, &t->d_rgb, &t->d_wext, &t->d_zf, &t->tgt,
                     &t->o, &t->d, &t->u_c, &t->u_f, &t->scal, &t->gmax, &t->z_new, &t->d_zm, &t->zero_rgb, &t->opt,
-                    &t->gsave[0], &t->gsave[1], &t->macc};
+                    &t->gsave[0], &t->gsave[1], &t->macc, &t->d_wdist, &t->dist_ray, &t->dacc};
     for (DevBuf* b : bs) free_buf(*b);
     delete t;
     c->train = nullptr;
@@ -1269,6 +1305,7 @@ int nerf_train_begin(nerf_ctx* c, const nerf_train_config* cfg) {
     c->train = t;
     t->cfg = *cfg;
     t->loss_w[0] = t->loss_w[1] = 1.f;
+    t->dist_w[0] = t->dist_w[1] = 0.f;
     t->mixed = cfg->mixed_float16 != 0;
     {
         OptState h{};
@@ -1348,6 +1385,55 @@ int nerf_train_set_loss_weights(nerf_ctx* c, float coarse_mse_weight, float fine
     c->train->loss_w[0] = coarse_mse_weight;
     c->train->loss_w[1] = fine_mse_weight;
     return 0;
+}
+
+int nerf_train_set_distortion_weights(nerf_ctx* c, float coarse, float fine) {
+    if (!c || !c->train) return fail("nerf_train_begin has not been called");
+    if (!(coarse >= 0.f) || !(coarse <= 3.0e38f))
+        return fail("distortion weight `coarse` must be finite and non-negative (got %g)", coarse);
+    if (!(fine >= 0.f) || !(fine <= 3.0e38f))
+        return fail("distortion weight `fine` must be finite and non-negative (got %g)", fine);
+    c->train->dist_w[0] = coarse;
+    c->train->dist_w[1] = fine;
+    return 0;
+}
+
+int nerf_train_read_distortion_sums(nerf_ctx* c, double* sums, int64_t* steps) {
+    ENTER(c);
+    TrainState* t = c->train;
+    if (!t) return fail("nerf_train_begin has not been called");
+    double h[3] = {0, 0, 0};
+    if (t->dacc.p) {
+        HIP_OK(hipMemcpyAsync(h, t->dacc.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemsetAsync(t->dacc.p, 0, sizeof h, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    if (sums) { sums[0] = h[0]; sums[1] = h[1]; }
+    if (steps) *steps = (int64_t)h[2];
+    return 0;
+}
+
+int nerf_distortion_loss(nerf_ctx* c, const float* weights, const float* z, int64_t N, int32_t S, float* loss_per_ray,
+                         float* d_weights, float* d_z, int mem) {
+    ENTER(c);
+    if (!weights) return fail("weights is NULL");
+    if (!z) return fail("z is NULL");
+    if (N < 0) return fail("bad N = %lld (need N >= 0)", (long long)N);
+    if (S < 1) return fail("bad S = %d (need S >= 1)", S);
+    if (!(c->cfg.far_boundary > c->cfg.near_boundary))
+        return fail("the distortion loss needs far_boundary > near_boundary (got %g, %g)", c->cfg.near_boundary,
+                    c->cfg.far_boundary);
+    const size_t f = sizeof(float);
+    Staging st(c, mem);
+    const float* dw = st.in(c->b_in0, weights, (size_t)N * S * f);
+    const float* dz = st.in(c->b_in1, z, (size_t)N * S * f);
+    float* dl = st.out(c->b_in2, loss_per_ray, (size_t)N * f);
+    float* gw = st.out(c->b_zc, d_weights, (size_t)N * S * f);
+    float* gz = st.out(c->b_zf, d_z, (size_t)N * S * f);
+    if (st.err) return st.err;
+    launch_distortion(dw, dz, N, S, c->cfg.near_boundary, c->cfg.far_boundary, nullptr, 1.0f, dl, gw, false, gz, false, c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
 }
 
 int nerf_train_gradients(nerf_ctx* c, const float* rays_orig, const float* rays_dirs, const float* target_rgb, int64_t N,

@@ -128,6 +128,14 @@ void launch_opt_verdict(OptState* st, hipStream_t s);                          /
 void launch_opt_tick(OptState* st, float beta1, float beta2, hipStream_t s);   // after Adam: iterations, adam_corr
 void launch_composite_bwd(const float* raw, const float* z, const float* T, long long N, int S, const float* d_rgb,
                           const float* d_w_ext, float* Graw, float* d_z, hipStream_t s);
+// distortion_kernels.hip: the distortion loss of one pass's compositing weights (weights, z: N x S; near_b / far_b: the ctx's
+// bounds).  loss_per_ray (N): the unscaled per-ray loss; d_w, d_z (N x S): factor * st->scale (st nullable: 1) * dL/dw, dL/dz,
+// stored or added to what is there.  Any output may be null.
+void launch_distortion(const float* weights, const float* z, long long N, int S, float near_b, float far_b, const OptState* st,
+                       float factor, float* loss_per_ray, float* d_w, bool add_w, float* d_z, bool add_z, hipStream_t s);
+// acc[which] += mean of loss_per_ray (fixed order); count_step: acc[2] += 1
+void launch_distortion_mean(const float* loss_per_ray, long long N, int which, bool count_step, double* acc /* [3] */,
+                            hipStream_t s);
 void launch_head_bwd(const float* Graw, const float* W9 /*[128][Np9] row-major, Np9 = 32*/, const float* H9,
                      long long M, float alpha, float* G9, hipStream_t s);
 // lx: octaves of the encoding-gradient rows' layout ([x, sin0, cos0, ...] per component, 1 + 2 lx columns each; 1..10)

@@ -295,9 +295,14 @@ class DietNeRF(NeRF):
 
     def train_read_extra_metric_sums(self):
         """Sums of cosine_similarity_loss over the steps since the last read (kept on the device; dataset.fit reads them
-        once per epoch beside the library's own loss / psnr sums).  -> ({"cosine_similarity_loss": sum}, steps)"""
+        once per epoch beside the library's own loss / psnr sums), and NeRF's own extra sums (the distortion losses, under
+        render_config["distortion_loss"]: the ray-loss half of a step goes through train_gradients and trains under the
+        regulariser as well).  -> ({"cosine_similarity_loss": sum, ...}, steps)"""
+        out, _ = super().train_read_extra_metric_sums()
         if self._extra_sums is None:
-            return {"cosine_similarity_loss": 0.0}, 0
+            out["cosine_similarity_loss"] = 0.0
+            return out, 0
         s = self._extra_sums.cpu().numpy()
         self._extra_sums.zero_()
-        return {"cosine_similarity_loss": float(s[0])}, int(s[1])
+        out["cosine_similarity_loss"] = float(s[0])
+        return out, int(s[1])

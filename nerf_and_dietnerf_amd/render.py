@@ -48,6 +48,7 @@ GRID_CULL_TRAIN_SAMPLES = "cull_train_samples"    # bool, default False: the sam
 _GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID_DILATE, GRID_UPDATE_EVERY, GRID_WARMUP_EPOCHS,
               GRID_CULL_SAMPLES, GRID_CULL_TRAIN_SAMPLES)
 GRID_NEEDS_BOX = "an occupancy grid needs a scene box"
+DISTORTION_LOSS = "distortion_loss"  # number, or [coarse, fine], default absent: weights of the distortion regulariser in training
 
 N_COORDINATES = 3
 N_COLOR_CHANNELS = 3
@@ -69,6 +70,23 @@ def check_grid_resolution(resolution) -> int:
     if r != resolution or r < 4 or r > 256 or r % 4:
         raise ValueError(f"occupancy grid resolution must be a multiple of 4 in [4, 256] (got {resolution!r})")
     return r
+
+
+def check_distortion_loss(value) -> Tuple[float, float]:
+    """render_config["distortion_loss"] -> (coarse, fine): one number for both passes, or [coarse, fine]; finite, >= 0."""
+    def number(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{DISTORTION_LOSS} must be a number or [coarse, fine] (got {value!r})")
+        v = float(v)
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{DISTORTION_LOSS} weights must be finite and >= 0 (got {value!r})")
+        return v
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != 2:
+            raise ValueError(f"{DISTORTION_LOSS} must be a number or [coarse, fine] (got {value!r})")
+        return number(value[0]), number(value[1])
+    v = number(value)
+    return v, v
 
 
 def pack_occupancy_grid(grid) -> np.ndarray:
@@ -759,6 +777,31 @@ class Context:
         (src/NeRF.py:151,157; what train_begin leaves); DietNeRF's tape differentiates (2, 1) (src/DietNeRF.py:160-170)."""
         _lib.check(self.lib.nerf_train_set_loss_weights(self.h, float(coarse_mse_weight), float(fine_mse_weight)))
 
+    def train_set_distortion_weights(self, coarse: float = 0.0, fine: float = 0.0) -> None:
+        """Objective += coarse * L(coarse pass) + fine * L(fine pass), L the batch mean of the distortion loss of mip-NeRF 360
+        on the pass's compositing weights (nerf_train_set_distortion_weights).  (0, 0) = off, what train_begin leaves.  Acts on
+        train_step / train_gradients only: the backward passes through ``render`` (train_render_*) ignore it."""
+        _lib.check(self.lib.nerf_train_set_distortion_weights(self.h, float(coarse), float(fine)))
+
+    def train_read_distortion_sums(self) -> Tuple[Dict[str, float], int]:
+        """Sums of the unweighted distortion losses of the steps that ran under a non-zero weight since the last read, and
+        how many such steps there were (kept on the device; this synchronises and clears them)."""
+        sums, steps = (C.c_double * 2)(), C.c_int64()
+        _lib.check(self.lib.nerf_train_read_distortion_sums(self.h, sums, C.byref(steps)))
+        return {"distortion_coarse": float(sums[0]), "distortion_fine": float(sums[1])}, int(steps.value)
+
+    def distortion_loss(self, weights, z_values):
+        """The bare distortion-loss operator: weights, z_values (N, S), depths sorted along each ray ->
+        (loss_per_ray (N,), d_weights (N, S), d_z (N, S)), per ray and unscaled; t is measured between the context's bounds."""
+        arr = self._arrays(weights, z_values)
+        n, s = tuple(weights.shape)
+        pw, pz = arr.inp(weights, (n, s)), arr.inp(z_values, (n, s))
+        loss, pl = arr.out((n,))
+        dw, pdw = arr.out((n, s))
+        dz, pdz = arr.out((n, s))
+        _lib.check(self.lib.nerf_distortion_loss(self.h, pw, pz, n, s, pl, pdw, pdz, arr.mem))
+        return loss, dw, dz
+
     def _train_inputs(self, rays_orig, rays_dirs, real_rgb, n_c, n_f, u_coarse, u_fine):
         arr = self._arrays(rays_orig, rays_dirs, real_rgb)
         n = int(rays_orig.shape[0])
@@ -1090,6 +1133,9 @@ class NeRF:
             self.ctx.set_sample_culling(True)
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_TRAIN_SAMPLES, False):
             self.ctx.set_train_sample_culling(True)
+        # distortion regulariser: an absent key leaves training as it was; compile() hands the weights to the trainer
+        self.distortion_weights = check_distortion_loss(render_config[DISTORTION_LOSS]) if DISTORTION_LOSS in render_config \
+            else None
 
     @staticmethod
     def _grid_config(cfg, scene_box):
@@ -1220,6 +1266,17 @@ class NeRF:
                              dynamic_growth_steps)
         self._train_calls = 0
         self._mixed = bool(mixed_float16)
+        if self.distortion_weights is not None:
+            self.ctx.train_set_distortion_weights(*self.distortion_weights)
+
+    def train_read_extra_metric_sums(self):
+        """Sums of the two distortion losses over the steps since the last read, for dataset.fit's per-epoch means -- only
+        with a non-zero render_config["distortion_loss"], so the histories of other runs keep their keys.
+        -> ({"distortion_coarse", "distortion_fine"}: sums, steps)"""
+        weights = getattr(self, "distortion_weights", None)
+        if not (weights and any(weights)):
+            return {}, 0
+        return self.ctx.train_read_distortion_sums()
 
     def train_step(self, data, *, u_coarse=None, u_fine=None, seed=None, group=None,
                    want_metrics: bool = True) -> Optional[Dict[str, float]]:
