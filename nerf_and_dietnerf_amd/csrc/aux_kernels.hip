@@ -9,6 +9,7 @@
 //   z_values, disparity-linear mode
 //   scene box     ray_box_interval: the part of [near, far] a ray spends inside an axis-aligned box; the box variants of
 //                 the two depth kernels draw on it, ray_box_bounds returns it
+//   repack        weight blob -> an operand stream of the MLP kernels, through a gather table (weight_tables.hip)
 //
 // All HBM-bound fp32/int32 work.  Evaluation order is the canonical one of oracle/nerf_oracle.py:
 // sums / cumsum / cumprod run left to right along the sample axis and products are NOT contracted
@@ -16,6 +17,8 @@
 // the oracle and the other outputs differ only through expf.
 #include "nerf_kernels.h"
 #include "nerf_device.h"
+
+#include <algorithm>
 
 namespace nerf {
 
@@ -828,6 +831,41 @@ void launch_posenc(const float* x, long long M, int n_enc, int passthrough, floa
     const int bs = 256;
     hipLaunchKernelGGL(posenc_kernel, dim3((unsigned)((M + bs - 1) / bs)), dim3(bs), 0, stream, x, M, n_enc,
                        passthrough, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// repack: weight blob -> one operand stream (and its constant block) through a gather table (nerf_kernels.h: launch_repack).
+// E = _Float16 / __bf16: entry 2 * (src + 1) + is_lo -> the weight rounded to E (RNE), or what rounding left, rounded again;
+// E = float: entry src + 1 -> the weight.  Entry 0: padding.
+// ------------------------------------------------------------------------------------------------
+template <class E>
+__global__ void repack_kernel(const float* __restrict__ blob, const int32_t* __restrict__ idx, E* __restrict__ out, size_t n,
+                              const int32_t* __restrict__ const_idx, float* __restrict__ cst) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int32_t t = idx[i];
+        E v = (E)0.f;
+        if constexpr (sizeof(E) == sizeof(float)) {
+            if (t != 0) v = blob[t - 1];
+        } else if (t != 0) {
+            const float w = blob[(t >> 1) - 1];
+            const E hi = (E)w;
+            v = (t & 1) ? (E)(w - (float)hi) : hi;
+        }
+        out[i] = v;
+    }
+    if (const_idx && i < (size_t)kConstFloats) {
+        const int32_t t = const_idx[i];
+        cst[i] = t ? blob[t - 1] : 0.f;
+    }
+}
+
+void launch_repack(StreamElem elem, const float* blob, const int32_t* idx, void* out, size_t n, const int32_t* const_idx,
+                   float* cst, hipStream_t s) {
+    const dim3 grid((unsigned)((std::max(n, (size_t)kConstFloats) + 255) / 256)), block(256);
+    if (elem == kElemF32) hipLaunchKernelGGL(repack_kernel<float>, grid, block, 0, s, blob, idx, (float*)out, n, const_idx, cst);
+    else if (elem == kElemBf16) hipLaunchKernelGGL(repack_kernel<__bf16>, grid, block, 0, s, blob, idx, (__bf16*)out, n, const_idx, cst);
+    else hipLaunchKernelGGL(repack_kernel<_Float16>, grid, block, 0, s, blob, idx, (_Float16*)out, n, const_idx, cst);
 }
 
 }  // namespace nerf

@@ -670,20 +670,16 @@ void mlp_bwd_f16x3_set_attributes() {
 
 // ------------------------------------------------------------------------------------------------
 // The backward stream as an index map (host): idx[slot] = 2 * (src + 1) + is_lo, 0 = padding; src = index into the
-// blob (Keras get_weights() order).  Re-packed on the device after every optimizer step by repack_bwd_kernel.
+// (layout_lx, kLd) blob (Keras get_weights() order).  Re-packed on the device after every optimizer step (launch_repack).
 // ------------------------------------------------------------------------------------------------
-void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 entries */, int xyz_dim) {
+void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 entries */, int layout_lx) {
     memset(idx, 0, (kBwdStreamBytes / 2) * sizeof(int32_t));
-    const int kd = 256 + 8 * (n_angles + 1);
     const bool xyz_only = n_angles == 0;
-    const int shapes_dir[12][2] = {{xyz_dim, 256}, {256, 256}, {256, 256}, {256, 256}, {xyz_dim + 256, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}, {0, 0}};
-    // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int shapes_xyz[12][2] = {{xyz_dim, 256}, {256, 256}, {256, 256}, {256, 256}, {xyz_dim + 256, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
-    const int (*shapes)[2] = xyz_only ? shapes_xyz : shapes_dir;
+    const int xyz_dim = 3 + 6 * layout_lx;
+    int shapes[12][2];
+    const int n_layers = layer_dims(layout_lx, kLd, n_angles, shapes);
     long long koff[12], off = 0;
-    for (int i = 0; i < 12; ++i) { koff[i] = off; off += (long long)shapes[i][0] * shapes[i][1] + shapes[i][1]; }
+    for (int i = 0; i < n_layers; ++i) { koff[i] = off; off += (long long)shapes[i][0] * shapes[i][1] + shapes[i][1]; }
     const int cq = hi_only ? BGeo<true>::CQ : BGeo<false>::CQ;        // the two arithmetics run different ring geometries
     const int chunk_halfs = cq * (kQuadBytes / 2);
     size_t chunk = 0;
@@ -732,27 +728,6 @@ void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdS
     else emit(8, 16, hidden(4, xyz_dim));
     for (int l = 3; l >= 1; --l) emit(8, 16, hidden(l, 0));
     if (dx) emit(2, 16, with_xyz(0, 2, 0));
-}
-
-__global__ void repack_bwd_kernel(const float* __restrict__ blob, const int32_t* __restrict__ idx,
-                                  uint16_t* __restrict__ stream, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t t = idx[i];
-    uint16_t out = 0;
-    if (t != 0) {
-        const float w = blob[(t >> 1) - 1];
-        const _Float16 hi = (_Float16)w;
-        const _Float16 v = (t & 1) ? (_Float16)(w - (float)hi) : hi;
-        out = __builtin_bit_cast(uint16_t, v);
-    }
-    stream[i] = out;
-}
-
-void launch_repack_bwd(const float* blob, const int32_t* idx, void* stream, hipStream_t s) {
-    const size_t n = kBwdStreamBytes / 2;
-    hipLaunchKernelGGL(repack_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blob, idx,
-                       reinterpret_cast<uint16_t*>(stream), n);
 }
 
 }  // namespace nerf

@@ -806,63 +806,12 @@ void mlp_f16x3_set_attributes() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
 #endif
 }
-#endif   // NERF_BF16
 
 // ------------------------------------------------------------------------------------------------
-// Host-side packing: blob (Keras get_weights() order) -> fp16 hi/lo fragment stream + fp32 constants
+// The streams + constants as index maps (host) over the (kPeLx, kLd) blob (Keras get_weights() order).  The fp16 builds
+// alone have them: a bf16 stream is re-packed from its fp16 twin's table (same slots).
 // ------------------------------------------------------------------------------------------------
 namespace {
-// fp32 -> fp16 round-to-nearest-even and back, by bit manipulation (no host _Float16 runtime needed)
-uint16_t f32_to_f16(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7FFFFFFFu;
-    if (x >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (x > 0x7F800000u ? 0x200u : 0));   // inf / nan
-    if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                                     // overflow -> inf
-    if (x < 0x33000001u) return (uint16_t)sign;                                                  // < 2^-25 -> 0
-    int e = (int)(x >> 23) - 127;
-    uint32_t m = (x & 0x7FFFFFu) | 0x800000u;
-    int shift;
-    uint32_t base;
-    if (e < -14) { shift = 13 + (-14 - e); base = 0; }          // subnormal half
-    else { shift = 13; base = (uint32_t)(e + 15) << 10; m &= 0x7FFFFFu; }
-    uint32_t q = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1), halfway = 1u << (shift - 1);
-    if (rem > halfway || (rem == halfway && (q & 1))) q += 1;   // may carry into the exponent: correct
-    return (uint16_t)(sign | (base + q));
-}
-float f16_to_f32(uint16_t hbits) {
-    const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16;
-    const uint32_t e = (hbits >> 10) & 0x1F, m = hbits & 0x3FF;
-    uint32_t x;
-    if (e == 0) {
-        if (m == 0) x = sign;
-        else { float f = (float)m * 5.9604644775390625e-08f; memcpy(&x, &f, 4); x |= sign; }   // m * 2^-24
-    } else if (e == 31) x = sign | 0x7F800000u | (m << 13);
-    else x = sign | ((e + 112) << 23) | (m << 13);
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
-#ifdef NERF_BF16
-// fp32 -> bf16 round-to-nearest-even (v_cvt_pk_bf16_f32) and back
-uint16_t f32_to_e16(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x40u);   // nan stays nan
-    return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
-}
-float e16_to_f32(uint16_t b) {
-    const uint32_t x = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &x, 4);
-    return f;
-}
-#else
-uint16_t f32_to_e16(float f) { return f32_to_f16(f); }
-float e16_to_f32(uint16_t hbits) { return f16_to_f32(hbits); }
-#endif
 int h_pe_row(int v, int h) {   // slot v (0..23) of lane half h -> row of the (33, .) kernel; -1 = pad
     if (v < 3 * kPeLx) { const int c = v / kPeLx, k = v % kPeLx; return c * (1 + 2 * kPeLx) + 1 + 2 * k + h; }
     if (kPeLx != 5) {              // wide-PE build: slots 0..31 of the (63, .) kernel; raw x, y in half 0, z in half 1
@@ -880,25 +829,19 @@ int h_dir_row(int v, int h, int n_angles) {   // slot v (0..15) -> row of the di
     if (c == 1) return -1;                       // n_angles == 1: (x,z) only, src/UtilsCV.py:134-135
     return (c == 0 ? 0 : 1) * 8 + 2 * k + h;
 }
-struct HLayer { const float* k; const float* b; int in, out; };
 }  // namespace
 
-// The packing as a pure index map: EmitW(pos_hi, pos_lo (-1 in the hi-only stream), src) for every 16-bit slot pair of
-// the stream, EmitC(pos, src) for every float of the constant region; src = index into the blob, -1 = zero padding.
+// EmitW(pos_hi, pos_lo (-1 in the hi-only stream), src) for every 16-bit slot pair of the stream, EmitC(pos, src) for
+// every float of the constant region; src = index into the blob, -1 = zero padding.
 // sig_only: the sigma-only stream (3-pass, n_angles 1 or 2): layer 8 is BODY_SIG instead of BODY_LAST; same constants.
 template <class EmitW, class EmitC>
 static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c, bool sig_only = false) {
-    const int kd = 256 + 8 * (n_angles + 1);
     const bool xyz_only = n_angles == 0;
-    // Keras creation order; xyz-only (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int shapes_dir[12][2] = {{kPeDim, 256}, {256, 256}, {256, 256}, {256, 256}, {kPeDim + 256, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}, {0, 0}};
-    const int shapes_xyz[12][2] = {{kPeDim, 256}, {256, 256}, {256, 256}, {256, 256}, {kPeDim + 256, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
-    const int (*shapes)[2] = xyz_only ? shapes_xyz : shapes_dir;
+    int shapes[12][2];
+    const int n_layers = layer_dims(kPeLx, kLd, n_angles, shapes);
     struct Lay { long long k, b; int in, out; } L[12];
     long long off = 0;
-    for (int i = 0; i < (xyz_only ? 12 : 11); ++i) {
+    for (int i = 0; i < n_layers; ++i) {
         L[i].in = shapes[i][0]; L[i].out = shapes[i][1];
         L[i].k = off; off += (long long)L[i].in * L[i].out;
         L[i].b = off; off += L[i].out;
@@ -967,121 +910,26 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c,
     for (int c = 0; c < 3; ++c) emit_c(kHConstBHead + c, L[9].b + c);
 }
 
-static void pack_weights_f16_impl(const float* blob, int n_angles, void* stream_out, float* const_out, bool hi_only,
-                                  bool sig_only = false) {
-    memset(stream_out, 0, sig_only ? kStreamBytesF16Sig : n_angles == 0 ? (hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz)
-                                                                        : (hi_only ? kStreamBytesF16Hi : kStreamBytesF16));
-    memset(const_out, 0, kConstBytes);
-    uint16_t* base = reinterpret_cast<uint16_t*>(stream_out);
-    pack_f16_map(n_angles, hi_only,
-                 [&](long long ph, long long pl, long long src) {
-                     const float w = src < 0 ? 0.f : blob[src];
-                     const uint16_t hi = f32_to_e16(w);
-                     base[ph] = hi;
-                     if (pl >= 0) base[pl] = f32_to_e16(w - e16_to_f32(hi));
-                 },
-                 [&](long long pos, long long src) { const_out[pos] = blob[src]; }, sig_only);
-}
-
-#if defined(NERF_BF16) && NERF_PE_LX == 5
-// device-side re-pack of a bf16 hi/lo stream from a blob: the fp16 build's gather table of the same stream (same slots,
-// build_f16x3_gather / build_f16x3_sig_gather), elements rounded as the host packer above rounds them
-__global__ void repack_bf16x3_kernel(const float* __restrict__ blob, const int32_t* __restrict__ stream_idx,
-                                     uint16_t* __restrict__ stream, size_t n_slots) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots) return;
-    const int32_t t = stream_idx[i];
-    uint16_t out = 0;
-    if (t != 0) {
-        const float w = blob[(t >> 1) - 1];
-        const __bf16 hi = (__bf16)w;                             // RNE, as the host packer
-        const __bf16 v = (t & 1) ? (__bf16)(w - (float)hi) : hi;
-        out = __builtin_bit_cast(uint16_t, v);
-    }
-    stream[i] = out;
-}
-void launch_repack_bf16x3(const float* blob, const int32_t* stream_idx, void* stream, size_t stream_bytes, hipStream_t s) {
-    const size_t n = stream_bytes / 2;
-    hipLaunchKernelGGL(repack_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blob, stream_idx,
-                       reinterpret_cast<uint16_t*>(stream), n);
-}
-void pack_weights_bf16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out) {
-    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false, true);
-}
-#endif
-#ifdef NERF_BF16
-void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out) {
-    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false);
-}
-#else    // !NERF_BF16
-// gather tables of the 3-pass stream for the device-side re-pack (the trainer's forward runs on this kernel and its
-// weights change every step): stream_idx[slot] = 2 * (src + 1) + is_lo, const_idx[float] = src + 1; 0 = padding
-size_t f16_stream_bytes(int n_angles, bool hi_only) {
-    if (n_angles == 0) return hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz;
-    return hi_only ? kStreamBytesF16Hi : kStreamBytesF16;
-}
-
-void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx /* f16_stream_bytes / 2 */,
-                        int32_t* const_idx /*kConstFloats*/) {
-    memset(stream_idx, 0, (f16_stream_bytes(n_angles, hi_only) / 2) * sizeof(int32_t));
-    memset(const_idx, 0, kConstFloats * sizeof(int32_t));
+// stream_idx[slot] = 2 * (src + 1) + is_lo, const_idx[float] = src + 1 (nullable); 0 = padding
+static void build_gather(int n_angles, bool hi_only, bool sig_only, int32_t* stream_idx, size_t stream_bytes, int32_t* const_idx) {
+    memset(stream_idx, 0, (stream_bytes / 2) * sizeof(int32_t));
+    if (const_idx) memset(const_idx, 0, kConstFloats * sizeof(int32_t));
     pack_f16_map(n_angles, hi_only,
                  [&](long long ph, long long pl, long long src) {
                      if (src < 0) return;
                      stream_idx[ph] = (int32_t)(2 * (src + 1));
                      if (pl >= 0) stream_idx[pl] = (int32_t)(2 * (src + 1) + 1);
                  },
-                 [&](long long pos, long long src) { const_idx[pos] = (int32_t)(src + 1); });
+                 [&](long long pos, long long src) { if (const_idx) const_idx[pos] = (int32_t)(src + 1); }, sig_only);
 }
 
-__global__ void repack_f16x3_kernel(const float* __restrict__ blob, const int32_t* __restrict__ stream_idx,
-                                    uint16_t* __restrict__ stream, const int32_t* __restrict__ const_idx,
-                                    float* __restrict__ cst, size_t n_slots) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_slots) {
-        const int32_t t = stream_idx[i];
-        uint16_t out = 0;
-        if (t != 0) {
-            const float w = blob[(t >> 1) - 1];
-            const _Float16 hi = (_Float16)w;                       // RNE, as the host packer
-            const _Float16 v = (t & 1) ? (_Float16)(w - (float)hi) : hi;
-            out = __builtin_bit_cast(uint16_t, v);
-        }
-        stream[i] = out;
-    }
-    if (i < (size_t)kConstFloats) {
-        const int32_t t = const_idx[i];
-        cst[i] = t ? blob[t - 1] : 0.f;
-    }
-}
-
-void launch_repack_f16x3(const float* blob, const int32_t* stream_idx, void* stream, const int32_t* const_idx, float* cst,
-                         size_t stream_bytes, hipStream_t s) {
-    const size_t n = stream_bytes / 2;
-    hipLaunchKernelGGL(repack_f16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, blob, stream_idx,
-                       reinterpret_cast<uint16_t*>(stream), const_idx, cst, n);
-}
-
-void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out) {
-    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false);
-}
-void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out) {
-    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, true);
+void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx, int32_t* const_idx) {
+    const size_t bytes = n_angles == 0 ? (hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz) : (hi_only ? kStreamBytesF16Hi : kStreamBytesF16);
+    build_gather(n_angles, hi_only, false, stream_idx, bytes, const_idx);
 }
 #if NERF_PE_LX == 5
-void pack_weights_f16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out) {
-    pack_weights_f16_impl(blob, n_angles, stream_out, const_out, false, true);
-}
-// gather table of the sigma-only stream (kStreamBytesF16Sig / 2 entries); its constants are build_f16x3_gather's
 void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx) {
-    memset(stream_idx, 0, (kStreamBytesF16Sig / 2) * sizeof(int32_t));
-    pack_f16_map(n_angles, false,
-                 [&](long long ph, long long pl, long long src) {
-                     if (src < 0) return;
-                     stream_idx[ph] = (int32_t)(2 * (src + 1));
-                     stream_idx[pl] = (int32_t)(2 * (src + 1) + 1);
-                 },
-                 [](long long, long long) {}, true);
+    build_gather(n_angles, false, true, stream_idx, kStreamBytesF16Sig, nullptr);
 }
 #endif
 #endif   // NERF_BF16

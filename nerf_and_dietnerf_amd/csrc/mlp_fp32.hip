@@ -435,7 +435,8 @@ void mlp_fp32_set_attributes() {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host-side packing: blob (Keras get_weights() order, kernel (in,out) row-major) -> stream + const.
+// The fp32 stream + constants as an index map (host) over the (kLx, kLd) blob (Keras get_weights() order, kernel
+// (in,out) row-major): entry = src + 1, 0 = zero padding.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // input row of the layer kernel for PE k-step s (0..19) and lane half h; -1 = zero pad
@@ -448,7 +449,7 @@ int pe_row(int s, int h) {
 int hid_row(int s, int h) { const int t = s >> 4, r = s & 15; return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h; }
 // dir k-step s (0..11) = component c (x,y,z) x octave k -> row of the dir block of the kernel, or -1.
 // n_angles == 2: view dirs are (x,y,z) -> 24 rows.  n_angles == 1: the reference feeds only (x,z)
-// (src/UtilsCV.py:134-135) -> 16 rows; the kernel still encodes y, its weights are packed as zero.
+// (src/UtilsCV.py:134-135) -> 16 rows; the kernel still encodes y, its weight slots are padding.
 int dir_row(int s, int h, int n_angles) {
     const int c = s / 4, k = s % 4;
     if (n_angles == 2) return c * 8 + 2 * k + h;
@@ -456,37 +457,32 @@ int dir_row(int s, int h, int n_angles) {
     return (c == 0 ? 0 : 1) * 8 + 2 * k + h;
 }
 
-struct Layer { const float* k; const float* b; int in, out; };
+struct Layer { int32_t k, b; int in, out; };   // k, b: 1 + the blob index of the kernel's / the bias's first float
 }  // namespace
 
-void pack_weights_fp32(const float* blob, int n_angles, float* stream_out, float* const_out) {
-    const int kd = 256 + 8 * (n_angles + 1);   // width of [hidden, dir_enc]: 280 (n_angles 2) or 272 (1)
+void build_fp32_gather(int n_angles, int32_t* stream_idx, int32_t* const_idx) {
     const bool xyz_only = n_angles == 0;
-    const int shapes_dir[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}, {0, 0}};
-    // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int shapes_xyz[12][2] = {{33, 256}, {256, 256}, {256, 256}, {256, 256}, {289, 256}, {256, 256},
-                                   {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
-    const int (*shapes)[2] = xyz_only ? shapes_xyz : shapes_dir;
+    int shapes[12][2];
+    const int n_layers = layer_dims(kLx, kLd, n_angles, shapes);
     Layer L[12];
-    size_t off = 0;
-    for (int i = 0; i < (xyz_only ? 12 : 11); ++i) {
+    int32_t off = 1;
+    for (int i = 0; i < n_layers; ++i) {
         L[i].in = shapes[i][0]; L[i].out = shapes[i][1];
-        L[i].k = blob + off; off += (size_t)L[i].in * L[i].out;
-        L[i].b = blob + off; off += L[i].out;
+        L[i].k = off; off += L[i].in * L[i].out;
+        L[i].b = off; off += L[i].out;
     }
-    memset(stream_out, 0, xyz_only ? kStreamBytesXyzF32 : kStreamBytes);
-    memset(const_out, 0, kConstBytes);
+    memset(stream_idx, 0, xyz_only ? kStreamBytesXyzF32 : kStreamBytes);
+    memset(const_idx, 0, kConstFloats * sizeof(int32_t));
     size_t chunk = 0;
     auto emit_body = [&](int layer, int body) {
         const int NU = (body == BODY_LAST || body == BODY_LASTX) ? 4 : 8;
         const int QPU = body == BODY_PE ? kQpuPE : (body == BODY_HID || body == BODY_LASTX) ? kQpuHid
                         : body == BODY_SKIP ? kQpuSkip : kQpuLast;
-        float* base = stream_out + chunk * (kChunkBytes / 4);
+        int32_t* base = stream_idx + chunk * (kChunkBytes / 4);
         for (int u = 0; u < NU; ++u)
             for (int q = 0; q < QPU; ++q) {
                 // tiles are consumed in pairs: quad order is (pair, q, tile-of-pair)
-                float* quad = base + (size_t)(((u >> 1) * QPU + q) * 2 + (u & 1)) * (kQuadBytes / 4);
+                int32_t* quad = base + (size_t)(((u >> 1) * QPU + q) * 2 + (u & 1)) * (kQuadBytes / 4);
                 for (int lane = 0; lane < 64; ++lane)
                     for (int e = 0; e < 4; ++e) {
                         const int i = lane & 31, h = lane >> 5;
@@ -496,7 +492,7 @@ void pack_weights_fp32(const float* blob, int n_angles, float* stream_out, float
                         else if (body == BODY_SKIP) row = q < kQpuPE ? pe_row(4 * q + e, h) : kXyzDim + hid_row(4 * (q - kQpuPE) + e, h);
                         else if (q < kQpuHid) row = hid_row(4 * q + e, h);
                         else { const int r = dir_row(4 * (q - kQpuHid) + e, h, n_angles); row = r < 0 ? -1 : kHidden + r; }
-                        quad[lane * 4 + e] = row < 0 ? 0.f : L[layer].k[(size_t)row * L[layer].out + 32 * u + i];
+                        quad[lane * 4 + e] = row < 0 ? 0 : L[layer].k + row * L[layer].out + 32 * u + i;
                     }
             }
         chunk += (NU * QPU + kChunkQuads - 1) / kChunkQuads;
@@ -506,34 +502,33 @@ void pack_weights_fp32(const float* blob, int n_angles, float* stream_out, float
     emit_body(4, BODY_SKIP);
     for (int l = 5; l <= 7; ++l) emit_body(l, BODY_HID);
     for (int l = 0; l < 8; ++l)
-        for (int f = 0; f < 256; ++f) const_out[kConstBias + l * 256 + f] = L[l].b[f];
+        for (int f = 0; f < 256; ++f) const_idx[kConstBias + l * 256 + f] = L[l].b + f;
     if (xyz_only) {
         emit_body(8, BODY_HID);          // the kernel runs it as BODY_HSIG: same operand order
         emit_body(9, BODY_LASTX);
-        for (int f = 0; f < 256; ++f) const_out[kFXConstBias8 + f] = L[8].b[f];
-        for (int f = 0; f < 128; ++f) const_out[kFXConstBias9 + f] = L[9].b[f];
+        for (int f = 0; f < 256; ++f) const_idx[kFXConstBias8 + f] = L[8].b + f;
+        for (int f = 0; f < 128; ++f) const_idx[kFXConstBias9 + f] = L[9].b + f;
         for (int c = 0; c < 3; ++c)
-            for (int f = 0; f < 128; ++f) const_out[kFXConstWrgb + c * 128 + f] = L[10].k[f * 3 + c];
-        for (int c = 0; c < 3; ++c) const_out[kFXConstBHead + c] = L[10].b[c];
-        const_out[kFXConstBHead + 3] = L[11].b[0];
-        for (int f = 0; f < 256; ++f) const_out[kFXConstWsigH + f] = L[11].k[f];
+            for (int f = 0; f < 128; ++f) const_idx[kFXConstWrgb + c * 128 + f] = L[10].k + f * 3 + c;
+        for (int c = 0; c < 3; ++c) const_idx[kFXConstBHead + c] = L[10].b + c;
+        const_idx[kFXConstBHead + 3] = L[11].b;
+        for (int f = 0; f < 256; ++f) const_idx[kFXConstWsigH + f] = L[11].k + f;
         return;
     }
     emit_body(8, BODY_LAST);
     // constants
-    for (int f = 0; f < 128; ++f) const_out[kConstBias8 + f] = L[8].b[f];
+    for (int f = 0; f < 128; ++f) const_idx[kConstBias8 + f] = L[8].b + f;
     for (int c = 0; c < 3; ++c)
-        for (int f = 0; f < 128; ++f) const_out[kConstWrgb + c * 128 + f] = L[9].k[f * 3 + c];
-    for (int c = 0; c < 3; ++c) const_out[kConstBHead + c] = L[9].b[c];
-    const_out[kConstBHead + 3] = L[10].b[0];
-    for (int f = 0; f < 256; ++f) const_out[kConstWsigH + f] = L[10].k[f];
+        for (int f = 0; f < 128; ++f) const_idx[kConstWrgb + c * 128 + f] = L[9].k + f * 3 + c;
+    for (int c = 0; c < 3; ++c) const_idx[kConstBHead + c] = L[9].b + c;
+    const_idx[kConstBHead + 3] = L[10].b;
+    for (int f = 0; f < 256; ++f) const_idx[kConstWsigH + f] = L[10].k + f;
     for (int g = 0; g < 3; ++g)
         for (int h = 0; h < 2; ++h)
-            for (int e = 0; e < 4; ++e)
-            {
-                    const int r = dir_row(4 * g + e, h, n_angles);
-                    const_out[kConstWsigD + (g * 2 + h) * 4 + e] = r < 0 ? 0.f : L[10].k[kHidden + r];
-                }
+            for (int e = 0; e < 4; ++e) {
+                const int r = dir_row(4 * g + e, h, n_angles);
+                const_idx[kConstWsigD + (g * 2 + h) * 4 + e] = r < 0 ? 0 : L[10].k + kHidden + r;
+            }
 }
 
 }  // namespace nerf

@@ -167,103 +167,38 @@ int compact_samples(nerf_ctx* c, SampleCompaction& rec, const float* o, const fl
     return cull_stamp(c, stamp);
 }
 
-// The Dense layers' (in, out) in Keras creation order; -> the layer count (11, or 12 for the xyz-only network)
-static int layer_dims(int lx, int ld, int n_angles, int dims[12][2]) {
-    const int xd = 3 + 6 * lx;                                  // src/NeRF.py:312
-    const int kd = 256 + 2 * ld * (n_angles + 1);               // [hidden, dir_enc], src/NeRF.py:313-314
-    const int with_dirs[11][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
-                                  {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}};
-    // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
-    const int xyz_only[12][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
-                                 {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
-    const int n = n_angles == 0 ? 12 : 11;
-    for (int l = 0; l < n; ++l) {
-        dims[l][0] = n_angles == 0 ? xyz_only[l][0] : with_dirs[l][0];
-        dims[l][1] = n_angles == 0 ? xyz_only[l][1] : with_dirs[l][1];
-    }
-    return n;
-}
-
-size_t blob_floats(int lx, int ld, int n_angles) {
-    int dims[12][2];
-    const int n = layer_dims(lx, ld, n_angles, dims);
-    size_t s = 0;
-    for (int l = 0; l < n; ++l) s += (size_t)dims[l][0] * dims[l][1] + dims[l][1];
-    return s;
-}
-
-void blob_expand_index(int lx, int ld, int n_angles, int32_t* idx, int layout_lx) {
-    int wide[12][2], dims[12][2];
-    const int n = layer_dims(layout_lx, kLd, n_angles, wide);
-    layer_dims(lx, ld, n_angles, dims);
-    const int xd_layout = 3 + 6 * layout_lx;
-    // xyz encoding row of the (layout_lx) layout -> row of the (lx) layout: per component [x, sin0, cos0, sin1, cos1, ...]
-    auto xyz_row = [&](int r) {
-        const int c = r / (1 + 2 * layout_lx), j = r % (1 + 2 * layout_lx);
-        if (j == 0) return c * (1 + 2 * lx);
-        const int k = (j - 1) / 2, h = (j - 1) % 2;
-        return k < lx ? c * (1 + 2 * lx) + 1 + 2 * k + h : -1;
+int ensure_render_tables(nerf_ctx* c) {
+    if (c->rt_built) return 0;
+    StreamTables t;
+    build_stream_tables(c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, c->cfg.n_angles, t);
+    auto up = [&](const std::vector<int32_t>& v, int32_t** dst) -> int {      // (blocking: the host table dies with this call)
+        if (v.empty()) return 0;
+        if (!*dst) HIP_OK(hipMalloc((void**)dst, v.size() * sizeof(int32_t)));
+        HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        return 0;
     };
-    // direction encoding row: per component [sin0, cos0, sin1, cos1, ...] (src/UtilsNeuralRadianceField.py:52-65)
-    auto dir_row = [&](int r) {
-        const int c = r / (2 * kLd), j = r % (2 * kLd), k = j / 2, h = j % 2;
-        return k < ld ? c * 2 * ld + 2 * k + h : -1;
-    };
-    size_t src = 0, dst = 0;
-    for (int l = 0; l < n; ++l) {
-        for (int r = 0; r < wide[l][0]; ++r) {
-            int rs = r;
-            if (l == 0) rs = xyz_row(r);
-            else if (l == 4) rs = r < xd_layout ? xyz_row(r) : 3 + 6 * lx + (r - xd_layout);
-            else if (n_angles != 0 && (l == 8 || l == 10)) rs = r < kHidden ? r : (dir_row(r - kHidden) < 0 ? -1 : kHidden + dir_row(r - kHidden));
-            for (int f = 0; f < wide[l][1]; ++f)
-                idx[dst++] = rs < 0 ? 0 : (int32_t)(src + (size_t)rs * dims[l][1] + f + 1);
-        }
-        src += (size_t)dims[l][0] * dims[l][1];
-        for (int f = 0; f < wide[l][1]; ++f) idx[dst++] = (int32_t)(src + f + 1);
-        src += dims[l][1];
-    }
+    for (int k = 0; k < kStreamKinds; ++k) if (int r = up(t.stream[k], &c->rt[k])) return r;
+    for (int b = 0; b < kConstBlocks; ++b) if (int r = up(t.cst[b], &c->rt_cst[b])) return r;
+    c->rt_built = true;
+    return 0;
 }
 
-int upload_packed_weights(nerf_ctx* c, int which, const float* blob_in) {
-    HIP_OK(hipSetDevice(c->cfg.device));
+int repack_render_streams(nerf_ctx* c, int which, const float* dev_blob) {
+    if (int r = ensure_render_tables(c)) return r;
     NetWeights& n = c->net[which];
-    // the packers take the (kLx, kLd) layout (the wide-PE packers the (kLxWide, kLd) one): a network with fewer octaves is
-    // spread into it with zero rows
-    std::vector<float> spread;
-    const float* blob = blob_in;
-    const int L = pe_layout_lx(c->cfg.n_pos_enc_xyz);
-    if (c->cfg.n_pos_enc_xyz != L || c->cfg.n_pos_enc_dir != kLd) {
-        std::vector<int32_t> idx(blob_floats(L, kLd, c->cfg.n_angles));
-        blob_expand_index(c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, c->cfg.n_angles, idx.data(), L);
-        spread.resize(idx.size());
-        for (size_t i = 0; i < idx.size(); ++i) spread[i] = idx[i] ? blob_in[idx[i] - 1] : 0.f;
-        blob = spread.data();
-    }
-    // pack and upload every stream the table lists for this network; the stream is drained once, before the first copy (a
-    // running kernel may still read the old weights), and the copies block: the host buffers die with this call
     StreamDesc d[kStreamKinds];
     render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, which, d);
-    std::vector<float> cst[kConstBlocks];
-    bool drained = false;
     for (int k = 0; k < kStreamKinds; ++k) {
         if (!d[k].bytes) continue;
-        std::vector<char> host(d[k].bytes);
-        cst[d[k].cst].resize(kConstFloats);
-        d[k].pack(blob, c->cfg.n_angles, host.data(), cst[d[k].cst].data());
+        const int32_t *tab = c->rt[d[k].table], *ctab = c->rt_cst[d[k].cst];
+        if (!tab || !ctab) return fail("internal: no gather table for stream kind %d of network %d", k, which);
         if (!n.stream[k]) HIP_OK(hipMalloc(&n.stream[k], d[k].bytes));
-        if (!drained) HIP_OK(hipStreamSynchronize(c->stream));
-        drained = true;
-        HIP_OK(hipMemcpy(n.stream[k], host.data(), d[k].bytes, hipMemcpyHostToDevice));
+        if (!n.cst[d[k].cst]) HIP_OK(hipMalloc((void**)&n.cst[d[k].cst], kConstBytes));
+        // (every kind of a block writes the block's constants: the same values, in stream order)
+        launch_repack(d[k].elem, dev_blob, tab, n.stream[k], d[k].bytes / (d[k].elem == kElemF32 ? 4 : 2), ctab, n.cst[d[k].cst],
+                      c->stream);
     }
-    for (int b = 0; b < kConstBlocks; ++b) {
-        if (cst[b].empty()) continue;
-        if (!n.cst[b]) HIP_OK(hipMalloc((void**)&n.cst[b], kConstBytes));
-        HIP_OK(hipMemcpy(n.cst[b], cst[b].data(), kConstBytes, hipMemcpyHostToDevice));
-    }
-    const size_t nf = nerf_blob_size(&c->cfg);
-    if (n.host_blob.data() != blob_in) n.host_blob.assign(blob_in, blob_in + nf);
-    n.loaded = true;
+    HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -558,7 +493,10 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     for (auto& n : c->net) {
         for (void* p : n.stream) if (p) (void)hipFree(p);
         for (float* p : n.cst) if (p) (void)hipFree(p);
+        if (n.dev_blob) (void)hipFree(n.dev_blob);
     }
+    for (int32_t* p : c->rt) if (p) (void)hipFree(p);
+    for (int32_t* p : c->rt_cst) if (p) (void)hipFree(p);
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (hipEvent_t e : c->copy_ev) (void)hipEventDestroy(e);
@@ -782,7 +720,17 @@ int nerf_load_weights(nerf_ctx* c, int which, const float* blob, size_t n_floats
     if (which != NERF_NET_COARSE && which != NERF_NET_FINE) return fail("which must be 0 (coarse) or 1 (fine)");
     const size_t want = nerf_blob_size(&c->cfg);
     if (n_floats != want) return fail("weight blob has %zu floats, expected %zu", n_floats, want);
-    if (int r = upload_packed_weights(c, which, blob)) return r;
+    HIP_OK(hipSetDevice(c->cfg.device));
+    // The blob goes to the device and every stream is re-packed from it there, all enqueued on the ctx stream: work already on
+    // that stream still reads the old weights, work enqueued later the new ones.  No other stream reads a render stream (the
+    // copy stream moves finished outputs, the trainer's side stream works on the trainer's own buffers), so nothing waits.
+    // host_blob is pageable: a copy from it has left the host when hipMemcpyAsync returns, and the next load may overwrite it.
+    NetWeights& n = c->net[which];
+    n.host_blob.assign(blob, blob + want);
+    if (!n.dev_blob) HIP_OK(hipMalloc((void**)&n.dev_blob, want * sizeof(float)));
+    HIP_OK(hipMemcpyAsync(n.dev_blob, n.host_blob.data(), want * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int r = repack_render_streams(c, which, n.dev_blob)) return r;
+    n.loaded = true;
     return train_on_load(c, which);      // a running trainer restarts from the new weights
 }
 

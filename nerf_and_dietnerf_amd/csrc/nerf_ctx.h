@@ -30,6 +30,7 @@ struct NetWeights {
     float* cst[kConstBlocks] = {};     // kConstBytes each
     bool loaded = false;
     std::vector<float> host_blob;   // last blob handed to nerf_load_weights (Keras order): seed of the trainer
+    float* dev_blob = nullptr;      // ... and its copy on the device, which nerf_load_weights re-packs the streams from
 };
 
 // The record of one culled pass (cull_kernels.hip): verdict bits, the scan's slot per mask byte (both grow-only), the row count.
@@ -74,6 +75,12 @@ struct nerf_ctx {
     hipStream_t copy_stream = nullptr;         // device-to-host copies of nerf_render_image(NERF_MEM_HOST), beside the kernels
     std::vector<hipEvent_t> copy_ev;           // "batch k is done" events the copy stream waits on (ring)
     nerf::NetWeights net[2];
+    // Device gather tables of the operand streams (nerf_kernels.h::build_stream_tables), built on first use: rt[k] the table
+    // of stream kind k where k is its own table source (StreamDesc::table), rt_cst[b] the table of constant block b.  The
+    // render path's streams and the fused trainer's stash-forward stream are all re-packed through them.
+    int32_t* rt[nerf::kStreamKinds] = {};
+    int32_t* rt_cst[nerf::kConstBlocks] = {};
+    bool rt_built = false;
     // scratch arena (grow-only).  Staging (nerf::Staging, host-memory calls): b_orig, b_dirs (rays), b_u0, b_u1 (draws), b_in0,
     // b_in1, b_in2 (other arguments), b_out[i] (member i of nerf_outputs); an entry also stages in b_zc, b_zf or b_raw where the
     // passes it runs leave that buffer alone.  The passes (draw_z_values, dev_render, dev_render_rays, run_mlp's callers, the
@@ -141,7 +148,11 @@ void train_free(nerf_ctx* c);                       // train_api.hip: releases c
 void comm_free(nerf_ctx* c);                        // comm_api.hip: releases c->comm (called by nerf_ctx_destroy)
 int comm_allreduce_mean(nerf_ctx* c, float* buf, size_t n);   // comm_api.hip: no-op without a communicator / one rank
 int comm_world(const nerf_ctx* c);                            // ranks of the ctx's communicator (1 without one)
-int upload_packed_weights(nerf_ctx* c, int which, const float* blob_host);   // nerf_api.hip: pack + upload streams
+// nerf_api.hip: the ctx's gather tables, built and uploaded once; every operand stream network `which` keeps (allocated on
+// first use) re-packed from a device blob of its weights, enqueued on the ctx stream -- after a weight load and after
+// optimizer steps alike
+int ensure_render_tables(nerf_ctx* c);
+int repack_render_streams(nerf_ctx* c, int which, const float* dev_blob);
 int train_on_load(nerf_ctx* c, int which);          // train_api.hip: no-op without a trainer
 int train_flush_weights(nerf_ctx* c, int which, bool to_host = false);
 // (train_flush_weights: train_api.hip, no-op unless optimizer steps changed the weights)

@@ -4,11 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace nerf {
 
 // ---- fixed network geometry of the fused kernel (all BASELINE configs) ----
 // n_angles_for_model 2 and 1 share the kernels: with 1 the y component of the view direction is still
-// encoded on device but its weight rows are packed as zeros (host side, pack_weights_*).
+// encoded on device but its weight rows are zeros (padding entries of the gather tables below).
 constexpr int kLx = 5;           // n_pos_enc_dim_xyz
 constexpr int kLd = 4;           // n_pos_enc_view_dir
 constexpr int kHidden = 256;
@@ -16,13 +18,19 @@ constexpr int kLast = 128;
 constexpr int kXyzDim = 3 + 6 * kLx;   // 33
 constexpr int kDirDim = 6 * kLd;       // 24
 // Fewer octaves (1 <= Lx <= kLx, 1 <= Ld <= kLd) run on the same kernels, the way n_angles 1 does: the octaves the network
-// does not have are still encoded on device, but their weight rows are zeros.  Every packer and gather table is written
-// for the (kLx, kLd) blob; an (Lx, Ld) blob is first spread into that layout (blob_expand_index, nerf_api.hip).
-// Floats of the weight blob of an (lx, ld, n_angles) network (Keras get_weights() order, src/NeRF.py:249-339)
+// does not have are still encoded on device, but their weight rows are zeros.  Every gather table is written for the
+// (kLx, kLd) blob (kLxWide: the wide-PE kernels') and then aimed at the network's own (lx, ld) blob (aim_gather).
+// weight_tables.hip: the Dense layers' (in, out) of an (lx, ld, n_angles) network in Keras creation order (src/NeRF.py:249-339)
+// -> the layer count, 11, or 12 for the xyz-only network.  The one place the shapes are written.
+int layer_dims(int lx, int ld, int n_angles, int dims[12][2]);
+// Floats of the weight blob of that network (Keras get_weights() order: kernel (in, out) row-major, bias, per layer)
 size_t blob_floats(int lx, int ld, int n_angles);
 // idx[i], i < blob_floats(layout_lx, kLd, n_angles): 1 + the index of the same weight in the (lx, ld) blob, 0 where the
 // (layout_lx, kLd) layout holds an octave row the (lx, ld) network does not have (a zero); layout_lx = kLx or kLxWide
 void blob_expand_index(int lx, int ld, int n_angles, int32_t* idx, int layout_lx = kLx);
+// A table written for the (pe_layout_lx(lx), kLd) blob, re-aimed at the (lx, ld) blob: the slots of the octave rows the network
+// does not have become padding.  f16: entries are 2 * (src + 1) + is_lo (the 16-bit streams); else src + 1
+void aim_gather(int lx, int ld, int n_angles, int32_t* idx, size_t n, bool f16);
 
 // ---- weight stream geometry (see DESIGN.md "weight stream") ----
 // A "quad" is the A operand of 4 consecutive MFMA k-steps for one 32-wide output tile:
@@ -91,72 +99,61 @@ struct MlpArgs {
 // mlp_fp32.hip
 void launch_mlp_fp32(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only = false);
 void mlp_fp32_set_attributes();
-// host-side packing of one network's blob (11 x (kernel(in,out), bias)) into stream + const
-void pack_weights_fp32(const float* blob, int n_angles, float* stream_out /*kStreamBytes/4; n_angles 0: kStreamBytesXyzF32/4*/, float* const_out /*kConstFloats*/);
+// gather table of the fp32 stream of the (kLx, kLd) blob (kStreamBytes / 4 entries; n_angles 0: kStreamBytesXyzF32 / 4) and of
+// its constant block (kConstFloats): entry = src + 1, 0 = padding
+void build_fp32_gather(int n_angles, int32_t* stream_idx, int32_t* const_idx);
 
 // mlp_f16x3.hip
 // single_pass: hi*hi only; xyz_only: the 12-layer network without view directions (its own streams / constants)
 void launch_mlp_f16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
 // forward that also writes a.st_ptr / a.mask_ptr (training); single_pass: the mixed_float16-class arithmetic
 void launch_mlp_f16x3_stash(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
-// device-side re-pack of the 3-pass (or hi-only) stream + constants from a blob (tables from build_f16x3_gather, host)
-size_t f16_stream_bytes(int n_angles, bool hi_only);     // kStreamBytesF16[Hi][Xyz]
-void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx /* f16_stream_bytes / 2 */,
-                        int32_t* const_idx /*kConstFloats*/);
-void launch_repack_f16x3(const float* blob, const int32_t* stream_idx, void* stream, const int32_t* const_idx, float* cst,
-                         size_t stream_bytes, hipStream_t s);
+// gather tables of the 3-pass (or hi-only) stream (kStreamBytesF16[Hi][Xyz] / 2 entries: 2 * (src + 1) + is_lo) and of the
+// 16-bit kernels' constant block (kConstFloats: src + 1; the same from either stream); 0 = padding
+void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx, int32_t* const_idx);
 void mlp_f16x3_set_attributes();
-// stream_out: kStreamBytesF16 / kStreamBytesF16Hi bytes (kStreamBytesF16Xyz / kStreamBytesF16HiXyz when n_angles == 0)
-void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
-void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
 // sigma-only coarse render (3-pass, n_angles 1 or 2, the kLx build only): a.raw receives sigma alone, (M,) floats; its
-// stream (kStreamBytesF16Sig) ends in layer 8's sigma tile, its constants are pack_weights_f16x3's
+// stream (kStreamBytesF16Sig) ends in layer 8's sigma tile, its constants are the full stream's
 void launch_mlp_f16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream);
-void pack_weights_f16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
 void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx /* kStreamBytesF16Sig / 2 */);
 
 // mlp_f16x3_wide.hip -- the same entry points for networks with n_pos_enc_dim_xyz 6..10: kernels that encode kLxWide octaves,
-// packers / gather tables for the (kLxWide, kLd) blob layout (same stream sizes).  No exact-fp32 render kernel exists for them.
+// gather tables for the (kLxWide, kLd) blob layout (same stream sizes).  No exact-fp32 render kernel exists for them.
 constexpr int kLxWide = 10;
 namespace wide {
 void launch_mlp_f16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
 void launch_mlp_f16x3_stash(const MlpArgs& a, int num_cus, hipStream_t stream, bool single_pass = false, bool xyz_only = false);
 void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx, int32_t* const_idx);
 void mlp_f16x3_set_attributes();
-void pack_weights_f16x3(const float* blob, int n_angles, void* stream_out, float* const_out);
-void pack_weights_f16(const float* blob, int n_angles, void* stream_out, float* const_out);
 }  // namespace wide
 // mlp_bf16x3.hip / mlp_bf16x3_wide.hip -- the bf16 build of mlp_f16x3.hip's 3-pass RENDER kernels (NERF_PRECISION_BF16X3):
-// bf16 hi/lo streams of the same geometry (kStreamBytesF16 / kStreamBytesF16Xyz / kStreamBytesF16Sig), the constants of
-// pack_weights_f16x3.  No single-pass and no stash variant.  The device re-pack reads build_f16x3_gather's /
-// build_f16x3_sig_gather's stream tables (same slots) and rounds to bf16.
+// bf16 hi/lo streams of the same geometry (kStreamBytesF16 / kStreamBytesF16Xyz / kStreamBytesF16Sig) and the same constants.
+// No single-pass and no stash variant.  Their streams are re-packed from the fp16 twins' gather tables (same slots), rounded
+// to bf16.
 namespace bf16 {
 void launch_mlp_bf16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only = false);
 void launch_mlp_bf16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream);      // the kLx build only, as the fp16 one
 void mlp_bf16x3_set_attributes();
-void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
-void pack_weights_bf16x3_sig(const float* blob, int n_angles, void* stream_out, float* const_out /*kConstFloats*/);
-void launch_repack_bf16x3(const float* blob, const int32_t* stream_idx, void* stream, size_t stream_bytes, hipStream_t s);
 namespace wide {
 void launch_mlp_bf16x3(const MlpArgs& a, int num_cus, hipStream_t stream, bool xyz_only = false);
 void mlp_bf16x3_set_attributes();
-void pack_weights_bf16x3(const float* blob, int n_angles, void* stream_out, float* const_out);
 }  // namespace wide
 }  // namespace bf16
 // the octaves of the blob layout the kernels of an (lx, .) network are packed for: kLx, or kLxWide for lx > kLx
 inline int pe_layout_lx(int lx) { return lx > kLx ? kLxWide : kLx; }
 
 // ---- the render path's resident operand streams, stated once ----
-// Upload (nerf_api.hip), kernel choice (pick_render_kernel), the device re-pack after optimizer steps (train_api.hip) and
-// the host-sanitizer tool (tools/pack_asan_test.cpp) all walk render_streams(); none of them names a stream on its own.
+// Every stream is a gather table over the weight blob plus one device re-pack (launch_repack).  The re-pack after a weight
+// load and after optimizer steps (nerf_api.hip: repack_render_streams), kernel choice (pick_render_kernel) and the
+// host-sanitizer tool (tools/pack_asan_test.cpp) all walk render_streams(); none of them names a stream on its own.
 enum StreamKind { kF16x3, kF16Hi, kBf16x3, kF16x3Sig, kBf16x3Sig, kFp32, kStreamKinds };   // in re-pack order
-enum ConstBlock { kConstFp32, kConst16, kConstBlocks };   // pack_weights_fp32's constants / the ones every 16-bit packer writes
+enum ConstBlock { kConstFp32, kConst16, kConstBlocks };   // the fp32 kernel's constants / the ones every 16-bit kernel reads
+enum StreamElem { kElemF16, kElemBf16, kElemF32 };        // what a slot holds: an fp16 or bf16 hi / lo part, or the fp32 value
 struct StreamDesc {
     size_t bytes;        // 0: this network does not keep the stream
-    void (*pack)(const float* blob, int n_angles, void* stream_out /*bytes*/, float* const_out /*kConstFloats*/);
-    ConstBlock cst;      // the constant block the packer fills
-    StreamKind table;    // the kind whose gather table the device re-pack reads (the bf16 kinds: their fp16 twins', same slots)
-    bool bf16;           // ... and whether it rounds to bf16 (launch_repack_bf16x3) or to fp16 (launch_repack_f16x3)
+    ConstBlock cst;      // the constant block its kernels read
+    StreamKind table;    // the kind whose gather table the re-pack reads (the bf16 kinds: their fp16 twins', same slots)
+    StreamElem elem;     // ... and what it rounds a gathered weight to
 };
 // the streams network `which` (0 = coarse, 1 = fine) of an (lx, n_angles) config keeps.  Wide-PE networks (lx > kLx) have no
 // fp32 and no sigma-only streams; xyz-only networks the ...Xyz sizes and no sigma-only streams; sigma-only: the coarse network
@@ -164,20 +161,31 @@ inline void render_streams(int lx, int n_angles, int which, StreamDesc d[kStream
     const bool wd = lx > kLx, xyz = n_angles == 0;
     const size_t b3 = xyz ? kStreamBytesF16Xyz : kStreamBytesF16, b1 = xyz ? kStreamBytesF16HiXyz : kStreamBytesF16Hi;
     const size_t bs = !wd && !xyz && which == 0 ? kStreamBytesF16Sig : 0, bf = wd ? 0 : xyz ? kStreamBytesXyzF32 : kStreamBytes;
-    d[kF16x3] = {b3, wd ? wide::pack_weights_f16x3 : pack_weights_f16x3, kConst16, kF16x3, false};
-    d[kF16Hi] = {b1, wd ? wide::pack_weights_f16 : pack_weights_f16, kConst16, kF16Hi, false};
-    d[kBf16x3] = {b3, wd ? bf16::wide::pack_weights_bf16x3 : bf16::pack_weights_bf16x3, kConst16, kF16x3, true};
-    d[kF16x3Sig] = {bs, pack_weights_f16x3_sig, kConst16, kF16x3Sig, false};
-    d[kBf16x3Sig] = {bs, bf16::pack_weights_bf16x3_sig, kConst16, kF16x3Sig, true};
-    d[kFp32] = {bf, [](const float* b, int na, void* s, float* c) { pack_weights_fp32(b, na, (float*)s, c); }, kConstFp32, kFp32, false};
+    d[kF16x3] = {b3, kConst16, kF16x3, kElemF16};
+    d[kF16Hi] = {b1, kConst16, kF16Hi, kElemF16};
+    d[kBf16x3] = {b3, kConst16, kF16x3, kElemBf16};
+    d[kF16x3Sig] = {bs, kConst16, kF16x3Sig, kElemF16};
+    d[kBf16x3Sig] = {bs, kConst16, kF16x3Sig, kElemBf16};
+    d[kFp32] = {bf, kConstFp32, kFp32, kElemF32};
 }
-// gather table (bytes / 2 entries) of a 16-bit kind that is its own table source; -> whether const_idx (kConstFloats entries,
-// the kConst16 block's: the same from every kind) was written too.  The fp32 kind's table is its packer run on an index blob.
+// The table builder of a kind that is its own table source: stream_idx (bytes / 2 entries, the fp32 kind: bytes / 4), written
+// for the (pe_layout_lx(lx), kLd) blob; -> whether the kind owns its constant block, i.e. const_idx (kConstFloats entries) was
+// written too.  kF16x3 owns kConst16 (every config keeps that stream), kFp32 owns kConstFp32.
 inline bool build_stream_gather(int lx, int n_angles, StreamKind k, int32_t* stream_idx, int32_t* const_idx) {
+    if (k == kFp32) { build_fp32_gather(n_angles, stream_idx, const_idx); return true; }
     if (k == kF16x3Sig) { build_f16x3_sig_gather(n_angles, stream_idx); return false; }
-    (lx > kLx ? wide::build_f16x3_gather : build_f16x3_gather)(n_angles, k == kF16Hi, stream_idx, const_idx);
-    return true;
+    (lx > kLx ? wide::build_f16x3_gather : build_f16x3_gather)(n_angles, k == kF16Hi, stream_idx, k == kF16x3 ? const_idx : nullptr);
+    return k == kF16x3;
 }
+// weight_tables.hip: every table of an (lx, ld, n_angles) config, aimed at its own blob -- stream[k] for each kind either
+// network keeps that is its own table source (empty otherwise), cst[b] for each constant block a kept kind owns
+struct StreamTables { std::vector<int32_t> stream[kStreamKinds], cst[kConstBlocks]; };
+void build_stream_tables(int lx, int ld, int n_angles, StreamTables& t);
+// aux_kernels.hip: the one device re-pack.  out[i], i < n: the weight slot idx[i] names, rounded to `elem` (fp16 / bf16: hi
+// = the rounded weight, lo = the rounded rest; fp32: the weight), 0 for padding; and, with const_idx, cst[i] for i <
+// kConstFloats the same way in fp32 (a table's constant block rides in its stream's launch)
+void launch_repack(StreamElem elem, const float* blob, const int32_t* idx, void* out, size_t n, const int32_t* const_idx,
+                   float* cst, hipStream_t s);
 
 // mlp_f16_2t.hip -- single-pass fp16 render kernel with two 32-sample tiles per wave (same hi-only stream / constants)
 void launch_mlp_f16_2t(const MlpArgs& a, int num_cus, hipStream_t stream);
@@ -194,7 +202,7 @@ constexpr int kBwdXyzLd = 64;                                      // floats per
 // true-scale value at all (a select and a multiply per value less than the fp32 buffers they replaced).  The mixed_float16
 // policy's single-pass chain stores plain fp16 gradients instead.
 struct MlpBwdArgs {
-    const void* wstream;     // backward operand stream of one network (build_bwd_gather / launch_repack_bwd)
+    const void* wstream;     // backward operand stream of one network (build_bwd_gather / launch_repack)
     const float* wconst;     // the forward kernel's constant block (rgb head weights are read from it)
     const float* graw;       // (Mp, 4) gradient w.r.t. the raw network output [r, g, b, sigma]; padding rows zero
     const uint32_t* mask_ptr[10];  // LeakyReLU' bit records of layers 0..8 (0..9: xyz-only network), written by the stash forward
@@ -215,10 +223,9 @@ struct MlpBwdArgs {
 void launch_mlp_bwd_f16x3(const MlpBwdArgs& a, bool dx, bool single_pass, int num_cus, hipStream_t stream,
                           bool xyz_only = false);
 void mlp_bwd_f16x3_set_attributes();
-// xyz_dim: rows of the encoding block of the blob layout the table indexes (kXyzDim, or 3 + 6 kLxWide for the wide-PE
-// layout: the chain's two encoding tiles hold up to 64 rows)
-void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 */, int xyz_dim = kXyzDim);
-void launch_repack_bwd(const float* blob, const int32_t* idx, void* stream, hipStream_t s);
+// layout_lx: the octaves of the blob layout the table indexes (kLx, or kLxWide: the chain's two encoding tiles hold up to 64
+// rows); entries as the fp16 streams' (2 * (src + 1) + is_lo), re-packed by launch_repack(kElemF16, ...)
+void build_bwd_gather(int n_angles, bool dx, bool hi_only, int32_t* idx /* kBwdStreamBytes / 2 */, int layout_lx = kLx);
 
 // aux_kernels.hip
 void launch_raygen(const float c2w_host[16], float fov, int H, int W,

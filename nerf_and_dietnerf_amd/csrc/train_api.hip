@@ -76,8 +76,9 @@ struct TrainState {
     // on fragment-major buffers (frag_layout.h::frag_index) that hold fp32 activations and "pair16" gradients (fp16 (hi, lo)
     // pairs in the fp32 slots, MlpBwdArgs::rs_ptr) under the float32 policy, fp16 values under mixed_float16.
     bool reference = false;
-    int32_t *sidx = nullptr, *cidx = nullptr;   // device gather tables of the fused forward's stream / constants
-    int32_t* bidx[2] = {nullptr, nullptr};      // gather tables of the backward stream: [0] plain, [1] with encoding tiles
+    // device gather tables of the backward stream: [0] plain, [1] with encoding tiles (the stash forward's stream and
+    // constants are re-packed through the ctx's tables of the render stream of the same kind: nerf_ctx::rt)
+    int32_t* bidx[2] = {nullptr, nullptr};
     long long step = 0;
     size_t nblob = 0;
     TNet net[2];
@@ -115,13 +116,9 @@ struct TrainState {
     DevBuf macc;                    // running sums of the step metrics (4 doubles: loss, psnr_coarse, psnr_fine, steps)
     DevBuf gsave[2];                // ... under mixed_float16 with accumulate = 1: the (unscaled) gradients already there
     // A render between optimizer steps (DietNeRF's consistency render every 13th step, the epoch plots) needs the render
-    // path's operand streams (nerf_kernels.h::render_streams) re-packed from the trained blob: on the DEVICE, by gather tables
-    // built once from the host packers (round 4; the device -> host -> pack x 3 -> device round trip this replaces cost ~30 ms
-    // and two synchronisations per render).  rt[k]: the table of stream kind k where k is its own table source (StreamDesc::
-    // table), rt_cst[b]: the table of constant block b.
-    int32_t* rt[kStreamKinds] = {};
-    int32_t* rt_cst[kConstBlocks] = {};
-    bool rt_built = false;
+    // path's operand streams (nerf_kernels.h::render_streams) re-packed from the trained blob: train_flush_weights does what
+    // nerf_load_weights does, from TNet::blob instead of the loaded blob's device copy (repack_render_streams: the ctx's
+    // gather tables and one kernel per stream on the ctx stream, no synchronisation).
     std::vector<RenderSlot> slots;  // nerf_train_render_forward / _backward
 };
 
@@ -130,23 +127,18 @@ struct TrainState {
 namespace {
 
 int layer_table(const nerf_config& cfg, TLayer L[12]) {
-    const int kd = 2 * cfg.n_pos_enc_dir * (cfg.n_angles + 1);   // direction encoding: 24 at (Ld 4, n_angles 2)
     const int xd = 3 + 6 * cfg.n_pos_enc_xyz;                    // xyz encoding: 33 at Lx 5
-    // {K_real, N_real, Kp, Np, rowmap}; rowmap = xd on layer 4 (train_kernels.h, ReduceArgs::rowmap)
-    const int with_dirs[11][5] = {
-        {xd, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {256 + xd, 256, kLdC4, 256, xd},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {256 + kd, 128, kLdC8, 128, 0}, {128, 3, 128, 32, 0}, {256 + kd, 1, kLdC8, 32, 0}};
-    // get_network_only_xyz (src/NeRF.py:248-288): ... h8 -> dense 256 -> dense 128 -> rgb; sigma from h8
-    const int xyz_only[12][5] = {
-        {xd, 256, kXyzPad, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {256 + xd, 256, kLdC4, 256, xd},  {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0}, {256, 256, 256, 256, 0},
-        {256, 256, 256, 256, 0}, {256, 128, 256, 128, 0}, {128, 3, 128, 32, 0}, {256, 1, 256, 32, 0}};
-    const int n = cfg.n_angles == 0 ? 12 : 11;
+    int dims[12][2];                                             // {K_real, N_real}
+    const int n = layer_dims(cfg.n_pos_enc_xyz, cfg.n_pos_enc_dir, cfg.n_angles, dims);
+    // {Kp, Np, rowmap} of the reference trainer's padded matrices; rowmap = xd on layer 4 (train_kernels.h, ReduceArgs::rowmap)
+    const int with_dirs[11][3] = {{kXyzPad, 256, 0}, {256, 256, 0}, {256, 256, 0}, {256, 256, 0}, {kLdC4, 256, xd}, {256, 256, 0},
+                                  {256, 256, 0}, {256, 256, 0}, {kLdC8, 128, 0}, {128, 32, 0}, {kLdC8, 32, 0}};
+    const int xyz_only[12][3] = {{kXyzPad, 256, 0}, {256, 256, 0}, {256, 256, 0}, {256, 256, 0}, {kLdC4, 256, xd}, {256, 256, 0},
+                                 {256, 256, 0}, {256, 256, 0}, {256, 256, 0}, {256, 128, 0}, {128, 32, 0}, {256, 32, 0}};
     size_t off = 0;
     for (int l = 0; l < n; ++l) {
-        const int* sh = cfg.n_angles == 0 ? xyz_only[l] : with_dirs[l];
-        L[l].K_real = sh[0]; L[l].N_real = sh[1]; L[l].Kp = sh[2]; L[l].Np = sh[3]; L[l].rowmap = sh[4];
+        const int* pad = cfg.n_angles == 0 ? xyz_only[l] : with_dirs[l];
+        L[l].K_real = dims[l][0]; L[l].N_real = dims[l][1]; L[l].Kp = pad[0]; L[l].Np = pad[1]; L[l].rowmap = pad[2];
         L[l].w_off = off; off += (size_t)L[l].K_real * L[l].N_real;
         L[l].b_off = off; off += L[l].N_real;
         L[l].W = L[l].WT = L[l].bias = nullptr;
@@ -168,28 +160,14 @@ void free_slot(RenderSlot& s) {
     for (DevBuf* b : {&s.o, &s.d, &s.u_c, &s.u_f, &s.z_new}) free_buf(*b);
 }
 
-// The gather tables index the (kLx, kLd) blob (nerf_kernels.h::blob_expand_index); a network with fewer octaves keeps its own
-// (shorter) blob on the device: its tables are re-aimed at it, and the slots of the octave rows it does not have become padding.
-// f16: entries are 2 * (src + 1) + is_lo (the fp16 streams); else src + 1
-// (the wide-PE tables index the (kLxWide, kLd) blob)
-void aim_gather(const nerf_config& cfg, int32_t* idx, size_t n, bool f16) {
-    const int L = pe_layout_lx(cfg.n_pos_enc_xyz);
-    if (cfg.n_pos_enc_xyz == L && cfg.n_pos_enc_dir == kLd) return;
-    std::vector<int32_t> map(blob_floats(L, kLd, cfg.n_angles));
-    blob_expand_index(cfg.n_pos_enc_xyz, cfg.n_pos_enc_dir, cfg.n_angles, map.data(), L);
-    for (size_t i = 0; i < n; ++i) {
-        const int32_t t = idx[i];
-        if (!t) continue;
-        const int32_t m = map[(f16 ? t >> 1 : t) - 1];
-        idx[i] = m == 0 ? 0 : f16 ? 2 * m + (t & 1) : m;
-    }
-}
-
 int relayout_net(nerf_ctx* c, TNet& n) {
     const TrainState* t = c->train;
     if (!t->reference) {     // the fused kernels read their two re-packed streams and nothing else
-        launch_repack_f16x3(n.blob, t->sidx, n.fstream, t->cidx, n.fcst, f16_stream_bytes(c->cfg.n_angles, t->mixed), c->stream);
-        launch_repack_bwd(n.blob, t->bidx[n.bdx ? 1 : 0], n.bstream, c->stream);
+        const StreamKind k = t->mixed ? kF16Hi : kF16x3;      // the stash forward reads the render stream of its arithmetic
+        StreamDesc d[kStreamKinds];
+        render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, 1, d);
+        launch_repack(kElemF16, n.blob, c->rt[k], n.fstream, d[k].bytes / 2, c->rt_cst[kConst16], n.fcst, c->stream);
+        launch_repack(kElemF16, n.blob, t->bidx[n.bdx ? 1 : 0], n.bstream, kBwdStreamBytes / 2, nullptr, nullptr, c->stream);
         HIP_OK(hipGetLastError());
         return 0;
     }
@@ -216,19 +194,9 @@ int alloc_optimizer(nerf_ctx* c, TrainState* t, TNet& n) {
     return 0;
 }
 
-// the fused trainer's operand streams of one network (and, once, the gather tables they are re-packed with)
+// the fused trainer's operand streams of one network (and, once, the backward gather table they are re-packed with)
 int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
-    if (!t->sidx) {
-        std::vector<int32_t> si(f16_stream_bytes(c->cfg.n_angles, t->mixed) / 2), ci(kConstFloats);
-        if (c->cfg.n_pos_enc_xyz > kLx) wide::build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
-        else build_f16x3_gather(c->cfg.n_angles, t->mixed, si.data(), ci.data());
-        aim_gather(c->cfg, si.data(), si.size(), true);
-        aim_gather(c->cfg, ci.data(), ci.size(), false);
-        HIP_OK(hipMalloc((void**)&t->sidx, si.size() * sizeof(int32_t)));
-        HIP_OK(hipMalloc((void**)&t->cidx, ci.size() * sizeof(int32_t)));
-        HIP_OK(hipMemcpy(t->sidx, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(t->cidx, ci.data(), ci.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (int r = ensure_render_tables(c)) return r;
     if (!n.fstream) HIP_OK(hipMalloc(&n.fstream, kStreamBytesF16Xyz));     // the largest of the four streams
     if (!n.fcst) HIP_OK(hipMalloc((void**)&n.fcst, kConstBytes));
     // the fine network's chain also produces the gradient w.r.t. the xyz encoding when the sampler is differentiated
@@ -236,8 +204,8 @@ int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
     int32_t*& bi = t->bidx[n.bdx ? 1 : 0];
     if (!bi) {
         std::vector<int32_t> idx(kBwdStreamBytes / 2);
-        build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data(), 3 + 6 * pe_layout_lx(c->cfg.n_pos_enc_xyz));
-        aim_gather(c->cfg, idx.data(), idx.size(), true);
+        build_bwd_gather(c->cfg.n_angles, n.bdx, t->mixed, idx.data(), pe_layout_lx(c->cfg.n_pos_enc_xyz));
+        aim_gather(c->cfg.n_pos_enc_xyz, c->cfg.n_pos_enc_dir, c->cfg.n_angles, idx.data(), idx.size(), true);
         HIP_OK(hipMalloc((void**)&bi, idx.size() * sizeof(int32_t)));
         HIP_OK(hipMemcpy(bi, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
@@ -1176,10 +1144,6 @@ void train_free(nerf_ctx* c) {
         if (n.fcst) (void)hipFree(n.fcst);
         if (n.bstream) (void)hipFree(n.bstream);
     }
-    for (int32_t* p : t->rt) if (p) (void)hipFree(p);
-    for (int32_t* p : t->rt_cst) if (p) (void)hipFree(p);
-    if (t->sidx) (void)hipFree(t->sidx);
-    if (t->cidx) (void)hipFree(t->cidx);
     for (int32_t* bi : t->bidx) if (bi) (void)hipFree(bi);
     for (TPass& p : t->pass) free_pass(p);
     for (RenderSlot& sl : t->slots) free_slot(sl);
@@ -1206,50 +1170,6 @@ int train_on_load(nerf_ctx* c, int which) {
     return relayout_net(c, n);
 }
 
-// gather tables of the render path's operand streams (see TrainState::rt): one for every kind either network keeps
-static int ensure_render_tables(nerf_ctx* c, TrainState* t) {
-    if (t->rt_built) return 0;
-    const int na = c->cfg.n_angles, lx = c->cfg.n_pos_enc_xyz;
-    auto up = [&](const std::vector<int32_t>& v, int32_t** dst) -> int {
-        if (!*dst) HIP_OK(hipMalloc((void**)dst, v.size() * sizeof(int32_t)));
-        HIP_OK(hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        return 0;
-    };
-    StreamDesc d[2][kStreamKinds];
-    for (int w = 0; w < 2; ++w) render_streams(lx, na, w, d[w]);
-    std::vector<int32_t> c16;                // the 16-bit kinds' constant table: every builder must give the same one
-    for (int k = 0; k < kStreamKinds; ++k) {
-        const size_t bytes = std::max(d[0][k].bytes, d[1][k].bytes);
-        if (!bytes || d[0][k].table != k) continue;
-        std::vector<int32_t> si(bytes / (k == kFp32 ? 4 : 2)), ci(kConstFloats);
-        if (k == kFp32) {
-            // pack a blob whose entry i holds i + 1 (exact in fp32: the blob has 5e5 entries) -- what lands in a slot is the
-            // 1-based index of the weight that belongs there, 0 where the packer pads.  The packer takes the (kLx, kLd)
-            // layout: its entry i holds the 1-based index of the trained blob's weight there, 0 for an octave row it does not have
-            std::vector<int32_t> wide(blob_floats(kLx, kLd, na));
-            for (size_t i = 0; i < wide.size(); ++i) wide[i] = (int32_t)(i + 1);
-            aim_gather(c->cfg, wide.data(), wide.size(), false);
-            std::vector<float> idx(wide.begin(), wide.end()), sf(si.size()), cf(kConstFloats);
-            d[0][k].pack(idx.data(), na, sf.data(), cf.data());
-            si.assign(sf.begin(), sf.end());
-            ci.assign(cf.begin(), cf.end());
-            if (int r = up(ci, &t->rt_cst[kConstFp32])) return r;
-        } else {
-            const bool has_cst = build_stream_gather(lx, na, (StreamKind)k, si.data(), ci.data());
-            aim_gather(c->cfg, si.data(), si.size(), true);
-            if (has_cst && !c16.empty() && ci != c16) return fail("internal: the two fp16 streams disagree about their constants");
-            if (has_cst && c16.empty()) {
-                c16 = ci;
-                aim_gather(c->cfg, ci.data(), ci.size(), false);
-                if (int r = up(ci, &t->rt_cst[kConst16])) return r;
-            }
-        }
-        if (int r = up(si, &t->rt[k])) return r;
-    }
-    t->rt_built = true;
-    return 0;
-}
-
 // The render path's view of a network that is being trained.  After optimizer steps its operand streams are
 // re-packed from the trained blob on the device (enqueued on the ctx stream: a render between steps does not synchronise);
 // to_host additionally brings NetWeights::host_blob up to date (nerf_train_end, a restarting nerf_train_begin: the next
@@ -1260,20 +1180,7 @@ int train_flush_weights(nerf_ctx* c, int which, bool to_host) {
     TNet& n = t->net[which];
     NetWeights& nw = c->net[which];
     if (n.render_dirty) {
-        if (int r = ensure_render_tables(c, t)) return r;
-        StreamDesc d[kStreamKinds];
-        render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, which, d);
-        for (int k = 0; k < kStreamKinds; ++k) {
-            if (!d[k].bytes) continue;
-            const int32_t *tab = t->rt[d[k].table], *ctab = t->rt_cst[d[k].cst];
-            if (!tab || !ctab || !nw.stream[k]) return fail("internal: no gather table for stream kind %d of network %d", k, which);
-            if (k == kFp32) {                // pack_weights_fp32 only moves values: plain gathers of stream and constants
-                launch_gather_blob(n.blob, tab, (float*)nw.stream[k], d[k].bytes / 4, c->stream);
-                launch_gather_blob(n.blob, ctab, nw.cst[d[k].cst], kConstFloats, c->stream);
-            } else if (d[k].bf16) bf16::launch_repack_bf16x3(n.blob, tab, nw.stream[k], d[k].bytes, c->stream);   // (constants: its fp16 twin's)
-            else launch_repack_f16x3(n.blob, tab, nw.stream[k], ctab, nw.cst[d[k].cst], d[k].bytes, c->stream);
-        }
-        HIP_OK(hipGetLastError());
+        if (int r = repack_render_streams(c, which, n.blob)) return r;
         n.render_dirty = false;
         n.host_stale = true;
     }

@@ -1,0 +1,99 @@
+// weight_tables.hip -- from a weight blob to the kernels' operand streams, host half: the shape of the blob (layer_dims), the
+// map between blobs of different octave counts (blob_expand_index, aim_gather) and every gather table of a config
+// (build_stream_tables).  Host code only; the device half is aux_kernels.hip::launch_repack.
+#include "nerf_kernels.h"
+
+#include <algorithm>
+
+namespace nerf {
+
+int layer_dims(int lx, int ld, int n_angles, int dims[12][2]) {
+    const int xd = 3 + 6 * lx;                                  // src/NeRF.py:312
+    const int kd = 256 + 2 * ld * (n_angles + 1);               // [hidden, dir_enc], src/NeRF.py:313-314
+    const int with_dirs[11][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
+                                  {256, 256}, {256, 256}, {kd, 128}, {128, 3}, {kd, 1}};
+    // get_network_only_xyz (src/NeRF.py:248-288): ..., 8: 256 -> 256, 9: 256 -> 128, 10: 128 -> 3, 11: 256 -> 1
+    const int xyz_only[12][2] = {{xd, 256}, {256, 256}, {256, 256}, {256, 256}, {xd + 256, 256}, {256, 256},
+                                 {256, 256}, {256, 256}, {256, 256}, {256, 128}, {128, 3}, {256, 1}};
+    const int n = n_angles == 0 ? 12 : 11;
+    for (int l = 0; l < n; ++l) {
+        dims[l][0] = n_angles == 0 ? xyz_only[l][0] : with_dirs[l][0];
+        dims[l][1] = n_angles == 0 ? xyz_only[l][1] : with_dirs[l][1];
+    }
+    return n;
+}
+
+size_t blob_floats(int lx, int ld, int n_angles) {
+    int dims[12][2];
+    const int n = layer_dims(lx, ld, n_angles, dims);
+    size_t s = 0;
+    for (int l = 0; l < n; ++l) s += (size_t)dims[l][0] * dims[l][1] + dims[l][1];
+    return s;
+}
+
+void blob_expand_index(int lx, int ld, int n_angles, int32_t* idx, int layout_lx) {
+    int wide[12][2], dims[12][2];
+    const int n = layer_dims(layout_lx, kLd, n_angles, wide);
+    layer_dims(lx, ld, n_angles, dims);
+    const int xd_layout = 3 + 6 * layout_lx;
+    // xyz encoding row of the (layout_lx) layout -> row of the (lx) layout: per component [x, sin0, cos0, sin1, cos1, ...]
+    auto xyz_row = [&](int r) {
+        const int c = r / (1 + 2 * layout_lx), j = r % (1 + 2 * layout_lx);
+        if (j == 0) return c * (1 + 2 * lx);
+        const int k = (j - 1) / 2, h = (j - 1) % 2;
+        return k < lx ? c * (1 + 2 * lx) + 1 + 2 * k + h : -1;
+    };
+    // direction encoding row: per component [sin0, cos0, sin1, cos1, ...] (src/UtilsNeuralRadianceField.py:52-65)
+    auto dir_row = [&](int r) {
+        const int c = r / (2 * kLd), j = r % (2 * kLd), k = j / 2, h = j % 2;
+        return k < ld ? c * 2 * ld + 2 * k + h : -1;
+    };
+    size_t src = 0, dst = 0;
+    for (int l = 0; l < n; ++l) {
+        for (int r = 0; r < wide[l][0]; ++r) {
+            int rs = r;
+            if (l == 0) rs = xyz_row(r);
+            else if (l == 4) rs = r < xd_layout ? xyz_row(r) : 3 + 6 * lx + (r - xd_layout);
+            else if (n_angles != 0 && (l == 8 || l == 10)) rs = r < kHidden ? r : (dir_row(r - kHidden) < 0 ? -1 : kHidden + dir_row(r - kHidden));
+            for (int f = 0; f < wide[l][1]; ++f)
+                idx[dst++] = rs < 0 ? 0 : (int32_t)(src + (size_t)rs * dims[l][1] + f + 1);
+        }
+        src += (size_t)dims[l][0] * dims[l][1];
+        for (int f = 0; f < wide[l][1]; ++f) idx[dst++] = (int32_t)(src + f + 1);
+        src += dims[l][1];
+    }
+}
+
+void aim_gather(int lx, int ld, int n_angles, int32_t* idx, size_t n, bool f16) {
+    const int L = pe_layout_lx(lx);
+    if (lx == L && ld == kLd) return;
+    std::vector<int32_t> map(blob_floats(L, kLd, n_angles));
+    blob_expand_index(lx, ld, n_angles, map.data(), L);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t t = idx[i];
+        if (!t) continue;
+        const int32_t m = map[(f16 ? t >> 1 : t) - 1];
+        idx[i] = m == 0 ? 0 : f16 ? 2 * m + (t & 1) : m;
+    }
+}
+
+void build_stream_tables(int lx, int ld, int n_angles, StreamTables& t) {
+    StreamDesc d[2][kStreamKinds];
+    for (int w = 0; w < 2; ++w) render_streams(lx, n_angles, w, d[w]);
+    for (auto& c : t.cst) c.clear();
+    for (int k = 0; k < kStreamKinds; ++k) {
+        const size_t bytes = std::max(d[0][k].bytes, d[1][k].bytes);
+        const bool f16 = d[0][k].elem != kElemF32;
+        t.stream[k].clear();
+        if (!bytes || d[0][k].table != k) continue;
+        t.stream[k].assign(bytes / (f16 ? 2 : 4), 0);
+        std::vector<int32_t> ci(kConstFloats, 0);
+        if (build_stream_gather(lx, n_angles, (StreamKind)k, t.stream[k].data(), ci.data())) {
+            aim_gather(lx, ld, n_angles, ci.data(), ci.size(), false);
+            t.cst[d[0][k].cst] = ci;
+        }
+        aim_gather(lx, ld, n_angles, t.stream[k].data(), t.stream[k].size(), f16);
+    }
+}
+
+}  // namespace nerf

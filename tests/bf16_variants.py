@@ -3,7 +3,7 @@ tests/test_bf16x3_host.py (CPU) and tests/test_gpu_bf16x3.py (GPU): the geometri
 and the emulation of the kernels' arithmetic (csrc/mlp_f16x3.hip built with NERF_BF16: mlp_bf16x3.hip, mlp_bf16x3_wide.hip).
 
 The emulation calls the oracle's functions and substitutes the 256-wide contractions; it rounds where the kernels round:
-  weights      hi = bf16(w) round-to-nearest-even, lo = bf16(w - hi)                 (host packer / device re-pack)
+  weights      hi = bf16(w) round-to-nearest-even, lo = bf16(w - hi)                 (the device re-pack)
   activations  hi = the top 16 bits of the fp32 value (truncation, no conversion), lo = bf16(x - hi)   (split_e / pack_lo)
   product      w_hi x_lo + w_lo x_hi + w_hi x_hi, accumulated in fp32 on top of the fp32 bias (C-in)
   heads        the 128 -> 3 rgb head in fp32 on the unsplit last hidden layer; sigma = a raw accumulator of an MFMA tile

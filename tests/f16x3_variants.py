@@ -5,10 +5,10 @@ build mlp_f16x3_wide.hip), seeded defects of that arithmetic, and the downward t
 
 The emulation calls the oracle's functions and substitutes the 256-wide contractions; it rounds where the kernels round
 (lines of csrc/mlp_f16x3.hip unless another file is named):
-  weights      hi = fp16(w) round-to-nearest-even, lo = fp16(w - hi) with w - hi in fp32.  Host packer: :979-981
-               (f32_to_e16 = f32_to_f16, :816-834: RNE with subnormal halves below 2^-14, zero below 2^-25, inf from
-               65520); device re-pack: :1045-1047 ((_Float16)w, (_Float16)(w - (float)hi): v_cvt_f16_f32, the same RNE).
-               f32_to_f16_host below restates the packer bit for bit; the host test holds it to numpy's conversion.
+  weights      hi = fp16(w) round-to-nearest-even, lo = fp16(w - hi) with w - hi in fp32: the device re-pack, repack_kernel
+               in csrc/aux_kernels.hip ((E)w, (E)(w - (float)hi) with E = _Float16: v_cvt_f16_f32, IEEE RNE with subnormal
+               halves below 2^-14, zero below 2^-25, inf from 65520).  The host test holds fp16_rne to numpy's conversion,
+               which is the same IEEE rounding.
   activations  split_trunc (mlp_f16_frag.h:42-45): hi_f = the fp32 value with its 13 low mantissa bits cleared (11
   and both     significant bits), lo_f = y - hi_f in fp32 (exact).  Both then go through pack_h2 (mlp_f16_frag.h:27-30,
   encodings    v_cvt_pk_f16_f32, RNE): hi is exact while 2^-14 <= |y| < 65536, rounds to an fp16 subnormal (step 2^-24)
@@ -37,8 +37,9 @@ kernel order inside each) and "f64" (float64 accumulation, rounded to fp32 once 
 how far they are apart.
 
 A k-step is 16 input SLOTS of the kernel's fragment layout, not 16 consecutive rows of the Keras kernel: ksteps() maps
-each to the rows of the oracle's (in, out) kernel it holds (h_pe_row, h_hid_row, h_dir_row, :866-882; a network of fewer
-octaves is spread into the (5 or 10, 4)-octave layout with zero rows, csrc/nerf_api.hip blob_expand_index)."""
+each to the rows of the oracle's (in, out) kernel it holds (h_pe_row, h_hid_row, h_dir_row of the gather-table builder in
+csrc/mlp_f16x3.hip; a network of fewer octaves sits in the (5 or 10, 4)-octave layout with zero rows, csrc/weight_tables.hip
+blob_expand_index)."""
 import collections
 import contextlib
 import functools
@@ -102,27 +103,6 @@ def flush_subnormal(a) -> np.ndarray:
     """fp16 values (held as fp32) with the fp16 subnormals set to zero."""
     a = np.asarray(a, F32)
     return np.where(np.abs(a) < F32(2.0 ** -14), F32(0), a).astype(F32)
-
-
-def f32_to_f16_host(f) -> np.ndarray:
-    """The host packer's f32_to_f16 (csrc/mlp_f16x3.hip:816-834) restated on uint32 arrays; returns the fp16 bits."""
-    x = np.ascontiguousarray(f, F32).view(np.uint32).astype(np.int64)
-    sign = (x >> 16) & 0x8000
-    x = x & 0x7FFFFFFF
-    e = (x >> 23) - 127
-    sub = e < -14
-    shift = np.where(sub, 13 + (-14 - e), 13)
-    shift = np.clip(shift, 13, 40)
-    m = np.where(sub, (x & 0x7FFFFF) | 0x800000, x & 0x7FFFFF)
-    base = np.where(sub, 0, (e + 15) << 10)
-    q = m >> shift
-    rem, halfway = m & ((np.int64(1) << shift) - 1), np.int64(1) << (shift - 1)
-    q = q + ((rem > halfway) | ((rem == halfway) & ((q & 1) == 1)))
-    out = sign | (base + q)
-    out = np.where(x < 0x33000001, sign, out)
-    out = np.where(x >= 0x477FF000, sign | 0x7C00, out)
-    out = np.where(x >= 0x7F800000, sign | 0x7C00 | np.where(x > 0x7F800000, 0x200, 0), out)
-    return out.astype(np.uint16)
 
 
 _split_w_cache = {}

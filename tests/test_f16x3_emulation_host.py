@@ -3,7 +3,7 @@ device needed.  tests/f16x3_variants.py holds the emulation, the seeded defects 
 tests/test_gpu_f16x3_emulation.py holds the kernels to it.
 
 What is established here, from the references alone:
-  * the roundings of the emulation are the kernels' (fp16 RNE with subnormals, the host packer's conversion), and with the
+  * the roundings of the emulation are the kernels' (fp16 RNE with subnormals, the device re-pack's conversion), and with the
     roundings off the emulation is the fp32 network, through the k-step map of the kernels' fragment layout as well;
   * the bar of a kernel against its emulation, RAW_BAR_FACTOR (4) x the emulation's error against the fp32 oracle, per
     geometry and network; that error is at most 5e-6, ten times inside the 5e-5 the suite held f16x3 to so far;
@@ -30,9 +30,9 @@ def _say(capsys, text):
 
 # ---- 1. roundings ----
 def test_fp16_roundings_agree_on_subnormal_and_halfway_cases():
-    """fp16_rne (the emulation), f32_to_f16_host (the host packer, restated) and numpy's conversion (IEEE RNE, what
-    v_cvt_f16_f32 of the device re-pack computes) give the same bits on every fp16 value, every midpoint between two
-    neighbours, the fp32 neighbours of both, and random values over 2^-30 .. 2^17."""
+    """fp16_rne (the emulation) and numpy's conversion (IEEE RNE, what v_cvt_f16_f32 of the device re-pack computes) give
+    the same bits on every fp16 value, every midpoint between two neighbours, the fp32 neighbours of both, and random
+    values over 2^-30 .. 2^17."""
     halfs = np.arange(0x0000, 0x7C00, dtype=np.uint16).view(np.float16).astype(np.float64)     # every finite half >= 0
     mid = (halfs[:-1] + halfs[1:]) / 2                                                        # exact in fp32
     base = np.concatenate([halfs, mid, [65520.0, 65536.0, 2.0 ** -25, 2.0 ** -26, 1e9]]).astype(np.float32)
@@ -43,14 +43,12 @@ def test_fp16_roundings_agree_on_subnormal_and_halfway_cases():
     with np.errstate(over="ignore"):
         want = x.astype(np.float16)
     np.testing.assert_array_equal(X.fp16_rne(x).view(np.uint32), want.astype(np.float32).view(np.uint32))
-    np.testing.assert_array_equal(X.f32_to_f16_host(x), want.view(np.uint16))
     assert np.isnan(X.fp16_rne(np.array([np.nan], np.float32))).all()
-    # the lo half of a weight: w - hi is exact in fp32, and the packer's conversion of it is the emulation's
+    # the lo half of a weight: w - hi is exact in fp32, and the re-pack's conversion of it is the emulation's
     w = (rng.standard_normal(100000) * 2.0 ** rng.integers(-22, 3, 100000)).astype(np.float32)
     hi, lo = X.split_w(w)
-    hi_bits = X.f32_to_f16_host(w)
-    np.testing.assert_array_equal(hi_bits.view(np.float16).astype(np.float32), hi)
-    np.testing.assert_array_equal(X.f32_to_f16_host(w - hi).view(np.float16).astype(np.float32), lo)
+    np.testing.assert_array_equal(w.astype(np.float16).astype(np.float32), hi)
+    np.testing.assert_array_equal((w - hi).astype(np.float16).astype(np.float32), lo)
     assert np.count_nonzero((np.abs(lo) < 2.0 ** -14) & (lo != 0)) > 1000          # subnormal lo halves were among them
     big = np.abs(w) >= 2.0 ** -3
     assert np.all(np.abs((hi + lo) - w)[big] <= np.abs(w[big]) * 2.0 ** -21)

@@ -271,6 +271,53 @@ def test_every_resident_stream_follows_reloads_and_train_steps(oracle, lx, na):
         ctx.close()
 
 
+@pytest.mark.parametrize("lx,ld,na", [(5, 4, 2), (3, 2, 1), (8, 4, 2), (5, 4, 0)])
+def test_reloading_a_blob_gives_its_first_render_again(oracle, lx, ld, na):
+    """nerf_load_weights re-packs every resident stream from the blob on the device, onto the streams the first load
+    allocated and in stream order behind the renders already enqueued.  Load A, render, load B, load A again: in every
+    precision the config has a kernel for (fp32 only at Lx <= 5) the last render has the bits of the first and of a fresh
+    context created in that precision, and B's render in between had others.  64 rays x (12 coarse, 12 + 20 fine)
+    samples; one config per class csrc/nerf_kernels.h::render_streams tells apart, one of them with fewer octaves than
+    the layout its tables are written for."""
+    n, sc, sf = 64, 12, 20
+    o, d, rng = B.rays(n, seed=23)
+    u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
+    precisions = (["fp32"] if lx <= 5 else []) + ["f16x3", "f16", "bf16x3"]
+    blob_a, blob_b = B.blobs(lx, ld, na, seed=13), B.blobs(lx, ld, na, seed=33)
+
+    def load(ctx, pair):
+        for which, blob in enumerate(pair):
+            ctx.load_weights(which, blob)
+
+    def render_all(ctx):
+        out = {}
+        for p in precisions:
+            ctx.set_precision(p)
+            out[p] = ctx.render(o, d, sc, sf, u_c, u_f)
+        return out
+
+    ctx = _context(blob_a, lx, ld, na, precision=precisions[0])
+    try:
+        first = render_all(ctx)
+        load(ctx, blob_b)
+        other = render_all(ctx)
+        load(ctx, blob_a)
+        last = render_all(ctx)
+        for p in precisions:
+            fresh = _context(blob_a, lx, ld, na, precision=p)
+            try:
+                want = fresh.render(o, d, sc, sf, u_c, u_f)
+            finally:
+                fresh.close()
+            assert np.count_nonzero(other[p][0] != first[p][0]) > 0, p
+            for i, (a, b, c) in enumerate(zip(last[p], first[p], want)):
+                np.testing.assert_array_equal(a, b, err_msg=f"{p}, output {i}: A again vs A first")
+                np.testing.assert_array_equal(a, c, err_msg=f"{p}, output {i}: A again vs a fresh context")
+        assert ctx.read_nonfinite() == 0
+    finally:
+        ctx.close()
+
+
 # ---- 6. precision="auto" on a wide network ----
 def test_auto_falls_back_to_bf16x3_on_a_wide_network(oracle, golden_ckpt):
     """Lx 10 has no exact-fp32 kernel: under precision="auto" a weight set that leaves the fp16 range is re-rendered in

@@ -264,9 +264,10 @@ def test_train_steps_reduce_loss_and_render_sees_new_weights(oracle, golden_ckpt
 @pytest.mark.parametrize("n_angles", [2, 1, 0])
 def test_render_between_steps_uses_device_repacked_streams(oracle, golden_ckpt, n_angles):
     """A render between optimizer steps (DietNeRF's consistency render, the epoch plots) re-packs the render path's three
-    operand streams from the trained blob ON THE DEVICE (gather tables built from the host packers; no host round trip).  In
+    operand streams from the trained blob ON THE DEVICE (the context's gather tables; no host round trip).  In
     every arithmetic mode and for every network variant the result must be bit-equal to a fresh context that loads
-    nerf_get_weights() through the host packers; more steps dirty the streams again; nerf_train_end leaves the host copy
+    nerf_get_weights() (nerf_load_weights: the same tables and re-pack kernel, from the loaded blob; the tables themselves are
+    pinned by tests/golden/stream_table_hashes.txt); more steps dirty the streams again; nerf_train_end leaves the host copy
     current (a second trainer starts from the trained weights) and so does a nerf_train_begin that restarts a running
     trainer."""
     import nerf_and_dietnerf_amd as N
