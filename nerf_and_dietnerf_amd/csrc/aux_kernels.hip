@@ -7,8 +7,8 @@
 // and two the reference does not have ("Ray and sampling space"):
 //   rays_to_ndc   world rays -> NDC rays of a forward-facing scene
 //   z_values, disparity-linear mode
-//   scene box     ray_box_interval: the part of [near, far] a ray spends inside an axis-aligned box; the box variants of
-//                 the two depth kernels draw on it, ray_box_bounds returns it
+//   scene box     ray_box_interval: the part of [near, far] a ray spends inside an axis-aligned box; the depth kernel's box
+//                 source draws on it, ray_box_bounds returns it
 //   repack        weight blob -> an operand stream of the MLP kernels, through a gather table (weight_tables.hip)
 //
 // All HBM-bound fp32/int32 work.  Evaluation order is the canonical one of oracle/nerf_oracle.py:
@@ -16,7 +16,7 @@
 // into FMAs (explicit __fmul_rn/__fadd_rn), so index selection in the sampler is bit-exact against
 // the oracle and the other outputs differ only through expf.
 #include "nerf_kernels.h"
-#include "nerf_device.h"
+#include "sampling_device.h"
 
 #include <algorithm>
 
@@ -109,45 +109,6 @@ void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float
 }
 
 // ------------------------------------------------------------------------------------------------
-// z_values: z[r,s] = linspace(near,far,S)[s] + (u * (far-near)) / S
-// ------------------------------------------------------------------------------------------------
-__global__ void z_values_kernel(float start, float stop, float delta, float span, long long N, int S,
-                                const float* __restrict__ u, uint64_t seed, long long ray_base,
-                                float* __restrict__ z) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= N * S) return;
-    const long long r = m / S;
-    const int s = (int)(m - r * S);
-    // tf.linspace: first = start, last = stop exactly, interior = start + delta*i
-    float lin = __fadd_rn(start, __fmul_rn(delta, (float)s));
-    if (s == 0) lin = start;
-    if (s == S - 1 && S > 1) lin = stop;
-    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
-    z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, span), (float)S));
-}
-
-// Disparity-linear mode: the strata are uniform in 1/z.  t = (s + u) / S,  z = 1 / (inv_near + (inv_far - inv_near) t),
-// u the same draw as above.  inv_near = 1/near and dinv = 1/far - 1/near come from the host (double, rounded once).  s + u
-// can round up to s + 1 (u = 1 - 2^-24): it is held at the largest float below, so t stays inside its stratum and t < 1;
-// the result is held in [near, far) (far_below = the largest float below far), which the roundings of the last stratum
-// could otherwise touch.
-__global__ void z_values_lindisp_kernel(float near_b, float far_below, float inv_near, float dinv, long long N, int S,
-                                        const float* __restrict__ u, uint64_t seed, long long ray_base,
-                                        float* __restrict__ z) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= N * S) return;
-    const long long r = m / S;
-    const int s = (int)(m - r * S);
-    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
-    const float top = (float)(s + 1);
-    float v = __fadd_rn((float)s, uu);
-    if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
-    const float t = __fdiv_rn(v, (float)S);
-    const float zz = __fdiv_rn(1.0f, __fadd_rn(inv_near, __fmul_rn(dinv, t)));
-    z[m] = fminf(fmaxf(zz, near_b), far_below);
-}
-
-// ------------------------------------------------------------------------------------------------
 // Scene box: the interval of a ray (o, d) inside an axis-aligned box lo < hi, clipped to
 // [near, far].  Depths are the parameter t of o + t d; d is not normalised.  float32, every operation rounded on its own:
 //   1. per axis with d_a != 0: t0 = (lo_a - o_a) / d_a, t1 = (hi_a - o_a) / d_a, axis interval [min, max]
@@ -159,7 +120,7 @@ __global__ void z_values_lindisp_kernel(float near_b, float far_below, float inv
 // are not guarded, as in rays_to_ndc).  -> narrowed; a, b are meant to be used only then.
 // A narrowed ray draws its depths on [a, b] with constants of its own; any other ray -- a miss, or a box that contains
 // its whole [near, far] -- keeps the host's constants and so the depths of a context without a box, bit for bit.
-// This one function decides for the depth kernels and for nerf_ray_box_bounds.
+// This one function decides for the depth kernel and for nerf_ray_box_bounds.
 // ------------------------------------------------------------------------------------------------
 struct BoxArgs {
     float lo[3], hi[3];
@@ -205,51 +166,6 @@ __global__ void ray_box_bounds_kernel(const BoxArgs bx, const float* __restrict_
     if (narrowed) narrowed[r] = nar ? 1 : 0;
 }
 
-// The depth kernels with a box: one thread per sample, like the two above, whose formulas these repeat.  c0..c3 are the
-// constants launch_z_values gives the kernel without a box -- linear: start, stop, delta, span; lindisp: near, far_below,
-// inv_near, dinv -- and a narrowed ray replaces them with its own, computed in float32 from (a, b):
-//   linear:  start = a, stop = b, span = b - a, delta = span / (S - 1) (0 for S == 1); the last stratum may pass b by span / S
-//   lindisp: near = a, far_below = the float below b, inv_near = 1 / a, dinv = 1 / b - inv_near   (a >= near > 0)
-// Every thread of a ray reads the ray's 32 bytes and takes the decision again: S threads, one cache line, no bounds buffer
-// and no launch in front of this one.
-template <bool LINDISP>
-__global__ void z_values_box_kernel(const BoxArgs bx, float c0, float c1, float c2, float c3,
-                                    const float* __restrict__ orig, const float* __restrict__ dirs, long long N, int S,
-                                    const float* __restrict__ u, uint64_t seed, long long ray_base,
-                                    float* __restrict__ z) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= N * S) return;
-    const long long r = m / S;
-    const int s = (int)(m - r * S);
-    float a, b;
-    if (ray_box_interval(bx, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b)) {
-        c0 = a;
-        if constexpr (LINDISP) {
-            c1 = __int_as_float(__float_as_int(b) - 1);           // b > a > 0
-            c2 = __fdiv_rn(1.0f, a);
-            c3 = __fsub_rn(__fdiv_rn(1.0f, b), c2);
-        } else {
-            c1 = b;
-            c3 = __fsub_rn(b, a);
-            c2 = S > 1 ? __fdiv_rn(c3, (float)(S - 1)) : 0.f;
-        }
-    }
-    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
-    if constexpr (LINDISP) {
-        const float top = (float)(s + 1);
-        float v = __fadd_rn((float)s, uu);
-        if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
-        const float t = __fdiv_rn(v, (float)S);
-        const float zz = __fdiv_rn(1.0f, __fadd_rn(c2, __fmul_rn(c3, t)));
-        z[m] = fminf(fmaxf(zz, c0), c1);
-    } else {
-        float lin = __fadd_rn(c0, __fmul_rn(c2, (float)s));
-        if (s == 0) lin = c0;
-        if (s == S - 1 && S > 1) lin = c1;
-        z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, c3), (float)S));
-    }
-}
-
 static BoxArgs box_args(const SceneBox& box, float near_b, float far_b) {
     BoxArgs bx;
     for (int i = 0; i < 3; ++i) { bx.lo[i] = box.lo[i]; bx.hi[i] = box.hi[i]; }
@@ -263,41 +179,6 @@ void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const
     const int bs = 256;
     hipLaunchKernelGGL(ray_box_bounds_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream,
                        box_args(box, near_b, far_b), orig, dirs, N, bounds, narrowed);
-}
-
-void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
-                     long long ray_base, float* z, hipStream_t stream, const float* orig, const float* dirs,
-                     const SceneBox* box) {
-    if (N <= 0) return;
-    const long long total = N * S;
-    const int bs = 256;
-    if (box && orig && dirs) {   // the same host constants as below, for the rays the box does not narrow
-        const BoxArgs bx = box_args(*box, near_b, far_b);
-        const dim3 grid((unsigned)((total + bs - 1) / bs));
-        if (lindisp) {
-            const float inv_near = (float)(1.0 / (double)near_b);
-            const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
-            hipLaunchKernelGGL(z_values_box_kernel<true>, grid, dim3(bs), 0, stream, bx, near_b, nextafterf(far_b, near_b),
-                               inv_near, dinv, orig, dirs, N, S, u, seed, ray_base, z);
-            return;
-        }
-        const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
-        const float span = (float)((double)far_b - (double)near_b);
-        hipLaunchKernelGGL(z_values_box_kernel<false>, grid, dim3(bs), 0, stream, bx, near_b, far_b, delta, span, orig, dirs,
-                           N, S, u, seed, ray_base, z);
-        return;
-    }
-    if (lindisp) {   // near_b > 0: the callers refuse anything else
-        const float inv_near = (float)(1.0 / (double)near_b);
-        const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
-        hipLaunchKernelGGL(z_values_lindisp_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream, near_b,
-                           nextafterf(far_b, near_b), inv_near, dinv, N, S, u, seed, ray_base, z);
-        return;
-    }
-    const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
-    const float span = (float)((double)far_b - (double)near_b);
-    hipLaunchKernelGGL(z_values_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, stream, near_b,
-                       far_b, delta, span, N, S, u, seed, ray_base, z);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -380,7 +261,7 @@ __device__ __forceinline__ int ray_grid_interval(const GridArgs& g, const float4
 }
 
 // One thread per ray: bounds (N,2), state (N).  The walk takes up to 3R + 3 steps, so unlike the box decision it is made
-// once per ray, here, and z_values_bounds_kernel reads the result.
+// once per ray, here, and z_values_kernel (kDepthBounds) reads the result.
 __global__ void ray_grid_bounds_kernel(const GridArgs g, const float* __restrict__ orig, const float* __restrict__ dirs,
                                        long long N, float* __restrict__ bounds, int* __restrict__ state) {
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -389,47 +270,6 @@ __global__ void ray_grid_bounds_kernel(const GridArgs g, const float* __restrict
     const int st = ray_grid_interval(g, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b);
     reinterpret_cast<float2*>(bounds)[r] = make_float2(a, b);
     if (state) state[r] = st;
-}
-
-// The depth kernels on given bounds: one thread per sample.  c0..c3 are the host constants of z_values_box_kernel; a ray of
-// state 1 or 2 replaces them with its own, by that kernel's formulas, so a state-1 ray has the bits the box kernel gives it
-// and a state-0 ray those of a context without a box.
-template <bool LINDISP>
-__global__ void z_values_bounds_kernel(float c0, float c1, float c2, float c3, const float* __restrict__ bounds,
-                                       const int* __restrict__ state, long long N, int S, const float* __restrict__ u,
-                                       uint64_t seed, long long ray_base, float* __restrict__ z) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= N * S) return;
-    const long long r = m / S;
-    const int s = (int)(m - r * S);
-    if (state[r] != 0) {
-        const float2 ab = reinterpret_cast<const float2*>(bounds)[r];
-        const float a = ab.x, b = ab.y;
-        c0 = a;
-        if constexpr (LINDISP) {
-            c1 = __int_as_float(__float_as_int(b) - 1);           // b > a > 0
-            c2 = __fdiv_rn(1.0f, a);
-            c3 = __fsub_rn(__fdiv_rn(1.0f, b), c2);
-        } else {
-            c1 = b;
-            c3 = __fsub_rn(b, a);
-            c2 = S > 1 ? __fdiv_rn(c3, (float)(S - 1)) : 0.f;
-        }
-    }
-    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
-    if constexpr (LINDISP) {
-        const float top = (float)(s + 1);
-        float v = __fadd_rn((float)s, uu);
-        if (v >= top) v = __int_as_float(__float_as_int(top) - 1);
-        const float t = __fdiv_rn(v, (float)S);
-        const float zz = __fdiv_rn(1.0f, __fadd_rn(c2, __fmul_rn(c3, t)));
-        z[m] = fminf(fmaxf(zz, c0), c1);
-    } else {
-        float lin = __fadd_rn(c0, __fmul_rn(c2, (float)s));
-        if (s == 0) lin = c0;
-        if (s == S - 1 && S > 1) lin = c1;
-        z[m] = __fadd_rn(lin, __fdiv_rn(__fmul_rn(uu, c3), (float)S));
-    }
 }
 
 void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, const uint32_t* bits, int R, const float* orig,
@@ -443,22 +283,67 @@ void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, cons
                        bounds, state);
 }
 
-void launch_z_values_bounds(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
-                            long long ray_base, float* z, const float* bounds, const int* state, hipStream_t stream) {
-    if (N <= 0) return;
-    const int bs = 256;
-    const dim3 grid((unsigned)((N * S + bs - 1) / bs));
-    if (lindisp) {   // the host constants of launch_z_values
-        const float inv_near = (float)(1.0 / (double)near_b);
-        const float dinv = (float)(1.0 / (double)far_b - 1.0 / (double)near_b);
-        hipLaunchKernelGGL(z_values_bounds_kernel<true>, grid, dim3(bs), 0, stream, near_b, nextafterf(far_b, near_b), inv_near,
-                           dinv, bounds, state, N, S, u, seed, ray_base, z);
-        return;
+// ------------------------------------------------------------------------------------------------
+// z_values: one thread per sample, z[r, s] = stratified_depth (sampling_device.h) on the ray's depth range.  The range is the
+// context's [near, far] with the host's constants, unless the ray has one of its own (depth_consts_of_interval on its (a, b)):
+//   kDepthHost    no ray has
+//   kDepthBox     a ray the scene box narrows (ray_box_interval).  Every thread of a ray reads the ray's 32 bytes and takes
+//                 the decision again: S threads, one cache line, no bounds buffer and no launch in front of this one
+//   kDepthBounds  a ray of state 1 or 2 in the bounds / state that ray_grid_bounds_kernel left (its walk is made once per ray)
+// One kernel, so a ray that keeps [near, far] has the depths of a context without a box under either source, and a state-1
+// ray those the box source gives it, bit for bit.
+// ------------------------------------------------------------------------------------------------
+enum DepthSrc { kDepthHost, kDepthBox, kDepthBounds };
+struct DepthRays {
+    BoxArgs bx; const float* orig; const float* dirs;     // kDepthBox
+    const float* bounds; const int* state;                // kDepthBounds
+};
+
+template <bool LINDISP, int SRC>
+__global__ void z_values_kernel(const DepthRays rays, DepthConsts k, long long N, int S, const float* __restrict__ u,
+                                uint64_t seed, long long ray_base, float* __restrict__ z) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= N * S) return;
+    const long long r = m / S;
+    const int s = (int)(m - r * S);
+    if constexpr (SRC == kDepthBox) {
+        float a, b;
+        if (ray_box_interval(rays.bx, reinterpret_cast<const float4*>(rays.orig)[r],
+                             reinterpret_cast<const float4*>(rays.dirs)[r], &a, &b))
+            k = depth_consts_of_interval<LINDISP>(a, b, S);
+    } else if constexpr (SRC == kDepthBounds) {
+        if (rays.state[r] != 0) {
+            const float2 ab = reinterpret_cast<const float2*>(rays.bounds)[r];
+            k = depth_consts_of_interval<LINDISP>(ab.x, ab.y, S);
+        }
     }
-    const float delta = S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f;
-    const float span = (float)((double)far_b - (double)near_b);
-    hipLaunchKernelGGL(z_values_bounds_kernel<false>, grid, dim3(bs), 0, stream, near_b, far_b, delta, span, bounds, state, N,
-                       S, u, seed, ray_base, z);
+    const float uu = u ? u[m] : philox_uniform(seed, (uint64_t)(ray_base + r), s, 0u);
+    z[m] = stratified_depth<LINDISP>(k, s, S, uu);
+}
+
+// the constants of [near, far]: inverses and differences in double, rounded once
+static DepthConsts depth_consts_host(float near_b, float far_b, bool lindisp, int S) {
+    if (lindisp)   // near_b > 0: the callers refuse anything else
+        return {near_b, nextafterf(far_b, near_b), (float)(1.0 / (double)near_b),
+                (float)(1.0 / (double)far_b - 1.0 / (double)near_b)};
+    return {near_b, far_b, S > 1 ? (far_b - near_b) / (float)(S - 1) : 0.f, (float)((double)far_b - (double)near_b)};
+}
+
+void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
+                     long long ray_base, float* z, hipStream_t stream, const float* orig, const float* dirs,
+                     const SceneBox* box, const float* bounds, const int* state) {
+    if (N <= 0) return;
+    using Kernel = void (*)(const DepthRays, DepthConsts, long long, int, const float*, uint64_t, long long, float*);
+    static const Kernel kernels[3][2] = {{z_values_kernel<false, kDepthHost>, z_values_kernel<true, kDepthHost>},
+                                         {z_values_kernel<false, kDepthBox>, z_values_kernel<true, kDepthBox>},
+                                         {z_values_kernel<false, kDepthBounds>, z_values_kernel<true, kDepthBounds>}};
+    const DepthSrc src = bounds && state ? kDepthBounds : box && orig && dirs ? kDepthBox : kDepthHost;
+    DepthRays rays = {};
+    if (src == kDepthBox) { rays.bx = box_args(*box, near_b, far_b); rays.orig = orig; rays.dirs = dirs; }
+    if (src == kDepthBounds) { rays.bounds = bounds; rays.state = state; }
+    const int bs = 256;
+    hipLaunchKernelGGL(kernels[src][lindisp ? 1 : 0], dim3((unsigned)((N * S + bs - 1) / bs)), dim3(bs), 0, stream, rays,
+                       depth_consts_host(near_b, far_b, lindisp, S), N, S, u, seed, ray_base, z);
 }
 
 // ---- baking: cell sample points -> the network's sigma (the MLP kernels, nerf_api.hip) -> bits -> dilation ----
@@ -547,11 +432,11 @@ void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t s
 }
 
 // ------------------------------------------------------------------------------------------------
-// sample_pdf: one ray per wavefront.  LDS per wave: cdf[S], mid[S-1], znew[Sf], zall[S+Sf].
-//   1. lane-parallel load of w,z; sequential (lane 0) sum and cumsum -> cdf  (canonical order)
-//   2. each lane: fine draws k = lane, lane+64, ...: binary search (searchsorted left), clip,
-//      1e-5 floor, lerp between bin midpoints
-//   3. rank sort of the Sf new depths, then a binary-search merge with the (already increasing) coarse
+// sample_pdf: one ray per wavefront.  LDS per wave: cdf[S], zc[S], znew[Sf], zall[S+Sf].  The arithmetic is
+// sampling_device.h's; the backward (train_kernels.hip: sample_pdf_bwd_kernel) recomputes it through the same functions:
+//   1. ray_cdf: w, z -> cdf in the canonical order
+//   2. each lane: fine draws k = lane, lane+64, ...: inverse_cdf_draw
+//   3. stable_rank sort of the Sf new depths, then a binary-search merge with the (already increasing) coarse
 //      depths for the fine pass
 // ------------------------------------------------------------------------------------------------
 constexpr int kPdfWaves = 4;   // rays per workgroup
@@ -574,98 +459,19 @@ __global__ __launch_bounds__(64 * kPdfWaves) void sample_pdf_kernel(
     float* za = zn + Sf4;
     const float* wr = weights + ray * S;
     const float* zr = zin + ray * S;
-    // Canonical left-to-right sum and cumsum of w / (sum + 1e-7).  The order is sequential by definition,
-    // but only the additions are: every lane keeps its samples in registers, the running value is formed
-    // redundantly in all lanes from v_readlane broadcasts (no LDS round trip, no single-lane loop) and
-    // the divisions run 64 wide.  S <= 256 takes this path; longer rays fall back to a one-lane loop.
-    constexpr int kMaxChunks = 4;
-    if (S <= 64 * kMaxChunks) {
-        float wreg[kMaxChunks], creg[kMaxChunks];
-#pragma unroll
-        for (int c = 0; c < kMaxChunks; ++c) {
-            const int s = lane + 64 * c;
-            wreg[c] = s < S ? wr[s] : 0.f;
-            if (s < S) zc[s] = zr[s];
-        }
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < kMaxChunks; ++c) {
-            const int n = min(64, S - 64 * c);
-            for (int i = 0; i < n; ++i) sum = __fadd_rn(sum, __shfl(wreg[c], i));
-        }
-        const float den = __fadd_rn(sum, 1e-7f);
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < kMaxChunks; ++c) {
-            const float pdf = __fdiv_rn(wreg[c], den);
-            const int n = min(64, S - 64 * c);
-            creg[c] = 0.f;
-            for (int i = 0; i < n; ++i) {
-                acc = __fadd_rn(acc, __shfl(pdf, i));
-                if (lane == i) creg[c] = acc;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < kMaxChunks; ++c) {
-            const int s = lane + 64 * c;
-            if (s < S) cdf[s] = creg[c];
-        }
-    } else {
-        for (int s = lane; s < S; s += 64) { cdf[s] = wr[s]; zc[s] = zr[s]; }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (lane == 0) {
-            float sum = 0.f;
-            for (int s = 0; s < S; ++s) sum = __fadd_rn(sum, cdf[s]);
-            const float den = __fadd_rn(sum, 1e-7f);
-            float acc = 0.f;
-            for (int s = 0; s < S; ++s) {
-                acc = __fadd_rn(acc, __fdiv_rn(cdf[s], den));
-                cdf[s] = acc;
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    ray_cdf(wr, zr, S, lane, cdf, zc, nullptr);
     const float kInf = __builtin_huge_valf();
     for (int k = lane; k < Sf4; k += 64) {
         if (k >= Sf) { zn[k] = kInf; continue; }   // padding never ranks below a real sample
         const float uu = u ? u[ray * Sf + k] : philox_uniform(seed, (uint64_t)(ray_base + ray), k, 1u);
-        // searchsorted(cdf, uu, side='left'): first i with cdf[i] >= uu, in [0, S]
-        int lo = 0, hi = S;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cdf[mid] < uu) lo = mid + 1; else hi = mid;
-        }
-        const int idx = lo;
-        const int b = max(0, idx - 1);
-        const int t = min(S - 1, idx);
-        const float c_lo = cdf[b], c_hi = cdf[t];
-        const int bz = min(max(b, 0), S - 2), tz = min(max(t, 0), S - 2);
-        const float z_lo = __fmul_rn(0.5f, __fadd_rn(zc[bz + 1], zc[bz]));
-        const float z_hi = __fmul_rn(0.5f, __fadd_rn(zc[tz + 1], zc[tz]));
-        float den = __fsub_rn(c_hi, c_lo);
-        den = den < 1e-5f ? 1e-5f : den;
-        const float tt = __fdiv_rn(__fsub_rn(uu, c_lo), den);
-        zn[k] = __fadd_rn(z_lo, __fmul_rn(tt, __fsub_rn(z_hi, z_lo)));
+        zn[k] = inverse_cdf_draw(cdf, zc, S, uu).z;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // rank sort (ties broken by index -> a permutation); every lane sweeps the array as float4 broadcasts
-    auto rank_of = [](const float* arr, int n4, float v, int k) -> int {
-        int rank = 0;
-        for (int i = 0; i < n4; i += 4) {
-            const float4 o = *reinterpret_cast<const float4*>(arr + i);
-            rank += (o.x < v || (o.x == v && i + 0 < k)) ? 1 : 0;
-            rank += (o.y < v || (o.y == v && i + 1 < k)) ? 1 : 0;
-            rank += (o.z < v || (o.z == v && i + 2 < k)) ? 1 : 0;
-            rank += (o.w < v || (o.w == v && i + 3 < k)) ? 1 : 0;
-        }
-        return rank;
-    };
+    // rank sort of the draws
     for (int k = lane; k < Sf; k += 64) {
         const float v = zn[k];
-        const int rank = rank_of(zn, Sf4, v, k);
+        const int rank = stable_rank(zn, Sf4, v, k);
         if (z_new) z_new[ray * Sf + rank] = v;
         za[rank] = v;                                   // za[0..Sf) = the new depths, sorted
     }
@@ -681,15 +487,11 @@ __global__ __launch_bounds__(64 * kPdfWaves) void sample_pdf_kernel(
             // elements of the OTHER run that precede it, by binary search instead of an O(n^2) sweep
             for (int k = lane; k < Sf; k += 64) {
                 const float v = za[k];
-                int lo = 0, hi = S;                      // # coarse depths < v
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (zc[mid] < v) lo = mid + 1; else hi = mid; }
-                z_merged[ray * T + k + lo] = v;
+                z_merged[ray * T + k + count_below(zc, S, v)] = v;
             }
             for (int j = lane; j < S; j += 64) {
                 const float v = zc[j];
-                int lo = 0, hi = Sf;                     // # new depths <= v
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (za[mid] <= v) lo = mid + 1; else hi = mid; }
-                z_merged[ray * T + j + lo] = v;
+                z_merged[ray * T + j + count_not_above(za, Sf, v)] = v;
             }
         } else {
             // general case: rank sort of the concatenation
@@ -698,7 +500,7 @@ __global__ __launch_bounds__(64 * kPdfWaves) void sample_pdf_kernel(
             __builtin_amdgcn_wave_barrier();
             for (int k = lane; k < T; k += 64) {
                 const float v = za[k];
-                z_merged[ray * T + rank_of(za, T4, v, k)] = v;
+                z_merged[ray * T + stable_rank(za, T4, v, k)] = v;
             }
         }
     }
@@ -746,12 +548,8 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
         const float4 o = SIGMA_ONLY ? make_float4(0.f, 0.f, 0.f, in ? raw[r * S + s] : 0.f)
                                     : in ? rw[s] : make_float4(0.f, 0.f, 0.f, 0.f);
         const float zc = in ? zr[s] : 0.f;
-        const float delta = s + 1 < S ? zr[s + 1] - zc : 1e9f;
-        const float sigma = fmaxf(o.w, 0.f);
-        const float a = in ? 1.0f - expf(-(sigma * delta)) : 0.f;
-        const float r0 = 1.0f / (1.0f + expf(-o.x));
-        const float r1 = 1.0f / (1.0f + expf(-o.y));
-        const float r2 = 1.0f / (1.0f + expf(-o.z));
+        const CompositeTerms ct = composite_terms(o, zr, s, S);
+        const float a = ct.alpha, r0 = ct.r0, r1 = ct.r1, r2 = ct.r2;
         // Exclusive transmittance in the canonical order T_l = fl(T_(l-1) * (1 - alpha_(l-1))): lane l reads its left
         // neighbour through a one-lane wavefront shift (DPP wave_shr:1; lane 0 keeps the carry) and multiplies; after k
         // rounds lanes 0..k are final and recomputing them changes nothing, so 63 rounds of one shift + one multiply

@@ -99,19 +99,19 @@ int sampling_ok(const nerf_ctx* c) {
 
 int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,
                   long long ray_base, float* z) {
-    const bool lindisp = c->sampling == NERF_SAMPLING_LINDISP;
+    const float* bounds = nullptr;
+    const int* state = nullptr;
     if (c->box_on && c->grid_R > 0 && o && d && N > 0) {
         // the walk through the grid is made once per ray, into the ctx's own scratch; the depth kernel reads the result
         if (int r = ensure(c, c->b_gbounds, (size_t)N * 8)) return r;
         if (int r = ensure(c, c->b_gstate, (size_t)N * 4)) return r;
         launch_ray_grid_bounds(c->box, c->cfg.near_boundary, c->cfg.far_boundary, (const uint32_t*)c->b_grid[c->grid_cur].p,
                                c->grid_R, o, d, N, (float*)c->b_gbounds.p, (int*)c->b_gstate.p, c->stream);
-        launch_z_values_bounds(c->cfg.near_boundary, c->cfg.far_boundary, lindisp, N, S, u, seed, ray_base, z,
-                               (const float*)c->b_gbounds.p, (const int*)c->b_gstate.p, c->stream);
-        return 0;
+        bounds = (const float*)c->b_gbounds.p;
+        state = (const int*)c->b_gstate.p;
     }
-    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, lindisp, N, S, u, seed, ray_base, z, c->stream, o, d,
-                    c->box_on ? &c->box : nullptr);
+    launch_z_values(c->cfg.near_boundary, c->cfg.far_boundary, c->sampling == NERF_SAMPLING_LINDISP, N, S, u, seed, ray_base,
+                    z, c->stream, o, d, c->box_on ? &c->box : nullptr, bounds, state);
     return 0;
 }
 

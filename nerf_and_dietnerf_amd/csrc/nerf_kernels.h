@@ -235,22 +235,21 @@ void launch_raygen(const float c2w_host[16], float fov, int H, int W,
 void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float fov, float near_plane, float* out_orig,
                         float* out_dirs, hipStream_t stream);
 // lindisp: strata uniform in 1/z (needs near_b > 0) instead of in z.  With rays (N,4) AND a box, every ray the box narrows
-// draws on its own interval (aux_kernels.hip: ray_box_interval); without either, the kernels and arguments of a context
-// that has no box.
+// draws on its own interval (aux_kernels.hip: ray_box_interval); with bounds AND state (launch_ray_grid_bounds' outputs,
+// below) a ray of state 0 draws with the host's constants, any other on its own (a, b); with neither, every ray on
+// [near_b, far_b].
 struct SceneBox { float lo[3], hi[3]; };
 void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
                      long long ray_base, float* z, hipStream_t stream, const float* orig = nullptr,
-                     const float* dirs = nullptr, const SceneBox* box = nullptr);
+                     const float* dirs = nullptr, const SceneBox* box = nullptr, const float* bounds = nullptr,
+                     const int* state = nullptr);
 // bounds (N,2): (a, b) of a narrowed ray, (near_b, far_b) of any other; narrowed (N) 0 / 1, nullable
 void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,
                            float* bounds, int* narrowed, hipStream_t stream);
 // Occupancy grid (aux_kernels.hip: ray_grid_interval): bits = R^3 / 32 device words over the box, cell (ix, iy, iz) = bit
-// ix + R (iy + R iz).  bounds (N,2) and state (N; 0 untouched / 1 box only / 2 grid; nullable) of every ray, walked once ...
+// ix + R (iy + R iz).  bounds (N,2) and state (N; 0 untouched / 1 box only / 2 grid; nullable) of every ray, walked once
 void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, const uint32_t* bits, int R, const float* orig,
                             const float* dirs, long long N, float* bounds, int* state, hipStream_t stream);
-// ... and launch_z_values on them: a ray of state 0 draws with the host's constants, any other on its own (a, b)
-void launch_z_values_bounds(float near_b, float far_b, bool lindisp, long long N, int S, const float* u, uint64_t seed,
-                            long long ray_base, float* z, const float* bounds, const int* state, hipStream_t stream);
 // baking: the sample points (n_cells * spc, 3) of cells [cell_begin, cell_begin + n_cells) and as many unit view directions
 // (nullable); raw (n_cells * spc, 4) -> their bits; one step of 26-neighbour growth.  cell_begin, n_cells: multiples of 64
 void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,

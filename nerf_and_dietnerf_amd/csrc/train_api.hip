@@ -705,7 +705,7 @@ int check_samples(const TrainState* t, long long N, int Sc, int Sf, bool* fine) 
     *fine = Sf > 0 && t->net[1].present;
     if (!*fine) return 0;
     if (Sc < 2) return fail("hierarchical sampling needs at least 2 coarse samples (got %d)", Sc);
-    if (Sf > 256) return fail("training supports at most 256 fine samples per ray (got %d)", Sf);
+    if (Sf > kTrainMaxFine) return fail("training supports at most %d fine samples per ray (got %d)", kTrainMaxFine, Sf);
     // same budget as the render path's sampler (nerf_api.hip): the backward sampler was validated up to 64 KiB of LDS
     if (sample_pdf_lds_bytes(Sc, Sf) > 64 * 1024 || sample_pdf_bwd_lds_bytes(Sc, Sf) > 64 * 1024)
         return fail("Sc=%d Sf=%d exceeds the sampler's LDS budget (forward %zu B, backward %zu B, limit 65536 B)", Sc, Sf,

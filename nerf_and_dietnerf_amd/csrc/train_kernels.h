@@ -143,6 +143,10 @@ void launch_pe_bwd(const float* dA0, const float* dA0b /* added to dA0, or null 
                    hipStream_t s, bool frag = false);     // frag: dA0 / dA0b are fragment-major (the fused backward chain's dx buffers)
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
                          hipStream_t s);
+// The sampler backward keeps a lane's fine samples (k = lane, lane + 64, ...) in kTrainFineChunks registers, so a training
+// call takes at most kTrainMaxFine fine samples per ray: train_api.hip's check_samples refuses more.
+constexpr int kTrainFineChunks = 4;
+constexpr int kTrainMaxFine = 64 * kTrainFineChunks;
 void launch_sample_pdf_bwd(const float* weights, const float* z, long long N, int S, int Sf, const float* u,
                            uint64_t seed, long long ray_base, const float* d_zf, float* d_w, hipStream_t s);
 size_t sample_pdf_bwd_lds_bytes(int S, int Sf);

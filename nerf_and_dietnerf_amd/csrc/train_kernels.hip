@@ -15,7 +15,7 @@
 // Per-ray backward kernels: compositing (division-free reverse scan), positional encoding, inverse-CDF sampler
 // (the reference has no stop_gradient there: src/UtilsCV.py:512-537), MSE, Adam.
 #include "train_kernels.h"
-#include "nerf_device.h"
+#include "sampling_device.h"
 
 namespace nerf {
 
@@ -1481,12 +1481,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
         const int s = s0 + lane;
         const bool in = s < S, last = s + 1 >= S;
         const float4 o = in ? rw[s] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float delta = last ? 1e9f : zr[s + 1] - zr[s];
-        const float sigma = fmaxf(o.w, 0.f);
-        const float e = in ? expf(-sigma * delta) : 1.0f;       // 1 - alpha
-        const float a = 1.0f - e;
+        // the forward's own alpha, e = 1 - alpha, delta and sigmoids (sampling_device.h); with its T, w = a * T is its w
+        const CompositeTerms ct = composite_terms(o, zr, s, S);
+        const float delta = ct.delta, sigma = ct.sigma, e = ct.e, a = ct.alpha, c0 = ct.r0, c1 = ct.r1, c2 = ct.r2;
         const float T = in ? Tin[r * S + s] : 0.f;
-        const float c0 = 1.0f / (1.0f + expf(-o.x)), c1 = 1.0f / (1.0f + expf(-o.y)), c2 = 1.0f / (1.0f + expf(-o.z));
         const float w = a * T;
         float gw = g0 * c0 + g1 * c1 + g2 * c2;
         if (d_w_ext && in) gw += d_w_ext[r * S + s];
@@ -1620,7 +1618,7 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
 
 // ------------------------------------------------------------------------------------------------
 // Backward of z = sort(concat(z_new, z_coarse)) (src/NeRF.py:132) w.r.t. z_new: sample_pdf_kernel (aux_kernels.hip)
-// puts the k-th new depth (they are sorted) into slot k + #{coarse depths < it}; the gradient of that slot is its.
+// puts the k-th new depth (they are sorted) into slot k + count_below(coarse depths, it); the gradient of that slot is its.
 // ------------------------------------------------------------------------------------------------
 __global__ void unmerge_grad_kernel(const float* __restrict__ z_new, const float* __restrict__ z_c,
                                     const float* __restrict__ d_zm, long long N, int S, int Sf,
@@ -1629,11 +1627,7 @@ __global__ void unmerge_grad_kernel(const float* __restrict__ z_new, const float
     if (i >= N * Sf) return;
     const long long ray = i / Sf;
     const int k = (int)(i % Sf);
-    const float v = z_new[i];
-    const float* zc = z_c + ray * S;
-    int lo = 0, hi = S;                       // # coarse depths < v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zc[mid] < v) lo = mid + 1; else hi = mid; }
-    d_zf[i] = d_zm[ray * (S + Sf) + k + lo];
+    d_zf[i] = d_zm[ray * (S + Sf) + k + count_below(z_c + ray * S, S, z_new[i])];
 }
 
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
@@ -1662,8 +1656,8 @@ void launch_pe_bwd(const float* dA0, const float* dA0b, const float* o, const fl
 // ------------------------------------------------------------------------------------------------
 // inverse-CDF sampler backward (get_z_vals_from_prob_dist_func, src/UtilsCV.py:502-539): the reference takes
 // gradients through pdf/cdf/gather/lerp/sort (indices are constants), so the fine loss reaches the coarse
-// weights.  One ray per wavefront; the forward quantities are recomputed with the forward kernel's arithmetic
-// (same cdf bits -> same bins and the same sort permutation).
+// weights.  One ray per wavefront; the forward quantities are recomputed through the functions the forward kernel calls
+// (sampling_device.h: ray_cdf, inverse_cdf_draw, stable_rank -- same cdf bits -> same bins and the same sort permutation).
 // ------------------------------------------------------------------------------------------------
 constexpr int kBwdWaves = 4;
 
@@ -1689,67 +1683,28 @@ __global__ __launch_bounds__(64 * kBwdWaves) void sample_pdf_bwd_kernel(
     float* den = tt + Sf4;        // clamped denominators are stored negated
     int* ilo = reinterpret_cast<int*>(den + Sf4);
     int* ihi = ilo + Sf4;
-    float* scal = reinterpret_cast<float*>(ihi + Sf4);   // [0] = sum + eps, [1] = sum_i dpdf_i * w_i
-    const float* wr = weights + ray * S;
-    const float* zr = zin + ray * S;
-    for (int s = lane; s < S; s += 64) { wv[s] = wr[s]; zc[s] = zr[s]; }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        float sum = 0.f;
-        for (int s = 0; s < S; ++s) sum = __fadd_rn(sum, wv[s]);
-        const float D = __fadd_rn(sum, 1e-7f);
-        float acc = 0.f;
-        for (int s = 0; s < S; ++s) {
-            acc = __fadd_rn(acc, __fdiv_rn(wv[s], D));
-            cdf[s] = acc;
-        }
-        scal[0] = D;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    float* scal = reinterpret_cast<float*>(ihi + Sf4);   // [1], [2] = sum_i dpdf_i * w_i as a float pair ([0], [3] spare)
+    const float Df = ray_cdf(weights + ray * S, zin + ray * S, S, lane, cdf, zc, wv);   // sum + eps
     const float kInf = __builtin_huge_valf();
     for (int k = lane; k < Sf4; k += 64) {
         if (k >= Sf) { zn[k] = kInf; continue; }
         const float uu = u ? u[ray * Sf + k] : philox_uniform(seed, (uint64_t)(ray_base + ray), k, 1u);
-        int lo = 0, hi = S;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cdf[mid] < uu) lo = mid + 1; else hi = mid;
-        }
-        const int b = max(0, lo - 1);
-        const int t = min(S - 1, lo);
-        const float c_lo = cdf[b], c_hi = cdf[t];
-        const int bz = min(max(b, 0), S - 2), tz = min(max(t, 0), S - 2);
-        const float z_lo = __fmul_rn(0.5f, __fadd_rn(zc[bz + 1], zc[bz]));
-        const float z_hi = __fmul_rn(0.5f, __fadd_rn(zc[tz + 1], zc[tz]));
-        float dn = __fsub_rn(c_hi, c_lo);
-        const bool clamped = dn < 1e-5f;
-        dn = clamped ? 1e-5f : dn;
-        const float tv = __fdiv_rn(__fsub_rn(uu, c_lo), dn);
-        zn[k] = __fadd_rn(z_lo, __fmul_rn(tv, __fsub_rn(z_hi, z_lo)));
-        span[k] = __fsub_rn(z_hi, z_lo);
-        tt[k] = tv;
-        den[k] = clamped ? -dn : dn;
-        ilo[k] = b;
-        ihi[k] = t;
+        const CdfDraw dr = inverse_cdf_draw(cdf, zc, S, uu);
+        zn[k] = dr.z;
+        span[k] = dr.span;
+        tt[k] = dr.t;
+        den[k] = dr.clamped ? -dr.den : dr.den;
+        ilo[k] = dr.b;
+        ihi[k] = dr.t_bin;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // gradient of each unsorted sample = gradient of its slot in the sorted output (stable rank, as forward)
-    float dlo_r[4], dhi_r[4];
+    // gradient of each unsorted sample = gradient of its slot in the sorted output (stable rank, as forward).  A lane holds
+    // its samples' results in kTrainFineChunks registers each: check_samples refuses Sf > kTrainMaxFine = 64 * kTrainFineChunks
+    float dlo_r[kTrainFineChunks], dhi_r[kTrainFineChunks];
     int nk = 0;
     for (int k = lane; k < Sf; k += 64, ++nk) {
-        const float v = zn[k];
-        int rank = 0;
-        for (int i = 0; i < Sf4; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(zn + i);
-            rank += (q.x < v || (q.x == v && i + 0 < k)) ? 1 : 0;
-            rank += (q.y < v || (q.y == v && i + 1 < k)) ? 1 : 0;
-            rank += (q.z < v || (q.z == v && i + 2 < k)) ? 1 : 0;
-            rank += (q.w < v || (q.w == v && i + 3 < k)) ? 1 : 0;
-        }
-        const float g = d_zf[ray * Sf + rank];
+        const float g = d_zf[ray * Sf + stable_rank(zn, Sf4, zn[k], k)];
         const float dsgn = den[k];
         const bool clamped = dsgn < 0.f;
         const float dn = fabsf(dsgn);
@@ -1760,7 +1715,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void sample_pdf_bwd_kernel(
             dhi = dden;
             dlo -= dden;
         }
-        if (nk < 4) { dlo_r[nk] = dlo; dhi_r[nk] = dhi; }
+        if (nk < kTrainFineChunks) { dlo_r[nk] = dlo; dhi_r[nk] = dhi; }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1796,7 +1751,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void sample_pdf_bwd_kernel(
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // d_w = (dpdf - sum_i dpdf_i pdf_i) / D is again a difference of nearly equal large numbers: double
-    const double D = (double)scal[0], dot = (double)scal[1] + (double)scal[2];
+    const double D = (double)Df, dot = (double)scal[1] + (double)scal[2];
     for (int s = lane; s < S; s += 64)
         d_w[ray * S + s] = (float)(((double)dcdf[s] + (double)dcdf_hi[s]) / D - dot / (D * D));
 }

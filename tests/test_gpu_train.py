@@ -1025,7 +1025,7 @@ def test_dietnerf_consistency_step_shape(oracle, golden_ckpt, capsys, policy):
     ctx.close()
 
 
-@pytest.mark.parametrize("shape", [(37, 20, 100), (42, 70, 130), (130, 2, 3)])
+@pytest.mark.parametrize("shape", [(37, 20, 100), (42, 70, 130), (130, 2, 3), (5, 64, 65), (3, 256, 256), (3, 257, 64)])
 def test_gradients_at_ragged_shapes(oracle, golden_ckpt, shape, capsys):
     """Ray and sample counts that fit none of the kernels' granularities -- rays not a multiple of the four per
     compositing workgroup, sample counts that end inside a 64-lane chunk (20, 100, 70, 130) or are tiny (2, 3), row
