@@ -544,6 +544,52 @@ int nerf_train_render_forward(nerf_ctx* ctx, int32_t slot, const float* rays_ori
 int nerf_train_render_backward(nerf_ctx* ctx, int32_t slot, const float* d_rgb, int32_t accumulate, float* grad_coarse,
                                float* grad_fine, int mem);
 int nerf_train_render_release(nerf_ctx* ctx);
+/* ABI 6+, differentiable render outputs: the same two calls with every output of NeRF.render() a training loss can be written
+ * on -- depth supervision, a depth-smoothness or ray-entropy regulariser, any loss on more than the colour -- and a cotangent
+ * for each.  The outputs are those of the LAST pass (the fine pass on the Sc + Sf merged, sorted depths; the coarse pass
+ * when there is no fine one): S = Sc + Sf with a fine pass, else Sc. */
+typedef struct nerf_train_outputs {   /* any pointer may be NULL */
+    float* rgb;      /* (N,3) render()[0], the forward of the tape                  */
+    float* depth;    /* (N)   sum_s w_s z_s of the last pass                        */
+    float* weights;  /* (N,S) compositing weights of the last pass                  */
+    float* z;        /* (N,S) its depths (merged and sorted with a fine pass)       */
+} nerf_train_outputs;
+typedef struct nerf_render_grads {    /* cotangents dL/d(output); any may be NULL = zero, not all four */
+    const float* d_rgb;      /* (N,3) */
+    const float* d_depth;    /* (N)   */
+    const float* d_weights;  /* (N,S) */
+    const float* d_z;        /* (N,S) */
+} nerf_render_grads;
+/* nerf_train_render_forward_outputs is nerf_train_render_forward with more outputs: same slot, same draws, same kernels; rgb
+ * is bit-equal to nerf_train_render_forward's; weights and z are copies of what the slot keeps of its last pass; depth is the
+ * compositing kernel's own sum (a buffer for it exists only once depth has been asked for).  Slots are interchangeable:
+ * either forward call fills a slot that either backward call consumes.
+ * nerf_train_render_backward_outputs is nerf_train_render_backward with the upstream gradient g.  With only g->d_rgb set it
+ * launches exactly what nerf_train_render_backward launches and leaves bit-identical gradients.  Every rule of that call
+ * holds: accumulate; mixed_float16 (the caller passes UNSCALED cotangents, all four are multiplied by the loss scale on the
+ * device, and the unscaled result is tested and stored or added like with like); the slot is consumed; a slot filled under
+ * nerf_ctx_set_train_sample_culling runs backward on its own record (compositing and its backward run on all samples, so the
+ * new cotangents follow the flag exactly as d_rgb does).  One kernel, one thread per sample, no atomics, folds the three new
+ * cotangents into the last pass -- in float32, multiply and add rounded separately, absent inputs counting as 0:
+ *     g_w[r,s] = d_weights[r,s] + d_depth[r] * z[r,s]         g_z[r,s] = d_z[r,s] + d_depth[r] * w[r,s]
+ * (times the loss scale; 1 under the float32 policy).  g_w enters the last pass's compositing backward as its external
+ * dL/d(weights) -- the input the sampler's gradient uses on the coarse pass; g_z is ADDED to that pass's dL/dz after the
+ * compositing backward has stored there, and travels on through the merge and the inverse-CDF sampler into the coarse network.
+ * Where it has an effect: d_z and the d_depth * w term act only with a fine pass under sampler_gradient = 1, and only through
+ * the Sf new depths; the coarse depths are data, their entries are dropped.  Without a fine pass or without the sampler term
+ * they are ignored, and the gradients are bit-equal with and without d_z.  Nothing of this launches and no buffer grows unless
+ * one of the three new cotangents or outputs is non-NULL.  sum_s w_s is 1 on every ray under this compositing (the last
+ * sample's interval is 1e9), so there is no accumulated-opacity output: it would carry no gradient.
+ * Errors: outs / g NULL, all four cotangents NULL, an empty or consumed slot. */
+int nerf_train_render_forward_outputs(nerf_ctx* ctx, int32_t slot, const float* rays_orig, const float* rays_dirs, int64_t N,
+                                      int32_t Sc, int32_t Sf, const float* u_coarse, const float* u_fine, uint64_t seed,
+                                      int64_t ray_base, const nerf_train_outputs* outs, int mem);
+int nerf_train_render_backward_outputs(nerf_ctx* ctx, int32_t slot, const nerf_render_grads* g, int32_t accumulate,
+                                       float* grad_coarse, float* grad_fine, int mem);
+/* ABI 6+: the bare operator on caller data, beside nerf_distortion_loss: the fold above for weights, z (N,S) and any subset of
+ * d_depth (N), d_weights, d_z (N,S) (NULL = 0) -> g_w, g_z (N,S), either may be NULL; unscaled.  Needs S >= 1. */
+int nerf_render_output_grads(nerf_ctx* ctx, const float* weights, const float* z, int64_t N, int32_t S, const float* d_depth,
+                             const float* d_weights, const float* d_z, float* g_w, float* g_z, int mem);
 /* ABI 3: the gradient blob of a network as the ctx holds it now -- after nerf_train_gradients /
  * nerf_train_render_gradients the gradients just computed, after a data-parallel nerf_train_step the all-reduced mean
  * the Adam update used (what the reference's tape.gradient returns, src/NeRF.py:159-165). */

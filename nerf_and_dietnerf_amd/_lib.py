@@ -40,6 +40,14 @@ class NerfOutputs(C.Structure):
                 ("rgb", "weights", "cumprod", "alpha", "rgb_samples", "z", "depth")]
 
 
+class NerfTrainOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("rgb", "depth", "weights", "z")]
+
+
+class NerfRenderGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("d_rgb", "d_depth", "d_weights", "d_z")]
+
+
 # every symbol include/nerf_mi355.h declares: (name, restype, argtypes)
 _P, _I32, _I64, _U64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 SYMBOLS = [
@@ -107,6 +115,10 @@ SYMBOLS = [
                                               C.c_int]),
     ("nerf_train_render_forward", C.c_int, [_P, _I32, _P, _P, _I64, _I32, _I32, _P, _P, _U64, _I64, _P, C.c_int]),
     ("nerf_train_render_backward", C.c_int, [_P, _I32, _P, _I32, _P, _P, C.c_int]),
+    ("nerf_train_render_forward_outputs", C.c_int, [_P, _I32, _P, _P, _I64, _I32, _I32, _P, _P, _U64, _I64,
+                                                    C.POINTER(NerfTrainOutputs), C.c_int]),
+    ("nerf_train_render_backward_outputs", C.c_int, [_P, _I32, C.POINTER(NerfRenderGrads), _I32, _P, _P, C.c_int]),
+    ("nerf_render_output_grads", C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, C.c_int]),
     ("nerf_train_render_release", C.c_int, [_P]),
     ("nerf_train_get_gradients", C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),
     ("nerf_get_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),

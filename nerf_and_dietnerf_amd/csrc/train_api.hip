@@ -113,6 +113,9 @@ struct TrainState {
     bool mixed = false;
     DevBuf opt;                     // OptState (train_kernels.h): loss scale, verdicts, Adam iteration count -- on the device
     DevBuf z_new, d_zm, zero_rgb;   // backward through NeRF.render(): the Sf new depths, d/dz of the merged fine pass
+    // nerf_train_render_forward_outputs / _backward_outputs: the last pass's depth output (N), the folded dL/dw of the depth /
+    // weights / z cotangents (N x S: that pass's d_w_ext) and a host caller's staged cotangents.  None exists until asked for.
+    DevBuf depth, g_wfold, in_dd, in_dw, in_dz;
     DevBuf macc;                    // running sums of the step metrics (4 doubles: loss, psnr_coarse, psnr_fine, steps)
     DevBuf gsave[2];                // ... under mixed_float16 with accumulate = 1: the (unscaled) gradients already there
     // A render between optimizer steps (DietNeRF's consistency render every 13th step, the epoch plots) needs the render
@@ -317,7 +320,9 @@ long long net_rows_padded(const TPass& p, const PassDims& d) { return p.cull.row
 const uint8_t* cull_mask(const TPass& p) { return p.cull.rows < 0 ? nullptr : (const uint8_t*)p.cull.mask.p; }
 const uint32_t* cull_first(const TPass& p) { return p.cull.rows < 0 ? nullptr : (const uint32_t*)p.cull.first.p; }
 
-int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs) {
+// depth: where the compositing kernel stores its depth sum (N), for the caller who asked for it
+int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs,
+                 float* depth = nullptr) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     float *raw = (float*)p.raw.p, *z = (float*)p.z.p;
@@ -365,7 +370,7 @@ int forward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const
     }
     if (p.cull.rows >= 0)     // the full raw buffer, zeros for the culled samples: the compositing runs on all N S samples
         launch_raw_expand(in.raw, d.M, false, cull_mask(p), cull_first(p), raw, c->stream);
-    launch_composite(raw, z, d.N, d.S, (float*)p.rgb.p, (float*)p.w.p, (float*)p.T.p, nullptr, nullptr, nullptr,
+    launch_composite(raw, z, d.N, d.S, (float*)p.rgb.p, (float*)p.w.p, (float*)p.T.p, nullptr, nullptr, depth,
                      c->stream);
     HIP_OK(hipGetLastError());
     return 0;
@@ -857,7 +862,8 @@ void take_verdict(nerf_ctx* c, bool recheck) {
 
 // The forward half, on TrainState::pass / z_new: coarse pass -> z_new and the merged, sorted depths -> fine pass.
 int render_forward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, const float* o,
-                        const float* d, const float* uc, const float* uf, uint64_t seed, long long ray_base) {
+                        const float* d, const float* uc, const float* uf, uint64_t seed, long long ray_base,
+                        float* depth = nullptr) {              // depth: of the last pass, or null
     const long long N = dc.N;
     const int Sc = dc.S, Sf = df.S - dc.S;                           // the fine pass renders the Sc + Sf merged samples
     if (int q = sampling_ok(c)) return q;
@@ -867,19 +873,26 @@ int render_forward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const Pa
     if (r) return r;
     TPass& pc = t->pass[0];
     if (int q = draw_z_values(c, o, d, N, Sc, uc, seed, ray_base, (float*)pc.z.p)) return q;
-    if (int q = forward_pass(c, t, 0, dc, o, d)) return q;
+    if (int q = forward_pass(c, t, 0, dc, o, d, fine ? nullptr : depth)) return q;
     if (!fine) return 0;
     launch_sample_pdf((const float*)pc.w.p, (const float*)pc.z.p, N, Sc, Sf, uf, seed, ray_base, (float*)t->z_new.p,
                       (float*)t->pass[1].z.p, c->stream);
-    return forward_pass(c, t, 1, df, o, d);
+    return forward_pass(c, t, 1, df, o, d, depth);
 }
+
+// the cotangents of render()'s outputs beside rgb (nerf_render_grads), on the device; null = zero
+struct OutputGrads {
+    const float *d_depth = nullptr, *d_weights = nullptr, *d_z = nullptr;
+};
 
 // The backward half's buffers: the common workspace, dL/dz of the new and of the merged depths, the sampler-only coarse
 // pass's zero d_rgb and, under mixed_float16, the scaled d_rgb and the gradients an accumulating call adds to.
-int ensure_render_bwd(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, bool accumulate) {
+int ensure_render_bwd(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, bool accumulate,
+                      bool fold_w = false) {      // fold_w: a depth or weights cotangent needs the last pass's folded dL/dw
     const size_t f = sizeof(float);
     const long long N = dc.N;
     int r = ensure_bwd_workspace(c, t, fine ? df.Mp : dc.Mp, dc.M);
+    if (fold_w) r |= ensure(c, t->g_wfold, (fine ? df.M : dc.M) * f);
     r |= ensure(c, t->d_zf, (fine ? N * (long long)(df.S - dc.S) : 1) * f);
     r |= ensure(c, t->d_zm, (fine ? df.M : 1) * f);
     r |= ensure(c, t->zero_rgb, N * 3 * f);
@@ -892,11 +905,12 @@ int ensure_render_bwd(nerf_ctx* c, TrainState* t, const PassDims& dc, const Pass
     return r;
 }
 
-// The backward half, on what render_forward_core left in TrainState::pass / z_new; dr: the caller's d_rgb on the device.
+// The backward half, on what render_forward_core left in TrainState::pass / z_new; dr: the caller's d_rgb on the device
+// (null: zero); x: the cotangents of the last pass's other outputs (nerf_train_render_backward_outputs), all null otherwise.
 // Runs under a SlotLease (which clears acc_grads on the way out).
 int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, const float* o,
                          const float* d, const float* uf, uint64_t seed, long long ray_base, const float* dr,
-                         bool accumulate) {
+                         bool accumulate, const OutputGrads& x = OutputGrads()) {
     const size_t f = sizeof(float);
     const long long N = dc.N;
     const int Sc = dc.S, Sf = df.S - dc.S;
@@ -913,8 +927,10 @@ int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const P
         // accumulate = 1 it collects over both calls and nerf_train_apply takes the one verdict.
         OptState* st = (OptState*)t->opt.p;
         if (!accumulate) launch_opt_begin(st, c->stream);
-        launch_scale_by_loss_scale(dr, N * 3, st, (float*)t->d_rgb.p, c->stream);
-        dr = (const float*)t->d_rgb.p;
+        if (dr) {
+            launch_scale_by_loss_scale(dr, N * 3, st, (float*)t->d_rgb.p, c->stream);
+            dr = (const float*)t->d_rgb.p;
+        }
         if (accumulate)
             for (int w = 0; w < 2; ++w)
                 if (computes[w] && t->net[w].present)
@@ -922,12 +938,31 @@ int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const P
     }
     t->acc_grads = accumulate && !t->mixed;      // (mixed: the scaled result overwrites, the addition happens after unscaling)
 
+    if (!dr) {      // no colour term: the zero buffer the sampler-only coarse pass has
+        HIP_OK(hipMemsetAsync(t->zero_rgb.p, 0, N * 3 * f, c->stream));
+        dr = (const float*)t->zero_rgb.p;
+    }
+    // the depth / weights cotangents of the last pass, folded into its dL/dw (carrying the loss scale like dr)
+    const TPass& pl = t->pass[fine ? 1 : 0];
+    const PassDims& dl = fine ? df : dc;
+    const float* g_w = nullptr;
+    if (x.d_depth || x.d_weights) {
+        launch_render_output_fold((const float*)pl.w.p, (const float*)pl.z.p, dl.N, dl.S, x.d_depth, x.d_weights, nullptr,
+                                  (const OptState*)t->opt.p, (float*)t->g_wfold.p, nullptr, false, c->stream);
+        g_w = (const float*)t->g_wfold.p;
+    }
+
     const TPass& pc = t->pass[0];
     if (!fine) {
-        if (int q = composite_backward_pass(c, t, 0, dc, o, d, dr, nullptr, nullptr)) return q;
+        if (int q = composite_backward_pass(c, t, 0, dc, o, d, dr, g_w, nullptr)) return q;     // (its depths are data)
     } else {
         float* d_zm = through_sampler ? (float*)t->d_zm.p : nullptr;
-        if (int q = composite_backward_pass(c, t, 1, df, o, d, dr, nullptr, d_zm)) return q;
+        if (int q = composite_backward_pass(c, t, 1, df, o, d, dr, g_w, d_zm)) return q;
+        // the depths' own cotangents join the pass's d_z AFTER the compositing backward, which stores there (as the
+        // distortion loss's dL/dz does in gradients_impl); only the sampler consumes them
+        if (d_zm && (x.d_depth || x.d_z))
+            launch_render_output_fold((const float*)pl.w.p, (const float*)pl.z.p, dl.N, dl.S, x.d_depth, nullptr, x.d_z,
+                                      (const OptState*)t->opt.p, nullptr, d_zm, true, c->stream);
         if (through_sampler) {
             launch_unmerge_grad((const float*)t->z_new.p, (const float*)pc.z.p, d_zm, N, Sc, Sf, (float*)t->d_zf.p,
                                 c->stream);
@@ -1026,13 +1061,15 @@ int render_gradients_impl(nerf_ctx* c, const float* rays_o, const float* rays_d,
 }
 
 int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float* rays_d, int64_t N, int Sc, int Sf,
-                        const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, int mem) {
+                        const float* u_c, const float* u_f, uint64_t seed, int64_t ray_base, int mem,
+                        bool want_depth = false) {    // want_depth: the last pass's depth sum -> TrainState::depth
     TrainState* t = c->train;
     if (!t) return fail("nerf_train_begin has not been called");
     if (!rays_o || !rays_d) return fail("NULL argument");
     if (slot < 0 || slot >= kMaxRenderSlots) return fail("slot %d out of range (0..%d)", slot, kMaxRenderSlots - 1);
     bool fine;
     if (int r = check_samples(t, N, Sc, Sf, &fine)) return r;
+    if (want_depth) if (int r = ensure(c, t->depth, N * sizeof(float))) return r;
     if ((size_t)slot >= t->slots.size()) t->slots.resize((size_t)slot + 1);
     RenderSlot& s = t->slots[slot];
     s.valid = false;
@@ -1052,31 +1089,36 @@ int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float*
     const float* uf = s.has_uf ? (const float*)s.u_f.p : nullptr;
     SlotLease lease(c, t, &s);
     if (int r = render_forward_core(c, t, pass_dims(N, Sc), pass_dims(N, Sc + Sf), fine, (const float*)s.o.p,
-                                    (const float*)s.d.p, uc, uf, seed, ray_base))
+                                    (const float*)s.d.p, uc, uf, seed, ray_base, want_depth ? (float*)t->depth.p : nullptr))
         return r;
     s.N = N; s.Sc = Sc; s.Sf = fine ? Sf : 0; s.seed = seed; s.ray_base = ray_base;
     s.valid = true;
     return 0;
 }
 
-int render_backward_impl(nerf_ctx* c, int slot, const float* d_rgb_in, bool accumulate, int mem) {
+// g: the caller's cotangents (nerf_render_grads; at least one is set).  nerf_train_render_backward passes d_rgb alone.
+int render_backward_impl(nerf_ctx* c, int slot, const nerf_render_grads& g, bool accumulate, int mem) {
     TrainState* t = c->train;
     if (!t) return fail("nerf_train_begin has not been called");
-    if (!d_rgb_in) return fail("NULL argument");
     if (slot < 0 || (size_t)slot >= t->slots.size() || !t->slots[slot].valid)
         return fail("slot %d holds no forward pass (nerf_train_render_forward first; a backward pass consumes it, and so does "
                     "an optimizer step)", slot);
     RenderSlot& s = t->slots[slot];
     const bool fine = s.Sf > 0;
     const PassDims dc = pass_dims(s.N, s.Sc), df = pass_dims(s.N, s.Sc + s.Sf);
+    const size_t ns = (size_t)(fine ? df.M : dc.M) * sizeof(float);
     Staging st(c, mem);
-    const float* dr = st.in(t->tgt, d_rgb_in, s.N * 3 * sizeof(float));
+    const float* dr = st.in(t->tgt, g.d_rgb, s.N * 3 * sizeof(float));
+    OutputGrads x;
+    x.d_depth = st.in(t->in_dd, g.d_depth, s.N * sizeof(float));
+    x.d_weights = st.in(t->in_dw, g.d_weights, ns);
+    x.d_z = st.in(t->in_dz, g.d_z, ns);
     if (st.err) return st.err;
-    if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate)) return r;
+    if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate, x.d_depth || x.d_weights)) return r;
     s.valid = false;                              // consumed, whatever happens below
     SlotLease lease(c, t, &s);
     return render_backward_core(c, t, dc, df, fine, (const float*)s.o.p, (const float*)s.d.p,
-                                s.has_uf ? (const float*)s.u_f.p : nullptr, s.seed, s.ray_base, dr, accumulate);
+                                s.has_uf ? (const float*)s.u_f.p : nullptr, s.seed, s.ray_base, dr, accumulate, x);
 }
 
 // The outputs of a gradient / render call, each only if the caller asks for it: rgb (N x 3) and the two gradient blobs,
@@ -1153,7 +1195,8 @@ void train_free(nerf_ctx* c) {
     free_buf(t->partial_side);
     DevBuf* bs[] = {&t->Gc, &t->Ga, &t->Gb, &t->G9, &t->Graw, &t->dsig, &t->dA0, &t->partial, &t->d_rgb, &t->d_wext, &t->d_zf, &t->tgt,
                     &t->o, &t->d, &t->u_c, &t->u_f, &t->scal, &t->gmax, &t->z_new, &t->d_zm, &t->zero_rgb, &t->opt,
-                    &t->gsave[0], &t->gsave[1], &t->macc, &t->d_wdist, &t->dist_ray, &t->dacc};
+                    &t->gsave[0], &t->gsave[1], &t->macc, &t->d_wdist, &t->dist_ray, &t->dacc, &t->depth, &t->g_wfold, &t->in_dd,
+                    &t->in_dw, &t->in_dz};
     for (DevBuf* b : bs) free_buf(*b);
     delete t;
     c->train = nullptr;
@@ -1379,8 +1422,59 @@ int nerf_train_render_backward(nerf_ctx* c, int32_t slot, const float* d_rgb, in
     ENTER(c);
     const bool fine = c->train && slot >= 0 && (size_t)slot < c->train->slots.size() && c->train->slots[slot].Sf > 0;
     if (grad_fine && !fine) return fail("grad_fine requested but slot %d ran no fine pass", slot);   // (before it is consumed)
-    if (int r = render_backward_impl(c, slot, d_rgb, accumulate != 0, mem)) return r;
+    if (c->train && !d_rgb) return fail("NULL argument");
+    if (int r = render_backward_impl(c, slot, nerf_render_grads{d_rgb, nullptr, nullptr, nullptr}, accumulate != 0, mem)) return r;
     return copy_out(c, mem, c->train->slots[slot].Sf, grad_coarse, grad_fine);
+}
+
+int nerf_train_render_forward_outputs(nerf_ctx* c, int32_t slot, const float* rays_orig, const float* rays_dirs, int64_t N,
+                                      int32_t Sc, int32_t Sf, const float* u_coarse, const float* u_fine, uint64_t seed,
+                                      int64_t ray_base, const nerf_train_outputs* outs, int mem) {
+    ENTER(c);
+    if (!outs) return fail("nerf_train_outputs is NULL");
+    if (int r = render_forward_impl(c, slot, rays_orig, rays_dirs, N, Sc, Sf, u_coarse, u_fine, seed, ray_base, mem,
+                                    outs->depth != nullptr)) return r;
+    const RenderSlot& s = c->train->slots[slot];
+    const TPass& p = s.pass[s.Sf > 0 ? 1 : 0];
+    const size_t f = sizeof(float), ns = (size_t)N * (s.Sc + s.Sf) * f;
+    if (outs->depth) if (int r = copy_to_caller(c, outs->depth, c->train->depth.p, N * f, mem)) return r;
+    if (outs->weights) if (int r = copy_to_caller(c, outs->weights, p.w.p, ns, mem)) return r;
+    if (outs->z) if (int r = copy_to_caller(c, outs->z, p.z.p, ns, mem)) return r;
+    return copy_out(c, mem, s.Sf, nullptr, nullptr, outs->rgb, p.rgb.p, N);      // (synchronises for a host caller)
+}
+
+int nerf_train_render_backward_outputs(nerf_ctx* c, int32_t slot, const nerf_render_grads* g, int32_t accumulate,
+                                       float* grad_coarse, float* grad_fine, int mem) {
+    ENTER(c);
+    if (!g) return fail("nerf_render_grads is NULL");
+    if (!g->d_rgb && !g->d_depth && !g->d_weights && !g->d_z)
+        return fail("all four cotangents of nerf_render_grads are NULL: nothing to differentiate");
+    const bool fine = c->train && slot >= 0 && (size_t)slot < c->train->slots.size() && c->train->slots[slot].Sf > 0;
+    if (grad_fine && !fine) return fail("grad_fine requested but slot %d ran no fine pass", slot);   // (before it is consumed)
+    if (int r = render_backward_impl(c, slot, *g, accumulate != 0, mem)) return r;
+    return copy_out(c, mem, c->train->slots[slot].Sf, grad_coarse, grad_fine);
+}
+
+int nerf_render_output_grads(nerf_ctx* c, const float* weights, const float* z, int64_t N, int32_t S, const float* d_depth,
+                             const float* d_weights, const float* d_z, float* g_w, float* g_z, int mem) {
+    ENTER(c);
+    if (!weights) return fail("weights is NULL");
+    if (!z) return fail("z is NULL");
+    if (N < 0) return fail("bad N = %lld (need N >= 0)", (long long)N);
+    if (S < 1) return fail("bad S = %d (need S >= 1)", S);
+    const size_t f = sizeof(float), ns = (size_t)N * S * f;
+    Staging st(c, mem);
+    const float* w = st.in(c->b_in0, weights, ns);
+    const float* zz = st.in(c->b_in1, z, ns);
+    const float* dd = st.in(c->b_in2, d_depth, (size_t)N * f);
+    const float* dw = st.in(c->b_zc, d_weights, ns);
+    const float* dz = st.in(c->b_zf, d_z, ns);
+    float* gw = st.out(c->b_out[0], g_w, ns);
+    float* gz = st.out(c->b_out[1], g_z, ns);
+    if (st.err) return st.err;
+    launch_render_output_fold(w, zz, N, S, dd, dw, dz, nullptr, gw, gz, false, c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
 }
 
 int nerf_train_render_release(nerf_ctx* c) {

@@ -143,6 +143,13 @@ void launch_pe_bwd(const float* dA0, const float* dA0b /* added to dA0, or null 
                    hipStream_t s, bool frag = false);     // frag: dA0 / dA0b are fragment-major (the fused backward chain's dx buffers)
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
                          hipStream_t s);
+// The fold of render()'s depth / weights / z cotangents into one pass's dL/dw and dL/dz (weights, z: N x S of that pass;
+// d_depth (N), d_weights, d_z (N x S): nullable = 0), one thread per sample, every operation rounded on its own:
+//     g_w = (d_weights + d_depth * z) * st->scale      g_z = (d_z + d_depth * weights) * st->scale      (st nullable: no factor)
+// g_w is stored; g_z is stored or, add_z, added to what is there.  Either output may be null.
+void launch_render_output_fold(const float* weights, const float* z, long long N, int S, const float* d_depth,
+                               const float* d_weights, const float* d_z, const OptState* st, float* g_w, float* g_z, bool add_z,
+                               hipStream_t s);
 // The sampler backward keeps a lane's fine samples (k = lane, lane + 64, ...) in kTrainFineChunks registers, so a training
 // call takes at most kTrainMaxFine fine samples per ray: train_api.hip's check_samples refuses more.
 constexpr int kTrainFineChunks = 4;

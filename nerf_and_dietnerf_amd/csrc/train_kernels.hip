@@ -1638,6 +1638,40 @@ void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm
                        d_zf);
 }
 
+// ------------------------------------------------------------------------------------------------
+// render()'s outputs beside rgb are functions of the last pass's weights and depths: depth = sum_s w_s z_s, weights = w, z = z.
+// Their cotangents fold into that pass's dL/dw (the compositing backward's d_w_ext) and dL/dz, sample by sample.  Multiply,
+// add and the loss-scale multiply are separate float32 roundings (the build runs under -ffp-contract=off; the intrinsics say
+// so here), so a numpy restatement gives the same bits.
+// ------------------------------------------------------------------------------------------------
+__global__ void render_output_fold_kernel(const float* __restrict__ w, const float* __restrict__ z, long long total, int S,
+                                          const float* __restrict__ d_depth, const float* __restrict__ d_w,
+                                          const float* __restrict__ d_z, const OptState* __restrict__ st,
+                                          float* __restrict__ g_w, float* __restrict__ g_z, int add_z) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const float dd = d_depth ? d_depth[i / S] : 0.f;
+    if (g_w) {
+        float g = __fadd_rn(d_w ? d_w[i] : 0.f, d_depth ? __fmul_rn(dd, z[i]) : 0.f);
+        if (st) g = __fmul_rn(g, st->scale);
+        g_w[i] = g;
+    }
+    if (g_z) {
+        float g = __fadd_rn(d_z ? d_z[i] : 0.f, d_depth ? __fmul_rn(dd, w[i]) : 0.f);
+        if (st) g = __fmul_rn(g, st->scale);
+        g_z[i] = add_z ? __fadd_rn(g_z[i], g) : g;
+    }
+}
+
+void launch_render_output_fold(const float* weights, const float* z, long long N, int S, const float* d_depth,
+                               const float* d_weights, const float* d_z, const OptState* st, float* g_w, float* g_z, bool add_z,
+                               hipStream_t s) {
+    const long long total = N * S;
+    if (total <= 0 || (!g_w && !g_z)) return;
+    hipLaunchKernelGGL(render_output_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, weights, z, total, S,
+                       d_depth, d_weights, d_z, st, g_w, g_z, add_z ? 1 : 0);
+}
+
 void launch_pe_bwd(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N, int S,
                    int lx, const uint8_t* mask, const uint32_t* first, float* d_z, hipStream_t s, bool frag) {
     const long long total = N * S;

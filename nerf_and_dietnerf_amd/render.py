@@ -876,6 +876,64 @@ class Context:
         _lib.check(self.lib.nerf_train_render_backward(self.h, int(slot), pg, 1 if accumulate else 0, pgc, pgf, arr.mem))
         return gc, gf
 
+    _TRAIN_OUTPUTS = ("rgb", "depth", "weights", "z")
+
+    def train_render_forward_outputs(self, slot: int, rays_orig, rays_dirs, n_c, n_f, u_coarse=None, u_fine=None, seed=0,
+                                     ray_base=0, outputs=_TRAIN_OUTPUTS) -> Dict[str, object]:
+        """``train_render_forward`` with every output a loss can be written on (nerf_train_render_forward_outputs): -> dict of
+        the ``outputs`` asked for, of the LAST pass -- ``rgb`` (N,3), the same bits as ``train_render_forward``; ``depth`` (N,)
+        = sum_s w_s z_s; ``weights`` and ``z`` (N,S), S = n_c + n_f with a fine pass (z merged and sorted), else n_c.  The
+        slot is the same slot: ``train_render_backward`` or ``train_render_backward_outputs`` consumes it."""
+        bad = [k for k in outputs if k not in self._TRAIN_OUTPUTS]
+        if bad or not len(outputs):
+            raise ValueError(f"outputs must name some of {self._TRAIN_OUTPUTS}, got {tuple(outputs)}")
+        arr = self._arrays(rays_orig, rays_dirs)
+        n = int(rays_orig.shape[0])
+        po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
+        uc = arr.inp(u_coarse, (n, n_c)) if u_coarse is not None else None
+        uf = arr.inp(u_fine, (n, n_f)) if (u_fine is not None and n_f > 0) else None
+        fine = n_f > 0 and self.loaded[1]
+        s = n_c + n_f if fine else n_c
+        shapes = {"rgb": (n, 3), "depth": (n,), "weights": (n, s), "z": (n, s)}
+        got = {k: arr.out(shapes[k]) for k in self._TRAIN_OUTPUTS if k in outputs}
+        o = _lib.NerfTrainOutputs(*[got[k][1] if k in got else None for k in self._TRAIN_OUTPUTS])
+        _lib.check(self.lib.nerf_train_render_forward_outputs(self.h, int(slot), po, pd, n, n_c, n_f, uc, uf, seed, ray_base,
+                                                              C.byref(o), arr.mem))
+        self._slot_fine[int(slot)] = fine
+        return {k: v[0] for k, v in got.items()}
+
+    def train_render_backward_outputs(self, slot: int, d_rgb=None, d_depth=None, d_weights=None, d_z=None, accumulate=False,
+                                      want_blobs=True):
+        """``train_render_backward`` with a cotangent for every output of ``train_render_forward_outputs``
+        (nerf_train_render_backward_outputs): any of ``d_rgb`` (N,3), ``d_depth`` (N,), ``d_weights``, ``d_z`` (N,S) may be
+        None (= zero), not all four -> (grad_coarse blob, grad_fine blob | None) copies (or (None, None)).  With ``d_rgb``
+        alone it is ``train_render_backward``, bit for bit.  ``d_z`` and the depth's own dependence on z reach the networks
+        only with a fine pass under ``sampler_gradient`` (through the n_f new depths; the coarse depths are data).  Under
+        mixed_float16 pass UNSCALED cotangents: the library applies the loss scale.  Consumes the slot."""
+        arr = self._arrays(d_rgb, d_depth, d_weights, d_z)
+        g = _lib.NerfRenderGrads(arr.inp(d_rgb), arr.inp(d_depth), arr.inp(d_weights), arr.inp(d_z))
+        fine = self._slot_fine.get(int(slot), False)
+        gc, pgc = arr.out((self.blob_size(),)) if want_blobs else (None, None)
+        gf, pgf = arr.out((self.blob_size(),)) if want_blobs and fine else (None, None)
+        _lib.check(self.lib.nerf_train_render_backward_outputs(self.h, int(slot), C.byref(g), 1 if accumulate else 0, pgc, pgf,
+                                                               arr.mem))
+        return gc, gf
+
+    def render_output_grads(self, weights, z_values, d_depth=None, d_weights=None, d_z=None):
+        """The bare fold of the depth / weights / z cotangents (nerf_render_output_grads): weights, z_values (N,S) and any of
+        d_depth (N,), d_weights, d_z (N,S) (None = 0) -> (g_w, g_z) (N,S): g_w = d_weights + d_depth * z, g_z = d_z +
+        d_depth * weights, float32 with every operation rounded on its own."""
+        arr = self._arrays(weights, z_values, d_depth, d_weights, d_z)
+        n, s = tuple(weights.shape)
+        pw, pz = arr.inp(weights, (n, s)), arr.inp(z_values, (n, s))
+        pdd = arr.inp(d_depth, (n,)) if d_depth is not None else None
+        pdw = arr.inp(d_weights, (n, s)) if d_weights is not None else None
+        pdz = arr.inp(d_z, (n, s)) if d_z is not None else None
+        gw, pgw = arr.out((n, s))
+        gz, pgz = arr.out((n, s))
+        _lib.check(self.lib.nerf_render_output_grads(self.h, pw, pz, n, s, pdd, pdw, pdz, pgw, pgz, arr.mem))
+        return gw, gz
+
     def train_render_release(self) -> None:
         """Frees the kept activations of every slot (they are grow-only otherwise; train_end frees them too)."""
         _lib.check(self.lib.nerf_train_render_release(self.h))
@@ -1309,6 +1367,27 @@ class NeRF:
         gf = allreduce_mean(gf, group, self.ctx.cfg.device) if gf is not None else None
         self.ctx.train_apply(gc, gf)
         return metrics if want_metrics else None
+
+    def train_step_custom(self, batch, loss_fn, slot: int = 0, *, u_coarse=None, u_fine=None, seed=None,
+                          want_loss: bool = False) -> Optional[float]:
+        """One optimizer step on a loss written in torch: ``batch`` = (rays_orig (N,4), rays_dirs (N,4), real_rgb) as torch
+        device tensors; ``loss = loss_fn(outputs, real_rgb)`` with ``outputs`` the dict of ``autograd.render_with_grad``
+        (rgb, depth, weights, z of ``render()`` on these rays); then ``loss.backward()`` and the Adam update.  Returns
+        ``float(loss)`` only with ``want_loss=True`` (which waits for the step), else None.  Under mixed_float16 do NOT scale
+        the loss: the library multiplies the cotangents by its loss scale on the device, unscales the gradients and skips a
+        non-finite step.  Single process only (no ``group``)."""
+        from .autograd import render_with_grad
+        rays_orig, rays_dirs, real_rgb = batch
+        n_f = self.n_render_samples_fine if self.model_fine else 0
+        if seed is None:
+            seed = self.seed + 7919 * self._train_calls
+        self._train_calls += 1
+        out = render_with_grad(self.ctx, rays_orig, rays_dirs, self.n_render_samples_coarse, n_f, slot=slot, seed=seed,
+                               u_coarse=u_coarse, u_fine=u_fine)
+        loss = loss_fn(out, real_rgb)
+        loss.backward()
+        self.ctx.train_apply()
+        return float(loss.detach()) if want_loss else None
 
     def get_weights(self):
         """(coarse blob, fine blob | None), Keras ``get_weights()`` order."""
