@@ -433,7 +433,8 @@ typedef struct nerf_train_config {
 } nerf_train_config;
 
 /* Starts a trainer on the weights currently loaded (coarse required, fine optional); zero Adam moments.  Called while a
- * trainer is running it restarts the optimizer on the TRAINED weights (and resets the loss weights to 1, 1).
+ * trainer is running it restarts the optimizer on the TRAINED weights (and resets the loss weights to 1, 1 and
+ * nerf_train_set_ray_gradients to off).
  * Rendering between optimizer steps is allowed at any time (DietNeRF's consistency render, the epoch plots,
  * src/ExecutionRun.py:193-201): the render path's operand streams are re-packed from the trained weights on the device,
  * enqueued on the ctx stream, without a host round trip. */
@@ -590,6 +591,44 @@ int nerf_train_render_backward_outputs(nerf_ctx* ctx, int32_t slot, const nerf_r
  * d_depth (N), d_weights, d_z (N,S) (NULL = 0) -> g_w, g_z (N,S), either may be NULL; unscaled.  Needs S >= 1. */
 int nerf_render_output_grads(nerf_ctx* ctx, const float* weights, const float* z, int64_t N, int32_t S, const float* d_depth,
                              const float* d_weights, const float* d_z, float* g_w, float* g_z, int mem);
+/* ABI 6+, ray gradients: dL/d(rays_orig) and dL/d(rays_dirs) of the same scalar the render backward differentiates, with
+ * respect to the ray arrays handed to the slot's forward call -- what pose refinement, registering a new photograph to a
+ * trained scene, or any loss that moves cameras needs.  Both are (N,4) float32 with component 3 exactly 0.
+ * Included is everything NeRF.render()'s graph routes through the rays:
+ *   - the sample points p = o + d z of every network pass that takes part in the call: the last pass and, with a fine network
+ *     under sampler_gradient = 1, the coarse pass, which is reached through the sampler
+ *     (d_o = sum_s dL/dp_s, d_d = sum_s z_s dL/dp_s);
+ *   - the view-direction input of those passes: the raw, un-normalised direction, components [0,1,2] for n_angles = 2 and
+ *     [0,2] for n_angles = 1 (none for the xyz-only network).
+ * Treated as data: the coarse depths (as everywhere in the trainer: the coarse depths are data), the near / far bounds, and
+ * the per-ray bounds that a scene box or an occupancy grid derives from the ray.  Under NDC rays the gradients are with
+ * respect to the NDC rays the call received.  Samples culled under nerf_ctx_set_train_sample_culling contribute nothing; a
+ * ray whose samples are all culled gets zeros.  Without a fine pass or without the sampler term the coarse pass contributes
+ * exactly what it contributes to the weights: nothing if a fine network exists and sampler_gradient = 0.  Under mixed_float16
+ * the chain carries the loss scale as it does for the weights and the ray gradients are unscaled on the device from the
+ * trainer's loss-scale state, without a host round trip; a non-finite ray gradient does not change the step verdict by
+ * itself (the weight gradients of the same call decide it).
+ * nerf_train_set_ray_gradients switches the feature on a running trainer: the encoding gradient is a by-product of how a
+ * network's backward operand stream is packed, so the call re-packs both networks' backward streams with (on) or without
+ * (off) the encoding tiles.  Off is the default and the state nerf_train_begin leaves -- a restarted trainer has it off
+ * again.  While it is off nothing changes: the same kernels run, the same buffers exist and every entry point leaves the
+ * same bits.  While it is on, the coarse network's backward chain runs its encoding-gradient variant (same arithmetic class;
+ * its weight gradients need not be bit-equal to the off state's), the fine network's is the variant it already runs under
+ * sampler_gradient = 1.  Kept slots stay valid across the switch.  The exact-fp32 reference trainer (NERF_TRAIN_FORWARD=gemm)
+ * does not implement it: switching on fails there with an error that names the fused trainer.
+ * nerf_train_render_backward_rays is nerf_train_render_backward_outputs plus the two ray outputs (either may be NULL); with
+ * both NULL it is that call, bit for bit.  The ray gradients are stored, never accumulated (`accumulate` acts on the blobs).
+ * Two kernels per pass, one ray per wavefront, fixed summation order, no atomics: the same inputs give the same bits on every
+ * run.  Fails if the switch is off.  Not covered: nerf_train_step / nerf_train_gradients (the two-MSE ray loss is another
+ * graph), the data-parallel path, gradients through box / grid / NDC bounds. */
+int nerf_train_set_ray_gradients(nerf_ctx* ctx, int32_t on);
+int nerf_train_render_backward_rays(nerf_ctx* ctx, int32_t slot, const nerf_render_grads* g, int32_t accumulate,
+                                    float* grad_coarse, float* grad_fine, float* d_rays_orig, float* d_rays_dirs, int mem);
+/* ABI 6+: the bare reduction on caller data, beside nerf_distortion_loss and nerf_render_output_grads: d_points (N,S,3) =
+ * dL/dp per sample, z (N,S) -> d_rays_orig[r] = sum_s d_points[r,s], d_rays_dirs[r] = sum_s z[r,s] d_points[r,s], (N,4) with
+ * component 3 = 0; either output may be NULL.  float32, the order of the kernel above.  Needs S >= 1. */
+int nerf_ray_position_grads(nerf_ctx* ctx, const float* d_points, const float* z, int64_t N, int32_t S, float* d_rays_orig,
+                            float* d_rays_dirs, int mem);
 /* ABI 3: the gradient blob of a network as the ctx holds it now -- after nerf_train_gradients /
  * nerf_train_render_gradients the gradients just computed, after a data-parallel nerf_train_step the all-reduced mean
  * the Adam update used (what the reference's tape.gradient returns, src/NeRF.py:159-165). */

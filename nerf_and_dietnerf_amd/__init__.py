@@ -16,7 +16,8 @@ from .sharding import allreduce_mean, dist_world, gather_slabs, ray_slab, render
 from .dataset import RayDataset, c2w_to_rays_prepare_ds, fit, prepare_ds
 from .dietnerf import DietNeRF
 from .autograd import render_with_grad
-from . import autograd, config, scene
+from .pose import rays_from_pose
+from . import autograd, config, pose, scene
 from .scene import estimate_point_of_interest_in_scene
 from .config import (get_nerf, get_num_of_batches, get_psnr_values, get_train_data, load_config,
                      save_psnr_values)

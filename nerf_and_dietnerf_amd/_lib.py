@@ -119,6 +119,9 @@ SYMBOLS = [
                                                     C.POINTER(NerfTrainOutputs), C.c_int]),
     ("nerf_train_render_backward_outputs", C.c_int, [_P, _I32, C.POINTER(NerfRenderGrads), _I32, _P, _P, C.c_int]),
     ("nerf_render_output_grads", C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, C.c_int]),
+    ("nerf_train_set_ray_gradients", C.c_int, [_P, _I32]),
+    ("nerf_train_render_backward_rays", C.c_int, [_P, _I32, C.POINTER(NerfRenderGrads), _I32, _P, _P, _P, _P, C.c_int]),
+    ("nerf_ray_position_grads", C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, C.c_int]),
     ("nerf_train_render_release", C.c_int, [_P]),
     ("nerf_train_get_gradients", C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),
     ("nerf_get_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),

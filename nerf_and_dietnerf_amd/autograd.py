@@ -45,8 +45,14 @@ def _render_function():
             ctx, slot, accumulate = fn.call
             grads = [None if g is None else g.detach().contiguous() for g in (d_rgb, d_depth, d_weights, d_z)]
             # consumes the slot: a second backward through the same graph fails with the library's "slot holds no forward pass"
-            ctx.train_render_backward_outputs(slot, *grads, accumulate=accumulate, want_blobs=False)
-            return (torch.zeros_like(fn.anchor_like),) + (None,) * 11
+            want_o, want_d = fn.needs_input_grad[4], fn.needs_input_grad[5]
+            if not (want_o or want_d):
+                ctx.train_render_backward_outputs(slot, *grads, accumulate=accumulate, want_blobs=False)
+                return (torch.zeros_like(fn.anchor_like),) + (None,) * 11
+            # rays that require grad: the library's ray gradients (its error if ctx.train_set_ray_gradients is off)
+            _, _, g_o, g_d = ctx.train_render_backward_outputs(slot, *grads, accumulate=accumulate, want_blobs=False, want_rays=True)
+            return (torch.zeros_like(fn.anchor_like), None, None, None, g_o if want_o else None, g_d if want_d else None) + \
+                (None,) * 6
 
     _function = _RenderWithGrad
     return _function

@@ -36,7 +36,7 @@ struct TNet {
     void* fstream = nullptr;       // fused forward (f16x3 stash kernel): operand stream + constants, re-packed on device
     float* fcst = nullptr;
     void* bstream = nullptr;       // fused backward (mlp_bwd_f16x3): transposed operand stream, re-packed on device
-    bool bdx = false;              // ... built with the encoding tiles (the fine network under sampler_gradient)
+    bool bdx = false;              // ... built with the encoding tiles (the fine network under sampler_gradient; both under ray_grads)
     int n_layers = 11;             // 11: xyz + view-direction network; 12: xyz-only network (n_angles_for_model = 0)
     TLayer L[12];
 };
@@ -116,6 +116,11 @@ struct TrainState {
     // nerf_train_render_forward_outputs / _backward_outputs: the last pass's depth output (N), the folded dL/dw of the depth /
     // weights / z cotangents (N x S: that pass's d_w_ext) and a host caller's staged cotangents.  None exists until asked for.
     DevBuf depth, g_wfold, in_dd, in_dw, in_dz;
+    // nerf_train_set_ray_gradients: both networks' backward streams carry the encoding tiles, so every pass's chain leaves
+    // the encoding gradient that nerf_train_render_backward_rays reduces per ray.  out_ro / out_rd: a host caller's (N, 4)
+    // results before they leave; neither exists until asked for.
+    bool ray_grads = false;
+    DevBuf out_ro, out_rd;
     DevBuf macc;                    // running sums of the step metrics (4 doubles: loss, psnr_coarse, psnr_fine, steps)
     DevBuf gsave[2];                // ... under mixed_float16 with accumulate = 1: the (unscaled) gradients already there
     // A render between optimizer steps (DietNeRF's consistency render every 13th step, the epoch plots) needs the render
@@ -202,8 +207,9 @@ int ensure_fused(nerf_ctx* c, TrainState* t, TNet& n) {
     if (int r = ensure_render_tables(c)) return r;
     if (!n.fstream) HIP_OK(hipMalloc(&n.fstream, kStreamBytesF16Xyz));     // the largest of the four streams
     if (!n.fcst) HIP_OK(hipMalloc((void**)&n.fcst, kConstBytes));
-    // the fine network's chain also produces the gradient w.r.t. the xyz encoding when the sampler is differentiated
-    n.bdx = (&n == &t->net[1]) && t->cfg.sampler_gradient != 0;
+    // the fine network's chain also produces the gradient w.r.t. the xyz encoding when the sampler is differentiated; both
+    // networks' chains do while ray gradients are switched on
+    n.bdx = t->ray_grads || ((&n == &t->net[1]) && t->cfg.sampler_gradient != 0);
     int32_t*& bi = t->bidx[n.bdx ? 1 : 0];
     if (!bi) {
         std::vector<int32_t> idx(kBwdStreamBytes / 2);
@@ -553,10 +559,18 @@ void dgrad_xyz(nerf_ctx* c, const float* G, const float* Wrows, float* dA0, long
 // add dL/dz through the sample positions (d_z must already hold the compositing part).  For a culled pass (TPass::cull.rows >= 0)
 // Mp is the kept rows' padded count, Graw is TrainState::Gc and d_z gets its addition at the kept samples only.
 
+// rays: where the pass adds its share of dL/d(rays_orig), dL/d(rays_dirs) ((N, 4) on the device, zeroed by the caller; either
+// may be null) -- the fused trainer with encoding tiles only (nerf_train_set_ray_gradients refuses the reference trainer).
+struct RayGrads {
+    float *d_o = nullptr, *d_d = nullptr;
+    bool any() const { return d_o || d_d; }
+};
+
 // The fused trainer: ONE kernel for the whole data-gradient chain (mlp_bwd_f16x3.hip: the gradient stays on the lane from
 // layer to layer; every D_l is written once, with max|D_l| in the pass's gmax slots), then the weight gradients from the
 // stashed activations and the D_l.
-int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z) {
+int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, const float* o, const float* dirs, float* d_z,
+                   const RayGrads& rays = RayGrads()) {
     TNet& n = t->net[which];
     TPass& p = t->pass[which];
     const long long Mp = net_rows_padded(p, d);
@@ -616,6 +630,22 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
         // zero gradient
         launch_pe_bwd(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S, pe_layout_lx(c->cfg.n_pos_enc_xyz),
                       cull_mask(p), cull_first(p), d_z, c->stream, true);
+    }
+    if (rays.any()) {
+        if (!n.bdx) return fail("internal: ray gradients need the backward stream with encoding tiles");
+        const OptState* st = t->mixed ? (const OptState*)t->opt.p : nullptr;      // the chain carried the loss scale
+        launch_ray_position_grads(b.dx_ptr[0], b.dx_ptr[1], o, dirs, (const float*)p.z.p, d.N, d.S,
+                                  pe_layout_lx(c->cfg.n_pos_enc_xyz), cull_mask(p), cull_first(p), st, rays.d_o, rays.d_d,
+                                  c->stream, true);
+        if (rays.d_d && !xyz) {
+            // the direction encoding is rows 256.. of the inputs of layer 8 and of the sigma head (10): layer_table's K_real
+            const TLayer &L8 = n.L[8], &L9 = n.L[9], &L10 = n.L[10];
+            if (L8.K_real - 256 != 2 * c->cfg.n_pos_enc_dir * (c->cfg.n_angles + 1) || L10.K_real != L8.K_real || L8.N_real != 128)
+                return fail("internal: the layer table does not match the view-direction encoding");
+            launch_view_dir_grads(Graw, p.H9.p, t->mixed, n.blob + L9.w_off, n.blob + L8.w_off + (size_t)256 * L8.N_real,
+                                  n.blob + L10.w_off + 256, dirs, d.N, d.S, c->cfg.n_angles, c->cfg.n_pos_enc_dir, cull_mask(p),
+                                  cull_first(p), c->cfg.leaky_relu_alpha, st, rays.d_d, c->stream);
+        }
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -682,7 +712,7 @@ int backward_reference(nerf_ctx* c, TrainState* t, int which, const PassDims& d,
 // dL/d(rgb) of pass `which` [+ dL/d(weights) from the sampler, d_wext] -> Graw through the compositing -> the network's
 // gradient blob [+ dL/dz into d_z]
 int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDims& pd, const float* o, const float* dirs,
-                            const float* d_rgb, const float* d_wext, float* d_z) {
+                            const float* d_rgb, const float* d_wext, float* d_z, const RayGrads& rays = RayGrads()) {
     const TPass& p = t->pass[which];
     float* Graw = (float*)t->Graw.p;
     HIP_OK(hipMemsetAsync(Graw + pd.M * 4, 0, (pd.Mp - pd.M) * 4 * sizeof(float), c->stream));
@@ -700,7 +730,7 @@ int composite_backward_pass(nerf_ctx* c, TrainState* t, int which, const PassDim
         launch_graw_gather(Graw, pd.M, p.cull.rows, Mp, cull_mask(p), cull_first(p), (float*)t->Gc.p, c->stream);
     }
     return t->reference ? backward_reference(c, t, which, pd, o, dirs, d_z)
-                        : backward_fused(c, t, which, pd, o, dirs, d_z);
+                        : backward_fused(c, t, which, pd, o, dirs, d_z, rays);
 }
 
 // the sample counts of a training call; *fine: whether the fine pass runs
@@ -910,11 +940,14 @@ int ensure_render_bwd(nerf_ctx* c, TrainState* t, const PassDims& dc, const Pass
 // Runs under a SlotLease (which clears acc_grads on the way out).
 int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const PassDims& df, bool fine, const float* o,
                          const float* d, const float* uf, uint64_t seed, long long ray_base, const float* dr,
-                         bool accumulate, const OutputGrads& x = OutputGrads()) {
+                         bool accumulate, const OutputGrads& x = OutputGrads(), const RayGrads& rays = RayGrads()) {
     const size_t f = sizeof(float);
     const long long N = dc.N;
     const int Sc = dc.S, Sf = df.S - dc.S;
     const bool through_sampler = fine && t->cfg.sampler_gradient != 0;
+    // the ray gradients of this call: stored, never accumulated; every pass below that runs adds its share
+    if (rays.d_o) HIP_OK(hipMemsetAsync(rays.d_o, 0, N * 4 * f, c->stream));
+    if (rays.d_d) HIP_OK(hipMemsetAsync(rays.d_d, 0, N * 4 * f, c->stream));
     // the networks this call computes gradients for: the fine one through its merged pass, the coarse one through the
     // sampler (or, without a fine network, through its own rgb)
     const bool computes[2] = {!fine || through_sampler, fine};
@@ -954,10 +987,10 @@ int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const P
 
     const TPass& pc = t->pass[0];
     if (!fine) {
-        if (int q = composite_backward_pass(c, t, 0, dc, o, d, dr, g_w, nullptr)) return q;     // (its depths are data)
+        if (int q = composite_backward_pass(c, t, 0, dc, o, d, dr, g_w, nullptr, rays)) return q;     // (its depths are data)
     } else {
         float* d_zm = through_sampler ? (float*)t->d_zm.p : nullptr;
-        if (int q = composite_backward_pass(c, t, 1, df, o, d, dr, g_w, d_zm)) return q;
+        if (int q = composite_backward_pass(c, t, 1, df, o, d, dr, g_w, d_zm, rays)) return q;
         // the depths' own cotangents join the pass's d_z AFTER the compositing backward, which stores there (as the
         // distortion loss's dL/dz does in gradients_impl); only the sampler consumes them
         if (d_zm && (x.d_depth || x.d_z))
@@ -971,7 +1004,7 @@ int render_backward_core(nerf_ctx* c, TrainState* t, const PassDims& dc, const P
             // the coarse network: no direct rgb term, only dL/d(weights_coarse) from the sampler
             HIP_OK(hipMemsetAsync(t->zero_rgb.p, 0, N * 3 * f, c->stream));
             if (int q = composite_backward_pass(c, t, 0, dc, o, d, (const float*)t->zero_rgb.p, (const float*)t->d_wext.p,
-                                                nullptr))
+                                                nullptr, rays))
                 return q;
         } else if (!accumulate) {
             HIP_OK(hipMemsetAsync(t->net[0].grad, 0, t->nblob * f, c->stream));   // render() does not depend on it
@@ -1097,7 +1130,9 @@ int render_forward_impl(nerf_ctx* c, int slot, const float* rays_o, const float*
 }
 
 // g: the caller's cotangents (nerf_render_grads; at least one is set).  nerf_train_render_backward passes d_rgb alone.
-int render_backward_impl(nerf_ctx* c, int slot, const nerf_render_grads& g, bool accumulate, int mem) {
+// d_rays_orig, d_rays_dirs: the caller's (N, 4) ray-gradient outputs (nerf_train_render_backward_rays), null otherwise.
+int render_backward_impl(nerf_ctx* c, int slot, const nerf_render_grads& g, bool accumulate, int mem,
+                         float* d_rays_orig = nullptr, float* d_rays_dirs = nullptr) {
     TrainState* t = c->train;
     if (!t) return fail("nerf_train_begin has not been called");
     if (slot < 0 || (size_t)slot >= t->slots.size() || !t->slots[slot].valid)
@@ -1113,12 +1148,17 @@ int render_backward_impl(nerf_ctx* c, int slot, const nerf_render_grads& g, bool
     x.d_depth = st.in(t->in_dd, g.d_depth, s.N * sizeof(float));
     x.d_weights = st.in(t->in_dw, g.d_weights, ns);
     x.d_z = st.in(t->in_dz, g.d_z, ns);
+    RayGrads rays;
+    rays.d_o = st.out(t->out_ro, d_rays_orig, s.N * 4 * sizeof(float));
+    rays.d_d = st.out(t->out_rd, d_rays_dirs, s.N * 4 * sizeof(float));
     if (st.err) return st.err;
     if (int r = ensure_render_bwd(c, t, dc, df, fine, accumulate, x.d_depth || x.d_weights)) return r;
     s.valid = false;                              // consumed, whatever happens below
     SlotLease lease(c, t, &s);
-    return render_backward_core(c, t, dc, df, fine, (const float*)s.o.p, (const float*)s.d.p,
-                                s.has_uf ? (const float*)s.u_f.p : nullptr, s.seed, s.ray_base, dr, accumulate, x);
+    if (int r = render_backward_core(c, t, dc, df, fine, (const float*)s.o.p, (const float*)s.d.p,
+                                     s.has_uf ? (const float*)s.u_f.p : nullptr, s.seed, s.ray_base, dr, accumulate, x, rays))
+        return r;
+    return rays.any() ? st.finish() : 0;      // (a host caller's ray gradients leave here; the blobs leave through copy_out)
 }
 
 // The outputs of a gradient / render call, each only if the caller asks for it: rgb (N x 3) and the two gradient blobs,
@@ -1196,7 +1236,7 @@ void train_free(nerf_ctx* c) {
     DevBuf* bs[] = {&t->Gc, &t->Ga, &t->Gb, &t->G9, &t->Graw, &t->dsig, &t->dA0, &t->partial, &t->d_rgb, &t->d_wext, &t->d_zf, &t->tgt,
                     &t->o, &t->d, &t->u_c, &t->u_f, &t->scal, &t->gmax, &t->z_new, &t->d_zm, &t->zero_rgb, &t->opt,
                     &t->gsave[0], &t->gsave[1], &t->macc, &t->d_wdist, &t->dist_ray, &t->dacc, &t->depth, &t->g_wfold, &t->in_dd,
-                    &t->in_dw, &t->in_dz};
+                    &t->in_dw, &t->in_dz, &t->out_ro, &t->out_rd};
     for (DevBuf* b : bs) free_buf(*b);
     delete t;
     c->train = nullptr;
@@ -1453,6 +1493,60 @@ int nerf_train_render_backward_outputs(nerf_ctx* c, int32_t slot, const nerf_ren
     if (grad_fine && !fine) return fail("grad_fine requested but slot %d ran no fine pass", slot);   // (before it is consumed)
     if (int r = render_backward_impl(c, slot, *g, accumulate != 0, mem)) return r;
     return copy_out(c, mem, c->train->slots[slot].Sf, grad_coarse, grad_fine);
+}
+
+int nerf_train_set_ray_gradients(nerf_ctx* c, int32_t on) {
+    ENTER(c);
+    TrainState* t = c->train;
+    if (!t) return fail("nerf_train_begin has not been called");
+    if (on && t->reference)
+        return fail("ray gradients run on the fused trainer only: unset NERF_TRAIN_FORWARD");
+    if (t->ray_grads == (on != 0)) return 0;
+    t->ray_grads = on != 0;
+    // the encoding tiles are a property of how a network's backward stream is packed: re-pack both from the master weights
+    // (the kept activations of the slots do not depend on it)
+    for (int w = 0; w < 2; ++w) {
+        TNet& n = t->net[w];
+        if (!n.present) continue;
+        if (int r = ensure_fused(c, t, n)) return r;
+        if (int r = relayout_net(c, n)) return r;
+    }
+    return 0;
+}
+
+int nerf_train_render_backward_rays(nerf_ctx* c, int32_t slot, const nerf_render_grads* g, int32_t accumulate, float* grad_coarse,
+                                    float* grad_fine, float* d_rays_orig, float* d_rays_dirs, int mem) {
+    ENTER(c);
+    if (!g) return fail("nerf_render_grads is NULL");
+    if (!g->d_rgb && !g->d_depth && !g->d_weights && !g->d_z)
+        return fail("all four cotangents of nerf_render_grads are NULL: nothing to differentiate");
+    if (c->train && !c->train->ray_grads)
+        return fail("ray gradients are switched off: call nerf_train_set_ray_gradients(ctx, 1) first");
+    const bool fine = c->train && slot >= 0 && (size_t)slot < c->train->slots.size() && c->train->slots[slot].Sf > 0;
+    if (grad_fine && !fine) return fail("grad_fine requested but slot %d ran no fine pass", slot);   // (before it is consumed)
+    if (int r = render_backward_impl(c, slot, *g, accumulate != 0, mem, d_rays_orig, d_rays_dirs)) return r;
+    return copy_out(c, mem, c->train->slots[slot].Sf, grad_coarse, grad_fine);
+}
+
+int nerf_ray_position_grads(nerf_ctx* c, const float* d_points, const float* z, int64_t N, int32_t S, float* d_rays_orig,
+                            float* d_rays_dirs, int mem) {
+    ENTER(c);
+    if (!d_points) return fail("d_points is NULL");
+    if (!z) return fail("z is NULL");
+    if (N < 0) return fail("bad N = %lld (need N >= 0)", (long long)N);
+    if (S < 1) return fail("bad S = %d (need S >= 1)", S);
+    const size_t f = sizeof(float);
+    Staging st(c, mem);
+    const float* dp = st.in(c->b_in0, d_points, (size_t)N * S * 3 * f);
+    const float* zz = st.in(c->b_in1, z, (size_t)N * S * f);
+    float* go = st.out(c->b_out[0], d_rays_orig, (size_t)N * 4 * f);
+    float* gd = st.out(c->b_out[1], d_rays_dirs, (size_t)N * 4 * f);
+    if (st.err) return st.err;
+    if (go && N > 0) HIP_OK(hipMemsetAsync(go, 0, (size_t)N * 4 * f, c->stream));
+    if (gd && N > 0) HIP_OK(hipMemsetAsync(gd, 0, (size_t)N * 4 * f, c->stream));
+    launch_ray_position_reduce(dp, zz, N, S, go, gd, c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
 }
 
 int nerf_render_output_grads(nerf_ctx* c, const float* weights, const float* z, int64_t N, int32_t S, const float* d_depth,

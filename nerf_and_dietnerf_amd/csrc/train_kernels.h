@@ -141,6 +141,20 @@ void launch_head_bwd(const float* Graw, const float* W9 /*[128][Np9] row-major, 
 void launch_pe_bwd(const float* dA0, const float* dA0b /* added to dA0, or null */, const float* o, const float* d,
                    const float* z, long long N, int S, int lx, const uint8_t* mask, const uint32_t* first, float* d_z,
                    hipStream_t s, bool frag = false);     // frag: dA0 / dA0b are fragment-major (the fused backward chain's dx buffers)
+// Ray gradients of one pass (nerf_train_render_backward_rays), one ray per wavefront, fixed order, no atomics; both ADD into
+// d_o / d_d ((N, 4), component 3 untouched; either nullable) times st->inv_scale (st nullable: 1).
+// The per-ray counterpart of launch_pe_bwd, same inputs: d_o[r] += sum_s dL/dp_s, d_d[r] += sum_s z_s dL/dp_s over the kept samples
+void launch_ray_position_grads(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N,
+                               int S, int lx, const uint8_t* mask, const uint32_t* first, const OptState* st, float* d_o,
+                               float* d_d, hipStream_t s, bool frag = false);
+// ... its reduction stage alone, dL/dp supplied: d_points (N, S, 3)
+void launch_ray_position_reduce(const float* d_points, const float* z, long long N, int S, float* d_o, float* d_d, hipStream_t s);
+// The view-direction input of layers 8 and 10 (n_angles 1 or 2, ld_oct 1..4 octaves): Graw (rows x 4) and the stashed H9
+// (fragment-major, pitch 128; fp16 elements with h9_f16) of the pass's network rows, W9 (128, 3), W8d (ddir, 128) and Wsd
+// (ddir): the rgb head and the direction rows of layers 8 and 10 in the weight blob.  d_d[r][component read] += the gradient.
+void launch_view_dir_grads(const float* Graw, const void* H9, bool h9_f16, const float* W9, const float* W8d, const float* Wsd,
+                           const float* d, long long N, int S, int n_angles, int ld_oct, const uint8_t* mask,
+                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s);
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
                          hipStream_t s);
 // The fold of render()'s depth / weights / z cotangents into one pass's dL/dw and dL/dz (weights, z: N x S of that pass;

@@ -1566,7 +1566,39 @@ void launch_head_bwd(const float* Graw, const float* W9, const float* H9, long l
 // Its encoding gradient is row m = t; for a culled pass (mask / first non-null: SampleCompaction) row m = the slot of a
 // kept sample (nerf_device.h::sample_slot), and a culled sample leaves d_z alone.
 // ------------------------------------------------------------------------------------------------
+// dL/dp of one sample (three floats) from row m of its encoding gradient: what both kernels below start from.  The gradient
+// may come in two parts (fused backward: through layer 4 and through layer 0).  frag: the (Mp, 64) rows are fragment-major
+// (frag_layout.h::frag_index; written by the fused backward chain): neighbouring threads read neighbouring 16-byte slots.
 template <int LX>      // octaves of the gradient rows' layout
+__device__ __forceinline__ void pe_point_grad(const float* __restrict__ dA0, const float* __restrict__ dA0b, long long m, int frag,
+                                              const float p[3], float dp[3]) {
+    const float kPi = 3.1415927410125732f;
+    constexpr int Q = (3 * (1 + 2 * LX) + 3) / 4;    // float4s covering the 3 + 6 LX encoding columns (rows are 64 floats)
+    static_assert(4 * Q <= kXyzPad, "the encoding columns fit a gradient row");
+    float g[4 * Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {                  // 33 floats (LX 5) read as 9 float4, 63 (LX 10) as 16: no overrun
+        const long long e = frag ? frag_index(m, 4 * q, kXyzPad) : m * kXyzPad + 4 * q;
+        float4 v = *reinterpret_cast<const float4*>(dA0 + e);
+        if (dA0b) { const float4 w = *reinterpret_cast<const float4*>(dA0b + e); v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
+        g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        constexpr int XC = 1 + 2 * LX;
+        float v = g[c * XC];
+#pragma unroll
+        for (int k = 0; k < LX; ++k) {
+            const float f = kPi * (float)(1 << k);
+            const float th = __fmul_rn(p[c], f);
+            const float sn = sin_shifted(th, 0), cs = sin_shifted(th, 1);
+            v += (cs * g[c * XC + 1 + 2 * k] - sn * g[c * XC + 2 + 2 * k]) * f;
+        }
+        dp[c] = v;
+    }
+}
+
+template <int LX>
 __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __restrict__ dA0b /* second part to add, or null */,
                               const float* __restrict__ o, const float* __restrict__ d,
                               const float* __restrict__ z, long long total, int S, const uint8_t* __restrict__ mask,
@@ -1581,38 +1613,15 @@ __global__ void pe_bwd_kernel(const float* __restrict__ dA0, const float* __rest
     }
     const long long r = t / S;
     const float zz = z[t];
-    const float kPi = 3.1415927410125732f;
     const float4 oo = reinterpret_cast<const float4*>(o)[r], dd = reinterpret_cast<const float4*>(d)[r];
     const float p[3] = {__fadd_rn(oo.x, __fmul_rn(dd.x, zz)), __fadd_rn(oo.y, __fmul_rn(dd.y, zz)),
                         __fadd_rn(oo.z, __fmul_rn(dd.z, zz))};
     const float dv[3] = {dd.x, dd.y, dd.z};
-    // the encoding gradient may come in two parts (fused backward: through layer 4 and through layer 0)
-    // frag: the (Mp, 64) rows are fragment-major (frag_layout.h::frag_index; written by the fused backward chain):
-    // neighbouring threads read neighbouring 16-byte slots
-    constexpr int Q = (3 * (1 + 2 * LX) + 3) / 4;    // float4s covering the 3 + 6 LX encoding columns (rows are 64 floats)
-    static_assert(4 * Q <= kXyzPad, "the encoding columns fit a gradient row");
-    float g[4 * Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {                  // 33 floats (LX 5) read as 9 float4, 63 (LX 10) as 16: no overrun
-        const long long e = frag ? frag_index(m, 4 * q, kXyzPad) : m * kXyzPad + 4 * q;
-        float4 v = *reinterpret_cast<const float4*>(dA0 + e);
-        if (dA0b) { const float4 w = *reinterpret_cast<const float4*>(dA0b + e); v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w; }
-        g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-    }
+    float dp[3];
+    pe_point_grad<LX>(dA0, dA0b, m, frag, p, dp);
     float acc = 0.f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        constexpr int XC = 1 + 2 * LX;
-        float dp = g[c * XC];
-#pragma unroll
-        for (int k = 0; k < LX; ++k) {
-            const float f = kPi * (float)(1 << k);
-            const float th = __fmul_rn(p[c], f);
-            const float sn = sin_shifted(th, 0), cs = sin_shifted(th, 1);
-            dp += (cs * g[c * XC + 1 + 2 * k] - sn * g[c * XC + 2 + 2 * k]) * f;
-        }
-        acc += dp * dv[c];
-    }
+    for (int c = 0; c < 3; ++c) acc += dp[c] * dv[c];
     d_z[t] += acc;
 }
 
@@ -1685,6 +1694,208 @@ void launch_pe_bwd(const float* dA0, const float* dA0b, const float* o, const fl
         NERF_PE_BWD(6) NERF_PE_BWD(7) NERF_PE_BWD(8) NERF_PE_BWD(9) NERF_PE_BWD(10)
     }
 #undef NERF_PE_BWD
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ray gradients (nerf_train_render_backward_rays): what a pass's backward leaves for the rays it was run on.
+//   position term: p_s = o + d z_s, so dL/do = sum_s dL/dp_s and dL/dd = sum_s z_s dL/dp_s (the depths are values here; what
+//     reaches them travels through d_z and the sampler) -- the per-ray counterpart of pe_bwd_kernel, same inputs;
+//   view-direction term: the direction encoding is a second input of layers 8 and 10.
+// One ray per wavefront: its samples are dealt to the lanes (each lane adds its own in ascending order), the lanes' sums
+// meet in a fixed shuffle butterfly and one lane adds them into d_o / d_d -- no atomics, the same inputs give the same bits
+// on every run.  The kernels ADD (times st->inv_scale, st nullable: 1), so the passes of one call land in the same arrays.
+// ------------------------------------------------------------------------------------------------
+constexpr int kRayWaves = 4;       // rays per workgroup
+
+__device__ __forceinline__ void ray_sums_add(float so[3], float sd[3], int lane, long long r, const OptState* __restrict__ st,
+                                             float* __restrict__ d_o, float* __restrict__ d_d) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            so[c] += __shfl_xor(so[c], off);
+            sd[c] += __shfl_xor(sd[c], off);
+        }
+    if (lane != 0) return;
+    const float inv = st ? st->inv_scale : 1.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (d_o) d_o[r * 4 + c] += so[c] * inv;
+        if (d_d) d_d[r * 4 + c] += sd[c] * inv;
+    }
+}
+
+template <int LX>
+__global__ __launch_bounds__(64 * kRayWaves) void ray_pos_grad_kernel(
+    const float* __restrict__ dA0, const float* __restrict__ dA0b, const float* __restrict__ o, const float* __restrict__ d,
+    const float* __restrict__ z, long long N, int S, const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first,
+    const OptState* __restrict__ st, float* __restrict__ d_o, float* __restrict__ d_d, int frag) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * kRayWaves + (threadIdx.x >> 6);
+    if (r >= N) return;
+    const float4 oo = reinterpret_cast<const float4*>(o)[r], dd = reinterpret_cast<const float4*>(d)[r];
+    float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
+    for (int s = lane; s < S; s += 64) {
+        const long long t = r * S + s;
+        long long m = t;
+        if (mask) {
+            size_t slot;
+            if (!sample_slot(mask, first, t, &slot)) continue;
+            m = (long long)slot;
+        }
+        const float zz = z[t];
+        const float p[3] = {__fadd_rn(oo.x, __fmul_rn(dd.x, zz)), __fadd_rn(oo.y, __fmul_rn(dd.y, zz)),
+                            __fadd_rn(oo.z, __fmul_rn(dd.z, zz))};
+        float dp[3];
+        pe_point_grad<LX>(dA0, dA0b, m, frag, p, dp);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            so[c] += dp[c];
+            sd[c] += zz * dp[c];
+        }
+    }
+    ray_sums_add(so, sd, lane, r, st, d_o, d_d);
+}
+
+// the reduction alone, dL/dp supplied: d_points (N, S, 3)
+__global__ __launch_bounds__(64 * kRayWaves) void ray_pos_reduce_kernel(const float* __restrict__ d_points,
+                                                                        const float* __restrict__ z, long long N, int S,
+                                                                        float* __restrict__ d_o, float* __restrict__ d_d) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * kRayWaves + (threadIdx.x >> 6);
+    if (r >= N) return;
+    float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f};
+    for (int s = lane; s < S; s += 64) {
+        const long long t = r * S + s;
+        const float zz = z[t];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float dp = d_points[t * 3 + c];
+            so[c] += dp;
+            sd[c] += zz * dp;
+        }
+    }
+    ray_sums_add(so, sd, lane, r, nullptr, d_o, d_d);
+}
+
+void launch_ray_position_grads(const float* dA0, const float* dA0b, const float* o, const float* d, const float* z, long long N,
+                               int S, int lx, const uint8_t* mask, const uint32_t* first, const OptState* st, float* d_o,
+                               float* d_d, hipStream_t s, bool frag) {
+    if (N <= 0 || S <= 0 || (!d_o && !d_d)) return;
+    const dim3 grid((unsigned)((N + kRayWaves - 1) / kRayWaves)), block(64 * kRayWaves);
+    const int fr = frag ? 1 : 0;
+#define NERF_RAY_POS(L) \
+    case L: hipLaunchKernelGGL(ray_pos_grad_kernel<L>, grid, block, 0, s, dA0, dA0b, o, d, z, N, S, mask, first, st, d_o, d_d, fr); break;
+    switch (lx) {      // check_cfg: 1..10
+        NERF_RAY_POS(1) NERF_RAY_POS(2) NERF_RAY_POS(3) NERF_RAY_POS(4) NERF_RAY_POS(5)
+        NERF_RAY_POS(6) NERF_RAY_POS(7) NERF_RAY_POS(8) NERF_RAY_POS(9) NERF_RAY_POS(10)
+    }
+#undef NERF_RAY_POS
+}
+
+void launch_ray_position_reduce(const float* d_points, const float* z, long long N, int S, float* d_o, float* d_d, hipStream_t s) {
+    if (N <= 0 || S <= 0 || (!d_o && !d_d)) return;
+    hipLaunchKernelGGL(ray_pos_reduce_kernel, dim3((unsigned)((N + kRayWaves - 1) / kRayWaves)), dim3(64 * kRayWaves), 0, s,
+                       d_points, z, N, S, d_o, d_d);
+}
+
+// View-direction term of one pass.  Per kept sample row m the rgb head's backward is recomputed as head_bwd_kernel does it,
+//     G9[m][j] = (sum_c Graw[m][c] W9[j][c]) * LeakyReLU'(H9[m][j]),
+// and the gradient of layer 8's direction-encoding inputs is G9 . W8[dir rows]^T + d_sigma * W_sigma[dir rows].  That is
+// linear in (G9, d_sigma) and the direction is the same for every sample of a ray, so the wave first sums G9 (128) and
+// d_sigma over the ray's samples -- 32 samples per round, lane = 32 * half + sample, four consecutive features per lane: for
+// each 8-feature group the wave reads one contiguous 1 KiB (fp32) / 512 B (fp16) run of the fragment-major H9 stash -- then
+// multiplies once by the weights' direction rows and applies the encoding backward once: lane 8 c + w holds encoding column
+// w (sin_0, cos_0, sin_1, ...) of component c, and the columns of a component meet in a 3-step butterfly.
+// W9: (128, 3), W8d: (ddir, 128), Wsd: (ddir) -- rows 256.. of layers 8 and 10 in the blob (Keras order).
+template <bool F16>
+__global__ __launch_bounds__(64 * kRayWaves) void view_dir_grad_kernel(
+    const float* __restrict__ Graw, const void* __restrict__ H9, const float* __restrict__ W9, const float* __restrict__ W8d,
+    const float* __restrict__ Wsd, const float* __restrict__ d, long long N, int S, int n_angles, int ld_oct,
+    const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first, float alpha, const OptState* __restrict__ st,
+    float* __restrict__ d_d) {
+    __shared__ float w9[128 * 3];
+    for (int i = threadIdx.x; i < 128 * 3; i += 64 * kRayWaves) w9[i] = W9[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+    const long long r = (long long)blockIdx.x * kRayWaves + (threadIdx.x >> 6);
+    if (r >= N) return;
+    float acc[64];      // acc[4 q + e]: feature 8 q + 4 h + e
+#pragma unroll
+    for (int i = 0; i < 64; ++i) acc[i] = 0.f;
+    float sig = 0.f;
+    for (int s = j; s < S; s += 32) {
+        const long long t = r * S + s;
+        long long m = t;
+        if (mask) {
+            size_t slot;
+            if (!sample_slot(mask, first, t, &slot)) continue;
+            m = (long long)slot;
+        }
+        const float4 g = reinterpret_cast<const float4*>(Graw)[m];
+        if (h == 0) sig += g.w;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const long long e = frag_index(m, 8 * q + 4 * h, 128);
+            float hv[4];
+            if constexpr (F16) {
+                const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(H9) + e);
+                const h2v lo = __builtin_bit_cast(h2v, v.x), hi = __builtin_bit_cast(h2v, v.y);
+                hv[0] = (float)lo[0]; hv[1] = (float)lo[1]; hv[2] = (float)hi[0]; hv[3] = (float)hi[1];
+            } else {
+                const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(H9) + e);
+                hv[0] = v.x; hv[1] = v.y; hv[2] = v.z; hv[3] = v.w;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int f = 8 * q + 4 * h + u;
+                const float v = g.x * w9[f * 3 + 0] + g.y * w9[f * 3 + 1] + g.z * w9[f * 3 + 2];
+                acc[4 * q + u] += hv[u] > 0.f ? v : alpha * v;
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 32; off <<= 1) {      // the 32 samples of a half meet; every lane of the half ends with the sums
+#pragma unroll
+        for (int i = 0; i < 64; ++i) acc[i] += __shfl_xor(acc[i], off);
+        sig += __shfl_xor(sig, off);
+    }
+    sig = __shfl(sig, 0);
+    // lane 8 c + w (of either half): encoding column k = 2 ld_oct c + w; each half multiplies its own 64 features
+    const int c = j >> 3, w = j & 7;
+    const bool live = c < n_angles + 1 && w < 2 * ld_oct;
+    const int k = live ? 2 * ld_oct * c + w : 0;
+    float part = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const float4 wv = *reinterpret_cast<const float4*>(W8d + (size_t)k * 128 + 8 * q + 4 * h);
+        part += acc[4 * q] * wv.x + acc[4 * q + 1] * wv.y + acc[4 * q + 2] * wv.z + acc[4 * q + 3] * wv.w;
+    }
+    part += __shfl_xor(part, 32);
+    const float gk = part + sig * Wsd[k];
+    // encoding column w of component c is sin (w even) or cos (w odd) of v * pi 2^(w / 2), v the direction component read
+    const int comp = n_angles == 2 ? c : (c == 0 ? 0 : 2);
+    const float v = live ? d[r * 4 + comp] : 0.f;
+    const float fq = 3.1415927410125732f * (float)(1 << (w >> 1));
+    const float th = __fmul_rn(v, fq);
+    float term = ((w & 1) ? -sin_shifted(th, 0) : sin_shifted(th, 1)) * gk * fq;
+    if (!live) term = 0.f;
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) term += __shfl_xor(term, off);
+    if (h == 0 && w == 0 && c < n_angles + 1) d_d[r * 4 + comp] += term * (st ? st->inv_scale : 1.0f);
+}
+
+void launch_view_dir_grads(const float* Graw, const void* H9, bool h9_f16, const float* W9, const float* W8d, const float* Wsd,
+                           const float* d, long long N, int S, int n_angles, int ld_oct, const uint8_t* mask,
+                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s) {
+    if (N <= 0 || S <= 0 || !d_d || n_angles < 1 || n_angles > 2 || ld_oct < 1 || ld_oct > 4) return;
+    const dim3 grid((unsigned)((N + kRayWaves - 1) / kRayWaves)), block(64 * kRayWaves);
+    if (h9_f16)
+        hipLaunchKernelGGL(view_dir_grad_kernel<true>, grid, block, 0, s, Graw, H9, W9, W8d, Wsd, d, N, S, n_angles, ld_oct, mask,
+                           first, alpha, st, d_d);
+    else
+        hipLaunchKernelGGL(view_dir_grad_kernel<false>, grid, block, 0, s, Graw, H9, W9, W8d, Wsd, d, N, S, n_angles, ld_oct, mask,
+                           first, alpha, st, d_d);
 }
 
 // ------------------------------------------------------------------------------------------------

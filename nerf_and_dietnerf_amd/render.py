@@ -286,6 +286,8 @@ class Context:
         self._auto_unchecked = False  # "auto": device-resident calls since the last look at the counter
         self.auto_fallbacks = 0      # "auto": calls that were re-rendered in exact fp32
         self._slot_fine = {}         # train_render_forward slots that ran a fine pass
+        self._slot_rays = {}         # ... and how many rays each holds
+        self._train_ray_gradients = False   # train_set_ray_gradients
         self.sampling, self.ray_space, self.ndc_near_plane = "linear", "world", 1.0   # what nerf_ctx_create leaves
         self.scene_box = None        # ((lo), (hi)) of set_scene_box
         self.grid_resolution = 0     # R of the occupancy grid (0: none)
@@ -748,6 +750,7 @@ class Context:
         cfg = NerfTrainConfig(learning_rate, beta_1, beta_2, epsilon, 1 if sampler_gradient else 0,
                               1 if mixed_float16 else 0, float(initial_loss_scale), int(dynamic_growth_steps))
         _lib.check(self.lib.nerf_train_begin(self.h, C.byref(cfg)))
+        self._train_ray_gradients = False      # (nerf_train_begin leaves the switch off)
 
     def train_loss_scale(self) -> Tuple[float, int, int]:
         """(current loss scale, optimizer steps applied, steps skipped) -- (1, n, 0) under the fp32 policy."""
@@ -862,6 +865,7 @@ class Context:
         _lib.check(self.lib.nerf_train_render_forward(self.h, int(slot), po, pd, n, n_c, n_f, uc, uf, seed, ray_base, prgb,
                                                       arr.mem))
         self._slot_fine[int(slot)] = n_f > 0 and self.loaded[1]
+        self._slot_rays[int(slot)] = n
         return rgb
 
     def train_render_backward(self, slot: int, d_rgb, accumulate=False, want_blobs=True):
@@ -900,24 +904,62 @@ class Context:
         _lib.check(self.lib.nerf_train_render_forward_outputs(self.h, int(slot), po, pd, n, n_c, n_f, uc, uf, seed, ray_base,
                                                               C.byref(o), arr.mem))
         self._slot_fine[int(slot)] = fine
+        self._slot_rays[int(slot)] = n
         return {k: v[0] for k, v in got.items()}
 
+    def train_set_ray_gradients(self, on) -> None:
+        """Switches the ray gradients of ``train_render_backward_outputs(..., want_rays=True)`` and of ``render_with_grad`` on
+        or off on a running trainer (nerf_train_set_ray_gradients has the rules): both networks' backward streams are
+        re-packed with or without the encoding tiles.  Off by default, and off again after every ``train_begin``; while it
+        is off nothing changes.  The fused trainer only."""
+        _lib.check(self.lib.nerf_train_set_ray_gradients(self.h, int(bool(on))))
+        self._train_ray_gradients = bool(on)
+
+    @property
+    def train_ray_gradients(self) -> bool:
+        """Whether train_set_ray_gradients is on."""
+        return self._train_ray_gradients
+
     def train_render_backward_outputs(self, slot: int, d_rgb=None, d_depth=None, d_weights=None, d_z=None, accumulate=False,
-                                      want_blobs=True):
+                                      want_blobs=True, want_rays=False):
         """``train_render_backward`` with a cotangent for every output of ``train_render_forward_outputs``
         (nerf_train_render_backward_outputs): any of ``d_rgb`` (N,3), ``d_depth`` (N,), ``d_weights``, ``d_z`` (N,S) may be
         None (= zero), not all four -> (grad_coarse blob, grad_fine blob | None) copies (or (None, None)).  With ``d_rgb``
         alone it is ``train_render_backward``, bit for bit.  ``d_z`` and the depth's own dependence on z reach the networks
         only with a fine pass under ``sampler_gradient`` (through the n_f new depths; the coarse depths are data).  Under
-        mixed_float16 pass UNSCALED cotangents: the library applies the loss scale.  Consumes the slot."""
+        mixed_float16 pass UNSCALED cotangents: the library applies the loss scale.  Consumes the slot.
+        ``want_rays=True`` (nerf_train_render_backward_rays; needs ``train_set_ray_gradients(True)``) -> (grad_coarse,
+        grad_fine, d_rays_orig, d_rays_dirs): the gradients of the same scalar with respect to the (N,4) rays the slot's
+        forward received, component 3 zero -- through the sample points of every pass that takes part and through the
+        view-direction input; the coarse depths, the bounds and what a box or grid derives from the ray are data."""
         arr = self._arrays(d_rgb, d_depth, d_weights, d_z)
         g = _lib.NerfRenderGrads(arr.inp(d_rgb), arr.inp(d_depth), arr.inp(d_weights), arr.inp(d_z))
         fine = self._slot_fine.get(int(slot), False)
         gc, pgc = arr.out((self.blob_size(),)) if want_blobs else (None, None)
         gf, pgf = arr.out((self.blob_size(),)) if want_blobs and fine else (None, None)
+        if want_rays:
+            n = self._slot_rays.get(int(slot))
+            if n is None:
+                raise RuntimeError(f"slot {int(slot)} holds no forward pass of train_render_forward_outputs")
+            g_o, pgo = arr.out((n, 4))
+            g_d, pgd = arr.out((n, 4))
+            _lib.check(self.lib.nerf_train_render_backward_rays(self.h, int(slot), C.byref(g), 1 if accumulate else 0, pgc, pgf,
+                                                                pgo, pgd, arr.mem))
+            return gc, gf, g_o, g_d
         _lib.check(self.lib.nerf_train_render_backward_outputs(self.h, int(slot), C.byref(g), 1 if accumulate else 0, pgc, pgf,
                                                                arr.mem))
         return gc, gf
+
+    def ray_position_grads(self, d_points, z_values):
+        """The bare per-ray reduction of the ray gradients (nerf_ray_position_grads): d_points (N,S,3) = dL/dp per sample,
+        z_values (N,S) -> (d_rays_orig, d_rays_dirs) (N,4): sum_s d_points and sum_s z d_points, component 3 zero."""
+        arr = self._arrays(d_points, z_values)
+        n, s = tuple(z_values.shape)
+        pp, pz = arr.inp(d_points, (n, s, 3)), arr.inp(z_values, (n, s))
+        g_o, pgo = arr.out((n, 4))
+        g_d, pgd = arr.out((n, 4))
+        _lib.check(self.lib.nerf_ray_position_grads(self.h, pp, pz, n, s, pgo, pgd, arr.mem))
+        return g_o, g_d
 
     def render_output_grads(self, weights, z_values, d_depth=None, d_weights=None, d_z=None):
         """The bare fold of the depth / weights / z cotangents (nerf_render_output_grads): weights, z_values (N,S) and any of
