@@ -238,6 +238,32 @@ int nerf_mesh_colors(nerf_ctx* ctx, int which, const float* vertices, const floa
 size_t nerf_blob_size(const nerf_config* cfg);
 int nerf_load_weights(nerf_ctx* ctx, int which, const float* blob, size_t n_floats);
 
+/* Coarse-to-fine positional encoding (additive entry points; the ABI version does not move): a weight in [0, 1] on every
+ * octave of the two sinusoidal encodings, as BARF opens them from low to high frequency and FreeNeRF masks them.  Under a
+ * window every network evaluation of the library -- every render and predict entry, the lattice, the bake, the vertex colours,
+ * every trainer pass -- sees, per component c,
+ *     xyz:  [ x_c, w_xyz[0] sin(2^0 pi x_c), w_xyz[0] cos(2^0 pi x_c), ..., w_xyz[L-1] sin(.), w_xyz[L-1] cos(.) ]
+ *     dir:  [ w_dir[0] sin, w_dir[0] cos, ... ]
+ * and the pass-through component always has weight 1.  nerf_positional_encoding, the bare operator, stays unwindowed.
+ * How: the encoding only ever enters a dense layer, so the weight of octave k is folded into the rows of that octave in
+ * layers 0 and 4 (xyz) and 8 and 10 (directions) while the kernels' operand streams are packed -- every packed weight is
+ * fl32(weight * w), split or rounded as before -- the master weights are never scaled: nerf_get_weights, checkpoints and
+ * Adam's moments stay in the unwindowed parametrisation, and gradients are with respect to the master weights: what the
+ * gradient entry points return, the optimizer applies and the data-parallel all-reduce sums is w times the gradient the
+ * kernels compute with respect to the windowed weights, applied to the contribution of the call at hand only (accumulated
+ * gradients are not rescaled; under mixed_float16 the loss-scale verdict is unchanged).  A row with weight 0 is not trained.
+ * w_xyz: n_pos_enc_xyz values, w_dir: n_pos_enc_dir values, HOST pointers; NULL = all ones.  A value that is not finite or
+ * outside [0, 1] fails and names its index.  w_dir on an n_angles = 0 context is accepted and has no effect.  All ones, or
+ * two NULLs, is "off": the library then launches exactly what it launches without a window.
+ * The window belongs to the context: it survives nerf_train_begin, nerf_train_end, nerf_load_weights and the slot calls.
+ * Setting it re-packs what exists (the render streams of loaded networks, both networks of a running trainer) on the context's
+ * stream, without a synchronise.  It fails while a render slot holds a forward pass (nerf_train_render_forward without its
+ * backward): a slot's backward must run under the window of its forward.  An occupancy grid is kept: it is a snapshot of the
+ * network as windowed when it was baked.  Data-parallel ranks must each be given the same window.
+ * nerf_ctx_get_encoding_window: the weights in force (ones when off; either pointer may be NULL) and whether a window is on. */
+int nerf_ctx_set_encoding_window(nerf_ctx* ctx, const float* w_xyz, const float* w_dir);
+int nerf_ctx_get_encoding_window(nerf_ctx* ctx, float* w_xyz, float* w_dir, int32_t* active);
+
 /* ---- the functions on the path, one entry each ---------------------- */
 /* get_rays_directions, src/UtilsCV.py:467-499.  c2w row-major (4,4) HOST; dirs (H*W,4). */
 int nerf_get_rays_directions(nerf_ctx* ctx, const float* c2w, float fov, int32_t H, int32_t W,

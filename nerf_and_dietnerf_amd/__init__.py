@@ -8,7 +8,7 @@ Importing this package does not need a GPU; creating a Context does (there is no
 from . import _lib
 from ._lib import (NERF_MEM_DEVICE, NERF_MEM_HOST, NERF_NET_COARSE, NERF_NET_FINE, NERF_PRECISION_F16X3,
                    NERF_PRECISION_FP32)
-from .render import (Context, NeRF, NetHandle, default_context, get_rays_directions, get_size_of_splits,
+from .render import (Context, NeRF, NetHandle, default_context, encoding_window, get_rays_directions, get_size_of_splits,
                      get_z_vals_from_prob_dist_func, get_z_values, model_predict, positional_encoding_for_views,
                      positional_encoding_for_xyz, ray_marching, render_rays, split_to_batches)
 from .keras_h5 import load_nerf_checkpoint, read_keras_weights, save_nerf_checkpoint, write_keras_weights

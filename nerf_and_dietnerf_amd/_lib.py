@@ -71,6 +71,8 @@ SYMBOLS = [
     ("nerf_mesh_colors", C.c_int, [_P, C.c_int, _P, _P, _I64, _P, C.c_int]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    ("nerf_ctx_set_encoding_window", C.c_int, [_P, _P, _P]),
+    ("nerf_ctx_get_encoding_window", C.c_int, [_P, _P, _P, C.POINTER(_I32)]),
     ("nerf_get_rays_directions", C.c_int, [_P, _P, _F, _I32, _I32, _P, C.c_int]),
     ("nerf_rays_to_ndc", C.c_int, [_P, _P, _P, _I64, _F, _F, _P, _P, C.c_int]),
     ("nerf_get_z_values", C.c_int, [_P, _I64, _I32, _P, _U64, _I64, _P, C.c_int]),

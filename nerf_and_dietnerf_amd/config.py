@@ -41,7 +41,8 @@ LINDISP, USE_NDC, NDC_NEAR_PLANE = "lindisp", "use_ndc", "ndc_near_plane"
 SCENE_BOX = "scene_box"            # [[x, y, z], [x, y, z]]: per-ray depth range from a scene bounding box
 OCCUPANCY_GRID = "occupancy_grid"  # {resolution, sigma_threshold, samples_per_cell, dilate, update_every, warmup_epochs, cull_samples, cull_train_samples}; needs scene_box
 DISTORTION_LOSS = "distortion_loss"  # number or [coarse, fine]: weights of the distortion regulariser on the compositing weights
-ESTIMATE = "estimate"              # get_nerf(estimated_intersection=...): run the scene analysis, as the reference does
+ENCODING_WINDOW = "encoding_window"  # {kind, start, end, epochs, dirs}: coarse-to-fine positional encoding opened over the fit epochs
+ESTIMATE = "estimate"             # get_nerf(estimated_intersection=...): run the scene analysis, as the reference does
 
 
 def load_config(config_file_path) -> Dict:

@@ -634,19 +634,26 @@ void launch_posenc(const float* x, long long M, int n_enc, int passthrough, floa
 // ------------------------------------------------------------------------------------------------
 // repack: weight blob -> one operand stream (and its constant block) through a gather table (nerf_kernels.h: launch_repack).
 // E = _Float16 / __bf16: entry 2 * (src + 1) + is_lo -> the weight rounded to E (RNE), or what rounding left, rounded again;
-// E = float: entry src + 1 -> the weight.  Entry 0: padding.
+// E = float: entry src + 1 -> the weight.  Entry 0: padding.  With a scale table (the encoding window: one float per blob
+// element, build_scale_table) "the weight" is fl32(blob[src] * scale[src]): the product is rounded on its own, never fused
+// into the hi / lo split.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float repack_weight(const float* __restrict__ blob, const float* __restrict__ scale, int32_t src) {
+    const float w = blob[src];
+    return scale ? __fmul_rn(w, scale[src]) : w;
+}
+
 template <class E>
-__global__ void repack_kernel(const float* __restrict__ blob, const int32_t* __restrict__ idx, E* __restrict__ out, size_t n,
-                              const int32_t* __restrict__ const_idx, float* __restrict__ cst) {
+__global__ void repack_kernel(const float* __restrict__ blob, const float* __restrict__ scale, const int32_t* __restrict__ idx,
+                              E* __restrict__ out, size_t n, const int32_t* __restrict__ const_idx, float* __restrict__ cst) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const int32_t t = idx[i];
         E v = (E)0.f;
         if constexpr (sizeof(E) == sizeof(float)) {
-            if (t != 0) v = blob[t - 1];
+            if (t != 0) v = repack_weight(blob, scale, t - 1);
         } else if (t != 0) {
-            const float w = blob[(t >> 1) - 1];
+            const float w = repack_weight(blob, scale, (t >> 1) - 1);
             const E hi = (E)w;
             v = (t & 1) ? (E)(w - (float)hi) : hi;
         }
@@ -654,16 +661,16 @@ __global__ void repack_kernel(const float* __restrict__ blob, const int32_t* __r
     }
     if (const_idx && i < (size_t)kConstFloats) {
         const int32_t t = const_idx[i];
-        cst[i] = t ? blob[t - 1] : 0.f;
+        cst[i] = t ? repack_weight(blob, scale, t - 1) : 0.f;
     }
 }
 
-void launch_repack(StreamElem elem, const float* blob, const int32_t* idx, void* out, size_t n, const int32_t* const_idx,
-                   float* cst, hipStream_t s) {
+void launch_repack(StreamElem elem, const float* blob, const float* scale, const int32_t* idx, void* out, size_t n,
+                   const int32_t* const_idx, float* cst, hipStream_t s) {
     const dim3 grid((unsigned)((std::max(n, (size_t)kConstFloats) + 255) / 256)), block(256);
-    if (elem == kElemF32) hipLaunchKernelGGL(repack_kernel<float>, grid, block, 0, s, blob, idx, (float*)out, n, const_idx, cst);
-    else if (elem == kElemBf16) hipLaunchKernelGGL(repack_kernel<__bf16>, grid, block, 0, s, blob, idx, (__bf16*)out, n, const_idx, cst);
-    else hipLaunchKernelGGL(repack_kernel<_Float16>, grid, block, 0, s, blob, idx, (_Float16*)out, n, const_idx, cst);
+    if (elem == kElemF32) hipLaunchKernelGGL(repack_kernel<float>, grid, block, 0, s, blob, scale, idx, (float*)out, n, const_idx, cst);
+    else if (elem == kElemBf16) hipLaunchKernelGGL(repack_kernel<__bf16>, grid, block, 0, s, blob, scale, idx, (__bf16*)out, n, const_idx, cst);
+    else hipLaunchKernelGGL(repack_kernel<_Float16>, grid, block, 0, s, blob, scale, idx, (_Float16*)out, n, const_idx, cst);
 }
 
 }  // namespace nerf

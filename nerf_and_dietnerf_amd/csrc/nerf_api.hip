@@ -195,8 +195,8 @@ int repack_render_streams(nerf_ctx* c, int which, const float* dev_blob) {
         if (!n.stream[k]) HIP_OK(hipMalloc(&n.stream[k], d[k].bytes));
         if (!n.cst[d[k].cst]) HIP_OK(hipMalloc((void**)&n.cst[d[k].cst], kConstBytes));
         // (every kind of a block writes the block's constants: the same values, in stream order)
-        launch_repack(d[k].elem, dev_blob, tab, n.stream[k], d[k].bytes / (d[k].elem == kElemF32 ? 4 : 2), ctab, n.cst[d[k].cst],
-                      c->stream);
+        launch_repack(d[k].elem, dev_blob, window_scale(c), tab, n.stream[k], d[k].bytes / (d[k].elem == kElemF32 ? 4 : 2), ctab,
+                      n.cst[d[k].cst], c->stream);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -497,6 +497,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     }
     for (int32_t* p : c->rt) if (p) (void)hipFree(p);
     for (int32_t* p : c->rt_cst) if (p) (void)hipFree(p);
+    if (c->win_scale) (void)hipFree(c->win_scale);
     for (auto& ev : c->ev_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (hipEvent_t e : c->copy_ev) (void)hipEventDestroy(e);
@@ -732,6 +733,55 @@ int nerf_load_weights(nerf_ctx* c, int which, const float* blob, size_t n_floats
     if (int r = repack_render_streams(c, which, n.dev_blob)) return r;
     n.loaded = true;
     return train_on_load(c, which);      // a running trainer restarts from the new weights
+}
+
+// ---- encoding window ----
+// The window is a scale table over the blob (weight_tables.hip::build_scale_table) that every re-pack multiplies by and every
+// gradient reduction scales its contribution with; no MLP kernel knows of it.  Setting it uploads the table and re-packs
+// whatever exists, all on the ctx stream: work already enqueued reads the old streams, work enqueued later the new ones.
+int nerf_ctx_set_encoding_window(nerf_ctx* c, const float* w_xyz, const float* w_dir) {
+    ENTER(c);
+    const int lx = c->cfg.n_pos_enc_xyz, ld = c->cfg.n_pos_enc_dir;
+    auto check = [](const char* name, const float* w, int n) -> int {
+        for (int k = 0; w && k < n; ++k)
+            if (!std::isfinite(w[k]) || w[k] < 0.f || w[k] > 1.f)
+                return fail("encoding window: every weight is finite and in [0, 1] (%s[%d] = %g)", name, k, w[k]);
+        return 0;
+    };
+    if (int r = check("w_xyz", w_xyz, lx)) return r;
+    if (int r = check("w_dir", w_dir, ld)) return r;
+    if (c->cfg.n_angles == 0) w_dir = nullptr;      // the xyz-only network has no direction encoding: accepted, no effect
+    bool on = false;
+    for (int k = 0; w_xyz && k < lx; ++k) on |= w_xyz[k] != 1.f;
+    for (int k = 0; w_dir && k < ld; ++k) on |= w_dir[k] != 1.f;
+    if (!on && !c->win_on) return 0;                // off stays off: nothing to launch
+    if (int r = train_window_guard(c)) return r;
+    for (int k = 0; k < 10; ++k) c->win_xyz[k] = on && w_xyz && k < lx ? w_xyz[k] : 1.f;
+    for (int k = 0; k < 4; ++k) c->win_dir[k] = on && w_dir && k < ld ? w_dir[k] : 1.f;
+    if (on) {
+        build_scale_table(lx, ld, c->cfg.n_angles, c->win_xyz, c->win_dir, c->win_host);
+        const size_t bytes = c->win_host.size() * sizeof(float);
+        if (!c->win_scale) HIP_OK(hipMalloc((void**)&c->win_scale, bytes));
+        // (win_host is pageable: the copy has left the host when hipMemcpyAsync returns, as nerf_load_weights relies on)
+        HIP_OK(hipMemcpyAsync(c->win_scale, c->win_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    c->win_on = on;
+    // the render streams: from the trainer's master blob where one trains the network (train_flush_weights re-packs after
+    // optimizer steps and keeps its own books), else from the loaded blob
+    for (int w = 0; w < 2; ++w) {
+        if (!c->net[w].loaded) continue;
+        const float* src = train_master_blob(c, w);
+        if (int r = repack_render_streams(c, w, src ? src : c->net[w].dev_blob)) return r;
+    }
+    return train_on_window(c);
+}
+
+int nerf_ctx_get_encoding_window(nerf_ctx* c, float* w_xyz, float* w_dir, int32_t* active) {
+    if (!c) return fail("ctx is NULL");
+    for (int k = 0; w_xyz && k < c->cfg.n_pos_enc_xyz; ++k) w_xyz[k] = c->win_xyz[k];
+    for (int k = 0; w_dir && k < c->cfg.n_pos_enc_dir; ++k) w_dir[k] = c->win_dir[k];
+    if (active) *active = c->win_on ? 1 : 0;
+    return 0;
 }
 
 int nerf_get_rays_directions(nerf_ctx* c, const float* c2w, float fov, int32_t H, int32_t W, float* dirs, int mem) {

@@ -81,6 +81,14 @@ struct nerf_ctx {
     int32_t* rt[nerf::kStreamKinds] = {};
     int32_t* rt_cst[nerf::kConstBlocks] = {};
     bool rt_built = false;
+    // Encoding window (nerf_ctx_set_encoding_window): the per-octave weights as given, and -- while a window is on -- the
+    // scale table over the blob (nerf_kernels.h::build_scale_table) every re-pack multiplies by and every writer into a
+    // trainer's gradient blob scales its contribution with.  Off (never set, or all ones): win_on false, no kernel sees a table.
+    bool win_on = false;
+    float win_xyz[10] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float win_dir[4] = {1.f, 1.f, 1.f, 1.f};
+    std::vector<float> win_host;               // the table on the host (source of the upload)
+    float* win_scale = nullptr;                // ... and on the device (blob size; kept once allocated)
     // scratch arena (grow-only).  Staging (nerf::Staging, host-memory calls): b_orig, b_dirs (rays), b_u0, b_u1 (draws), b_in0,
     // b_in1, b_in2 (other arguments), b_out[i] (member i of nerf_outputs); an entry also stages in b_zc, b_zf or b_raw where the
     // passes it runs leave that buffer alone.  The passes (draw_z_values, dev_render, dev_render_rays, run_mlp's callers, the
@@ -153,6 +161,16 @@ int comm_world(const nerf_ctx* c);                            // ranks of the ct
 // optimizer steps alike
 int ensure_render_tables(nerf_ctx* c);
 int repack_render_streams(nerf_ctx* c, int which, const float* dev_blob);
+// the device scale table of the ctx's encoding window, NULL while it is off: what launch_repack, launch_relayout and the
+// gradient reductions take
+inline const float* window_scale(const nerf_ctx* c) { return c->win_on ? c->win_scale : nullptr; }
+// train_api.hip, both no-ops without a trainer.  train_window_guard, before the window changes: refuses while a render slot
+// holds a forward pass, and makes the ctx stream wait for the side stream's gradient reduction (it reads the table).
+// train_on_window, after: both networks' operand streams (the reference trainer: matrices) re-packed under the new window.
+// train_master_blob: the device blob of the master weights of network `which` while a trainer holds it, else NULL.
+int train_window_guard(nerf_ctx* c);
+int train_on_window(nerf_ctx* c);
+const float* train_master_blob(const nerf_ctx* c, int which);
 int train_on_load(nerf_ctx* c, int which);          // train_api.hip: no-op without a trainer
 int train_flush_weights(nerf_ctx* c, int which, bool to_host = false);
 // (train_flush_weights: train_api.hip, no-op unless optimizer steps changed the weights)

@@ -181,11 +181,17 @@ inline bool build_stream_gather(int lx, int n_angles, StreamKind k, int32_t* str
 // network keeps that is its own table source (empty otherwise), cst[b] for each constant block a kept kind owns
 struct StreamTables { std::vector<int32_t> stream[kStreamKinds], cst[kConstBlocks]; };
 void build_stream_tables(int lx, int ld, int n_angles, StreamTables& t);
+// weight_tables.hip: the encoding window (nerf_ctx_set_encoding_window) as a scale table over the (lx, ld, n_angles) blob, one
+// float per blob element: w_xyz[k] on the rows of octave k of the xyz encoding in layers 0 and 4, w_dir[k] on the rows of
+// octave k of the direction encoding in layers 8 and 10 (n_angles 1 or 2), 1 everywhere else (pass-through rows, hidden rows,
+// biases, the xyz-only network's layers 8..11).  w_xyz: lx values, w_dir: ld values.
+void build_scale_table(int lx, int ld, int n_angles, const float* w_xyz, const float* w_dir, std::vector<float>& scale);
 // aux_kernels.hip: the one device re-pack.  out[i], i < n: the weight slot idx[i] names, rounded to `elem` (fp16 / bf16: hi
 // = the rounded weight, lo = the rounded rest; fp32: the weight), 0 for padding; and, with const_idx, cst[i] for i <
-// kConstFloats the same way in fp32 (a table's constant block rides in its stream's launch)
-void launch_repack(StreamElem elem, const float* blob, const int32_t* idx, void* out, size_t n, const int32_t* const_idx,
-                   float* cst, hipStream_t s);
+// kConstFloats the same way in fp32 (a table's constant block rides in its stream's launch).  scale (nullable: none): a
+// device scale table over the blob; every gathered weight is then fl32(blob[i] * scale[i]).
+void launch_repack(StreamElem elem, const float* blob, const float* scale, const int32_t* idx, void* out, size_t n,
+                   const int32_t* const_idx, float* cst, hipStream_t s);
 
 // mlp_f16_2t.hip -- single-pass fp16 render kernel with two 32-sample tiles per wave (same hi-only stream / constants)
 void launch_mlp_f16_2t(const MlpArgs& a, int num_cus, hipStream_t stream);

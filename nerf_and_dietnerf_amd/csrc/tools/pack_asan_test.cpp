@@ -6,6 +6,7 @@
 //   hipcc -fsanitize=address -fno-gpu-sanitize -O1 -g --offload-arch=gfx950 -std=c++17 -I. tools/pack_asan_test.cpp \
 //         weight_tables.hip mlp_fp32.hip mlp_f16x3.hip mlp_f16x3_wide.hip mlp_bwd_f16x3.hip -o pack_asan \
 //         && ./pack_asan ../../tests/golden/stream_table_hashes.txt
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -63,6 +64,19 @@ int main(int argc, char** argv) {
                 }
                 for (int b = 0; b < kConstBlocks; ++b)
                     if (!t.cst[b].empty()) check(std::string(cfg) + kBlock[b], t.cst[b], false, nblob);
+                {   // the encoding window's scale table: one float per blob element, whole windowed rows and nothing else
+                    const float wx[10] = {.5f, .5f, .5f, .5f, .5f, .5f, .5f, .5f, .5f, .5f}, wd[4] = {.25f, .25f, .25f, .25f};
+                    std::vector<float> s;
+                    build_scale_table(lx, ld, n_angles, wx, wd, s);
+                    size_t nx = 0, nd = 0;
+                    for (float v : s) { nx += v == .5f; nd += v == .25f; }
+                    const size_t want_x = (size_t)2 * 6 * lx * 256, want_d = n_angles ? (size_t)2 * ld * (n_angles + 1) * (128 + 1) : 0;
+                    if (s.size() != nblob || nx != want_x || nd != want_d || nx + nd + (size_t)std::count(s.begin(), s.end(), 1.f) != nblob) {
+                        printf("FAIL %sscale table: %zu entries (blob %zu), %zu / %zu xyz, %zu / %zu dir\n", cfg, s.size(), nblob, nx,
+                               want_x, nd, want_d);
+                        ++g_bad;
+                    }
+                }
                 // the trainer's backward stream (not a render stream: no table entry)
                 for (int dx : {0, 1})
                     for (int hi_only : {0, 1}) {

@@ -168,14 +168,22 @@ void free_slot(RenderSlot& s) {
     for (DevBuf* b : {&s.o, &s.d, &s.u_c, &s.u_f, &s.z_new}) free_buf(*b);
 }
 
+// The encoding window's scale table over layer l's weights (the layout of the blob, as TLayer::w_off), or null: window off, or
+// a layer no encoding enters (scale 1 throughout).  What relayout and the gradient reductions of that layer multiply by.
+const float* layer_scale(const nerf_ctx* c, const TNet& n, int l) {
+    const bool enc = l == 0 || l == 4 || (n.n_layers == 11 && (l == 8 || l == 10));
+    return window_scale(c) && enc ? window_scale(c) + n.L[l].w_off : nullptr;
+}
+
 int relayout_net(nerf_ctx* c, TNet& n) {
     const TrainState* t = c->train;
     if (!t->reference) {     // the fused kernels read their two re-packed streams and nothing else
         const StreamKind k = t->mixed ? kF16Hi : kF16x3;      // the stash forward reads the render stream of its arithmetic
         StreamDesc d[kStreamKinds];
         render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, 1, d);
-        launch_repack(kElemF16, n.blob, c->rt[k], n.fstream, d[k].bytes / 2, c->rt_cst[kConst16], n.fcst, c->stream);
-        launch_repack(kElemF16, n.blob, t->bidx[n.bdx ? 1 : 0], n.bstream, kBwdStreamBytes / 2, nullptr, nullptr, c->stream);
+        const float* sc = window_scale(c);     // the encoding window: both streams are packed from the scaled weights
+        launch_repack(kElemF16, n.blob, sc, c->rt[k], n.fstream, d[k].bytes / 2, c->rt_cst[kConst16], n.fcst, c->stream);
+        launch_repack(kElemF16, n.blob, sc, t->bidx[n.bdx ? 1 : 0], n.bstream, kBwdStreamBytes / 2, nullptr, nullptr, c->stream);
         HIP_OK(hipGetLastError());
         return 0;
     }
@@ -183,6 +191,7 @@ int relayout_net(nerf_ctx* c, TNet& n) {
         const TLayer& L = n.L[l];
         RelayoutArgs a;
         a.w = n.blob + L.w_off; a.b = n.blob + L.b_off;
+        a.scale = layer_scale(c, n, l);
         a.K_real = L.K_real; a.N_real = L.N_real; a.Kp = L.Kp; a.Np = L.Np; a.rowmap = L.rowmap;
         a.W = L.W; a.WT = L.WT; a.bias = L.bias;
         launch_relayout(a, c->stream);
@@ -459,8 +468,8 @@ int wgrad_flush(nerf_ctx* c, TrainState* t, WgradQueue& q, long long Mp, bool on
 // `want_splits` of them, whole multiples of `row_quantum` rows), the slab sums' destination
 struct Wgrad { GemmAtb g; ReduceArgs r; int splits; };
 
-Wgrad wgrad_args(TrainState* t, TNet& n, int l, const float* A, int lda, const float* G, int ldg, int Ncols, int n_src_off,
-                 long long Mp, int want_splits, int row_quantum) {
+Wgrad wgrad_args(const nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* G, int ldg, int Ncols,
+                 int n_src_off, long long Mp, int want_splits, int row_quantum) {
     const TLayer& L = n.L[l];
     Wgrad w{};
     GemmAtb& g = w.g;
@@ -476,6 +485,7 @@ Wgrad wgrad_args(TrainState* t, TNet& n, int l, const float* A, int lda, const f
     r.grad_w = n.grad + L.w_off; r.grad_b = n.grad + L.b_off;
     r.K_real = L.K_real; r.N_real = L.N_real; r.n_src_off = n_src_off; r.rowmap = L.rowmap;
     r.accumulate = t->acc_grads ? 1 : 0;
+    r.scale_w = layer_scale(c, n, l);
     return w;
 }
 
@@ -486,7 +496,7 @@ void wgrad_reference(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A,
     // C8 (kLdC8 wide, its first 256 columns for the xyz-only network's sigma head): whole, 16-byte-aligned column quads,
     // at most 256 of them, as head_wgrad_rows_kernel requires
     static_assert(kLdC8 % 4 == 0 && kLdC8 <= 1024, "head_wgrad_rows_kernel: Kp % 4 == 0, Kp <= 1024, lda % 4 == 0");
-    const Wgrad w = wgrad_args(t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp, Ncols == 4 ? 1024 : kTrainSplits, 16);
+    const Wgrad w = wgrad_args(c, t, n, l, A, lda, G, ldg, Ncols, n_src_off, Mp, Ncols == 4 ? 1024 : kTrainSplits, 16);
     if (Ncols == 4) launch_head_wgrad(w.g, false, c->stream);
     else launch_gemm_atb(w.g, c->stream);
     launch_reduce_grad(w.r, c->stream);
@@ -496,10 +506,10 @@ void wgrad_reference(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A,
 // gradient from the backward chain, rs / gmax: its row factors (pair16, float32 policy; else null) and max|D| slots.
 // A 256-wide layer joins the pass's batched launch.  wgrad_flush owns the slab layout of a queued entry: it sets
 // rows_per_split, partial and splits of both halves for the batch as a whole, whatever wgrad_args put there.
-int wgrad_queue(TrainState* t, TNet& n, int l, const float* A, int lda, const float* D, const uint16_t* rs,
+int wgrad_queue(const nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* D, const uint16_t* rs,
                 const unsigned* gmax, long long Mp, WgradQueue& q) {
     if (q.gemm.n >= kWgradBatchMax) return fail("internal: more 256-wide layers than a batched weight-gradient launch holds");
-    Wgrad w = wgrad_args(t, n, l, A, lda, D, 256, 256, 0, Mp, kTrainSplitsWide, 32);
+    Wgrad w = wgrad_args(c, t, n, l, A, lda, D, 256, 256, 0, Mp, kTrainSplitsWide, 32);
     w.g.g_rs = rs; w.g.gmax = gmax;
     q.gemm.e[q.gemm.n++] = w.g;
     q.red.e[q.red.n++] = w.r;
@@ -511,7 +521,7 @@ int wgrad_queue(TrainState* t, TNet& n, int l, const float* A, int lda, const fl
 // the head's slab sums land behind this GEMM's.
 void wgrad_tile128(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* D, const uint16_t* rs,
                    const unsigned* gmax, long long Mp, int sig_layer = -1) {
-    Wgrad w = wgrad_args(t, n, l, A, lda, D, 128, 128, 0, Mp, kTrainSplits, 32);
+    Wgrad w = wgrad_args(c, t, n, l, A, lda, D, 128, 128, 0, Mp, kTrainSplits, 32);
     w.g.g_rs = rs; w.g.gmax = gmax;
     if (sig_layer >= 0) {
         w.g.sig_g = (const float*)t->dsig.p;
@@ -527,6 +537,7 @@ void wgrad_tile128(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, i
         sig_r.grad_w = n.grad + Ls.w_off; sig_r.grad_b = n.grad + Ls.b_off;
         sig_r.K_real = Ls.K_real; sig_r.N_real = 1; sig_r.n_src_off = 0; sig_r.rowmap = Ls.rowmap;
         sig_r.accumulate = t->acc_grads ? 1 : 0;
+        sig_r.scale_w = layer_scale(c, n, sig_layer);
         launch_reduce_grad(sig_r, c->stream);
     }
 }
@@ -534,7 +545,7 @@ void wgrad_tile128(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, i
 // A head (4-wide G = column n_src_off.. of Graw, row-major) on the VALU kernel, which wants many small slabs
 void wgrad_head(nerf_ctx* c, TrainState* t, TNet& n, int l, const float* A, int lda, const float* Graw, int n_src_off,
                 long long Mp) {
-    const Wgrad w = wgrad_args(t, n, l, A, lda, Graw, 4, 4, n_src_off, Mp, 1024, 32);
+    const Wgrad w = wgrad_args(c, t, n, l, A, lda, Graw, 4, 4, n_src_off, Mp, 1024, 32);
     launch_head_wgrad(w.g, true, c->stream);
     launch_reduce_grad(w.r, c->stream);
 }
@@ -601,7 +612,7 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
     WgradQueue wq;
     // layer l's gradient buffer is d_ptr[l], its gmax group nrec - 1 - l
     auto queue = [&](int l, const float* A, int lda) {
-        return wgrad_queue(t, n, l, A, lda, b.d_ptr[l], b.rs_ptr[l], gm + 64 * (nrec - 1 - l), Mp, wq);
+        return wgrad_queue(c, t, n, l, A, lda, b.d_ptr[l], b.rs_ptr[l], gm + 64 * (nrec - 1 - l), Mp, wq);
     };
     if (xyz) {
         // get_network_only_xyz (src/NeRF.py:248-288): 10 = the rgb head on h9, 11 = the sigma head on h8 (the first 256
@@ -644,7 +655,10 @@ int backward_fused(nerf_ctx* c, TrainState* t, int which, const PassDims& d, con
                 return fail("internal: the layer table does not match the view-direction encoding");
             launch_view_dir_grads(Graw, p.H9.p, t->mixed, n.blob + L9.w_off, n.blob + L8.w_off + (size_t)256 * L8.N_real,
                                   n.blob + L10.w_off + 256, dirs, d.N, d.S, c->cfg.n_angles, c->cfg.n_pos_enc_dir, cull_mask(p),
-                                  cull_first(p), c->cfg.leaky_relu_alpha, st, rays.d_d, c->stream);
+                                  cull_first(p), c->cfg.leaky_relu_alpha, st, rays.d_d, c->stream,
+                                  // (this kernel reads the master blob, not a packed stream: it scales the two blocks itself)
+                                  layer_scale(c, n, 8) ? layer_scale(c, n, 8) + (size_t)256 * L8.N_real : nullptr,
+                                  layer_scale(c, n, 10) ? layer_scale(c, n, 10) + 256 : nullptr);
         }
     }
     HIP_OK(hipGetLastError());
@@ -1240,6 +1254,30 @@ void train_free(nerf_ctx* c) {
     for (DevBuf* b : bs) free_buf(*b);
     delete t;
     c->train = nullptr;
+}
+
+int train_window_guard(nerf_ctx* c) {
+    TrainState* t = c->train;
+    if (!t) return 0;
+    // A slot's backward pass runs on the trainer's backward streams and scales its weight gradients by the table of the day:
+    // both must be the ones its forward pass ran under.  The rule is the simple one: no change while a pass is held.
+    for (size_t s = 0; s < t->slots.size(); ++s)
+        if (t->slots[s].valid)
+            return fail("the encoding window cannot change while render slot %zu holds a forward pass: run its "
+                        "nerf_train_render_backward first (an optimizer step or nerf_train_render_release drops it)", s);
+    return join_side(c, t);      // the side stream's gradient reduction reads the scale table the caller is about to overwrite
+}
+
+int train_on_window(nerf_ctx* c) {
+    TrainState* t = c->train;
+    if (!t) return 0;
+    for (TNet& n : t->net)
+        if (n.present) if (int r = relayout_net(c, n)) return r;
+    return 0;
+}
+
+const float* train_master_blob(const nerf_ctx* c, int which) {
+    return c->train && c->train->net[which].present ? c->train->net[which].blob : nullptr;
 }
 
 int train_on_load(nerf_ctx* c, int which) {

@@ -81,6 +81,10 @@ struct ReduceArgs {
     int K_real, N_real; int n_src_off;  // gradient column n comes from partial column n_src_off + n
     int rowmap;                         // 0: identity; > 0: layer 4 (blob rows [xyz(rowmap); hidden(256)] <- training rows [hidden; xyz])
     int accumulate;                     // 1: add to the gradient blob instead of overwriting it
+    // The encoding window's scale table over this layer's weights, laid out as grad_w (null: none).  The sum s of the call at
+    // hand is written as fl32(s * scale_w[i]) -- the gradient with respect to the master weights -- before it is stored or
+    // added; what the blob already holds is never rescaled, and the bias has no factor.
+    const float* scale_w;
 };
 void launch_reduce_grad(const ReduceArgs& a, hipStream_t s);
 struct ReduceBatch { int n; ReduceArgs e[kWgradBatchMax]; };
@@ -91,6 +95,7 @@ void launch_reduce_grad_batch(const ReduceBatch& b, hipStream_t s);  // one laun
 struct RelayoutArgs {
     const float* w; const float* b; int K_real, N_real, Kp, Np, rowmap;
     float* W; float* WT; float* bias;
+    const float* scale;                 // the encoding window's scale table over w (null: none): the matrices hold fl32(w * scale)
 };
 void launch_relayout(const RelayoutArgs& a, hipStream_t s);
 
@@ -154,7 +159,9 @@ void launch_ray_position_reduce(const float* d_points, const float* z, long long
 // (ddir): the rgb head and the direction rows of layers 8 and 10 in the weight blob.  d_d[r][component read] += the gradient.
 void launch_view_dir_grads(const float* Graw, const void* H9, bool h9_f16, const float* W9, const float* W8d, const float* Wsd,
                            const float* d, long long N, int S, int n_angles, int ld_oct, const uint8_t* mask,
-                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s);
+                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s,
+                           // the encoding window's scale tables over W8d and Wsd (null: none): the weights read are fl32(W * scale)
+                           const float* scale8d = nullptr, const float* scalesd = nullptr);
 void launch_unmerge_grad(const float* z_new, const float* z_c, const float* d_zm, long long N, int S, int Sf, float* d_zf,
                          hipStream_t s);
 // The fold of render()'s depth / weights / z cotangents into one pass's dL/dw and dL/dz (weights, z: N x S of that pass;

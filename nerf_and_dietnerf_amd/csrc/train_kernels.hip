@@ -1098,6 +1098,7 @@ __global__ void reduce_grad_kernel(const ReduceArgs a) {
     for (int o = 1; o < L; o <<= 1) s += __shfl_xor(s, o);
     if (live && q == 0) {
         float* dst = is_bias ? a.grad_b + n : a.grad_w + (size_t)kb * a.N_real + n;
+        if (a.scale_w && !is_bias) s = __fmul_rn(s, a.scale_w[(size_t)kb * a.N_real + n]);   // rounded before it is added
         *dst = a.accumulate ? *dst + s : s;
     }
 }
@@ -1138,6 +1139,11 @@ __global__ __launch_bounds__(512) void reduce_grad_vec_kernel(const ReduceBatch 
             r[c] = ((f[0] + f[W8]) + (f[2 * W8] + f[3 * W8])) + ((f[4 * W8] + f[5 * W8]) + (f[6 * W8] + f[7 * W8]));
         }
         float* dst = is_bias ? a.grad_b + n : a.grad_w + (size_t)kb * a.N_real + n;
+        if (a.scale_w && !is_bias) {
+            const float* sc = a.scale_w + (size_t)kb * a.N_real + n;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) r[c] = __fmul_rn(r[c], sc[c]);      // rounded before it is added
+        }
 #pragma unroll
         for (int c = 0; c < 4; ++c) dst[c] = a.accumulate ? dst[c] + r[c] : r[c];
     }
@@ -1179,7 +1185,8 @@ __global__ void relayout_kernel(const RelayoutArgs a) {
     int kb = kt;
     if (a.rowmap > 0) kb = kt < 256 ? kt + a.rowmap : kt - 256;
     const bool valid = n < a.N_real && kb >= 0 && kb < a.K_real && (a.rowmap <= 0 || kt < 256 + a.rowmap);
-    const float v = valid ? a.w[(size_t)kb * a.N_real + n] : 0.f;
+    float v = valid ? a.w[(size_t)kb * a.N_real + n] : 0.f;
+    if (valid && a.scale) v = __fmul_rn(v, a.scale[(size_t)kb * a.N_real + n]);
     a.W[(size_t)kt * a.Np + n] = v;
     a.WT[(size_t)n * a.Kp + kt] = v;
     if (kt == 0) a.bias[n] = n < a.N_real ? a.b[n] : 0.f;
@@ -1813,7 +1820,7 @@ __global__ __launch_bounds__(64 * kRayWaves) void view_dir_grad_kernel(
     const float* __restrict__ Graw, const void* __restrict__ H9, const float* __restrict__ W9, const float* __restrict__ W8d,
     const float* __restrict__ Wsd, const float* __restrict__ d, long long N, int S, int n_angles, int ld_oct,
     const uint8_t* __restrict__ mask, const uint32_t* __restrict__ first, float alpha, const OptState* __restrict__ st,
-    float* __restrict__ d_d) {
+    float* __restrict__ d_d, const float* __restrict__ scale8d, const float* __restrict__ scalesd) {
     __shared__ float w9[128 * 3];
     for (int i = threadIdx.x; i < 128 * 3; i += 64 * kRayWaves) w9[i] = W9[i];
     __syncthreads();
@@ -1868,11 +1875,15 @@ __global__ __launch_bounds__(64 * kRayWaves) void view_dir_grad_kernel(
     float part = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const float4 wv = *reinterpret_cast<const float4*>(W8d + (size_t)k * 128 + 8 * q + 4 * h);
+        float4 wv = *reinterpret_cast<const float4*>(W8d + (size_t)k * 128 + 8 * q + 4 * h);
+        if (scale8d) {      // the windowed weights, each product rounded as the re-pack rounds it
+            const float4 sv = *reinterpret_cast<const float4*>(scale8d + (size_t)k * 128 + 8 * q + 4 * h);
+            wv.x = __fmul_rn(wv.x, sv.x); wv.y = __fmul_rn(wv.y, sv.y); wv.z = __fmul_rn(wv.z, sv.z); wv.w = __fmul_rn(wv.w, sv.w);
+        }
         part += acc[4 * q] * wv.x + acc[4 * q + 1] * wv.y + acc[4 * q + 2] * wv.z + acc[4 * q + 3] * wv.w;
     }
     part += __shfl_xor(part, 32);
-    const float gk = part + sig * Wsd[k];
+    const float gk = part + sig * (scalesd ? __fmul_rn(Wsd[k], scalesd[k]) : Wsd[k]);
     // encoding column w of component c is sin (w even) or cos (w odd) of v * pi 2^(w / 2), v the direction component read
     const int comp = n_angles == 2 ? c : (c == 0 ? 0 : 2);
     const float v = live ? d[r * 4 + comp] : 0.f;
@@ -1887,15 +1898,16 @@ __global__ __launch_bounds__(64 * kRayWaves) void view_dir_grad_kernel(
 
 void launch_view_dir_grads(const float* Graw, const void* H9, bool h9_f16, const float* W9, const float* W8d, const float* Wsd,
                            const float* d, long long N, int S, int n_angles, int ld_oct, const uint8_t* mask,
-                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s) {
+                           const uint32_t* first, float alpha, const OptState* st, float* d_d, hipStream_t s,
+                           const float* scale8d, const float* scalesd) {
     if (N <= 0 || S <= 0 || !d_d || n_angles < 1 || n_angles > 2 || ld_oct < 1 || ld_oct > 4) return;
     const dim3 grid((unsigned)((N + kRayWaves - 1) / kRayWaves)), block(64 * kRayWaves);
     if (h9_f16)
         hipLaunchKernelGGL(view_dir_grad_kernel<true>, grid, block, 0, s, Graw, H9, W9, W8d, Wsd, d, N, S, n_angles, ld_oct, mask,
-                           first, alpha, st, d_d);
+                           first, alpha, st, d_d, scale8d, scalesd);
     else
         hipLaunchKernelGGL(view_dir_grad_kernel<false>, grid, block, 0, s, Graw, H9, W9, W8d, Wsd, d, N, S, n_angles, ld_oct, mask,
-                           first, alpha, st, d_d);
+                           first, alpha, st, d_d, scale8d, scalesd);
 }
 
 // ------------------------------------------------------------------------------------------------

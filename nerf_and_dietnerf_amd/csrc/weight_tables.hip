@@ -77,6 +77,27 @@ void aim_gather(int lx, int ld, int n_angles, int32_t* idx, size_t n, bool f16) 
     }
 }
 
+void build_scale_table(int lx, int ld, int n_angles, const float* w_xyz, const float* w_dir, std::vector<float>& scale) {
+    int dims[12][2];
+    const int n = layer_dims(lx, ld, n_angles, dims);
+    scale.assign(blob_floats(lx, ld, n_angles), 1.f);
+    const int xd = 3 + 6 * lx, dd = 2 * ld * (n_angles + 1);
+    size_t off = 0;
+    for (int l = 0; l < n; ++l) {
+        // the rows of layer l that an encoding enters, in blob_expand_index's row order: xyz [x, sin0, cos0, ...] per
+        // component at the top of layers 0 and 4, direction [sin0, cos0, ...] per component below the 256 hidden rows of 8, 10
+        const bool xyz_rows = l == 0 || l == 4, dir_rows = n_angles != 0 && (l == 8 || l == 10);
+        for (int r = 0; r < (xyz_rows ? xd : 0); ++r) {
+            const int j = r % (1 + 2 * lx);
+            if (j == 0) continue;                    // the pass-through component
+            std::fill_n(scale.begin() + off + (size_t)r * dims[l][1], dims[l][1], w_xyz[(j - 1) / 2]);
+        }
+        for (int r = 0; r < (dir_rows ? dd : 0); ++r)
+            std::fill_n(scale.begin() + off + (size_t)(kHidden + r) * dims[l][1], dims[l][1], w_dir[(r % (2 * ld)) / 2]);
+        off += (size_t)dims[l][0] * dims[l][1] + dims[l][1];
+    }
+}
+
 void build_stream_tables(int lx, int ld, int n_angles, StreamTables& t) {
     StreamDesc d[2][kStreamKinds];
     for (int w = 0; w < 2; ++w) render_streams(lx, n_angles, w, d[w]);

@@ -96,7 +96,11 @@ def fit(model, ds: RayDataset, epochs: int = 1, steps_per_epoch: Optional[int] =
     With render_config ``occupancy_grid`` the model's grid follows its schedule at the start of every epoch
     (NeRF.occupancy_grid_epoch: off during ``warmup_epochs``, baked again every ``update_every`` epochs after them); within
     an epoch the grid is the snapshot taken at its start.  Under ``"cull_train_samples"`` that snapshot also decides which
-    samples train: a culled cell receives no gradient until a re-bake (with ``dilate``) brings it back."""
+    samples train: a culled cell receives no gradient until a re-bake (with ``dilate``) brings it back.
+
+    With render_config ``encoding_window`` the positional encoding opens from low to high octaves over the epochs
+    (NeRF.encoding_window_epoch, called before the grid's hook): epoch e since compile() trains under
+    alpha = start + (end - start) min(e / epochs, 1).  A checkpoint saved mid-schedule does not record the window."""
     ctx = model.ctx
     ctx.train_read_metric_sums()                     # start from clean sums
     extra = getattr(model, "train_read_extra_metric_sums", None)    # DietNeRF: cosine_similarity_loss, kept by the model
@@ -104,7 +108,10 @@ def fit(model, ds: RayDataset, epochs: int = 1, steps_per_epoch: Optional[int] =
         extra()
     history = []
     grid_epoch = getattr(model, "occupancy_grid_epoch", None)
+    window_epoch = getattr(model, "encoding_window_epoch", None)
     for _ in range(epochs):
+        if window_epoch:
+            window_epoch()           # before the grid: a re-baked grid sees the epoch's window
         if grid_epoch:
             grid_epoch()
         sums: Dict[str, float] = {}

@@ -49,6 +49,10 @@ _GRID_KEYS = (GRID_RESOLUTION, GRID_SIGMA_THRESHOLD, GRID_SAMPLES_PER_CELL, GRID
               GRID_CULL_SAMPLES, GRID_CULL_TRAIN_SAMPLES)
 GRID_NEEDS_BOX = "an occupancy grid needs a scene box"
 DISTORTION_LOSS = "distortion_loss"  # number, or [coarse, fine], default absent: weights of the distortion regulariser in training
+ENCODING_WINDOW = "encoding_window"  # dict of the keys below, default absent: coarse-to-fine positional encoding over the fit epochs
+WINDOW_KIND, WINDOW_START, WINDOW_END, WINDOW_EPOCHS, WINDOW_DIRS = "kind", "start", "end", "epochs", "dirs"
+_WINDOW_KEYS = (WINDOW_KIND, WINDOW_START, WINDOW_END, WINDOW_EPOCHS, WINDOW_DIRS)
+_WINDOW_KINDS = ("cosine", "linear")
 
 N_COORDINATES = 3
 N_COLOR_CHANNELS = 3
@@ -87,6 +91,51 @@ def check_distortion_loss(value) -> Tuple[float, float]:
         return number(value[0]), number(value[1])
     v = number(value)
     return v, v
+
+
+def encoding_window(alpha, n_octaves, kind="cosine") -> np.ndarray:
+    """The coarse-to-fine window at progress ``alpha`` in [0, n_octaves]: the weight of octave k, float32 (n_octaves,).
+    "cosine" (BARF): 0 for alpha < k, (1 - cos((alpha - k) pi)) / 2 for 0 <= alpha - k < 1, 1 above.  "linear" (FreeNeRF's
+    ramp): clip(alpha - k, 0, 1).  alpha = 0 masks every octave, alpha >= n_octaves none."""
+    if kind not in _WINDOW_KINDS:
+        raise ValueError(f"encoding window kind must be one of {_WINDOW_KINDS} (got {kind!r})")
+    n = int(n_octaves)
+    if n != n_octaves or n < 1:
+        raise ValueError(f"encoding window: n_octaves must be a positive integer (got {n_octaves!r})")
+    alpha = float(alpha)
+    if not np.isfinite(alpha):
+        raise ValueError(f"encoding window: alpha must be finite (got {alpha!r})")
+    t = np.clip(alpha - np.arange(n, dtype=np.float64), 0.0, 1.0)
+    w = t if kind == "linear" else (1.0 - np.cos(t * np.pi)) / 2.0
+    return w.astype(np.float32)
+
+
+def check_encoding_window(value, n_octaves) -> dict:
+    """render_config["encoding_window"] -> the dict with defaults filled in: kind "cosine", start 0, end n_octaves, epochs
+    (required, a positive integer), dirs False.  An unknown key, kind or a value out of range fails."""
+    if not isinstance(value, dict):
+        raise ValueError(f"{ENCODING_WINDOW} must be a dict with keys from {_WINDOW_KEYS} (got {value!r})")
+    unknown = set(value) - set(_WINDOW_KEYS)
+    if unknown:
+        raise ValueError(f"unknown {ENCODING_WINDOW} keys {sorted(unknown)}: expected {_WINDOW_KEYS}")
+    if WINDOW_EPOCHS not in value:
+        raise ValueError(f"{ENCODING_WINDOW} needs \"{WINDOW_EPOCHS}\": the fit epochs over which the window opens")
+    kind = value.get(WINDOW_KIND, "cosine")
+    if kind not in _WINDOW_KINDS:
+        raise ValueError(f"{ENCODING_WINDOW} kind must be one of {_WINDOW_KINDS} (got {kind!r})")
+    epochs = value[WINDOW_EPOCHS]
+    if isinstance(epochs, bool) or int(epochs) != epochs or epochs < 1:
+        raise ValueError(f"{ENCODING_WINDOW} {WINDOW_EPOCHS} must be a positive integer (got {epochs!r})")
+    start, end = float(value.get(WINDOW_START, 0.0)), float(value.get(WINDOW_END, n_octaves))
+    if not (np.isfinite(start) and np.isfinite(end) and 0.0 <= start <= end):
+        raise ValueError(f"{ENCODING_WINDOW} needs finite 0 <= start <= end (got start {start!r}, end {end!r})")
+    return {WINDOW_KIND: kind, WINDOW_START: start, WINDOW_END: end, WINDOW_EPOCHS: int(epochs),
+            WINDOW_DIRS: bool(value.get(WINDOW_DIRS, False))}
+
+
+def encoding_window_alpha(cfg, epoch) -> float:
+    """alpha_xyz at the start of fit epoch ``epoch`` (0-based) under a checked config: start + (end - start) min(e / E, 1)."""
+    return cfg[WINDOW_START] + (cfg[WINDOW_END] - cfg[WINDOW_START]) * min(epoch / cfg[WINDOW_EPOCHS], 1.0)
 
 
 def pack_occupancy_grid(grid) -> np.ndarray:
@@ -319,6 +368,38 @@ class Context:
         _lib.check(self.lib.nerf_load_weights(self.h, which, blob.ctypes.data, blob.size))
         self.loaded[which] = True
         self._auto_new_weights()
+
+    # ---- coarse-to-fine positional encoding (include/nerf_mi355.h: nerf_ctx_set_encoding_window has the rules) ----
+    def set_encoding_window(self, xyz=None, dirs=None) -> None:
+        """A weight in [0, 1] per octave of the xyz encoding (``xyz``: n_pos_enc_xyz values) and of the direction encoding
+        (``dirs``: n_pos_enc_dir values; accepted and without effect when n_angles is 0); None = all ones, and all ones is
+        "off".  Every network evaluation of the context then sees octave k's sin / cos features times its weight -- renders,
+        model_predict, the lattice, the bake, every trainer pass -- while the pass-through component keeps weight 1.  The
+        master weights are never scaled (get_weights, checkpoints and Adam's moments do not know of the window) and weight
+        gradients are with respect to the master weights: a row with weight 0 gets gradient 0 and is not trained.  The window
+        belongs to the context and survives load_weights, train_begin and train_end.  Setting it re-packs the loaded
+        networks and a running trainer's on the context's stream without synchronising; it fails while a render slot holds
+        a forward pass (run its backward first).  An occupancy grid is kept as baked.  Under data-parallel training every
+        rank's context must be given the same window: nothing synchronises it."""
+        def vec(name, v, n):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(v, np.float32).ravel())
+            if a.size != n:
+                raise ValueError(f"encoding window: {name} needs {n} values, one per octave (got {a.size})")
+            return a
+        wx = vec("xyz", xyz, int(self.cfg.n_pos_enc_xyz))
+        wd = vec("dirs", dirs, int(self.cfg.n_pos_enc_dir))
+        _lib.check(self.lib.nerf_ctx_set_encoding_window(self.h, None if wx is None else wx.ctypes.data,
+                                                        None if wd is None else wd.ctypes.data))
+        self._auto_new_weights()         # "auto": what the networks compute has changed, as with new weights
+
+    def encoding_window(self):
+        """(xyz, dirs) float32 arrays of the window in force, or None when it is off."""
+        wx, wd = np.empty(int(self.cfg.n_pos_enc_xyz), np.float32), np.empty(int(self.cfg.n_pos_enc_dir), np.float32)
+        active = C.c_int32()
+        _lib.check(self.lib.nerf_ctx_get_encoding_window(self.h, wx.ctypes.data, wd.ctypes.data, C.byref(active)))
+        return (wx, wd) if active.value else None
 
     def set_bounds(self, near: float, far: float) -> None:
         _lib.check(self.lib.nerf_ctx_set_bounds(self.h, near, far))
@@ -1236,6 +1317,10 @@ class NeRF:
         # distortion regulariser: an absent key leaves training as it was; compile() hands the weights to the trainer
         self.distortion_weights = check_distortion_loss(render_config[DISTORTION_LOSS]) if DISTORTION_LOSS in render_config \
             else None
+        # coarse-to-fine encoding: an absent key leaves everything as it was; compile() applies epoch 0, fit() the rest
+        self.window_config = check_encoding_window(render_config[ENCODING_WINDOW], self.n_pos_enc_dim_xyz) \
+            if ENCODING_WINDOW in render_config else None
+        self._window_epochs = 0      # epochs fit() has run since compile(): the window's schedule counts them
 
     @staticmethod
     def _grid_config(cfg, scene_box):
@@ -1330,6 +1415,31 @@ class NeRF:
         elif done % g[GRID_UPDATE_EVERY] == 0:
             self.update_occupancy_grid()
 
+    # ---- coarse-to-fine positional encoding (Context.set_encoding_window) ----
+    def set_encoding_alpha(self, alpha_xyz, alpha_dirs=None, kind: str = "cosine") -> None:
+        """Open the xyz encoding's window to progress ``alpha_xyz`` in [0, n_pos_enc_dim_xyz] (``encoding_window``) and, with
+        ``alpha_dirs``, the direction encoding's to that one in [0, n_pos_enc_view_dir]; None leaves the directions at full
+        band.  Per-step control for a caller's own loop -- a pose refinement that opens the window as it converges.  At
+        alpha_xyz >= n_pos_enc_dim_xyz (and no direction window) the window is off."""
+        wx = encoding_window(alpha_xyz, self.n_pos_enc_dim_xyz, kind)
+        wd = None if alpha_dirs is None else encoding_window(alpha_dirs, self.n_pos_enc_view_dir, kind)
+        self.ctx.set_encoding_window(wx, wd)
+
+    def encoding_window_epoch(self) -> None:
+        """dataset.fit's hook, at the start of every epoch and before the occupancy grid's (a re-baked grid sees the epoch's
+        window): with render_config["encoding_window"] = {"kind", "start", "end", "epochs", "dirs"} epoch e, counted from
+        compile(), trains under alpha_xyz = start + (end - start) min(e / epochs, 1); with "dirs" the direction encoding
+        gets alpha_xyz * n_pos_enc_view_dir / n_pos_enc_dim_xyz.  Once alpha reaches n_pos_enc_dim_xyz the window is off and
+        a checkpoint saved from then on is an ordinary network.  A checkpoint saved mid-schedule does NOT record the window:
+        it holds the master weights, which render as trained only under the window of that epoch."""
+        w = self.window_config
+        if w is None:
+            return
+        alpha = encoding_window_alpha(w, self._window_epochs)
+        self._window_epochs += 1
+        self.set_encoding_alpha(alpha, alpha * self.n_pos_enc_view_dir / self.n_pos_enc_dim_xyz if w[WINDOW_DIRS] else None,
+                                w[WINDOW_KIND])
+
     def set_weights(self, coarse, fine=None) -> None:
         self._blobs = [coarse, fine]
         self.ctx.load_weights(NERF_NET_COARSE, coarse)
@@ -1368,6 +1478,10 @@ class NeRF:
         self._mixed = bool(mixed_float16)
         if self.distortion_weights is not None:
             self.ctx.train_set_distortion_weights(*self.distortion_weights)
+        if getattr(self, "window_config", None) is not None:      # the schedule starts over: epoch 0's window, now
+            self._window_epochs = 0
+            self.encoding_window_epoch()
+            self._window_epochs = 0
 
     def train_read_extra_metric_sums(self):
         """Sums of the two distortion losses over the steps since the last read, for dataset.fit's per-epoch means -- only
