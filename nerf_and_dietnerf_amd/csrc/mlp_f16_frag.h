@@ -72,6 +72,12 @@ constexpr int kHStreamChunks = kHChunksPE + 6 * kHChunksHid + kHChunksSkip + kHC
 constexpr int kHChunksSig = (kHQpuLast + kHCQ - 1) / kHCQ;                                   // 2
 constexpr int kHStreamChunksSig = kHStreamChunks - kHChunksLast + kHChunksSig;               // 62
 static_assert(kHStreamChunksSig * (size_t)kHChunkBytes == kStreamBytesF16Sig, "sigma-only stream size mismatch");
+// sigma-first stream of the rgb-skipping fine kernel (mlp_f16x3_rgbskip_kernel): the same chunks up to layer 7, the sigma tile
+// by itself as above (BODY_SIG, 2 chunks), then layer 8's four rgb tiles as a body of their own (BODY_RGB: 4 x 36 quads = 4.5
+// chunks, chunk-aligned like every body: 5) -- one chunk more than the full stream
+constexpr int kHChunksRgb = (4 * kHQpuLast + kHCQ - 1) / kHCQ;                               // 5
+constexpr int kHStreamChunksSkip = kHStreamChunksSig + kHChunksRgb;                          // 67
+static_assert(kHStreamChunksSkip * (size_t)kHChunkBytes == kStreamBytesF16Skip, "sigma-first stream size mismatch");
 // single-pass mode: its own stream with the hi fragments only (one quad per k-step)
 constexpr int kFChunksPE = (8 * kHStepsPE + kHCQ - 1) / kHCQ;                          // 1
 constexpr int kFChunksHid = (8 * kHStepsHid) / kHCQ;                                   // 4
@@ -108,8 +114,11 @@ constexpr int kXConstBHead = 2848;    // b_r, b_g, b_b, (unused)
 constexpr int kXConstWsig = 2864;     // [256] the sigma head's weights as floats (the trainer's backward adds its rank-1 term on the VALU)
 constexpr int kXConstFloats = 3120;
 static_assert(kXConstFloats <= kConstFloats, "xyz-only constants must fit the shared LDS carve");
-enum { BODY_HIDSIG = 4, BODY_LAST0 = 5, BODY_SIG = 6 };
+enum { BODY_HIDSIG = 4, BODY_LAST0 = 5, BODY_SIG = 6, BODY_RGB = 7 };
 static_assert(kHConstFloats <= kConstFloats, "f16x3 constants must fit the shared LDS carve");
+// the rgb-skipping kernel's vote: one word per wave behind the constants
+constexpr int kLdsVote = kLdsConst + kHConstFloats * 4;
+static_assert(kLdsVote % 16 == 0 && kLdsVote + 16 <= kLdsTotal, "the vote words must fit the shared LDS carve");
 
 // Stash / gradient-buffer stores of the fused trainer kernels: streamed out once, read back gigabytes later by the
 // weight-gradient GEMMs -- non-temporal (`global_store ... nt`): the lines do not displace the weight stream in L2

@@ -16,6 +16,9 @@
 // ends in BODY_SIG, layer 8's sigma tile by itself (same bias, same 18 k-steps in the same pass order, same register
 // as the full kernel's tile 4, so sigma is bit-identical), skips the four rgb tiles and the rgb head, and writes sigma
 // alone: raw is then a compact (M,) vector.
+// A render that reads rgb only through the pixel sums runs mlp_f16x3_rgbskip_kernel (RGBSKIP, see mlp_f16_body): layer 8 sigma
+// first, and a 128-row tile without density skips the rgb tiles (BODY_RGB) and the rgb head.  The non-finite watch then sees a
+// skipped tile's sigma but not its rgb, which is not computed.
 // Measured accuracy (tests/test_gpu_parity.py): final RGB within 1e-4 of the fp32 oracle.
 //
 // NERF_BF16 (mlp_bf16x3.hip, mlp_bf16x3_wide.hip) builds the 3-pass render kernels of this source a second time with bf16
@@ -104,9 +107,9 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
                                              frag4 (&xh)[16], frag4 (&xl)[16], frag4 (&nh)[PP ? 16 : 14], frag4 (&nl)[PP ? 16 : 14],
                                              const frag4 (&peh)[kHStepsPE], const frag4 (&pel)[kHStepsPE], const frag4 (&dh)[2],
                                              const frag4 (&dl)[2], float (&xc)[64], float& sigma_raw) {
-    constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_SIG ? 1 : BODY == BODY_HIDSIG ? 9 : BODY == BODY_LAST0 ? 4 : 8;
+    constexpr int NU = BODY == BODY_LAST ? kHTilesLast : BODY == BODY_SIG ? 1 : BODY == BODY_HIDSIG ? 9 : (BODY == BODY_LAST0 || BODY == BODY_RGB) ? 4 : 8;
     constexpr int NSTEP = BODY == BODY_PE ? kHStepsPE : (BODY == BODY_HID || BODY == BODY_HIDSIG || BODY == BODY_LAST0) ? kHStepsHid
-                          : BODY == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;   // BODY_LAST, BODY_SIG: [h7, dir]
+                          : BODY == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;   // BODY_LAST, BODY_SIG, BODY_RGB: [h7, dir]
     constexpr int SIG0 = BODY == BODY_HIDSIG ? 1 : 0;      // tiles before the first hidden tile (the leading sigma tile)
     constexpr int TPS = FAST ? 1 : 2;        // quads (A fragments) per k-step: hi [, lo]
     constexpr int QPU = TPS * NSTEP;
@@ -310,7 +313,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             constexpr bool kPend = (u == 0) && PENDING && n < 8;
             constexpr bool kPrevS = (u > SIG0) && BODY != BODY_PE && NSTEP >= 16 && n < 16;
             constexpr int et = kPend ? 7 : (u > SIG0 ? u - 1 - SIG0 : 0);      // hidden-tile index of the previous tile
-            constexpr bool kXc = (BODY == BODY_LAST || BODY == BODY_LAST0) && kPrevS;
+            constexpr bool kXc = (BODY == BODY_LAST || BODY == BODY_LAST0 || BODY == BODY_RGB) && kPrevS;
             // the leading sigma tile (row 0 = the raw density, no activation, src/NeRF.py:283) is complete after tile 0
             if constexpr (BODY == BODY_HIDSIG && u == 1 && n == 0) sigma_raw = prv[0];
             if constexpr (!FAST) {
@@ -364,7 +367,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             // contiguous in the constant region) into the accumulator it will use -- free since 2 tiles
             if constexpr (n == (NSTEP >= 12 ? 10 : 0)) {
                 if constexpr (u + 1 < NU) load_bias(bias_off_bytes + (u + 1) * 128, nxt);
-                else if constexpr (BODY != BODY_LAST && BODY != BODY_LAST0 && BODY != BODY_SIG) load_bias(bias_off_bytes + NU * 128, nxt);
+                else if constexpr (BODY != BODY_LAST && BODY != BODY_LAST0 && BODY != BODY_SIG && BODY != BODY_RGB) load_bias(bias_off_bytes + NU * 128, nxt);
             }
             // layer 0 has only 3 k-steps per tile: its epilogues go in one block per tile
             if constexpr (BODY == BODY_PE && u > 0 && n == 0) {
@@ -389,7 +392,7 @@ __device__ __forceinline__ void layer_body_h(Pipe& p, uint32_t lane16, uint32_t 
             }
         });
     });
-    if constexpr (BODY == BODY_LAST0) {
+    if constexpr (BODY == BODY_LAST0 || BODY == BODY_RGB) {
         // the last 32 features have no following chain in this body: their activation is exposed once per tile
         f32x16& lastacc = accs[(NU - 1 + ROT) & 3];
 #pragma unroll
@@ -435,9 +438,49 @@ __device__ __forceinline__ void split8(const float (&v)[8], frag4& hi, frag4& lo
     }
 }
 
-template <bool FAST, bool STASH = false, bool XYZ = false, bool SIGONLY = false>
-__device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
+// The weight ring primed for a tile that starts at chunk p.ck: the cyclic stream rewound to its start, chunks 0 .. R-2 on their
+// way into the slots of p.ck .. p.ck + R-2.  The caller waits for chunk 0 (vmcnt((kHCQ / 4) * (kHRing - 2)), then a barrier)
+// before the tile's first fragment read.  The kernel's prologue, and the rgb-skipping kernel's fast-forward past a tile's
+// rgb chunks.
+// The fast-forward calls it with no barrier of its own, which rests on two things.  (1) A wave's pieces write only its own
+// share of a slot: bytes [wave_lds, wave_lds + kHCQ / 4 KiB) of every chunk, by Pipe::voff / wave_lds -- so a wave that has
+// waited vmcnt(0) on its own pieces may aim new ones at the same slots whatever its neighbours have in flight.  (2) Every
+// body ends chunk-aligned with R-1 chunks issued beyond the one it finished (layer_body_h's closing pipe_sync_c), so behind
+// BODY_SIG the slots of p.ck .. p.ck + R-2 are exactly the ones the dropped chunks occupy and slot p.ck - 1 is the one the
+// next mid-chunk sync refills.  A change to the piece distribution or to the bodies' alignment has to revisit the skip path.
+static_assert(4 * (kHCQ / 4) * kQuadBytes == kHChunkBytes, "four waves' shares of kHCQ / 4 pieces make one chunk");
+__device__ __forceinline__ void pipe_prime(Pipe& p) {
+    p.src_next = 0;
+#pragma unroll
+    for (int c = 0; c < kHRing - 1; ++c) {
+        p.cur_src = p.wbase + (size_t)p.src_next * kHChunkBytes;
+        p.cur_dst = kLdsRing + ((p.ck + c) & (kHRing - 1)) * kHChunkBytes + p.wave_lds;
+        p.src_next += 1;
+#pragma unroll
+        for (int j = 0; j < kHCQ / 4; ++j) dma_piece(p.cur_src, p.voff + j * kQuadBytes, p.cur_dst + j * kQuadBytes);
+    }
+}
+__device__ __forceinline__ void pipe_prime_land() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kHCQ / 4) * (kHRing - 2)) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// RGBSKIP (mlp_f16x3_rgbskip_kernel; the fp16 ping-pong build with view directions, as SIGONLY): a render whose caller reads
+// no per-sample rgb needs layer 8's rgb half and the rgb head only where a sample has weight, and a sample with raw sigma <= 0
+// has alpha = 1 - exp(-0 * delta) = 0 exactly: its rgb reaches the pixel as +0 whatever it is.  The kernel therefore runs
+// layer 8 sigma first -- BODY_SIG as the sigma-only kernel has it (sigma is the bits the full kernel gives) -- and the four
+// waves then vote: if every row of the 128-row tile is empty (raw sigma <= 0, or past M; a NaN never is), the tile writes
+// {0, 0, 0, sigma}, issues no rgb MFMA, fragment read or head, drops the rgb chunks the ring had prefetched and re-primes
+// it for the next tile (pipe_prime; the landing wait hides behind that tile's front end).  Otherwise BODY_RGB runs the four
+// rgb tiles, each with the chain it has in BODY_LAST (bias as C-in, 16 hidden and 2 direction k-steps, three passes), then
+// the head and the store as in the full kernel: rgb bit-identical.  The decision is uniform across the workgroup because the
+// waves share the ring.  The non-finite watch counts a non-finite sigma on both paths; the rgb of a skipped tile is not
+// computed and so not watched.
+template <bool FAST, bool STASH = false, bool XYZ = false, bool SIGONLY = false, bool RGBSKIP = false>
+__device__ __forceinline__ void mlp_f16_body(const MlpArgs& a, unsigned long long* skip_count = nullptr) {
     static_assert(!SIGONLY || (!FAST && !STASH && !XYZ), "the sigma-only variant is a render kernel of the 3-pass network");
+    static_assert(!RGBSKIP || (!FAST && !STASH && !XYZ && !SIGONLY), "the rgb-skipping variant is a render kernel of the 3-pass network");
     // the fp16 3-pass render kernels with view directions (mlp_f16x3_kernel, mlp_f16x3_sig_kernel) ping-pong their fragment
     // sets across layers (layer_body_h's PP); every other instantiation and build keeps the copy-back schedule
 #if defined(NERF_BF16) || NERF_PE_LX != 5
@@ -463,6 +506,15 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
 
     // SIGONLY: layer 7's last tile preloads the next body's bias from kHConstBias8 (the layers' biases are contiguous), and
     // the next body is the sigma tile: its 32-float block (kHConstBiasSig) is copied there instead
+    // RGBSKIP: the sigma tile comes first and the rgb tiles after it: [sigma block (32), layer 8's bias (128)] at kHConstBias8
+    if constexpr (RGBSKIP) {
+        for (int i = tid; i < kHConstFloats / 4; i += 256) {
+            int s = i;
+            if (i >= kHConstBias8 / 4 && i < (kHConstBias8 + 32) / 4) s = i + (kHConstBiasSig - kHConstBias8) / 4;
+            else if (i >= (kHConstBias8 + 32) / 4 && i < (kHConstBiasSig + 32) / 4) s = i - 32 / 4;
+            reinterpret_cast<f32x4*>(smem + kLdsConst)[i] = reinterpret_cast<const f32x4*>(a.wconst)[s];
+        }
+    } else
     for (int i = tid; i < (XYZ ? kXConstFloats : kHConstFloats) / 4; i += 256) {
         const bool sig = SIGONLY && i >= kHConstBias8 / 4 && i < (kHConstBias8 + 32) / 4;
         reinterpret_cast<f32x4*>(smem + kLdsConst)[i] =
@@ -472,31 +524,28 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     Pipe p;
     p.ck = 0;
     p.src_next = 0;
-    p.n_chunks = XYZ ? (FAST ? kXFStreamChunks : kXStreamChunks) : SIGONLY ? kHStreamChunksSig : (FAST ? kFStreamChunks : kHStreamChunks);
+    p.n_chunks = XYZ ? (FAST ? kXFStreamChunks : kXStreamChunks) : SIGONLY ? kHStreamChunksSig : RGBSKIP ? kHStreamChunksSkip : (FAST ? kFStreamChunks : kHStreamChunks);
     p.wbase = reinterpret_cast<const char*>(a.wstream);
     p.voff = wave * (kHCQ / 4 * kQuadBytes) + lane * 16;
     p.wave_lds = wave * (kHCQ / 4 * kQuadBytes);
     __syncthreads();
     // pipeline prologue: chunks 0 .. R-2 in flight, chunk 0 landed for everyone
-#pragma unroll
-    for (int c = 0; c < kHRing - 1; ++c) {
-        p.cur_src = p.wbase + (size_t)p.src_next * kHChunkBytes;
-        p.cur_dst = kLdsRing + c * kHChunkBytes + p.wave_lds;
-        p.src_next += 1;
-#pragma unroll
-        for (int j = 0; j < kHCQ / 4; ++j) dma_piece(p.cur_src, p.voff + j * kQuadBytes, p.cur_dst + j * kQuadBytes);
-    }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kHCQ / 4) * (kHRing - 2)) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    pipe_prime(p);
+    pipe_prime_land();
 
     frag4 xh[16], xl[16], nh[kPP ? 16 : 14], nl[kPP ? 16 : 14], peh[kHStepsPE], pel[kHStepsPE], dh[2], dl[2];
     f32x16 accs[4];
     float xc[64];
     float sigma_raw = 0.f;
 
-    unsigned long long t0 = 0, t1 = 0, acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // phases 0..5 and the tile count 6 as tools/stamps.py names them; RGBSKIP: 7 = the vote, 8 = the skipped tiles' store and
+    // fast-forward, 9 = the skipped tiles
+    unsigned long long t0 = 0, t1 = 0, acc_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     (void)t0; (void)t1; (void)acc_t;
+    bool landing = false;      // RGBSKIP: the ring was re-primed behind a skipped tile and chunk 0 has not been waited for
+    (void)landing;
+    unsigned long long n_tiles = 0, n_skipped = 0;     // RGBSKIP: this workgroup's tiles, for skip_count
+    (void)n_tiles; (void)n_skipped;
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         STAMP(t0);
         const long long m = tile * 128 + wave * 32 + j;
@@ -590,6 +639,9 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
         frag4 *mk_prev_ptr = nullptr, *mk_cur_ptr = mk_of(0);
         float* st_prev = nullptr;
         float* st_cur = st_of(0);
+        if constexpr (RGBSKIP) {
+            if (landing) { pipe_prime_land(); landing = false; }
+        }
         STAMP(t1); acc_t[0] += t1 - t0;
         layer_body_h<BODY_PE, false, FAST, STASH, 0, kPP>(p, lane16, cb_h, (kHConstBias + 0 * 256) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
         STAMP(t0); acc_t[1] += t0 - t1;
@@ -639,6 +691,45 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
         } else if constexpr (SIGONLY) {
             if constexpr (kPP) layer_body_h<BODY_SIG, true, FAST, STASH, 0, true>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
             else layer_body_h<BODY_SIG, true, FAST, STASH>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, xh, xl, nh, nl, peh, pel, dh, dl, xc, sigma_raw);
+            STAMP(t1); acc_t[4] += t1 - t0;
+        } else if constexpr (RGBSKIP) {
+            static_assert(!RGBSKIP || kPP, "the rgb-skipping kernel exists in the ping-pong build only");
+            layer_body_h<BODY_SIG, true, FAST, STASH, 0, true>(p, lane16, cb_h, kHConstBias8 * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
+            STAMP(t1); acc_t[4] += t1 - t0;
+            // The vote.  A lane's row is empty if it lies past M or its raw sigma is <= 0 (false for a NaN); sigma sits in
+            // lane half 0.  One word per wave, one barrier, and the sum of the four words through readfirstlane: a scalar,
+            // the same in every wave.  (The barrier waits for no DMA: the rgb chunks stay in flight under the vote.)
+            const bool row_empty = !valid || h != 0 || sigma_raw <= 0.f;
+            const uint32_t wave_empty = __builtin_amdgcn_ballot_w64(row_empty) == ~0ull ? 1u : 0u;
+            uint32_t vote_w = kLdsVote + wave * 4, vote_r = kLdsVote;
+            frag4 votes;
+            asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(vote_w), "v"(wave_empty) : "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(votes) : "v"(vote_r) : "memory");
+            const bool skip = __builtin_amdgcn_readfirstlane(votes[0] + votes[1] + votes[2] + votes[3]) == 4u;
+            STAMP(t0); acc_t[7] += t0 - t1;
+            n_tiles += 1;
+            if (skip) {
+                n_skipped += 1;
+                if (valid && h == 0) {
+                    f32x4 out;
+                    out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; out[3] = sigma_raw;
+                    *reinterpret_cast<f32x4*>(a.raw + m * 4) = out;
+                    if (a.nonfinite && !(fabsf(sigma_raw) <= 3.0e38f)) atomicAdd(a.nonfinite, 1ull);
+                }
+                // Fast-forward to the next tile.  Every wave finished its fragment reads before the vote's barrier, and a
+                // wave's DMA pieces only ever write its own share of a slot: once its own outstanding pieces (the rgb
+                // chunks, dropped) have landed it may aim new ones at the same slots.  Nobody reads them before the landing
+                // barrier behind the next tile's front end.  The last tile of a workgroup primes nothing.
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                if (tile + gridDim.x < ntiles) {
+                    pipe_prime(p);
+                    landing = true;
+                }
+                STAMP(t1); acc_t[8] += t1 - t0; acc_t[9] += 1; acc_t[6] += 1;
+                continue;
+            }
+            layer_body_h<BODY_RGB, false, FAST, STASH, 0, true>(p, lane16, cb_h, (kHConstBias8 + 32) * 4, a.alpha, st_prev, st_cur, mk_prev_ptr, mk_cur_ptr, mk_prev, mk_cur, accs, nh, nl, xh, xl, peh, pel, dh, dl, xc, sigma_raw);
             STAMP(t1); acc_t[4] += t1 - t0;
         } else {
             st_prev = st_cur;
@@ -692,8 +783,14 @@ __device__ __forceinline__ void mlp_f16_body(const MlpArgs& a) {
     }
 #ifdef NERF_STAMPS
     if (blockIdx.x == 0 && tid == 0)
-        for (int i = 0; i < 8; ++i) g_stamps_h[i] = acc_t[i];
+        for (int i = 0; i < 10; ++i) g_stamps_h[i] = acc_t[i];
 #endif
+    if constexpr (RGBSKIP) {      // what the host's per-launch gate reads (nerf_ctx.h: RgbSkipGate; the kernel's second argument): two atomics per workgroup
+        if (skip_count && tid == 0) {
+            atomicAdd(skip_count + 0, n_tiles);
+            atomicAdd(skip_count + 1, n_skipped);
+        }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
@@ -737,6 +834,9 @@ __global__ __launch_bounds__(256, 1) void mlp_f16_stash_kernel(const MlpArgs a) 
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_xyz_kernel(const MlpArgs a) { mlp_f16_body<false, false, true>(a); }
 #if NERF_PE_LX == 5
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_sig_kernel(const MlpArgs a) { mlp_f16_body<false, false, false, true>(a); }
+__global__ __launch_bounds__(256, 1) void mlp_f16x3_rgbskip_kernel(const MlpArgs a, unsigned long long* skip_count) {
+    mlp_f16_body<false, false, false, false, true>(a, skip_count);
+}
 #endif
 __global__ __launch_bounds__(256, 1) void mlp_f16_xyz_kernel(const MlpArgs a) { mlp_f16_body<true, false, true>(a); }
 __global__ __launch_bounds__(256, 1) void mlp_f16x3_xyz_stash_kernel(const MlpArgs a) { mlp_f16_body<false, true, true>(a); }
@@ -775,6 +875,12 @@ void launch_mlp_f16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream) {
     const int grid = (int)(ntiles < (long long)num_cus ? ntiles : (long long)num_cus);
     hipLaunchKernelGGL(mlp_f16x3_sig_kernel, dim3(grid), dim3(256), kLdsTotal, stream, a);
 }
+void launch_mlp_f16x3_rgbskip(const MlpArgs& a, int num_cus, hipStream_t stream, unsigned long long* skip_count) {
+    if (a.M <= 0) return;
+    const long long ntiles = (a.M + 127) / 128;
+    const int grid = (int)(ntiles < (long long)num_cus ? ntiles : (long long)num_cus);
+    hipLaunchKernelGGL(mlp_f16x3_rgbskip_kernel, dim3(grid), dim3(256), kLdsTotal, stream, a, skip_count);
+}
 #endif
 
 #if defined(NERF_STAMPS) && NERF_PE_LX == 5
@@ -803,6 +909,8 @@ void mlp_f16x3_set_attributes() {
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
 #if NERF_PE_LX == 5
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_f16x3_sig_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_f16x3_rgbskip_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsTotal);
 #endif
 }
@@ -833,9 +941,11 @@ int h_dir_row(int v, int h, int n_angles) {   // slot v (0..15) -> row of the di
 
 // EmitW(pos_hi, pos_lo (-1 in the hi-only stream), src) for every 16-bit slot pair of the stream, EmitC(pos, src) for
 // every float of the constant region; src = index into the blob, -1 = zero padding.
-// sig_only: the sigma-only stream (3-pass, n_angles 1 or 2): layer 8 is BODY_SIG instead of BODY_LAST; same constants.
+// tail (3-pass, n_angles 1 or 2): how layer 8 is laid out -- kTailFull: BODY_LAST; kTailSig, the sigma-only stream: BODY_SIG
+// alone; kTailSigFirst, the rgb-skipping kernel's stream: BODY_SIG, then the four rgb tiles as BODY_RGB.  Same constants.
+enum { kTailFull = 0, kTailSig = 1, kTailSigFirst = 2 };
 template <class EmitW, class EmitC>
-static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c, bool sig_only = false) {
+static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c, int tail = kTailFull) {
     const bool xyz_only = n_angles == 0;
     int shapes[12][2];
     const int n_layers = layer_dims(kPeLx, kLd, n_angles, shapes);
@@ -848,7 +958,7 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c,
     }
     size_t chunk = 0;
     auto emit_body = [&](int layer, int body) {
-        const int NU = body == BODY_LAST ? kHTilesLast : body == BODY_SIG ? 1 : body == BODY_HIDSIG ? 9 : body == BODY_LAST0 ? 4 : 8;
+        const int NU = body == BODY_LAST ? kHTilesLast : body == BODY_SIG ? 1 : body == BODY_HIDSIG ? 9 : (body == BODY_LAST0 || body == BODY_RGB) ? 4 : 8;
         const int NSTEP = body == BODY_PE ? kHStepsPE : (body == BODY_HID || body == BODY_HIDSIG || body == BODY_LAST0) ? kHStepsHid
                           : body == BODY_SKIP ? kHStepsPE + kHStepsHid : kHStepsHid + kHStepsDir;
         const long long b0 = (long long)chunk * (kHChunkBytes / 2);
@@ -902,7 +1012,8 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c,
         for (int f = 0; f < 256; ++f) emit_c(kXConstWsig + f, L[11].k + f);
         return;
     }
-    emit_body(8, sig_only ? BODY_SIG : BODY_LAST);
+    emit_body(8, tail == kTailFull ? BODY_LAST : BODY_SIG);
+    if (tail == kTailSigFirst) emit_body(8, BODY_RGB);
     for (int f = 0; f < 128; ++f) emit_c(kHConstBias8 + f, L[8].b + f);
     emit_c(kHConstBiasSig + 0, L[10].b);
     for (int c = 0; c < 3; ++c)
@@ -911,7 +1022,7 @@ static void pack_f16_map(int n_angles, bool hi_only, EmitW emit_w, EmitC emit_c,
 }
 
 // stream_idx[slot] = 2 * (src + 1) + is_lo, const_idx[float] = src + 1 (nullable); 0 = padding
-static void build_gather(int n_angles, bool hi_only, bool sig_only, int32_t* stream_idx, size_t stream_bytes, int32_t* const_idx) {
+static void build_gather(int n_angles, bool hi_only, int tail, int32_t* stream_idx, size_t stream_bytes, int32_t* const_idx) {
     memset(stream_idx, 0, (stream_bytes / 2) * sizeof(int32_t));
     if (const_idx) memset(const_idx, 0, kConstFloats * sizeof(int32_t));
     pack_f16_map(n_angles, hi_only,
@@ -920,16 +1031,19 @@ static void build_gather(int n_angles, bool hi_only, bool sig_only, int32_t* str
                      stream_idx[ph] = (int32_t)(2 * (src + 1));
                      if (pl >= 0) stream_idx[pl] = (int32_t)(2 * (src + 1) + 1);
                  },
-                 [&](long long pos, long long src) { if (const_idx) const_idx[pos] = (int32_t)(src + 1); }, sig_only);
+                 [&](long long pos, long long src) { if (const_idx) const_idx[pos] = (int32_t)(src + 1); }, tail);
 }
 
 void build_f16x3_gather(int n_angles, bool hi_only, int32_t* stream_idx, int32_t* const_idx) {
     const size_t bytes = n_angles == 0 ? (hi_only ? kStreamBytesF16HiXyz : kStreamBytesF16Xyz) : (hi_only ? kStreamBytesF16Hi : kStreamBytesF16);
-    build_gather(n_angles, hi_only, false, stream_idx, bytes, const_idx);
+    build_gather(n_angles, hi_only, kTailFull, stream_idx, bytes, const_idx);
 }
 #if NERF_PE_LX == 5
 void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx) {
-    build_gather(n_angles, false, true, stream_idx, kStreamBytesF16Sig, nullptr);
+    build_gather(n_angles, false, kTailSig, stream_idx, kStreamBytesF16Sig, nullptr);
+}
+void build_f16x3_rgbskip_gather(int n_angles, int32_t* stream_idx) {
+    build_gather(n_angles, false, kTailSigFirst, stream_idx, kStreamBytesF16Skip, nullptr);
 }
 #endif
 #endif   // NERF_BF16

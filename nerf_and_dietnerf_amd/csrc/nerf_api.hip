@@ -186,6 +186,12 @@ int ensure_render_tables(nerf_ctx* c) {
 int repack_render_streams(nerf_ctx* c, int which, const float* dev_blob) {
     if (int r = ensure_render_tables(c)) return r;
     NetWeights& n = c->net[which];
+    {   // new weights: what the rgb-skipping kernel's gate knew is about the old ones (a copy still in flight included)
+        RgbSkipGate& g = c->skip_gate[which];
+        g.full_left = g.since_copy = 0;
+        g.known = false;
+        g.discard = g.pending;
+    }
     StreamDesc d[kStreamKinds];
     render_streams(c->cfg.n_pos_enc_xyz, c->cfg.n_angles, which, d);
     for (int k = 0; k < kStreamKinds; ++k) {
@@ -209,40 +215,45 @@ namespace {
 // The kernel that renders a network of `cfg` in `precision`: its operand stream, its constant block and its launcher.
 // want_sigma asks for the sigma-only kernel (f16x3 / bf16x3, the kLx build, n_angles 1 or 2; the coarse network alone keeps its
 // stream); sigma_only says whether that is what came back: raw then receives sigma alone, (M,) floats.
+// rgb_unread says that nothing reads the rgb of a sample whose weight is exactly 0 (the composite's pixel sum is the only
+// reader: no rgb_samples): f16x3, the kLx build and n_angles 1 or 2 then render with the rgb-skipping kernel (mlp_f16x3.hip),
+// either network; same raw layout, same pixels.
 struct RenderKernel {
     StreamKind stream;
     ConstBlock cst;
-    void (*launch)(const MlpArgs& a, int num_cus, hipStream_t s, bool xyz_only);
+    void (*launch)(const MlpArgs& a, int num_cus, hipStream_t s, bool xyz_only, unsigned long long* skip_count);   // (the last: rgb-skipping kernel only)
     bool sigma_only;
 };
 // -> 0; 1: the config has no kernel of that precision; 2: no such precision (nerf_last_error() says which, either way)
-int pick_render_kernel(const nerf_config& cfg, int precision, bool want_sigma, RenderKernel* k) {
+int pick_render_kernel(const nerf_config& cfg, int precision, bool want_sigma, RenderKernel* k, bool rgb_unread = false) {
     const bool wide_pe = cfg.n_pos_enc_xyz > kLx, sig = want_sigma && !wide_pe && cfg.n_angles != 0;
+    const bool skip = rgb_unread && !wide_pe && cfg.n_angles != 0;
     switch (precision) {
     case NERF_PRECISION_FP32:
         if (wide_pe)
             return fail("n_pos_enc_dim_xyz %d (> %d) renders with the 16-bit-core kernels only: precision f16x3, bf16x3 or f16, not fp32",
                         cfg.n_pos_enc_xyz, kLx);
-        *k = {kFp32, kConstFp32, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_fp32(a, n, s, x); }, false};
+        *k = {kFp32, kConstFp32, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { launch_mlp_fp32(a, n, s, x); }, false};
         return 0;
     case NERF_PRECISION_F16X3:
-        if (sig) *k = {kF16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { launch_mlp_f16x3_sig(a, n, s); }, true};
-        else if (wide_pe) *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { wide::launch_mlp_f16x3(a, n, s, false, x); }, false};
-        else *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_f16x3(a, n, s, false, x); }, false};
+        if (sig) *k = {kF16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool, unsigned long long*) { launch_mlp_f16x3_sig(a, n, s); }, true};
+        else if (skip) *k = {kF16x3Skip, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool, unsigned long long* sc) { launch_mlp_f16x3_rgbskip(a, n, s, sc); }, false};
+        else if (wide_pe) *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { wide::launch_mlp_f16x3(a, n, s, false, x); }, false};
+        else *k = {kF16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { launch_mlp_f16x3(a, n, s, false, x); }, false};
         return 0;
     case NERF_PRECISION_F16: {
         // two sample tiles per wave (half the weight stream per row) unless NERF_F16_TILES=1 asks for the one-tile kernel;
         // the xyz-only network and the wide-PE build have the one-tile variant only
         static const bool one_tile = [] { const char* e = getenv("NERF_F16_TILES"); return e && e[0] == '1'; }();
-        if (wide_pe) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { wide::launch_mlp_f16x3(a, n, s, true, x); }, false};
-        else if (cfg.n_angles != 0 && !one_tile) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { launch_mlp_f16_2t(a, n, s); }, false};
-        else *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { launch_mlp_f16x3(a, n, s, true, x); }, false};
+        if (wide_pe) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { wide::launch_mlp_f16x3(a, n, s, true, x); }, false};
+        else if (cfg.n_angles != 0 && !one_tile) *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool, unsigned long long*) { launch_mlp_f16_2t(a, n, s); }, false};
+        else *k = {kF16Hi, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { launch_mlp_f16x3(a, n, s, true, x); }, false};
         return 0;
     }
     case NERF_PRECISION_BF16X3:
-        if (sig) *k = {kBf16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool) { bf16::launch_mlp_bf16x3_sig(a, n, s); }, true};
-        else if (wide_pe) *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { bf16::wide::launch_mlp_bf16x3(a, n, s, x); }, false};
-        else *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x) { bf16::launch_mlp_bf16x3(a, n, s, x); }, false};
+        if (sig) *k = {kBf16x3Sig, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool, unsigned long long*) { bf16::launch_mlp_bf16x3_sig(a, n, s); }, true};
+        else if (wide_pe) *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { bf16::wide::launch_mlp_bf16x3(a, n, s, x); }, false};
+        else *k = {kBf16x3, kConst16, [](const MlpArgs& a, int n, hipStream_t s, bool x, unsigned long long*) { bf16::launch_mlp_bf16x3(a, n, s, x); }, false};
         return 0;
     }
     fail("unknown precision %d", precision);
@@ -290,7 +301,7 @@ int run_mlp(nerf_ctx* c, int which, const RenderKernel& k, const float* in_a, co
         c->timed_rows += M;
         HIP_OK(hipEventRecord(e0, c->stream));
     }
-    k.launch(a, c->num_cus, c->stream, c->cfg.n_angles == 0);
+    k.launch(a, c->num_cus, c->stream, c->cfg.n_angles == 0, k.stream == kF16x3Skip ? c->skip_gate[which].dev : nullptr);
     if (c->timing) HIP_OK(hipEventRecord(e1, c->stream));
     HIP_OK(hipGetLastError());
     return 0;
@@ -378,6 +389,51 @@ int network_pass(nerf_ctx* c, int which, const RenderKernel& k, const float* o, 
     return r;
 }
 
+// The per-launch gate of the rgb-skipping kernel (nerf_ctx.h: RgbSkipGate).  rgb_skip_wanted, before a launch that may use it:
+// takes in a counter copy whose event has completed, and says whether this launch runs that kernel (*want) or, the network's
+// skipped share having stayed under 1 / kMinShareDen, the full one.  rgb_skip_launched, behind a launch that used it: sends
+// the counters to the host unless a copy is in flight or a share is known and fewer than kCopyEvery launches have passed.
+// Neither waits for the device.
+int rgb_skip_wanted(nerf_ctx* c, int which, bool* want) {
+    RgbSkipGate& g = c->skip_gate[which];
+    if (!g.dev) {
+        HIP_OK(hipMalloc((void**)&g.dev, 2 * sizeof(unsigned long long)));
+        HIP_OK(hipMemset(g.dev, 0, 2 * sizeof(unsigned long long)));
+        HIP_OK(hipHostMalloc((void**)&g.host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_OK(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
+    }
+    if (g.pending) {
+        const hipError_t e = hipEventQuery(g.ev);
+        if (e == hipErrorNotReady) (void)hipGetLastError();      // still on its way: not an error to keep
+        else if (e != hipSuccess) HIP_OK(e);
+        else {
+            g.pending = false;
+            const unsigned long long tiles = g.host[0] - g.seen[0], skipped = g.host[1] - g.seen[1];
+            g.seen[0] = g.host[0]; g.seen[1] = g.host[1];
+            if (tiles > 0 && !g.discard) {
+                g.known = true;
+                if (skipped * RgbSkipGate::kMinShareDen < tiles) {
+                    g.full_left = RgbSkipGate::kFullRun;
+                    g.known = false;                             // the probe behind the full run reports at once
+                }
+            }
+            g.discard = false;
+        }
+    }
+    *want = g.full_left == 0;
+    if (g.full_left > 0) --g.full_left;
+    return 0;
+}
+int rgb_skip_launched(nerf_ctx* c, int which) {
+    RgbSkipGate& g = c->skip_gate[which];
+    if (g.pending || (g.known && ++g.since_copy < RgbSkipGate::kCopyEvery)) return 0;
+    g.since_copy = 0;
+    HIP_OK(hipMemcpyAsync(g.host, g.dev, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipEventRecord(g.ev, c->stream));
+    g.pending = true;
+    return 0;
+}
+
 // render_rays on device pointers
 // A coarse pass whose only output is the weights (the coarse pass of NeRF.render) runs the sigma-only network and the
 // weights-only composite where pick_render_kernel has one: the weights depend on sigma alone and come out bit-identical.
@@ -386,7 +442,12 @@ int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, cons
     const bool weights_only = outs.weights && !outs.rgb && !outs.cumprod && !outs.alpha && !outs.rgb_samples && !outs.z &&
                               !outs.depth;
     RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, which == NERF_NET_COARSE && weights_only, &k)) return 1;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, which == NERF_NET_COARSE && weights_only, &k, outs.rgb && !outs.rgb_samples)) return 1;
+    if (k.stream == kF16x3Skip) {      // the gate: a network that skips next to nothing runs the full kernel, same bits
+        bool want = true;
+        if (int r = rgb_skip_wanted(c, which, &want)) return r;
+        if (!want && pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    }
     if (k.sigma_only) {
         if (int r = ensure(c, c->b_raw, (size_t)N * S * sizeof(float))) return r;
         float* sigma = (float*)c->b_raw.p;
@@ -398,6 +459,7 @@ int dev_render_rays(nerf_ctx* c, int which, const float* o, const float* d, cons
     if (int r = ensure(c, c->b_raw, (size_t)N * S * 4 * sizeof(float))) return r;
     float* raw = (float*)c->b_raw.p;
     if (int r = network_pass(c, which, k, o, d, z, N, S, raw)) return r;
+    if (k.stream == kF16x3Skip) if (int r = rgb_skip_launched(c, which)) return r;
     launch_composite(raw, z, N, S, outs.rgb, outs.weights, outs.cumprod, outs.alpha, outs.rgb_samples, outs.depth,
                      c->stream);
     if (outs.z && outs.z != z)
@@ -503,11 +565,31 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     for (hipEvent_t e : c->copy_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->cull_ev) (void)hipEventDestroy(e);
     if (c->cull_rows) (void)hipHostFree(c->cull_rows);
+    for (RgbSkipGate& g : c->skip_gate) {
+        if (g.pending) (void)hipEventSynchronize(g.ev);
+        if (g.ev) (void)hipEventDestroy(g.ev);
+        if (g.host) (void)hipHostFree(g.host);
+        if (g.dev) (void)hipFree(g.dev);
+    }
     comm_free(c);
     train_free(c);
     if (c->nonfinite) (void)hipFree(c->nonfinite);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
+}
+
+// Debug entry (not part of include/nerf_mi355.h): the rgb-skipping kernel's counters of network `which` after the ctx stream has
+// drained -- out[0] the 128-row tiles it ran, out[1] those it skipped, both cumulative -- and out[2], the launches the gate
+// still sends to the full kernel.  What tests/test_gpu_rgb_skip.py reads to see which kernel a render ran.
+extern "C" int nerf_debug_rgb_skip_counts(nerf_ctx* c, int which, unsigned long long* out) {
+    ENTER(c);
+    if ((which != 0 && which != 1) || !out) return fail("nerf_debug_rgb_skip_counts: bad argument");
+    const RgbSkipGate& g = c->skip_gate[which];
+    out[0] = out[1] = 0;
+    out[2] = (unsigned long long)g.full_left;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (g.dev) HIP_OK(hipMemcpy(out, g.dev, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int nerf_ctx_synchronize(nerf_ctx* c) {

@@ -37,6 +37,26 @@ struct NetWeights {
 // The render path keeps one on the ctx, the trainer one per TPass: a slot's backward pass reads it long after its forward pass.
 struct SampleCompaction { DevBuf mask, first; long long rows = -1; };   // rows < 0: no compaction, every sample ran
 
+// Per-launch gate of the rgb-skipping f16x3 kernel (mlp_f16x3.hip), one per network.  That kernel adds the tiles it ran and
+// the tiles it skipped to `dev`; a copy of the two counters travels to the page-locked `host` behind a launch, and once its event
+// has completed the host knows the share of skipped tiles of the launches since the previous copy.  A network whose share
+// stays under kMinShare pays the vote for nothing (a trained scene: 0.002), so its next kFullRun launches run the full kernel
+// and the one after them probes again.  Both kernels give the same bits, so the gate can change speed and nothing else.
+// Reset with the weights (repack_render_streams).
+struct RgbSkipGate {
+    static constexpr int kFullRun = 63;          // launches on the full kernel between two probes
+    static constexpr int kCopyEvery = 8;         // launches of the rgb-skipping kernel between two copies once a share is known
+    static constexpr unsigned kMinShareDen = 4;  // kMinShare = 1 / 4: a skipped tile saves ~5 %, one not skipped costs ~1.8 %
+    unsigned long long* dev = nullptr;           // {tiles, skipped}, cumulative since the weights were loaded
+    unsigned long long* host = nullptr;
+    hipEvent_t ev = nullptr;
+    bool pending = false;                        // a copy is in flight (host is not to be read)
+    bool discard = false;                        // ... and it counts launches of weights since replaced: no verdict from it
+    unsigned long long seen[2] = {0, 0};         // the counters at the previous completed copy
+    int full_left = 0, since_copy = 0;
+    bool known = false;                          // a share has been seen since the reset
+};
+
 struct TrainState;   // train_api.hip
 struct CommState;    // comm_api.hip
 
@@ -102,6 +122,7 @@ struct nerf_ctx {
     size_t ev_used = 0;
     long long timed_rows = 0;
     unsigned long long* nonfinite = nullptr;   // device counter fed by the MLP kernels
+    nerf::RgbSkipGate skip_gate[2];            // nerf_api.hip: rgb_skip_wanted / rgb_skip_launched
     nerf::TrainState* train = nullptr;         // optimizer state + training buffers (nerf_train_begin)
     nerf::CommState* comm = nullptr;           // RCCL communicator + slab buffers (nerf_comm_init)
 };

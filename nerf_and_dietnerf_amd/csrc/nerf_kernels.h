@@ -56,6 +56,7 @@ constexpr size_t kStreamBytesXyzF32 = size_t(142) * kChunkBytes;   // the xyz-on
 constexpr size_t kStreamBytesF16 = size_t(66) * 32 * kQuadBytes;   // f16x3 stream: 66 chunks of 32 KiB (mlp_f16x3.hip)
 constexpr size_t kStreamBytesF16Hi = size_t(33) * 32 * kQuadBytes; // single-pass fp16 stream: hi fragments only
 constexpr size_t kStreamBytesF16Sig = size_t(62) * 32 * kQuadBytes; // f16x3 sigma-only stream (coarse render pass)
+constexpr size_t kStreamBytesF16Skip = size_t(67) * 32 * kQuadBytes; // f16x3 sigma-first stream (rgb-skipping render pass)
 constexpr size_t kStreamBytesF16Xyz = size_t(73) * 32 * kQuadBytes;    // the xyz-only network's streams (12 Dense layers)
 constexpr size_t kStreamBytesF16HiXyz = size_t(37) * 32 * kQuadBytes;
 
@@ -116,6 +117,14 @@ void mlp_f16x3_set_attributes();
 // stream (kStreamBytesF16Sig) ends in layer 8's sigma tile, its constants are the full stream's
 void launch_mlp_f16x3_sig(const MlpArgs& a, int num_cus, hipStream_t stream);
 void build_f16x3_sig_gather(int n_angles, int32_t* stream_idx /* kStreamBytesF16Sig / 2 */);
+// rgb-skipping render (3-pass, n_angles 1 or 2, the kLx build only), for a caller that reads no per-sample rgb: a.raw as the
+// full kernel's, except that a 128-row tile whose every row has raw sigma <= 0 (or lies past M) is written {0, 0, 0, sigma}
+// without its rgb being computed -- such a row has alpha = 0 exactly and its rgb reaches no pixel.  Its stream
+// (kStreamBytesF16Skip) holds layer 8 sigma tile first, its constants are the full stream's.
+// skip_count (nullable; a kernel argument of its own, so MlpArgs and with it every other kernel's argument layout stay as they
+// are): [0] += the 128-row tiles the launch ran, [1] += those it skipped
+void launch_mlp_f16x3_rgbskip(const MlpArgs& a, int num_cus, hipStream_t stream, unsigned long long* skip_count = nullptr);
+void build_f16x3_rgbskip_gather(int n_angles, int32_t* stream_idx /* kStreamBytesF16Skip / 2 */);
 
 // mlp_f16x3_wide.hip -- the same entry points for networks with n_pos_enc_dim_xyz 6..10: kernels that encode kLxWide octaves,
 // gather tables for the (kLxWide, kLd) blob layout (same stream sizes).  No exact-fp32 render kernel exists for them.
@@ -146,7 +155,7 @@ inline int pe_layout_lx(int lx) { return lx > kLx ? kLxWide : kLx; }
 // Every stream is a gather table over the weight blob plus one device re-pack (launch_repack).  The re-pack after a weight
 // load and after optimizer steps (nerf_api.hip: repack_render_streams), kernel choice (pick_render_kernel) and the
 // host-sanitizer tool (tools/pack_asan_test.cpp) all walk render_streams(); none of them names a stream on its own.
-enum StreamKind { kF16x3, kF16Hi, kBf16x3, kF16x3Sig, kBf16x3Sig, kFp32, kStreamKinds };   // in re-pack order
+enum StreamKind { kF16x3, kF16Hi, kBf16x3, kF16x3Sig, kBf16x3Sig, kFp32, kF16x3Skip, kStreamKinds };   // in re-pack order
 enum ConstBlock { kConstFp32, kConst16, kConstBlocks };   // the fp32 kernel's constants / the ones every 16-bit kernel reads
 enum StreamElem { kElemF16, kElemBf16, kElemF32 };        // what a slot holds: an fp16 or bf16 hi / lo part, or the fp32 value
 struct StreamDesc {
@@ -156,7 +165,8 @@ struct StreamDesc {
     StreamElem elem;     // ... and what it rounds a gathered weight to
 };
 // the streams network `which` (0 = coarse, 1 = fine) of an (lx, n_angles) config keeps.  Wide-PE networks (lx > kLx) have no
-// fp32 and no sigma-only streams; xyz-only networks the ...Xyz sizes and no sigma-only streams; sigma-only: the coarse network
+// fp32 and no sigma-only streams; xyz-only networks the ...Xyz sizes and no sigma-only streams; sigma-only: the coarse network;
+// the sigma-first stream of the rgb-skipping kernel: either network that has view directions and the kLx build
 inline void render_streams(int lx, int n_angles, int which, StreamDesc d[kStreamKinds]) {
     const bool wd = lx > kLx, xyz = n_angles == 0;
     const size_t b3 = xyz ? kStreamBytesF16Xyz : kStreamBytesF16, b1 = xyz ? kStreamBytesF16HiXyz : kStreamBytesF16Hi;
@@ -167,6 +177,7 @@ inline void render_streams(int lx, int n_angles, int which, StreamDesc d[kStream
     d[kF16x3Sig] = {bs, kConst16, kF16x3Sig, kElemF16};
     d[kBf16x3Sig] = {bs, kConst16, kF16x3Sig, kElemBf16};
     d[kFp32] = {bf, kConstFp32, kFp32, kElemF32};
+    d[kF16x3Skip] = {!wd && !xyz ? kStreamBytesF16Skip : 0, kConst16, kF16x3Skip, kElemF16};
 }
 // The table builder of a kind that is its own table source: stream_idx (bytes / 2 entries, the fp32 kind: bytes / 4), written
 // for the (pe_layout_lx(lx), kLd) blob; -> whether the kind owns its constant block, i.e. const_idx (kConstFloats entries) was
@@ -174,6 +185,7 @@ inline void render_streams(int lx, int n_angles, int which, StreamDesc d[kStream
 inline bool build_stream_gather(int lx, int n_angles, StreamKind k, int32_t* stream_idx, int32_t* const_idx) {
     if (k == kFp32) { build_fp32_gather(n_angles, stream_idx, const_idx); return true; }
     if (k == kF16x3Sig) { build_f16x3_sig_gather(n_angles, stream_idx); return false; }
+    if (k == kF16x3Skip) { build_f16x3_rgbskip_gather(n_angles, stream_idx); return false; }
     (lx > kLx ? wide::build_f16x3_gather : build_f16x3_gather)(n_angles, k == kF16Hi, stream_idx, k == kF16x3 ? const_idx : nullptr);
     return k == kF16x3;
 }

@@ -2,10 +2,11 @@
 // recorded hashes.  It walks the render path's stream table (nerf_kernels.h::render_streams, build_stream_tables) and the
 // trainer's backward tables: every table has exactly the size its stream lists, so a write past it is reported; every index
 // must lie in the network's own blob; and the 64-bit FNV-1a hash of every table must be the one listed in the file given
-// as argument (tests/golden/stream_table_hashes.txt, recorded from the host packers these tables replaced).
+// as arguments (tests/golden/stream_table_hashes.txt, recorded from the host packers these tables replaced, and
+// tests/golden/stream_table_hashes_rgbskip.txt, the sigma-first stream's).
 //   hipcc -fsanitize=address -fno-gpu-sanitize -O1 -g --offload-arch=gfx950 -std=c++17 -I. tools/pack_asan_test.cpp \
 //         weight_tables.hip mlp_fp32.hip mlp_f16x3.hip mlp_f16x3_wide.hip mlp_bwd_f16x3.hip -o pack_asan \
-//         && ./pack_asan ../../tests/golden/stream_table_hashes.txt
+//         && ./pack_asan ../../tests/golden/stream_table_hashes.txt ../../tests/golden/stream_table_hashes_rgbskip.txt
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -35,14 +36,16 @@ static void check(const std::string& key, const std::vector<int32_t>& v, bool f1
 }
 
 int main(int argc, char** argv) {
-    if (argc != 2) { printf("usage: %s stream_table_hashes.txt\n", argv[0]); return 2; }
-    std::ifstream in(argv[1]);
-    for (std::string line; std::getline(in, line);) {
-        const size_t sp = line.rfind(' ');
-        if (sp != std::string::npos) g_want[line.substr(0, sp)] = line.substr(sp + 1);
+    if (argc < 2) { printf("usage: %s stream_table_hashes.txt [more hash files]\n", argv[0]); return 2; }
+    for (int f = 1; f < argc; ++f) {
+        std::ifstream in(argv[f]);
+        for (std::string line; std::getline(in, line);) {
+            const size_t sp = line.rfind(' ');
+            if (sp != std::string::npos) g_want[line.substr(0, sp)] = line.substr(sp + 1);
+        }
     }
     if (g_want.empty()) { printf("no hashes in %s\n", argv[1]); return 2; }
-    static const char* kKind[kStreamKinds] = {"f16x3", "f16hi", "bf16x3", "f16x3sig", "bf16x3sig", "fp32"};
+    static const char* kKind[kStreamKinds] = {"f16x3", "f16hi", "bf16x3", "f16x3sig", "bf16x3sig", "fp32", "f16x3skip"};
     static const char* kBlock[kConstBlocks] = {"cst_fp32", "cst_16"};
     for (int lx : {5, 3, 10, 8})
         for (int ld : {4, 2})

@@ -3,6 +3,8 @@
 // (build_stream_tables).  Host code only; the device half is aux_kernels.hip::launch_repack.
 #include "nerf_kernels.h"
 
+#include <string.h>
+
 #include <algorithm>
 
 namespace nerf {
@@ -118,3 +120,28 @@ void build_stream_tables(int lx, int ld, int n_angles, StreamTables& t) {
 }
 
 }  // namespace nerf
+
+// Debug entry (not part of include/nerf_mi355.h; host only, no device is touched): the 64-bit FNV-1a hash of the gather table
+// of stream kind `kind` of network `which` of an (lx, ld, n_angles) config, over its int32 entries' bytes in little-endian
+// order -- the hash tests/golden/stream_table_hashes*.txt record, the kind by the name those files give it.  0: that network
+// keeps no such stream of its own; ~0: no kind of that name.
+extern "C" unsigned long long nerf_debug_stream_table_hash(int lx, int ld, int n_angles, int which, const char* kind_name) {
+    using namespace nerf;
+    static const char* kNames[kStreamKinds] = {"f16x3", "f16hi", "bf16x3", "f16x3sig", "bf16x3sig", "fp32", "f16x3skip"};
+    static_assert(kF16x3 == 0 && kF16Hi == 1 && kBf16x3 == 2 && kF16x3Sig == 3 && kBf16x3Sig == 4 && kFp32 == 5 && kF16x3Skip == 6,
+                  "kNames follows StreamKind");
+    int kind = -1;
+    for (int k = 0; k < kStreamKinds; ++k) if (kind_name && !strcmp(kind_name, kNames[k])) kind = k;
+    if (kind < 0) return ~0ull;
+    if (which != 0 && which != 1) return 0;
+    StreamDesc d[kStreamKinds];
+    render_streams(lx, n_angles, which, d);
+    if (!d[kind].bytes || d[kind].table != kind) return 0;
+    StreamTables t;
+    build_stream_tables(lx, ld, n_angles, t);
+    const size_t n = d[kind].bytes / (d[kind].elem != kElemF32 ? 2 : 4);
+    unsigned long long h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n; ++i)
+        for (int b = 0; b < 4; ++b) { h ^= ((uint32_t)t.stream[kind][i] >> (8 * b)) & 0xffu; h *= 0x100000001b3ull; }
+    return h;
+}
