@@ -34,7 +34,8 @@ extern "C" {
  * occupancy-grid entries (nerf_ctx_set_occupancy_grid, nerf_ctx_get_occupancy_grid, nerf_occupancy_bake,
  * nerf_ray_occupancy_bounds) and the mesh entries (nerf_density_lattice, nerf_isosurface, nerf_isosurface_fetch,
  * nerf_mesh_colors) and the distortion-loss entries (nerf_train_set_distortion_weights, nerf_train_read_distortion_sums,
- * nerf_distortion_loss), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_distortion_loss) and the radiance-volume entries (nerf_radiance_lattice, nerf_volume_sample, nerf_volume_march,
+ * nerf_volume_render_image), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -231,6 +232,56 @@ int nerf_isosurface_fetch(nerf_ctx* ctx, float* vertices, float* normals, int32_
  * surface travels against its normal; a zero normal uses (0, 0, 1) -- through the sigmoid nerf_ray_marching applies for
  * rgb_samples.  vertices, normals, rgb: (V, 3).  The directions are ignored for n_angles == 0. */
 int nerf_mesh_colors(nerf_ctx* ctx, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem);
+
+/* ---- ABI 6+, a radiance volume: the network baked to an RGB-sigma lattice, and the lattice ray-marched ---------------------
+ * The volume is an (n, n, n, 4) float32 array indexed [iz, iy, ix, channel], n in 2..512, over a box lo3 < hi3: vertex i of axis
+ * a lies at lo_a + step_a * float(i), step_a = (hi_a - lo_a) / float(n - 1), as in nerf_density_lattice.  Channels 0..2 are the
+ * colour after the sigmoid (as nerf_mesh_colors writes it), channel 3 the density after the ReLU, fmaxf(raw sigma, 0) (as
+ * nerf_ray_marching takes it).  16 bytes a vertex: 256 MiB at n = 256, 2 GiB at n = 512.  A volume is a snapshot of one
+ * network under one view direction (or one camera); nothing rebuilds it, and it is no parity mode of the renderer.
+ *
+ * nerf_radiance_lattice: nerf_density_lattice with all four channels -- the same checks, chunks, kernels, the ctx's precision
+ * and encoding window.  At most one of view_dir3 (HOST, 3 floats) and camera_c2w16 (HOST, row-major 4x4 as nerf_render_image
+ * takes it) may be given.  Neither: direction (0, 0, 1) at every vertex, as the density lattice and the occupancy bake.
+ * view_dir3: that direction at every vertex.  camera_c2w16: every vertex p gets the direction the ray generator gives the pixel
+ * whose ray passes through p: q = p - t with t = (c[3], c[7], c[11]); s = -((c[2] q_x + c[6] q_y) + c[10] q_z), float32, every
+ * operation rounded on its own; the direction is q / s (one division per component) if s > 0 and finite, otherwise that of the
+ * central ray, (-c[2], -c[6], -c[10]).  A camera is refused while the ctx's ray space is NDC (the box is then not in world
+ * space).  Directions are ignored for n_angles == 0.  Fails without a box ("a radiance lattice needs a scene box"), if the
+ * network is not loaded, if n is outside 2..512, if both view_dir3 and camera_c2w16 are given. */
+int nerf_radiance_lattice(nerf_ctx* ctx, int which, int32_t n, const float* view_dir3, const float* camera_c2w16, float* volume,
+                          int mem);
+/* nerf_volume_sample: the volume at M points (M, 3) -> out (M, 4), trilinear, one thread per point; lo3, hi3 HOST.  float32,
+ * every operation rounded on its own, no FMA.  Per axis: g = (p - lo) / step; the cell i = g >= 0 ? (g < n - 1 ? (int)floor(g)
+ * : n - 2) : 0, so a NaN lands in cell 0; f = g - float(i), clamped to [0, 1] by comparisons (a NaN stays).  The cell is in
+ * [0, n - 2] wherever the volume is read: no input, finite or not, reads outside the array.  Per channel, along x first,
+ * v00 = v000 + f_x (v100 - v000) (subtract, multiply, add), then along y, then along z.  A point outside the box takes the
+ * value of the nearest face; a NaN coordinate gives NaN. */
+int nerf_volume_sample(nerf_ctx* ctx, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
+                       int64_t M, float* out, int mem);
+/* nerf_volume_march: N rays (N, 4) through the volume.  rgb (N, 3), depth (N), opacity (N): any may be NULL, not all three.
+ * n_steps >= 1, t_min in [0, 1).  Per ray, float32, every operation rounded on its own, sequentially in k:
+ *   1. (hit, a, b) = the scene-box rule (nerf_ctx_set_scene_box, steps 1-4) on the box (lo3, hi3) and the ctx's near / far.
+ *      A ray with a non-finite component in its origin or direction is a miss.
+ *   2. No hit: rgb, depth and opacity are exact zeros.
+ *   3. D = (b - a) / float(n_steps), T = 1, sums 0.
+ *   4. k = 0 .. n_steps - 1: z_k = a + (float(k) + 0.5) D; p = o + d z_k; v = nerf_volume_sample's value at p;
+ *      e = expf(-(v.sigma D)), alpha = 1 - e, w = alpha T; rgb += w v.rgb (multiply, add); depth += w z_k;
+ *      T = T (1 - alpha); if T < t_min the ray stops after this step.
+ *   5. opacity = 1 - T.
+ * There is no 1e9 last interval: a ray may leave the box partly transparent, rgb is premultiplied, and blending it over a
+ * background by opacity is the caller's business.  D is in units of the ray parameter, like the network render's intervals
+ * (no |d| factor), so the density scale is the network's.  Stopping at t_min changes rgb and opacity by at most t_min and depth
+ * by at most t_min b (the dropped tail carries total weight T < t_min). */
+int nerf_volume_march(nerf_ctx* ctx, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
+                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
+                      int mem);
+/* nerf_volume_render_image: the march of the rays nerf_render_image prepares for the slab [ray_begin, +ray_count) of an H x W
+ * image (ray_count <= 0: the whole image) -- the ray generator and, on an NDC ctx, nerf_rays_to_ndc -- made on the device in
+ * batches; the results equal nerf_get_rays_directions (+ nerf_rays_to_ndc) + nerf_volume_march bit for bit. */
+int nerf_volume_render_image(nerf_ctx* ctx, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
+                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
+                             float* rgb, float* depth, float* opacity, int mem);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of

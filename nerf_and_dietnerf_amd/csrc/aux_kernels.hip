@@ -16,6 +16,7 @@
 // into FMAs (explicit __fmul_rn/__fadd_rn), so index selection in the sampler is bit-exact against
 // the oracle and the other outputs differ only through expf.
 #include "nerf_kernels.h"
+#include "ray_box_device.h"
 #include "sampling_device.h"
 
 #include <algorithm>
@@ -109,52 +110,12 @@ void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float
 }
 
 // ------------------------------------------------------------------------------------------------
-// Scene box: the interval of a ray (o, d) inside an axis-aligned box lo < hi, clipped to
-// [near, far].  Depths are the parameter t of o + t d; d is not normalised.  float32, every operation rounded on its own:
-//   1. per axis with d_a != 0: t0 = (lo_a - o_a) / d_a, t1 = (hi_a - o_a) / d_a, axis interval [min, max]
-//   2. per axis with d_a == 0 (either zero): no constraint if lo_a <= o_a <= hi_a, otherwise the ray misses -- a branch,
-//      not the NaN of 0 / 0, which would turn "on the face" into a miss
-//   3. tn = largest lower end, tf = smallest upper end; a = max(tn, near), b = min(tf, far)
-//   4. hit: no axis missed and b > a.  NARROWED: hit and (a > near or b < far)
-// min / max are written as comparisons: nothing hangs on how fminf / fmaxf treat NaN or the sign of zero (non-finite rays
-// are not guarded, as in rays_to_ndc).  -> narrowed; a, b are meant to be used only then.
+// Scene box: ray_box_hit / ray_box_interval, the rule and its statement, are in ray_box_device.h
+// (the volume march of volume_kernels.hip clips its rays with the same function).
 // A narrowed ray draws its depths on [a, b] with constants of its own; any other ray -- a miss, or a box that contains
 // its whole [near, far] -- keeps the host's constants and so the depths of a context without a box, bit for bit.
 // This one function decides for the depth kernel and for nerf_ray_box_bounds.
 // ------------------------------------------------------------------------------------------------
-struct BoxArgs {
-    float lo[3], hi[3];
-    float near_b, far_b;
-};
-
-// steps 1-3 and the first half of 4: -> hit; (a, b) = the ray clipped to the box and to near / far
-__device__ __forceinline__ bool ray_box_hit(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
-    const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-    float tn = -__builtin_huge_valf(), tf = __builtin_huge_valf();
-    bool miss = false;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        if (dd[ax] == 0.0f) {
-            if (!(bx.lo[ax] <= oo[ax] && oo[ax] <= bx.hi[ax])) miss = true;
-            continue;
-        }
-        const float t0 = __fdiv_rn(__fsub_rn(bx.lo[ax], oo[ax]), dd[ax]);
-        const float t1 = __fdiv_rn(__fsub_rn(bx.hi[ax], oo[ax]), dd[ax]);
-        const bool first = t0 < t1;
-        const float low = first ? t0 : t1, high = first ? t1 : t0;
-        if (low > tn) tn = low;
-        if (high < tf) tf = high;
-    }
-    *a = tn > bx.near_b ? tn : bx.near_b;
-    *b = tf < bx.far_b ? tf : bx.far_b;
-    return !miss && *b > *a;
-}
-
-__device__ __forceinline__ bool ray_box_interval(const BoxArgs& bx, const float4 o, const float4 d, float* a, float* b) {
-    const bool hit = ray_box_hit(bx, o, d, a, b);
-    return hit && (*a > bx.near_b || *b < bx.far_b);
-}
-
 // nerf_ray_box_bounds: one thread per ray.  bounds (N,2) = (a, b) of a narrowed ray, (near, far) of any other.
 __global__ void ray_box_bounds_kernel(const BoxArgs bx, const float* __restrict__ orig, const float* __restrict__ dirs,
                                       long long N, float* __restrict__ bounds, int* __restrict__ narrowed) {
@@ -164,13 +125,6 @@ __global__ void ray_box_bounds_kernel(const BoxArgs bx, const float* __restrict_
     const bool nar = ray_box_interval(bx, reinterpret_cast<const float4*>(orig)[r], reinterpret_cast<const float4*>(dirs)[r], &a, &b);
     reinterpret_cast<float2*>(bounds)[r] = nar ? make_float2(a, b) : make_float2(bx.near_b, bx.far_b);
     if (narrowed) narrowed[r] = nar ? 1 : 0;
-}
-
-static BoxArgs box_args(const SceneBox& box, float near_b, float far_b) {
-    BoxArgs bx;
-    for (int i = 0; i < 3; ++i) { bx.lo[i] = box.lo[i]; bx.hi[i] = box.hi[i]; }
-    bx.near_b = near_b; bx.far_b = far_b;
-    return bx;
 }
 
 void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,

@@ -760,6 +760,134 @@ int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_di
     return st.finish();
 }
 
+// ---- radiance volume: the network baked to an (n, n, n, 4) lattice, and the lattice ray-marched (volume_kernels.hip) ----
+int nerf_radiance_lattice(nerf_ctx* c, int which, int32_t n, const float* view_dir3, const float* camera_c2w16, float* volume,
+                          int mem) {
+    ENTER(c);
+    if (!volume) return fail("NULL argument");
+    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
+    if (view_dir3 && camera_c2w16) return fail("radiance lattice: give view_dir or camera, not both");
+    if (!c->box_on) return fail("a radiance lattice needs a scene box (nerf_ctx_set_scene_box)");
+    if (n < 2 || n > 512) return fail("radiance lattice: n must be in 2..512 (got %d)", n);
+    if (camera_c2w16 && c->ray_space == NERF_RAYS_NDC)
+        return fail("radiance lattice: camera is refused while the ray space is NDC (the scene box is not in world space)");
+    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    const float up[3] = {0.f, 0.f, 1.f};
+    const float* vd = view_dir3 ? view_dir3 : up;
+    const long long points = (long long)n * n * n;
+    const size_t pts = (size_t)std::min(points, kMeshChunk);
+    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
+    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
+    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
+    Staging st(c, mem);
+    float* out = st.out(c->b_lattice, volume, (size_t)points * 16);
+    if (st.err) return st.err;
+    float *xyz = (float*)c->b_in0.p, *view = c->cfg.n_angles != 0 ? (float*)c->b_in1.p : nullptr, *raw = (float*)c->b_raw.p;
+    const bool camera = camera_c2w16 && view;
+    for (long long begin = 0; begin < points; begin += kMeshChunk) {
+        const long long m = std::min(kMeshChunk, points - begin);
+        launch_lattice_points(c->box, n, begin, m, vd, xyz, camera ? nullptr : view, c->stream);
+        if (camera) launch_camera_view(camera_c2w16, xyz, m, view, c->stream);
+        if (int r = run_mlp(c, which, k, xyz, view, nullptr, raw, m, 1, 1)) return r;
+        launch_raw_rgba(raw, m, out + 4 * begin, c->stream);
+    }
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+// the arguments every volume call shares
+static int volume_ok(const char* what, const float* volume, int32_t n, const float* lo3, const float* hi3) {
+    if (!volume || !lo3 || !hi3) return fail("NULL argument");
+    if (n < 2 || n > 512) return fail("%s: n must be in 2..512 (got %d)", what, n);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
+            return fail("%s needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", what, a, lo3[a], hi3[a]);
+    return 0;
+}
+
+static int march_ok(int32_t n_steps, float t_min, const float* rgb, const float* depth, const float* opacity) {
+    if (n_steps < 1) return fail("volume march: n_steps must be >= 1 (got %d)", n_steps);
+    if (!(t_min >= 0.f && t_min < 1.f)) return fail("volume march: t_min must be in [0, 1) (got %g)", t_min);
+    if (!rgb && !depth && !opacity) return fail("volume march: rgb, depth and opacity are all NULL");
+    return 0;
+}
+
+int nerf_volume_sample(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
+                       int64_t M, float* out, int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume sample", volume, n, lo3, hi3)) return r;
+    if (M < 0) return fail("bad shape M=%lld", (long long)M);
+    if (M == 0) return 0;
+    if (!points || !out) return fail("NULL argument");
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* p = st.in(c->b_in0, points, (size_t)M * 12);
+    float* o = st.out(c->b_raw, out, (size_t)M * 16);
+    if (st.err) return st.err;
+    launch_volume_sample(vol, n, lo3, hi3, p, M, o, c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+int nerf_volume_march(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
+                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
+                      int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume march", volume, n, lo3, hi3)) return r;
+    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
+    if (N < 0) return fail("bad shape N=%lld", (long long)N);
+    if (N == 0) return 0;
+    if (!rays_orig || !rays_dirs) return fail("NULL argument");
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
+    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
+    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
+    if (st.err) return st.err;
+    launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb, ddepth, dopac,
+                        c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
+                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
+                             float* rgb, float* depth, float* opacity, int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume render", volume, n, lo3, hi3)) return r;
+    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
+    if (!c2w) return fail("NULL argument");
+    if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
+    const long long total = (long long)H * W;
+    if (ray_count <= 0) { ray_begin = 0; ray_count = total; }
+    if (ray_begin < 0 || ray_begin + ray_count > total) return fail("ray slab [%lld,+%lld) outside %lld rays",
+                                                                    (long long)ray_begin, (long long)ray_count, total);
+    const long long N = ray_count, batch = std::min<long long>(N, 1 << 18);
+    if (int r = ensure(c, c->b_orig, (size_t)batch * 16)) return r;
+    if (int r = ensure(c, c->b_dirs, (size_t)batch * 16)) return r;
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
+    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
+    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
+    if (st.err) return st.err;
+    float *o = (float*)c->b_orig.p, *d = (float*)c->b_dirs.p;
+    for (long long off = 0; off < N; off += batch) {      // the rays of nerf_render_image, batch by batch on the stream
+        const long long m = std::min(batch, N - off);
+        launch_raygen(c2w, fov, H, W, ray_begin + off, m, o, d, c->stream);
+        if (c->ray_space == NERF_RAYS_NDC) launch_rays_to_ndc(o, d, m, fov, c->ndc_near_plane, o, d, c->stream);
+        launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
+                            drgb ? drgb + 3 * off : nullptr, ddepth ? ddepth + off : nullptr, dopac ? dopac + off : nullptr,
+                            c->stream);
+    }
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
 int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem) {
     ENTER(c);
     if (V < 0) return fail("bad V");

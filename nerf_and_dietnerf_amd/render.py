@@ -597,6 +597,122 @@ class Context:
             return out
         return self._auto_call(run, arr.mem)
 
+    # ---- radiance volume: bake the network to an RGB-sigma lattice, ray-march the lattice (include/nerf_mi355.h:
+    # nerf_radiance_lattice has the format, nerf_volume_sample and nerf_volume_march the rules) ----
+    def radiance_lattice(self, which, n, view_dir=None, camera=None, device_out=False):
+        """Network ``which`` (0 coarse, 1 fine) at the n^3 lattice points of the scene box, n in 2..512, in the context's
+        precision: an (n, n, n, 4) float32 array indexed [iz, iy, ix, channel], channels 0..2 the colour after the sigmoid,
+        channel 3 the density after the ReLU.  At most one of ``view_dir`` (three numbers: the view direction of every vertex)
+        and ``camera`` (a (4, 4) camera-to-world matrix: every vertex gets the direction of that camera's ray through it, a
+        vertex behind the camera the central ray's; refused on an "ndc" context) may be given; neither means (0, 0, 1), the
+        density lattice's.  Directions are ignored for n_angles == 0.  The result is a snapshot of this network under these
+        directions: a numpy array, or a torch-device tensor if ``device_out`` is set (256 MiB at n = 256, 2 GiB at n = 512:
+        keep it on the device)."""
+        if view_dir is not None and camera is not None:
+            raise ValueError("radiance lattice: give view_dir or camera, not both")
+        if self.scene_box is None:
+            raise RuntimeError("a radiance lattice needs a scene box (set_scene_box)")
+        n = int(n)
+        if not 2 <= n <= 512:
+            raise ValueError(f"radiance lattice: n must be in 2..512 (got {n})")
+        if device_out:
+            import torch
+            arr = self._arrays(torch.empty(1, device=torch.device("cuda", self.cfg.device)))   # torch's current stream
+        else:
+            arr = self._arrays()
+
+        def host(x, shape, name):
+            a = np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+            if a.size != int(np.prod(shape)):
+                raise ValueError(f"{name} must have {int(np.prod(shape))} components, got {a.size}")
+            return a.reshape(shape)
+        vd = None if view_dir is None else host(view_dir, (3,), "view_dir")
+        cam = None if camera is None else host(camera, (4, 4), "camera")
+        pv, pc = None if vd is None else vd.ctypes.data, None if cam is None else cam.ctypes.data
+
+        def run():
+            out, p = arr.out((n, n, n, 4))
+            _lib.check(self.lib.nerf_radiance_lattice(self.h, int(which), n, pv, pc, p, arr.mem))
+            return out
+        return self._auto_call(run, arr.mem)
+
+    @staticmethod
+    def _volume_args(volume, lo, hi, what):
+        """(n, lo, hi as float32 (3,) arrays) of an (n, n, n, 4) volume over (lo, hi), checked as the library checks them."""
+        shape = tuple(volume.shape)
+        if len(shape) != 4 or shape[3] != 4 or shape[0] != shape[1] or shape[0] != shape[2]:
+            raise ValueError(f"volume must be an (n, n, n, 4) array, got {shape}")
+        if not 2 <= shape[0] <= 512:
+            raise ValueError(f"{what}: n must be in 2..512 (got {shape[0]})")
+        lo_a, hi_a = np.asarray(lo, np.float32).ravel(), np.asarray(hi, np.float32).ravel()
+        if lo_a.shape != (3,) or hi_a.shape != (3,):
+            raise ValueError(f"box corners must have 3 components each, got {lo_a.shape[0]} and {hi_a.shape[0]}")
+        if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
+            raise ValueError(f"{what} needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
+        return shape[0], lo_a, hi_a
+
+    @staticmethod
+    def _march_args(n_steps, t_min):
+        if int(n_steps) != n_steps or n_steps < 1:
+            raise ValueError(f"volume march: n_steps must be an integer >= 1 (got {n_steps!r})")
+        t = float(t_min)
+        if not 0.0 <= t < 1.0:                  # a NaN fails both comparisons
+            raise ValueError(f"volume march: t_min must be in [0, 1) (got {t_min!r})")
+        return int(n_steps), t
+
+    def sample_volume(self, volume, lo, hi, points):
+        """The (n, n, n, 4) ``volume`` over the box (lo, hi) at ``points`` (M, 3), trilinear -> (M, 4); numpy or torch-device
+        arrays.  A point outside the box takes the value of the nearest face, a NaN coordinate gives NaN
+        (nerf_volume_sample has the rule).  A numpy volume is staged to the device on every call: keep it on the device."""
+        arr = self._arrays(volume, points)
+        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume sample")
+        m = int(points.shape[0])
+        pvol, pp = arr.inp(volume, (n, n, n, 4)), arr.inp(points, (m, 3))
+        out, po = arr.out((m, 4))
+        _lib.check(self.lib.nerf_volume_sample(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, pp, m, po, arr.mem))
+        return out
+
+    def march_volume(self, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min=0.0):
+        """Rays (N, 4) marched through the (n, n, n, 4) ``volume`` over the box (lo, hi) in ``n_steps`` equal steps of the
+        part of [near, far] each ray spends inside the box -> (rgb (N, 3), depth (N,), opacity (N,)).  rgb is premultiplied: a
+        ray may leave the box partly transparent, and blending over a background by ``opacity`` is the caller's business.  A
+        ray that misses the box gives zeros.  ``t_min`` in [0, 1): a ray stops once its transmittance falls below it, which
+        changes rgb and opacity by at most t_min (nerf_volume_march has the rule).  A numpy volume is staged to the device on
+        every call: keep it on the device."""
+        arr = self._arrays(volume, rays_orig, rays_dirs)
+        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume march")
+        steps, t = self._march_args(n_steps, t_min)
+        nr = int(rays_orig.shape[0])
+        pvol = arr.inp(volume, (n, n, n, 4))
+        po, pd = arr.inp(rays_orig, (nr, 4)), arr.inp(rays_dirs, (nr, 4))
+        rgb, p0 = arr.out((nr, 3))
+        depth, p1 = arr.out((nr,))
+        opacity, p2 = arr.out((nr,))
+        _lib.check(self.lib.nerf_volume_march(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, po, pd, nr, steps, t, p0, p1,
+                                              p2, arr.mem))
+        return rgb, depth, opacity
+
+    def render_volume_image(self, volume, lo, hi, c2w, fov, h, w, n_steps, t_min=0.0, ray_begin=0, ray_count=0):
+        """march_volume of the rays render_image makes for camera ``c2w`` (through rays_to_ndc on an "ndc" context), generated
+        on the device -> (rgb, depth, opacity) shaped (h, w, ...), or (ray_count, ...) for a slab of rays; equal to
+        get_rays_directions + march_volume bit for bit.  A numpy volume is staged to the device on every call: keep it on the
+        device."""
+        arr = self._arrays(volume)
+        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume render")
+        steps, t = self._march_args(n_steps, t_min)
+        c2w_h = np.ascontiguousarray(c2w.detach().cpu().numpy() if _is_torch(c2w) else c2w, dtype=np.float32)
+        if c2w_h.shape != (4, 4):
+            raise ValueError("c2w must be (4,4)")
+        pvol = arr.inp(volume, (n, n, n, 4))
+        lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
+        rgb, p0 = arr.out(lead + (3,))
+        depth, p1 = arr.out(lead)
+        opacity, p2 = arr.out(lead)
+        _lib.check(self.lib.nerf_volume_render_image(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, c2w_h.ctypes.data,
+                                                     float(fov), int(h), int(w), int(ray_begin), int(ray_count), steps, t, p0,
+                                                     p1, p2, arr.mem))
+        return rgb, depth, opacity
+
     def ray_occupancy_bounds(self, rays_orig, rays_dirs):
         """Rays (N,4) -> (bounds (N,2) float32, state (N,) int32) under the context's box, grid and bounds: state 2 and the
         grid's interval, state 1 and the box's for a ray only the box narrows, state 0 and (near, far) for any other
@@ -1310,6 +1426,7 @@ class NeRF:
         # occupancy grid: an absent key (or None) leaves everything as it was
         self.grid_config = self._grid_config(render_config.get(OCCUPANCY_GRID), self.scene_box)
         self._grid_epochs = 0        # epochs fit() has run: the grid's schedule counts them
+        self._preview = None         # bake_preview: (volume on the device, lo, hi, resolution)
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_SAMPLES, False):
             self.ctx.set_sample_culling(True)
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_TRAIN_SAMPLES, False):
@@ -1400,6 +1517,40 @@ class NeRF:
             from .mesh import write_ply
             write_ply(path, mesh["vertices"], mesh["triangles"], mesh["normals"], mesh.get("colors"))
         return mesh
+
+    def bake_preview(self, resolution: int = 256, which: Optional[int] = None, view_dir=None, camera=None) -> None:
+        """Bake network ``which`` (None: the fine network if it is loaded, else the coarse one) onto a ``resolution``^3
+        RGB-sigma lattice over render_config["scene_box"] (Context.radiance_lattice) and keep it, as a device tensor together
+        with the box it was baked on, for render_preview.  Colours are those of ONE view direction (``view_dir``, default
+        (0, 0, 1)) or ONE camera (``camera``, a (4, 4) camera-to-world matrix): the preview shows no view-dependent effects
+        from any other pose and is no parity mode of render_image.  It is a snapshot, like the occupancy grid: nothing
+        rebuilds it -- training on, loading other weights or changing the box leave it as baked until this is called again.
+        16 bytes a vertex: 256 MiB at 256, 2 GiB at 512."""
+        if self.scene_box is None:
+            raise ValueError(f"bake_preview needs render_config[{SCENE_BOX!r}]")
+        if which is None:
+            which = NERF_NET_FINE if self.model_fine is not None and self.ctx.loaded[NERF_NET_FINE] else NERF_NET_COARSE
+        self._preview = None
+        volume = self.ctx.radiance_lattice(which, resolution, view_dir=view_dir, camera=camera, device_out=True)
+        if self.ctx.auto_check():            # precision "auto": the f16x3 pass overflowed, the context is in fp32 now
+            volume = self.ctx.radiance_lattice(which, resolution, view_dir=view_dir, camera=camera, device_out=True)
+        self._preview = (volume, tuple(self.scene_box[0]), tuple(self.scene_box[1]), int(resolution))
+
+    def render_preview(self, c2w, fov, h, w, n_steps: Optional[int] = None, t_min: float = 1.0 / 512.0):
+        """The baked preview seen from camera ``c2w``: (rgb (h, w, 3), depth (h, w), opacity (h, w)) as torch-device
+        tensors, by marching the volume of bake_preview in ``n_steps`` steps per ray (default 2 * resolution) with no network
+        in the loop (Context.render_volume_image).  rgb is premultiplied by opacity.  depth is a depth MAP: the mean depth of
+        what the ray met, the march's weighted sum of step depths over its opacity -- inside the ray's stretch of [near, far]
+        whatever the opacity, where the sum itself shrinks with it -- and 0 where the ray met nothing (opacity 0); it means
+        little where the opacity is tiny.  ``t_min``: a ray stops once its transmittance is below it; the default 1/512 keeps
+        the error under half an 8-bit level.  The preview is as baked: see bake_preview for what it is not."""
+        if self._preview is None:
+            raise RuntimeError("render_preview: no preview is baked (call bake_preview first)")
+        volume, lo, hi, resolution = self._preview
+        rgb, depth_sum, opacity = self.ctx.render_volume_image(volume, lo, hi, c2w, fov, h, w,
+                                                               2 * resolution if n_steps is None else n_steps, t_min)
+        depth = depth_sum.div_(opacity).masked_fill_(opacity <= 0, 0.0)      # on the device, no synchronisation
+        return rgb, depth, opacity
 
     def occupancy_grid_epoch(self) -> None:
         """dataset.fit's hook, at the start of every epoch: the grid is off during the warm-up epochs and baked again every

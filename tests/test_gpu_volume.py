@@ -1,0 +1,414 @@
+"""The radiance volume on the device: trilinear sampling against the numpy restatement of tests/volume_ref.py bit for bit, the
+bake against the public point queries (density_lattice, mesh_colors, model_predict), the march against the restatement up to
+expf, early termination, invariance under batching / host-device / the image call, the refusals, and NeRF.bake_preview /
+render_preview on the shipped checkpoint."""
+import numpy as np
+import pytest
+
+import volume_ref as V
+from test_gpu_isosurface import NET, _glorot_ctx
+from test_gpu_occupancy import GOLDEN_BOX
+from test_volume_host import HI, LO, march_bar, random_volume, rays_through_box
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+NEAR, FAR = 0.5, 4.5            # the march's context: rays from the radius-4 sphere enter near 3 and some leave past 4.5
+VIEW = (0.6, -0.48, 0.64)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=F).view(np.uint32)
+
+
+def assert_same_bits(got, want):
+    assert got.shape == want.shape and got.dtype == F, (got.shape, got.dtype, want.shape)
+    np.testing.assert_array_equal(bits(got), bits(want))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    """A context for the calls that need no network."""
+    import nerf_and_dietnerf_amd as N
+    c = N.Context(precision="fp32", near=NEAR, far=FAR)
+    yield c
+    c.close()
+
+
+# ---- 1. sampling equals the restatement bit for bit -----------------------------------------------------------------------------
+def sample_points(n, m=257, seed=0):
+    """Vertices, points on faces, points outside on every side, NaN and +-Inf coordinates, and random points in and around the
+    box -> (m, 3)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array(LO, F), np.array(HI, F)
+    vertices = V.lattice_points(LO, HI, n)
+    vertices = vertices[rng.permutation(len(vertices))[:32]]
+    inner = rng.uniform(lo, hi, (32, 3)).astype(F)
+    faces = inner.copy()
+    for k in range(len(faces)):
+        faces[k, k % 3] = (lo, hi)[(k // 3) % 2][k % 3]
+    outside = inner[:12].copy()
+    for k in range(12):
+        outside[k, k % 3] = (lo - F(0.5 + k), hi + F(0.25 + k))[(k // 3) % 2][k % 3]
+    odd = np.array([[np.nan, 0, 0], [0, np.nan, 0], [0, 0, np.nan], [np.nan, np.nan, np.nan], [np.inf, 0, 0], [0, -np.inf, 0],
+                    [0, 0, np.inf], [-np.inf, np.inf, -np.inf], [3e38, -3e38, 0]], F)
+    fixed = np.concatenate([vertices, faces, outside, odd])
+    rest = rng.uniform(lo - F(0.3), hi + F(0.3), (m - len(fixed), 3)).astype(F)
+    return np.concatenate([fixed, rest]), np.isnan(np.concatenate([fixed, rest])).any(axis=1)
+
+
+@pytest.mark.parametrize("n", [2, 3, 9])
+def test_sampling_equals_the_restatement(ctx, n):
+    v = random_volume(n, n)
+    p, has_nan = sample_points(n)
+    assert p.shape == (257, 3) and has_nan.sum() == 4
+    got = ctx.sample_volume(v, LO, HI, p)
+    want = V.sample(v, LO, HI, p)
+    assert got.shape == (257, 4) and got.dtype == F
+    np.testing.assert_array_equal(np.isnan(got).any(axis=1), has_nan)        # NaN out only for NaN in
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
+    np.testing.assert_array_equal(bits(got)[~has_nan], bits(want)[~has_nan])
+    import torch
+    dev = ctx.sample_volume(torch.as_tensor(v).cuda(), LO, HI, torch.as_tensor(p).cuda())
+    assert dev.is_cuda
+    np.testing.assert_array_equal(bits(dev.cpu().numpy())[~has_nan], bits(got)[~has_nan])
+
+
+# ---- 2. the bake, one direction -------------------------------------------------------------------------------------------------
+def check_constant_bake(c, which, n, view):
+    vol = c.radiance_lattice(which, n, view_dir=view)
+    assert vol.shape == (n, n, n, 4) and vol.dtype == F
+    sigma = c.density_lattice(which, n, view_dir=view)
+    assert_same_bits(vol[..., 3], np.maximum(sigma, F(0)))
+    pts = V.lattice_points(c.scene_box[0], c.scene_box[1], n)
+    normals = np.tile(-np.array((0.0, 0.0, 1.0) if view is None else view, F), (len(pts), 1))
+    assert_same_bits(vol[..., :3].reshape(-1, 3), c.mesh_colors(which, pts, normals))
+    assert np.unique(vol[..., 0]).size > n and (vol[..., 3] > 0).any()        # a field, not a constant
+    return vol
+
+
+@pytest.mark.parametrize("precision", ["fp32", "f16x3", "f16", "bf16x3"])
+def test_bake_constant_direction(precision):
+    c = _glorot_ctx(precision)
+    c.set_scene_box(LO, HI)
+    check_constant_bake(c, 1, 9, VIEW)
+    check_constant_bake(c, 0, 9, None)
+    import torch
+    dev = c.radiance_lattice(1, 9, view_dir=VIEW, device_out=True)
+    assert dev.is_cuda and tuple(dev.shape) == (9, 9, 9, 4)
+    assert_same_bits(dev.cpu().numpy(), c.radiance_lattice(1, 9, view_dir=VIEW))
+    c.close()
+
+
+def test_bake_across_the_chunk_seam():
+    c = _glorot_ctx("f16x3")
+    c.set_scene_box(LO, HI)
+    assert 102 ** 3 == 1061208 > 1 << 20 > 101 ** 3
+    check_constant_bake(c, 0, 102, VIEW)
+    c.close()
+
+
+def test_bake_wide_encoding_network():
+    import nerf_and_dietnerf_amd as N
+    kw = dict(n_pos_enc_xyz=10, n_pos_enc_dir=4, n_angles=2)
+    c = N.Context(precision="f16x3", **kw)
+    blob = N.glorot_blob(1, **kw)
+    blob[-1] = 0.5
+    c.load_weights(0, blob)
+    c.set_scene_box(LO, HI)
+    check_constant_bake(c, 0, 9, VIEW)
+    c.close()
+
+
+def test_bake_without_directions_ignores_them(oracle):
+    c = _glorot_ctx("fp32", n_angles=0)
+    c.set_scene_box(LO, HI)
+    plain = c.radiance_lattice(0, 5)
+    assert_same_bits(c.radiance_lattice(0, 5, view_dir=(1.0, 0.0, 0.0)), plain)
+    assert_same_bits(c.radiance_lattice(0, 5, camera=oracle.get_sphere_matrix(4.0, -30.0, 45.0, 0.0)), plain)
+    c.close()
+
+
+# ---- 3. the bake, camera mode ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision,inside", [("fp32", False), ("f16x3", False), ("f16x3", True)])
+def test_bake_camera_mode(oracle, precision, inside):
+    c = _glorot_ctx(precision)
+    c.set_scene_box(LO, HI)
+    c2w = oracle.get_sphere_matrix(0.3 if inside else 4.0, -30.0, 45.0, 10.0).astype(F)
+    n = 9
+    pts = V.lattice_points(LO, HI, n)
+    dirs = V.camera_directions(pts, c2w)
+    central = np.tile(-c2w[:3, 2], (len(pts), 1))
+    behind = (bits(dirs) == bits(central)).all(axis=1)
+    assert behind.any() == inside and not behind.all()                        # the inside camera has vertices behind it
+    raw = c.model_predict(1, pts, dirs)
+    vol = c.radiance_lattice(1, n, camera=c2w).reshape(-1, 4)
+    assert_same_bits(vol[:, 3], np.maximum(raw[:, 3], F(0)))
+    want = 1.0 / (1.0 + np.exp(-raw[:, :3].astype(np.float64)))
+    err = float(np.abs(vol[:, :3] - want).max())
+    print(f"[camera bake, {precision}, inside={inside}] max |rgb - sigmoid(model_predict)| = {err:.2e}, bar {2.0 ** -22:.2e}")
+    assert err <= 2.0 ** -22
+    # and it is not the constant-direction bake
+    assert not np.array_equal(vol[:, :3], c.radiance_lattice(1, n).reshape(-1, 4)[:, :3])
+    c.close()
+
+
+# ---- 4. the march against the restatement -----------------------------------------------------------------------------------------
+def march_rays(n_rays, seed):
+    """Hits from the radius-4 sphere (some leave past FAR), origins inside the box and close to it (cut by NEAR), misses, rays
+    with a direction component exactly 0 inside and outside that slab, one NaN ray -> (o, d, category names)."""
+    rng = np.random.default_rng(seed)
+    special_o = np.array([[0.2, -0.3, 0.1, 1], [0.0, 0.1, 0.3, 1], [0.5, 0.2, 1.6, 1],       # inside, inside, just outside
+                          [3.0, 0.0, 4.0, 1], [0.0, 0.0, 4.0, 1], [0.0, 0.0, -4.0, 1],       # three misses
+                          [0.3, 0.2, 4.0, 1], [1.5, 0.2, 4.0, 1], [0.3, 0.2, 4.0, 1],        # d_x = d_y = 0: in, out, -0.0
+                          [np.nan, 0.0, 4.0, 1]], F)
+    special_d = np.array([[0.3, 0.5, -0.8, 0], [-1, 0, 0, 0], [0.0, 0.1, -1, 0],
+                          [0, 0, -1, 0], [0, 0, 1, 0], [0, 0, -1, 0],
+                          [0, 0, -1, 0], [0, 0, -1, 0], [-0.0, -0.0, -1, 0],
+                          [0, 0, -1, 0]], F)
+    o, d = rays_through_box(n_rays - len(special_o), seed)
+    d[::5] *= F(1.7)                                                          # un-normalised directions
+    order = rng.permutation(n_rays)
+    return np.concatenate([o, special_o])[order], np.concatenate([d, special_d])[order]
+
+
+@pytest.mark.parametrize("n,n_rays", [(5, 37), (9, 257)])
+def test_march_against_the_restatement(ctx, n, n_rays):
+    v = random_volume(n, 10 + n)
+    o, d = march_rays(n_rays, n)
+    a, b, hit, _ = V.ray_box_interval(o, d, LO, HI, NEAR, FAR)
+    finite = np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1)
+    hit &= finite
+    assert (~finite).sum() == 1 and (~hit).sum() >= 5
+    assert (hit & (a == F(NEAR))).any() and (hit & (b == F(FAR))).any() and (hit & (a > F(NEAR)) & (b < F(FAR))).any()
+    assert (hit & (d[:, 0] == 0)).any() and (~hit & (d[:, 0] == 0)).any()
+    for n_steps in (1, 2, 7, 48):
+        rgb, depth, opacity = ctx.march_volume(v, LO, HI, o, d, n_steps)
+        w_rgb, w_depth, w_opacity = V.march(v, LO, HI, NEAR, FAR, o, d, n_steps)
+        assert rgb.shape == (n_rays, 3) and depth.shape == (n_rays,) and opacity.shape == (n_rays,)
+        bar = march_bar(n_steps)
+        errs = (float(np.abs(rgb - w_rgb).max()), float(np.abs(opacity - w_opacity).max()), float(np.abs(depth - w_depth).max()))
+        print(f"[march n={n}, {n_rays} rays, {n_steps} steps] rgb {errs[0]:.2e} opacity {errs[1]:.2e} (bar {bar:.2e}) "
+              f"depth {errs[2]:.2e} (bar {bar * FAR:.2e})")
+        assert errs[0] <= bar and errs[1] <= bar and errs[2] <= bar * FAR
+        for out in (rgb, depth, opacity):                                     # misses and the NaN ray: exact zeros
+            assert (bits(out)[~hit] == 0).all()
+        assert (opacity[hit] > 0).all() and (opacity <= 1).all()
+
+
+# ---- 5. termination -------------------------------------------------------------------------------------------------------------
+def test_termination(ctx):
+    tau = 1e-2
+    o, d = rays_through_box(257, 20)
+    _, b, hit, _ = V.ray_box_interval(o, d, LO, HI, NEAR, FAR)
+    dense = np.empty((3, 3, 3, 4), F)
+    dense[..., :3], dense[..., 3] = F(0.5), F(1e4)
+    for v in (random_volume(9, 21, sigma_scale=40.0), dense):
+        full = ctx.march_volume(v, LO, HI, o, d, 48)
+        again = ctx.march_volume(v, LO, HI, o, d, 48)
+        for x, y in zip(full, again):
+            assert_same_bits(x, y)
+        cut = ctx.march_volume(v, LO, HI, o, d, 48, t_min=tau)
+        assert (bits(cut[2]) != bits(full[2])).any() or v is dense            # the cut acts on the random medium
+        assert np.abs(cut[0] - full[0]).max() <= tau and np.abs(cut[2] - full[2]).max() <= tau
+        assert (np.abs(cut[1] - full[1]) <= tau * b).all()
+        assert np.isfinite(cut[0]).all() and np.isfinite(cut[1]).all()
+    assert (full[2][hit] == 1).all()                                          # sigma = 1e4: opaque after one step
+
+
+# ---- 6. invariance, bit for bit ---------------------------------------------------------------------------------------------------
+def test_march_of_halves_and_of_device_arrays(ctx):
+    import torch
+    v = random_volume(9, 30)
+    o, d = march_rays(257, 31)
+    whole = ctx.march_volume(v, LO, HI, o, d, 7)
+    first, second = ctx.march_volume(v, LO, HI, o[:128], d[:128], 7), ctx.march_volume(v, LO, HI, o[128:], d[128:], 7)
+    dev = ctx.march_volume(torch.as_tensor(v).cuda(), LO, HI, torch.as_tensor(o).cuda(), torch.as_tensor(d).cuda(), 7)
+    for k in range(3):
+        assert_same_bits(np.concatenate([first[k], second[k]]), whole[k])
+        assert dev[k].is_cuda
+        assert_same_bits(dev[k].cpu().numpy(), whole[k])
+
+
+@pytest.mark.parametrize("ndc", [False, True])
+def test_image_call_equals_rays_plus_march(oracle, ndc):
+    import nerf_and_dietnerf_amd as N
+    h, w, fov, n_steps = 13, 11, 0.6911112, 7
+    v = random_volume(9, 32)
+    if ndc:
+        c = N.Context(precision="fp32", near=0.0, far=1.0)
+        c.set_ray_space("ndc", 1.0)
+        c2w = oracle.get_sphere_matrix(0.5, 0.0, 0.0, 0.0).astype(F)           # looking down -z
+        c2w[0, 3], c2w[1, 3] = 0.03, -0.02
+        lo, hi = (-0.9, -1.0, -1.0), (1.0, 0.8, 0.7)
+    else:
+        c = N.Context(precision="fp32", near=NEAR, far=FAR)
+        c2w = oracle.get_sphere_matrix(4.0, -30.0, 45.0, 10.0).astype(F)
+        lo, hi = LO, HI
+    d = c.get_rays_directions(h, w, fov, c2w).reshape(-1, 4)
+    o = np.tile(c2w[:, 3], (h * w, 1)).astype(F)
+    if ndc:
+        o, d = c.rays_to_ndc(o, d, fov, 1.0)
+    want = c.march_volume(v, lo, hi, o, d, n_steps)
+    assert (want[2] > 0).sum() > h * w // 4                                   # the camera sees the volume
+    got = c.render_volume_image(v, lo, hi, c2w, fov, h, w, n_steps)
+    assert got[0].shape == (h, w, 3) and got[1].shape == (h, w) and got[2].shape == (h, w)
+    for k in range(3):
+        assert_same_bits(got[k].reshape(want[k].shape), want[k])
+    for begin, count in ((0, 5), (5, 40), (45, h * w - 45)):                  # slabs that split rows of 11
+        part = c.render_volume_image(v, lo, hi, c2w, fov, h, w, n_steps, ray_begin=begin, ray_count=count)
+        for k in range(3):
+            assert_same_bits(part[k], want[k][begin:begin + count])
+    import torch
+    dev = c.render_volume_image(torch.as_tensor(v).cuda(), lo, hi, c2w, fov, h, w, n_steps)
+    for k in range(3):
+        assert_same_bits(dev[k].cpu().numpy(), got[k])
+    c.close()
+
+
+# ---- 7. refusals ------------------------------------------------------------------------------------------------------------------
+def test_refusals(oracle):
+    import nerf_and_dietnerf_amd as N
+    last = N._lib.last_error
+    c = N.Context(precision="fp32", near=NEAR, far=FAR)
+    v = random_volume(3, 40)
+    o, d = rays_through_box(4, 41)
+    c2w = oracle.get_sphere_matrix(4.0, 0.0, 0.0, 0.0).astype(F)
+    lo, hi = np.array(LO, F), np.array(HI, F)
+    out = np.zeros(4 ** 3 * 4, F)
+    # the bake: box, weights, n, both directions, camera under NDC
+    with pytest.raises(RuntimeError, match="needs a scene box"):
+        c.radiance_lattice(0, 5)
+    assert c.lib.nerf_radiance_lattice(c.h, 0, 2, None, None, out.ctypes.data, 0) != 0 and "needs a scene box" in last()
+    c.set_scene_box(LO, HI)
+    with pytest.raises(RuntimeError, match="no weights loaded"):
+        c.radiance_lattice(0, 5)
+    c.load_weights(0, N.glorot_blob(0))
+    for n in (1, 513):
+        with pytest.raises(ValueError, match=r"n must be in 2\.\.512"):
+            c.radiance_lattice(0, n)
+        assert c.lib.nerf_radiance_lattice(c.h, 0, n, None, None, out.ctypes.data, 0) != 0 and "n must be in 2..512" in last()
+    with pytest.raises(ValueError, match="view_dir or camera, not both"):
+        c.radiance_lattice(0, 3, view_dir=VIEW, camera=c2w)
+    vd = np.array(VIEW, F)
+    assert c.lib.nerf_radiance_lattice(c.h, 0, 3, vd.ctypes.data, c2w.ctypes.data, out.ctypes.data, 0) != 0
+    assert "view_dir or camera, not both" in last()
+    c.set_ray_space("ndc", 1.0)
+    with pytest.raises(RuntimeError, match="camera is refused while the ray space is NDC"):
+        c.radiance_lattice(0, 3, camera=c2w)
+    c.set_ray_space("world")
+    assert c.radiance_lattice(0, 2, camera=c2w).shape == (2, 2, 2, 4)
+    # the volume calls: shape, n, box, n_steps, t_min, outputs
+    with pytest.raises(ValueError, match=r"volume must be an \(n, n, n, 4\) array"):
+        c.march_volume(v[..., :3], LO, HI, o, d, 4)
+    with pytest.raises(ValueError, match=r"volume must be an \(n, n, n, 4\) array"):
+        c.sample_volume(v[:2], LO, HI, o[:, :3])
+    with pytest.raises(ValueError, match=r"n must be in 2\.\.512"):
+        c.march_volume(np.zeros((1, 1, 1, 4), F), LO, HI, o, d, 4)
+    with pytest.raises(ValueError, match="lo < hi on every axis"):
+        c.march_volume(v, LO, (HI[0], LO[1], HI[2]), o, d, 4)
+    with pytest.raises(ValueError, match="lo < hi on every axis"):
+        c.sample_volume(v, LO, (LO[0] - 1.0, HI[1], HI[2]), o[:, :3])
+    for steps in (0, -3):
+        with pytest.raises(ValueError, match="n_steps must be"):
+            c.march_volume(v, LO, HI, o, d, steps)
+    for t in (-0.1, 1.0, 2.0, float("nan")):
+        with pytest.raises(ValueError, match=r"t_min must be in \[0, 1\)"):
+            c.march_volume(v, LO, HI, o, d, 4, t_min=t)
+        with pytest.raises(ValueError, match=r"t_min must be in \[0, 1\)"):
+            c.render_volume_image(v, LO, HI, c2w, 0.7, 4, 4, 4, t_min=t)
+    # ... and the library's own checks of the same arguments
+    res = [np.zeros(12, F), np.zeros(4, F), np.zeros(4, F)]
+
+    def march(n=3, lo=lo, hi=hi, steps=4, t_min=0.0, outs=res):
+        p = [None if x is None else x.ctypes.data for x in outs]
+        return c.lib.nerf_volume_march(c.h, v.ctypes.data, n, lo.ctypes.data, hi.ctypes.data, o.ctypes.data, d.ctypes.data, 4,
+                                       steps, t_min, p[0], p[1], p[2], 0)
+    assert march() == 0
+    assert march(outs=[None, res[1], None]) == 0
+    assert march(n=1) != 0 and "n must be in 2..512" in last()
+    assert march(n=513) != 0 and "n must be in 2..512" in last()
+    assert march(hi=lo) != 0 and "lo < hi on every axis" in last()
+    assert march(steps=0) != 0 and "n_steps must be >= 1" in last()
+    for t in (-0.1, 1.0, float("nan")):
+        assert march(t_min=t) != 0 and "t_min must be in [0, 1)" in last()
+    assert march(outs=[None, None, None]) != 0 and "rgb, depth and opacity are all NULL" in last()
+    assert c.lib.nerf_volume_render_image(c.h, v.ctypes.data, 3, lo.ctypes.data, hi.ctypes.data, c2w.ctypes.data, 0.7, 4, 4, 0, 0,
+                                          4, 0.0, None, None, None, 0) != 0 and "all NULL" in last()
+    assert c.lib.nerf_volume_sample(c.h, v.ctypes.data, 600, lo.ctypes.data, hi.ctypes.data, o.ctypes.data, 4, out.ctypes.data,
+                                    0) != 0 and "n must be in 2..512" in last()
+    c.close()
+    # the model: no box, no bake
+    m = N.NeRF(NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 16}, 2.0, 6.0, precision="fp32")
+    with pytest.raises(ValueError, match="scene_box"):
+        m.bake_preview(8)
+    with pytest.raises(RuntimeError, match="bake_preview first"):
+        m.render_preview(c2w, 0.7, 4, 4)
+    m.ctx.close()
+    boxed = N.NeRF(NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(LO), list(HI)]}, 2.0, 6.0,
+                   precision="fp32")
+    with pytest.raises(RuntimeError, match="no weights loaded"):
+        boxed.bake_preview(8)
+    with pytest.raises(RuntimeError, match="bake_preview first"):
+        boxed.render_preview(c2w, 0.7, 4, 4)
+    boxed.ctx.close()
+
+
+# ---- 8. the shipped checkpoint ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def preview(golden_ckpt):
+    """bake_preview(64, camera = the golden test pose) of the fine network in f16x3 and render_preview at the fixture's
+    resolution, once for the tests below -> (model, c2w, fov, (rgb, depth, opacity) as numpy)."""
+    import nerf_and_dietnerf_amd as N
+    near, far, fov = float(golden_ckpt["near"]), float(golden_ckpt["far"]), float(golden_ckpt["fov"])
+    rc = {"n_render_samples_coarse": 64, "n_render_samples_fine": 128, "scene_box": [list(GOLDEN_BOX[0]), list(GOLDEN_BOX[1])]}
+    m = N.NeRF(NET, rc, near, far, precision="f16x3")
+    m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
+    c2w = golden_ckpt["c2w_test"]
+    h, w = golden_ckpt["img_test"].shape[:2]
+    m.bake_preview(64, camera=c2w)
+    frame = tuple(x.cpu().numpy() for x in m.render_preview(c2w, fov, h, w))
+    yield m, c2w, fov, frame
+    m.ctx.close()
+
+
+def test_preview_of_the_shipped_checkpoint(golden_ckpt, preview):
+    m, c2w, fov, (rgb, depth, opacity) = preview
+    near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
+    h, w = golden_ckpt["img_test"].shape[:2]
+    volume, lo, hi, resolution = m._preview
+    assert volume.is_cuda and tuple(volume.shape) == (64, 64, 64, 4) and resolution == 64 and (lo, hi) == GOLDEN_BOX
+    assert rgb.shape == (h, w, 3) and depth.shape == (h, w) and opacity.shape == (h, w)
+    assert np.isfinite(rgb).all() and np.isfinite(depth).all() and np.isfinite(opacity).all()
+    assert opacity.min() >= 0.0 and opacity.max() <= 1.0 and (opacity > 0.5).sum() > 100
+    assert rgb.min() >= 0.0 and (rgb.max(axis=2) <= opacity + 2 * march_bar(128)).all()           # premultiplied: sum of w c, c <= 1
+    # the preview's depth is a map: 0 where the ray met nothing, inside [near, far] everywhere else
+    assert (depth[opacity == 0] == 0).all()
+    seen = opacity > 1e-3
+    assert (depth[seen] >= near).all() and (depth[seen] <= far).all()
+    # the default step count is 2 * resolution; the fine network was baked (which = None)
+    by_hand = [x.cpu().numpy() for x in m.ctx.render_volume_image(volume, lo, hi, c2w, fov, h, w, 128, 1.0 / 512.0)]
+    assert_same_bits(by_hand[0], rgb)
+    assert_same_bits(by_hand[2], opacity)
+    # ... and its depth the march's weighted sum of step depths over the opacity
+    met = opacity > 0
+    np.testing.assert_allclose(depth[met], by_hand[1][met] / opacity[met], rtol=2.0 ** -22, atol=0)      # one division
+    assert (by_hand[1][met] < depth[met]).any()                                # the sum shrinks with the opacity, the map does not
+    assert_same_bits(m.ctx.radiance_lattice(1, 64, camera=c2w), volume.cpu().numpy())
+    # printed, not barred: what the preview costs against the library's own network render of the same pose
+    net = np.asarray(m.render_image(c2w, fov, h, w, seed=0)[0]).reshape(h, w, 3)
+    mse = float(np.mean((rgb.astype(np.float64) - net.astype(np.float64)) ** 2))
+    print(f"[preview, shipped checkpoint, n = 64, camera bake] PSNR against the network render at 64 + 128: "
+          f"{-10.0 * np.log10(mse):.2f} dB; mean opacity {opacity.mean():.3f}")
+
+
+def test_preview_depth_within_near_far_where_opaque(golden_ckpt, preview):
+    """Depth within [near, far] wherever opacity > 0.5.  render_preview's depth is the mean depth of what a ray met (the
+    march's weighted sum over its opacity): the sum by itself is about opacity x depth and falls below near for a half-opaque
+    ray -- on this fixture 4 of the 2098 pixels, down to 0.4715 against near 0.5576."""
+    _, _, _, (_, depth, opacity) = preview
+    near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
+    solid = opacity > 0.5
+    print(f"[preview depth] {int(solid.sum())} pixels with opacity > 0.5: depth in [{depth[solid].min():.4f}, {depth[solid].max():.4f}], "
+          f"near {near:.4f}, far {far:.4f}; {int((depth[solid] < near).sum())} below near, {int((depth[solid] > far).sum())} above far")
+    assert (depth[solid] >= near).all() and (depth[solid] <= far).all()
