@@ -15,6 +15,7 @@
 // sums / cumsum / cumprod run left to right along the sample axis and products are NOT contracted
 // into FMAs (explicit __fmul_rn/__fadd_rn), so index selection in the sampler is bit-exact against
 // the oracle and the other outputs differ only through expf.
+#include "field_device.h"
 #include "nerf_kernels.h"
 #include "ray_box_device.h"
 #include "sampling_device.h"
@@ -70,8 +71,7 @@ void launch_raygen(const float c2w_host[16], float fov, int H, int W, long long 
     for (int i = 0; i < 16; ++i) a.c[i] = c2w_host[i];
     a.tan_half = raygen_tan_half(fov);
     a.H = H; a.W = W; a.ray_begin = ray_begin; a.ray_count = ray_count; a.orig = orig; a.dirs = dirs;
-    const int bs = 256;
-    hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((ray_count + bs - 1) / bs)), dim3(bs), 0, stream, a);
+    hipLaunchKernelGGL(raygen_kernel, dim3(blocks_for(ray_count)), dim3(kBs), 0, stream, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -104,8 +104,7 @@ void launch_rays_to_ndc(const float* orig, const float* dirs, long long N, float
                         float* out_dirs, hipStream_t stream) {
     if (N <= 0) return;
     const float k = (float)(1.0 / (double)raygen_tan_half(fov));   // the raygen's own (rounded) tangent, inverted once
-    const int bs = 256;
-    hipLaunchKernelGGL(rays_to_ndc_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream, orig, dirs, N,
+    hipLaunchKernelGGL(rays_to_ndc_kernel, dim3(blocks_for(N)), dim3(kBs), 0, stream, orig, dirs, N,
                        near_plane, 2.0f * near_plane, k, out_orig, out_dirs);
 }
 
@@ -130,8 +129,7 @@ __global__ void ray_box_bounds_kernel(const BoxArgs bx, const float* __restrict_
 void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const float* orig, const float* dirs, long long N,
                            float* bounds, int* narrowed, hipStream_t stream) {
     if (N <= 0) return;
-    const int bs = 256;
-    hipLaunchKernelGGL(ray_box_bounds_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream,
+    hipLaunchKernelGGL(ray_box_bounds_kernel, dim3(blocks_for(N)), dim3(kBs), 0, stream,
                        box_args(box, near_b, far_b), orig, dirs, N, bounds, narrowed);
 }
 
@@ -232,8 +230,7 @@ void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, cons
     GridArgs g;
     g.bx = box_args(box, near_b, far_b);
     g.bits = bits; g.R = R;
-    const int bs = 256;
-    hipLaunchKernelGGL(ray_grid_bounds_kernel, dim3((unsigned)((N + bs - 1) / bs)), dim3(bs), 0, stream, g, orig, dirs, N,
+    hipLaunchKernelGGL(ray_grid_bounds_kernel, dim3(blocks_for(N)), dim3(kBs), 0, stream, g, orig, dirs, N,
                        bounds, state);
 }
 
@@ -295,94 +292,8 @@ void launch_z_values(float near_b, float far_b, bool lindisp, long long N, int S
     DepthRays rays = {};
     if (src == kDepthBox) { rays.bx = box_args(*box, near_b, far_b); rays.orig = orig; rays.dirs = dirs; }
     if (src == kDepthBounds) { rays.bounds = bounds; rays.state = state; }
-    const int bs = 256;
-    hipLaunchKernelGGL(kernels[src][lindisp ? 1 : 0], dim3((unsigned)((N * S + bs - 1) / bs)), dim3(bs), 0, stream, rays,
+    hipLaunchKernelGGL(kernels[src][lindisp ? 1 : 0], dim3(blocks_for(N * S)), dim3(kBs), 0, stream, rays,
                        depth_consts_host(near_b, far_b, lindisp, S), N, S, u, seed, ray_base, z);
-}
-
-// ---- baking: cell sample points -> the network's sigma (the MLP kernels, nerf_api.hip) -> bits -> dilation ----
-// Cells are numbered as their bits are.  A chunk is a run of whole 64-cell groups [cell_begin, cell_begin + n_cells), so a
-// wavefront's ballot is two whole words.  Point j of a cell: j == 0 the centre lo + cell (i + 0.5), j > 0 lo + cell (i + u)
-// with u = Philox(seed, cell number, 3 j + axis), stream 2 (the depth draws use 0 and 1).  The view direction is the unit
-// vector (0, 0, 1): sigma does not depend on it.
-__global__ void grid_points_kernel(const BoxArgs bx, int R, long long cell_begin, long long n_points, int spc, uint64_t seed,
-                                   float* __restrict__ xyz, float* __restrict__ view) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_points) return;
-    const long long cell = cell_begin + p / spc;
-    const int j = (int)(p % spc);
-    const int i[3] = {(int)(cell % R), (int)((cell / R) % R), (int)(cell / ((long long)R * R))};
-    float x[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const float w = __fdiv_rn(__fsub_rn(bx.hi[ax], bx.lo[ax]), (float)R);
-        const float f = j == 0 ? 0.5f : philox_uniform(seed, (uint64_t)cell, 3 * j + ax, 2u);
-        x[ax] = __fadd_rn(bx.lo[ax], __fmul_rn(w, __fadd_rn((float)i[ax], f)));
-    }
-    xyz[3 * p + 0] = x[0]; xyz[3 * p + 1] = x[1]; xyz[3 * p + 2] = x[2];
-    if (view) { view[3 * p + 0] = 0.f; view[3 * p + 1] = 0.f; view[3 * p + 2] = 1.f; }
-}
-
-// raw (n_cells * spc, 4): column 3 is sigma.  One thread per cell; lanes 0 and 32 of a wavefront store its two words.
-__global__ void grid_threshold_kernel(const float* __restrict__ raw, long long cell_begin, long long n_cells, int spc,
-                                      float threshold, uint32_t* __restrict__ bits) {
-    const long long cl = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool occ = false;
-    if (cl < n_cells) {
-        float m = raw[4 * (cl * spc) + 3];
-        for (int j = 1; j < spc; ++j) {
-            const float v = raw[4 * (cl * spc + j) + 3];
-            if (v > m) m = v;
-        }
-        occ = m > threshold;      // NaN: empty
-    }
-    const unsigned long long vote = __ballot(occ);
-    const int lane = threadIdx.x & 63;
-    if (cl < n_cells && (lane & 31) == 0) bits[(cell_begin + cl) >> 5] = (uint32_t)(vote >> lane);
-}
-
-// dst = src grown by one cell in the 26-neighbourhood.  One thread per cell, R^3 a multiple of 64.
-__global__ void grid_dilate_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int R) {
-    const long long cells = (long long)R * R * R;
-    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool occ = false;
-    if (c < cells) {
-        const int ix = (int)(c % R), iy = (int)((c / R) % R), iz = (int)(c / ((long long)R * R));
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int x = ix + dx, y = iy + dy, zc = iz + dz;
-                    if (x < 0 || x >= R || y < 0 || y >= R || zc < 0 || zc >= R) continue;
-                    const int bit = x + R * (y + R * zc);
-                    occ = occ || ((src[bit >> 5] >> (bit & 31)) & 1u);
-                }
-    }
-    const unsigned long long vote = __ballot(occ);
-    const int lane = threadIdx.x & 63;
-    if (c < cells && (lane & 31) == 0) dst[c >> 5] = (uint32_t)(vote >> lane);
-}
-
-void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,
-                        float* xyz, float* view, hipStream_t stream) {
-    const long long n_points = n_cells * spc;
-    if (n_points <= 0) return;
-    const int bs = 256;
-    hipLaunchKernelGGL(grid_points_kernel, dim3((unsigned)((n_points + bs - 1) / bs)), dim3(bs), 0, stream,
-                       box_args(box, 0.f, 0.f), R, cell_begin, n_points, spc, seed, xyz, view);
-}
-
-void launch_grid_threshold(const float* raw, long long cell_begin, long long n_cells, int spc, float threshold,
-                           uint32_t* bits, hipStream_t stream) {
-    if (n_cells <= 0) return;
-    const int bs = 256;
-    hipLaunchKernelGGL(grid_threshold_kernel, dim3((unsigned)((n_cells + bs - 1) / bs)), dim3(bs), 0, stream, raw, cell_begin,
-                       n_cells, spc, threshold, bits);
-}
-
-void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t stream) {
-    const long long cells = (long long)R * R * R;
-    const int bs = 256;
-    hipLaunchKernelGGL(grid_dilate_kernel, dim3((unsigned)((cells + bs - 1) / bs)), dim3(bs), 0, stream, src, dst, R);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -580,8 +491,7 @@ __global__ void posenc_kernel(const float* __restrict__ x, long long M, int n_en
 
 void launch_posenc(const float* x, long long M, int n_enc, int passthrough, float* out, hipStream_t stream) {
     if (M <= 0) return;
-    const int bs = 256;
-    hipLaunchKernelGGL(posenc_kernel, dim3((unsigned)((M + bs - 1) / bs)), dim3(bs), 0, stream, x, M, n_enc,
+    hipLaunchKernelGGL(posenc_kernel, dim3(blocks_for(M)), dim3(kBs), 0, stream, x, M, n_enc,
                        passthrough, out);
 }
 

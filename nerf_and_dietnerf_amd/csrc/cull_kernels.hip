@@ -15,13 +15,12 @@
 
 #include <cstdint>
 
+#include "field_device.h"
 #include "nerf_device.h"
 #include "nerf_kernels.h"
 
 namespace nerf {
 namespace {
-
-constexpr int kBs = 256;
 
 struct CullArgs {
     float lo[3], hi[3], cell[3];   // cell_a = (hi_a - lo_a) / R, float32
@@ -38,8 +37,6 @@ CullArgs cull_args(const SceneBox& box, const uint32_t* bits, int R) {
     g.bits = bits; g.R = R;
     return g;
 }
-
-unsigned blocks_for(long long items) { return (unsigned)((items + kBs - 1) / kBs); }
 
 // The verdict of one sample: float32, every operation rounded on its own, comparisons instead of fminf / fmaxf.
 //   1. p_a = o_a + d_a z, multiply then add: the point the MLP kernels form in mode 0, bit for bit

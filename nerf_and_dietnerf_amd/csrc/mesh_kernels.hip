@@ -1,6 +1,6 @@
-// mesh_kernels.hip -- a triangle mesh out of the density field: the lattice the network is evaluated on (points in,
-// sigma / colours out; the network itself runs in nerf_api.hip), and the isosurface of an n^3 volume by marching tetrahedra
-// (nerf_isosurface / nerf_isosurface_fetch, include/nerf_mi355.h has the rule).
+// mesh_kernels.hip -- a triangle mesh out of the density field: the isosurface of an n^3 volume over a lattice
+// (field_device.h) by marching tetrahedra (nerf_isosurface / nerf_isosurface_fetch, include/nerf_mi355.h has the rule), and
+// the exclusive scan it numbers its output with.  The network on the lattice and at the vertices: field_api.hip.
 //
 // The isosurface is canonical: no atomics, no hashing.  Every output slot is known from two exclusive scans -- the crossed
 // edges of every lattice point, the triangles of every cube -- so a vertex id is (first id of the edge's base point) + (rank
@@ -11,76 +11,11 @@
 #include <cmath>
 #include <cstdint>
 
+#include "field_device.h"
 #include "nerf_ctx.h"
 
 namespace nerf {
 namespace {
-
-constexpr int kBs = 256;
-
-struct Lattice {
-    float lo[3], step[3];
-    int n;
-};
-
-Lattice make_lattice(const float* lo3, const float* hi3, int n) {
-    Lattice l;
-    for (int a = 0; a < 3; ++a) {
-        l.lo[a] = lo3[a];
-        l.step[a] = (hi3[a] - lo3[a]) / (float)(n - 1);
-    }
-    l.n = n;
-    return l;
-}
-
-__device__ __forceinline__ float lattice_coord(const Lattice& l, int axis, int i) {
-    return __fadd_rn(l.lo[axis], __fmul_rn(l.step[axis], (float)i));
-}
-
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-unsigned blocks_for(long long items) { return (unsigned)((items + kBs - 1) / kBs); }
-
-// ---- the lattice the network is evaluated on ----
-__global__ void lattice_points_kernel(const Lattice l, long long begin, long long count, float vx, float vy, float vz,
-                                      float* __restrict__ xyz, float* __restrict__ view) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const long long p = begin + t;
-    const int n = l.n;
-    const int i[3] = {(int)(p % n), (int)((p / n) % n), (int)(p / ((long long)n * n))};
-    xyz[3 * t + 0] = lattice_coord(l, 0, i[0]);
-    xyz[3 * t + 1] = lattice_coord(l, 1, i[1]);
-    xyz[3 * t + 2] = lattice_coord(l, 2, i[2]);
-    if (view) { view[3 * t + 0] = vx; view[3 * t + 1] = vy; view[3 * t + 2] = vz; }
-}
-
-// raw (count, 4) -> its column 3
-__global__ void raw_sigma_kernel(const float* __restrict__ raw, long long count, float* __restrict__ sigma) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < count) sigma[t] = raw[4 * t + 3];
-}
-
-// the direction a ray that sees the surface travels in: against the normal; a zero normal looks down +z like the bake
-__global__ void mesh_view_kernel(const float* __restrict__ normals, long long count, float* __restrict__ view) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const float x = normals[3 * t], y = normals[3 * t + 1], z = normals[3 * t + 2];
-    const bool zero = x == 0.f && y == 0.f && z == 0.f;
-    view[3 * t + 0] = zero ? 0.f : -x;
-    view[3 * t + 1] = zero ? 0.f : -y;
-    view[3 * t + 2] = zero ? 1.f : -z;
-}
-
-// raw (count, 4) -> the sigmoid of columns 0..2, as composite_kernel writes rgb_samples
-__global__ void raw_rgb_kernel(const float* __restrict__ raw, long long count, float* __restrict__ rgb) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const float4 o = reinterpret_cast<const float4*>(raw)[t];
-    rgb[3 * t + 0] = 1.0f / (1.0f + expf(-o.x));
-    rgb[3 * t + 1] = 1.0f / (1.0f + expf(-o.y));
-    rgb[3 * t + 2] = 1.0f / (1.0f + expf(-o.z));
-}
 
 // ---- marching tetrahedra ----
 // Edge types in key order: 100, 010, 001, 110, 011, 101, 111 as (dx, dy, dz).
@@ -402,28 +337,6 @@ void launch_scan_popc(const uint8_t* in, long long N, uint32_t* sums, uint32_t* 
     launch_scan<true>(in, N, sums, out, total_dev, stream);
 }
 
-void launch_lattice_points(const SceneBox& box, int n, long long begin, long long count, const float view_dir[3], float* xyz,
-                           float* view, hipStream_t stream) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(lattice_points_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, make_lattice(box.lo, box.hi, n),
-                       begin, count, view_dir[0], view_dir[1], view_dir[2], xyz, view);
-}
-
-void launch_raw_sigma(const float* raw, long long count, float* sigma, hipStream_t stream) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(raw_sigma_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, raw, count, sigma);
-}
-
-void launch_mesh_view(const float* normals, long long count, float* view, hipStream_t stream) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(mesh_view_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, normals, count, view);
-}
-
-void launch_raw_rgb(const float* raw, long long count, float* rgb, hipStream_t stream) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(raw_rgb_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, raw, count, rgb);
-}
-
 }  // namespace nerf
 
 using namespace nerf;
@@ -434,7 +347,7 @@ int nerf_isosurface(nerf_ctx* c, const float* sigma, int32_t n, const float* lo3
                     int64_t* n_vertices, int64_t* n_triangles, int mem) {
     ENTER(c);
     if (!sigma || !lo3 || !hi3 || !n_vertices || !n_triangles) return fail("NULL argument");
-    if (n < 2 || n > 512) return fail("isosurface: n must be in 2..512 (got %d)", n);
+    if (int r = lattice_n_ok("isosurface", n)) return r;
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
             return fail("isosurface needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", a, lo3[a], hi3[a]);

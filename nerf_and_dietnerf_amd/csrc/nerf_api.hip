@@ -1,5 +1,5 @@
 // nerf_api.hip -- the C ABI of libnerf_mi355.so (include/nerf_mi355.h): context, weight upload,
-// scratch arena and the orchestration of the render path
+// scratch arena and the orchestration of the render path (field queries: field_api.hip; isosurface, radiance volume: beside their kernels)
 //   NeRF.render        src/NeRF.py:109-134
 //   NeRF.render_image  src/NeRF.py:190-246
 //   render_rays        src/UtilsNeuralRadianceField.py:181-211
@@ -491,6 +491,13 @@ int dev_render(nerf_ctx* c, const float* o, const float* d, long long N, int Sc,
 
 }  // namespace
 
+// the one way out of this file to run_mlp (nerf_ctx.h): model_predict's kernel on M device-resident rows
+int nerf::eval_points(nerf_ctx* c, int which, const float* xyz, const float* view, long long M, float* raw) {
+    RenderKernel k;
+    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
+    return run_mlp(c, which, k, xyz, view, nullptr, raw, M, 1, 1);
+}
+
 extern "C" {
 
 int nerf_abi_version(void) { return NERF_ABI_VERSION; }
@@ -640,280 +647,6 @@ int nerf_ctx_set_scene_box(nerf_ctx* c, const float* lo3, const float* hi3) {
     for (int a = 0; a < 3; ++a) { c->box.lo[a] = lo3[a]; c->box.hi[a] = hi3[a]; }
     c->box_on = true;
     c->grid_R = 0;
-    return 0;
-}
-
-// ---- occupancy grid ----
-static int grid_resolution_ok(int R) {
-    if (R < 4 || R > 256 || R % 4) return fail("occupancy grid resolution must be a multiple of 4 in [4, 256] (got %d)", R);
-    return 0;
-}
-static const char* kGridNeedsBox = "an occupancy grid needs a scene box (nerf_ctx_set_scene_box)";
-
-int nerf_ctx_set_occupancy_grid(nerf_ctx* c, const uint32_t* bits, int32_t R) {
-    ENTER(c);
-    if (!bits && R == 0) { c->grid_R = 0; return 0; }
-    if (!bits) return fail("occupancy grid: bits is NULL (NULL, 0 clears the grid)");
-    if (!c->box_on) return fail("%s", kGridNeedsBox);
-    if (int r = grid_resolution_ok(R)) return r;
-    const size_t bytes = (size_t)R * R * R / 8;
-    c->grid_R = 0;
-    if (int r = ensure(c, c->b_grid[0], bytes)) return r;
-    HIP_OK(hipMemcpyAsync(c->b_grid[0].p, bits, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));          // the caller's array is free again
-    c->grid_cur = 0;
-    c->grid_R = R;
-    return 0;
-}
-
-int nerf_ctx_get_occupancy_grid(nerf_ctx* c, uint32_t* bits, int32_t* R) {
-    ENTER(c);
-    if (!R) return fail("NULL argument");
-    *R = c->grid_R;
-    if (!bits || c->grid_R == 0) return 0;
-    const size_t bytes = (size_t)c->grid_R * c->grid_R * c->grid_R / 8;
-    HIP_OK(hipMemcpyAsync(bits, c->b_grid[c->grid_cur].p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int nerf_occupancy_bake(nerf_ctx* c, int which, int32_t R, float sigma_threshold, int32_t samples_per_cell, int32_t dilate,
-                        uint64_t seed, int64_t* n_occupied) {
-    ENTER(c);
-    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
-    if (!c->box_on) return fail("%s", kGridNeedsBox);
-    if (int r = grid_resolution_ok(R)) return r;
-    if (!std::isfinite(sigma_threshold) || !(sigma_threshold > 0.f))
-        return fail("occupancy grid: sigma_threshold must be finite and > 0 (got %g)", sigma_threshold);
-    if (samples_per_cell < 1 || samples_per_cell > 8)
-        return fail("occupancy grid: samples_per_cell must be in 1..8 (got %d)", samples_per_cell);
-    if (dilate < 0 || dilate > 2) return fail("occupancy grid: dilate must be 0, 1 or 2 (got %d)", dilate);
-    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
-    RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
-    const long long cells = (long long)R * R * R;                 // a multiple of 64
-    const size_t bytes = (size_t)cells / 8;
-    c->grid_R = 0;                                                // a bake that fails leaves no grid behind
-    if (int r = ensure(c, c->b_grid[0], bytes)) return r;
-    if (int r = ensure(c, c->b_grid[1], bytes)) return r;
-    // chunks of whole 64-cell groups, at most 2^20 points each, through the device-resident model_predict path
-    const long long chunk_cells = std::min(cells, (((long long)1 << 20) / samples_per_cell) & ~63LL);
-    const size_t pts = (size_t)chunk_cells * samples_per_cell;
-    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
-    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
-    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    float *xyz = (float*)c->b_in0.p, *view = (float*)c->b_in1.p, *raw = (float*)c->b_raw.p;
-    int cur = 0;
-    for (long long begin = 0; begin < cells; begin += chunk_cells) {
-        const long long n = std::min(chunk_cells, cells - begin);
-        launch_grid_points(c->box, R, begin, n, samples_per_cell, seed, xyz, view, c->stream);
-        if (int r = run_mlp(c, which, k, xyz, c->cfg.n_angles != 0 ? view : nullptr, nullptr, raw, n * samples_per_cell, 1, 1))
-            return r;
-        launch_grid_threshold(raw, begin, n, samples_per_cell, sigma_threshold, (uint32_t*)c->b_grid[cur].p, c->stream);
-    }
-    for (int i = 0; i < dilate; ++i, cur ^= 1)
-        launch_grid_dilate((const uint32_t*)c->b_grid[cur].p, (uint32_t*)c->b_grid[cur ^ 1].p, R, c->stream);
-    HIP_OK(hipGetLastError());
-    if (n_occupied) {
-        std::vector<uint32_t> host(bytes / 4);
-        HIP_OK(hipMemcpyAsync(host.data(), c->b_grid[cur].p, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        long long count = 0;
-        for (uint32_t w : host) count += __builtin_popcount(w);
-        *n_occupied = count;
-    }
-    c->grid_cur = cur;
-    c->grid_R = R;
-    return 0;
-}
-
-// ---- mesh extraction: the network on the lattice and at the vertices (the isosurface itself: mesh_kernels.hip) ----
-static constexpr long long kMeshChunk = 1LL << 20;   // points per pass through the network, as the bake
-
-int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_dir3, float* sigma, int mem) {
-    ENTER(c);
-    if (!sigma) return fail("NULL argument");
-    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
-    if (!c->box_on) return fail("a density lattice needs a scene box (nerf_ctx_set_scene_box)");
-    if (n < 2 || n > 512) return fail("density lattice: n must be in 2..512 (got %d)", n);
-    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
-    RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
-    const float up[3] = {0.f, 0.f, 1.f};
-    const float* vd = view_dir3 ? view_dir3 : up;
-    const long long points = (long long)n * n * n;
-    const size_t pts = (size_t)std::min(points, kMeshChunk);
-    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
-    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
-    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    Staging st(c, mem);
-    float* out = st.out(c->b_lattice, sigma, (size_t)points * 4);
-    if (st.err) return st.err;
-    float *xyz = (float*)c->b_in0.p, *view = c->cfg.n_angles != 0 ? (float*)c->b_in1.p : nullptr, *raw = (float*)c->b_raw.p;
-    for (long long begin = 0; begin < points; begin += kMeshChunk) {
-        const long long m = std::min(kMeshChunk, points - begin);
-        launch_lattice_points(c->box, n, begin, m, vd, xyz, view, c->stream);
-        if (int r = run_mlp(c, which, k, xyz, view, nullptr, raw, m, 1, 1)) return r;
-        launch_raw_sigma(raw, m, out + begin, c->stream);
-    }
-    HIP_OK(hipGetLastError());
-    return st.finish();
-}
-
-// ---- radiance volume: the network baked to an (n, n, n, 4) lattice, and the lattice ray-marched (volume_kernels.hip) ----
-int nerf_radiance_lattice(nerf_ctx* c, int which, int32_t n, const float* view_dir3, const float* camera_c2w16, float* volume,
-                          int mem) {
-    ENTER(c);
-    if (!volume) return fail("NULL argument");
-    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
-    if (view_dir3 && camera_c2w16) return fail("radiance lattice: give view_dir or camera, not both");
-    if (!c->box_on) return fail("a radiance lattice needs a scene box (nerf_ctx_set_scene_box)");
-    if (n < 2 || n > 512) return fail("radiance lattice: n must be in 2..512 (got %d)", n);
-    if (camera_c2w16 && c->ray_space == NERF_RAYS_NDC)
-        return fail("radiance lattice: camera is refused while the ray space is NDC (the scene box is not in world space)");
-    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
-    RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
-    const float up[3] = {0.f, 0.f, 1.f};
-    const float* vd = view_dir3 ? view_dir3 : up;
-    const long long points = (long long)n * n * n;
-    const size_t pts = (size_t)std::min(points, kMeshChunk);
-    if (int r = ensure(c, c->b_in0, pts * 12)) return r;
-    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
-    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    Staging st(c, mem);
-    float* out = st.out(c->b_lattice, volume, (size_t)points * 16);
-    if (st.err) return st.err;
-    float *xyz = (float*)c->b_in0.p, *view = c->cfg.n_angles != 0 ? (float*)c->b_in1.p : nullptr, *raw = (float*)c->b_raw.p;
-    const bool camera = camera_c2w16 && view;
-    for (long long begin = 0; begin < points; begin += kMeshChunk) {
-        const long long m = std::min(kMeshChunk, points - begin);
-        launch_lattice_points(c->box, n, begin, m, vd, xyz, camera ? nullptr : view, c->stream);
-        if (camera) launch_camera_view(camera_c2w16, xyz, m, view, c->stream);
-        if (int r = run_mlp(c, which, k, xyz, view, nullptr, raw, m, 1, 1)) return r;
-        launch_raw_rgba(raw, m, out + 4 * begin, c->stream);
-    }
-    HIP_OK(hipGetLastError());
-    return st.finish();
-}
-
-// the arguments every volume call shares
-static int volume_ok(const char* what, const float* volume, int32_t n, const float* lo3, const float* hi3) {
-    if (!volume || !lo3 || !hi3) return fail("NULL argument");
-    if (n < 2 || n > 512) return fail("%s: n must be in 2..512 (got %d)", what, n);
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
-            return fail("%s needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", what, a, lo3[a], hi3[a]);
-    return 0;
-}
-
-static int march_ok(int32_t n_steps, float t_min, const float* rgb, const float* depth, const float* opacity) {
-    if (n_steps < 1) return fail("volume march: n_steps must be >= 1 (got %d)", n_steps);
-    if (!(t_min >= 0.f && t_min < 1.f)) return fail("volume march: t_min must be in [0, 1) (got %g)", t_min);
-    if (!rgb && !depth && !opacity) return fail("volume march: rgb, depth and opacity are all NULL");
-    return 0;
-}
-
-int nerf_volume_sample(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
-                       int64_t M, float* out, int mem) {
-    ENTER(c);
-    if (int r = volume_ok("volume sample", volume, n, lo3, hi3)) return r;
-    if (M < 0) return fail("bad shape M=%lld", (long long)M);
-    if (M == 0) return 0;
-    if (!points || !out) return fail("NULL argument");
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
-    const float* p = st.in(c->b_in0, points, (size_t)M * 12);
-    float* o = st.out(c->b_raw, out, (size_t)M * 16);
-    if (st.err) return st.err;
-    launch_volume_sample(vol, n, lo3, hi3, p, M, o, c->stream);
-    HIP_OK(hipGetLastError());
-    return st.finish();
-}
-
-int nerf_volume_march(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
-                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
-                      int mem) {
-    ENTER(c);
-    if (int r = volume_ok("volume march", volume, n, lo3, hi3)) return r;
-    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
-    if (N < 0) return fail("bad shape N=%lld", (long long)N);
-    if (N == 0) return 0;
-    if (!rays_orig || !rays_dirs) return fail("NULL argument");
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
-    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
-    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
-    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
-    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
-    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
-    if (st.err) return st.err;
-    launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb, ddepth, dopac,
-                        c->stream);
-    HIP_OK(hipGetLastError());
-    return st.finish();
-}
-
-int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
-                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
-                             float* rgb, float* depth, float* opacity, int mem) {
-    ENTER(c);
-    if (int r = volume_ok("volume render", volume, n, lo3, hi3)) return r;
-    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
-    if (!c2w) return fail("NULL argument");
-    if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
-    const long long total = (long long)H * W;
-    if (ray_count <= 0) { ray_begin = 0; ray_count = total; }
-    if (ray_begin < 0 || ray_begin + ray_count > total) return fail("ray slab [%lld,+%lld) outside %lld rays",
-                                                                    (long long)ray_begin, (long long)ray_count, total);
-    const long long N = ray_count, batch = std::min<long long>(N, 1 << 18);
-    if (int r = ensure(c, c->b_orig, (size_t)batch * 16)) return r;
-    if (int r = ensure(c, c->b_dirs, (size_t)batch * 16)) return r;
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
-    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
-    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
-    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
-    if (st.err) return st.err;
-    float *o = (float*)c->b_orig.p, *d = (float*)c->b_dirs.p;
-    for (long long off = 0; off < N; off += batch) {      // the rays of nerf_render_image, batch by batch on the stream
-        const long long m = std::min(batch, N - off);
-        launch_raygen(c2w, fov, H, W, ray_begin + off, m, o, d, c->stream);
-        if (c->ray_space == NERF_RAYS_NDC) launch_rays_to_ndc(o, d, m, fov, c->ndc_near_plane, o, d, c->stream);
-        launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
-                            drgb ? drgb + 3 * off : nullptr, ddepth ? ddepth + off : nullptr, dopac ? dopac + off : nullptr,
-                            c->stream);
-    }
-    HIP_OK(hipGetLastError());
-    return st.finish();
-}
-
-int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem) {
-    ENTER(c);
-    if (V < 0) return fail("bad V");
-    if (V == 0) return 0;
-    if (!vertices || !normals || !rgb) return fail("NULL argument");
-    if (which != 0 && which != 1) return fail("which must be 0 (coarse) or 1 (fine)");
-    if (!c->net[which].loaded) return fail("network %d has no weights loaded", which);
-    RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
-    const size_t pts = (size_t)std::min((long long)V, kMeshChunk);
-    if (int r = ensure(c, c->b_in1, pts * 12)) return r;
-    if (int r = ensure(c, c->b_raw, pts * 16)) return r;
-    float *view = (float*)c->b_in1.p, *raw = (float*)c->b_raw.p;
-    for (long long begin = 0; begin < V; begin += kMeshChunk) {      // a host caller's chunk is staged, and leaves, by itself
-        const long long m = std::min(kMeshChunk, (long long)V - begin);
-        Staging st(c, mem);
-        const float* xyz = st.in(c->b_in0, vertices + 3 * begin, (size_t)m * 12);
-        const float* nrm = st.in(c->b_in2, normals + 3 * begin, (size_t)m * 12);
-        float* out = st.out(c->b_out[0], rgb + 3 * begin, (size_t)m * 12);
-        if (st.err) return st.err;
-        launch_mesh_view(nrm, m, view, c->stream);
-        if (int r = run_mlp(c, which, k, xyz, c->cfg.n_angles != 0 ? view : nullptr, nullptr, raw, m, 1, 1)) return r;
-        launch_raw_rgb(raw, m, out, c->stream);
-        HIP_OK(hipGetLastError());
-        if (int r = st.finish()) return r;
-    }
     return 0;
 }
 
@@ -1199,9 +932,7 @@ int nerf_model_predict(nerf_ctx* c, int which, const float* xyz, const float* vi
     const float* dv = st.in(c->b_in1, view_dirs, (size_t)M * 12);
     float* dr = st.out(c->b_raw, raw, (size_t)M * 16);
     if (st.err) return st.err;
-    RenderKernel k;
-    if (pick_render_kernel(c->cfg, c->cfg.precision, false, &k)) return 1;
-    if (int r = run_mlp(c, which, k, dx, dv, nullptr, dr, M, 1, 1)) return r;
+    if (int r = eval_points(c, which, dx, dv, M, dr)) return r;
     return st.finish();
 }
 

@@ -1,5 +1,5 @@
-// nerf_ctx.h -- the context object behind the C ABI, shared by nerf_api.hip (render path) and
-// train_api.hip (training path).  Internal: nothing here is part of include/nerf_mi355.h.
+// nerf_ctx.h -- the context object behind the C ABI, shared by every unit with entry points: nerf_api.hip (render path), field_api.hip
+// (field queries), train_api.hip (training path), mesh_kernels.hip, volume_kernels.hip.  Internal: not part of include/nerf_mi355.h.
 #pragma once
 #include "../../include/nerf_mi355.h"
 
@@ -88,7 +88,7 @@ struct nerf_ctx {
     long long mesh_V = 0, mesh_T = 0;
     nerf::DevBuf b_mesh_v, b_mesh_n, b_mesh_t;                             // vertices, normals, triangles
     nerf::DevBuf b_mesh_sigma, b_mesh_mask, b_mesh_first, b_mesh_count, b_mesh_tfirst, b_mesh_sums;
-    nerf::DevBuf b_lattice;                    // nerf_density_lattice(NERF_MEM_HOST): the volume before it leaves
+    nerf::DevBuf b_lattice;                    // a host caller's lattice: baked, before it leaves; a volume, staged in
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -160,6 +160,10 @@ private:
 };
 #define ENTER(c) do { if (int r__ = nerf::enter(c)) return r__; } while (0)
 int sampling_ok(const nerf_ctx* c);                 // nerf_api.hip: the ctx's bounds suit its sampling mode (lindisp: near > 0)
+inline int lattice_n_ok(const char* what, int n) { return n < 2 || n > 512 ? fail("%s: n must be in 2..512 (got %d)", what, n) : 0; }
+// nerf_api.hip: network `which` on M device-resident points (view: NULL for n_angles == 0) -> raw (M, 4) in the ctx's precision, on the ctx
+// stream: what nerf_model_predict runs, for a caller that makes its own points.  Before it: a lattice size outside 2..512, refused by name.
+int eval_points(nerf_ctx* c, int which, const float* xyz, const float* view, long long M, float* raw);
 // The coarse depths of N rays as this ctx draws them (bounds, sampling mode, scene box, occupancy grid): every call site that
 // has rays.  Without a grid it launches what it always launched and cannot fail; with one it may grow two scratch buffers.
 int draw_z_values(nerf_ctx* c, const float* o, const float* d, long long N, int S, const float* u, uint64_t seed,

@@ -268,14 +268,15 @@ void launch_ray_box_bounds(const SceneBox& box, float near_b, float far_b, const
 // ix + R (iy + R iz).  bounds (N,2) and state (N; 0 untouched / 1 box only / 2 grid; nullable) of every ray, walked once
 void launch_ray_grid_bounds(const SceneBox& box, float near_b, float far_b, const uint32_t* bits, int R, const float* orig,
                             const float* dirs, long long N, float* bounds, int* state, hipStream_t stream);
-// baking: the sample points (n_cells * spc, 3) of cells [cell_begin, cell_begin + n_cells) and as many unit view directions
-// (nullable); raw (n_cells * spc, 4) -> their bits; one step of 26-neighbour growth.  cell_begin, n_cells: multiples of 64
+// field_kernels.hip (to launch_raw_rgba): the fills and drains of field_api.hip's queries.  Baking: the sample points (n_cells * spc, 3)
+// of cells [cell_begin, cell_begin + n_cells), as many unit view directions (nullable); raw (n_cells * spc, 4) -> their bits; one
+// step of 26-neighbour growth.  cell_begin, n_cells: multiples of 64
 void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,
                         float* xyz, float* view, hipStream_t stream);
 void launch_grid_threshold(const float* raw, long long cell_begin, long long n_cells, int spc, float threshold,
                            uint32_t* bits, hipStream_t stream);
 void launch_grid_dilate(const uint32_t* src, uint32_t* dst, int R, hipStream_t stream);
-// mesh_kernels.hip: points [begin, begin + count) of the n^3 lattice over the box (x fastest) and as many copies of view_dir
+// points [begin, begin + count) of the n^3 lattice over the box (x fastest) and as many copies of view_dir
 // (view nullable); column 3 of raw (count, 4); the view directions -normal ((0, 0, 1) for a zero normal); the sigmoid of
 // columns 0..2 of raw (count, 4)
 void launch_lattice_points(const SceneBox& box, int n, long long begin, long long count, const float view_dir[3], float* xyz,
@@ -283,18 +284,11 @@ void launch_lattice_points(const SceneBox& box, int n, long long begin, long lon
 void launch_raw_sigma(const float* raw, long long count, float* sigma, hipStream_t stream);
 void launch_mesh_view(const float* normals, long long count, float* view, hipStream_t stream);
 void launch_raw_rgb(const float* raw, long long count, float* rgb, hipStream_t stream);
-// volume_kernels.hip (the radiance volume: nerf_radiance_lattice has the format, nerf_volume_sample and nerf_volume_march the
-// rules).  The bake: the direction camera c2w's ray generator gives the pixel whose ray passes through each of xyz (count, 3);
-// raw (count, 4) -> texels (count, 4), sigmoid of columns 0..2 and ReLU of column 3.  The trilinear sampler at points (M, 3) ->
-// out (M, 4), and the march of N rays (any of rgb (N, 3), depth (N), opacity (N) nullable) through an (n, n, n, 4) volume over
-// (lo3, hi3); the cell index is held in [0, n - 2] wherever the volume is read.
+// The radiance volume (nerf_radiance_lattice has the format, nerf_volume_sample and nerf_volume_march the rules).  The bake,
+// still field_kernels.hip: the direction camera c2w's ray generator gives the pixel whose ray passes through each of xyz
+// (count, 3); raw (count, 4) -> texels (count, 4), sigmoid of columns 0..2 and ReLU of column 3.
 void launch_camera_view(const float c2w[16], const float* xyz, long long count, float* view, hipStream_t stream);
 void launch_raw_rgba(const float* raw, long long count, float* texels, hipStream_t stream);
-void launch_volume_sample(const float* volume, int n, const float* lo3, const float* hi3, const float* points, long long M,
-                          float* out, hipStream_t stream);
-void launch_volume_march(const float* volume, int n, const float* lo3, const float* hi3, float near_b, float far_b,
-                         const float* orig, const float* dirs, long long N, int n_steps, float t_min, float* rgb, float* depth,
-                         float* opacity, hipStream_t stream);
 // mesh_kernels.hip's exclusive scan for bit-mask items: out[i] = set bits of in[0..i), *total_dev = set bits of all N bytes;
 // sums: scratch of scan_sums_words(N) words.  No atomics: the result does not depend on the launch.
 size_t scan_sums_words(long long N);

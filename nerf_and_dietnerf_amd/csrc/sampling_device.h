@@ -189,15 +189,18 @@ __device__ __forceinline__ CdfDraw inverse_cdf_draw(const float* cdf, const floa
 // ------------------------------------------------------------------------------------------------
 struct CompositeTerms { float delta, sigma, e, alpha, r0, r1, r2; };
 
+// a raw colour column -> the colour: the one sigmoid of the compositing, the vertex colours and the radiance volume's texels
+__device__ __forceinline__ float raw_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 __device__ __forceinline__ CompositeTerms composite_terms(const float4 o, const float* __restrict__ zr, int s, int S) {
     CompositeTerms c;
     c.delta = s + 1 < S ? zr[s + 1] - zr[s] : 1e9f;
     c.sigma = fmaxf(o.w, 0.f);
     c.e = s < S ? expf(-(c.sigma * c.delta)) : 1.0f;
     c.alpha = 1.0f - c.e;
-    c.r0 = 1.0f / (1.0f + expf(-o.x));
-    c.r1 = 1.0f / (1.0f + expf(-o.y));
-    c.r2 = 1.0f / (1.0f + expf(-o.z));
+    c.r0 = raw_sigmoid(o.x);
+    c.r1 = raw_sigmoid(o.y);
+    c.r2 = raw_sigmoid(o.z);
     return c;
 }
 

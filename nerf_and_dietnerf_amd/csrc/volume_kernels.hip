@@ -1,71 +1,29 @@
 // volume_kernels.hip -- the radiance volume: an (n, n, n, 4) float32 lattice of (r, g, b, sigma) over a box, indexed
 // [iz, iy, ix, channel], colour after the sigmoid and density after the ReLU (include/nerf_mi355.h: nerf_radiance_lattice has
-// the format, nerf_volume_sample the trilinear rule, nerf_volume_march the march).  Here: the two kernels of the bake that
-// mesh_kernels.hip does not have (per-vertex camera directions, raw -> stored texel), the trilinear sampler and the march.
-// The network itself runs in nerf_api.hip.
+// the format, nerf_volume_sample the trilinear rule, nerf_volume_march the march).  Here: the trilinear sampler, the march and
+// their entry points.  The bake (nerf_radiance_lattice) is a field query: field_api.hip.
 //
 // Everything is float32 with every operation rounded on its own (the __f*_rn idiom of aux_kernels.hip), so the numpy
 // restatement of tests/volume_ref.py matches the sampler bit for bit and the march up to expf.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
+#include "field_device.h"
 #include "nerf_ctx.h"
 #include "ray_box_device.h"
 
 namespace nerf {
 namespace {
 
-constexpr int kBs = 256;
-unsigned blocks_for(long long items, int bs = kBs) { return (unsigned)((items + bs - 1) / bs); }
-
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// ---- the bake ----
-// The direction the ray generator gives the pixel whose ray passes through point p of camera c (row-major 4x4, looking down
-// -z): raygen's direction has camera-space z = -1, so it is (p - t) over the depth of p along the central ray.  A point
-// behind the camera (or at it, or a non-finite depth) gets the central ray's direction.
-struct CameraArgs { float c[16]; };
-
-__global__ void camera_view_kernel(const CameraArgs cam, const float* __restrict__ xyz, long long count, float* __restrict__ view) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const float* c = cam.c;
-    const float qx = __fsub_rn(xyz[3 * t + 0], c[3]), qy = __fsub_rn(xyz[3 * t + 1], c[7]), qz = __fsub_rn(xyz[3 * t + 2], c[11]);
-    const float s = -__fadd_rn(__fadd_rn(__fmul_rn(c[2], qx), __fmul_rn(c[6], qy)), __fmul_rn(c[10], qz));
-    const bool front = s > 0.0f && finite_f(s);
-    view[3 * t + 0] = front ? __fdiv_rn(qx, s) : -c[2];
-    view[3 * t + 1] = front ? __fdiv_rn(qy, s) : -c[6];
-    view[3 * t + 2] = front ? __fdiv_rn(qz, s) : -c[10];
-}
-
-// raw (count, 4) -> the stored texel: the sigmoid of columns 0..2 as raw_rgb_kernel writes it, the ReLU of column 3 as
-// composite_terms takes it
-__global__ void raw_rgba_kernel(const float* __restrict__ raw, long long count, float* __restrict__ texels) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const float4 o = reinterpret_cast<const float4*>(raw)[t];
-    reinterpret_cast<float4*>(texels)[t] = make_float4(1.0f / (1.0f + expf(-o.x)), 1.0f / (1.0f + expf(-o.y)),
-                                                       1.0f / (1.0f + expf(-o.z)), fmaxf(o.w, 0.f));
-}
-
 // ---- trilinear sampling ----
-struct VolumeArgs {
-    const float4* texels;
-    float lo[3], step[3];
-    int n;
-};
+// the volume's texels and the lattice they sit on: field_device.h's, so the sampler's step is the bake's by construction
+struct VolumeArgs { const float4* texels; Lattice l; };
 
 VolumeArgs volume_args(const float* volume, int n, const float* lo3, const float* hi3) {
-    VolumeArgs g;
-    g.texels = reinterpret_cast<const float4*>(volume);
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = lo3[a];
-        g.step[a] = (hi3[a] - lo3[a]) / (float)(n - 1);      // mesh_kernels.hip::make_lattice's step
-    }
-    g.n = n;
-    return g;
+    return {reinterpret_cast<const float4*>(volume), make_lattice(lo3, hi3, n)};
 }
 
 // One axis: the cell of coordinate p and the weight of the cell's upper vertex.  The cell is in [0, n - 2] for every input: a
@@ -85,10 +43,10 @@ struct CellFetch {
 };
 
 __device__ __forceinline__ void volume_fetch(const VolumeArgs& g, float px, float py, float pz, CellFetch* c) {
-    const int n = g.n;
-    const int ix = volume_cell(px, g.lo[0], g.step[0], n, &c->f[0]);
-    const int iy = volume_cell(py, g.lo[1], g.step[1], n, &c->f[1]);
-    const int iz = volume_cell(pz, g.lo[2], g.step[2], n, &c->f[2]);
+    const int n = g.l.n;
+    const int ix = volume_cell(px, g.l.lo[0], g.l.step[0], n, &c->f[0]);
+    const int iy = volume_cell(py, g.l.lo[1], g.l.step[1], n, &c->f[1]);
+    const int iz = volume_cell(pz, g.l.lo[2], g.l.step[2], n, &c->f[2]);
     const float4* row = g.texels + ((size_t)iz * n + iy) * n + ix;     // ix + 1, iy + 1, iz + 1 <= n - 1
     const size_t sy = (size_t)n, sz = (size_t)n * n;
     c->v[0] = row[0];       c->v[1] = row[1];
@@ -179,20 +137,8 @@ __global__ __launch_bounds__(64) void volume_march_kernel(const VolumeArgs g, co
     if (opacity) opacity[r] = __fsub_rn(1.0f, T);
 }
 
-}  // namespace
-
-void launch_camera_view(const float c2w[16], const float* xyz, long long count, float* view, hipStream_t stream) {
-    if (count <= 0) return;
-    CameraArgs cam;
-    for (int i = 0; i < 16; ++i) cam.c[i] = c2w[i];
-    hipLaunchKernelGGL(camera_view_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, cam, xyz, count, view);
-}
-
-void launch_raw_rgba(const float* raw, long long count, float* texels, hipStream_t stream) {
-    if (count <= 0) return;
-    hipLaunchKernelGGL(raw_rgba_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, raw, count, texels);
-}
-
+// The trilinear sampler at points (M, 3) -> out (M, 4), and the march of N rays (any of rgb (N, 3), depth (N), opacity (N)
+// nullable) through an (n, n, n, 4) volume over (lo3, hi3); the cell index is held in [0, n - 2] wherever the volume is read.
 void launch_volume_sample(const float* volume, int n, const float* lo3, const float* hi3, const float* points, long long M,
                           float* out, hipStream_t stream) {
     if (M <= 0) return;
@@ -210,4 +156,102 @@ void launch_volume_march(const float* volume, int n, const float* lo3, const flo
                        box_args(box, near_b, far_b), orig, dirs, N, n_steps, t_min, rgb, depth, opacity);
 }
 
+}  // namespace
 }  // namespace nerf
+
+using namespace nerf;
+
+// the arguments every volume call shares
+static int volume_ok(const char* what, const float* volume, int32_t n, const float* lo3, const float* hi3) {
+    if (!volume || !lo3 || !hi3) return fail("NULL argument");
+    if (int r = lattice_n_ok(what, n)) return r;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
+            return fail("%s needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", what, a, lo3[a], hi3[a]);
+    return 0;
+}
+
+static int march_ok(int32_t n_steps, float t_min, const float* rgb, const float* depth, const float* opacity) {
+    if (n_steps < 1) return fail("volume march: n_steps must be >= 1 (got %d)", n_steps);
+    if (!(t_min >= 0.f && t_min < 1.f)) return fail("volume march: t_min must be in [0, 1) (got %g)", t_min);
+    if (!rgb && !depth && !opacity) return fail("volume march: rgb, depth and opacity are all NULL");
+    return 0;
+}
+
+extern "C" {
+
+int nerf_volume_sample(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
+                       int64_t M, float* out, int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume sample", volume, n, lo3, hi3)) return r;
+    if (M < 0) return fail("bad shape M=%lld", (long long)M);
+    if (M == 0) return 0;
+    if (!points || !out) return fail("NULL argument");
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* p = st.in(c->b_in0, points, (size_t)M * 12);
+    float* o = st.out(c->b_raw, out, (size_t)M * 16);
+    if (st.err) return st.err;
+    launch_volume_sample(vol, n, lo3, hi3, p, M, o, c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+int nerf_volume_march(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
+                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
+                      int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume march", volume, n, lo3, hi3)) return r;
+    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
+    if (N < 0) return fail("bad shape N=%lld", (long long)N);
+    if (N == 0) return 0;
+    if (!rays_orig || !rays_dirs) return fail("NULL argument");
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
+    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
+    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
+    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
+    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
+    if (st.err) return st.err;
+    launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb, ddepth, dopac,
+                        c->stream);
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
+                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
+                             float* rgb, float* depth, float* opacity, int mem) {
+    ENTER(c);
+    if (int r = volume_ok("volume render", volume, n, lo3, hi3)) return r;
+    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
+    if (!c2w) return fail("NULL argument");
+    if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
+    const long long total = (long long)H * W;
+    if (ray_count <= 0) { ray_begin = 0; ray_count = total; }
+    if (ray_begin < 0 || ray_begin + ray_count > total) return fail("ray slab [%lld,+%lld) outside %lld rays",
+                                                                    (long long)ray_begin, (long long)ray_count, total);
+    const long long N = ray_count, batch = std::min<long long>(N, 1 << 18);
+    if (int r = ensure(c, c->b_orig, (size_t)batch * 16)) return r;
+    if (int r = ensure(c, c->b_dirs, (size_t)batch * 16)) return r;
+    Staging st(c, mem);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
+    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
+    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
+    if (st.err) return st.err;
+    float *o = (float*)c->b_orig.p, *d = (float*)c->b_dirs.p;
+    for (long long off = 0; off < N; off += batch) {      // the rays of nerf_render_image, batch by batch on the stream
+        const long long m = std::min(batch, N - off);
+        launch_raygen(c2w, fov, H, W, ray_begin + off, m, o, d, c->stream);
+        if (c->ray_space == NERF_RAYS_NDC) launch_rays_to_ndc(o, d, m, fov, c->ndc_near_plane, o, d, c->stream);
+        launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
+                            drgb ? drgb + 3 * off : nullptr, ddepth ? ddepth + off : nullptr, dopac ? dopac + off : nullptr,
+                            c->stream);
+    }
+    HIP_OK(hipGetLastError());
+    return st.finish();
+}
+
+}  // extern "C"

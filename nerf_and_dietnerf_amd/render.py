@@ -163,6 +163,26 @@ def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
 
+def _host_floats(x, shape, name, exact=False) -> np.ndarray:
+    """A small host argument (numpy array, list or torch tensor) as a contiguous float32 array of ``shape``.  It may come in any
+    shape with that many components, unless ``exact`` asks for ``shape`` itself; shape None: any size, flattened."""
+    a = np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+    if shape is None:
+        return a.ravel()
+    if exact and a.shape != tuple(shape):
+        raise ValueError(f"{name} must be ({','.join(map(str, shape))})")
+    if a.size != int(np.prod(shape)):
+        raise ValueError(f"{name} must have {int(np.prod(shape))} components, got {a.size}")
+    return a.reshape(shape)
+
+
+def _box_corners(lo, hi) -> Tuple[np.ndarray, np.ndarray]:
+    lo_a, hi_a = _host_floats(lo, None, "lo"), _host_floats(hi, None, "hi")
+    if lo_a.size != 3 or hi_a.size != 3:
+        raise ValueError(f"box corners must have 3 components each, got {lo_a.size} and {hi_a.size}")
+    return lo_a, hi_a
+
+
 class _PinnedBlock:
     """One nerf_host_alloc allocation seen as a numpy array: ``np.asarray(block)`` makes an array whose ``base`` is this
     object, so the block lives exactly as long as the array or any view of it; then it returns to the pool."""
@@ -295,15 +315,15 @@ class _Arrays:
         self.keep.append(a)
         return a.ctypes.data
 
-    def out(self, shape):
+    def out(self, shape, dtype=np.float32):
         if self.torch:
-            t = self.torch.empty(tuple(shape), dtype=self.torch.float32, device=self.device)
+            t = self.torch.empty(tuple(shape), dtype=getattr(self.torch, np.dtype(dtype).name), device=self.device)
             self.keep.append(t)
             return t, t.data_ptr()
         nbytes = 4 * int(np.prod(shape, dtype=np.int64))
-        a = _pinned.take(shape) if nbytes >= _PinnedPool.MIN_BYTES else None
-        if a is None:                # small output, pinned budget exhausted or pinning failed: pageable memory
-            a = np.empty(tuple(shape), np.float32)
+        a = _pinned.take(shape) if dtype is np.float32 and nbytes >= _PinnedPool.MIN_BYTES else None
+        if a is None:                # small or non-float32 output, pinned budget exhausted or pinning failed: pageable memory
+            a = np.empty(tuple(shape), dtype)
         self.keep.append(a)
         return a, a.ctypes.data
 
@@ -532,26 +552,29 @@ class Context:
         the points lo + step * i, step = (hi - lo) / (n - 1).  ``view_dir``: three numbers, the view direction of every point
         (default (0, 0, 1), the bake's; ignored for n_angles == 0).  The result is a numpy array, or a torch-device tensor if
         ``view_dir`` is one or ``device_out`` is set."""
+        return self._lattice("density lattice", self.lib.nerf_density_lattice, which, n, (), [(view_dir, (3,), "view_dir")],
+                             view_dir, device_out)
+
+    def _lattice(self, what, entry, which, n, channels, small, probe, device_out):
+        """density_lattice and radiance_lattice: the checks, the (n, n, n) + ``channels`` output -- on the device if ``probe``
+        is a torch-device tensor or ``device_out`` is set -- and the call of ``entry`` with the ``small`` host arguments
+        ((value or None, shape, name), in the entry's order) between n and the output."""
         if self.scene_box is None:
-            raise RuntimeError("a density lattice needs a scene box (set_scene_box)")
+            raise RuntimeError(f"a {what} needs a scene box (set_scene_box)")
         n = int(n)
         if not 2 <= n <= 512:
-            raise ValueError(f"density lattice: n must be in 2..512 (got {n})")
-        if device_out and not (_is_torch(view_dir) and view_dir.is_cuda):
+            raise ValueError(f"{what}: n must be in 2..512 (got {n})")
+        if device_out and not (_is_torch(probe) and probe.is_cuda):
             import torch
             arr = self._arrays(torch.empty(1, device=torch.device("cuda", self.cfg.device)))   # torch's current stream
         else:
-            arr = self._arrays(view_dir)
-        pv = None
-        if view_dir is not None:
-            vd = np.ascontiguousarray(view_dir.detach().cpu().numpy() if _is_torch(view_dir) else view_dir, dtype=np.float32).ravel()
-            if vd.shape != (3,):
-                raise ValueError(f"view_dir must have 3 components, got {vd.shape[0]}")
-            pv = vd.ctypes.data
+            arr = self._arrays(probe)
+        host = [None if x is None else _host_floats(x, shape, name) for x, shape, name in small]
+        ptrs = [None if a is None else a.ctypes.data for a in host]
 
         def run():
-            out, p = arr.out((n, n, n))
-            _lib.check(self.lib.nerf_density_lattice(self.h, int(which), n, pv, p, arr.mem))
+            out, p = arr.out((n, n, n) + channels)
+            _lib.check(entry(self.h, int(which), n, *ptrs, p, arr.mem))
             return out
         return self._auto_call(run, arr.mem)
 
@@ -566,21 +589,14 @@ class Context:
             raise ValueError(f"sigma must be an (n, n, n) array, got {shape}")
         n = shape[0]
         ps = arr.inp(sigma, shape)
-        lo_a, hi_a = np.asarray(lo, np.float32).ravel(), np.asarray(hi, np.float32).ravel()
-        if lo_a.shape != (3,) or hi_a.shape != (3,):
-            raise ValueError(f"box corners must have 3 components each, got {lo_a.shape[0]} and {hi_a.shape[0]}")
+        lo_a, hi_a = _box_corners(lo, hi)
         nv, nt = C.c_int64(0), C.c_int64(0)
         _lib.check(self.lib.nerf_isosurface(self.h, ps, n, lo_a.ctypes.data, hi_a.ctypes.data, float(iso), C.byref(nv),
                                             C.byref(nt), arr.mem))
         v, t = int(nv.value), int(nt.value)
         vertices, pvx = arr.out((v, 3))
         nrm, pn = arr.out((v, 3)) if normals else (None, None)
-        if arr.torch is not None:
-            triangles = arr.torch.empty((t, 3), dtype=arr.torch.int32, device=arr.device)
-            pt = triangles.data_ptr()
-        else:
-            triangles = np.empty((t, 3), np.int32)
-            pt = triangles.ctypes.data
+        triangles, pt = arr.out((t, 3), np.int32)
         _lib.check(self.lib.nerf_isosurface_fetch(self.h, pvx, pn, pt, arr.mem))
         return vertices, triangles, nrm
 
@@ -610,31 +626,8 @@ class Context:
         keep it on the device)."""
         if view_dir is not None and camera is not None:
             raise ValueError("radiance lattice: give view_dir or camera, not both")
-        if self.scene_box is None:
-            raise RuntimeError("a radiance lattice needs a scene box (set_scene_box)")
-        n = int(n)
-        if not 2 <= n <= 512:
-            raise ValueError(f"radiance lattice: n must be in 2..512 (got {n})")
-        if device_out:
-            import torch
-            arr = self._arrays(torch.empty(1, device=torch.device("cuda", self.cfg.device)))   # torch's current stream
-        else:
-            arr = self._arrays()
-
-        def host(x, shape, name):
-            a = np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-            if a.size != int(np.prod(shape)):
-                raise ValueError(f"{name} must have {int(np.prod(shape))} components, got {a.size}")
-            return a.reshape(shape)
-        vd = None if view_dir is None else host(view_dir, (3,), "view_dir")
-        cam = None if camera is None else host(camera, (4, 4), "camera")
-        pv, pc = None if vd is None else vd.ctypes.data, None if cam is None else cam.ctypes.data
-
-        def run():
-            out, p = arr.out((n, n, n, 4))
-            _lib.check(self.lib.nerf_radiance_lattice(self.h, int(which), n, pv, pc, p, arr.mem))
-            return out
-        return self._auto_call(run, arr.mem)
+        return self._lattice("radiance lattice", self.lib.nerf_radiance_lattice, which, n, (4,),
+                             [(view_dir, (3,), "view_dir"), (camera, (4, 4), "camera")], None, device_out)
 
     @staticmethod
     def _volume_args(volume, lo, hi, what):
@@ -644,9 +637,7 @@ class Context:
             raise ValueError(f"volume must be an (n, n, n, 4) array, got {shape}")
         if not 2 <= shape[0] <= 512:
             raise ValueError(f"{what}: n must be in 2..512 (got {shape[0]})")
-        lo_a, hi_a = np.asarray(lo, np.float32).ravel(), np.asarray(hi, np.float32).ravel()
-        if lo_a.shape != (3,) or hi_a.shape != (3,):
-            raise ValueError(f"box corners must have 3 components each, got {lo_a.shape[0]} and {hi_a.shape[0]}")
+        lo_a, hi_a = _box_corners(lo, hi)
         if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
             raise ValueError(f"{what} needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
         return shape[0], lo_a, hi_a
@@ -700,9 +691,7 @@ class Context:
         arr = self._arrays(volume)
         n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume render")
         steps, t = self._march_args(n_steps, t_min)
-        c2w_h = np.ascontiguousarray(c2w.detach().cpu().numpy() if _is_torch(c2w) else c2w, dtype=np.float32)
-        if c2w_h.shape != (4, 4):
-            raise ValueError("c2w must be (4,4)")
+        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
         pvol = arr.inp(volume, (n, n, n, 4))
         lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
         rgb, p0 = arr.out(lead + (3,))
@@ -721,12 +710,7 @@ class Context:
         n = int(rays_orig.shape[0])
         po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
         bounds, pb = arr.out((n, 2))
-        if arr.torch is not None:
-            state = arr.torch.empty((n,), dtype=arr.torch.int32, device=arr.device)
-            ps = state.data_ptr()
-        else:
-            state = np.empty((n,), np.int32)
-            ps = state.ctypes.data
+        state, ps = arr.out((n,), np.int32)
         _lib.check(self.lib.nerf_ray_occupancy_bounds(self.h, po, pd, n, pb, ps, arr.mem))
         return bounds, state
 
@@ -760,12 +744,7 @@ class Context:
         arr = self._arrays(rays_orig, rays_dirs, z_values)
         n, s = int(z_values.shape[0]), int(z_values.shape[1])
         po, pd, pz = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4)), arr.inp(z_values, (n, s))
-        if arr.torch is not None:
-            keep = arr.torch.empty((n, s), dtype=arr.torch.int32, device=arr.device)
-            pk = keep.data_ptr()
-        else:
-            keep = np.empty((n, s), np.int32)
-            pk = keep.ctypes.data
+        keep, pk = arr.out((n, s), np.int32)
         _lib.check(self.lib.nerf_sample_occupancy(self.h, po, pd, pz, n, s, pk, arr.mem))
         return keep
 
@@ -789,12 +768,7 @@ class Context:
         n = int(rays_orig.shape[0])
         po, pd = arr.inp(rays_orig, (n, 4)), arr.inp(rays_dirs, (n, 4))
         bounds, pb = arr.out((n, 2))
-        if arr.torch is not None:
-            narrowed = arr.torch.empty((n,), dtype=arr.torch.int32, device=arr.device)
-            pn = narrowed.data_ptr()
-        else:
-            narrowed = np.empty((n,), np.int32)
-            pn = narrowed.ctypes.data
+        narrowed, pn = arr.out((n,), np.int32)
         _lib.check(self.lib.nerf_ray_box_bounds(self.h, po, pd, n, pb, pn, arr.mem))
         return bounds, narrowed
 
@@ -1229,9 +1203,7 @@ class Context:
 
     def get_rays_directions(self, height, width, field_of_view, c2w):
         arr = self._arrays(c2w if _is_torch(c2w) else None)
-        c2w_h = np.ascontiguousarray(c2w.detach().cpu().numpy() if _is_torch(c2w) else c2w, dtype=np.float32)
-        if c2w_h.shape != (4, 4):
-            raise ValueError("c2w must be (4,4)")
+        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
         out, p = arr.out((height, width, 4))
         _lib.check(self.lib.nerf_get_rays_directions(self.h, c2w_h.ctypes.data, float(field_of_view), height, width,
                                                      p, arr.mem))
@@ -1341,9 +1313,7 @@ class Context:
         if device_out and arr.torch is None:
             import torch
             arr = self._arrays(torch.empty(1, device=torch.device("cuda", self.cfg.device)))
-        c2w_h = np.ascontiguousarray(c2w.detach().cpu().numpy() if _is_torch(c2w) else c2w, dtype=np.float32)
-        if c2w_h.shape != (4, 4):
-            raise ValueError("c2w must be (4,4)")
+        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
         total = h * w
         fine = n_f > 0 and self.loaded[NERF_NET_FINE]
         s = n_c + n_f if fine else n_c
