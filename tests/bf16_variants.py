@@ -20,6 +20,8 @@ if ROOT not in sys.path:
 
 from oracle import nerf_oracle as O  # noqa: E402
 
+from support import kw  # noqa: E402,F401  (re-exported: V.kw, B.kw)
+
 F32 = np.float32
 
 # (Lx, Ld, n_angles) of the parity cases: both view-direction forms, the xyz-only network, fewer octaves, the wide-PE build
@@ -29,10 +31,6 @@ RANGE_SCALE = 3e4           # range_blob: layer-1 activations of the shipped net
 RANGE_BOUNDS = (2.0, 6.0)   # ... on the test view out to depth 6 (the library's default frustum); see test_bf16x3_host.py
 RAW_ROWS = 4173             # model_predict rows of the raw-output checks (ragged last tile)
 RAW_BAR_FACTOR = 4.0        # kernel vs its own emulation: 4 x the emulation's error against the oracle (raw_figures)
-
-
-def kw(lx, ld, na):
-    return dict(n_pos_enc_xyz=lx, n_pos_enc_dir=ld, n_angles=na)
 
 
 def bf16_rne(a) -> np.ndarray:

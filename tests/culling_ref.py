@@ -2,7 +2,7 @@
 include/nerf_mi355.h: nerf_ctx_set_sample_culling has the rule), in numpy with the device function's operations in its order,
 vectorised over samples.  ``dtype=F32`` rounds every operation on its own, as the device does; ``dtype=F64`` is the same rule in
 float64 on the same float32 inputs, the reference the float32 verdict is judged against.  Imported by
-tests/test_culling_host.py and tests/test_gpu_culling.py; nothing here touches the library.
+tests/test_culling_host.py and tests/test_gpu_culling.py; only culled_context, at the end, touches the library.
 
 A grid is a bool array (R, R, R) indexed [ix, iy, iz].  For sample (ray, s):
   1. p_a = o_a + d_a z, multiply then add
@@ -11,6 +11,9 @@ A grid is a bool array (R, R, R) indexed [ix, iy, iz].  For sample (ray, s):
      interior cell face to the upper cell
   4. culled iff inside and the cell is empty; every other sample is kept (outside the box the grid knows nothing)"""
 import numpy as np
+
+import sampling_space_ref as R
+from occupancy_ref import GOLDEN_BOX
 
 F32, F64 = np.float32, np.float64
 
@@ -60,7 +63,7 @@ def scatter_rows(rows, keep, width=4):
     return out
 
 
-# ---- hand cases: the box [-1, 1]^3 at R = 4 (cells of 0.5, every plane exact in float32) -------------------------------------------
+# ---- hand cases: the box [-1, 1]^3 at R = 4 (cells of 0.5, every plane exact in float32) -----------------------------------------
 HAND_LO, HAND_HI = np.array([-1.0, -1.0, -1.0], F32), np.array([1.0, 1.0, 1.0], F32)
 HAND_O = np.array([[0.25, 0.25, 4.0, 1.0]], F32)
 HAND_D = np.array([[0.0, 0.0, -1.0, 0.0]], F32)
@@ -84,3 +87,43 @@ def hand_grids():
             g[c] = True
         out.append((g, want))
     return out
+
+
+# ---- the golden scene of tests/test_gpu_culling.py, test_gpu_train_culling.py and test_gpu_ray_gradients.py  ---------------------
+HALF_GRID = np.random.default_rng(16).random((16, 16, 16)) < 0.5      # a 16^3 grid, about half full
+
+
+def camera_rays(oracle, golden_ckpt, n, spread=False):
+    """n rays of the golden training camera (a 23 x 23 image), the last ten turned round so that they miss the box: the first
+    n, or with ``spread`` n spread evenly over the image -- its first rows see only empty space, where the colour branch gets
+    no gradient."""
+    o, d = R.world_rays(oracle, golden_ckpt["c2w_train"], float(golden_ckpt["fov"]), 23, 23)
+    idx = (np.arange(n) * len(o)) // n if spread else slice(n)
+    o, d = np.ascontiguousarray(o[idx]), np.ascontiguousarray(d[idx])
+    if n > 10:
+        d[-10:, :3] *= -1.0
+    return o, d
+
+
+def train_scene(oracle, golden_ckpt, n, sc, sf, seed):
+    """n spread camera rays with draws, targets and a d_rgb cotangent (drawn in this order), the shipped weights and bounds."""
+    o, d = camera_rays(oracle, golden_ckpt, n, spread=True)
+    rng = np.random.default_rng(seed)
+    return dict(o=o, d=d, n=n, sc=sc, sf=sf, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
+                tgt=rng.random((n, 3), dtype=np.float32), d_rgb=(rng.standard_normal((n, 3)) * 0.1).astype(np.float32),
+                near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]), bc=golden_ckpt["blob_coarse"],
+                bf=golden_ckpt["blob_fine"])
+
+
+def culled_context(p, grid, flag, box=GOLDEN_BOX, precision="fp32", **kw):
+    """A context on the scene's weights and bounds under the box and the grid, with training-time sample culling set to flag."""
+    import nerf_and_dietnerf_amd as N
+    c = N.Context(near=p["near"], far=p["far"], precision=precision, **kw)
+    c.load_weights(0, p["bc"])
+    c.load_weights(1, p["bf"])
+    c.set_scene_box(*box)
+    if grid is not None:
+        c.set_occupancy_grid(grid)
+    c.set_train_sample_culling(flag)
+    assert c.train_sample_culling is bool(flag)
+    return c

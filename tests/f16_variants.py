@@ -22,6 +22,8 @@ if ROOT not in sys.path:
 
 from oracle import nerf_oracle as O  # noqa: E402
 
+from support import kw  # noqa: E402,F401  (re-exported: V.kw, B.kw)
+
 # (Lx, Ld, n_angles); Ld is unused by the xyz-only network
 TWO_TILE = [(3, 2, 2), (1, 1, 2), (5, 4, 1), (4, 3, 1), (2, 2, 1)]
 ONE_TILE_XYZ = [(5, 4, 0), (1, 4, 0), (3, 2, 0)]
@@ -31,10 +33,6 @@ TILES1_GEOMETRIES = [(5, 4, 2), (3, 2, 2), (4, 3, 1)]     # the one-tile kernel 
 EPILOGUES = (True, "c_in", False)
 GPU_BAR = 2e-3             # kernel vs its own emulation, relative to max(1, |emu|) (tests/test_gpu_parity.py's bar)
 HOST_ROWS = 4173           # rows the cross-epilogue comparisons run on (a prefix of every GPU row set)
-
-
-def kw(lx, ld, na):
-    return dict(n_pos_enc_xyz=lx, n_pos_enc_dir=ld, n_angles=na)
 
 
 def epilogue_of(lx, na, tiles1=False):

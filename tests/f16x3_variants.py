@@ -56,6 +56,7 @@ from oracle import nerf_oracle as O  # noqa: E402
 
 import bf16_variants as B  # noqa: E402
 import f16_variants as V  # noqa: E402
+import support as S  # noqa: E402
 
 F32 = np.float32
 
@@ -69,7 +70,7 @@ SHRINK_KS = (0, -4, -8, -12, -16)   # shrink_blob exponents of the low-magnitude
 PASSES = ("hl", "lh", "hh")         # kernel order: w_hi x_lo, w_lo x_hi, w_hi x_hi
 PASS_NAMES = {"hl": "w_hi.x_lo", "lh": "w_lo.x_hi", "hh": "w_hi.x_hi"}
 
-kw = B.kw
+kw = S.kw
 inputs = V.inputs
 rel_err = V.rel_err
 rays = B.rays

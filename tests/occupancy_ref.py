@@ -219,3 +219,41 @@ def hand_rays():
     o = np.array([list(r[0]) + [1.0] for r in HAND_RAYS], F32)
     d = np.array([list(r[1]) + [0.0] for r in HAND_RAYS], F32)
     return o, d
+
+
+# ---- the scenes of tests/test_gpu_occupancy.py and tests/test_gpu_culling.py -----------------------------------------------------
+NDC_NEAR = 0.5
+NDC_BOX = ((-0.5, -0.4, -0.6), (0.5, 0.4, 0.4))            # NDC rays run from z = -1 (t = 0) to z = +1 (t = 1)
+GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))        # around the golden scene's content, as seen from its cameras
+
+
+def grid_for(r, lo, hi):
+    """The two balls on an r^3 grid over (lo, hi), plus 3 % scattered cells (seeded by r)."""
+    return two_balls(r, lo, hi) | (np.random.default_rng(r).random((r, r, r)) < 0.03)
+
+
+def arm(ctx, lo, hi, near, far, grid):
+    ctx.set_sampling("linear")
+    ctx.set_bounds(near, far)
+    ctx.set_scene_box(lo, hi)
+    if grid is not None:
+        ctx.set_occupancy_grid(grid)
+
+
+def world_scene(n):
+    """The six hand rays, then rays of the issue's recipe, n in all -> (o, d, lo, hi, near, far)."""
+    ho, hd = hand_rays()
+    o, d = sphere_rays(n - len(ho), seed=11)
+    return np.concatenate([ho, o]), np.concatenate([hd, d]), LO, HI, NEAR, FAR
+
+
+def ndc_scene(ctx, n=65 * 65):
+    """The first n rays of a 65 x 65 image of a forward-facing camera through ctx.rays_to_ndc (4225 NDC rays), bounds 0 and 1."""
+    import sampling_space_ref as R
+    poses, fov = R.forward_facing_poses()
+    c2w = poses[1]
+    dirs = ctx.get_rays_directions(65, 65, fov, c2w).reshape(-1, 4)
+    orig = np.tile(c2w[:, 3], (65 * 65, 1)).astype(np.float32)
+    o, d = ctx.rays_to_ndc(orig, dirs, fov, NDC_NEAR)
+    return (np.ascontiguousarray(o[:n]), np.ascontiguousarray(d[:n]), np.array(NDC_BOX[0], np.float32),
+            np.array(NDC_BOX[1], np.float32), 0.0, 1.0)

@@ -94,3 +94,22 @@ def render_outputs_gradient_sets(blob_c, blob_f, rays_o, rays_d, near, far, u_c,
         grads[name] = (np.concatenate(flat[:len(pc)]), np.concatenate(flat[len(pc):]) if pf is not None else None)
     rgb, depth, w, z = (t.detach().numpy() for t in outs)
     return dict(rgb=rgb, depth=depth, weights=w, z=z, grads=grads)
+
+
+# ---- what tests/test_gpu_render_outputs.py and tests/test_gpu_ray_gradients.py both draw and call --------------------------------
+NAMES = ("d_rgb", "d_depth", "d_weights", "d_z")
+
+
+def cotangents(n, s, seed=3):
+    """0.1 N(0, 1) for each of the four outputs; d_rgb is drawn first, as test_backward_through_render draws its own."""
+    rng = np.random.default_rng(seed)
+    shapes = {"d_rgb": (n, 3), "d_depth": (n,), "d_weights": (n, s), "d_z": (n, s)}
+    return {k: (rng.standard_normal(shapes[k]) * 0.1).astype(np.float32) for k in NAMES}
+
+
+def draws(p):
+    return (p["sc"], p["sf"], p["u_c"], p["u_f"])
+
+
+def forward(ctx, p, slot=0, **kw):
+    return ctx.train_render_forward_outputs(slot, p["o"], p["d"], *draws(p), **kw)

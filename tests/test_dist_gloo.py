@@ -4,13 +4,14 @@ stand-in model whose per-ray output is a pure function of the global ray index -
 the real renderer has (Philox keyed by global ray index; tests/test_gpu_parity.py checks slab
 invariance on the device)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+import support as S
 
 
 class _FakeModel:
@@ -43,17 +44,11 @@ def _worker(rank, world, port, h, w, rgb_only, q):
         dist.destroy_process_group()
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.mark.parametrize("h,w,rgb_only", [(8, 8, True), (5, 3, False), (1, 1, True)])
 def test_sharded_assembly_world2(h, w, rgb_only):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = S.free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, h, w, rgb_only, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -98,7 +93,7 @@ def _video_worker(rank, world, port, n_frames, q):
 def test_video_frame_sharding_world2(n_frames):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = S.free_port()
     procs = [ctx.Process(target=_video_worker, args=(r, 2, port, n_frames, q)) for r in range(2)]
     for p in procs:
         p.start()

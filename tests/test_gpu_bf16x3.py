@@ -11,40 +11,20 @@ was built (coarse / fine network of bf16_variants.blobs, 4173 rows):
     (5,4,2)  3.84e-6 / 4.96e-6   -> bar 1.53e-5 / 1.99e-5        (3,2,2)   4.08e-6 / 3.24e-6   -> 1.63e-5 / 1.30e-5
     (5,4,1)  3.89e-6 / 3.75e-6   -> bar 1.56e-5 / 1.50e-5        (10,4,2)  3.91e-6 / 5.15e-6   -> 1.56e-5 / 2.06e-5
     (5,4,0)  4.43e-6 / 4.14e-6   -> bar 1.77e-5 / 1.66e-5        (7,2,0)   4.34e-6 / 4.86e-6   -> 1.74e-5 / 1.94e-5"""
-import ctypes as C
 import types
 
 import numpy as np
 import pytest
 
 import bf16_variants as B
-from test_video_pins import (DEPTH_BAR, DEPTH_MEAN_BAR, DEPTH_SELF_MARGIN, NET, RGB_BAR, RGB_MEAN_BAR, RGB_SELF_MARGIN,
-                             frames, psnr, scene, tours)  # noqa: F401  (frames, scene: fixtures)
+import support as S
+from video_ref import (DEPTH_BAR, DEPTH_MEAN_BAR, DEPTH_SELF_MARGIN, NET, RGB_BAR, RGB_MEAN_BAR, RGB_SELF_MARGIN,
+                       frames, psnr, scene, tours)  # noqa: F401  (frames, scene: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 NEAR, FAR = 0.6, 2.4
-
-
-def _context(blob_pair, lx=5, ld=4, na=2, precision="bf16x3", near=NEAR, far=FAR):
-    import nerf_and_dietnerf_amd as N
-    ctx = N.Context(near=near, far=far, precision=precision, **B.kw(lx, ld, na))
-    for which, blob in enumerate(blob_pair):
-        if blob is not None:
-            ctx.load_weights(which, blob)
-    return ctx
-
-
-def _same_bits(a, b, label):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape and np.isfinite(a).all(), label
-    diff = int(np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)))
-    assert diff == 0, (label, diff, float(np.abs(a - b).max()))
-
-
-def _n_cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
+WEIGHTS_ONLY, WITH_RGB = ("weights",), ("weights", "rgb")      # outputs {weights}: the sigma-only path; with rgb: the full network
 
 
 # ---- 1. parity ----
@@ -55,7 +35,7 @@ def test_parity_with_the_oracle_and_with_its_own_emulation(oracle, lx, ld, na, c
     the oracle; nothing non-finite."""
     bc, bf = B.blobs(lx, ld, na)
     kw = B.kw(lx, ld, na)
-    ctx = _context((bc, bf), lx, ld, na)
+    ctx = S.blob_context((bc, bf), lx, ld, na, precision="bf16x3")
     try:
         coarse, fine = oracle.unpack_blob(bc, **kw), oracle.unpack_blob(bf, **kw)
         o, d, rng = B.rays(64, 2 + lx + 7 * ld + 31 * na)
@@ -95,8 +75,8 @@ def test_range_beyond_fp16(oracle, golden_ckpt, capsys):
     c2w, fov = golden_ckpt["c2w_test"], float(golden_ckpt["fov"])
     ref = oracle.render_image(oracle.unpack_blob(big), oracle.unpack_blob(bf), c2w, fov, 12, 12, near, far, 64, 128, seed=3)[0]
     assert np.isfinite(ref).all()
-    f16 = _context((big, bf), precision="f16x3", near=near, far=far)
-    bf16 = _context((big, bf), near=near, far=far)
+    f16 = S.blob_context((big, bf), precision="f16x3", near=near, far=far)
+    bf16 = S.blob_context((big, bf), near=near, far=far, precision="bf16x3")
     try:
         f16.render_image(c2w, fov, 12, 12, 0, 64, 128, seed=3)
         n16 = f16.read_nonfinite()
@@ -113,49 +93,23 @@ def test_range_beyond_fp16(oracle, golden_ckpt, capsys):
 
 
 # ---- 3. sigma-only coarse pass ----
-def _render_rays(ctx, o, d, z, with_rgb):
-    from nerf_and_dietnerf_amd import _lib
-    n, s = z.shape
-    w = np.full((n, s), np.nan, np.float32)
-    rgb = np.full((n, 3), np.nan, np.float32)
-    outs = _lib.NerfOutputs()
-    outs.weights = w.ctypes.data
-    if with_rgb:
-        outs.rgb = rgb.ctypes.data
-    _lib.check(ctx.lib.nerf_render_rays(ctx.h, 0, o.ctypes.data, d.ctypes.data, z.ctypes.data, n, s, C.byref(outs),
-                                        _lib.NERF_MEM_HOST))
-    return w
-
-
-def _rays_z(n, s, seed=3):
-    rng = np.random.default_rng(seed)
-    o = np.zeros((n, 4), np.float32)
-    o[:, :3] = rng.uniform(-0.3, 0.3, (n, 3))
-    o[:, 2] += 1.5
-    d = np.zeros((n, 4), np.float32)
-    d[:, :3] = rng.uniform(-0.4, 0.4, (n, 3))
-    d[:, 2] = -1.0
-    z = np.sort(rng.uniform(NEAR, FAR, (n, s)), axis=1).astype(np.float32)
-    return o, d, z
-
-
 @pytest.mark.parametrize("lx,ld,na", [(5, 4, 2), (5, 4, 1), (3, 2, 2)])
 def test_sigma_only_coarse_pass_is_bit_identical(oracle, lx, ld, na):
     """A coarse render_rays that asks for the weights alone runs mlp_bf16x3_sig_kernel; with rgb as well, the full kernel:
     the same bits, from one row to every workgroup looping twice.  And an rgb-only render_image equals the render with all
     six outputs."""
-    ctx = _context(B.blobs(lx, ld, na), lx, ld, na)
+    ctx = S.blob_context(B.blobs(lx, ld, na), lx, ld, na, precision="bf16x3")
     try:
-        for n, s in [(1, 1), (1, 64), (37, 64), (129, 3), (2 * _n_cus() * 128 + 77, 1), (2 * _n_cus() * 2 + 1, 64)]:
-            o, d, z = _rays_z(n, s)
-            full = _render_rays(ctx, o, d, z, True)
-            _same_bits(_render_rays(ctx, o, d, z, False), full, f"({lx},{ld},{na}) N={n} S={s}")
+        for n, s in [(1, 1), (1, 64), (37, 64), (129, 3), (2 * S.n_cus() * 128 + 77, 1), (2 * S.n_cus() * 2 + 1, 64)]:
+            o, d, z = S.rays_towards_origin(n, s, NEAR, FAR)
+            full = S.render_rays(ctx, 0, o, d, z, WITH_RGB)[0]
+            S.assert_same_bits(S.render_rays(ctx, 0, o, d, z, WEIGHTS_ONLY)[0], full, f"({lx},{ld},{na}) N={n} S={s}", finite=True)
             if s > 1 and n > 1:
                 assert full.max() > 1e-3
         c2w = oracle.get_sphere_matrix(1.0, -25.0, 40.0, 0.0).astype(np.float32)
         all_six = ctx.render_image(c2w, 0.6, 40, 40, 0, 64, 128, seed=5)
         only = ctx.render_image(c2w, 0.6, 40, 40, 0, 64, 128, seed=5, rgb_only=True)
-        _same_bits(only[0], all_six[0], "rgb-only render_image vs all six outputs")
+        S.assert_same_bits(only[0], all_six[0], "rgb-only render_image vs all six outputs", finite=True)
         assert ctx.read_nonfinite() == 0
     finally:
         ctx.close()
@@ -167,7 +121,7 @@ def test_batch_slab_and_mode_switch_invariance(oracle, golden_ckpt):
     context leaves the f16x3 result as it was."""
     c2w, fov = golden_ckpt["c2w_test"], float(golden_ckpt["fov"])
     near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
-    ctx = _context((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), precision="f16x3", near=near, far=far)
+    ctx = S.blob_context((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), precision="f16x3", near=near, far=far)
     try:
         h = w = 48
         before = ctx.render_image(c2w, fov, h, w, 0, 64, 128, seed=9)
@@ -177,17 +131,17 @@ def test_batch_slab_and_mode_switch_invariance(oracle, golden_ckpt):
         for batch in (128, 777, 4096):
             part = ctx.render_image(c2w, fov, h, w, batch, 64, 128, seed=9)
             for i, (a, b) in enumerate(zip(part, whole)):
-                _same_bits(a, b, f"batch {batch}, output {i}")
+                S.assert_same_bits(a, b, f"batch {batch}, output {i}", finite=True)
         cuts = [0, 1, 130, 1000, 1777, h * w]
         slabs = [ctx.render_image(c2w, fov, h, w, 512, 64, 128, seed=9, ray_begin=a, ray_count=b - a)
                  for a, b in zip(cuts[:-1], cuts[1:])]
         for i in range(6):
             glued = np.concatenate([np.asarray(s[i]) for s in slabs])
-            _same_bits(glued, np.asarray(whole[i]).reshape(glued.shape), f"slabs, output {i}")
+            S.assert_same_bits(glued, np.asarray(whole[i]).reshape(glued.shape), f"slabs, output {i}", finite=True)
         ctx.set_precision("f16x3")
         after = ctx.render_image(c2w, fov, h, w, 0, 64, 128, seed=9)
         for i, (a, b) in enumerate(zip(after, before)):
-            _same_bits(a, b, f"f16x3 after the switch, output {i}")
+            S.assert_same_bits(a, b, f"f16x3 after the switch, output {i}", finite=True)
         assert ctx.read_nonfinite() == 0
     finally:
         ctx.close()
@@ -201,11 +155,11 @@ def test_render_after_train_steps_matches_fresh_context(oracle, lx, ld, na, mixe
     same bits as a fresh bf16x3 context loaded with get_weights()."""
     rng = np.random.default_rng(7)
     n, sc, sf = 512, 64, 128
-    o, d, _ = _rays_z(n, 1, seed=9)
+    o, d, _ = S.rays_towards_origin(n, 1, NEAR, FAR, seed=9)
     tgt = rng.random((n, 3), dtype=np.float32)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     c2w = oracle.get_sphere_matrix(1.0, -25.0, 40.0, 0.0).astype(np.float32)
-    trained = _context(B.blobs(lx, ld, na), lx, ld, na)
+    trained = S.blob_context(B.blobs(lx, ld, na), lx, ld, na, precision="bf16x3")
     fresh = None
     try:
         start = trained.render_image(c2w, 0.6, 32, 32, 0, sc, sf, seed=4)
@@ -214,10 +168,10 @@ def test_render_after_train_steps_matches_fresh_context(oracle, lx, ld, na, mixe
             trained.train_step(o, d, tgt, sc, sf, u_c, u_f)
         got = trained.render_image(c2w, 0.6, 32, 32, 0, sc, sf, seed=4)
         assert np.count_nonzero(got[0] != start[0]) > 0                       # the weights moved
-        fresh = _context((trained.get_weights(0), trained.get_weights(1)), lx, ld, na)
+        fresh = S.blob_context((trained.get_weights(0), trained.get_weights(1)), lx, ld, na, precision="bf16x3")
         want = fresh.render_image(c2w, 0.6, 32, 32, 0, sc, sf, seed=4)
         for i, (a, b) in enumerate(zip(got, want)):
-            _same_bits(a, b, f"trained vs fresh, output {i}")
+            S.assert_same_bits(a, b, f"trained vs fresh, output {i}", finite=True)
         trained.train_end()
     finally:
         trained.close()
@@ -242,7 +196,7 @@ def test_every_resident_stream_follows_reloads_and_train_steps(oracle, lx, na):
         for p in precisions:
             ctx.set_precision(p)
             got = ctx.render(o, d, sc, sf, u_c, u_f)
-            fresh = _context(pair, lx, 4, na, precision=p)
+            fresh = S.blob_context(pair, lx, 4, na, precision=p)
             try:
                 want = fresh.render(o, d, sc, sf, u_c, u_f)
             finally:
@@ -251,7 +205,7 @@ def test_every_resident_stream_follows_reloads_and_train_steps(oracle, lx, na):
                 np.testing.assert_array_equal(a, b, err_msg=f"{label}, {p}, output {i}")
 
     first, second, third = (B.blobs(lx, 4, na, seed=s) for s in (11, 31, 51))
-    ctx = _context(first, lx, 4, na, precision=precisions[0])
+    ctx = S.blob_context(first, lx, 4, na, precision=precisions[0])
     try:
         check(ctx, first, "(a) first load")
         for which, blob in enumerate(second):
@@ -296,7 +250,7 @@ def test_reloading_a_blob_gives_its_first_render_again(oracle, lx, ld, na):
             out[p] = ctx.render(o, d, sc, sf, u_c, u_f)
         return out
 
-    ctx = _context(blob_a, lx, ld, na, precision=precisions[0])
+    ctx = S.blob_context(blob_a, lx, ld, na, precision=precisions[0])
     try:
         first = render_all(ctx)
         load(ctx, blob_b)
@@ -304,7 +258,7 @@ def test_reloading_a_blob_gives_its_first_render_again(oracle, lx, ld, na):
         load(ctx, blob_a)
         last = render_all(ctx)
         for p in precisions:
-            fresh = _context(blob_a, lx, ld, na, precision=p)
+            fresh = S.blob_context(blob_a, lx, ld, na, precision=p)
             try:
                 want = fresh.render(o, d, sc, sf, u_c, u_f)
             finally:
@@ -342,8 +296,8 @@ def test_auto_falls_back_to_bf16x3_on_a_wide_network(oracle, golden_ckpt):
                                       batch_size_render=4096, model_coarse=_Keras(big), model_fine=_Keras(fine))
     seeds = iter(range(100, 200))
     ctx = mi355_shim.attach(ref_model, to_tensor=lambda a: a, seed_source=lambda: next(seeds))      # precision: the default
-    bf = _context((big, fine), 10, 4, 2, near=near, far=far)
-    f16x3 = _context((plain, fine), 10, 4, 2, precision="f16x3", near=near, far=far)
+    bf = S.blob_context((big, fine), 10, 4, 2, near=near, far=far, precision="bf16x3")
+    f16x3 = S.blob_context((plain, fine), 10, 4, 2, precision="f16x3", near=near, far=far)
     try:
         assert ctx.precision == "auto" and ctx.cfg.precision == N._lib.NERF_PRECISION_F16X3
         img = ref_model.render_image(c2w, fov, 24, 24)                                                  # seed 100
@@ -351,16 +305,17 @@ def test_auto_falls_back_to_bf16x3_on_a_wide_network(oracle, golden_ckpt):
         assert ctx.cfg.precision == N._lib.NERF_PRECISION_BF16X3
         want = bf.render_image(c2w, fov, 24, 24, 0, 64, 128, seed=100)
         for i, (a, b) in enumerate(zip(img, want)):
-            _same_bits(a, b, f"auto fallback vs plain bf16x3, output {i}")
+            S.assert_same_bits(a, b, f"auto fallback vs plain bf16x3, output {i}", finite=True)
         img2 = ref_model.render_image(c2w, fov, 24, 24)                                                 # seed 101
-        _same_bits(img2[0], bf.render_image(c2w, fov, 24, 24, 0, 64, 128, seed=101)[0], "second call")
+        S.assert_same_bits(img2[0], bf.render_image(c2w, fov, 24, 24, 0, 64, 128, seed=101)[0], "second call", finite=True)
         assert ctx.auto_fallbacks == 1 and ctx.cfg.precision == N._lib.NERF_PRECISION_BF16X3
         ref_model.model_coarse = _Keras(plain)
         ctx.refresh_weights()
         assert ctx.cfg.precision == N._lib.NERF_PRECISION_F16X3
         img3 = ref_model.render_image(c2w, fov, 24, 24)                                                 # seed 102
         assert ctx.cfg.precision == N._lib.NERF_PRECISION_F16X3 and ctx.auto_fallbacks == 1
-        _same_bits(img3[0], f16x3.render_image(c2w, fov, 24, 24, 0, 64, 128, seed=102)[0], "ordinary weights stay on f16x3")
+        S.assert_same_bits(img3[0], f16x3.render_image(c2w, fov, 24, 24, 0, 64, 128, seed=102)[0], "ordinary weights stay on f16x3",
+                           finite=True)
     finally:
         for c in (ctx, bf, f16x3):
             c.close()
@@ -407,7 +362,7 @@ def test_rate_against_f16x3(golden_ckpt, capsys):
     count and rate, one conversion less per pair).  The measured ratio is recorded in DESIGN.md section 4.1."""
     c2w, fov = golden_ckpt["c2w_test"], float(golden_ckpt["fov"])
     near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
-    ctxs = {p: _context((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), precision=p, near=near, far=far)
+    ctxs = {p: S.blob_context((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), precision=p, near=near, far=far)
             for p in ("f16x3", "bf16x3")}
     try:
         ms = {p: [] for p in ctxs}

@@ -9,34 +9,14 @@ import pytest
 
 import culling_ref as K
 import occupancy_ref as G
-import sampling_space_ref as R
+import support as S
 
 pytestmark = pytest.mark.gpu
 
 NEAR, FAR = G.NEAR, G.FAR
-NDC_NEAR = 0.5
-NDC_BOX = ((-0.5, -0.4, -0.6), (0.5, 0.4, 0.4))
-GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))
 WIDE_BOX = ((-1.5, -1.5, -2.2), (1.5, 1.5, 0.5))
 NO_GRID = "no occupancy grid"
 PRECISIONS = ["fp32", "f16x3", "f16", "bf16x3"]
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def _same_bits(got, want):
-    assert len(got) == len(want)
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(_bits(a).reshape(_bits(b).shape), _bits(b))
-
-
-def _grid_for(r, lo, hi):
-    """The two balls on an r^3 grid over (lo, hi), plus 3 % scattered cells (seeded by r)."""
-    return G.two_balls(r, lo, hi) | (np.random.default_rng(r).random((r, r, r)) < 0.03)
 
 
 # ---- 1. the verdict ------------------------------------------------------------------------------------------------------------
@@ -51,29 +31,13 @@ def ctx():
 @pytest.fixture(scope="module")
 def world(ctx):
     """The six hand rays of the grid's tests, then 4090 rays of its recipe: 4096 in all."""
-    ho, hd = G.hand_rays()
-    o, d = G.sphere_rays(4096 - len(ho), seed=11)
-    return np.concatenate([ho, o]), np.concatenate([hd, d]), G.LO, G.HI, NEAR, FAR
+    return G.world_scene(4096)
 
 
 @pytest.fixture(scope="module")
 def ndc(ctx):
     """A 65 x 65 image of a forward-facing camera through rays_to_ndc (its first 4096 rays), bounds 0 and 1."""
-    poses, fov = R.forward_facing_poses()
-    c2w = poses[1]
-    dirs = ctx.get_rays_directions(65, 65, fov, c2w).reshape(-1, 4)
-    orig = np.tile(c2w[:, 3], (65 * 65, 1)).astype(np.float32)
-    o, d = ctx.rays_to_ndc(orig, dirs, fov, NDC_NEAR)
-    return (np.ascontiguousarray(o[:4096]), np.ascontiguousarray(d[:4096]), np.array(NDC_BOX[0], np.float32),
-            np.array(NDC_BOX[1], np.float32), 0.0, 1.0)
-
-
-def _arm(c, lo, hi, near, far, grid):
-    c.set_sampling("linear")
-    c.set_bounds(near, far)
-    c.set_scene_box(lo, hi)
-    if grid is not None:
-        c.set_occupancy_grid(grid)
+    return G.ndc_scene(ctx, 4096)
 
 
 @pytest.mark.parametrize("n", [1, 63, 65, 4096])
@@ -83,12 +47,12 @@ def _arm(c, lo, hi, near, far, grid):
 def test_verdicts_equal_the_restatement(ctx, world, ndc, space, r, s, n):
     """Depths drawn on the grid's own bounds, as a render draws them; one wave, a wave and a lane, many blocks."""
     o, d, lo, hi, near, far = world if space == "world" else ndc
-    grid = _grid_for(r, lo, hi)
+    grid = G.grid_for(r, lo, hi)
     u = np.random.default_rng(s).random((4096, s), dtype=np.float32)
     z = np.ascontiguousarray(G.z_values(o, d, lo, hi, near, far, grid, u)[:n])
     o, d = o[:n], d[:n]
     want = K.sample_keep(o, d, z, lo, hi, grid, K.F32)
-    _arm(ctx, lo, hi, near, far, grid)
+    G.arm(ctx, lo, hi, near, far, grid)
     keep = ctx.sample_occupancy(o, d, z)
     assert keep.dtype == np.int32 and keep.shape == (n, s)
     np.testing.assert_array_equal(keep, want.astype(np.int32))
@@ -104,7 +68,7 @@ def test_verdicts_equal_the_restatement(ctx, world, ndc, space, r, s, n):
 def test_hand_cases_on_the_device(ctx):
     """A point on the hi face, on an interior cell face, outside the box, and a NaN depth (tests/culling_ref.py)."""
     for grid, want in K.hand_grids():
-        _arm(ctx, K.HAND_LO, K.HAND_HI, NEAR, FAR, grid)
+        G.arm(ctx, K.HAND_LO, K.HAND_HI, NEAR, FAR, grid)
         assert ctx.sample_occupancy(K.HAND_O, K.HAND_D, K.HAND_Z).tolist() == [[int(w) for w in want]]
 
 
@@ -119,7 +83,7 @@ def gold(golden_ckpt):
     c.close()
 
 
-def _gold_arm(c, precision, grid, cull, box=GOLDEN_BOX):
+def _gold_arm(c, precision, grid, cull, box=G.GOLDEN_BOX):
     c.set_precision(precision)
     c.set_scene_box(*box)
     if grid is not None:
@@ -128,32 +92,10 @@ def _gold_arm(c, precision, grid, cull, box=GOLDEN_BOX):
     c.read_culling()
 
 
-def _camera_rays(oracle, golden_ckpt, n):
-    """The first n rays of the golden training camera (a 23 x 23 image), the last ten turned round so that they miss the box."""
-    o, d = R.world_rays(oracle, golden_ckpt["c2w_train"], float(golden_ckpt["fov"]), 23, 23)
-    o, d = np.ascontiguousarray(o[:n]), np.ascontiguousarray(d[:n])
-    if n > 10:
-        d[-10:, :3] *= -1.0
-    return o, d
-
-
-RANDOM_GRID = np.random.default_rng(16).random((16, 16, 16)) < 0.5
-
-
 def _outputs7(n, s):
     from nerf_and_dietnerf_amd._lib import NerfOutputs
     arrays = [np.empty(shape, np.float32) for shape in ((n, 3), (n, s), (n, s), (n, s), (n, s, 3), (n, s), (n,))]
     return NerfOutputs(*[a.ctypes.data for a in arrays]), arrays
-
-
-def _render_rays7(c, which, o, d, z):
-    """All seven outputs of nerf_render_rays: rgb, weights, cumprod, alpha, rgb_samples, z, depth."""
-    from nerf_and_dietnerf_amd import _lib
-    n, s = z.shape
-    outs, arrays = _outputs7(n, s)
-    o, d, z = (np.ascontiguousarray(x, np.float32) for x in (o, d, z))
-    _lib.check(c.lib.nerf_render_rays(c.h, which, o.ctypes.data, d.ctypes.data, z.ctypes.data, n, s, C.byref(outs), _lib.NERF_MEM_HOST))
-    return arrays
 
 
 def _ray_marching7(c, raw, z):
@@ -167,24 +109,24 @@ def _ray_marching7(c, raw, z):
 
 # ---- 2. off is off -------------------------------------------------------------------------------------------------------------
 def test_culling_without_a_grid_is_off(oracle, golden_ckpt, gold):
-    o, d = _camera_rays(oracle, golden_ckpt, 130)
+    o, d = K.camera_rays(oracle, golden_ckpt, 130)
     rng = np.random.default_rng(2)
     u_c, u_f = rng.random((130, 8), dtype=np.float32), rng.random((130, 16), dtype=np.float32)
     _gold_arm(gold, "f16x3", None, False)
     want = gold.render(o, d, 8, 16, u_c, u_f, want_depth=True)
     z = gold.get_z_values_for_rays(o, d, 8, uniform_values=u_c)
-    want_rays = _render_rays7(gold, 0, o, d, z)
+    want_rays = S.render_rays(gold, 0, o, d, z, S.RENDER_OUTPUTS)
     gold.set_sample_culling(True)
-    _same_bits(gold.render(o, d, 8, 16, u_c, u_f, want_depth=True), want)
-    _same_bits(_render_rays7(gold, 0, o, d, z), want_rays)
+    S.assert_same_bits_each(gold.render(o, d, 8, 16, u_c, u_f, want_depth=True), want)
+    S.assert_same_bits_each(S.render_rays(gold, 0, o, d, z, S.RENDER_OUTPUTS), want_rays)
     assert gold.read_culling() == (0, 0)
     with pytest.raises(RuntimeError, match=NO_GRID):
         gold.sample_occupancy(o, d, z)
     # the flag outlives a grid that comes and goes
-    gold.set_occupancy_grid(RANDOM_GRID)
+    gold.set_occupancy_grid(K.HALF_GRID)
     gold.set_occupancy_grid(None)
     assert gold.sample_culling
-    _same_bits(_render_rays7(gold, 0, o, d, z), want_rays)
+    S.assert_same_bits_each(S.render_rays(gold, 0, o, d, z, S.RENDER_OUTPUTS), want_rays)
     assert gold.read_culling() == (0, 0)
     gold.set_sample_culling(False)
 
@@ -196,12 +138,12 @@ RAY_SIZES = [(1, 2), (130, 24), (521, 40)]
 @pytest.fixture(scope="module")
 def compact_scene(oracle, golden_ckpt, gold):
     """Per size: rays, the depths the context draws for them under the random grid, and the restatement's verdict."""
-    _gold_arm(gold, "fp32", RANDOM_GRID, False)
+    _gold_arm(gold, "fp32", K.HALF_GRID, False)
     out = {}
     for n, s in RAY_SIZES:
-        o, d = _camera_rays(oracle, golden_ckpt, n)
+        o, d = K.camera_rays(oracle, golden_ckpt, n)
         z = gold.get_z_values_for_rays(o, d, s, seed=n)
-        keep = K.sample_keep(o, d, z, *GOLDEN_BOX, RANDOM_GRID, K.F32)
+        keep = K.sample_keep(o, d, z, *G.GOLDEN_BOX, K.HALF_GRID, K.F32)
         out[(n, s)] = (o, d, z, keep)
     assert any(v[3].sum() % 128 != 0 for v in out.values())              # a last tile of the network kernels that is not full
     assert any(v[3].any() and not v[3].all() for v in out.values())      # kept and culled samples exist
@@ -217,20 +159,20 @@ def test_render_rays_equals_the_network_on_the_compacted_rows(gold, compact_scen
     o, d, z, keep = compact_scene[(n, s)]
     pts = K.sample_points(o, d, z, K.F32)
     dirs = np.broadcast_to(d[:, None, :3], (n, s, 3))
-    _gold_arm(gold, precision, RANDOM_GRID, False)
+    _gold_arm(gold, precision, K.HALF_GRID, False)
     m = int(keep.sum())
     raw_c = gold.model_predict(which, np.ascontiguousarray(pts[keep]), np.ascontiguousarray(dirs[keep])) if m else np.zeros((0, 4), np.float32)
     # row independence, which the bake already relies on: the network on all rows, restricted to the kept ones
     raw_all = gold.model_predict(which, np.ascontiguousarray(pts.reshape(-1, 3)), np.ascontiguousarray(dirs.reshape(-1, 3)))
-    np.testing.assert_array_equal(_bits(raw_all.reshape(n, s, 4)[keep]), _bits(raw_c))
+    np.testing.assert_array_equal(S.bits(raw_all.reshape(n, s, 4)[keep]), S.bits(raw_c))
     want = _ray_marching7(gold, K.scatter_rows(raw_c, keep), z)
     gold.set_sample_culling(True)
     gold.read_culling()
-    got = _render_rays7(gold, which, o, d, z)
+    got = S.render_rays(gold, which, o, d, z, S.RENDER_OUTPUTS)
     assert gold.read_culling() == (n * s, m)
     assert gold.read_culling() == (0, 0)                                  # read clears
     gold.set_sample_culling(False)
-    _same_bits(got, want)
+    S.assert_same_bits_each(got, want)
     culled = ~keep
     if culled.any():                                                      # what the rule promises of a culled sample
         assert not got[1][culled].any() and not got[3][culled].any() and (got[4][culled] == 0.5).all()
@@ -242,20 +184,20 @@ def test_render_equals_the_chain_done_by_hand(oracle, golden_ckpt, gold, precisi
     """render's coarse pass is the sigma-only network where the precision has one (f16x3): this pins the culled sigma-only pass
     to the culled full one."""
     n, sc, sf = 130, 8, 16
-    o, d = _camera_rays(oracle, golden_ckpt, n)
+    o, d = K.camera_rays(oracle, golden_ckpt, n)
     rng = np.random.default_rng(4)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
-    _gold_arm(gold, precision, RANDOM_GRID, True)
+    _gold_arm(gold, precision, K.HALF_GRID, True)
     got = gold.render(o, d, sc, sf, u_c, u_f, want_depth=True)
     samples, kept = gold.read_culling()
     assert samples == n * (sc + sc + sf) and 0 < kept < samples
     zc = gold.get_z_values_for_rays(o, d, sc, uniform_values=u_c)
-    weights = _render_rays7(gold, 0, o, d, zc)[1]
+    weights = S.render_rays(gold, 0, o, d, zc, S.RENDER_OUTPUTS)[1]
     _, zf = gold.get_z_vals_from_prob_dist_func(weights, zc, sf, uniform_values=u_f, return_merged=True)
-    want = _render_rays7(gold, 1, o, d, zf)
+    want = S.render_rays(gold, 1, o, d, zf, S.RENDER_OUTPUTS)
     gold.set_sample_culling(False)
-    _same_bits(got, want)
-    _same_bits([got[5]], [zf])
+    S.assert_same_bits_each(got, want)
+    S.assert_same_bits_each([got[5]], [zf])
 
 
 # ---- 5. nothing kept ---------------------------------------------------------------------------------------------------------
@@ -263,7 +205,7 @@ def test_nothing_kept(oracle, golden_ckpt, gold):
     """An all-zero grid and rays whose depths all lie inside the box: no row reaches the network and every output is an exact
     zero.  With ten rays that miss the box appended, those equal the culling-off render bit for bit."""
     n, s = 130, 24
-    o, d = _camera_rays(oracle, golden_ckpt, n)
+    o, d = K.camera_rays(oracle, golden_ckpt, n)
     empty = np.zeros((16, 16, 16), bool)
     _gold_arm(gold, "f16x3", empty, False)
     bounds, narrowed = gold.ray_box_bounds(o, d)
@@ -272,11 +214,11 @@ def test_nothing_kept(oracle, golden_ckpt, gold):
     oi, di, bi = o[hit], d[hit], bounds[hit]
     t = (np.arange(s, dtype=np.float32) + np.float32(0.5)) / np.float32(s)
     zi = (bi[:, :1] + (bi[:, 1:] - bi[:, :1]) * t[None, :]).astype(np.float32)
-    inside, _ = K.sample_cells(oi, di, zi, *GOLDEN_BOX, 16, K.F32)
-    assert inside.all() and not K.sample_keep(oi, di, zi, *GOLDEN_BOX, empty, K.F32).any()
+    inside, _ = K.sample_cells(oi, di, zi, *G.GOLDEN_BOX, 16, K.F32)
+    assert inside.all() and not K.sample_keep(oi, di, zi, *G.GOLDEN_BOX, empty, K.F32).any()
     gold.set_sample_culling(True)
     gold.read_culling()
-    got = _render_rays7(gold, 1, oi, di, zi)
+    got = S.render_rays(gold, 1, oi, di, zi, S.RENDER_OUTPUTS)
     assert gold.read_culling() == (zi.size, 0)
     for k in (0, 1, 3, 6):                                                # rgb, weights, alpha, depth
         assert np.isfinite(got[k]).all() and not got[k].any()
@@ -284,12 +226,12 @@ def test_nothing_kept(oracle, golden_ckpt, gold):
     # the same with the ten rays that miss the box
     om, dm = np.concatenate([oi, o[-10:]]), np.concatenate([di, d[-10:]])
     zm = np.concatenate([zi, np.tile(zi[:1], (10, 1))])
-    assert K.sample_keep(om, dm, zm, *GOLDEN_BOX, empty, K.F32)[-10:].all()
-    got = _render_rays7(gold, 1, om, dm, zm)
+    assert K.sample_keep(om, dm, zm, *G.GOLDEN_BOX, empty, K.F32)[-10:].all()
+    got = S.render_rays(gold, 1, om, dm, zm, S.RENDER_OUTPUTS)
     assert gold.read_culling() == (zm.size, 10 * s)
     gold.set_sample_culling(False)
-    off = _render_rays7(gold, 1, om, dm, zm)
-    _same_bits([g[-10:] for g in got], [w[-10:] for w in off])
+    off = S.render_rays(gold, 1, om, dm, zm, S.RENDER_OUTPUTS)
+    S.assert_same_bits_each([g[-10:] for g in got], [w[-10:] for w in off])
     assert not got[0][:-10].any() and not got[1][:-10].any() and not got[6][:-10].any()
     assert off[1][:-10].any()                                            # and without culling those rays do see the network
 
@@ -300,7 +242,7 @@ def test_a_full_grid_is_culling_off(oracle, golden_ckpt, gold, precision):
     """Every sample kept: the network in point mode on the gathered points against ray mode, which forms the same points with the
     same two rounded operations."""
     n, sc, sf = 130, 8, 16
-    o, d = _camera_rays(oracle, golden_ckpt, n)
+    o, d = K.camera_rays(oracle, golden_ckpt, n)
     rng = np.random.default_rng(6)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     _gold_arm(gold, precision, np.ones((16, 16, 16), bool), False)
@@ -309,22 +251,22 @@ def test_a_full_grid_is_culling_off(oracle, golden_ckpt, gold, precision):
     got = gold.render(o, d, sc, sf, u_c, u_f, want_depth=True)
     assert gold.read_culling() == (n * (2 * sc + sf), n * (2 * sc + sf))
     gold.set_sample_culling(False)
-    _same_bits(got, want)
+    S.assert_same_bits_each(got, want)
 
 
 # ---- 7. render_image ---------------------------------------------------------------------------------------------------------
 def test_render_image_is_slab_and_batch_invariant_with_culling(golden_ckpt, gold):
     (h, w), sc, sf, seed = (23, 23), 8, 16, 5
     c2w, fov = golden_ckpt["c2w_train"], float(golden_ckpt["fov"])
-    _gold_arm(gold, "f16x3", RANDOM_GRID, True)
+    _gold_arm(gold, "f16x3", K.HALF_GRID, True)
     whole = gold.render_image(c2w, fov, h, w, 0, sc, sf, seed=seed, want_depth=True)
     samples, kept = gold.read_culling()
     assert samples == h * w * (2 * sc + sf) and 0 < kept < samples
-    _same_bits(gold.render_image(c2w, fov, h, w, 100, sc, sf, seed=seed, want_depth=True), whole)
+    S.assert_same_bits_each(gold.render_image(c2w, fov, h, w, 100, sc, sf, seed=seed, want_depth=True), whole)
     first = gold.render_image(c2w, fov, h, w, 0, sc, sf, seed=seed, ray_begin=0, ray_count=200, want_depth=True)
     rest = gold.render_image(c2w, fov, h, w, 64, sc, sf, seed=seed, ray_begin=200, ray_count=329, want_depth=True)
     flat = [a.reshape((h * w,) + a.shape[2:]) for a in whole]
-    _same_bits([np.concatenate([a, b]) for a, b in zip(first, rest)], flat)
+    S.assert_same_bits_each([np.concatenate([a, b]) for a, b in zip(first, rest)], flat)
     gold.set_sample_culling(False)
     off = gold.render_image(c2w, fov, h, w, 0, sc, sf, seed=seed, want_depth=True)
     assert not np.array_equal(off[1], whole[1])                           # and culling did act
@@ -334,7 +276,7 @@ def test_render_image_is_slab_and_batch_invariant_with_culling(golden_ckpt, gold
 def test_the_trainer_ignores_the_flag(oracle, golden_ckpt):
     import nerf_and_dietnerf_amd as N
     n, sc, sf = 130, 8, 16
-    o, d = _camera_rays(oracle, golden_ckpt, n)
+    o, d = K.camera_rays(oracle, golden_ckpt, n)
     rng = np.random.default_rng(8)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     tgt = rng.random((n, 3), dtype=np.float32)
@@ -343,8 +285,8 @@ def test_the_trainer_ignores_the_flag(oracle, golden_ckpt):
         c = N.Context(near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]), precision="fp32")
         c.load_weights(0, golden_ckpt["blob_coarse"])
         c.load_weights(1, golden_ckpt["blob_fine"])
-        c.set_scene_box(*GOLDEN_BOX)
-        c.set_occupancy_grid(RANDOM_GRID)
+        c.set_scene_box(*G.GOLDEN_BOX)
+        c.set_occupancy_grid(K.HALF_GRID)
         c.set_sample_culling(cull)
         c.train_begin(5e-4, mixed_float16=False)
         res.append(c.train_gradients(o, d, tgt, sc, sf, u_c, u_f))
@@ -353,16 +295,16 @@ def test_the_trainer_ignores_the_flag(oracle, golden_ckpt):
         c.close()
     (m0, gc0, gf0), (m1, gc1, gf1) = res
     assert m0 == m1 and np.isfinite(gc0).all() and gc0.any()
-    _same_bits([gc1, gf1], [gc0, gf0])
+    S.assert_same_bits_each([gc1, gf1], [gc0, gf0])
 
 
 # ---- 9. the model class --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cull", [True, False])
 def test_render_config_turns_culling_on(golden_ckpt, cull):
     import nerf_and_dietnerf_amd as N
-    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(GOLDEN_BOX[0]), list(GOLDEN_BOX[1])],
+    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(G.GOLDEN_BOX[0]), list(G.GOLDEN_BOX[1])],
           "occupancy_grid": {"resolution": 16, "sigma_threshold": 10.0, "dilate": 0, "cull_samples": cull}}
-    m = N.NeRF(NET, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="f16x3")
+    m = N.NeRF(S.NET, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="f16x3")
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     assert m.ctx.sample_culling is cull
     count = m.update_occupancy_grid()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import grad_blocks as GB
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +33,6 @@ def _embedder(dtype, device):
     for prm in net.parameters():
         prm.requires_grad_(False)
     return lambda x: net(x.permute(0, 3, 1, 2))          # (B,224,224,3) -> (B,32)
-
-
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a = np.asarray(a, np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
 
 
 def _setup(oracle, golden_ckpt, alpha, mixed, side=12, samples=8, n=48, sc=16, sf=24, seed=5, **kw):
@@ -119,8 +111,8 @@ def test_dietnerf_step_gradients_match_autograd(oracle, golden_ckpt, alpha, keep
     assert abs(metrics["psnr_coarse"] - r["psnr_coarse"]) <= 1e-4 and abs(metrics["psnr_fine"] - r["psnr_fine"]) <= 1e-4
     gc, gf = gc.cpu().numpy(), gf.cpu().numpy()
     np.testing.assert_array_equal(gc, model.ctx.train_get_gradients(0))       # the returned copies are the ctx's blobs
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
-    cc, cf = _cos(gc, r["grad_coarse"]), _cos(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
+    cc, cf = S.cos(gc, r["grad_coarse"]), S.cos(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[DietNeRF consistency step, alpha {alpha:g}, activations {'kept' if keep else 're-computed'}] gradients vs float64 autograd of src/DietNeRF.py:120-222: "
               f"coarse {ec:.2e}, fine {ef:.2e} of max|g|; cosine {cc:.7f}, {cf:.7f}; consistency loss "
@@ -173,7 +165,7 @@ def test_dietnerf_plain_steps_use_the_doubled_coarse_term(oracle, golden_ckpt, c
     coarse_only = T.train_gradients(golden_ckpt["blob_coarse"], None, p["o"], p["d"], p["tgt"], p["near"], p["far"],
                                     draws[0], None, alpha=1.0)
     want_c = both["grad_coarse"] + coarse_only["grad_coarse"]
-    assert _relerr(gc, want_c) <= 2e-4 and _relerr(gf, both["grad_fine"]) <= 2e-4
+    assert S.relerr(gc, want_c) <= 2e-4 and S.relerr(gf, both["grad_fine"]) <= 2e-4
     import torch
     both32 = T.train_gradients(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"], p["o"], p["d"], p["tgt"], p["near"],
                                p["far"], *draws, alpha=1.0, dtype=torch.float32)
@@ -200,7 +192,7 @@ def test_dietnerf_step_under_mixed_float16(oracle, golden_ckpt, keep, capsys):
     assert used
     r, _ = _oracle_step(oracle, golden_ckpt, model, p, 21, 1.0, fp16_loss_scale=32768.0)
     gc, gf = gc.cpu().numpy(), gf.cpu().numpy()
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[DietNeRF consistency step, mixed_float16] gradients vs the fp16-emulating autograd oracle: coarse "
               f"{ec:.2e}, fine {ef:.2e} of max|g|; consistency loss {metrics['cosine_similarity_loss']:.5f} "
@@ -269,7 +261,7 @@ def test_dietnerf_schedule_and_fit_at_the_reference_constants(oracle, golden_ckp
     model.ctx.close()
 
 
-def _dp_rank(rank, world, port, q, golden, seed):
+def _dp_rank(rank, world, port, golden, seed, q):
     import os
     import torch
     import torch.distributed as dist
@@ -288,7 +280,7 @@ def _dp_rank(rank, world, port, q, golden, seed):
         u_c = torch.as_tensor(O.philox_uniform(9, ray, p["sc"], 0)[rank * n:(rank + 1) * n], device="cuda")
         u_f = torch.as_tensor(O.philox_uniform(9, ray, p["sf"], 1)[rank * n:(rank + 1) * n], device="cuda")
         model.train_step(shard, u_coarse=u_c, u_fine=u_f, seed=9, group=dist.group.WORLD, want_metrics=False)
-        q.put((rank, model.ctx.train_get_gradients(0), model.ctx.train_get_gradients(1), model.ctx.get_weights(1)))
+        q.put((rank, (model.ctx.train_get_gradients(0), model.ctx.train_get_gradients(1), model.ctx.get_weights(1))))
         model.ctx.close()
     finally:
         dist.destroy_process_group()
@@ -298,9 +290,7 @@ def test_dietnerf_data_parallel_step_equals_single_rank(oracle, golden_ckpt):
     """BASELINE configs[3] names 4 GPUs: two ranks (gloo, sharing this box's GPU) take half the ray batch each AND half the
     source image's rays each (one all-gather assembles the image, the embedding runs replicated, each rank back-propagates
     its slab); after one mean all-reduce per blob the gradients applied are the single-rank step's."""
-    import socket
     import torch
-    import torch.multiprocessing as mp
     golden = {k: golden_ckpt[k] for k in ("near", "far", "fov", "blob_coarse", "blob_fine", "c2w_train", "c2w_test")}
     model, data, p = _setup(oracle, golden_ckpt, 1.0, mixed=False, seed=5)
     model.counter = 12
@@ -312,21 +302,11 @@ def test_dietnerf_data_parallel_step_equals_single_rank(oracle, golden_ckpt):
     model.ctx.train_apply()
     w_full = model.ctx.get_weights(1)
     model.ctx.close()
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    procs = [mpc.Process(target=_dp_rank, args=(r, 2, port, q, golden, 5)) for r in range(2)]
-    for pr in procs:
-        pr.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
-    for pr in procs:
-        pr.join(timeout=60)
-    for rank, gc, gf, w in res:
-        assert _relerr(gc, gc_full) <= 1e-5 and _relerr(gf, gf_full) <= 1e-5, rank
+    res = S.run_ranks(_dp_rank, 2, (S.free_port(), golden, 5), timeout=300)
+    for rank, (gc, gf, w) in enumerate(res):
+        assert S.relerr(gc, gc_full) <= 1e-5 and S.relerr(gf, gf_full) <= 1e-5, rank
         assert np.abs(w - w_full).max() <= 1e-6
-    np.testing.assert_array_equal(res[0][3], res[1][3])
+    np.testing.assert_array_equal(res[0][2], res[1][2])
 
 
 def test_get_nerf_from_the_reference_configs(oracle, golden_ckpt, tmp_path, capsys):
@@ -416,11 +396,11 @@ def test_dietnerf_without_a_fine_network(oracle, golden_ckpt, capsys):
                              oracle.philox_uniform(lc["seed"], pix, s, 0), None, side, emb64,
                              targets[lc["target_index"]].numpy(), alpha=1.0)
     gc = gc.cpu().numpy()
-    ec = _relerr(gc, r["grad_coarse"])
+    ec = S.relerr(gc, r["grad_coarse"])
     with capsys.disabled():
         print(f"\n[DietNeRF, coarse network only] gradient vs float64 autograd {ec:.2e} of max|g|; loss {metrics['loss']:.5f} "
               f"(oracle {r['loss'] + r['cosine_similarity_loss']:.5f})")
-    assert ec <= 5e-4 and _cos(gc, r["grad_coarse"]) > 0.9999999
+    assert ec <= 5e-4 and S.cos(gc, r["grad_coarse"]) > 0.9999999
     assert abs(metrics["loss_for_rays"] - r["loss_for_rays"]) <= 5e-6 * r["loss_for_rays"]
     assert abs(metrics["loss"] - (r["loss"] + r["cosine_similarity_loss"])) <= 5e-6 * r["loss"]
     model.ctx.train_apply()

@@ -10,6 +10,8 @@ import pytest
 
 import distortion_ref as D
 import grad_blocks as GB
+from occupancy_ref import GOLDEN_BOX
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -17,7 +19,6 @@ BLOCKS = GB.blocks(5, 4, 2)
 NEAR, FAR = 2.0, 6.0                       # the operator tests' bounds
 SIZES = [1, 2, 63, 64, 65, 129, 1024]      # the chunk seams, the single-sample ray, the longest coarse pass
 N_RAYS = 5                                 # a partly filled block of four rays
-GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))
 
 
 # ---- shared references (computed once) --------------------------------------------------------------------------------------------
@@ -35,22 +36,6 @@ def _operator_case(s):
     return w, z, ref, own
 
 
-def _rays(oracle, n, seed=0, hw=8):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(hw, hw, 0.46, c2w).reshape(-1, 4)
-    idx = rng.choice(d.shape[0], n, replace=n > d.shape[0])
-    return np.tile(c2w[:, 3], (n, 1)).astype(np.float32), np.ascontiguousarray(d[idx]), rng
-
-
-def _problem(oracle, golden_ckpt, n=48, sc=16, sf=24, seed=0):
-    """tests/test_gpu_train.py::_problem."""
-    o, d, rng = _rays(oracle, n, seed)
-    return dict(o=o, d=d, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
-                tgt=rng.random((n, 3), dtype=np.float32), sc=sc, sf=sf, near=float(golden_ckpt["near"]),
-                far=float(golden_ckpt["far"]), bc=golden_ckpt["blob_coarse"], bf=golden_ckpt["blob_fine"])
-
-
 _REFS = {}
 
 
@@ -64,27 +49,8 @@ def _ref(p, key, dtype="float64", **kw):
     return _REFS[full]
 
 
-def _ctx(p, **kw):
-    import nerf_and_dietnerf_amd as N
-    kw.setdefault("precision", "fp32")
-    ctx = N.Context(near=p["near"], far=p["far"], **kw)
-    ctx.load_weights(0, p["bc"])
-    ctx.load_weights(1, p["bf"])
-    return ctx
-
-
 def _grads(ctx, p):
     return ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
-
-
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _same_bits(got, want):
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32),
-                                      np.ascontiguousarray(b, np.float32).view(np.uint32))
 
 
 def _raw_call(ctx, w, z, want=(True, True, True)):
@@ -134,7 +100,7 @@ def test_operator_against_the_float64_definition(op_ctx, s, mem, capsys):
             want = tuple(i != k for i in range(3))
             rc, outs = _raw_call(op_ctx, w, z, want)
             assert rc == 0 and outs[k] is None
-            _same_bits([o for o in outs if o is not None], [g for i, g in enumerate(got) if i != k])
+            S.assert_same_bits_each([o for o in outs if o is not None], [g for i, g in enumerate(got) if i != k])
         rc, _ = _raw_call(op_ctx, w, z, (False, False, False))
         assert rc == 0
 
@@ -148,11 +114,11 @@ def test_operator_gives_the_same_bits_on_every_run(op_ctx, s):
     first = [g.cpu().numpy() for g in op_ctx.distortion_loss(wd, zd)]
     again = [g.cpu().numpy() for g in op_ctx.distortion_loss(wd, zd)]
     host = [np.array(g) for g in op_ctx.distortion_loss(w, z)]
-    _same_bits(again, first)
-    _same_bits(host, first)
+    S.assert_same_bits_each(again, first)
+    S.assert_same_bits_each(host, first)
     # ... and for another batching of the rays: a ray's results do not depend on its neighbours in the block
     alone = [g.cpu().numpy() for g in op_ctx.distortion_loss(wd[3:4].contiguous(), zd[3:4].contiguous())]
-    _same_bits(alone, [f[3:4] for f in first])
+    S.assert_same_bits_each(alone, [f[3:4] for f in first])
 
 
 # ---- 3. the regulariser alone, through the network -----------------------------------------------------------------------------------
@@ -169,10 +135,10 @@ def test_regulariser_alone_through_the_network(oracle, golden_ckpt, lam, sampler
     5e-6 of its max, far below any fp32 bar.  The third case, weights (0, 1), takes the coarse pass's own term away: the
     coarse blob is then the sampler term alone, the reference without dL/dz is off by 2.2 x the blob's max, and it is that
     case which shows the term is there."""
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     kw = dict(loss_w=(0.0, 0.0), lam=lam, sampler_grad=sampler_gradient, alpha=1.0)
     r, r32 = _ref(p, "default", **kw), _ref(p, "default", "float32", **kw)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, sampler_gradient=sampler_gradient)
     ctx.train_set_loss_weights(0.0, 0.0)
     ctx.train_set_distortion_weights(*lam)
@@ -184,16 +150,16 @@ def test_regulariser_alone_through_the_network(oracle, golden_ckpt, lam, sampler
     tag = f"[distortion alone, weights {lam}, 48 x (16+24), alpha 1, sampler term {'on' if sampler_gradient else 'off'}]"
     with capsys.disabled():
         print(f"\n    {tag} L coarse {sums['distortion_coarse']:.6f} (ref {r['dist_coarse']:.6f}), fine "
-              f"{sums['distortion_fine']:.6f} (ref {r['dist_fine']:.6f}); blob error coarse {_relerr(gc, r['grad_coarse']):.2e}, "
-              f"fine {_relerr(gf, r['grad_fine']):.2e} of max|g|", end="")
+              f"{sums['distortion_fine']:.6f} (ref {r['dist_fine']:.6f}); blob error coarse {S.relerr(gc, r['grad_coarse']):.2e}, "
+              f"fine {S.relerr(gf, r['grad_fine']):.2e} of max|g|", end="")
         GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, 2e-4, tag + " coarse")
         GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, 2e-4, tag + " fine")
-    assert _relerr(gc, r["grad_coarse"]) <= 2e-4 and _relerr(gf, r["grad_fine"]) <= 2e-4
+    assert S.relerr(gc, r["grad_coarse"]) <= 2e-4 and S.relerr(gf, r["grad_fine"]) <= 2e-4
     if sampler_gradient:
         no_dz = _ref(p, "default", **kw, dz_term=False)
         np.testing.assert_array_equal(no_dz["grad_fine"], r["grad_fine"])      # (the fine network does not see that term)
         with capsys.disabled():
-            print(f"; the reference without dL/dz differs by {_relerr(no_dz['grad_coarse'], r['grad_coarse']):.2e} of the "
+            print(f"; the reference without dL/dz differs by {S.relerr(no_dz['grad_coarse'], r['grad_coarse']):.2e} of the "
                   f"coarse blob's max", end="")
             if lam[0] == 0.0:
                 with pytest.raises(AssertionError):
@@ -208,24 +174,24 @@ def test_mse_and_regulariser_together(oracle, golden_ckpt, shape, sampler_gradie
     partly filled block; 65 coarse samples: one past a chunk seam; 7 fine ones) takes the blob bar of
     tests/test_gpu_train.py::test_gradients_at_ragged_shapes, 5e-4."""
     n, sc, sf = shape
-    p = _problem(oracle, golden_ckpt, n=n, sc=sc, sf=sf, seed=0 if n == 48 else 11)
+    p = S.golden_problem(oracle, golden_ckpt, n=n, sc=sc, sf=sf, seed=0 if n == 48 else 11)
     kw = dict(loss_w=(1.0, 1.0), lam=(0.01, 0.01), sampler_grad=sampler_gradient, alpha=1.0)
     key = "default" if n == 48 else "ragged"
     r, r32 = _ref(p, key, **kw), _ref(p, key, "float32", **kw)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, sampler_gradient=sampler_gradient)
     ctx.train_set_distortion_weights(0.01, 0.01)
     m, gc, gf = _grads(ctx, p)
     ctx.close()
     tag = f"[MSE + 0.01 distortion, {n} x ({sc}+{sf}), alpha 1, sampler term {'on' if sampler_gradient else 'off'}]"
     with capsys.disabled():
-        print(f"\n    {tag} blob error coarse {_relerr(gc, r['grad_coarse']):.2e}, fine {_relerr(gf, r['grad_fine']):.2e} of "
+        print(f"\n    {tag} blob error coarse {S.relerr(gc, r['grad_coarse']):.2e}, fine {S.relerr(gf, r['grad_fine']):.2e} of "
               f"max|g|", end="")
         GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, blob_bar, tag + " coarse")
         GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, blob_bar, tag + " fine")
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]                         # the metric stays the weighted MSE sum
     assert abs(m["psnr_coarse"] - r["psnr_coarse"]) <= 1e-4 and abs(m["psnr_fine"] - r["psnr_fine"]) <= 1e-4
-    assert _relerr(gc, r["grad_coarse"]) <= blob_bar and _relerr(gf, r["grad_fine"]) <= blob_bar
+    assert S.relerr(gc, r["grad_coarse"]) <= blob_bar and S.relerr(gf, r["grad_fine"]) <= blob_bar
 
 
 # ---- 5. mixed_float16 -------------------------------------------------------------------------------------------------------------
@@ -235,12 +201,12 @@ def test_mixed_float16_policy(oracle, golden_ckpt, capsys):
     larger on this problem, a regulariser without its loss scale would hide under the fp16-class bars) -- against the autograd
     oracle that rounds where the kernels round, block by block (grad_blocks.check_mixed); the unscaled gradients at two
     initial loss scales agree as in tests/test_gpu_train.py::test_mixed_float16_policy_gradients_and_loss_scaling."""
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     grads = {}
     for scale in (32768.0, 4096.0):
         kw = dict(loss_w=(0.0, 0.0), lam=(1.0, 1.0), sampler_grad=True, alpha=1.0, fp16_loss_scale=scale)
         r16, e32 = _ref(p, "default", **kw), _ref(p, "default", "float32", **kw)
-        ctx = _ctx(p, leaky_relu_alpha=1.0)
+        ctx = S.golden_context(p, leaky_relu_alpha=1.0)
         ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=scale)
         ctx.train_set_loss_weights(0.0, 0.0)
         ctx.train_set_distortion_weights(1.0, 1.0)
@@ -264,16 +230,16 @@ def test_mixed_float16_policy(oracle, golden_ckpt, capsys):
 # ---- 6. off means off -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
 def test_off_means_off(oracle, golden_ckpt, policy):
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     d_rgb = (np.random.default_rng(3).standard_normal((48, 3)) * 0.1).astype(np.float32)
     mixed = policy == "mixed_float16"
-    never = _ctx(p)
+    never = S.golden_context(p)
     never.train_begin(5e-4, mixed_float16=mixed)
     m0, gc0, gf0 = _grads(never, p)
     render0 = never.train_render_gradients(p["o"], p["d"], d_rgb, p["sc"], p["sf"], p["u_c"], p["u_f"])
     assert never.train_read_distortion_sums() == ({"distortion_coarse": 0.0, "distortion_fine": 0.0}, 0)
     never.close()
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4, mixed_float16=mixed)
     ctx.train_set_distortion_weights(0.5, 0.25)
     m1, gc1, gf1 = _grads(ctx, p)
@@ -281,19 +247,19 @@ def test_off_means_off(oracle, golden_ckpt, policy):
     assert m1 == m0 and not np.array_equal(gc1, gc0) and not np.array_equal(gf1, gf0)
     # the backward passes through render() ignore it
     render1 = ctx.train_render_gradients(p["o"], p["d"], d_rgb, p["sc"], p["sf"], p["u_c"], p["u_f"])
-    _same_bits(render1, render0)
+    S.assert_same_bits_each(render1, render0)
     # switched off again: the step of a context that never heard of it
     ctx.train_set_distortion_weights(0.0, 0.0)
     m2, gc2, gf2 = _grads(ctx, p)
     assert m2 == m0
-    _same_bits([gc2, gf2], [gc0, gf0])
+    S.assert_same_bits_each([gc2, gf2], [gc0, gf0])
     assert ctx.train_read_distortion_sums()[1] == 1
     # a restarted trainer starts without it
     ctx.train_set_distortion_weights(0.5, 0.25)
     ctx.train_begin(5e-4, mixed_float16=mixed)
     m3, gc3, gf3 = _grads(ctx, p)
     assert m3 == m0
-    _same_bits([gc3, gf3], [gc0, gf0])
+    S.assert_same_bits_each([gc3, gf3], [gc0, gf0])
     ctx.close()
 
 
@@ -301,10 +267,10 @@ def test_off_means_off(oracle, golden_ckpt, policy):
 def test_full_grid_culling_is_the_flag_off(oracle, golden_ckpt):
     """A culled sample has weight zero and the compositing runs on all samples: the trainer's sample culling needs no special
     case.  Under a full grid, where every sample is kept, the gradients with the regulariser are the flag-off ones bit for bit."""
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     res = []
     for flag in (False, True):
-        ctx = _ctx(p)
+        ctx = S.golden_context(p)
         ctx.set_scene_box(*GOLDEN_BOX)
         ctx.set_occupancy_grid(np.ones((16, 16, 16), bool))
         ctx.set_train_sample_culling(flag)
@@ -316,7 +282,7 @@ def test_full_grid_culling_is_the_flag_off(oracle, golden_ckpt):
         res.append((m, [gc, gf], ctx.train_read_distortion_sums()))
         ctx.close()
     assert res[0][0] == res[1][0] and res[0][2] == res[1][2] and res[0][1][0].any() and res[0][1][1].any()
-    _same_bits(res[1][1], res[0][1])
+    S.assert_same_bits_each(res[1][1], res[0][1])
 
 
 # ---- 8. the running sums ------------------------------------------------------------------------------------------------------------
@@ -324,12 +290,12 @@ def test_running_sums(oracle, golden_ckpt, capsys):
     """Three nerf_train_gradients calls on three batches: the sums are the reference's three L values added up, the bar test
     1's bar for L_ray (4 x the float32 restatement's error, the largest over test 1's sizes) times the pass's S; a read clears
     them; a pass whose weight is 0 adds nothing."""
-    probs = [_problem(oracle, golden_ckpt, n=12, seed=s) for s in (0, 1, 2)]
+    probs = [S.golden_problem(oracle, golden_ckpt, n=12, seed=s) for s in (0, 1, 2)]
     refs = [_ref(q, f"sums{i}", alpha=1.0) for i, q in enumerate(probs)]
     want = {"distortion_coarse": sum(r["dist_coarse"] for r in refs), "distortion_fine": sum(r["dist_fine"] for r in refs)}
     bar_ray = 4 * max(_operator_case(s)[3][0] for s in SIZES)
     bars = {"distortion_coarse": bar_ray * 16, "distortion_fine": bar_ray * 24}
-    ctx = _ctx(probs[0], leaky_relu_alpha=1.0)
+    ctx = S.golden_context(probs[0], leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4)
     ctx.train_set_distortion_weights(0.01, 0.01)
     for q in probs:
@@ -364,10 +330,10 @@ def test_the_regulariser_lowers_the_fine_distortion(oracle, golden_ckpt, capsys)
     nerf_train_gradients call under the same weights.  It ends lower with the regulariser.
     K = 20 and weights (0, 1) were chosen once, on the GPU, and were the first pair tried: L ended at 0.167408 without and at
     0.019766 with the regulariser."""
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     ends = []
     for on in (False, True):
-        ctx = _ctx(p)
+        ctx = S.golden_context(p)
         ctx.train_begin(5e-4)
         if on:
             ctx.train_set_distortion_weights(*BEHAVIOUR_WEIGHTS)
@@ -389,8 +355,8 @@ def test_the_regulariser_lowers_the_fine_distortion(oracle, golden_ckpt, capsys)
 # ---- 10. errors -------------------------------------------------------------------------------------------------------------------
 def test_errors_name_the_argument(oracle, golden_ckpt, op_ctx):
     from nerf_and_dietnerf_amd import _lib
-    p = _problem(oracle, golden_ckpt)
-    ctx = _ctx(p)
+    p = S.golden_problem(oracle, golden_ckpt)
+    ctx = S.golden_context(p)
     for call in (lambda: ctx.train_set_distortion_weights(0.1, 0.1), ctx.train_read_distortion_sums):
         with pytest.raises(RuntimeError, match="nerf_train_begin"):
             call()

@@ -15,16 +15,13 @@ import pytest
 
 import encoding_window_ref as W
 import grad_blocks as GB
+from occupancy_ref import GOLDEN_BOX as BOX
+import support
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(16, 8, 8), (7, 33, 32)]
-BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))
 COT = ("d_rgb", "d_depth", "d_weights", "d_z")
-
-
-def _kw(lx, ld, na):
-    return dict(n_pos_enc_xyz=lx, n_pos_enc_dir=ld, n_angles=na)
 
 
 def _windows(lx, ld, seed=0):
@@ -42,17 +39,13 @@ def _setup(oracle, golden_ckpt, lx, ld, na):
     import nerf_and_dietnerf_amd as N
     if (lx, ld, na) == (5, 4, 2):
         return golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"], float(golden_ckpt["near"]), float(golden_ckpt["far"])
-    bc, bf = N.glorot_blob(3, **_kw(lx, ld, na)), N.glorot_blob(4, **_kw(lx, ld, na))
+    bc, bf = N.glorot_blob(3, **support.kw(lx, ld, na)), N.glorot_blob(4, **support.kw(lx, ld, na))
     bc[-1] = bf[-1] = 1.5                   # lift sigma: Glorot networks are almost transparent
     return bc, bf, 0.5, 2.5
 
 
 def _problem(oracle, n, sc, sf, near, far, na, seed=0):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(8, 8, 0.46, c2w).reshape(-1, 4)
-    d = np.ascontiguousarray(d[rng.choice(d.shape[0], n, replace=False)])
-    o = np.tile(c2w[:, 3], (n, 1)).astype(np.float32)
+    o, d, rng = support.oracle_rays(oracle, n, seed)         # n <= 64: drawn without replacement
     z = np.sort(rng.uniform(near, far, (n, sc)).astype(np.float32), axis=1)
     pts = rng.uniform(-1, 1, (3 * n + 1, 3)).astype(np.float32)
     views = None if na == 0 else rng.uniform(-1, 1, (3 * n + 1, na + 1)).astype(np.float32)
@@ -113,7 +106,7 @@ FORWARD_CASES = ([(5, 4, 2, prec) for prec in ("fp32", "f16x3", "bf16x3", "f16")
 def test_forward_equals_the_folded_blob_bit_for_bit(oracle, golden_ckpt, lx, ld, na, precision):
     """Test 4: render (rgb and every extra output; at f16x3 / bf16x3 with view directions its coarse pass is the sigma-only
     network), render_rays and model_predict of both networks and density_lattice(8)."""
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     for name, (wx, wd) in _windows(lx, ld, lx + ld + na).items():
         S = W.scale_table(lx, ld, na, wx, wd)
@@ -152,7 +145,7 @@ def test_off_is_off(oracle, golden_ckpt):
     """Test 5: never set, set to None, set to all ones, set and cleared -- the same bits everywhere; get_weights returns W
     after each, and under an active window too (with and without a trainer)."""
     lx, ld, na = 5, 4, 2
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     wx, wd = _windows(lx, ld)["distinct"]
     p = _problem(oracle, *SHAPES[0], near, far, na)
@@ -196,7 +189,7 @@ def test_off_is_off(oracle, golden_ckpt):
 @pytest.mark.parametrize("sampler_gradient", [True, False])
 def test_trainer_gradients_float32_policy(oracle, golden_ckpt, lx, ld, na, sampler_gradient):
     """Test 6, float32 policy: train_gradients and the slot forward / backward with all four cotangents and the ray gradients."""
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     blocks = GB.blocks(lx, ld, na)
     prec = "fp32" if lx <= 5 else "f16x3"
@@ -228,7 +221,7 @@ def test_trainer_gradients_mixed_float16_policy(oracle, golden_ckpt):
     """Test 6, mixed_float16: equal wherever S is 0 or 1, within 1 ulp (fp32) elsewhere -- the loss scale, a power of two, is
     taken off after the window's factor instead of before it --, the same loss scale and the same verdict."""
     lx, ld, na = 5, 4, 2
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     for name, (wx, wd) in _windows(lx, ld, 3).items():
         S = W.scale_table(lx, ld, na, wx, wd)
@@ -259,7 +252,7 @@ def test_trainer_gradients_reference_trainer(oracle, golden_ckpt, monkeypatch):
     """Test 6, the exact-fp32 layer-wise trainer (NERF_TRAIN_FORWARD=gemm): launch_relayout and its reductions."""
     monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
     lx, ld, na = 5, 4, 2
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     wx, wd = _windows(lx, ld, 5)["distinct"]
     S = W.scale_table(lx, ld, na, wx, wd)
@@ -284,7 +277,7 @@ def test_accumulate_does_not_rescale_what_is_there(oracle, golden_ckpt):
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     wx, wd = _windows(lx, ld, 9)["distinct"]
     p = _problem(oracle, *SHAPES[0], near, far, na, seed=5)
-    ctx = _ctx(_kw(lx, ld, na), near, far, bc, bf, (wx, wd), alpha=1.0)
+    ctx = _ctx(support.kw(lx, ld, na), near, far, bc, bf, (wx, wd), alpha=1.0)
     ctx.train_begin(5e-4)
     ctx.train_render_forward_outputs(0, p["o"], p["d"], *_draws(p), outputs=("rgb",))
     gc, gf = ctx.train_render_backward_outputs(0, **p["cot"])
@@ -308,7 +301,7 @@ def test_optimizer_leaves_closed_rows_alone(oracle, golden_ckpt, mixed):
     """Test 8: one train_step under a window with zeros leaves every master weight whose S is 0 at its initial bits and
     moves the rows with S > 0; train_step is train_gradients + train_apply under the same window, bit for bit."""
     lx, ld, na = 5, 4, 2
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     wx, wd = _windows(lx, ld)["zeros"]
     S = W.scale_table(lx, ld, na, wx, wd)
@@ -337,7 +330,7 @@ def test_order_change_and_persistence(oracle, golden_ckpt):
     """Test 9: (set, load) == (load, set); a changed window makes the next train_gradients a fresh trainer's under the new
     one; train_begin / train_end leave it in place; no change while a render slot holds a forward pass (the rule chosen)."""
     lx, ld, na = 5, 4, 2
-    kw = _kw(lx, ld, na)
+    kw = support.kw(lx, ld, na)
     bc, bf, near, far = _setup(oracle, golden_ckpt, lx, ld, na)
     wins = _windows(lx, ld, 11)
     w1, w2 = wins["distinct"], wins["zeros"]
@@ -379,7 +372,7 @@ def test_order_change_and_persistence(oracle, golden_ckpt):
     # w_dir on an xyz-only context: accepted, no effect
     c = None
     import nerf_and_dietnerf_amd as N
-    c = N.Context(near=near, far=far, precision="f16x3", **_kw(5, 4, 0))
+    c = N.Context(near=near, far=far, precision="f16x3", **support.kw(5, 4, 0))
     c.set_encoding_window(None, [0.5, 0.5, 0.5, 0.5])
     assert c.encoding_window() is None
     c.close()

@@ -10,14 +10,10 @@ import numpy as np
 import pytest
 
 import grad_blocks as GB
+import support as S
 
 pytestmark = pytest.mark.gpu
 
-
-def _f32(fn, *a, **kw):
-    """The same oracle call in float32: the yardstick of the block-wise bars (tests/grad_blocks.py)."""
-    import torch
-    return fn(*a, dtype=torch.float32, **kw)
 
 RGB_TOL = {"fp32": 1e-4, "f16x3": 1e-4, "f16": 3e-2}          # the bars of the (5, 4) render tests
 RAW_TOL = {"fp32": 5e-5, "f16x3": 5e-5, "f16": 5e-2}          # model_predict, relative to max(1, |ref|)
@@ -32,13 +28,9 @@ def _prec(lx, precision="fp32"):
     return precision if lx <= 5 or precision != "fp32" else "f16x3"
 
 
-def _kw(lx, ld, na):
-    return dict(n_pos_enc_xyz=lx, n_pos_enc_dir=ld, n_angles=na)
-
-
 def _blobs(lx, ld, na, seed=3):
     import nerf_and_dietnerf_amd as N
-    bc, bf = N.glorot_blob(seed, **_kw(lx, ld, na)), N.glorot_blob(seed + 1, **_kw(lx, ld, na))
+    bc, bf = N.glorot_blob(seed, **S.kw(lx, ld, na)), N.glorot_blob(seed + 1, **S.kw(lx, ld, na))
     bc[-1] = bf[-1] = 1.5                   # lift sigma: Glorot networks are almost transparent
     return bc, bf
 
@@ -48,8 +40,8 @@ def _spread(blob, lx, ld, na, L=5):
     library's layout, written from the reference's encodings: [x, sin_k, cos_k, ...] per xyz component, [sin_k, cos_k, ...]
     per direction component)."""
     from oracle import nerf_oracle as O
-    small = O.unpack_blob(blob, **_kw(lx, ld, na))
-    wide = O.unpack_blob(np.zeros(O.blob_size(**_kw(L, 4, na)), np.float32), **_kw(L, 4, na))
+    small = O.unpack_blob(blob, **S.kw(lx, ld, na))
+    wide = O.unpack_blob(np.zeros(O.blob_size(**S.kw(L, 4, na)), np.float32), **S.kw(L, 4, na))
     XC = 1 + 2 * L
 
     def xyz_rows():
@@ -98,7 +90,7 @@ def test_render_and_model_predict(oracle, lx, ld, na, precision):
     against the oracle with the network's own encodings."""
     import nerf_and_dietnerf_amd as N
     near, far = 0.6, 2.4
-    kw = _kw(lx, ld, na)
+    kw = S.kw(lx, ld, na)
     if lx > 5 and precision == "fp32":
         # no exact-fp32 kernel for the wide-PE networks: refused loudly, at creation and when switched to
         with pytest.raises(RuntimeError, match="not fp32"):
@@ -143,17 +135,17 @@ def test_fewer_octaves_equal_the_default_network_with_zero_rows(oracle, lx, ld, 
     L = 5 if lx <= 5 else 10
     bc, bf = _blobs(lx, ld, na, seed=11)
     wc, wf = _spread(bc, lx, ld, na, L), _spread(bf, lx, ld, na, L)
-    small = N.Context(near=near, far=far, precision=_prec(lx), **_kw(lx, ld, na))
-    wide = N.Context(near=near, far=far, precision=_prec(L), **_kw(L, 4, na))
+    small = N.Context(near=near, far=far, precision=_prec(lx), **S.kw(lx, ld, na))
+    wide = N.Context(near=near, far=far, precision=_prec(L), **S.kw(L, 4, na))
     small.load_weights(0, bc); small.load_weights(1, bf)
     wide.load_weights(0, wc); wide.load_weights(1, wf)
     # the spread is the right network (the oracle with (5, 4) encodings on it agrees with the (Lx, Ld) oracle)
     o, d, rng = _rays(oracle, 48, 5)
     uc, uf = rng.random((48, 32), dtype=np.float32), rng.random((48, 64), dtype=np.float32)
-    r_small = oracle.render(oracle.unpack_blob(bc, **_kw(lx, ld, na)), oracle.unpack_blob(bf, **_kw(lx, ld, na)), o, d,
-                            near, far, uc, uf, **_kw(lx, ld, na))
-    r_wide = oracle.render(oracle.unpack_blob(wc, **_kw(L, 4, na)), oracle.unpack_blob(wf, **_kw(L, 4, na)), o, d, near,
-                           far, uc, uf, **_kw(L, 4, na))
+    r_small = oracle.render(oracle.unpack_blob(bc, **S.kw(lx, ld, na)), oracle.unpack_blob(bf, **S.kw(lx, ld, na)), o, d,
+                            near, far, uc, uf, **S.kw(lx, ld, na))
+    r_wide = oracle.render(oracle.unpack_blob(wc, **S.kw(L, 4, na)), oracle.unpack_blob(wf, **S.kw(L, 4, na)), o, d, near,
+                           far, uc, uf, **S.kw(L, 4, na))
     assert np.abs(r_small[0] - r_wide[0]).max() <= 1e-6
     for precision in ("fp32", "f16x3", "f16") if L == 5 else ("f16x3", "f16"):
         small.set_precision(precision)
@@ -166,21 +158,9 @@ def test_fewer_octaves_equal_the_default_network_with_zero_rows(oracle, lx, ld, 
     wide.close()
 
 
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a = a.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 def _train_problem(oracle, n=48, sc=16, sf=24, seed=0):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(8, 8, 0.46, c2w).reshape(-1, 4)
-    d = np.ascontiguousarray(d[rng.choice(d.shape[0], n, replace=False)])
-    o = np.tile(c2w[:, 3], (n, 1)).astype(np.float32)
+    """The rays and draws of S.golden_problem (n <= 64) for this file's Glorot networks, on the bounds 0.5 .. 2.5."""
+    o, d, rng = S.oracle_rays(oracle, n, seed)
     return dict(o=o, d=d, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
                 tgt=rng.random((n, 3), dtype=np.float32), sc=sc, sf=sf, near=0.5, far=2.5)
 
@@ -194,7 +174,7 @@ def test_training_gradients_float32_policy(oracle, lx, ld, na, capsys):
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     p = _train_problem(oracle, seed=lx + 10 * ld)
-    kw = _kw(lx, ld, na)
+    kw = S.kw(lx, ld, na)
     bc, bf = _blobs(lx, ld, na, seed=21)
     for alpha in (1.0, 0.05):
         ctx = N.Context(near=p["near"], far=p["far"], leaky_relu_alpha=alpha, precision=_prec(lx), **kw)
@@ -203,7 +183,7 @@ def test_training_gradients_float32_policy(oracle, lx, ld, na, capsys):
         m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
         r = T.train_gradients(bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                               sampler_grad=True, alpha=alpha, **kw)
-        ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+        ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
         with capsys.disabled():
             print(f"\n[({lx},{ld},{na}) float32 policy, alpha {alpha}] vs float64 autograd: coarse {ec:.2e}, "
                   f"fine {ef:.2e} of max|g|", end="")
@@ -214,8 +194,8 @@ def test_training_gradients_float32_policy(oracle, lx, ld, na, capsys):
         assert abs(m["loss"] - r["loss"]) <= (1e-5 if wide else 2e-6) * r["loss"]
         assert np.isfinite(gc).all() and np.isfinite(gf).all()
         tol, cos_min = ((5e-3 if wide else 2e-4), (0.9999 if wide else 0.9999999)) if alpha == 1.0 else (5e-2, 0.999)
-        assert ec <= tol and _cos(gc, r["grad_coarse"]) > cos_min
-        assert ef <= tol and _cos(gf, r["grad_fine"]) > cos_min
+        assert ec <= tol and S.cos(gc, r["grad_coarse"]) > cos_min
+        assert ef <= tol and S.cos(gf, r["grad_fine"]) > cos_min
         # block by block.  alpha 1: 2e-4 of each block's own max where float32 autograd resolves the block.  At Lx >= 6 the top
         # octave's fp32 angle rounding (below) keeps most blocks at the blob-relative bar by that rule; one block it does not
         # catch is named: (10,4,0) fine b11, 2.4e-4 of its own max.  b11 is the plain sum over all rows of d(loss)/d(sigma):
@@ -226,7 +206,7 @@ def test_training_gradients_float32_policy(oracle, lx, ld, na, capsys):
         # device forward has one at (5,2,2) (layer 4: k0 4.3e-4 .. b4 2.6e-4, all twelve blocks of layers 0..4 and no other)
         # (see "One LeakyReLU mask flip" in tests/test_gpu_train.py): the blocks of layers 0..4 keep the blob-wide bar there,
         # every block above is asserted.  (3,4,0): k0 8.0e-5, b0 7.7e-5, under the bar's floor of 2e-4.
-        r32 = _f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+        r32 = S.f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                    sampler_grad=True, alpha=alpha, **kw)
         blks = GB.blocks(lx, ld, na)
         with capsys.disabled():
@@ -262,7 +242,7 @@ def test_layerwise_exact_fp32_trainer(oracle, lx, ld, na, monkeypatch, capsys):
     import nerf_and_dietnerf_amd as N
     monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
     p = _train_problem(oracle, seed=7)
-    kw = _kw(lx, ld, na)
+    kw = S.kw(lx, ld, na)
     bc, bf = _blobs(lx, ld, na, seed=27)
     ctx = N.Context(near=p["near"], far=p["far"], leaky_relu_alpha=1.0, precision=_prec(lx), **kw)
     ctx.load_weights(0, bc); ctx.load_weights(1, bf)
@@ -272,8 +252,8 @@ def test_layerwise_exact_fp32_trainer(oracle, lx, ld, na, monkeypatch, capsys):
                           alpha=1.0, **kw)
     tol = 5e-3 if lx > 5 else 2e-4          # Lx >= 6: the fp32 angle rounding of the top octave (see the float32-policy test)
     assert abs(m["loss"] - r["loss"]) <= (1e-5 if lx > 5 else 2e-6) * r["loss"]
-    assert _relerr(gc, r["grad_coarse"]) <= tol and _relerr(gf, r["grad_fine"]) <= tol
-    r32 = _f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"], sampler_grad=True,
+    assert S.relerr(gc, r["grad_coarse"]) <= tol and S.relerr(gf, r["grad_fine"]) <= tol
+    r32 = S.f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"], sampler_grad=True,
                alpha=1.0, **kw)
     with capsys.disabled():
         GB.check_fp32_smooth(gc, r["grad_coarse"], r32["grad_coarse"], GB.blocks(lx, ld, na), tol, f"[({lx},{ld},{na}) layer-wise] coarse")
@@ -289,7 +269,7 @@ def test_training_gradients_mixed_float16_policy(oracle, lx, ld, na, capsys):
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     p = _train_problem(oracle, seed=3 + lx + 10 * ld)
-    kw = _kw(lx, ld, na)
+    kw = S.kw(lx, ld, na)
     bc, bf = _blobs(lx, ld, na, seed=25)
     ctx = N.Context(near=p["near"], far=p["far"], leaky_relu_alpha=1.0, precision=_prec(lx), **kw)
     ctx.load_weights(0, bc); ctx.load_weights(1, bf)
@@ -301,14 +281,14 @@ def test_training_gradients_mixed_float16_policy(oracle, lx, ld, na, capsys):
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     r16 = T.train_gradients(bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                             sampler_grad=not wide, alpha=1.0, fp16_loss_scale=32768.0, **kw)
-    qc, qf = _relerr(gc, r16["grad_coarse"]), _relerr(gf, r16["grad_fine"])
+    qc, qf = S.relerr(gc, r16["grad_coarse"]), S.relerr(gf, r16["grad_fine"])
     with capsys.disabled():
         print(f"\n[({lx},{ld},{na}) mixed_float16] vs the fp16-emulating oracle: coarse {qc:.2e}, fine {qf:.2e} of max|g|",
               end="")
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
     assert abs(m["loss"] - r16["loss"]) <= (1e-3 if wide else 2e-5) * r16["loss"]
     assert qc <= 3e-2 and qf <= (2e-2 if wide else 5e-3)
-    e32 = _f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+    e32 = S.f32(T.train_gradients, bc, bf, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                sampler_grad=not wide, alpha=1.0, fp16_loss_scale=32768.0, **kw)
     with capsys.disabled():
         GB.check_mixed(gc, r16["grad_coarse"], e32["grad_coarse"], GB.blocks(lx, ld, na), f"[({lx},{ld},{na}) mixed_float16] coarse")
@@ -326,7 +306,7 @@ def test_backward_through_render(oracle, policy, capsys):
     import nerf_and_dietnerf_amd as N
     mixed = policy == "mixed_float16"
     for lx, ld in ((5, 2), (2, 1), (10, 4), (7, 2)):
-        kw = _kw(lx, ld, 2)
+        kw = S.kw(lx, ld, 2)
         p = _train_problem(oracle, n=40, sc=55, sf=55, seed=9)
         rng = np.random.default_rng(3)
         d_rgb = (rng.standard_normal((40, 3)) * 0.1).astype(np.float32)
@@ -338,7 +318,7 @@ def test_backward_through_render(oracle, policy, capsys):
         rgb, gc, gf = ctx.train_render_gradients(p["o"], p["d"], d_rgb, p["sc"], p["sf"], p["u_c"], p["u_f"])
         r = T.render_gradients(bc, bf, p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"], alpha=1.0, sampler_grad=sg,
                                fp16_loss_scale=32768.0 if mixed else None, **kw)
-        ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+        ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
         with capsys.disabled():
             print(f"\n[({lx},{ld},2) backward through render(), {policy}] coarse {ec:.2e}, fine {ef:.2e} of max|g|", end="")
         assert np.isfinite(gc).all() and np.isfinite(gf).all()
@@ -375,7 +355,7 @@ def test_fit_and_checkpoint(tmp_path, policy, capsys):
         net_cfg = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05,
                    "n_pos_enc_dim_xyz": lx, "n_pos_enc_view_dir": ld, "n_angles_for_model": 2,
                    "n_rays_in_batch_train": 4096, "n_rays_in_batch_render": 4096}
-        kw = _kw(lx, ld, 2)
+        kw = S.kw(lx, ld, 2)
         model = N.NeRF(net_cfg, ren, near, far)
         model.set_weights(N.glorot_blob(0, **kw), N.glorot_blob(1, **kw))
         model.compile(4.0e-4, mixed_float16=mixed)
@@ -419,7 +399,7 @@ def test_get_nerf_with_fewer_direction_octaves(tmp_path):
     cfg[C.NEURAL_NET]["n_pos_enc_view_dir"] = 2
     images, poses, fov, near, far, _, _ = C.get_data(cfg, os.path.join(here, "golden"))
     model = C.get_nerf(cfg, near, far, save_location=None)
-    kw = _kw(cfg[C.NEURAL_NET]["n_pos_enc_dim_xyz"], 2, cfg[C.NEURAL_NET]["n_angles_for_model"])
+    kw = S.kw(cfg[C.NEURAL_NET]["n_pos_enc_dim_xyz"], 2, cfg[C.NEURAL_NET]["n_angles_for_model"])
     assert model.ctx.blob_size() == N.blob_size(**kw)
     _, tr_img, tr_pose = C.get_train_data(cfg, images, poses)
     ds = N.prepare_ds(cfg[C.NEURAL_NET][C.N_RAYS_IN_BATCH_TRAIN], tr_pose[:4], tr_img[:4], fov, model.ctx)

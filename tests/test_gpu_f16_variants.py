@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import f16_variants as V
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -58,19 +59,11 @@ def _check(predict, layers, lx, ld, na, epilogue, rows, label):
     return line
 
 
-def _context(lx, ld, na, precision, blob_pair):
-    import nerf_and_dietnerf_amd as N
-    ctx = N.Context(near=0.6, far=2.4, precision=precision, **V.kw(lx, ld, na))
-    for which, blob in enumerate(blob_pair):
-        ctx.load_weights(which, blob)
-    return ctx
-
-
 @pytest.mark.parametrize("lx,ld,na", V.TWO_TILE + V.ONE_TILE_XYZ + V.WIDE)
 def test_model_predict_matches_its_kernels_emulation(oracle, lx, ld, na, capsys):
     rows = _rows()
     blob_pair = V.blobs(lx, ld, na)
-    ctx = _context(lx, ld, na, "f16", blob_pair)
+    ctx = S.blob_context(blob_pair, lx, ld, na, "f16")
     xyz, dirs = V.inputs(max(rows), na)
     ep = V.epilogue_of(lx, na)
     try:
@@ -88,7 +81,7 @@ def test_model_predict_matches_its_kernels_emulation(oracle, lx, ld, na, capsys)
 def test_shipped_checkpoint_matches_two_tile_emulation(oracle, golden_ckpt, capsys):
     rows = _rows()
     blob_pair = (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
-    ctx = _context(5, 4, 2, "f16", blob_pair)
+    ctx = S.blob_context(blob_pair, 5, 4, 2, "f16")
     xyz, dirs = V.inputs(max(rows), 2)
     try:
         for which, blob in enumerate(blob_pair):
@@ -127,7 +120,7 @@ def test_render_matches_emulating_oracle(oracle, lx, ld, na, monkeypatch, capsys
     forward is that kernel's emulation, at ragged (rays, coarse, fine) shapes; config 5's RGB bar."""
     near, far = 0.6, 2.4
     blob_pair = V.blobs(lx, ld, na)
-    ctx = _context(lx, ld, na, "f16", blob_pair)
+    ctx = S.blob_context(blob_pair, lx, ld, na, "f16")
     coarse, fine = (oracle.unpack_blob(b, **V.kw(lx, ld, na)) for b in blob_pair)
     ep = V.epilogue_of(lx, na)
     emu = lambda layers, xe, de, alpha=0.05: oracle.mlp_forward_fp16(layers, xe, de, alpha, packed_epilogue=ep)  # noqa: E731
@@ -160,7 +153,7 @@ def test_wide_build_f16x3_row_sweep(oracle, lx, ld, na, capsys):
     tests/test_gpu_encodings.py (which checks model_predict at 400 rows only)."""
     rows = _rows()
     blob_pair = V.blobs(lx, ld, na)
-    ctx = _context(lx, ld, na, "f16x3", blob_pair)
+    ctx = S.blob_context(blob_pair, lx, ld, na, "f16x3")
     xyz, dirs = V.inputs(max(rows), na)
     worst = 0.0
     try:

@@ -17,25 +17,16 @@ that one is more than a bar away from the correct emulation; it is not at ordina
 Measured when the tests were written (one MI355X; kernel vs emulation, as a fraction of the bar): 0.15 .. 0.88 over the 26
 networks -- two to four units in the last place of the fp32 outputs; the largest are (5,4,0) biased coarse 1.02e-6 of
 1.16e-6 and (5,4,1) biased fine 6.9e-7 of 8.4e-7.  DESIGN.md section 4.1b lists every case."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import bf16_variants as B
 import f16x3_variants as X
+import support as S
 
 pytestmark = pytest.mark.gpu
 
 NEAR, FAR = 0.6, 2.4
-
-
-def _context(blob_pair, lx=5, ld=4, na=2, precision="f16x3", near=NEAR, far=FAR):
-    import nerf_and_dietnerf_amd as N
-    ctx = N.Context(near=near, far=far, precision=precision, **X.kw(lx, ld, na))
-    for which, blob in enumerate(blob_pair):
-        ctx.load_weights(which, blob)
-    return ctx
 
 
 def _say(capsys):
@@ -54,7 +45,7 @@ def test_kernel_follows_its_emulation(golden_ckpt, capsys, family, lx, ld, na):
     """check_kernel (tests/f16x3_variants.py) on both networks: within the bar of the emulation, finite, and -- Glorot
     families -- identified against every whole-layer defect, the flushed-subnormal and the RNE-hi emulation;
     read_nonfinite() == 0."""
-    ctx = _context(X.networks(family, lx, ld, na, golden_ckpt), lx, ld, na)
+    ctx = S.blob_context(X.networks(family, lx, ld, na, golden_ckpt), lx, ld, na)
     try:
         xyz, dirs = X.inputs(X.RAW_ROWS, na)
         figures = X.raw_figures(family, lx, ld, na)
@@ -68,19 +59,6 @@ def test_kernel_follows_its_emulation(golden_ckpt, capsys, family, lx, ld, na):
 
 
 # ---- 2. the sigma-only kernel ----
-def _render_rays_weights(ctx, o, d, z):
-    """nerf_render_rays on the coarse network with outputs {weights} alone: mlp_f16x3_sig_kernel."""
-    from nerf_and_dietnerf_amd import _lib
-    n, s = z.shape
-    w = np.full((n, s), np.nan, np.float32)
-    outs = _lib.NerfOutputs()
-    outs.weights = w.ctypes.data
-    o, d, z = np.ascontiguousarray(o), np.ascontiguousarray(d), np.ascontiguousarray(z)
-    _lib.check(ctx.lib.nerf_render_rays(ctx.h, 0, o.ctypes.data, d.ctypes.data, z.ctypes.data, n, s, C.byref(outs),
-                                        _lib.NERF_MEM_HOST))
-    return w
-
-
 def test_sigma_only_kernel_follows_the_emulated_sigma(oracle, capsys):
     """1391 rays x 3 samples = 4173 rows (ragged last tile, the ray changes inside a wave) through the sigma-only kernel of
     the biased Glorot network; reference: the emulated raw outputs composited by oracle.ray_marching.
@@ -96,14 +74,7 @@ def test_sigma_only_kernel_follows_the_emulated_sigma(oracle, capsys):
     blobs = X.networks("biased", lx, ld, na)
     layers = oracle.unpack_blob(blobs[0], **X.kw(lx, ld, na))
     n, s = 1391, 3
-    rng = np.random.default_rng(3)
-    o = np.zeros((n, 4), np.float32)
-    o[:, :3] = rng.uniform(-0.3, 0.3, (n, 3))
-    o[:, 2] += 1.5
-    d = np.zeros((n, 4), np.float32)
-    d[:, :3] = rng.uniform(-0.4, 0.4, (n, 3))
-    d[:, 2] = -1.0
-    z = np.sort(rng.uniform(NEAR, FAR, (n, s)), axis=1).astype(np.float32)
+    o, d, z = S.rays_towards_origin(n, s, NEAR, FAR)
     pts = oracle.sample_along_rays(o, d, z)[..., :3].reshape(-1, 3)
     view = oracle.get_view_directions(s, d, na)
     ref_raw = oracle.model_predict(layers, pts, view, lx, ld)
@@ -112,9 +83,9 @@ def test_sigma_only_kernel_follows_the_emulated_sigma(oracle, capsys):
     w_emu = oracle.ray_marching(emu_raw.reshape(n, s, 4), z)[1]
     fig = X.rel_err(emu_raw, ref_raw)
     bound = (FAR - NEAR) * X.RAW_BAR_FACTOR * fig * max(1.0, float(np.abs(ref_raw).max()))
-    ctx = _context(blobs, lx, ld, na)
+    ctx = S.blob_context(blobs, lx, ld, na)
     try:
-        w = _render_rays_weights(ctx, o, d, z)
+        w, = S.render_rays(ctx, 0, o, d, z, ("weights",))                 # {weights} alone: mlp_f16x3_sig_kernel
         err = float(np.abs(w[:, :-1] - w_emu[:, :-1]).max())
         _say(capsys)(f"[f16x3 sigma-only, {n} rays x {s}] emulation vs oracle (raw) {fig:.3e} -> weights bound {bound:.3e}; "
                      f"kernel vs emulated weights (all but the last sample) {err:.3e}; largest weight {w[:, :-1].max():.3f}")
@@ -135,7 +106,7 @@ def test_low_magnitude_kernels_follow_their_emulations(oracle, golden_ckpt, caps
     subnormals, or this fails).  The bf16x3 kernel on the same blobs meets its own bar."""
     xyz, dirs = X.inputs(X.RAW_ROWS, 2)
     figures = X.raw_figures("checkpoint", 5, 4, 2, k)
-    ctx = _context([X.shrink_blob(golden_ckpt[n], k) for n in ("blob_coarse", "blob_fine")])
+    ctx = S.blob_context([X.shrink_blob(golden_ckpt[n], k) for n in ("blob_coarse", "blob_fine")])
     try:
         for which, fg in enumerate(figures):
             flushed = X.variant(fg, 5, 4, 2, flush=True)
@@ -169,7 +140,7 @@ def test_render_at_the_rgb_floor(golden_ckpt, capsys):
     emu, ref = X.rgb_at(k)
     o, d = X.checkpoint_rays(golden_ckpt)
     uc, uf = X.render_draws()
-    ctx = _context([X.shrink_blob(golden_ckpt[n], k) for n in ("blob_coarse", "blob_fine")],
+    ctx = S.blob_context([X.shrink_blob(golden_ckpt[n], k) for n in ("blob_coarse", "blob_fine")],
                    near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]))
     try:
         got = ctx.render(o, d, 64, 128, uc, uf)[0]

@@ -19,12 +19,11 @@ ring wraps).  model_predict (mode 1) and render_rays with S = 1 run exactly thes
 a wave's 32 rows) run the fewest rays that give at least as many rows.  render_rays with outputs {weights} is the
 sigma-only kernel, with more outputs the full network.  Networks: plain Glorot blobs, Glorot kernels with random biases
 and a lifted sigma bias (tests/f16_variants.py), and the shipped epoch-95 checkpoint."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import f16_variants as V
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +33,8 @@ NETS = ("glorot", "glorot_biased", "checkpoint")
 SAMPLES = (1, 3, 64)
 
 
-def _n_cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
 def _row_counts():
-    cus = _n_cus()
+    cus = S.n_cus()
     return [1, 127, 129, 257, 2 * cus * 128 + 77, 3 * cus * 128 + 1]
 
 
@@ -52,51 +46,10 @@ def contexts(golden_ckpt):
     import nerf_and_dietnerf_amd as N
     blobs = {"glorot": (N.glorot_blob(0), N.glorot_blob(1)), "glorot_biased": V.blobs(5, 4, 2),
              "checkpoint": (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])}
-    ctxs = {}
-    for name, pair in blobs.items():
-        ctx = N.Context(near=NEAR, far=FAR, precision="f16x3", **V.kw(5, 4, 2))
-        for which, blob in enumerate(pair):
-            ctx.load_weights(which, blob)
-        ctxs[name] = ctx
+    ctxs = {name: S.blob_context(pair, near=NEAR, far=FAR) for name, pair in blobs.items()}
     yield ctxs
     for ctx in ctxs.values():
         ctx.close()
-
-
-def _rays(n, s, seed=3):
-    """n rays towards the origin from radius ~1.5, and n x s sorted depths in [NEAR, FAR]."""
-    rng = np.random.default_rng(seed)
-    o = np.zeros((n, 4), np.float32)
-    o[:, :3] = rng.uniform(-0.3, 0.3, (n, 3))
-    o[:, 2] += 1.5
-    d = np.zeros((n, 4), np.float32)
-    d[:, :3] = rng.uniform(-0.4, 0.4, (n, 3))
-    d[:, 2] = -1.0
-    z = np.sort(rng.uniform(NEAR, FAR, (n, s)), axis=1).astype(np.float32)
-    return o, d, z
-
-
-def _render_rays(ctx, o, d, z, full):
-    """nerf_render_rays on the coarse network: outputs {weights} (the sigma-only kernel) or, with full, {weights,
-    rgb_samples} (the full network).  Returns (weights, rgb_samples or None)."""
-    from nerf_and_dietnerf_amd import _lib
-    n, s = z.shape
-    w = np.full((n, s), np.nan, np.float32)
-    rs = np.full((n, s, 3), np.nan, np.float32) if full else None
-    outs = _lib.NerfOutputs()
-    outs.weights = w.ctypes.data
-    if full:
-        outs.rgb_samples = rs.ctypes.data
-    o, d, z = np.ascontiguousarray(o), np.ascontiguousarray(d), np.ascontiguousarray(z)
-    _lib.check(ctx.lib.nerf_render_rays(ctx.h, 0, o.ctypes.data, d.ctypes.data, z.ctypes.data, n, s, C.byref(outs),
-                                        _lib.NERF_MEM_HOST))
-    return w, rs
-
-
-def _same_bits(a, b, label):
-    assert a.shape == b.shape and np.isfinite(a).all(), label
-    diff = int(np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)))
-    assert diff == 0, (label, diff, float(np.abs(a - b).max()))
 
 
 def _rel(a, ref):
@@ -108,12 +61,12 @@ def _rel(a, ref):
 def test_model_predict_split_invariant_and_fp32_class(contexts, net, rows_i):
     ctx = contexts[net]
     m = _row_counts()[rows_i]
-    step = _n_cus() * 128
+    step = S.n_cus() * 128
     xyz, dirs = V.inputs(m, 2)
     for which in (0, 1):
         one = ctx.model_predict(which, xyz, dirs)
         parts = np.concatenate([ctx.model_predict(which, xyz[i:i + step], dirs[i:i + step]) for i in range(0, m, step)])
-        _same_bits(one, parts, f"{net} net {which} M={m}: one launch vs launches of <= {step} rows")
+        S.assert_same_bits(one, parts, f"{net} net {which} M={m}: one launch vs launches of <= {step} rows", finite=True)
         ctx.set_precision("fp32")
         try:
             ref = ctx.model_predict(which, xyz, dirs)
@@ -132,18 +85,20 @@ def test_render_rays_split_invariant_and_fp32_class(contexts, net, s, rows_i):
     ctx = contexts[net]
     rows = _row_counts()[rows_i]
     n = (rows + s - 1) // s                      # the fewest rays with at least `rows` rows
-    per = max(1, (_n_cus() * 128) // s)          # rays of a launch in which no workgroup sees a second tile
-    o, d, z = _rays(n, s)
+    per = max(1, (S.n_cus() * 128) // s)          # rays of a launch in which no workgroup sees a second tile
+    o, d, z = S.rays_towards_origin(n, s, NEAR, FAR)
     for full in (True, False):
         label = f"{net} {'full' if full else 'sigma-only'} N={n} S={s}"
-        w, rs = _render_rays(ctx, o, d, z, full)
-        cut = [_render_rays(ctx, o[i:i + per], d[i:i + per], z[i:i + per], full) for i in range(0, n, per)]
-        _same_bits(w, np.concatenate([c[0] for c in cut]), label + ": weights, one launch vs split")
+        outputs = ("weights", "rgb_samples") if full else ("weights",)       # {weights} alone: the sigma-only kernel
+        w, *rs = S.render_rays(ctx, 0, o, d, z, outputs)
+        cut = [S.render_rays(ctx, 0, o[i:i + per], d[i:i + per], z[i:i + per], outputs) for i in range(0, n, per)]
+        S.assert_same_bits(w, np.concatenate([c[0] for c in cut]), label + ": weights, one launch vs split", finite=True)
         if full:
-            _same_bits(rs, np.concatenate([c[1] for c in cut]), label + ": rgb_samples, one launch vs split")
+            S.assert_same_bits(rs[0], np.concatenate([c[1] for c in cut]), label + ": rgb_samples, one launch vs split",
+                               finite=True)
         ctx.set_precision("fp32")
         try:
-            w_ref, rs_ref = _render_rays(ctx, o, d, z, True)
+            w_ref, rs_ref = S.render_rays(ctx, 0, o, d, z, ("weights", "rgb_samples"))
         finally:
             ctx.set_precision("f16x3")
         if s > 1:
@@ -151,7 +106,7 @@ def test_render_rays_split_invariant_and_fp32_class(contexts, net, s, rows_i):
             print(f"{label}: weights (all but the last sample) vs fp32 mode max-abs {err_w:.3e}")
             assert err_w <= (FAR - NEAR) * BAR, (label, err_w)
         if full:
-            err_c = float(np.abs(rs - rs_ref).max())
+            err_c = float(np.abs(rs[0] - rs_ref).max())
             print(f"{label}: rgb_samples vs fp32 mode max-abs {err_c:.3e}")
             assert err_c <= BAR, (label, err_c)
     assert ctx.read_nonfinite() == 0

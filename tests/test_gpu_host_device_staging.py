@@ -8,6 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import support as S
+
 pytestmark = pytest.mark.gpu
 
 BOX = ((-1.5, -1.5, -2.2), (1.5, 1.5, 0.5))
@@ -69,10 +71,6 @@ def _device(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _bits(a):
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
 def same(case):
     """case(put) makes one call with its array arguments passed through ``put`` and returns an array, or a tuple of arrays,
     Nones and plain values: the host call's against the device call's.  -> the host call's results."""
@@ -86,7 +84,9 @@ def same(case):
         assert isinstance(a, np.ndarray) and b.is_cuda, i
         b = b.cpu().numpy()
         assert a.dtype == b.dtype and a.shape == b.shape, (i, a.dtype, b.dtype, a.shape, b.shape)
-        np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=f"output {i}")
+        if a.dtype == np.float32:                                  # bit for bit: a NaN equals itself, -0.0 is not +0.0
+            a, b = a.view(np.uint32), b.view(np.uint32)
+        np.testing.assert_array_equal(a, b, err_msg=f"output {i}")
     return host
 
 
@@ -112,7 +112,7 @@ def test_rays_to_ndc_in_place(ctx, p):
         return arr.keep[0], arr.keep[1]
     in_place = same(case)
     for a, b in zip(in_place, ctx.rays_to_ndc(p["o"], p["d"], p["fov"], 1.0)):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        S.assert_same_bits(a, b, dtype=np.float32)
 
 
 def test_get_z_values(ctx, p):
@@ -152,7 +152,7 @@ def test_ray_box_bounds_without_narrowed(ctx, p):
         _lib.check(ctx.lib.nerf_ray_box_bounds(ctx.h, arr.inp(o), arr.inp(d), p["n"], pb, None, arr.mem))
         return bounds
     (bounds,) = same(case)
-    np.testing.assert_array_equal(_bits(bounds), _bits(ctx.ray_box_bounds(p["o"], p["d"])[0]))
+    S.assert_same_bits(bounds, ctx.ray_box_bounds(p["o"], p["d"])[0], dtype=np.float32)
 
 
 def test_ray_occupancy_bounds(ctx, p):
@@ -250,7 +250,7 @@ def test_render_with_some_outputs_absent(ctx, p):
     rgb, depth = same(lambda put: case(put, ("rgb", "depth")))
     (weights,) = same(lambda put: case(put, ("weights",)))
     for a, b in ((rgb, full[0]), (weights, full[1]), (depth, full[6])):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        S.assert_same_bits(a, b, dtype=np.float32)
 
 
 # ---- mesh extraction -------------------------------------------------------------------------------------------------------------

@@ -5,12 +5,10 @@ import numpy as np
 import pytest
 
 import isosurface_ref as R
-from test_gpu_occupancy import GOLDEN_BOX
+from occupancy_ref import GOLDEN_BOX
+import support as S
 
 pytestmark = pytest.mark.gpu
-
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 
 
 @pytest.fixture(scope="module")
@@ -139,19 +137,9 @@ def test_full_size_lattice(ctx):
 
 
 # ---- 3. the density lattice -----------------------------------------------------------------------------------------------------
-def _glorot_ctx(precision, n_angles=2):
-    import nerf_and_dietnerf_amd as N
-    c = N.Context(precision=precision, n_angles=n_angles)
-    blob = N.glorot_blob(1, n_angles=n_angles)
-    blob[-1] = 0.5
-    c.load_weights(0, blob)
-    c.load_weights(1, N.glorot_blob(2, n_angles=n_angles))
-    return c
-
-
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_lattice_equals_the_point_query(precision):
-    c = _glorot_ctx(precision)
+    c = S.glorot_context(precision)
     c.set_scene_box(R.LO, R.HI)
     for n, which, view in ((5, 0, None), (17, 1, (0.6, -0.48, 0.64)), (102, 0, None)) if precision == "f16x3" else \
             ((5, 1, (0.0, 1.0, 0.0)), (17, 0, None)):
@@ -170,7 +158,7 @@ def test_lattice_equals_the_point_query(precision):
 
 
 def test_lattice_without_directions_ignores_view_dir():
-    c = _glorot_ctx("fp32", n_angles=0)
+    c = S.glorot_context("fp32", n_angles=0)
     c.set_scene_box(R.LO, R.HI)
     a = c.density_lattice(0, 5)
     b = c.density_lattice(0, 5, view_dir=(1.0, 0.0, 0.0))
@@ -203,7 +191,7 @@ def test_lattice_refusals():
 # ---- 4. vertex colours ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_colors_equal_the_point_query(precision):
-    c = _glorot_ctx(precision)
+    c = S.glorot_context(precision)
     v, nrm, _ = R.isosurface(R.ball(17), R.LO, R.HI, 0.0)
     v, nrm = v.copy(), nrm.copy()
     assert len(v) > 1024 and len(v) % 64 != 0
@@ -229,7 +217,7 @@ def test_colors_equal_the_point_query(precision):
 def test_extract_mesh_on_the_shipped_checkpoint(golden_ckpt, tmp_path):
     import nerf_and_dietnerf_amd as N
     rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(GOLDEN_BOX[0]), list(GOLDEN_BOX[1])]}
-    m = N.NeRF(NET, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="f16x3")
+    m = N.NeRF(S.NET, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="f16x3")
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     n = 65
     sigma = m.ctx.density_lattice(1, n)
@@ -264,7 +252,7 @@ def test_extract_mesh_on_the_shipped_checkpoint(golden_ckpt, tmp_path):
     plain = m.extract_mesh(resolution=17, sigma_threshold=thr, which=0, colors=False)
     assert "colors" not in plain and plain["triangles"].shape[1] == 3 and plain["normals"].shape == plain["vertices"].shape
     m.ctx.close()
-    box_less = N.NeRF(NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 16}, 2.0, 6.0, precision="fp32")
+    box_less = N.NeRF(S.NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 16}, 2.0, 6.0, precision="fp32")
     with pytest.raises(ValueError, match="scene_box"):
         box_less.extract_mesh()
     box_less.ctx.close()

@@ -9,81 +9,39 @@ Context.comm_init_from_torch -- is the shipped library code, which until round 3
 (The reference has no distributed layer, SURVEY.md section 8e: the single-process results are the oracle here.)
 """
 import os
-import socket
-import subprocess
-import time
 
 import numpy as np
 import pytest
 
+import support as S
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FOV = 0.4613422
 
 
 @pytest.fixture(scope="module")
 def stub_lib(tmp_path_factory):
-    out = tmp_path_factory.mktemp("stub_rccl") / "libstub_rccl.so"
-    subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "stub_rccl.c"),
-                    "-o", str(out), "-L/opt/rocm/lib", "-lamdhip64", "-lrt"], check=True)
-    return str(out)
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _exchange_id(N, rank, id_path):
-    """rank 0 draws the communicator id, the others read it from a file (any channel will do: it is 128 bytes)."""
-    if rank == 0:
-        uid = N.Context.comm_unique_id()
-        with open(id_path + ".tmp", "wb") as f:
-            f.write(uid)
-        os.replace(id_path + ".tmp", id_path)
-        return uid
-    t0 = time.time()
-    while not os.path.exists(id_path):
-        time.sleep(0.02)
-        if time.time() - t0 > 120:
-            raise TimeoutError("rank 0 never published the communicator id")
-    with open(id_path, "rb") as f:
-        return f.read()
-
-
-def _assert_stand_in_loaded():
-    """The collective really went through tests/stub_rccl.c (NERF_RCCL_LIB), not through a librccl of the process."""
-    with open("/proc/self/maps") as f:
-        assert "libstub_rccl.so" in f.read()
-
-
-def _make_ctx(N, p, **kw):
-    kw.setdefault("precision", "fp32")
-    ctx = N.Context(near=p["near"], far=p["far"], **kw)
-    ctx.load_weights(0, p["bc"])
-    ctx.load_weights(1, p["bf"])
-    return ctx
+    return S.build_stub_rccl(tmp_path_factory.mktemp("stub_rccl"))
 
 
 def _rank_main(rank, world, case, p, id_path, port, q):
     try:
         import nerf_and_dietnerf_amd as N
         if case == "render":
-            ctx = _make_ctx(N, p, precision=p.get("precision", "fp32"))
-            ctx.comm_init(_exchange_id(N, rank, id_path), rank, world)
+            ctx = S.golden_context(p, precision=p.get("precision", "fp32"))
+            ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
             imgs = []
             for (h, w, sc, sf, dev) in p["shapes"]:
                 img = ctx.render_image_sharded(p["c2w"], FOV, h, w, 0, sc, sf, seed=5, device_out=dev)
                 imgs.append(img.cpu().numpy() if dev else img)
-            _assert_stand_in_loaded()
+            S.assert_stand_in_loaded()
             ctx.comm_destroy()
             q.put((rank, imgs))
         elif case == "render_outputs":
             # ABI 4: nerf_render_image_sharded_outputs -- one all-gather per requested output
-            ctx = _make_ctx(N, p)
-            ctx.comm_init(_exchange_id(N, rank, id_path), rank, world)
+            ctx = S.golden_context(p)
+            ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
             res = []
             to_np = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else t       # noqa: E731
             for (h, w, sc, sf, dev) in p["shapes"]:
@@ -92,27 +50,25 @@ def _rank_main(rank, world, case, p, id_path, port, q):
                 two = ctx.render_image_sharded(p["c2w"], FOV, h, w, 0, sc, sf, seed=5, device_out=dev,
                                                outputs="rgb_depth")
                 res.append(([to_np(t) for t in six], [to_np(t) for t in two]))
-            _assert_stand_in_loaded()
+            S.assert_stand_in_loaded()
             ctx.comm_destroy()
             q.put((rank, res))
         elif case == "video_within_frame":
             # video.render_video with an in-library communicator: every frame is sharded by rays from C
-            net_cfg = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05,
-                       "n_pos_enc_dim_xyz": 5, "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
-            model = N.NeRF(net_cfg, {"n_render_samples_coarse": 16, "n_render_samples_fine": 24}, p["near"], p["far"],
+            model = N.NeRF(S.NET, {"n_render_samples_coarse": 16, "n_render_samples_fine": 24}, p["near"], p["far"],
                            precision="fp32")
             model.set_weights(p["bc"], p["bf"])
-            model.ctx.comm_init(_exchange_id(N, rank, id_path), rank, world)
+            model.ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
             rgb, dep = N.render_video(model, p["mats"], FOV, 9, 11, seed=3, equalize_depth=False)
-            _assert_stand_in_loaded()
+            S.assert_stand_in_loaded()
             model.ctx.comm_destroy()
             q.put((rank, (rgb, dep)))
         elif case in ("train_fp32", "train_mixed"):
             mixed = case == "train_mixed"
-            ctx = _make_ctx(N, p)
-            ctx.comm_init(_exchange_id(N, rank, id_path), rank, world)
+            ctx = S.golden_context(p)
+            ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
             ctx.train_begin(5e-4, mixed_float16=mixed, initial_loss_scale=1024.0 if mixed else 0.0)
-            _assert_stand_in_loaded()
+            S.assert_stand_in_loaded()
             n = p["o"].shape[0] // world
             sl = slice(rank * n, (rank + 1) * n)
             out = []
@@ -128,15 +84,13 @@ def _rank_main(rank, world, case, p, id_path, port, q):
             os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
             dist.init_process_group("gloo", rank=rank, world_size=world)
             try:
-                net_cfg = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05,
-                           "n_pos_enc_dim_xyz": 5, "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
-                model = N.NeRF(net_cfg, {"n_render_samples_coarse": p["sc"], "n_render_samples_fine": p["sf"]},
+                model = N.NeRF(S.NET, {"n_render_samples_coarse": p["sc"], "n_render_samples_fine": p["sf"]},
                                p["near"], p["far"], precision="fp32")
                 model.set_weights(p["bc"], p["bf"])
                 if case == "torch_group_lib":
                     model.ctx.comm_init_from_torch()
                     assert model.ctx.comm_world == world
-                    _assert_stand_in_loaded()
+                    S.assert_stand_in_loaded()
                 model.compile(5e-4, mixed_float16=True, initial_loss_scale=1024.0)
                 n = p["o"].shape[0] // world
                 sl = slice(rank * n, (rank + 1) * n)
@@ -158,30 +112,8 @@ def _rank_main(rank, world, case, p, id_path, port, q):
 
 
 def _run_ranks(world, case, payload, stub_lib, tmp_path, with_stub=True):
-    import torch.multiprocessing as mp
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
     id_path = str(tmp_path / f"comm_id_{case}_{world}")
-    port = _free_port()
-    old = os.environ.get("NERF_RCCL_LIB")
-    if with_stub:
-        os.environ["NERF_RCCL_LIB"] = stub_lib       # inherited by the ranks; this process keeps whatever it had loaded
-    try:
-        procs = [mpc.Process(target=_rank_main, args=(r, world, case, payload, id_path, port, q)) for r in range(world)]
-        for pr in procs:
-            pr.start()
-    finally:
-        if old is None:
-            os.environ.pop("NERF_RCCL_LIB", None)
-        else:
-            os.environ["NERF_RCCL_LIB"] = old
-    res = [q.get(timeout=420) for _ in procs]
-    for pr in procs:
-        pr.join(timeout=60)
-    for _, r in res:
-        if isinstance(r, BaseException):
-            raise r
-    return [r for _, r in sorted(res, key=lambda t: t[0])]
+    return S.run_ranks(_rank_main, world, (case, payload, id_path, S.free_port()), stub_lib if with_stub else None, timeout=420)
 
 
 def _weights(golden_ckpt):
@@ -201,7 +133,7 @@ def test_render_image_sharded_multi_rank(oracle, golden_ckpt, stub_lib, tmp_path
     p = _weights(golden_ckpt)
     p["c2w"] = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
     p["shapes"] = shapes
-    ctx = _make_ctx(N, p)
+    ctx = S.golden_context(p)
     want = [ctx.render_image(p["c2w"], FOV, h, w, 0, sc, sf, seed=5, rgb_only=True)[0] for (h, w, sc, sf, _) in shapes]
     ctx.close()
     got = _run_ranks(world, "render", p, stub_lib, tmp_path)
@@ -228,7 +160,7 @@ def test_render_image_sharded_every_output_multi_rank(oracle, golden_ckpt, stub_
     p = _weights(golden_ckpt)
     p["c2w"] = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
     p["shapes"] = shapes
-    ctx = _make_ctx(N, p)
+    ctx = S.golden_context(p)
     want = [ctx.render_image(p["c2w"], FOV, h, w, 0, sc, sf, seed=5, want_depth=True) for (h, w, sc, sf, _) in shapes]
     ctx.close()
     got = _run_ranks(world, "render_outputs", p, stub_lib, tmp_path)
@@ -250,9 +182,7 @@ def test_video_loop_shards_within_a_frame_from_c(oracle, golden_ckpt, stub_lib, 
     import nerf_and_dietnerf_amd as N
     p = _weights(golden_ckpt)
     p["mats"] = np.stack([oracle.get_sphere_matrix(1.0, -20, a, 0) for a in (10.0, 30.0, 50.0)]).astype(np.float32)
-    net_cfg = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05,
-               "n_pos_enc_dim_xyz": 5, "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
-    model = N.NeRF(net_cfg, {"n_render_samples_coarse": 16, "n_render_samples_fine": 24}, p["near"], p["far"],
+    model = N.NeRF(S.NET, {"n_render_samples_coarse": 16, "n_render_samples_fine": 24}, p["near"], p["far"],
                    precision="fp32")
     model.set_weights(p["bc"], p["bf"])
     rgb, dep = N.render_video(model, p["mats"], FOV, 9, 11, seed=3, equalize_depth=False)
@@ -262,30 +192,14 @@ def test_video_loop_shards_within_a_frame_from_c(oracle, golden_ckpt, stub_lib, 
         np.testing.assert_array_equal(r_dep, dep)
 
 
-def _train_problem(oracle, golden_ckpt, n=64, sc=16, sf=24, seed=4):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(8, 8, 0.46, c2w).reshape(-1, 4)
-    idx = rng.choice(d.shape[0], n, replace=n > d.shape[0])
-    p = _weights(golden_ckpt)
-    p.update(o=np.tile(c2w[:, 3], (n, 1)).astype(np.float32), d=np.ascontiguousarray(d[idx]),
-             u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32), sc=sc, sf=sf)
-    p["tgt"] = rng.random((n, 3), dtype=np.float32)
-    return p
-
-
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
 def test_data_parallel_train_step_inside_the_library(oracle, golden_ckpt, stub_lib, tmp_path):
     """nerf_train_step with a 2-rank communicator, fp32 policy: each rank passes half of the batch, the library averages
     the two gradient blobs (ncclAllReduce + 1/world) and steps.  The averaged gradients equal the single-process
     full-batch gradients (MSE is a mean over rays) to 1e-5 of max|g| and are bit-identical on both ranks, and so are the
     weights after one and after two steps."""
     import nerf_and_dietnerf_amd as N
-    p = _train_problem(oracle, golden_ckpt)
-    ctx = _make_ctx(N, p)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, seed=4)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4)
     _, gc_full, gf_full = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     ctx.close()
@@ -294,7 +208,7 @@ def test_data_parallel_train_step_inside_the_library(oracle, golden_ckpt, stub_l
     for step in range(2):
         for k in range(4):                      # gradients and weights of both networks: the same bits on both ranks
             np.testing.assert_array_equal(r0[step][k], r1[step][k])
-    assert _relerr(r0[0][0], gc_full) <= 1e-5 and _relerr(r0[0][1], gf_full) <= 1e-5
+    assert S.relerr(r0[0][0], gc_full) <= 1e-5 and S.relerr(r0[0][1], gf_full) <= 1e-5
     assert not np.array_equal(r0[0][2], p["bc"]) and not np.array_equal(r0[1][2], r0[0][2])
     assert r0[1][4] == (1.0, 2, 0)
 
@@ -304,7 +218,7 @@ def test_mixed_policy_skip_verdict_is_shared_by_all_ranks(oracle, golden_ckpt, s
     all-reduced blobs are not -- the finiteness test repeated on the reduced blobs makes BOTH ranks drop the step and
     halve the loss scale (weights bit for bit the loaded ones); the next, finite step is applied by both and leaves them
     with bit-identical weights again."""
-    p = _train_problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, seed=4)
     bad = p["tgt"].copy()
     bad[p["o"].shape[0] // 2 + 3, 1] = np.inf           # a ray of rank 1's half
     p["targets"] = [bad, p["tgt"]]
@@ -329,7 +243,7 @@ def test_nerf_mirror_train_step_under_a_torch_group(oracle, golden_ckpt, stub_li
         -> nerf_train_apply, which tests the blobs it is given (round 2 tested the local ones: one rank would have skipped
         while the other applied Inf).
     Either way both ranks skip the first step, apply the second, and agree bit for bit."""
-    p = _train_problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, seed=4)
     bad = p["tgt"].copy()
     bad[p["o"].shape[0] // 2 + 3, 1] = np.inf
     p["targets"] = [bad, p["tgt"]]

@@ -10,20 +10,13 @@ import grad_blocks as GB
 import occupancy_ref as G
 import sampling_space_ref as R
 import scene_box_ref as B
+import support as S
 
 pytestmark = pytest.mark.gpu
 
 NEAR, FAR = G.NEAR, G.FAR
-NDC_NEAR = 0.5
-NDC_BOX = ((-0.5, -0.4, -0.6), (0.5, 0.4, 0.4))            # NDC rays run from z = -1 (t = 0) to z = +1 (t = 1)
-GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))        # around the golden scene's content, as seen from its cameras
 NO_GRID = "no occupancy grid"
 NEEDS_BOX = "an occupancy grid needs a scene box"
-
-
-def _grid_for(r, lo, hi):
-    """The two balls on an r^3 grid over (lo, hi), plus 3 % scattered cells (seeded by r)."""
-    return G.two_balls(r, lo, hi) | (np.random.default_rng(r).random((r, r, r)) < 0.03)
 
 
 @pytest.fixture(scope="module")
@@ -37,28 +30,13 @@ def ctx():
 @pytest.fixture(scope="module")
 def world(ctx):
     """The six hand rays, then 4167 rays of the issue's recipe: 4173 in all."""
-    ho, hd = G.hand_rays()
-    o, d = G.sphere_rays(4173 - len(ho), seed=11)
-    return np.concatenate([ho, o]), np.concatenate([hd, d]), G.LO, G.HI, NEAR, FAR
+    return G.world_scene(4173)
 
 
 @pytest.fixture(scope="module")
 def ndc(ctx):
     """A 65 x 65 image of a forward-facing camera through rays_to_ndc: 4225 NDC rays, bounds 0 and 1."""
-    poses, fov = R.forward_facing_poses()
-    c2w = poses[1]
-    dirs = ctx.get_rays_directions(65, 65, fov, c2w).reshape(-1, 4)
-    orig = np.tile(c2w[:, 3], (65 * 65, 1)).astype(np.float32)
-    o, d = ctx.rays_to_ndc(orig, dirs, fov, NDC_NEAR)
-    return np.ascontiguousarray(o), np.ascontiguousarray(d), np.array(NDC_BOX[0], np.float32), np.array(NDC_BOX[1], np.float32), 0.0, 1.0
-
-
-def _arm(ctx, lo, hi, near, far, grid):
-    ctx.set_sampling("linear")
-    ctx.set_bounds(near, far)
-    ctx.set_scene_box(lo, hi)
-    if grid is not None:
-        ctx.set_occupancy_grid(grid)
+    return G.ndc_scene(ctx)
 
 
 # ---- 1. the walk -------------------------------------------------------------------------------------------------------------
@@ -68,8 +46,8 @@ def _arm(ctx, lo, hi, near, far, grid):
 def test_bounds_equal_the_restatement(ctx, world, ndc, space, r, n):
     o, d, lo, hi, near, far = world if space == "world" else ndc
     o, d = o[:n], d[:n]
-    grid = _grid_for(r, lo, hi)
-    _arm(ctx, lo, hi, near, far, grid)
+    grid = G.grid_for(r, lo, hi)
+    G.arm(ctx, lo, hi, near, far, grid)
     want_bounds, want_state = G.ray_occupancy_bounds(o, d, lo, hi, near, far, grid)
     bounds, state = ctx.ray_occupancy_bounds(o, d)
     assert state.dtype == np.int32 and bounds.dtype == np.float32 and bounds.shape == (n, 2)
@@ -101,7 +79,7 @@ def test_hand_cases_on_the_device(ctx):
         grids.append(g)
     grids.append(np.ones((4, 4, 4), bool))
     for g in grids:
-        _arm(ctx, G.LO, G.HI, NEAR, FAR, g)
+        G.arm(ctx, G.LO, G.HI, NEAR, FAR, g)
         want_bounds, want_state = G.ray_occupancy_bounds(o, d, G.LO, G.HI, NEAR, FAR, g)
         bounds, state = ctx.ray_occupancy_bounds(o, d)
         np.testing.assert_array_equal(state, want_state)
@@ -110,11 +88,11 @@ def test_hand_cases_on_the_device(ctx):
     def get(name):
         bounds, state = ctx.ray_occupancy_bounds(o, d)
         return tuple(bounds[names.index(name)].tolist()), int(state[names.index(name)])
-    _arm(ctx, G.LO, G.HI, NEAR, FAR, grids[0])
+    G.arm(ctx, G.LO, G.HI, NEAR, FAR, grids[0])
     assert get("through_cell_centres") == ((4.0, 4.5), 2)
-    _arm(ctx, G.LO, G.HI, NEAR, FAR, grids[7])
+    G.arm(ctx, G.LO, G.HI, NEAR, FAR, grids[7])
     assert get("through_cell_corners") == ((2.5, 3.0), 2)
-    _arm(ctx, G.LO, G.HI, NEAR, FAR, grids[5])
+    G.arm(ctx, G.LO, G.HI, NEAR, FAR, grids[5])
     assert get("through_cell_corners") == ((2.0, 4.0), 1)                 # (1, 0) is touched in a point: the box alone
 
 
@@ -127,14 +105,14 @@ def test_depths_equal_the_restatement(ctx, world, oracle, lindisp, s):
     o, d, lo, hi, near, far = world
     n = 521
     o, d = o[:n], d[:n]
-    grid = _grid_for(16, lo, hi)
+    grid = G.grid_for(16, lo, hi)
     _, state = G.ray_occupancy_bounds(o, d, lo, hi, near, far, grid)
     assert (state == 2).sum() >= n // 20 and (state == 1).sum() >= n // 20 and (state == 0).sum() >= n // 20
     u = np.random.default_rng(7 + s).random((n, s), dtype=np.float32)
     u[0], u[-1] = 0.0, R.U_BELOW_ONE
     u[np.nonzero(state == 2)[0][:2]] = np.array([[0.0], [R.U_BELOW_ONE]], np.float32)
     up = oracle.philox_uniform(9, np.arange(n, dtype=np.uint64), s, 0)
-    _arm(ctx, lo, hi, near, far, grid)
+    G.arm(ctx, lo, hi, near, far, grid)
     if lindisp:
         ctx.set_sampling("lindisp")
     z = ctx.get_z_values_for_rays(o, d, s, uniform_values=u)
@@ -161,7 +139,7 @@ def test_depths_equal_the_restatement(ctx, world, oracle, lindisp, s):
 def test_round_trip_and_refusals(ctx, world):
     import nerf_and_dietnerf_amd as N
     o, d = world[0][:8], world[1][:8]
-    _arm(ctx, G.LO, G.HI, NEAR, FAR, None)
+    G.arm(ctx, G.LO, G.HI, NEAR, FAR, None)
     assert ctx.occupancy_grid() is None
     with pytest.raises(RuntimeError, match=NO_GRID):
         ctx.ray_occupancy_bounds(o, d)
@@ -204,10 +182,10 @@ BAND = 1e-3
 
 @pytest.fixture(scope="module")
 def bake_ref(oracle, golden_ckpt):
-    """The 4096 float32 centres of a 16^3 grid over GOLDEN_BOX in bit order, the numpy oracle's sigma of the fine network there,
+    """The 4096 float32 centres of a 16^3 grid over G.GOLDEN_BOX in bit order, the numpy oracle's sigma of the fine network there,
     and a threshold chosen on the CPU: the first candidate that leaves fewer than 1 % of the cells inside the band
     |sigma - thr| <= 1e-3 max(1, thr) and marks between 2 % and 50 % of them."""
-    centres = G.centres_in_bit_order(*GOLDEN_BOX, 16)
+    centres = G.centres_in_bit_order(*G.GOLDEN_BOX, 16)
     view = np.tile(np.array([0.0, 0.0, 1.0], np.float32), (centres.shape[0], 1))
     sigma = oracle.model_predict(oracle.unpack_blob(golden_ckpt["blob_fine"]), centres, view)[:, 3]
     for thr in (10.0, 20.0, 5.0, 40.0, 2.5):
@@ -217,7 +195,7 @@ def bake_ref(oracle, golden_ckpt):
     raise AssertionError("no candidate threshold leaves fewer than 1 % of the cells inside the band")
 
 
-def _golden_ctx(golden_ckpt, precision, box=GOLDEN_BOX):
+def _golden_ctx(golden_ckpt, precision, box=G.GOLDEN_BOX):
     import nerf_and_dietnerf_amd as N
     c = N.Context(near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]), precision=precision)
     c.load_weights(0, golden_ckpt["blob_coarse"])
@@ -280,7 +258,7 @@ def test_bake_in_chunks(golden_ckpt):
         grid = c.occupancy_grid()
         assert count == int(grid.sum()) and 0 < count < r ** 3
         if spc == 1:
-            centres = G.centres_in_bit_order(*GOLDEN_BOX, r)
+            centres = G.centres_in_bit_order(*G.GOLDEN_BOX, r)
             for begin in (0, (1 << 20) - 2048, r ** 3 - 4096):         # the grid's first cells, across the chunk seam, its last cells
                 x = np.ascontiguousarray(centres[begin:begin + 4096])
                 raw = c.model_predict(1, x, np.tile(np.array([0.0, 0.0, 1.0], np.float32), (4096, 1)))
@@ -292,7 +270,7 @@ def test_render_config_bakes_on_request(golden_ckpt):
     import nerf_and_dietnerf_amd as N
     net = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
            "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
-    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(GOLDEN_BOX[0]), list(GOLDEN_BOX[1])],
+    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(G.GOLDEN_BOX[0]), list(G.GOLDEN_BOX[1])],
           "occupancy_grid": {"resolution": 16, "sigma_threshold": 10.0, "dilate": 0}}
     m = N.NeRF(net, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="fp32")
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
@@ -323,7 +301,7 @@ def golden_scene(oracle, golden_ckpt, bake_ref):
         o, d = R.world_rays(oracle, golden_ckpt["c2w_train"], float(golden_ckpt["fov"]), h, w)
         o, d = np.ascontiguousarray(o[:n]), np.ascontiguousarray(d[:n])
         d[-10:, :3] *= -1.0
-        _, state = G.ray_occupancy_bounds(o, d, *GOLDEN_BOX, near, far, grid)
+        _, state = G.ray_occupancy_bounds(o, d, *G.GOLDEN_BOX, near, far, grid)
         assert (state == 2).sum() >= n // 4 and (state == 1).sum() >= n // 20 and (state == 0).sum() >= 10, np.bincount(state)
         out[n] = (o, d, state)
     return grid, near, far, out
@@ -346,7 +324,7 @@ def test_render_follows_the_grid(oracle, golden_ckpt, golden_scene, precision, n
     o, d, state = rays[n]
     rng = np.random.default_rng(n)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
-    z_ref = G.z_values(o, d, *GOLDEN_BOX, near, far, grid, u_c)
+    z_ref = G.z_values(o, d, *G.GOLDEN_BOX, near, far, grid, u_c)
     c = _golden_ctx(golden_ckpt, precision)
     c.set_occupancy_grid(grid)
     out = c.render(o, d, sc, sf, u_c, u_f)
@@ -374,15 +352,6 @@ def test_render_follows_the_grid(oracle, golden_ckpt, golden_scene, precision, n
     assert not np.array_equal(out[5][state == 2], box_only[5][state == 2])
 
 
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a, b = a.astype(np.float64), b.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 @pytest.mark.parametrize("n,sc,sf", SIZES)
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
 def test_train_gradients_follow_the_grid(oracle, golden_ckpt, golden_scene, policy, n, sc, sf, capsys):
@@ -404,10 +373,10 @@ def test_train_gradients_follow_the_grid(oracle, golden_ckpt, golden_scene, poli
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     tgt = rng.random((n, 3), dtype=np.float32)
     mixed = policy == "mixed_float16"
-    z_ref = G.z_values(o, d, *GOLDEN_BOX, near, far, grid, u_c)
+    z_ref = G.z_values(o, d, *G.GOLDEN_BOX, near, far, grid, u_c)
     res = {}
     for mode in ("grid", "substituted", "box"):
-        c = _golden_ctx(golden_ckpt, "fp32", box=None if mode == "substituted" else GOLDEN_BOX)
+        c = _golden_ctx(golden_ckpt, "fp32", box=None if mode == "substituted" else G.GOLDEN_BOX)
         if mode == "grid":
             c.set_occupancy_grid(grid)
         u = _substituted(oracle, z_ref, near, far) if mode == "substituted" else u_c
@@ -419,12 +388,12 @@ def test_train_gradients_follow_the_grid(oracle, golden_ckpt, golden_scene, poli
     blks = GB.blocks(5, 4, 2)
     with capsys.disabled():
         print(f"\n[{policy}, {n} x ({sc}+{sf})] grid vs substituted draws: loss {m0['loss']:.7f} / {m1['loss']:.7f} (box only: "
-              f"{m2['loss']:.7f}), gradients {_relerr(gc0, gc1):.2e} (coarse), {_relerr(gf0, gf1):.2e} (fine) of max|g|; "
+              f"{m2['loss']:.7f}), gradients {S.relerr(gc0, gc1):.2e} (coarse), {S.relerr(gf0, gf1):.2e} (fine) of max|g|; "
               f"coarse {GB.summary(GB.block_errors(gc0, gc1, blks))}; fine {GB.summary(GB.block_errors(gf0, gf1, blks))}", end="")
     assert np.isfinite(gc0).all() and np.isfinite(gf0).all()
     assert abs(m0["loss"] - m1["loss"]) <= (2e-3 if mixed else 2e-6) * m1["loss"]
-    assert _relerr(gc0, gc1) <= 5e-2 and _cos(gc0, gc1) > 0.999
-    assert _relerr(gf0, gf1) <= 5e-2 and _cos(gf0, gf1) > 0.999
+    assert S.relerr(gc0, gc1) <= 5e-2 and S.cos(gc0, gc1) > 0.999
+    assert S.relerr(gf0, gf1) <= 5e-2 and S.cos(gf0, gf1) > 0.999
     bar = GB.MIXED_LEAST if mixed else 5 * GB.FP32_BAR
     GB.assert_blocks(gc0, gc1, blks, bar, "max", "coarse")
     GB.assert_blocks(gf0, gf1, blks, bar, "max", "fine")

@@ -11,19 +11,20 @@ term missing.
 import numpy as np
 import pytest
 
+import culling_ref as K
 import grad_blocks as GB
+import occupancy_ref as O
 import ray_grad_ref as G
 import render_outputs_ref as R
-from test_gpu_render_outputs import GOLDEN_BOX, _cos, _cotangents, _ctx, _draws, _fwd, _problem, _relerr
+import support as S
 
 pytestmark = pytest.mark.gpu
 
 BLOCKS = GB.blocks(5, 4, 2)
-NAMES = ("d_rgb", "d_depth", "d_weights", "d_z")
 
 
 def _sets(cot):
-    return {**{k: {k: cot[k]} for k in NAMES}, "all": dict(cot)}
+    return {**{k: {k: cot[k]} for k in R.NAMES}, "all": dict(cot)}
 
 
 def _args(p, fine=True):
@@ -31,7 +32,7 @@ def _args(p, fine=True):
 
 
 def _begin(p, ray_gradients=True, fine=True, ctx_kw=None, **train_kw):
-    ctx = _ctx(p, fine=fine, **(ctx_kw or {}))
+    ctx = S.golden_context(p, fine=fine, **(ctx_kw or {}))
     ctx.train_begin(5e-4, **train_kw)
     if ray_gradients:
         ctx.train_set_ray_gradients(True)
@@ -39,7 +40,7 @@ def _begin(p, ray_gradients=True, fine=True, ctx_kw=None, **train_kw):
 
 
 def _rays_backward(ctx, p, slot=0, **cot):
-    _fwd(ctx, p, slot=slot, outputs=("rgb",))
+    R.forward(ctx, p, slot=slot, outputs=("rgb",))
     return ctx.train_render_backward_outputs(slot, **cot, want_rays=True)
 
 
@@ -49,7 +50,7 @@ def _figures(capsys, label, got, ref):
     for name, g, r in zip(("d_rays_orig", "d_rays_dirs"), got, ref):
         assert g.shape == r.shape and g.dtype == np.float32
         assert not g[:, 3].any(), f"{label}: {name}[:, 3] is not zero"
-        out.append((_relerr(g, r), _cos(g.ravel(), r.ravel().astype(np.float64))))
+        out.append((S.relerr(g, r), S.cos(g.ravel(), r.ravel().astype(np.float64))))
     with capsys.disabled():
         print(f"\n    {label}: d_rays_orig {out[0][0]:.2e} of max|g|, cosine {out[0][1]:.8f}; d_rays_dirs {out[1][0]:.2e}, "
               f"cosine {out[1][1]:.8f}", end="")
@@ -60,8 +61,8 @@ def _figures(capsys, label, got, ref):
 def big(oracle, golden_ckpt):
     """The 40 x (55 + 55) problem of tests/test_gpu_render_outputs.py with its cotangents and, computed once per (sampler
     term, dtype, loss scale) and shared, the oracle's ray and weight gradients for the five cotangent sets."""
-    p = _problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
-    p["cot"] = _cotangents(40, 110)
+    p = S.golden_problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
+    p["cot"] = R.cotangents(40, 110)
     cache = {}
 
     def ref(sampler_grad, fp16_loss_scale=None, weights=False):
@@ -102,7 +103,7 @@ def test_bare_operator(golden_ckpt):
     ctx.close()
 
 
-@pytest.mark.parametrize("name", NAMES + ("all",))
+@pytest.mark.parametrize("name", R.NAMES + ("all",))
 @pytest.mark.parametrize("sampler_gradient", [True, False])
 def test_against_float64_autograd(big, sampler_gradient, name, capsys):
     """40 x (55 + 55), alpha = 1, the shipped checkpoint: both ray gradients within 2e-4 of the tensor's max|g| of float64
@@ -131,15 +132,15 @@ def test_against_float64_autograd(big, sampler_gradient, name, capsys):
     else:
         assert not gc.any() and not rc.any()
     for g, r, which in blobs:
-        e, c = _relerr(g, r), _cos(g, r)
+        e, c = S.relerr(g, r), S.cos(g, r)
         assert e <= 2e-4 and c > 0.9999999, (which, e, c)
 
 
 def test_ragged_pass_at_the_trained_slope(oracle, golden_ckpt, capsys):
     """7 rays x (33 + 32): the merged S = 65 crosses the 64 lanes and the 32-sample rounds, N is no multiple of the four rays
     per workgroup; alpha = 0.05 and all four cotangents at the alpha = 0.05 bars (1e-2 of max|g|, cosine > 0.9999)."""
-    p = _problem(oracle, golden_ckpt, n=7, sc=33, sf=32, seed=21)
-    cot = _cotangents(7, 65, seed=5)
+    p = S.golden_problem(oracle, golden_ckpt, n=7, sc=33, sf=32, seed=21)
+    cot = R.cotangents(7, 65, seed=5)
     ref = G.ray_gradients(*_args(p), **cot)
     ctx = _begin(p)
     _, _, g_o, g_d = _rays_backward(ctx, p, **cot)
@@ -150,8 +151,8 @@ def test_ragged_pass_at_the_trained_slope(oracle, golden_ckpt, capsys):
 
 def test_coarse_only_context(oracle, golden_ckpt, capsys):
     """A context without a fine network, 5 rays x 3 samples: the coarse pass is the last pass; d_z changes no bit."""
-    p = _problem(oracle, golden_ckpt, n=5, sc=3, sf=0, seed=2)
-    cot = _cotangents(5, 3, seed=8)
+    p = S.golden_problem(oracle, golden_ckpt, n=5, sc=3, sf=0, seed=2)
+    cot = R.cotangents(5, 3, seed=8)
     three = {k: cot[k] for k in ("d_rgb", "d_depth", "d_weights")}
     ref = G.ray_gradients(*_args(p, fine=False), **three)
     ctx = _begin(p, fine=False)
@@ -177,10 +178,10 @@ def test_network_variants(oracle, golden_ckpt, lx, ld, na, capsys):
     2e-2 of max|d_rays_dirs| there and the sampler term about 100 %, so the 1e-2 bar still tells either from missing.)"""
     import nerf_and_dietnerf_amd as N
     kw = dict(n_pos_enc_xyz=lx, n_pos_enc_dir=ld, n_angles=na)
-    p = _problem(oracle, golden_ckpt, n=6, sc=8, sf=8, seed=13)
+    p = S.golden_problem(oracle, golden_ckpt, n=6, sc=8, sf=8, seed=13)
     p["bc"], p["bf"] = N.glorot_blob(3, **kw), N.glorot_blob(4, **kw)
     p["bc"][-1] = p["bf"][-1] = 1.5              # lift sigma: Glorot networks are almost transparent
-    cot = _cotangents(6, 16, seed=7)
+    cot = R.cotangents(6, 16, seed=7)
     ref = G.ray_gradients(*_args(p), **cot, **kw)
     ctx = _begin(p, ctx_kw=dict(precision="fp32" if lx <= 5 else "f16x3", **kw))
     _, _, g_o, g_d = _rays_backward(ctx, p, **cot)
@@ -220,14 +221,14 @@ def test_switch_semantics(big):
     assert ctx.train_ray_gradients is False
 
     def both():
-        _fwd(ctx, p, outputs=("rgb",))
+        R.forward(ctx, p, outputs=("rgb",))
         a = ctx.train_render_backward_outputs(0, **cot)
-        ctx.train_render_forward(0, p["o"], p["d"], *_draws(p))
+        ctx.train_render_forward(0, p["o"], p["d"], *R.draws(p))
         return a + ctx.train_render_backward(0, d_rgb)
 
     off = both()
     # off: asking for the rays raises, and the slot survives the refusal
-    _fwd(ctx, p, outputs=("rgb",))
+    R.forward(ctx, p, outputs=("rgb",))
     with pytest.raises(RuntimeError, match="nerf_train_set_ray_gradients"):
         ctx.train_render_backward_outputs(0, **cot, want_rays=True)
     ctx.train_render_backward_outputs(0, **cot, want_blobs=False)
@@ -238,12 +239,12 @@ def test_switch_semantics(big):
     np.testing.assert_array_equal(on[1], off[1])
     np.testing.assert_array_equal(on[3], off[3])
     rc, _ = R.render_outputs_gradient_sets(*_args(p), {"all": dict(cot)}, alpha=1.0)["grads"]["all"]
-    assert _relerr(on[0], rc) <= 2e-4 and _cos(on[0], rc) > 0.9999999
+    assert S.relerr(on[0], rc) <= 2e-4 and S.cos(on[0], rc) > 0.9999999
     # both ray outputs NULL: nerf_train_render_backward_outputs, bit for bit
     import ctypes as C
     import nerf_and_dietnerf_amd as N
-    _fwd(ctx, p, outputs=("rgb",))
-    keep = [np.ascontiguousarray(cot[k]) for k in NAMES]
+    R.forward(ctx, p, outputs=("rgb",))
+    keep = [np.ascontiguousarray(cot[k]) for k in R.NAMES]
     g = N._lib.NerfRenderGrads(*[a.ctypes.data for a in keep])
     gc, gf = np.empty(ctx.blob_size(), np.float32), np.empty(ctx.blob_size(), np.float32)
     N._lib.check(ctx.lib.nerf_train_render_backward_rays(ctx.h, 0, C.byref(g), 0, gc.ctypes.data, gf.ctypes.data, None, None, 0))
@@ -258,7 +259,7 @@ def test_switch_semantics(big):
     ctx.train_set_ray_gradients(True)
     ctx.train_begin(5e-4)
     assert ctx.train_ray_gradients is False
-    _fwd(ctx, p, outputs=("rgb",))
+    R.forward(ctx, p, outputs=("rgb",))
     with pytest.raises(RuntimeError, match="nerf_train_set_ray_gradients"):
         ctx.train_render_backward_outputs(0, **cot, want_rays=True)
     fresh = both()
@@ -271,21 +272,19 @@ def test_train_sample_culling(oracle, golden_ckpt):
     """Sixteen rays of the golden training camera, the last ten turned round so that they miss the box.  Under
     nerf_ctx_set_train_sample_culling with a full grid the ray gradients are the bits of the flag being off; with one half of
     the grid emptied the rays that miss the box keep their bits, the others change, and every ray's result is finite."""
-    import culling_ref as K
-    from test_gpu_train_culling import _ctx as cull_ctx, scene
-    p = scene(oracle, golden_ckpt, 16, 20, 17, 4)
-    cot = _cotangents(16, 37, seed=6)
+    p = K.train_scene(oracle, golden_ckpt, 16, 20, 17, 4)
+    cot = R.cotangents(16, 37, seed=6)
     full, half = np.ones((16, 16, 16), bool), np.ones((16, 16, 16), bool)
     half[:8] = False
     got = {}
     for key, flag, grid in (("off", False, full), ("full", True, full), ("half", True, half)):
-        ctx = cull_ctx(p, grid, flag)
+        ctx = K.culled_context(p, grid, flag)
         ctx.train_begin(5e-4)
         ctx.train_set_ray_gradients(True)
-        z = _fwd(ctx, p)["z"]
+        z = R.forward(ctx, p)["z"]
         got[key] = ctx.train_render_backward_outputs(0, **cot, want_rays=True)[2:]
         if key == "off":
-            inside, _ = K.sample_cells(p["o"], p["d"], z, *GOLDEN_BOX, 16, K.F32)
+            inside, _ = K.sample_cells(p["o"], p["d"], z, *O.GOLDEN_BOX, 16, K.F32)
             outside = ~inside.any(-1)
         ctx.close()
     assert outside[6:].all() and not outside[:6].any()

@@ -12,45 +12,13 @@ import numpy as np
 import pytest
 
 import grad_blocks as GB
+import occupancy_ref as O
 import render_outputs_ref as R
+import support as S
 
 pytestmark = pytest.mark.gpu
 
 BLOCKS = GB.blocks(5, 4, 2)
-NAMES = ("d_rgb", "d_depth", "d_weights", "d_z")
-GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))
-
-
-def _rays(oracle, n, seed=0, hw=8):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(hw, hw, 0.46, c2w).reshape(-1, 4)
-    idx = rng.choice(d.shape[0], n, replace=n > d.shape[0])
-    return np.tile(c2w[:, 3], (n, 1)).astype(np.float32), np.ascontiguousarray(d[idx]), rng
-
-
-def _problem(oracle, golden_ckpt, n=48, sc=16, sf=24, seed=0):
-    o, d, rng = _rays(oracle, n, seed)
-    return dict(o=o, d=d, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
-                tgt=rng.random((n, 3), dtype=np.float32), sc=sc, sf=sf, n=n, near=float(golden_ckpt["near"]),
-                far=float(golden_ckpt["far"]), bc=golden_ckpt["blob_coarse"], bf=golden_ckpt["blob_fine"])
-
-
-def _ctx(p, fine=True, **kw):
-    import nerf_and_dietnerf_amd as N
-    kw.setdefault("precision", "fp32")
-    ctx = N.Context(near=p["near"], far=p["far"], **kw)
-    ctx.load_weights(0, p["bc"])
-    if fine:
-        ctx.load_weights(1, p["bf"])
-    return ctx
-
-
-def _cotangents(n, s, seed=3):
-    """0.1 N(0, 1) for each of the four outputs; d_rgb is drawn first, as test_backward_through_render draws its own."""
-    rng = np.random.default_rng(seed)
-    shapes = {"d_rgb": (n, 3), "d_depth": (n,), "d_weights": (n, s), "d_z": (n, s)}
-    return {k: (rng.standard_normal(shapes[k]) * 0.1).astype(np.float32) for k in NAMES}
 
 
 def _sets(cot):
@@ -58,29 +26,12 @@ def _sets(cot):
             "all": dict(cot)}
 
 
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a = a.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
-def _draws(p):
-    return (p["sc"], p["sf"], p["u_c"], p["u_f"])
-
-
-def _fwd(ctx, p, slot=0, **kw):
-    return ctx.train_render_forward_outputs(slot, p["o"], p["d"], *_draws(p), **kw)
-
-
 @pytest.fixture(scope="module")
 def big(oracle, golden_ckpt):
     """The 40 x (55 + 55) problem of test_backward_through_render, its cotangents, and -- computed once per (sampler term,
     dtype, loss scale) and shared -- the oracle's outputs and gradients for the four cotangent sets."""
-    p = _problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
-    p["cot"] = _cotangents(40, 110)
+    p = S.golden_problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
+    p["cot"] = R.cotangents(40, 110)
     cache = {}
 
     def ref(sampler_grad, dtype="float64", fp16_loss_scale=None, alpha=1.0):
@@ -131,10 +82,10 @@ def test_forward_outputs_and_interchangeable_slots(big, capsys):
     z within 1e-6 x far.  Either forward fills a slot that either backward consumes, bit for bit."""
     p, far = big, big["far"]
     r = p["ref"](True)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4)
-    out = _fwd(ctx, p, slot=2)
-    rgb_old = ctx.train_render_forward(5, p["o"], p["d"], *_draws(p))
+    out = R.forward(ctx, p, slot=2)
+    rgb_old = ctx.train_render_forward(5, p["o"], p["d"], *R.draws(p))
     np.testing.assert_array_equal(out["rgb"], rgb_old)
     assert out["depth"].shape == (40,) and out["weights"].shape == (40, 110) and out["z"].shape == (40, 110)
     figs = {k: float(np.abs(out[k] - r[k]).max()) for k in ("rgb", "weights", "depth", "z")}
@@ -146,13 +97,13 @@ def test_forward_outputs_and_interchangeable_slots(big, capsys):
     assert figs["z"] <= 1e-6 * far
     assert (np.diff(out["z"], axis=-1) >= 0).all()
     # a subset of the outputs: the same bits, nothing else returned
-    part = _fwd(ctx, p, slot=3, outputs=("depth", "z"))
+    part = R.forward(ctx, p, slot=3, outputs=("depth", "z"))
     assert set(part) == {"depth", "z"}
     np.testing.assert_array_equal(part["depth"], out["depth"])
     np.testing.assert_array_equal(part["z"], out["z"])
     # slots: new forward (2) -> old backward, old forward (5) -> new backward, against old -> old (6)
     d_rgb = p["cot"]["d_rgb"]
-    ctx.train_render_forward(6, p["o"], p["d"], *_draws(p))
+    ctx.train_render_forward(6, p["o"], p["d"], *R.draws(p))
     gc0, gf0 = ctx.train_render_backward(6, d_rgb)
     gc1, gf1 = ctx.train_render_backward(2, d_rgb)
     gc2, gf2 = ctx.train_render_backward_outputs(5, d_rgb=d_rgb)
@@ -176,11 +127,11 @@ def test_forward_outputs_and_interchangeable_slots(big, capsys):
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
 def test_d_rgb_alone_is_the_existing_backward_bit_for_bit(big, policy):
     p, d_rgb = big, big["cot"]["d_rgb"]
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, mixed_float16=policy == "mixed_float16")
-    rgb_old = ctx.train_render_forward(0, p["o"], p["d"], *_draws(p))
+    rgb_old = ctx.train_render_forward(0, p["o"], p["d"], *R.draws(p))
     gc0, gf0 = ctx.train_render_backward(0, d_rgb)
-    out = _fwd(ctx, p, slot=0)
+    out = R.forward(ctx, p, slot=0)
     gc1, gf1 = ctx.train_render_backward_outputs(0, d_rgb=d_rgb)
     np.testing.assert_array_equal(out["rgb"], rgb_old)
     GB.check_equal(gc1, gc0, BLOCKS, 0, f"[{policy}] coarse")
@@ -192,7 +143,7 @@ def test_d_rgb_alone_is_the_existing_backward_bit_for_bit(big, policy):
 def _report(capsys, label, g, ref64, ref32_fn):
     """The blob-wide figures; where they miss the bar, the block-wise ones as well (GB.check_fp32_smooth prints them; what it
     asserts of its own is printed too, the caller fails the case on the blob-wide bar)."""
-    e, c = _relerr(g, ref64), _cos(g, ref64)
+    e, c = S.relerr(g, ref64), S.cos(g, ref64)
     with capsys.disabled():
         print(f"\n    {label}: {e:.2e} of max|g|, cosine {c:.8f}", end="")
         if not (e <= 2e-4 and c > 0.9999999):
@@ -211,13 +162,13 @@ def test_gradients_against_float64_autograd(big, sampler_gradient, capsys):
     changes no bit."""
     p, cot = big, big["cot"]
     r = p["ref"](sampler_gradient)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, sampler_gradient=sampler_gradient)
     with capsys.disabled():
         print(f"\n[render-output gradients, 40 x (55 + 55), sampler term {'on' if sampler_gradient else 'off'}]", end="")
     failed = []
     for name, kw in _sets(cot).items():
-        _fwd(ctx, p, outputs=("rgb",))
+        R.forward(ctx, p, outputs=("rgb",))
         gc, gf = ctx.train_render_backward_outputs(0, **kw)
         rc, rf = r["grads"][name]
         r32 = lambda which: (lambda: p["ref"](sampler_gradient, "float32")["grads"][name][which])      # noqa: E731
@@ -236,9 +187,9 @@ def test_gradients_against_float64_autograd(big, sampler_gradient, capsys):
     assert not failed, failed
     if not sampler_gradient:
         three = {k: cot[k] for k in ("d_rgb", "d_depth", "d_weights")}
-        _fwd(ctx, p, outputs=("rgb",))
+        R.forward(ctx, p, outputs=("rgb",))
         gc_a, gf_a = ctx.train_render_backward_outputs(0, **three)
-        _fwd(ctx, p, outputs=("rgb",))
+        R.forward(ctx, p, outputs=("rgb",))
         gc_b, gf_b = ctx.train_render_backward_outputs(0, **three, d_z=cot["d_z"])
         np.testing.assert_array_equal(gf_a, gf_b)
         np.testing.assert_array_equal(gc_a, gc_b)
@@ -250,15 +201,15 @@ def test_ragged_merged_pass_at_the_trained_slope(oracle, golden_ckpt, capsys):
     trained slope alpha = 0.05 and the combined cotangent, at the project's alpha = 0.05 blob bars (relative error <= 1e-2 of
     max|g|, cosine > 0.9999; float32 autograd itself is at 3.5e-5 / 6.9e-5 (fine / coarse) of max|g| on these inputs, with
     gradients of order 0.1 .. 1)."""
-    p = _problem(oracle, golden_ckpt, n=7, sc=33, sf=32, seed=21)
-    cot = _cotangents(7, 65, seed=5)
+    p = S.golden_problem(oracle, golden_ckpt, n=7, sc=33, sf=32, seed=21)
+    cot = R.cotangents(7, 65, seed=5)
     r = R.render_outputs_gradients(p["bc"], p["bf"], p["o"], p["d"], p["near"], p["far"], p["u_c"], p["u_f"], **cot)
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4)
-    out = _fwd(ctx, p)
+    out = R.forward(ctx, p)
     gc, gf = ctx.train_render_backward_outputs(0, **cot)
     assert np.abs(out["depth"] - r["depth"]).max() <= 5e-5 * p["far"]
-    ef, cf, ec, cc = _relerr(gf, r["grad_fine"]), _cos(gf, r["grad_fine"]), _relerr(gc, r["grad_coarse"]), _cos(gc, r["grad_coarse"])
+    ef, cf, ec, cc = S.relerr(gf, r["grad_fine"]), S.cos(gf, r["grad_fine"]), S.relerr(gc, r["grad_coarse"]), S.cos(gc, r["grad_coarse"])
     with capsys.disabled():
         print(f"\n[render-output gradients, 7 x (33 + 32), alpha 0.05, all four] fine {ef:.2e} cosine {cf:.7f}; "
               f"coarse {ec:.2e} cosine {cc:.7f}; max|g| fine {np.abs(r['grad_fine']).max():.2e} coarse "
@@ -271,18 +222,18 @@ def test_ragged_merged_pass_at_the_trained_slope(oracle, golden_ckpt, capsys):
 def test_coarse_only_context_ignores_d_z(oracle, golden_ckpt, capsys):
     """A context without a fine network, 5 rays x 3 samples: d_depth + d_weights against the oracle at the same alpha = 0.05
     bars (the same network and policy as the ragged case); the depths of a coarse pass are data, so d_z changes no bit."""
-    p = _problem(oracle, golden_ckpt, n=5, sc=3, sf=0, seed=2)
-    cot = _cotangents(5, 3, seed=8)
+    p = S.golden_problem(oracle, golden_ckpt, n=5, sc=3, sf=0, seed=2)
+    cot = R.cotangents(5, 3, seed=8)
     two = {k: cot[k] for k in ("d_depth", "d_weights")}
     r = R.render_outputs_gradients(p["bc"], None, p["o"], p["d"], p["near"], p["far"], p["u_c"], None, **two)
-    ctx = _ctx(p, fine=False)
+    ctx = S.golden_context(p, fine=False)
     ctx.train_begin(5e-4)
     out = ctx.train_render_forward_outputs(0, p["o"], p["d"], 3, 0, p["u_c"])
     assert out["weights"].shape == (5, 3) and out["z"].shape == (5, 3)
     assert np.abs(out["weights"] - r["weights"]).max() <= 5e-5 and np.abs(out["depth"] - r["depth"]).max() <= 5e-5 * p["far"]
     gc, gf = ctx.train_render_backward_outputs(0, **two)
     assert gf is None
-    e, c = _relerr(gc, r["grad_coarse"]), _cos(gc, r["grad_coarse"])
+    e, c = S.relerr(gc, r["grad_coarse"]), S.cos(gc, r["grad_coarse"])
     with capsys.disabled():
         print(f"\n[render-output gradients, coarse only, 5 x 3, d_depth + d_weights] {e:.2e} of max|g|, cosine {c:.7f}", end="")
     assert e <= 1e-2 and c > 0.9999
@@ -300,16 +251,16 @@ def test_mixed_float16_policy(big, capsys):
     range -- the emulating oracle itself returns non-finite fine gradients there (306 entries for d_weights alone), a step
     the dynamic loss scale exists to skip.  Then an inf in d_depth: the step is skipped and the loss scale halves."""
     p, cot, scale = big, big["cot"], 2048.0
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=scale)
-    out = _fwd(ctx, p)
+    out = R.forward(ctx, p)
     gc, gf = ctx.train_render_backward_outputs(0, **cot)
     r16 = p["ref"](True, "float64", scale)
     e32 = p["ref"](True, "float32", scale)
     rc, rf = r16["grads"]["all"]
     assert np.abs(out["rgb"] - r16["rgb"]).max() <= 2e-3
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
-    qf, cf, qc, cc = _relerr(gf, rf), _cos(gf, rf), _relerr(gc, rc), _cos(gc, rc)
+    qf, cf, qc, cc = S.relerr(gf, rf), S.cos(gf, rf), S.relerr(gc, rc), S.cos(gc, rc)
     with capsys.disabled():
         print(f"\n[render-output gradients, mixed_float16, loss scale {scale:g}, all four] fine vs the fp16-emulating oracle "
               f"{qf:.2e} of max|g|, cosine {cf:.6f}; coarse {qc:.2e}, cosine {cc:.6f}", end="")
@@ -322,7 +273,7 @@ def test_mixed_float16_policy(big, capsys):
     w0, w1 = ctx.get_weights(0), ctx.get_weights(1)
     bad = cot["d_depth"].copy()
     bad[3] = np.inf
-    _fwd(ctx, p, outputs=("rgb",))
+    R.forward(ctx, p, outputs=("rgb",))
     ctx.train_render_backward_outputs(0, d_rgb=cot["d_rgb"], d_depth=bad, want_blobs=False)
     ctx.train_apply()
     assert ctx.train_loss_scale() == (scale / 2, 1, 1)
@@ -334,12 +285,12 @@ def test_mixed_float16_policy(big, capsys):
 def test_accumulate_adds_to_the_ray_loss_gradients(big):
     """accumulate = 1 after nerf_train_gradients: the sum of the two gradients, to 1e-6 of max|g| (the existing test's bar)."""
     p, cot = big, big["cot"]
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4)
-    _fwd(ctx, p, outputs=("rgb",))
+    R.forward(ctx, p, outputs=("rgb",))
     gc, gf = ctx.train_render_backward_outputs(0, **cot)
-    _, gc1, gf1 = ctx.train_gradients(p["o"], p["d"], p["tgt"], *_draws(p))
-    _fwd(ctx, p, outputs=("rgb",))
+    _, gc1, gf1 = ctx.train_gradients(p["o"], p["d"], p["tgt"], *R.draws(p))
+    R.forward(ctx, p, outputs=("rgb",))
     gc2, gf2 = ctx.train_render_backward_outputs(0, **cot, accumulate=True)
     assert np.abs(gf2 - (gf1 + gf)).max() <= 1e-6 * np.abs(gf2).max()
     assert np.abs(gc2 - (gc1 + gc)).max() <= 1e-6 * max(np.abs(gc2).max(), 1e-30)
@@ -351,18 +302,18 @@ def test_train_sample_culling_under_a_full_grid_changes_no_bit(oracle, golden_ck
     """nerf_ctx_set_train_sample_culling with a grid that keeps every cell: outputs and gradients of the new calls are the
     bits of the flag being off (compositing, its backward and the fold run on all samples either way)."""
     import nerf_and_dietnerf_amd as N
-    p = _problem(oracle, golden_ckpt, n=13, sc=20, sf=17, seed=4)
-    cot = _cotangents(13, 37, seed=6)
+    p = S.golden_problem(oracle, golden_ckpt, n=13, sc=20, sf=17, seed=4)
+    cot = R.cotangents(13, 37, seed=6)
     got = []
     for flag in (False, True):
         ctx = N.Context(near=p["near"], far=p["far"], precision="fp32")
         ctx.load_weights(0, p["bc"])
         ctx.load_weights(1, p["bf"])
-        ctx.set_scene_box(*GOLDEN_BOX)
+        ctx.set_scene_box(*O.GOLDEN_BOX)
         ctx.set_occupancy_grid(np.ones((16, 16, 16), bool))
         ctx.set_train_sample_culling(flag)
         ctx.train_begin(5e-4)
-        out = _fwd(ctx, p)
+        out = R.forward(ctx, p)
         gc, gf = ctx.train_render_backward_outputs(0, **cot)
         got.append((out, gc, gf))
         ctx.close()
@@ -380,7 +331,7 @@ def test_bridge_mse_equals_the_d_rgb_backward(big):
     import torch
     import nerf_and_dietnerf_amd as N
     p = big
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4)
     dev = lambda a: torch.as_tensor(a, device="cuda")                                              # noqa: E731
     o, d, t, uc, uf = (dev(p[k]) for k in ("o", "d", "tgt", "u_c", "u_f"))
@@ -394,7 +345,7 @@ def test_bridge_mse_equals_the_d_rgb_backward(big):
     d_rgb = leaf.grad.cpu().numpy()
     formula = 2.0 * (out["rgb"].detach().cpu().numpy().astype(np.float64) - p["tgt"]) / (3 * p["n"])
     np.testing.assert_allclose(d_rgb, formula, rtol=1e-6, atol=1e-12)
-    rgb = ctx.train_render_forward(0, p["o"], p["d"], *_draws(p))
+    rgb = ctx.train_render_forward(0, p["o"], p["d"], *R.draws(p))
     np.testing.assert_array_equal(rgb, out["rgb"].detach().cpu().numpy())
     gc0, gf0 = ctx.train_render_backward(0, d_rgb)
     np.testing.assert_array_equal(gc, gc0)
@@ -422,7 +373,7 @@ def test_train_step_custom_reduces_a_depth_loss(oracle, golden_ckpt, capsys):
                float(golden_ckpt["far"]))
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     m.compile(2e-5)
-    o, d, rng = _rays(oracle, 48, 0)
+    o, d, rng = S.oracle_rays(oracle, 48, 0)
     dev = lambda a: torch.as_tensor(a, device="cuda")                                              # noqa: E731
     o, d, tgt = dev(o), dev(d), dev(rng.random((48, 3), dtype=np.float32))
     u_c, u_f = dev(rng.random((48, 16), dtype=np.float32)), dev(rng.random((48, 24), dtype=np.float32))

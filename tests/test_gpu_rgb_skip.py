@@ -9,6 +9,7 @@ import pytest
 
 import bench
 import occupancy_ref as G
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +21,11 @@ C2W = bench.sphere_matrix(1.0, -30.0, 45.0, 0.0)
 SLABS = [min(int(b), H * W - 400) for b in np.linspace(0, H * W - 128, 8)]
 
 
-def _context(blob_c=None, blob_f=None, near=bench.NEAR, far=bench.FAR):
+def _bench_context(blob_c=None, blob_f=None, near=bench.NEAR, far=bench.FAR):
+    """f16x3 on bench.py's bounds; a blob that is not given is bench.py's Glorot blob of that network."""
     import nerf_and_dietnerf_amd as N
-    ctx = N.Context(near=near, far=far, precision="f16x3")
-    ctx.load_weights(0, N.glorot_blob(0) if blob_c is None else blob_c)
-    ctx.load_weights(1, N.glorot_blob(1) if blob_f is None else blob_f)
-    return ctx
-
-
-def _same_bits(a, b, label):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    assert a.shape == b.shape, label
-    diff = int(np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)))
-    assert diff == 0, (label, diff, float(np.nanmax(np.abs(a - b))))
+    pair = (N.glorot_blob(0) if blob_c is None else blob_c, N.glorot_blob(1) if blob_f is None else blob_f)
+    return S.blob_context(pair, near=near, far=far)
 
 
 def _counts(ctx, which=1):
@@ -65,8 +58,8 @@ def _identity(ctx, c2w, fov, h, w, sc, sf, label, tiles=None, **kw):
     culling); -> (six-output run, tiles skipped)"""
     six, only, (ran, skipped) = _both(ctx, c2w, fov, h, w, sc, sf, **kw)
     assert np.isfinite(six[0]).all(), label
-    _same_bits(only[0], six[0], label + ": rgb")
-    _same_bits(only[6], six[6], label + ": depth")
+    S.assert_same_bits(only[0], six[0], label + ": rgb")
+    S.assert_same_bits(only[6], six[6], label + ": depth")
     rays = kw.get("count") or h * w
     want = -(-rays * (sc + sf) // 128) if tiles is None else tiles
     assert ran == want if want is not None and want >= 0 else ran > 0, (label, "tiles of the rgb-skipping kernel", ran, want)
@@ -84,7 +77,7 @@ def _empty_groups(alpha):
 def test_mixed_groups_are_bit_identical():
     """400-ray slabs of the bench frame: 76 800 fine rows = 600 groups over at most 256 workgroups, so every workgroup runs two
     or three tiles and skipped and computed tiles follow each other either way round."""
-    ctx = _context()
+    ctx = _bench_context()
     try:
         empty = []
         for b in SLABS:
@@ -105,7 +98,7 @@ def test_mixed_groups_are_bit_identical():
 @pytest.mark.parametrize("n_side,sc,sf", [((37, 1), 8, 16), ((3, 1), 2, 3)])
 def test_ragged_shapes(n_side, sc, sf):
     """37 rays x (8+16): M = 888 is no multiple of 128, S none of 32, the last group has invalid lanes; 3 rays x (2+3)."""
-    ctx = _context()
+    ctx = _bench_context()
     try:
         h, w = n_side
         _identity(ctx, C2W, bench.FOV, h, w, sc, sf, f"{h * w} rays x ({sc}+{sf})")
@@ -119,7 +112,7 @@ def test_all_empty_and_none_empty():
     for bias, label in ((-50.0, "sigma bias -50"), (1.5, "sigma bias +1.5")):
         blob = fine.copy()
         blob[-1] = bias                                    # the sigma head's bias: the blob's last element
-        ctx = _context(blob_f=blob)
+        ctx = _bench_context(blob_f=blob)
         try:
             six, skipped = _identity(ctx, C2W, bench.FOV, 24, 24, 32, 48, label)
             if bias < 0:
@@ -134,7 +127,7 @@ def test_all_empty_and_none_empty():
 def test_shipped_checkpoint(golden_ckpt):
     """24 x 24, 32+48: groups with single empty waves and no empty group."""
     g = golden_ckpt
-    ctx = _context(g["blob_coarse"], g["blob_fine"], float(g["near"]), float(g["far"]))
+    ctx = _bench_context(g["blob_coarse"], g["blob_fine"], float(g["near"]), float(g["far"]))
     try:
         _identity(ctx, g["c2w_test"], float(g["fov"]), 24, 24, 32, 48, "shipped checkpoint")
     finally:
@@ -144,7 +137,7 @@ def test_shipped_checkpoint(golden_ckpt):
 def test_per_sample_rgb_is_never_skipped():
     """A caller that asks for rgb_samples gets every sample's colour, also where alpha is 0: the six-output run's rgb_samples
     on such rows are sigmoid(model_predict's rgb) within 1e-4 (the f16x3 mode's bar on colours), not a skipped row's 0.5."""
-    ctx = _context()
+    ctx = _bench_context()
     try:
         h = w = 16
         six = ctx.render_image(C2W, bench.FOV, h, w, 0, SC, SF, seed=2)
@@ -171,21 +164,12 @@ def test_per_sample_rgb_is_never_skipped():
 def test_nonfinite_sigma_is_counted(golden_ckpt, golden_vec):
     """test_nonfinite_watch's network (layer 1 scaled beyond the fp16 range) and rays through renders that read rgb alone: a
     render_rays call (one launch of the rgb-skipping kernel), then a whole rgb_only frame."""
-    import ctypes as C
-
-    from nerf_and_dietnerf_amd import _lib
     g = golden_ckpt
     big = g["blob_coarse"].copy()
     big[33 * 256 + 256: 33 * 256 + 256 + 256 * 256] *= 3e4        # layer-1 kernel: activations ~1e5 > 65504
-    ctx = _context(big, big, float(g["near"]), float(g["far"]))
+    ctx = _bench_context(big, big, float(g["near"]), float(g["far"]))
     try:
-        o, d, z = (np.ascontiguousarray(golden_vec[k], np.float32) for k in ("rays_orig", "rays_dirs", "z_coarse"))
-        n, s = z.shape
-        rgb = np.full((n, 3), np.nan, np.float32)
-        outs = _lib.NerfOutputs()
-        outs.rgb = rgb.ctypes.data
-        _lib.check(ctx.lib.nerf_render_rays(ctx.h, 0, o.ctypes.data, d.ctypes.data, z.ctypes.data, n, s, C.byref(outs),
-                                            _lib.NERF_MEM_HOST))
+        S.render_rays(ctx, 0, golden_vec["rays_orig"], golden_vec["rays_dirs"], golden_vec["z_coarse"], ("rgb",))
         assert ctx.read_nonfinite() > 0
         ctx.render_image(g["c2w_test"], float(g["fov"]), 8, 8, 0, 16, 16, seed=1, rgb_only=True)
         assert ctx.read_nonfinite() > 0
@@ -195,7 +179,7 @@ def test_nonfinite_sigma_is_counted(golden_ckpt, golden_vec):
 
 def test_culled_launch():
     """The mode-1 launch under sample culling (tools/culling_measure.py's synthetic grid), a small frame."""
-    ctx = _context()
+    ctx = _bench_context()
     try:
         lo, hi = (-0.4, -0.4, -0.4), (0.4, 0.4, 0.4)
         grid = G.two_balls(128, np.array(lo, np.float32) * 2.5, np.array(hi, np.float32) * 2.5) | \
@@ -218,7 +202,7 @@ def test_gate_falls_back_to_the_full_kernel_and_probes_again():
     import nerf_and_dietnerf_amd as N
     blob = N.glorot_blob(1)
     blob[-1] = 1.5
-    ctx = _context(blob_f=blob)
+    ctx = _bench_context(blob_f=blob)
     try:
         tiles = 24 * 24 * 80 // 128
 
@@ -228,7 +212,7 @@ def test_gate_falls_back_to_the_full_kernel_and_probes_again():
         first = frame()
         assert _counts(ctx)[:2] == (tiles, 0)                      # ... and the read drains the stream: the copy has landed
         for _ in range(3):
-            _same_bits(frame(), first, "full kernel behind the gate")
+            S.assert_same_bits(frame(), first, "full kernel behind the gate")
         ran, skipped, full_left = _counts(ctx)
         assert (ran, skipped) == (tiles, 0) and full_left == 63 - 3, (ran, skipped, full_left)
         ctx.load_weights(1, N.glorot_blob(1))                      # new weights: the gate forgets

@@ -8,21 +8,16 @@ One case of the plan cannot exist as written: disparity sampling refuses near <=
 test_parity_end_to_end therefore asserts that refusal for "use_ndc + lindisp at bounds (0, 1)" and runs the end-to-end
 comparison for use_ndc at (0, 1) with linear depths (the NDC configuration) and for use_ndc + lindisp at (2^-4, 1), the same
 case with the near bound lifted off zero."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from occupancy_ref import NDC_NEAR       # 0.5; the rig's own near bound is 0.56 (tests/golden/alexander50_epoch095.npz)
 import sampling_space_ref as R
+import support as S
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 IMAGES = [(8, 8), (16, 24), (24, 16)]            # (h, w): 8 x 8, 24 x 16 and 16 x 24 pixels
-NDC_NEAR = 0.5                                   # the rig's own near bound is 0.56 (tests/golden/alexander50_epoch095.npz)
 LINDISP_MESSAGE = "lindisp needs near_boundary > 0"
 
 
@@ -285,10 +280,10 @@ def test_parity_end_to_end(oracle, rig, blobs, precision, capsys):
     h, w = IMAGES[1]
     rc = {"n_render_samples_coarse": 64, "n_render_samples_fine": 128, "use_ndc": True, "ndc_near_plane": NDC_NEAR}
     with pytest.raises(RuntimeError, match=LINDISP_MESSAGE):
-        N.NeRF(NET, dict(rc, lindisp=True), 0.0, 1.0, precision=precision)
+        N.NeRF(S.NET, dict(rc, lindisp=True), 0.0, 1.0, precision=precision)
     for lindisp, near, far in ((False, 0.0, 1.0), (True, 2.0 ** -4, 1.0)):
         u_c, u_f, ref, ref_z = _parity_reference(oracle, rig, blobs, lindisp, near, far)
-        model = N.NeRF(NET, dict(rc, lindisp=lindisp), near, far, precision=precision)
+        model = N.NeRF(S.NET, dict(rc, lindisp=lindisp), near, far, precision=precision)
         model.set_weights(*blobs)
         out = model.render_image(poses[1], fov, h, w, u_coarse=u_c, u_fine=u_f)
         err = float(np.abs(out[0].reshape(-1, 3) - ref).max())
@@ -301,15 +296,6 @@ def test_parity_end_to_end(oracle, rig, blobs, precision, capsys):
 
 
 # ---- 6. training follows the mode ----------------------------------------------------------------------------------------
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a, b = a.astype(np.float64), b.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
 def test_train_gradients_follow_the_sampling_mode(oracle, rig, golden_ckpt, policy, capsys):
     """One train_gradients call in lindisp mode with draws u against one in linear mode with the draws
@@ -344,11 +330,11 @@ def test_train_gradients_follow_the_sampling_mode(oracle, rig, golden_ckpt, poli
     (m0, gc0, gf0), (m1, gc1, gf1) = res["lindisp"], res["linear"]
     with capsys.disabled():
         print(f"\n[{policy}] lindisp vs linear on the same depths: loss {m0['loss']:.7f} / {m1['loss']:.7f}, gradients "
-              f"{_relerr(gc0, gc1):.2e} (coarse), {_relerr(gf0, gf1):.2e} (fine) of max|g|", end="")
+              f"{S.relerr(gc0, gc1):.2e} (coarse), {S.relerr(gf0, gf1):.2e} (fine) of max|g|", end="")
     assert np.isfinite(gc0).all() and np.isfinite(gf0).all()
     assert abs(m0["loss"] - m1["loss"]) <= (2e-3 if mixed else 2e-6) * m1["loss"]
-    assert _relerr(gc0, gc1) <= 5e-2 and _cos(gc0, gc1) > 0.999
-    assert _relerr(gf0, gf1) <= 5e-2 and _cos(gf0, gf1) > 0.999
+    assert S.relerr(gc0, gc1) <= 5e-2 and S.cos(gc0, gc1) > 0.999
+    assert S.relerr(gf0, gf1) <= 5e-2 and S.cos(gf0, gf1) > 0.999
     # and the mode matters: linear depths on the lindisp draws are another problem
     ctx = _ctx((golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"]), near=near, far=far)
     ctx.train_begin(5e-4, mixed_float16=mixed)
@@ -363,7 +349,7 @@ def test_use_ndc_dataset_holds_the_ndc_rays(rig):
     import nerf_and_dietnerf_amd as N
     poses, fov = rig
     images = np.random.default_rng(8).random((2, 8, 8, 3), dtype=np.float32)
-    model = N.NeRF(NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 8, "use_ndc": True, "ndc_near_plane": NDC_NEAR},
+    model = N.NeRF(S.NET, {"n_render_samples_coarse": 8, "n_render_samples_fine": 8, "use_ndc": True, "ndc_near_plane": NDC_NEAR},
                    0.0, 1.0, precision="fp32")
     assert model.ctx.ray_space == "ndc" and model.ctx.sampling == "linear"
     ds = N.prepare_ds(32, poses[:2], images, fov, model.ctx)
@@ -387,28 +373,16 @@ def test_use_ndc_dataset_holds_the_ndc_rays(rig):
 # ---- 7. sharded render ---------------------------------------------------------------------------------------------------
 def _rank_main(rank, world, p, id_path, q):
     try:
-        import time
         import nerf_and_dietnerf_amd as N
         ctx = N.Context(near=0.0, far=1.0, precision="fp32")
         ctx.load_weights(0, p["blobs"][0])
         ctx.load_weights(1, p["blobs"][1])
         ctx.set_ray_space("ndc", NDC_NEAR)
-        if rank == 0:
-            with open(id_path + ".tmp", "wb") as f:
-                f.write(N.Context.comm_unique_id())
-            os.replace(id_path + ".tmp", id_path)
-        t0 = time.time()
-        while not os.path.exists(id_path):
-            time.sleep(0.02)
-            if time.time() - t0 > 120:
-                raise TimeoutError("rank 0 never published the communicator id")
-        with open(id_path, "rb") as f:
-            ctx.comm_init(f.read(), rank, world)
+        ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
         h, w = p["hw"]
         img = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5)
         six = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5, outputs="all")
-        with open("/proc/self/maps") as f:
-            assert "libstub_rccl.so" in f.read()
+        S.assert_stand_in_loaded()
         ctx.comm_destroy()
         q.put((rank, (img, six[5])))
     except BaseException as e:
@@ -420,12 +394,8 @@ def _rank_main(rank, world, p, id_path, q):
 def test_sharded_render_in_ndc_mode(rig, blobs, tmp_path):
     """nerf_render_image_sharded over two ranks (the test-only RCCL stand-in, tests/stub_rccl.c) on NDC contexts == the one-rank
     image, bit for bit: the slabs go through the same raygen -> rays_to_ndc as nerf_render_image."""
-    import torch.multiprocessing as mp
     poses, fov = rig
     h, w = 7, 13                                                  # 91 rays: the second slab is one ray short
-    stub = tmp_path / "libstub_rccl.so"
-    subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "stub_rccl.c"),
-                    "-o", str(stub), "-L/opt/rocm/lib", "-lamdhip64", "-lrt"], check=True)
     one = _ctx(blobs, near=0.0, far=1.0)
     one.set_ray_space("ndc", NDC_NEAR)
     want = one.render_image(poses[0], fov, h, w, 0, 16, 24, seed=5)
@@ -433,26 +403,7 @@ def test_sharded_render_in_ndc_mode(rig, blobs, tmp_path):
     assert not np.array_equal(want[0], world_img)                 # NDC mode is not a no-op
     one.close()
     p = dict(blobs=blobs, c2w=poses[0], fov=fov, hw=(h, w))
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    id_path = str(tmp_path / "comm_id")
-    old = os.environ.get("NERF_RCCL_LIB")
-    os.environ["NERF_RCCL_LIB"] = str(stub)                        # inherited by the ranks
-    try:
-        procs = [mpc.Process(target=_rank_main, args=(r, 2, p, id_path, q)) for r in range(2)]
-        for pr in procs:
-            pr.start()
-    finally:
-        if old is None:
-            os.environ.pop("NERF_RCCL_LIB", None)
-        else:
-            os.environ["NERF_RCCL_LIB"] = old
-    res = [q.get(timeout=300) for _ in procs]
-    for pr in procs:
-        pr.join(timeout=60)
-    for _, r in res:
-        if isinstance(r, BaseException):
-            raise r
-    for _, (img, z) in res:
+    res = S.run_ranks(_rank_main, 2, (p, str(tmp_path / "comm_id")), S.build_stub_rccl(tmp_path), timeout=300)
+    for img, z in res:
         np.testing.assert_array_equal(img, want[0])
         np.testing.assert_array_equal(z, want[5])

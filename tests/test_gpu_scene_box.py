@@ -3,30 +3,25 @@
 form, the trainer under both policies and the kept-activation slots.  The rule and its float32 restatement live in
 tests/scene_box_ref.py; the CPU oracle is used unchanged, through the entries it has for given rays and depths.  Every test
 here needs the three entry points this adds to the ABI."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from occupancy_ref import NDC_BOX, NDC_NEAR
 import sampling_space_ref as R
 import scene_box_ref as B
+import support as S
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 LINDISP_MESSAGE = "lindisp needs near_boundary > 0"
 BOX_MESSAGE = "scene box needs finite lo < hi on every axis"
 NEAR, FAR = B.NEAR, B.FAR
 SAMPLES = (1, 2, 5, 64)
 FAR_AWAY = ((50.0, 50.0, 50.0), (51.0, 51.0, 51.0))        # a box no ray of these tests hits
 HUGE = ((-100.0,) * 3, (100.0,) * 3)                       # a box that contains every [near, far]
-# the golden scene's content lies about here (cameras near the unit sphere, near 0.56, far 2.56)
-GOLDEN_BOX = ((-0.3, 0.0, -1.0), (0.1, 0.5, -0.7))
-NDC_NEAR = 0.5
-NDC_BOX = ((-0.5, -0.4, -0.6), (0.5, 0.4, 0.4))            # NDC rays run from z = -1 (t = 0) to z = +1 (t = 1)
+# the golden scene's content lies about here (cameras near the unit sphere, near 0.56, far 2.56); tighter than, and not to be
+# replaced by, occupancy_ref.GOLDEN_BOX: the training tests need rays that miss it
+TRAIN_BOX = ((-0.3, 0.0, -1.0), (0.1, 0.5, -0.7))
 
 
 @pytest.fixture(scope="module")
@@ -257,7 +252,7 @@ def test_parity_end_to_end(oracle, blobs, precision, lindisp, capsys):
     u_c, u_f, ref, ref_z, hit, narrowed = _parity_reference(oracle, blobs, lindisp)
     assert narrowed.sum() >= h * w // 8 and (~hit).sum() >= h * w // 8
     rc = {"n_render_samples_coarse": 64, "n_render_samples_fine": 128, "scene_box": [B.LO.tolist(), B.HI.tolist()], "lindisp": lindisp}
-    model = N.NeRF(NET, rc, NEAR, FAR, precision=precision)
+    model = N.NeRF(S.NET, rc, NEAR, FAR, precision=precision)
     assert model.ctx.scene_box == (tuple(B.LO.tolist()), tuple(B.HI.tolist()))
     model.set_weights(*blobs)
     out = model.render_image(_camera(oracle), IMAGE_FOV, h, w, u_coarse=u_c, u_fine=u_f)
@@ -280,7 +275,7 @@ def test_render_image_in_ndc_mode_clips_the_ndc_rays(blobs):
     (h, w), sc, sf, seed = (16, 24), 16, 24, 5
     rc = {"n_render_samples_coarse": sc, "n_render_samples_fine": sf, "use_ndc": True, "ndc_near_plane": NDC_NEAR,
           "scene_box": [list(NDC_BOX[0]), list(NDC_BOX[1])]}
-    model = N.NeRF(NET, rc, 0.0, 1.0, precision="fp32")
+    model = N.NeRF(S.NET, rc, 0.0, 1.0, precision="fp32")
     model.set_weights(*blobs)
     ndc = model.ctx
     plain = _ctx(blobs, near=0.0, far=1.0, box=NDC_BOX)
@@ -308,22 +303,13 @@ def test_render_image_in_ndc_mode_clips_the_ndc_rays(blobs):
 
 
 # ---- 7. training follows the box ---------------------------------------------------------------------------------------------------
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a, b = a.astype(np.float64), b.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 def _golden_rays(oracle, golden_ckpt, n, seed):
-    """n rays of the golden checkpoint's training camera (8 x 8 pixels), its bounds, and the reference's verdict under GOLDEN_BOX."""
+    """n rays of the golden checkpoint's training camera (8 x 8 pixels), its bounds, and the reference's verdict under TRAIN_BOX."""
     near, far = float(golden_ckpt["near"]), float(golden_ckpt["far"])
     o, d = R.world_rays(oracle, golden_ckpt["c2w_train"], float(golden_ckpt["fov"]), 8, 8)
     idx = np.random.default_rng(seed).choice(64, n, replace=False)
     o, d = o[idx], np.ascontiguousarray(d[idx])
-    _, _, hit, narrowed = B.ray_box_interval(o, d, *GOLDEN_BOX, near, far)
+    _, _, hit, narrowed = B.ray_box_interval(o, d, *TRAIN_BOX, near, far)
     assert narrowed.sum() >= n // 4 and (~hit).sum() >= n // 4
     return o, d, near, far
 
@@ -343,7 +329,7 @@ def test_train_gradients_follow_the_box(oracle, golden_ckpt, policy, capsys):
     w = (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     res = {}
     for mode in ("box", "substituted", "plain"):
-        ctx = _ctx(w, near=near, far=far, box=GOLDEN_BOX if mode == "box" else None)
+        ctx = _ctx(w, near=near, far=far, box=TRAIN_BOX if mode == "box" else None)
         if mode == "box":
             z_box = ctx.get_z_values_for_rays(o, d, sc, uniform_values=u_c)
             u = u_c
@@ -361,11 +347,11 @@ def test_train_gradients_follow_the_box(oracle, golden_ckpt, policy, capsys):
     (m0, gc0, gf0), (m1, gc1, gf1), (m2, _, _) = res["box"], res["substituted"], res["plain"]
     with capsys.disabled():
         print(f"\n[{policy}] box vs no box on the same depths: loss {m0['loss']:.7f} / {m1['loss']:.7f} (no box, same draws: "
-              f"{m2['loss']:.7f}), gradients {_relerr(gc0, gc1):.2e} (coarse), {_relerr(gf0, gf1):.2e} (fine) of max|g|", end="")
+              f"{m2['loss']:.7f}), gradients {S.relerr(gc0, gc1):.2e} (coarse), {S.relerr(gf0, gf1):.2e} (fine) of max|g|", end="")
     assert np.isfinite(gc0).all() and np.isfinite(gf0).all()
     assert abs(m0["loss"] - m1["loss"]) <= (2e-3 if mixed else 2e-6) * m1["loss"]
-    assert _relerr(gc0, gc1) <= 5e-2 and _cos(gc0, gc1) > 0.999
-    assert _relerr(gf0, gf1) <= 5e-2 and _cos(gf0, gf1) > 0.999
+    assert S.relerr(gc0, gc1) <= 5e-2 and S.cos(gc0, gc1) > 0.999
+    assert S.relerr(gf0, gf1) <= 5e-2 and S.cos(gf0, gf1) > 0.999
     assert abs(m2["loss"] - m0["loss"]) > 1e-4 * m0["loss"]                      # and the box matters
 
 
@@ -378,7 +364,7 @@ def test_a_slot_keeps_the_depths_it_drew(oracle, golden_ckpt):
     rng = np.random.default_rng(9)
     d_rgb = (rng.random((n, 3), dtype=np.float32) - 0.5) / n
     w = (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
-    ctx = _ctx(w, near=near, far=far, box=GOLDEN_BOX)
+    ctx = _ctx(w, near=near, far=far, box=TRAIN_BOX)
     ctx.train_begin(5e-4)
     rgb, gc, gf = ctx.train_render_gradients(o, d, d_rgb, sc, sf, seed=7, ray_base=11)
     rgb_slot = ctx.train_render_forward(0, o, d, sc, sf, seed=7, ray_base=11)
@@ -397,28 +383,16 @@ def test_a_slot_keeps_the_depths_it_drew(oracle, golden_ckpt):
 # ---- 9. sharded render -------------------------------------------------------------------------------------------------------------
 def _rank_main(rank, world, p, id_path, q):
     try:
-        import time
         import nerf_and_dietnerf_amd as N
         ctx = N.Context(near=NEAR, far=FAR, precision="fp32")
         ctx.load_weights(0, p["blobs"][0])
         ctx.load_weights(1, p["blobs"][1])
         ctx.set_scene_box(*p["box"])
-        if rank == 0:
-            with open(id_path + ".tmp", "wb") as f:
-                f.write(N.Context.comm_unique_id())
-            os.replace(id_path + ".tmp", id_path)
-        t0 = time.time()
-        while not os.path.exists(id_path):
-            time.sleep(0.02)
-            if time.time() - t0 > 120:
-                raise TimeoutError("rank 0 never published the communicator id")
-        with open(id_path, "rb") as f:
-            ctx.comm_init(f.read(), rank, world)
+        ctx.comm_init(S.exchange_comm_id(N, rank, id_path), rank, world)
         h, w = p["hw"]
         img = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5)
         six = ctx.render_image_sharded(p["c2w"], p["fov"], h, w, 0, 16, 24, seed=5, outputs="all")
-        with open("/proc/self/maps") as f:
-            assert "libstub_rccl.so" in f.read()
+        S.assert_stand_in_loaded()
         ctx.comm_destroy()
         q.put((rank, (img, six[5])))
     except BaseException as e:
@@ -430,38 +404,15 @@ def _rank_main(rank, world, p, id_path, q):
 def test_sharded_render_with_a_box(oracle, blobs, tmp_path):
     """nerf_render_image_sharded over two ranks (the test-only RCCL stand-in, tests/stub_rccl.c) on contexts with a box == the
     one-context image, bit for bit."""
-    import torch.multiprocessing as mp
     h, w = 7, 13                                                  # 91 rays: the second slab is one ray short
     c2w = _camera(oracle)
-    stub = tmp_path / "libstub_rccl.so"
-    subprocess.run(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "stub_rccl.c"),
-                    "-o", str(stub), "-L/opt/rocm/lib", "-lamdhip64", "-lrt"], check=True)
     one = _ctx(blobs, box=(B.LO, B.HI))
     want = one.render_image(c2w, IMAGE_FOV, h, w, 0, 16, 24, seed=5)
     one.set_scene_box(None)
     assert not np.array_equal(want[5], one.render_image(c2w, IMAGE_FOV, h, w, 0, 16, 24, seed=5)[5])    # the box is not a no-op
     one.close()
     p = dict(blobs=blobs, c2w=c2w, fov=IMAGE_FOV, hw=(h, w), box=(B.LO.tolist(), B.HI.tolist()))
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    id_path = str(tmp_path / "comm_id")
-    old = os.environ.get("NERF_RCCL_LIB")
-    os.environ["NERF_RCCL_LIB"] = str(stub)                        # inherited by the ranks
-    try:
-        procs = [mpc.Process(target=_rank_main, args=(r, 2, p, id_path, q)) for r in range(2)]
-        for pr in procs:
-            pr.start()
-    finally:
-        if old is None:
-            os.environ.pop("NERF_RCCL_LIB", None)
-        else:
-            os.environ["NERF_RCCL_LIB"] = old
-    res = [q.get(timeout=300) for _ in procs]
-    for pr in procs:
-        pr.join(timeout=60)
-    for _, r in res:
-        if isinstance(r, BaseException):
-            raise r
-    for _, (img, z) in res:
+    res = S.run_ranks(_rank_main, 2, (p, str(tmp_path / "comm_id")), S.build_stub_rccl(tmp_path), timeout=300)
+    for img, z in res:
         np.testing.assert_array_equal(img, want[0])
         np.testing.assert_array_equal(z, want[5])

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import grad_blocks as GB
+import support as S
 
 pytestmark = pytest.mark.gpu
 
@@ -33,60 +34,20 @@ BLOCKS = GB.blocks(5, 4, 2)
 # blob-wide bar (5e-2 of the blob max), and every block above L is asserted at the oracle-derived bar.
 
 
-def _f32(fn, *a, **kw):
-    """The same oracle call in float32: the reference's own rounding, the yardstick of the block-wise bars."""
-    import torch
-    return fn(*a, dtype=torch.float32, **kw)
-
-
-def _rays(oracle, n, seed=0, hw=8):
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(hw, hw, 0.46, c2w).reshape(-1, 4)
-    idx = rng.choice(d.shape[0], n, replace=n > d.shape[0])
-    return np.tile(c2w[:, 3], (n, 1)).astype(np.float32), np.ascontiguousarray(d[idx]), rng
-
-
-def _problem(oracle, golden_ckpt, n=48, sc=16, sf=24, seed=0):
-    o, d, rng = _rays(oracle, n, seed)
-    return dict(o=o, d=d, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
-                tgt=rng.random((n, 3), dtype=np.float32), sc=sc, sf=sf, near=float(golden_ckpt["near"]),
-                far=float(golden_ckpt["far"]), bc=golden_ckpt["blob_coarse"], bf=golden_ckpt["blob_fine"])
-
-
-def _ctx(p, fine=True, **kw):
-    import nerf_and_dietnerf_amd as N
-    kw.setdefault("precision", "fp32")      # the render checks of this file compare against the exact-fp32 mode
-    ctx = N.Context(near=p["near"], far=p["far"], **kw)
-    ctx.load_weights(0, p["bc"])
-    if fine:
-        ctx.load_weights(1, p["bf"])
-    return ctx
-
-
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a = a.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 def test_gradients_coarse_only(oracle, golden_ckpt, capsys):
     """No fine network (n_render_samples_fine == 0, src/NeRF.py:36-39,153): loss = coarse MSE alone.  No sampler term either:
     every block of the coarse gradient at the alpha = 0.05 bar (relative L2, 16 x the float32 oracle's)."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt)
-    ctx = _ctx(p, fine=False)
+    p = S.golden_problem(oracle, golden_ckpt)
+    ctx = S.golden_context(p, fine=False)
     ctx.train_begin(5e-4)
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], 0, p["u_c"])
     r = T.train_gradients(p["bc"], None, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], None)
     assert gf is None and "psnr_fine" not in m
     assert abs(m["loss"] - r["loss"]) <= 1e-6 * r["loss"] + 1e-7
     assert abs(m["psnr_coarse"] - r["psnr_coarse"]) <= 1e-4
-    assert _relerr(gc, r["grad_coarse"]) <= 1e-2 and _cos(gc, r["grad_coarse"]) > 0.9999
-    r32 = _f32(T.train_gradients, p["bc"], None, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], None)
+    assert S.relerr(gc, r["grad_coarse"]) <= 1e-2 and S.cos(gc, r["grad_coarse"]) > 0.9999
+    r32 = S.f32(T.train_gradients, p["bc"], None, p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], None)
     with capsys.disabled():
         GB.check_fp32_masks(gc, r["grad_coarse"], r32["grad_coarse"], BLOCKS, "[coarse only, alpha 0.05] coarse")
     ctx.close()
@@ -105,8 +66,8 @@ def test_gradients_coarse_and_fine(oracle, golden_ckpt, sampler_gradient, alpha,
     Block by block: alpha = 1 at 2e-4 of each block's own max; alpha = 0.05 by relative L2 at 16 x the float32 oracle's, on
     the fine network and -- where the sampler term, which one fine-pass flip moves by ~1/N, is off -- on the coarse one."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt)
-    ctx = _ctx(p, leaky_relu_alpha=alpha)
+    p = S.golden_problem(oracle, golden_ckpt)
+    ctx = S.golden_context(p, leaky_relu_alpha=alpha)
     ctx.train_begin(5e-4, sampler_gradient=sampler_gradient)
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     r = T.train_gradients(p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
@@ -115,9 +76,9 @@ def test_gradients_coarse_and_fine(oracle, golden_ckpt, sampler_gradient, alpha,
     assert abs(m["psnr_coarse"] - r["psnr_coarse"]) <= 1e-4 and abs(m["psnr_fine"] - r["psnr_fine"]) <= 1e-4
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
     tol, cos_min = (2e-4, 0.9999999) if alpha == 1.0 else (5e-2, 0.999)
-    assert _relerr(gc, r["grad_coarse"]) <= tol and _cos(gc, r["grad_coarse"]) > cos_min
-    assert _relerr(gf, r["grad_fine"]) <= tol and _cos(gf, r["grad_fine"]) > cos_min
-    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+    assert S.relerr(gc, r["grad_coarse"]) <= tol and S.cos(gc, r["grad_coarse"]) > cos_min
+    assert S.relerr(gf, r["grad_fine"]) <= tol and S.cos(gf, r["grad_fine"]) > cos_min
+    r32 = S.f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                sampler_grad=sampler_gradient, alpha=alpha)
     tag = f"[48 x (16+24), alpha {alpha:g}, sampler term {'on' if sampler_gradient else 'off'}]"
     with capsys.disabled():
@@ -145,8 +106,8 @@ def test_gradients_with_a_wide_dynamic_range_between_rays(oracle, golden_ckpt, p
     the loss scale), the rendered colour itself for a third of the rays (loss gradients orders of magnitude below the rest),
     ordinary for the others.  Same bars as the ordinary batch (alpha = 1: the smooth network)."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt, n=48, sc=16, sf=24, seed=9)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    p = S.golden_problem(oracle, golden_ckpt, n=48, sc=16, sf=24, seed=9)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     rgb = ctx.render(p["o"], p["d"], p["sc"], p["sf"], p["u_c"], p["u_f"])[0]
     tgt = p["tgt"].copy()
     mixed = policy == "mixed_float16"
@@ -157,7 +118,7 @@ def test_gradients_with_a_wide_dynamic_range_between_rays(oracle, golden_ckpt, p
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], tgt, p["sc"], p["sf"], p["u_c"], p["u_f"])
     r = T.train_gradients(p["bc"], p["bf"], p["o"], p["d"], tgt, p["near"], p["far"], p["u_c"], p["u_f"], alpha=1.0,
                           fp16_loss_scale=32768.0 if mixed else None)
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[{policy}, two rays far off, a third of the rays at their own rendered colour] vs "
               f"{'the fp16-emulating' if mixed else 'float64'} autograd: coarse {ec:.2e}, fine {ef:.2e} of max|g|", end="")
@@ -165,7 +126,7 @@ def test_gradients_with_a_wide_dynamic_range_between_rays(oracle, golden_ckpt, p
     assert abs(m["loss"] - r["loss"]) <= (2e-3 if mixed else 2e-6) * r["loss"]
     tol = 2e-2 if mixed else 2e-4
     assert ec <= tol and ef <= tol, (ec, ef)
-    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], tgt, p["near"], p["far"], p["u_c"], p["u_f"], alpha=1.0,
+    r32 = S.f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], tgt, p["near"], p["far"], p["u_c"], p["u_f"], alpha=1.0,
                fp16_loss_scale=32768.0 if mixed else None)
     with capsys.disabled():
         for net, g in (("coarse", gc), ("fine", gf)):
@@ -182,7 +143,7 @@ def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt, capsys):
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     n, sc, sf, seed = 37, 11, 19, 1234
-    o, d, rng = _rays(oracle, n, 3)
+    o, d, rng = S.oracle_rays(oracle, n, 3)
     tgt = rng.random((n, 3), dtype=np.float32)
     kw = dict(n_pos_enc_xyz=5, n_pos_enc_dir=4, n_angles=1)
     bc, bf = N.glorot_blob(1, **kw), N.glorot_blob(2, **kw)
@@ -199,12 +160,12 @@ def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt, capsys):
     u_f = oracle.philox_uniform(seed, ray, sf, 1)
     r = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=1)
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
-    assert _relerr(gc, r["grad_coarse"]) <= 5e-2 and _cos(gc, r["grad_coarse"]) > 0.999
-    assert _relerr(gf, r["grad_fine"]) <= 5e-2 and _cos(gf, r["grad_fine"]) > 0.999
+    assert S.relerr(gc, r["grad_coarse"]) <= 5e-2 and S.cos(gc, r["grad_coarse"]) > 0.999
+    assert S.relerr(gf, r["grad_fine"]) <= 5e-2 and S.cos(gf, r["grad_fine"]) > 0.999
     # Block by block (fine network, alpha 0.05, relative L2 at 16 x the float32 oracle's largest = 3.7e-3): one mask flip in
     # layer 0 (see the note at the top of this file) -- k0 4.3e-3, b0 3.9e-3, every block of layers 1..10 under the bar -- so
     # k0 and b0 keep the blob-wide 5e-2 and the other 26 blocks, the sigma head and the row groups included, are asserted.
-    r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=1)
+    r32 = S.f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=1)
     blks = GB.blocks(5, 4, 1)
     with capsys.disabled():
         GB.check_fp32_masks(gf, r["grad_fine"], r32["grad_fine"], blks, "[37 x (11+19), device RNG, n_angles 1] fine",
@@ -215,8 +176,8 @@ def test_gradients_device_rng_and_odd_sizes(oracle, golden_ckpt, capsys):
 def test_adam_update_matches_keras_formula(oracle, golden_ckpt):
     """nerf_train_apply on caller-supplied gradients == Keras-2.7 Adam (oracle.adam_update), three steps."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt)
-    ctx = _ctx(p)
+    p = S.golden_problem(oracle, golden_ckpt)
+    ctx = S.golden_context(p)
     lr = 5e-4
     ctx.train_begin(lr)
     rng = np.random.default_rng(5)
@@ -241,9 +202,9 @@ def test_train_steps_reduce_loss_and_render_sees_new_weights(oracle, golden_ckpt
     """A few optimizer steps on a fixed batch lower the loss; the render path then uses the trained weights
     (operand streams re-packed lazily) and agrees with the oracle run on nerf_get_weights()."""
     import nerf_and_dietnerf_amd as N
-    p = _problem(oracle, golden_ckpt, n=64, sc=16, sf=24, seed=2)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=16, sf=24, seed=2)
     p["tgt"][:] = np.array([0.9, 0.2, 0.1], np.float32)
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4)
     losses = [ctx.train_step(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])["loss"]
               for _ in range(25)]
@@ -271,7 +232,7 @@ def test_render_between_steps_uses_device_repacked_streams(oracle, golden_ckpt, 
     current (a second trainer starts from the trained weights) and so does a nerf_train_begin that restarts a running
     trainer."""
     import nerf_and_dietnerf_amd as N
-    p = _problem(oracle, golden_ckpt, n=64, sc=12, sf=20, seed=6)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=12, sf=20, seed=6)
     if n_angles == 2:
         bc, bf = p["bc"], p["bf"]
     else:
@@ -336,7 +297,7 @@ def test_nerf_mirror_train_step_and_full_batch_timing(oracle, golden_ckpt, capsy
     m = N.NeRF(net_cfg, ren_cfg, float(golden_ckpt["near"]), float(golden_ckpt["far"]))
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     m.compile(5e-4)
-    o, d, rng = _rays(oracle, 4096, 7, hw=64)
+    o, d, rng = S.oracle_rays(oracle, 4096, 7, hw=64)
     tgt = rng.random((4096, 3), dtype=np.float32)
     first = m.train_step((o, d, tgt))
     assert set(first) == {"loss", "psnr_coarse", "psnr_fine"} and math.isfinite(first["loss"])
@@ -417,7 +378,7 @@ def _dp_rank(rank, world, port, prob, q):
                                         prob["u_c"][sl], prob["u_f"][sl])
         gc, gf = N.allreduce_mean(gc), N.allreduce_mean(gf)
         ctx.train_apply(gc, gf)
-        q.put((rank, gc, gf, ctx.get_weights(0)))
+        q.put((rank, (gc, gf, ctx.get_weights(0))))
         ctx.close()
     finally:
         dist.destroy_process_group()
@@ -427,29 +388,17 @@ def test_data_parallel_gradients_equal_full_batch(oracle, golden_ckpt):
     """Two ranks (gloo, sharing this box's GPU), half the batch each, one all-reduce per gradient blob: the
     averaged gradients equal the single-process full-batch gradients (MSE is a mean over rays) and both ranks
     end the step with identical weights."""
-    import socket
-    import torch.multiprocessing as mp
-    p = _problem(oracle, golden_ckpt, n=64, sc=16, sf=24, seed=4)
-    ctx = _ctx(p)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=16, sf=24, seed=4)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4)
     _, gc_full, gf_full = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     ctx.close()
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    procs = [mpc.Process(target=_dp_rank, args=(r, 2, port, p, q)) for r in range(2)]
-    for pr in procs:
-        pr.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
-    for pr in procs:
-        pr.join(timeout=60)
-    for rank, gc, gf, w in res:
-        assert _relerr(gc, gc_full) <= 1e-5 and _relerr(gf, gf_full) <= 1e-5, rank
+    res = S.run_ranks(_dp_rank, 2, (S.free_port(), p), timeout=300)
+    for rank, (gc, gf, w) in enumerate(res):
+        assert S.relerr(gc, gc_full) <= 1e-5 and S.relerr(gf, gf_full) <= 1e-5, rank
         GB.check_equal(gc, gc_full, BLOCKS, 1e-5, f"rank {rank}, coarse")
         GB.check_equal(gf, gf_full, BLOCKS, 1e-5, f"rank {rank}, fine")
-    np.testing.assert_array_equal(res[0][3], res[1][3])
+    np.testing.assert_array_equal(res[0][2], res[1][2])
 
 
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
@@ -473,7 +422,7 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
     # (6 rays at the reference's 64 + 128 samples: nearly transparent rays whose colour gradient vanishes while the density
     # gradient does not -- the case that overflowed the fp16 packing of the sigma term before its scale was fixed)
     for n, sc, sf, seed in ((40, 12, 20, 6), (6, 64, 128, 7)):
-        o, d, rng = _rays(oracle, n, seed)
+        o, d, rng = S.oracle_rays(oracle, n, seed)
         tgt = rng.random((n, 3), dtype=np.float32)
         u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
         for alpha, tol, cmin in ((1.0, 2e-4, 0.9999999), (0.05, 5e-2, 0.999)):
@@ -484,21 +433,21 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
             m, gc, gf = ctx.train_gradients(o, d, tgt, sc, sf, u_c, u_f)
             r = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha)
             assert np.isfinite(gc).all() and np.isfinite(gf).all()
-            ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+            ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
             if mixed:
                 r16 = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha,
                                         fp16_loss_scale=32768.0)
-                qc, qf = _relerr(gc, r16["grad_coarse"]), _relerr(gf, r16["grad_fine"])
-                cc, cf = _cos(gc, r16["grad_coarse"]), _cos(gf, r16["grad_fine"])
+                qc, qf = S.relerr(gc, r16["grad_coarse"]), S.relerr(gf, r16["grad_fine"])
+                cc, cf = S.cos(gc, r16["grad_coarse"]), S.cos(gf, r16["grad_fine"])
                 with capsys.disabled():
                     print(f"\n[xyz-only, mixed_float16, {n} rays x ({sc}+{sf}), alpha {alpha:g}] vs float64: coarse {ec:.2e}, "
                           f"fine {ef:.2e}; vs the fp16-emulating oracle: coarse {qc:.2e}, fine {qf:.2e}, cosine {cc:.6f}, "
                           f"{cf:.6f}", end="")
                 assert abs(m["loss"] - r["loss"]) <= 1e-3 * r["loss"] and abs(m["loss"] - r16["loss"]) <= 1e-4 * r16["loss"]
-                assert _cos(gc, r["grad_coarse"]) > 0.99 and _cos(gf, r["grad_fine"]) > 0.999
+                assert S.cos(gc, r["grad_coarse"]) > 0.99 and S.cos(gf, r["grad_fine"]) > 0.999
                 if alpha == 1.0:        # the arithmetic, mask-free: measured 8.6e-4 / 4.0e-4
                     assert qc <= 5e-3 and qf <= 5e-3 and cc > 0.99999 and cf > 0.99999
-                    e32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha,
+                    e32 = S.f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha,
                                fp16_loss_scale=32768.0)
                     with capsys.disabled():
                         for net, g in (("coarse", gc), ("fine", gf)):
@@ -511,9 +460,9 @@ def test_xyz_only_network_gradients_and_steps(oracle, policy, capsys):
                     print(f"\n[xyz-only, float32 policy, {n} rays x ({sc}+{sf}), alpha {alpha:g}] vs float64: coarse {ec:.2e}, "
                           f"fine {ef:.2e}", end="")
                 assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
-                assert ec <= tol and _cos(gc, r["grad_coarse"]) > cmin
-                assert ef <= tol and _cos(gf, r["grad_fine"]) > cmin
-                r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha)
+                assert ec <= tol and S.cos(gc, r["grad_coarse"]) > cmin
+                assert ef <= tol and S.cos(gf, r["grad_fine"]) > cmin
+                r32 = S.f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, n_angles=0, alpha=alpha)
                 with capsys.disabled():
                     tag = f"[xyz-only, float32, {n} rays, alpha {alpha:g}]"
                     if alpha == 1.0:
@@ -703,7 +652,7 @@ def test_xyz_only_network_learns_the_scene(capsys, policy):
 def test_save_weights_after_training(oracle, golden_ckpt, tmp_path):
     """NeRF.save_weights after optimizer steps -> .h5 -> a second model loads it and renders the same pixels."""
     import nerf_and_dietnerf_amd as N
-    p = _problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=9)
+    p = S.golden_problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=9)
     net_cfg = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05,
                "n_pos_enc_dim_xyz": 5, "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
     ren_cfg = {"n_render_samples_coarse": 8, "n_render_samples_fine": 8}
@@ -730,22 +679,22 @@ def test_train_edge_shapes_and_transparent_scene(oracle, golden_ckpt, n, sc, sf)
     multiple of anything -- and a fully transparent coarse network (sigma = 0 everywhere: all-zero weights feed the
     sampler, every cdf bin hits the 1e-5 clamp): loss equals the oracle's, gradients are finite and close."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt, n=max(n, 2), sc=sc, sf=sf, seed=n)
+    p = S.golden_problem(oracle, golden_ckpt, n=max(n, 2), sc=sc, sf=sf, seed=n)
     o, d, tgt, u_c, u_f = (p[k][:n] for k in ("o", "d", "tgt", "u_c", "u_f"))
     for transparent in (False, True):
         bc = p["bc"].copy()
         if transparent:
             bc[-(256 + 24 + 1):] = 0.0          # sigma head kernel ...
             bc[-1] = -5.0                       # ... and a negative bias: relu -> sigma = 0
-        ctx = _ctx(dict(p, bc=bc))
+        ctx = S.golden_context(dict(p, bc=bc))
         ctx.train_begin(5e-4)
         m, gc, gf = ctx.train_gradients(o, d, tgt, sc, sf, u_c, u_f)
         r = T.train_gradients(bc, p["bf"], o, d, tgt, p["near"], p["far"], u_c, u_f)
         assert np.isfinite(gc).all() and np.isfinite(gf).all() and np.isfinite(m["loss"])
         assert abs(m["loss"] - r["loss"]) <= 5e-6 * r["loss"] + 1e-7
-        assert _relerr(gf, r["grad_fine"]) <= 5e-2
+        assert S.relerr(gf, r["grad_fine"]) <= 5e-2
         if np.abs(r["grad_coarse"]).max() > 1e-12:
-            assert _relerr(gc, r["grad_coarse"]) <= 5e-2
+            assert S.relerr(gc, r["grad_coarse"]) <= 5e-2
         else:
             assert np.abs(gc).max() <= 1e-9
         if not r["grad_coarse"].any():          # the transparent network: zero on purpose, and exactly zero block by block
@@ -759,10 +708,10 @@ def test_train_step_with_one_rank_communicator(oracle, golden_ckpt):
     """nerf_train_step under a (one-rank) RCCL communicator == without one: the in-library gradient all-reduce is a
     no-op at world 1 and must not disturb the step."""
     import nerf_and_dietnerf_amd as N
-    p = _problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=13)
+    p = S.golden_problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=13)
     res = []
     for with_comm in (False, True):
-        ctx = _ctx(p)
+        ctx = S.golden_context(p)
         if with_comm:
             ctx.comm_init(N.Context.comm_unique_id(), 0, 1)
         ctx.train_begin(5e-4)
@@ -777,7 +726,7 @@ def test_train_step_with_one_rank_communicator(oracle, golden_ckpt):
     # whenever a communicator exists -- an infinite target is skipped, the scale halves, the weights stay
     bad = p["tgt"].copy()
     bad[0, 0] = np.inf
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.comm_init(N.Context.comm_unique_id(), 0, 1)
     ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=1024.0)
     ctx.train_step(p["o"], p["d"], bad, p["sc"], p["sf"], p["u_c"], p["u_f"])
@@ -793,11 +742,11 @@ def test_mixed_policy_split_api_takes_its_verdict_on_the_applied_blobs(oracle, g
     caller all-reduces between the two).  The verdict belongs to the blobs that are APPLIED: finite local gradients
     followed by a non-finite (all-reduced) blob are skipped with a halved scale; gradients computed and never applied
     do not leak their verdict into the next step; the ctx's own blobs behave like nerf_train_step."""
-    p = _problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=14)
+    p = S.golden_problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=14)
     args = (p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     bad = p["tgt"].copy()
     bad[0, 0] = np.inf
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=1024.0)
     _, gc, gf = ctx.train_gradients(*args)
     assert np.isfinite(gc).all() and ctx.train_loss_scale() == (1024.0, 0, 0)      # no verdict yet
@@ -818,7 +767,7 @@ def test_mixed_policy_split_api_takes_its_verdict_on_the_applied_blobs(oracle, g
     assert ctx.train_loss_scale() == (256.0, 1, 2)
     np.testing.assert_array_equal(ctx.get_weights(0), w1)
     # the same two finite steps through nerf_train_step give the same weights as gradients + apply
-    ctx2 = _ctx(p)
+    ctx2 = S.golden_context(p)
     ctx2.train_begin(5e-4, mixed_float16=True, initial_loss_scale=512.0)
     ctx2.train_step(*args)
     np.testing.assert_array_equal(ctx2.get_weights(0), w1)
@@ -841,35 +790,35 @@ def test_mixed_float16_policy_gradients_and_loss_scaling(oracle, golden_ckpt, ca
       * dynamic scaling: `dynamic_growth_steps` finite steps double the scale; a batch with a non-finite target makes the
         gradients non-finite -> that step is SKIPPED (weights unchanged) and the scale halves."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt)
+    p = S.golden_problem(oracle, golden_ckpt)
     args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"])
     r = T.train_gradients(*args, sampler_grad=True, alpha=1.0)
     grads = {}
     for scale in (32768.0, 4096.0):
-        ctx = _ctx(p, leaky_relu_alpha=1.0)
+        ctx = S.golden_context(p, leaky_relu_alpha=1.0)
         ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=scale)
         m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
         grads[scale] = (gc, gf)
         assert abs(m["loss"] - r["loss"]) <= 1e-3 * r["loss"]
         assert np.isfinite(gc).all() and np.isfinite(gf).all()
-        ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
-        cc, cf = _cos(gc, r["grad_coarse"]), _cos(gf, r["grad_fine"])
+        ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
+        cc, cf = S.cos(gc, r["grad_coarse"]), S.cos(gf, r["grad_fine"])
         # ... and against the autograd oracle that rounds where the kernels round (oracle/train_oracle.py::_mlp16: fp16
         # operands, fp16 stash, row-scaled fp16 gradient operands, fp16 D carrying this loss scale).  The float64 figure
         # for the coarse network is the inverse-CDF sampler's 1e5 gain (its 1e-5 clamp) acting on the FORWARD's fp16
         # rounding -- the emulation reproduces the same 1.1e-1 against float64 -- so the emulation, which shares the
         # forward rounding, is what tests the fp16 backward chain through the sampler term.
         r16 = T.train_gradients(*args, sampler_grad=True, alpha=1.0, fp16_loss_scale=scale)
-        qc, qf = _relerr(gc, r16["grad_coarse"]), _relerr(gf, r16["grad_fine"])
+        qc, qf = S.relerr(gc, r16["grad_coarse"]), S.relerr(gf, r16["grad_fine"])
         with capsys.disabled():
             print(f"\n[mixed_float16, loss scale {scale:g}] gradients vs float64 autograd: coarse {ec:.2e}, fine {ef:.2e} "
                   f"of max|g|; cosine {cc:.5f}, {cf:.5f}; vs the fp16-emulating autograd oracle: coarse {qc:.2e}, fine "
                   f"{qf:.2e} (the emulation itself vs float64: coarse "
-                  f"{_relerr(r16['grad_coarse'], r['grad_coarse']):.2e}, fine {_relerr(r16['grad_fine'], r['grad_fine']):.2e})", end="")
+                  f"{S.relerr(r16['grad_coarse'], r['grad_coarse']):.2e}, fine {S.relerr(r16['grad_fine'], r['grad_fine']):.2e})", end="")
         assert ef <= 2e-2 and cf > 0.9999 and ec <= 2e-1 and cc > 0.999
         assert qc <= 2e-2 and qf <= 2e-3                 # measured 6.5e-3 / 5.0e-4
         assert abs(m["loss"] - r16["loss"]) <= 2e-5 * r16["loss"]
-        e32 = _f32(T.train_gradients, *args, sampler_grad=True, alpha=1.0, fp16_loss_scale=scale)
+        e32 = S.f32(T.train_gradients, *args, sampler_grad=True, alpha=1.0, fp16_loss_scale=scale)
         with capsys.disabled():
             GB.check_mixed(gc, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, f"[mixed_float16, scale {scale:g}] coarse")
             GB.check_mixed(gf, r16["grad_fine"], e32["grad_fine"], BLOCKS, f"[mixed_float16, scale {scale:g}] fine")
@@ -882,31 +831,31 @@ def test_mixed_float16_policy_gradients_and_loss_scaling(oracle, golden_ckpt, ca
     for alpha, sg in ((0.05, True), (0.05, False), (1.0, False)):
         r64 = T.train_gradients(*args, sampler_grad=sg, alpha=alpha)
         r16 = T.train_gradients(*args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=32768.0)
-        ctx = _ctx(p, leaky_relu_alpha=alpha)
+        ctx = S.golden_context(p, leaky_relu_alpha=alpha)
         ctx.train_begin(5e-4, mixed_float16=True, sampler_gradient=sg)
         m, gc0, gf0 = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
         ctx.close()
-        qc, qf = _relerr(gc0, r16["grad_coarse"]), _relerr(gf0, r16["grad_fine"])
+        qc, qf = S.relerr(gc0, r16["grad_coarse"]), S.relerr(gf0, r16["grad_fine"])
         with capsys.disabled():
             print(f"\n[mixed_float16, alpha {alpha:g}, sampler_gradient={sg}] vs float64 autograd: coarse "
-                  f"{_relerr(gc0, r64['grad_coarse']):.2e}, fine {_relerr(gf0, r64['grad_fine']):.2e}; vs the fp16-emulating "
-                  f"oracle: coarse {qc:.2e}, fine {qf:.2e}; cosine {_cos(gc0, r16['grad_coarse']):.6f}, "
-                  f"{_cos(gf0, r16['grad_fine']):.6f}", end="")
+                  f"{S.relerr(gc0, r64['grad_coarse']):.2e}, fine {S.relerr(gf0, r64['grad_fine']):.2e}; vs the fp16-emulating "
+                  f"oracle: coarse {qc:.2e}, fine {qf:.2e}; cosine {S.cos(gc0, r16['grad_coarse']):.6f}, "
+                  f"{S.cos(gf0, r16['grad_fine']):.6f}", end="")
         assert abs(m["loss"] - r16["loss"]) <= 1e-4 * r16["loss"]
         # measured at alpha 0.05 with the sampler term: coarse 2.5e-3, fine 9.8e-3 (a few LeakyReLU sign flips of near-zero
         # pre-activations: fp32 against float64 accumulation of the same fp16 products)
-        assert qc <= 2e-2 and qf <= 3e-2 and _cos(gc0, r16["grad_coarse"]) > 0.9999 and _cos(gf0, r16["grad_fine"]) > 0.9999
+        assert qc <= 2e-2 and qf <= 3e-2 and S.cos(gc0, r16["grad_coarse"]) > 0.9999 and S.cos(gf0, r16["grad_fine"]) > 0.9999
         if alpha == 1.0:                   # (the block-wise mixed bar is an alpha = 1 bar: no mask flips)
-            e32 = _f32(T.train_gradients, *args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=32768.0)
+            e32 = S.f32(T.train_gradients, *args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=32768.0)
             with capsys.disabled():
                 GB.check_mixed(gc0, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, "[mixed_float16, sampler term off] coarse")
                 GB.check_mixed(gf0, r16["grad_fine"], e32["grad_fine"], BLOCKS, "[mixed_float16, sampler term off] fine")
     # a power-of-two loss scale changes nothing but which gradient entries leave fp16's normal range in the half-width
     # buffers: between two sane scales the unscaled gradients agree to fp16 class
     np.testing.assert_allclose(grads[32768.0][1], grads[4096.0][1], rtol=0, atol=2e-2 * np.abs(grads[4096.0][1]).max())
-    assert _cos(grads[32768.0][0], grads[4096.0][0].astype(np.float64)) > 0.999
+    assert S.cos(grads[32768.0][0], grads[4096.0][0].astype(np.float64)) > 0.999
     # dynamics
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=1024.0, dynamic_growth_steps=3)
     step = lambda tgt: ctx.train_step(p["o"], p["d"], tgt, p["sc"], p["sf"], p["u_c"], p["u_f"])   # noqa: E731
     for _ in range(3):
@@ -932,10 +881,10 @@ def test_backward_through_render(oracle, golden_ckpt, sampler_gradient, capsys):
     autograd of that graph for a random upstream d_rgb, with alpha = 1 (smooth network: bar 2e-4 of max|g|); then
     accumulate = 1 on top of a train_gradients call gives the sum of the two gradients."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
+    p = S.golden_problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
     rng = np.random.default_rng(3)
     d_rgb = (rng.standard_normal((40, 3)) * 0.1).astype(np.float32)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, sampler_gradient=sampler_gradient)
     rgb, gc, gf = ctx.train_render_gradients(p["o"], p["d"], d_rgb, p["sc"], p["sf"], p["u_c"], p["u_f"])
     r = T.render_gradients(p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
@@ -943,17 +892,17 @@ def test_backward_through_render(oracle, golden_ckpt, sampler_gradient, capsys):
     # the forward it re-ran is the render path's: same rgb as nerf_render on the same draws
     out = ctx.render(p["o"], p["d"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     assert np.abs(rgb - r["rgb"]).max() <= 5e-5 and np.abs(rgb - out[0]).max() <= 5e-5      # fp32 vs float64 forward
-    ef, cf = _relerr(gf, r["grad_fine"]), _cos(gf, r["grad_fine"])
+    ef, cf = S.relerr(gf, r["grad_fine"]), S.cos(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[backward through render(), 40 rays x (55 + 55), sampler term {'on' if sampler_gradient else 'off'}] "
               f"fine gradient vs float64 autograd {ef:.2e} of max|g|, cosine {cf:.7f}", end="")
     assert ef <= 2e-4 and cf > 0.9999999
-    r32 = _f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
+    r32 = S.f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
                sampler_grad=sampler_gradient, alpha=1.0)
     with capsys.disabled():
         GB.check_fp32_smooth(gf, r["grad_fine"], r32["grad_fine"], BLOCKS, 2e-4, "[backward through render()] fine")
     if sampler_gradient:
-        ec, cc = _relerr(gc, r["grad_coarse"]), _cos(gc, r["grad_coarse"])
+        ec, cc = S.relerr(gc, r["grad_coarse"]), S.cos(gc, r["grad_coarse"])
         with capsys.disabled():
             print(f"; coarse (through the sampler only) {ec:.2e}, cosine {cc:.7f}")
         assert ec <= 2e-4 and cc > 0.9999999
@@ -1034,20 +983,20 @@ def test_gradients_at_ragged_shapes(oracle, golden_ckpt, shape, capsys):
     counts: a 20-bin coarse pdf leaves the inverse-CDF interpolation more intervals at its 1e-5 clamp)."""
     from oracle import train_oracle as T
     n, sc, sf = shape
-    p = _problem(oracle, golden_ckpt, n=n, sc=sc, sf=sf, seed=11)
-    ctx = _ctx(p, leaky_relu_alpha=1.0)
+    p = S.golden_problem(oracle, golden_ckpt, n=n, sc=sc, sf=sf, seed=11)
+    ctx = S.golden_context(p, leaky_relu_alpha=1.0)
     ctx.train_begin(5e-4, sampler_gradient=True)
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     r = T.train_gradients(p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                           sampler_grad=True, alpha=1.0)
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
-    cc, cf = _cos(gc, r["grad_coarse"]), _cos(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
+    cc, cf = S.cos(gc, r["grad_coarse"]), S.cos(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[{n} rays x ({sc} + {sf}), alpha 1.0, sampler term on] vs float64 autograd: max gradient difference / "
               f"max|g| coarse {ec:.2e}, fine {ef:.2e}; cosine {cc:.7f}, {cf:.7f}")
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     assert ec <= 5e-4 and cc > 0.999999 and ef <= 5e-4 and cf > 0.999999
-    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+    r32 = S.f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                sampler_grad=True, alpha=1.0)
     # 130 x (2 + 3): two coarse samples per ray in almost empty space leave the coarse sigma head's four blocks at 1e-11 of
     # the blob max (under the floor, above the cap of two).  Lifting the sigma bias until they resolve makes the problem so
@@ -1068,21 +1017,21 @@ def test_gradients_at_the_reference_sample_counts(oracle, golden_ckpt, alpha, ca
     use 16 + 24 samples).  alpha = 1 removes the LeakyReLU sign-flip excuse altogether: bar 2e-4 of max|g| for both
     networks; with the reference's alpha = 0.05 the flip-limited bars of test_gradients_coarse_and_fine apply."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt, n=32, sc=64, sf=128, seed=5)
-    ctx = _ctx(p, leaky_relu_alpha=alpha)
+    p = S.golden_problem(oracle, golden_ckpt, n=32, sc=64, sf=128, seed=5)
+    ctx = S.golden_context(p, leaky_relu_alpha=alpha)
     ctx.train_begin(5e-4, sampler_gradient=True)
     m, gc, gf = ctx.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
     r = T.train_gradients(p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                           sampler_grad=True, alpha=alpha)
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
-    cc, cf = _cos(gc, r["grad_coarse"]), _cos(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
+    cc, cf = S.cos(gc, r["grad_coarse"]), S.cos(gf, r["grad_fine"])
     with capsys.disabled():
         print(f"\n[32 rays x (64 + 128), alpha {alpha}, sampler term on] vs float64 autograd: max gradient difference / "
               f"max|g| coarse {ec:.2e}, fine {ef:.2e}; cosine {cc:.7f}, {cf:.7f}")
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     tol, cos_min = (2e-4, 0.9999999) if alpha == 1.0 else (5e-2, 0.999)
     assert ec <= tol and cc > cos_min and ef <= tol and cf > cos_min
-    r32 = _f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
+    r32 = S.f32(T.train_gradients, p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"],
                sampler_grad=True, alpha=alpha)
     with capsys.disabled():
         if alpha == 1.0:
@@ -1106,7 +1055,7 @@ def test_small_blocks_survive_a_dominant_batch(oracle, n_angles, policy, capsys)
     import nerf_and_dietnerf_amd as N
     mixed = policy == "mixed_float16"
     n, sc, sf = 130, 5, 3
-    o, d, rng = _rays(oracle, n, 17, hw=16)
+    o, d, rng = S.oracle_rays(oracle, n, 17, hw=16)
     tgt = rng.random((n, 3), dtype=np.float32)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     bc, bf = N.glorot_blob(51, n_angles=n_angles), N.glorot_blob(52, n_angles=n_angles)
@@ -1121,7 +1070,7 @@ def test_small_blocks_survive_a_dominant_batch(oracle, n_angles, policy, capsys)
     ctx.close()
     kw = dict(n_angles=n_angles, alpha=1.0, fp16_loss_scale=32768.0 if mixed else None)
     r = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, **kw)
-    r32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, **kw)
+    r32 = S.f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, **kw)
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
     assert abs(m["loss"] - r["loss"]) <= (1e-4 if mixed else 2e-6) * r["loss"]
     with capsys.disabled():
@@ -1140,8 +1089,8 @@ def test_fp16_core_trainer_equals_exact_fp32_trainer_at_full_size(oracle, golden
     Compared with the sampler term off: through the sampler a single LeakyReLU sign flip in the fine pass (the two
     forwards differ by ~1e-6, and ~1e2 of 3e7 pre-activations per layer sit that close to zero) moves one ray's whole
     contribution to the coarse gradient -- with the term on, only the direction is pinned."""
-    p = _problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=21)           # only for weights / near / far
-    o, d, rng = _rays(oracle, 1024, 17, hw=64)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=21)           # only for weights / near / far
+    o, d, rng = S.oracle_rays(oracle, 1024, 17, hw=64)
     tgt = rng.random((1024, 3), dtype=np.float32)
     res = {}
     for sg in (False, True):
@@ -1150,15 +1099,15 @@ def test_fp16_core_trainer_equals_exact_fp32_trainer_at_full_size(oracle, golden
                 monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
             else:
                 monkeypatch.delenv("NERF_TRAIN_FORWARD", raising=False)
-            ctx = _ctx(p)
+            ctx = S.golden_context(p)
             ctx.train_begin(5e-4, sampler_gradient=sg)
             res[(sg, mode)] = ctx.train_gradients(o, d, tgt, 64, 128, seed=3)
             ctx.close()
     lines = []
     for sg in (False, True):
         (m32, gc32, gf32), (m16, gc16, gf16) = res[(sg, "fp32")], res[(sg, "f16")]
-        ec, ef = _relerr(gc16, gc32.astype(np.float64)), _relerr(gf16, gf32.astype(np.float64))
-        cc, cf = _cos(gc16, gc32.astype(np.float64)), _cos(gf16, gf32.astype(np.float64))
+        ec, ef = S.relerr(gc16, gc32.astype(np.float64)), S.relerr(gf16, gf32.astype(np.float64))
+        cc, cf = S.cos(gc16, gc32.astype(np.float64)), S.cos(gf16, gf32.astype(np.float64))
         lines.append(f"sampler term {'on ' if sg else 'off'}: loss {m16['loss']:.8f} vs {m32['loss']:.8f}; max gradient "
                      f"difference / max|g|: coarse {ec:.2e}, fine {ef:.2e}; cosine {cc:.7f}, {cf:.7f}")
         assert abs(m16["loss"] - m32["loss"]) <= 2e-6 * m32["loss"]
@@ -1177,8 +1126,8 @@ def test_gradients_of_a_large_batch_equal_the_mean_of_its_halves(oracle, golden_
     the reference's batch): the loss is a mean over rays, so the gradients of the batch are the mean of the gradients of its two
     4096-ray halves -- whatever slab counts, batched launches and buffer sizes the larger call picks."""
     import torch
-    p = _problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=2)            # only for weights / near / far
-    ctx = _ctx(p)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=2)            # only for weights / near / far
+    ctx = S.golden_context(p)
     ctx.use_torch_stream()
     ctx.train_begin(5e-4, mixed_float16=policy == "mixed_float16")
     n = 8192
@@ -1196,7 +1145,7 @@ def test_gradients_of_a_large_batch_equal_the_mean_of_its_halves(oracle, golden_
         sl = slice(k * 4096, (k + 1) * 4096)
         mk, c, f = ctx.train_gradients(o[sl], d[sl], tgt[sl], 64, 128, uc[sl], uf[sl])
         acc_c += host(c) / 2; acc_f += host(f) / 2; loss += float(mk["loss"]) / 2
-    ec, ef = _relerr(gc, acc_c), _relerr(gf, acc_f)
+    ec, ef = S.relerr(gc, acc_c), S.relerr(gf, acc_f)
     with capsys.disabled():
         print(f"\n[{policy}] 8192 rays in one call vs the mean of its halves: loss {float(m['loss']):.7f} / {loss:.7f}, "
               f"gradients coarse {ec:.1e}, fine {ef:.1e} of max|g|", end="")
@@ -1218,13 +1167,13 @@ def test_side_stream_weight_gradients_are_result_preserving(oracle, golden_ckpt,
     (own slab-sum buffer, per-pass max|D| slots, joined before anything reads the fine gradient blob); NERF_TRAIN_OVERLAP=0
     keeps one stream.  A selector, not a numerics switch: gradients, loss and the weights after three Adam steps must be
     bit-identical either way."""
-    p = _problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=5)
-    o, d, rng = _rays(oracle, 512, 23, hw=32)
+    p = S.golden_problem(oracle, golden_ckpt, n=64, sc=8, sf=8, seed=5)
+    o, d, rng = S.oracle_rays(oracle, 512, 23, hw=32)
     tgt = rng.random((512, 3), dtype=np.float32)
     got = {}
     for ov in ("0", "1"):
         monkeypatch.setenv("NERF_TRAIN_OVERLAP", ov)
-        ctx = _ctx(p)
+        ctx = S.golden_context(p)
         ctx.train_begin(5e-4, mixed_float16=policy == "mixed_float16")
         m, gc, gf = ctx.train_gradients(o, d, tgt, 64, 128, seed=11)
         for i in range(3):
@@ -1247,7 +1196,7 @@ def test_backward_through_render_and_mixed_policy_for_the_other_network_variants
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     n, sc, sf = 24, 16, 20
-    o, d, rng = _rays(oracle, n, 11)
+    o, d, rng = S.oracle_rays(oracle, n, 11)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     d_rgb = (rng.standard_normal((n, 3)) * 1e-2).astype(np.float32)
     tgt = rng.random((n, 3), dtype=np.float32)
@@ -1261,7 +1210,7 @@ def test_backward_through_render_and_mixed_policy_for_the_other_network_variants
     ctx.train_begin(1e-3)
     rgb, gc, gf = ctx.train_render_gradients(o, d, d_rgb, sc, sf, u_c, u_f)
     r = T.render_gradients(bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, **kw)
-    ec, ef = _relerr(gc, r["grad_coarse"]), _relerr(gf, r["grad_fine"])
+    ec, ef = S.relerr(gc, r["grad_coarse"]), S.relerr(gf, r["grad_fine"])
     assert np.abs(rgb - r["rgb"]).max() <= 5e-5
     ctx.close()
     ctx = N.Context(near=near, far=far, n_angles=n_angles, leaky_relu_alpha=1.0)
@@ -1270,7 +1219,7 @@ def test_backward_through_render_and_mixed_policy_for_the_other_network_variants
     ctx.train_begin(1e-3, mixed_float16=True)
     m, hc, hf = ctx.train_gradients(o, d, tgt, sc, sf, u_c, u_f)
     r16 = T.train_gradients(bc, bf, o, d, tgt, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
-    qc, qf = _relerr(hc, r16["grad_coarse"]), _relerr(hf, r16["grad_fine"])
+    qc, qf = S.relerr(hc, r16["grad_coarse"]), S.relerr(hf, r16["grad_fine"])
     ctx.close()
     with capsys.disabled():
         print(f"\n[n_angles {n_angles}] backward through render() vs float64: coarse {ec:.2e}, fine {ef:.2e}; mixed_float16 "
@@ -1279,8 +1228,8 @@ def test_backward_through_render_and_mixed_policy_for_the_other_network_variants
     # (the coarse gradient runs through the sampler's gains: measured 1.2e-2 on this problem, 8.6e-4 on the one above)
     assert abs(m["loss"] - r16["loss"]) <= 1e-4 * r16["loss"] and qc <= 3e-2 and qf <= 5e-3
     blks = GB.blocks(5, 4, n_angles)
-    r32 = _f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, **kw)
-    e32 = _f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
+    r32 = S.f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, **kw)
+    e32 = S.f32(T.train_gradients, bc, bf, o, d, tgt, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
     with capsys.disabled():
         for net, g, h in (("coarse", gc, hc), ("fine", gf, hf)):
             GB.check_fp32_smooth(g, r["grad_" + net], r32["grad_" + net], blks, 2e-4, f"[n_angles {n_angles}, render()] {net}")
@@ -1297,12 +1246,12 @@ def test_backward_through_render_mixed_policy(oracle, golden_ckpt, sampler_gradi
     max|g|, alpha = 1), at two loss scales (the unscaled result must not depend on a sane scale beyond fp16 class);
     then accumulate = 1 on top of nerf_train_gradients gives the sum of the two unscaled gradients and one finite verdict."""
     from oracle import train_oracle as T
-    p = _problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
+    p = S.golden_problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
     rng = np.random.default_rng(3)
     d_rgb = (rng.standard_normal((40, 3)) * 0.1).astype(np.float32)
     got = {}
     for scale in (32768.0, 2048.0):
-        ctx = _ctx(p, leaky_relu_alpha=1.0)
+        ctx = S.golden_context(p, leaky_relu_alpha=1.0)
         ctx.train_begin(5e-4, sampler_gradient=sampler_gradient, mixed_float16=True, initial_loss_scale=scale)
         rgb, gc, gf = ctx.train_render_gradients(p["o"], p["d"], d_rgb, p["sc"], p["sf"], p["u_c"], p["u_f"])
         r16 = T.render_gradients(p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
@@ -1310,16 +1259,16 @@ def test_backward_through_render_mixed_policy(oracle, golden_ckpt, sampler_gradi
         # the emulation's forward is the kernel's up to the accumulation order of fp16 products (measured 5e-4: fp16 class)
         assert np.abs(rgb - r16["rgb"]).max() <= 2e-3
         assert np.isfinite(gc).all() and np.isfinite(gf).all()
-        qf, cf = _relerr(gf, r16["grad_fine"]), _cos(gf, r16["grad_fine"])
+        qf, cf = S.relerr(gf, r16["grad_fine"]), S.cos(gf, r16["grad_fine"])
         line = (f"\n[backward through render(), mixed_float16, loss scale {scale:g}, sampler term "
                 f"{'on' if sampler_gradient else 'off'}] fine vs the fp16-emulating oracle {qf:.2e} of max|g|, cosine {cf:.6f}")
         assert qf <= 5e-3 and cf > 0.9999
-        e32 = _f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
+        e32 = S.f32(T.render_gradients, p["bc"], p["bf"], p["o"], p["d"], d_rgb, p["near"], p["far"], p["u_c"], p["u_f"],
                    sampler_grad=sampler_gradient, alpha=1.0, fp16_loss_scale=scale)
         with capsys.disabled():
             GB.check_mixed(gf, r16["grad_fine"], e32["grad_fine"], BLOCKS, f"[render(), mixed, scale {scale:g}] fine")
         if sampler_gradient:
-            qc, cc = _relerr(gc, r16["grad_coarse"]), _cos(gc, r16["grad_coarse"])
+            qc, cc = S.relerr(gc, r16["grad_coarse"]), S.cos(gc, r16["grad_coarse"])
             line += f"; coarse (through the sampler only) {qc:.2e}, cosine {cc:.6f}"
             assert qc <= 3e-2 and cc > 0.999
             with capsys.disabled():
@@ -1349,7 +1298,7 @@ def test_backward_through_render_mixed_policy_verdicts(oracle, golden_ckpt):
       * a non-finite nerf_train_gradients that is never applied does not leak into a following accumulate = 0 call
         (ADVICE r3: the stale finite = 0 made the apply skip a finite step);
       * a finite sum is applied and counts one step."""
-    p = _problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=14)
+    p = S.golden_problem(oracle, golden_ckpt, n=32, sc=8, sf=8, seed=14)
     rng = np.random.default_rng(5)
     d_rgb = (rng.standard_normal((32, 3)) * 0.1).astype(np.float32)
     bad_d = d_rgb.copy()
@@ -1358,7 +1307,7 @@ def test_backward_through_render_mixed_policy_verdicts(oracle, golden_ckpt):
     bad_t[0, 0] = np.inf
     rays = (p["o"], p["d"])
     draws = (p["sc"], p["sf"], p["u_c"], p["u_f"])
-    ctx = _ctx(p)
+    ctx = S.golden_context(p)
     ctx.train_begin(5e-4, mixed_float16=True, initial_loss_scale=1024.0)
     ctx.train_render_gradients(*rays, bad_d, *draws)
     ctx.train_apply()
@@ -1392,7 +1341,7 @@ def test_backward_through_render_mixed_policy_other_variants(oracle, n_angles, c
     from oracle import train_oracle as T
     import nerf_and_dietnerf_amd as N
     n, sc, sf = 24, 16, 20
-    o, d, rng = _rays(oracle, n, 11)
+    o, d, rng = S.oracle_rays(oracle, n, 11)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     d_rgb = (rng.standard_normal((n, 3)) * 1e-2).astype(np.float32)
     kw = dict(n_pos_enc_xyz=5, n_pos_enc_dir=4, n_angles=n_angles)
@@ -1405,13 +1354,13 @@ def test_backward_through_render_mixed_policy_other_variants(oracle, n_angles, c
     ctx.train_begin(1e-3, mixed_float16=True)
     rgb, gc, gf = ctx.train_render_gradients(o, d, d_rgb, sc, sf, u_c, u_f)
     r16 = T.render_gradients(bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
-    qc, qf = _relerr(gc, r16["grad_coarse"]), _relerr(gf, r16["grad_fine"])
+    qc, qf = S.relerr(gc, r16["grad_coarse"]), S.relerr(gf, r16["grad_fine"])
     with capsys.disabled():
         print(f"\n[n_angles {n_angles}] backward through render() under mixed_float16 vs the fp16-emulating oracle: coarse "
               f"{qc:.2e}, fine {qf:.2e} of max|g|", end="")
     assert np.abs(rgb - r16["rgb"]).max() <= 2e-3
     assert qc <= 3e-2 and qf <= 5e-3
-    e32 = _f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
+    e32 = S.f32(T.render_gradients, bc, bf, o, d, d_rgb, near, far, u_c, u_f, alpha=1.0, fp16_loss_scale=32768.0, **kw)
     with capsys.disabled():
         for net, g in (("coarse", gc), ("fine", gf)):
             GB.check_mixed(g, r16["grad_" + net], e32["grad_" + net], GB.blocks(5, 4, n_angles),
@@ -1432,8 +1381,8 @@ def test_render_forward_backward_slots_equal_the_one_call_path(oracle, golden_ck
     invalidated by an optimizer step and a slot that was never filled are refused; slots can be released and refilled."""
     import nerf_and_dietnerf_amd as N
     mixed = policy == "mixed_float16"
-    pa = _problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
-    pb = _problem(oracle, golden_ckpt, n=33, sc=55, sf=55, seed=10)
+    pa = S.golden_problem(oracle, golden_ckpt, n=40, sc=55, sf=55, seed=9)
+    pb = S.golden_problem(oracle, golden_ckpt, n=33, sc=55, sf=55, seed=10)
     if n_angles == 0:
         for q in (pa, pb):
             q["bc"], q["bf"] = N.glorot_blob(5, n_angles=0), N.glorot_blob(6, n_angles=0)
@@ -1442,7 +1391,7 @@ def test_render_forward_backward_slots_equal_the_one_call_path(oracle, golden_ck
     db = (rng.standard_normal((33, 3)) * 0.1).astype(np.float32)
 
     def begin():
-        c = _ctx(pa, n_angles=n_angles)
+        c = S.golden_context(pa, n_angles=n_angles)
         c.train_begin(5e-4, mixed_float16=mixed)
         return c
 
@@ -1505,8 +1454,8 @@ def test_abi3_entry_points_fail_loudly(oracle, golden_ckpt):
     buf[:] = 3.0                                        # ordinary host memory to the CPU
     assert float(buf.sum()) == 3.0 * (1 << 18)
     assert lib.nerf_host_free(out) == 0 and lib.nerf_host_free(None) == 0
-    p = _problem(oracle, golden_ckpt, n=8, sc=4, sf=4)
-    ctx = _ctx(p)
+    p = S.golden_problem(oracle, golden_ckpt, n=8, sc=4, sf=4)
+    ctx = S.golden_context(p)
     g = np.empty(ctx.blob_size(), np.float32)
     assert lib.nerf_train_get_gradients(ctx.h, 0, g.ctypes.data, g.size, 0) != 0          # no trainer yet
     assert "nerf_train_begin" in N._lib.last_error()

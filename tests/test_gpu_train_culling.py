@@ -12,19 +12,16 @@ import pytest
 
 import culling_ref as K
 import grad_blocks as GB
-import sampling_space_ref as R
+import occupancy_ref as G
+import support as S
 import train_culling_ref as TC
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN_BOX = ((-0.6, -0.4, -1.3), (0.4, 0.8, -0.4))
-HALF_GRID = np.random.default_rng(16).random((16, 16, 16)) < 0.5      # seeded like tests/test_gpu_culling.py::RANDOM_GRID
 FULL_GRID = np.ones((16, 16, 16), bool)
 EMPTY_GRID = np.zeros((16, 16, 16), bool)
 MARGIN = 1e-4
 BLOCKS = GB.blocks(5, 4, 2)
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 # Draw seeds for which the margin condition holds in every restatement run of the test (found on the CPU with
 # tests/occupancy_ref.py::z_values standing in for the device's depths) and for which float32 autograd, standing in for the
 # device, passes the block-wise helpers.  The render-gradient scene took one more step.  Its bars are alpha = 1 bars, and at
@@ -38,62 +35,10 @@ NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha"
 SEED_STEP, SEED_RENDER, SEED_OTHER = 4, {"float32": 138, "mixed_float16": 12}, 42
 
 
-def _camera_rays(oracle, golden_ckpt, n):
-    """n rays of the golden training camera (a 23 x 23 image), spread evenly over the image -- its first rows see only empty
-    space, where the colour branch gets no gradient -- the last ten turned round so that they miss the box."""
-    o, d = R.world_rays(oracle, golden_ckpt["c2w_train"], float(golden_ckpt["fov"]), 23, 23)
-    idx = (np.arange(n) * len(o)) // n
-    o, d = np.ascontiguousarray(o[idx]), np.ascontiguousarray(d[idx])
-    if n > 10:
-        d[-10:, :3] *= -1.0
-    return o, d
-
-
-def scene(oracle, golden_ckpt, n, sc, sf, seed):
-    o, d = _camera_rays(oracle, golden_ckpt, n)
-    rng = np.random.default_rng(seed)
-    return dict(o=o, d=d, n=n, sc=sc, sf=sf, u_c=rng.random((n, sc), dtype=np.float32), u_f=rng.random((n, sf), dtype=np.float32),
-                tgt=rng.random((n, 3), dtype=np.float32), d_rgb=(rng.standard_normal((n, 3)) * 0.1).astype(np.float32),
-                near=float(golden_ckpt["near"]), far=float(golden_ckpt["far"]), bc=golden_ckpt["blob_coarse"],
-                bf=golden_ckpt["blob_fine"])
-
-
-def _ctx(p, grid, flag, box=GOLDEN_BOX, precision="fp32", **kw):
-    import nerf_and_dietnerf_amd as N
-    c = N.Context(near=p["near"], far=p["far"], precision=precision, **kw)
-    c.load_weights(0, p["bc"])
-    c.load_weights(1, p["bf"])
-    c.set_scene_box(*box)
-    if grid is not None:
-        c.set_occupancy_grid(grid)
-    c.set_train_sample_culling(flag)
-    assert c.train_sample_culling is bool(flag)
-    return c
-
-
-def _f32(fn, *a, **kw):
-    import torch
-    return fn(*a, dtype=torch.float32, **kw)
-
-
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    a = a.astype(np.float64)
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
-def _same_bits(got, want):
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
-
-
 def check_conditions(p, r, grid, lo_share=0.2, hi_share=0.9, label=""):
     """What a comparison against the restatement `r` rests on: kept shares, a ragged last tile, the margin to every face."""
     shares = [float(k.mean()) for k in r["keeps"]]
-    margins = [TC.face_margin(p["o"], p["d"], z, *GOLDEN_BOX, grid.shape[0]) for z in r["depths"]]
+    margins = [TC.face_margin(p["o"], p["d"], z, *G.GOLDEN_BOX, grid.shape[0]) for z in r["depths"]]
     print(f"\n{label} kept {[int(k.sum()) for k in r['keeps']]} of {[k.size for k in r['keeps']]} samples, margins "
           f"{[f'{m:.2e}' for m in margins]} cell edges", end="")
     assert all(lo_share <= s <= hi_share for s in shares), shares
@@ -103,8 +48,8 @@ def check_conditions(p, r, grid, lo_share=0.2, hi_share=0.9, label=""):
 
 # ---- 1. off is off -------------------------------------------------------------------------------------------------------------
 def test_the_flag_without_a_grid_is_off(oracle, golden_ckpt):
-    p = scene(oracle, golden_ckpt, 130, 8, 16, 2)
-    c = _ctx(p, None, False)
+    p = K.train_scene(oracle, golden_ckpt, 130, 8, 16, 2)
+    c = K.culled_context(p, None, False)
     c.train_begin(5e-4)
     c.read_culling()
     res = []
@@ -115,14 +60,14 @@ def test_the_flag_without_a_grid_is_off(oracle, golden_ckpt):
         res.append((m, [gc, gf, rgb, rc, rf]))
         assert c.read_culling() == (0, 0)
     assert res[0][0] == res[1][0] and np.isfinite(res[0][1][0]).all() and res[0][1][0].any()
-    _same_bits(res[1][1], res[0][1])
+    S.assert_same_bits_each(res[1][1], res[0][1])
     # the flag outlives a grid that comes and goes, and a restarted trainer
-    c.set_occupancy_grid(HALF_GRID)
+    c.set_occupancy_grid(K.HALF_GRID)
     c.set_occupancy_grid(None)
     c.train_begin(5e-4)
     assert c.train_sample_culling
     m, gc, gf = c.train_gradients(p["o"], p["d"], p["tgt"], 8, 16, p["u_c"], p["u_f"])
-    _same_bits([gc, gf], res[0][1][:2])
+    S.assert_same_bits_each([gc, gf], res[0][1][:2])
     assert m == res[0][0] and c.read_culling() == (0, 0)
     c.close()
 
@@ -136,10 +81,10 @@ def test_a_full_grid_is_the_flag_off(oracle, golden_ckpt, trainer, monkeypatch):
     if trainer == "reference":
         monkeypatch.setenv("NERF_TRAIN_FORWARD", "gemm")
     n, sc, sf = 130, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, 6)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, 6)
     res = []
     for flag in (False, True):
-        c = _ctx(p, FULL_GRID, flag)
+        c = K.culled_context(p, FULL_GRID, flag)
         c.train_begin(5e-4, mixed_float16=trainer == "mixed_float16")
         m, gc, gf = c.train_gradients(p["o"], p["d"], p["tgt"], sc, sf, p["u_c"], p["u_f"])
         assert c.read_culling() == ((n * (sc + sf),) * 2 if flag else (0, 0))
@@ -151,7 +96,7 @@ def test_a_full_grid_is_the_flag_off(oracle, golden_ckpt, trainer, monkeypatch):
     assert all(g.any() for g in res[0][1])
     for name, a, b in zip(("coarse", "fine"), res[1][1][:2], res[0][1][:2]):
         GB.check_equal(a, b, BLOCKS, 0, f"full grid, {trainer}, {name}")            # (names the block that differs)
-    _same_bits(res[1][1], res[0][1])
+    S.assert_same_bits_each(res[1][1], res[0][1])
 
 
 # ---- 3. a partial grid against the restatement -----------------------------------------------------------------------------------
@@ -162,7 +107,7 @@ def _step_against_restatement(c, p, grid, alpha, sampler, blocks, tag, capsys, f
     the angle by ~1e-4 rad (alpha 1: 5e-3 of max|g|, cosine 0.9999, loss 1e-5)."""
     wide = net.get("n_pos_enc_xyz", 5) > 5
     z = c.get_z_values_for_rays(p["o"], p["d"], p["sc"], uniform_values=p["u_c"])
-    args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*GOLDEN_BOX, grid))
+    args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*G.GOLDEN_BOX, grid))
     r = TC.train_gradients(*args, sampler_grad=sampler, alpha=alpha, **net)
     with capsys.disabled():
         kept = check_conditions(p, r, grid, label=tag)
@@ -174,11 +119,11 @@ def _step_against_restatement(c, p, grid, alpha, sampler, blocks, tag, capsys, f
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
     tol, cos_min = ((5e-3 if wide else 2e-4), (0.9999 if wide else 0.9999999)) if alpha == 1.0 else (5e-2, 0.999)
     with capsys.disabled():
-        print(f"\n{tag} vs float64: coarse {_relerr(gc, r['grad_coarse']):.2e}, fine {_relerr(gf, r['grad_fine']):.2e} of max|g|, "
-              f"cosine {_cos(gc, r['grad_coarse']):.8f}, {_cos(gf, r['grad_fine']):.8f}", end="")
-    assert _relerr(gc, r["grad_coarse"]) <= tol and _cos(gc, r["grad_coarse"]) > cos_min
-    assert _relerr(gf, r["grad_fine"]) <= tol and _cos(gf, r["grad_fine"]) > cos_min
-    r32 = _f32(TC.train_gradients, *args, sampler_grad=sampler, alpha=alpha, **net)
+        print(f"\n{tag} vs float64: coarse {S.relerr(gc, r['grad_coarse']):.2e}, fine {S.relerr(gf, r['grad_fine']):.2e} of max|g|, "
+              f"cosine {S.cos(gc, r['grad_coarse']):.8f}, {S.cos(gf, r['grad_fine']):.8f}", end="")
+    assert S.relerr(gc, r["grad_coarse"]) <= tol and S.cos(gc, r["grad_coarse"]) > cos_min
+    assert S.relerr(gf, r["grad_fine"]) <= tol and S.cos(gf, r["grad_fine"]) > cos_min
+    r32 = S.f32(TC.train_gradients, *args, sampler_grad=sampler, alpha=alpha, **net)
     assert [k.sum() for k in r32["keeps"]] == [k.sum() for k in r["keeps"]]
     with capsys.disabled():
         if alpha == 1.0:
@@ -195,16 +140,16 @@ def _step_against_restatement(c, p, grid, alpha, sampler, blocks, tag, capsys, f
 @pytest.mark.parametrize("alpha", [1.0, 0.05])
 @pytest.mark.parametrize("sampler_gradient", [False, True])
 def test_gradients_under_a_half_full_grid(oracle, golden_ckpt, sampler_gradient, alpha, capsys):
-    p = scene(oracle, golden_ckpt, 48, 16, 24, SEED_STEP)
-    c = _ctx(p, HALF_GRID, True, leaky_relu_alpha=alpha)
+    p = K.train_scene(oracle, golden_ckpt, 48, 16, 24, SEED_STEP)
+    c = K.culled_context(p, K.HALF_GRID, True, leaky_relu_alpha=alpha)
     c.train_begin(5e-4, sampler_gradient=sampler_gradient)
     tag = f"[culled 48 x (16+24), alpha {alpha:g}, sampler term {'on' if sampler_gradient else 'off'}]"
-    kept, gc, gf = _step_against_restatement(c, p, HALF_GRID, alpha, sampler_gradient, BLOCKS, tag, capsys)
+    kept, gc, gf = _step_against_restatement(c, p, K.HALF_GRID, alpha, sampler_gradient, BLOCKS, tag, capsys)
     assert any(k % 128 for k in kept)                                      # a last tile of the network kernels that is not full
     # culling did act: the un-culled step on the same depths has other gradients
     c.set_train_sample_culling(False)
     _, gc0, gf0 = c.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
-    assert _relerr(gf, gf0) > 1e-2
+    assert S.relerr(gf, gf0) > 1e-2
     c.close()
 
 
@@ -212,34 +157,34 @@ def test_mixed_float16_gradients_under_a_half_full_grid(oracle, golden_ckpt, cap
     """tests/test_gpu_train.py::test_mixed_float16_policy_gradients_and_loss_scaling's gradient bars, culled: against the
     restatement that rounds where the kernels round (fp16_loss_scale), block by block with check_mixed at alpha = 1.  (That test's
     distance to FLOAT64 is the arithmetic class on its own inputs and is not repeated here: the emulation pins the kernels.)"""
-    p = scene(oracle, golden_ckpt, 48, 16, 24, SEED_STEP)
+    p = K.train_scene(oracle, golden_ckpt, 48, 16, 24, SEED_STEP)
     scale = 32768.0
     for alpha, sg in ((1.0, True), (0.05, True), (0.05, False), (1.0, False)):
-        c = _ctx(p, HALF_GRID, True, leaky_relu_alpha=alpha)
+        c = K.culled_context(p, K.HALF_GRID, True, leaky_relu_alpha=alpha)
         c.train_begin(5e-4, mixed_float16=True, sampler_gradient=sg, initial_loss_scale=scale)
         z = c.get_z_values_for_rays(p["o"], p["d"], p["sc"], uniform_values=p["u_c"])
-        args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*GOLDEN_BOX, HALF_GRID))
+        args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*G.GOLDEN_BOX, K.HALF_GRID))
         r16 = TC.train_gradients(*args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=scale)
         tag = f"[culled, mixed_float16, alpha {alpha:g}, sampler term {'on' if sg else 'off'}]"
         with capsys.disabled():
-            kept = check_conditions(p, r16, HALF_GRID, label=tag)
+            kept = check_conditions(p, r16, K.HALF_GRID, label=tag)
         c.read_culling()
         m, gc, gf = c.train_gradients(p["o"], p["d"], p["tgt"], p["sc"], p["sf"], p["u_c"], p["u_f"])
         assert c.read_culling() == (48 * 40, sum(kept))
         c.close()
         assert np.isfinite(gc).all() and np.isfinite(gf).all()
-        qc, qf = _relerr(gc, r16["grad_coarse"]), _relerr(gf, r16["grad_fine"])
+        qc, qf = S.relerr(gc, r16["grad_coarse"]), S.relerr(gf, r16["grad_fine"])
         with capsys.disabled():
             print(f"\n{tag} vs the fp16-emulating restatement: coarse {qc:.2e}, fine {qf:.2e}; cosine "
-                  f"{_cos(gc, r16['grad_coarse']):.6f}, {_cos(gf, r16['grad_fine']):.6f}", end="")
+                  f"{S.cos(gc, r16['grad_coarse']):.6f}, {S.cos(gf, r16['grad_fine']):.6f}", end="")
         if (alpha, sg) == (1.0, True):
             assert qc <= 2e-2 and qf <= 2e-3
             assert abs(m["loss"] - r16["loss"]) <= 2e-5 * r16["loss"]
         else:
             assert abs(m["loss"] - r16["loss"]) <= 1e-4 * r16["loss"]
-            assert qc <= 2e-2 and qf <= 3e-2 and _cos(gc, r16["grad_coarse"]) > 0.9999 and _cos(gf, r16["grad_fine"]) > 0.9999
+            assert qc <= 2e-2 and qf <= 3e-2 and S.cos(gc, r16["grad_coarse"]) > 0.9999 and S.cos(gf, r16["grad_fine"]) > 0.9999
         if alpha == 1.0:                   # (the block-wise mixed bar is an alpha = 1 bar: no mask flips)
-            e32 = _f32(TC.train_gradients, *args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=scale)
+            e32 = S.f32(TC.train_gradients, *args, sampler_grad=sg, alpha=alpha, fp16_loss_scale=scale)
             with capsys.disabled():
                 GB.check_mixed(gc, r16["grad_coarse"], e32["grad_coarse"], BLOCKS, tag + " coarse")
                 GB.check_mixed(gf, r16["grad_fine"], e32["grad_fine"], BLOCKS, tag + " fine")
@@ -256,22 +201,22 @@ def test_render_gradients_and_slots_under_a_half_full_grid(oracle, golden_ckpt, 
     n, sc, sf = 130, 8, 16
     mixed = policy == "mixed_float16"
     scale = 32768.0 if mixed else None
-    p = scene(oracle, golden_ckpt, n, sc, sf, SEED_RENDER[policy])
-    c = _ctx(p, HALF_GRID, True, leaky_relu_alpha=1.0)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, SEED_RENDER[policy])
+    c = K.culled_context(p, K.HALF_GRID, True, leaky_relu_alpha=1.0)
     c.train_begin(5e-4, sampler_gradient=sampler_gradient, mixed_float16=mixed, initial_loss_scale=scale or 0.0)
     z = c.get_z_values_for_rays(p["o"], p["d"], sc, uniform_values=p["u_c"])
-    args = (p["bc"], p["bf"], p["o"], p["d"], p["d_rgb"], z, p["u_f"], TC.grid_keep(*GOLDEN_BOX, HALF_GRID))
+    args = (p["bc"], p["bf"], p["o"], p["d"], p["d_rgb"], z, p["u_f"], TC.grid_keep(*G.GOLDEN_BOX, K.HALF_GRID))
     r = TC.render_gradients(*args, sampler_grad=sampler_gradient, alpha=1.0, fp16_loss_scale=scale)
     tag = f"[culled render(), {policy}, 130 x (8+16), sampler term {'on' if sampler_gradient else 'off'}]"
     with capsys.disabled():
-        kept = check_conditions(p, r, HALF_GRID, label=tag)
+        kept = check_conditions(p, r, K.HALF_GRID, label=tag)
     assert r["keeps"][1].shape == (n, sc + sf)
     c.read_culling()
     rgb, gc, gf = c.train_render_gradients(p["o"], p["d"], p["d_rgb"], sc, sf, p["u_c"], p["u_f"])
     assert c.read_culling() == (n * (2 * sc + sf), sum(kept))
     assert np.isfinite(gc).all() and np.isfinite(gf).all()
-    r32 = _f32(TC.render_gradients, *args, sampler_grad=sampler_gradient, alpha=1.0, fp16_loss_scale=scale)
-    ef, cf = _relerr(gf, r["grad_fine"]), _cos(gf, r["grad_fine"])
+    r32 = S.f32(TC.render_gradients, *args, sampler_grad=sampler_gradient, alpha=1.0, fp16_loss_scale=scale)
+    ef, cf = S.relerr(gf, r["grad_fine"]), S.cos(gf, r["grad_fine"])
     line = f"\n{tag} fine vs the restatement {ef:.2e} of max|g|, cosine {cf:.7f}"
     if mixed:
         assert np.abs(rgb - r["rgb"]).max() <= 2e-3
@@ -286,7 +231,7 @@ def test_render_gradients_and_slots_under_a_half_full_grid(oracle, golden_ckpt, 
     with capsys.disabled():
         check(gf, "fine")
     if sampler_gradient:
-        ec, cc = _relerr(gc, r["grad_coarse"]), _cos(gc, r["grad_coarse"])
+        ec, cc = S.relerr(gc, r["grad_coarse"]), S.cos(gc, r["grad_coarse"])
         line += f"; coarse (through the sampler only) {ec:.2e}, cosine {cc:.7f}"
         assert ec <= bar_c and cc > cos_c
         with capsys.disabled():
@@ -303,13 +248,13 @@ def test_render_gradients_and_slots_under_a_half_full_grid(oracle, golden_ckpt, 
     # ... and with the flag off and another grid by the time of the backward pass
     np.testing.assert_array_equal(c.train_render_forward(0, p["o"], p["d"], sc, sf, p["u_c"], p["u_f"]), rgb)
     c.set_train_sample_culling(False)
-    c.set_occupancy_grid(~HALF_GRID)
+    c.set_occupancy_grid(~K.HALF_GRID)
     c.read_culling()
     tc_, tf_ = c.train_render_backward(0, p["d_rgb"])
     assert c.read_culling() == (0, 0)                                    # the backward half compacts nothing anew
     GB.check_equal(tc_, gc, BLOCKS, 0, "slot path after the switch, coarse")
     GB.check_equal(tf_, gf, BLOCKS, 0, "slot path after the switch, fine")
-    _same_bits([sc_, sf_, tc_, tf_], [gc, gf, gc, gf])
+    S.assert_same_bits_each([sc_, sf_, tc_, tf_], [gc, gf, gc, gf])
     c.close()
 
 
@@ -318,8 +263,8 @@ def test_a_culled_render_between_forward_and_backward_leaves_the_slot_alone(orac
     another grid between a slot's forward and its backward pass overwrites the context's record and the shared scratch, and the
     slot's backward pass still equals the one call bit for bit."""
     n, sc, sf = 130, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, SEED_RENDER["float32"])
-    c = _ctx(p, HALF_GRID, True)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, SEED_RENDER["float32"])
+    c = K.culled_context(p, K.HALF_GRID, True)
     c.train_begin(5e-4)
     rgb, gc, gf = c.train_render_gradients(p["o"], p["d"], p["d_rgb"], sc, sf, p["u_c"], p["u_f"])
     c.read_culling()
@@ -327,22 +272,22 @@ def test_a_culled_render_between_forward_and_backward_leaves_the_slot_alone(orac
     samples, kept = c.read_culling()
     assert samples == n * (2 * sc + sf) and 0 < kept < samples            # the slot does hold a record
     c.set_sample_culling(True)
-    c.set_occupancy_grid(~HALF_GRID)
+    c.set_occupancy_grid(~K.HALF_GRID)
     assert np.isfinite(c.render(p["o"], p["d"], sc, sf, p["u_c"], p["u_f"])[0]).all()
     samples, kept_render = c.read_culling()
     assert 0 < kept_render < samples and kept_render != kept              # the render did compact, to other rows
     sc_, sf_ = c.train_render_backward(0, p["d_rgb"])
     assert c.read_culling() == (0, 0)
     assert gc.any() and gf.any()
-    _same_bits([sc_, sf_], [gc, gf])
+    S.assert_same_bits_each([sc_, sf_], [gc, gf])
     c.close()
 
 
 def test_stage_events_belong_to_render_passes_only(oracle, golden_ckpt):
     """With timing on, a culled render pass records its six stage events and a culled training pass records none."""
     n, sc, sf = 130, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, 2)
-    c = _ctx(p, HALF_GRID, True)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, 2)
+    c = K.culled_context(p, K.HALF_GRID, True)
     c.set_sample_culling(True)
     c.train_begin(5e-4)
     c.enable_timing(True)
@@ -364,7 +309,7 @@ def _rays_inside(oracle, golden_ckpt, c, n, sc):
     """As tests/test_gpu_culling.py::test_nothing_kept: the rays that hit the box.  The trainer draws its own depths; uniform in
     disparity at draws of 0.5 they lie strictly inside the box interval (linear depths put a ray's last sample at or behind
     the far end of its interval, outside the box, where it is kept)."""
-    o, d = _camera_rays(oracle, golden_ckpt, n)
+    o, d = K.camera_rays(oracle, golden_ckpt, n, spread=True)
     _, narrowed = c.ray_box_bounds(o, d)
     hit = narrowed == 1
     assert hit[:-10].sum() >= 30 and not hit[-10:].any()
@@ -376,15 +321,15 @@ def test_nothing_kept(oracle, golden_ckpt, policy):
     """An all-zero grid and rays whose depths all lie inside the box: no network kernel runs, the render is black, both gradients
     are exact zeros, and the optimizer step is an applied one.  With ten rays that miss the box the gradients are back."""
     n, sc, sf = 130, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, 3)
-    c = _ctx(p, EMPTY_GRID, True)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, 3)
+    c = K.culled_context(p, EMPTY_GRID, True)
     c.set_sampling("lindisp")
     oi, di, om, dm = _rays_inside(oracle, golden_ckpt, c, n, sc)
     ni = len(oi)
     u_c, u_f, tgt = np.full((ni, sc), 0.5, np.float32), p["u_f"][:ni], p["tgt"][:ni]
     zi = c.get_z_values_for_rays(oi, di, sc, uniform_values=u_c)
-    inside, _ = K.sample_cells(oi, di, zi, *GOLDEN_BOX, 16, K.F32)
-    assert inside.all() and not K.sample_keep(oi, di, zi, *GOLDEN_BOX, EMPTY_GRID, K.F32).any()
+    inside, _ = K.sample_cells(oi, di, zi, *G.GOLDEN_BOX, 16, K.F32)
+    assert inside.all() and not K.sample_keep(oi, di, zi, *G.GOLDEN_BOX, EMPTY_GRID, K.F32).any()
     c.train_begin(5e-4, mixed_float16=policy == "mixed_float16")
     c.read_culling()
     m, gc, gf = c.train_gradients(oi, di, tgt, sc, sf, u_c, u_f)
@@ -414,7 +359,7 @@ def test_nothing_kept(oracle, golden_ckpt, policy):
     if policy == "float32":
         c.set_train_sample_culling(False)
         _, g10c, g10f = c.train_gradients(om, dm, p["tgt"][ni:ni + 10], sc, sf, p["u_c"][:10], p["u_f"][:10])
-        assert _relerr(gc * ((ni + 10) / 10.0), g10c) <= 1e-5 and _relerr(gf * ((ni + 10) / 10.0), g10f) <= 1e-5
+        assert S.relerr(gc * ((ni + 10) / 10.0), g10c) <= 1e-5 and S.relerr(gf * ((ni + 10) / 10.0), g10f) <= 1e-5
     c.close()
 
 
@@ -428,7 +373,7 @@ def one_row_scene(oracle, golden_ckpt):
     has none; the other two rays meet neither and lose every sample.  The pair was found on the CPU by trying the pairs of cells
     the ray crosses (tests/occupancy_ref.py::z_values for the depths) for one that keeps exactly one coarse sample with a
     non-zero gradient.  (A grid of one cell would narrow the ray to that cell and keep all four.)"""
-    p = scene(oracle, golden_ckpt, 360, 4, 6, 4)
+    p = K.train_scene(oracle, golden_ckpt, 360, 4, 6, 4)
     grid = np.zeros((16, 16, 16), bool)
     for cell in ONE_ROW_CELLS:
         grid[cell] = True
@@ -442,12 +387,12 @@ def test_one_kept_row(oracle, golden_ckpt, capsys):
     outputs saturate the sigmoid on this one sample: float32 autograd itself returns zeros there, no yardstick.)"""
     alpha = 0.05
     p, grid = one_row_scene(oracle, golden_ckpt)
-    c = _ctx(p, grid, True, leaky_relu_alpha=alpha)
+    c = K.culled_context(p, grid, True, leaky_relu_alpha=alpha)
     c.set_sampling("lindisp")
     c.train_begin(5e-4)
     z = c.get_z_values_for_rays(p["o"], p["d"], p["sc"], uniform_values=p["u_c"])
     assert c.sample_occupancy(p["o"], p["d"], z).tolist() == [[1, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]]
-    args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*GOLDEN_BOX, grid))
+    args = (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], z, p["u_f"], TC.grid_keep(*G.GOLDEN_BOX, grid))
     r = TC.train_gradients(*args, alpha=alpha)
     tag = f"[one kept coarse row, alpha {alpha:g}]"
     with capsys.disabled():
@@ -460,15 +405,15 @@ def test_one_kept_row(oracle, golden_ckpt, capsys):
     assert abs(m["loss"] - r["loss"]) <= 2e-6 * r["loss"]
     tol, cos_min = (2e-4, 0.9999999) if alpha == 1.0 else (5e-2, 0.999)
     with capsys.disabled():
-        print(f"\n{tag} vs float64: coarse {_relerr(gc, r['grad_coarse']):.2e}, fine "
-              f"{_relerr(gf, r['grad_fine']) if r['grad_fine'].any() else 0.0:.2e} of max|g|", end="")
-    r32 = _f32(TC.train_gradients, *args, alpha=alpha)
+        print(f"\n{tag} vs float64: coarse {S.relerr(gc, r['grad_coarse']):.2e}, fine "
+              f"{S.relerr(gf, r['grad_fine']) if r['grad_fine'].any() else 0.0:.2e} of max|g|", end="")
+    r32 = S.f32(TC.train_gradients, *args, alpha=alpha)
     for net, g in (("coarse", gc), ("fine", gf)):
         ref = r["grad_" + net]
         if not ref.any():
             assert not g.any()
             continue
-        assert _relerr(g, ref) <= tol and _cos(g, ref) > cos_min
+        assert S.relerr(g, ref) <= tol and S.cos(g, ref) > cos_min
         with capsys.disabled():
             if alpha == 1.0:
                 GB.check_fp32_smooth(g, ref, r32["grad_" + net], BLOCKS, tol, f"{tag} {net}")
@@ -481,10 +426,10 @@ def test_one_kept_row(oracle, golden_ckpt, capsys):
 @pytest.mark.parametrize("policy", ["float32", "mixed_float16"])
 def test_train_step_is_gradients_plus_apply_and_counts_its_rows(oracle, golden_ckpt, policy):
     n, sc, sf = 130, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, 7)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, 7)
     w = []
     for split in (False, True):
-        c = _ctx(p, HALF_GRID, True)
+        c = K.culled_context(p, K.HALF_GRID, True)
         c.train_begin(5e-4, mixed_float16=policy == "mixed_float16")
         for _ in range(2):
             if split:
@@ -500,11 +445,11 @@ def test_train_step_is_gradients_plus_apply_and_counts_its_rows(oracle, golden_c
             # the coarse pass's share of the counter: a coarse-only call against the verdict entry point on the same depths
             z = c.get_z_values_for_rays(p["o"], p["d"], sc, uniform_values=p["u_c"])
             want = int(c.sample_occupancy(p["o"], p["d"], z).sum())
-            assert want == int(K.sample_keep(p["o"], p["d"], z, *GOLDEN_BOX, HALF_GRID, K.F32).sum())
+            assert want == int(K.sample_keep(p["o"], p["d"], z, *G.GOLDEN_BOX, K.HALF_GRID, K.F32).sum())
             c.train_gradients(p["o"], p["d"], p["tgt"], sc, 0, p["u_c"], want_blobs=False)
             assert c.read_culling() == (n * sc, want) and 0 < want < n * sc
         c.close()
-    _same_bits(w[1], w[0])
+    S.assert_same_bits_each(w[1], w[0])
     assert not np.array_equal(w[0][0], p["bc"]) and not np.array_equal(w[0][1], p["bf"])
 
 
@@ -516,10 +461,10 @@ def test_the_other_networks_under_a_half_full_grid(oracle, golden_ckpt, lx, n_an
     Glorot weights with a positive density bias: the culled step against the restatement as in test 3."""
     import nerf_and_dietnerf_amd as N
     kw = dict(n_pos_enc_xyz=lx, n_pos_enc_dir=4, n_angles=n_angles)
-    p = scene(oracle, golden_ckpt, 37, 11, 19, SEED_OTHER)
+    p = K.train_scene(oracle, golden_ckpt, 37, 11, 19, SEED_OTHER)
     p["bc"], p["bf"] = N.glorot_blob(21, **kw), N.glorot_blob(22, **kw)
     p["bc"][-1] = p["bf"][-1] = 1.5
-    c = _ctx(p, HALF_GRID, True, precision="auto", leaky_relu_alpha=alpha, **kw)
+    c = K.culled_context(p, K.HALF_GRID, True, precision="auto", leaky_relu_alpha=alpha, **kw)
     c.train_begin(5e-4)
     tag = f"[culled 37 x (11+19), Lx {lx}, n_angles {n_angles}, alpha {alpha:g}]"
     # One LeakyReLU mask flip (tests/test_gpu_train.py has the signature; tests/test_gpu_encodings.py names its own the same way):
@@ -528,7 +473,7 @@ def test_the_other_networks_under_a_half_full_grid(oracle, golden_ckpt, lx, n_an
     # at the fp32 floor, and float32 autograd has no flip here (1.6e-6).  The forward's arithmetic is the un-culled step's:
     # the blocks of layers 0..9 keep the blob-wide bar, every block above is asserted.
     flip = {(5, 0, 0.05): 9}.get((lx, n_angles, alpha))
-    _step_against_restatement(c, p, HALF_GRID, alpha, True, GB.blocks(lx, 4, n_angles), tag, capsys, flip=flip, **kw)
+    _step_against_restatement(c, p, K.HALF_GRID, alpha, True, GB.blocks(lx, 4, n_angles), tag, capsys, flip=flip, **kw)
     c.close()
 
 
@@ -536,10 +481,10 @@ def test_the_other_networks_under_a_half_full_grid(oracle, golden_ckpt, lx, n_an
 @pytest.mark.parametrize("cull", [True, False])
 def test_fit_trains_under_the_grid(golden_ckpt, cull):
     import nerf_and_dietnerf_amd as N
-    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(GOLDEN_BOX[0]), list(GOLDEN_BOX[1])],
+    rc = {"n_render_samples_coarse": 8, "n_render_samples_fine": 16, "scene_box": [list(G.GOLDEN_BOX[0]), list(G.GOLDEN_BOX[1])],
           "occupancy_grid": {"resolution": 16, "sigma_threshold": 10.0, "dilate": 0, "update_every": 1, "warmup_epochs": 0,
                              "cull_train_samples": cull}}
-    net = dict(NET, n_rays_in_batch_train=64)
+    net = dict(S.NET, n_rays_in_batch_train=64)
     m = N.NeRF(net, rc, float(golden_ckpt["near"]), float(golden_ckpt["far"]), precision="f16x3")
     m.set_weights(golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"])
     assert m.ctx.train_sample_culling is cull and m.ctx.sample_culling is False
@@ -566,8 +511,8 @@ def test_the_mean_of_two_shards_is_the_full_batch(oracle, golden_ckpt):
     shards of one batch with different kept counts, computed one after the other on one context, average to the full-batch culled
     gradients at the bar of tests/test_gpu_train.py::test_data_parallel_gradients_equal_full_batch."""
     n, sc, sf = 128, 8, 16
-    p = scene(oracle, golden_ckpt, n, sc, sf, 11)
-    c = _ctx(p, HALF_GRID, True)
+    p = K.train_scene(oracle, golden_ckpt, n, sc, sf, 11)
+    c = K.culled_context(p, K.HALF_GRID, True)
     c.train_begin(5e-4)
     c.read_culling()
     _, gc_full, gf_full = c.train_gradients(p["o"], p["d"], p["tgt"], sc, sf, p["u_c"], p["u_f"])
@@ -581,6 +526,6 @@ def test_the_mean_of_two_shards_is_the_full_batch(oracle, golden_ckpt):
     assert kept[0] != kept[1] and sum(kept) == full[1] and 0 < full[1] < full[0]
     gc = (parts[0][0].astype(np.float64) + parts[1][0]) / 2
     gf = (parts[0][1].astype(np.float64) + parts[1][1]) / 2
-    assert _relerr(gc, gc_full) <= 1e-5 and _relerr(gf, gf_full) <= 1e-5
+    assert S.relerr(gc, gc_full) <= 1e-5 and S.relerr(gf, gf_full) <= 1e-5
     GB.check_equal(gc.astype(np.float32), gc_full, BLOCKS, 1e-5, "two shards, coarse")
     GB.check_equal(gf.astype(np.float32), gf_full, BLOCKS, 1e-5, "two shards, fine")

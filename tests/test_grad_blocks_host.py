@@ -6,32 +6,18 @@ import pytest
 import torch
 
 import grad_blocks as GB
+import support as S
 from oracle import nerf_oracle as O
 from oracle import train_oracle as T
 
 FP32_BLOB_BAR, MIXED_BLOB_BAR = 2e-4, 2e-2          # the blob-wide bars of tests/test_gpu_train.py at alpha = 1
 
 
-def _relerr(a, b):
-    return float(np.abs(a - b).max() / np.abs(b).max())
-
-
-def _cos(a, b):
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)))
-
-
 @pytest.fixture(scope="module")
 def default_problem(golden_ckpt):
     """test_gradients_coarse_and_fine's problem: 48 rays x (16 + 24) samples, the shipped checkpoint."""
-    rng = np.random.default_rng(0)
-    c2w = O.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = O.get_rays_directions(8, 8, 0.46, c2w).reshape(-1, 4)
-    d = np.ascontiguousarray(d[rng.choice(d.shape[0], 48, replace=False)])
-    o = np.tile(c2w[:, 3], (48, 1)).astype(np.float32)
-    u_c, u_f = rng.random((48, 16), dtype=np.float32), rng.random((48, 24), dtype=np.float32)
-    tgt = rng.random((48, 3), dtype=np.float32)
-    return (golden_ckpt["blob_coarse"], golden_ckpt["blob_fine"], o, d, tgt, float(golden_ckpt["near"]),
-            float(golden_ckpt["far"]), u_c, u_f)
+    p = S.golden_problem(O, golden_ckpt)
+    return (p["bc"], p["bf"], p["o"], p["d"], p["tgt"], p["near"], p["far"], p["u_c"], p["u_f"])
 
 
 @pytest.fixture(scope="module")
@@ -61,21 +47,21 @@ def test_tampered_gradients_pass_the_blob_metric_and_fail_block_by_block(grads):
     g = ref.copy()
     g[_block(blks, "b10")] = 0.0
     g[_block(blks, "k10[dir]")] = 0.0
-    assert _relerr(g, ref) <= FP32_BLOB_BAR and _cos(g, ref) > 0.9999999          # today's fp32 bar accepts it
-    assert _relerr(g, ref) <= MIXED_BLOB_BAR                                      # ... and so does the mixed one
+    assert S.relerr(g, ref) <= FP32_BLOB_BAR and S.cos(g, ref) > 0.9999999          # today's fp32 bar accepts it
+    assert S.relerr(g, ref) <= MIXED_BLOB_BAR                                      # ... and so does the mixed one
     msg = _rejected(g, ref, blks, GB.FP32_BAR)
     assert "worst block b10:" in msg or "worst block k10[dir]:" in msg
     assert "b10:" in msg and "k10[dir]:" in msg and "of the blob max" in msg
     # 2: b8 has the wrong sign
     g = ref.copy()
     g[_block(blks, "b8")] *= -1.0
-    assert _relerr(g, ref) <= MIXED_BLOB_BAR and _cos(g, ref) > 0.9999            # the mixed bar accepts it
+    assert S.relerr(g, ref) <= MIXED_BLOB_BAR and S.cos(g, ref) > 0.9999            # the mixed bar accepts it
     msg = _rejected(g, ref, blks, GB.MIXED_LEAST)
     assert "worst block b8:" in msg and "k8" not in msg
     # 1 + 2 together, as a mixed_float16 result might carry them
     g[_block(blks, "b10")] = 0.0
     g[_block(blks, "k10[dir]")] = 0.0
-    assert _relerr(g, ref) <= MIXED_BLOB_BAR and _cos(g, ref) > 0.9999
+    assert S.relerr(g, ref) <= MIXED_BLOB_BAR and S.cos(g, ref) > 0.9999
     msg = _rejected(g, ref, blks, GB.MIXED_LEAST)
     assert all(n in msg for n in ("b8:", "b10:", "k10[dir]:"))
     # 3: layer 4's [xyz | hidden] row groups written in the other order

@@ -9,6 +9,7 @@ import pytest
 
 import occupancy_ref as G
 import scene_box_ref as B
+import support as S
 
 NEAR, FAR = G.NEAR, G.FAR
 NEEDS_BOX = "an occupancy grid needs a scene box"
@@ -249,8 +250,6 @@ def test_bad_threshold_and_counts():
 
 
 # ---- render_config["occupancy_grid"] ---------------------------------------------------------------------------------------------
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 BOX = [[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]]
 
 
@@ -274,7 +273,7 @@ class _RecordingContext:
 def _model(monkeypatch, render_config, fine=8):
     from nerf_and_dietnerf_amd import render
     monkeypatch.setattr(render, "Context", _RecordingContext)
-    return render.NeRF(NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": fine}, **render_config), NEAR, FAR)
+    return render.NeRF(S.NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": fine}, **render_config), NEAR, FAR)
 
 
 def test_render_config_without_the_key_leaves_everything_as_it_was(monkeypatch):

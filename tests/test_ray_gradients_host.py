@@ -14,6 +14,7 @@ import torch
 
 import ray_grad_ref as G
 import render_outputs_ref as R
+import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"nerf_train_set_ray_gradients": 2, "nerf_train_render_backward_rays": 9, "nerf_ray_position_grads": 8}
@@ -23,24 +24,15 @@ def _two_digits(x):
     return float(f"{x:.1e}")
 
 
-def _rays(oracle, n, seed=0, hw=8):
-    """tests/test_gpu_render_outputs.py::_rays."""
-    rng = np.random.default_rng(seed)
-    c2w = oracle.get_sphere_matrix(1.0, -20, 30, 0).astype(np.float32)
-    d = oracle.get_rays_directions(hw, hw, 0.46, c2w).reshape(-1, 4)
-    idx = rng.choice(d.shape[0], n, replace=n > d.shape[0])
-    return np.tile(c2w[:, 3], (n, 1)).astype(np.float32), np.ascontiguousarray(d[idx]), rng
-
-
 def _problem(oracle, ck, n, sc, sf, seed):
-    """tests/test_gpu_render_outputs.py::_problem: the same draws in the same order."""
-    o, d, rng = _rays(oracle, n, seed)
+    """The rays and draws of support.golden_problem, as the argument tuple of the references."""
+    o, d, rng = S.oracle_rays(oracle, n, seed)
     u_c, u_f = rng.random((n, sc), dtype=np.float32), rng.random((n, sf), dtype=np.float32)
     return (ck["blob_coarse"], ck["blob_fine"], o, d, float(ck["near"]), float(ck["far"]), u_c, u_f)
 
 
 def _d_rgb(n, seed=3):
-    """The first draw of tests/test_gpu_render_outputs.py::_cotangents."""
+    """The first draw of tests/render_outputs_ref.py::cotangents."""
     return (np.random.default_rng(seed).standard_normal((n, 3)) * 0.1).astype(np.float32)
 
 

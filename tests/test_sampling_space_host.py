@@ -10,10 +10,9 @@ import numpy as np
 import pytest
 
 import sampling_space_ref as R
+import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 LINDISP_MESSAGE = "lindisp needs near_boundary > 0"
 
 
@@ -57,7 +56,7 @@ class _RecordingContext:
 def _model(monkeypatch, render_config, near=2.0, far=6.0):
     from nerf_and_dietnerf_amd import render
     monkeypatch.setattr(render, "Context", _RecordingContext)
-    return render.NeRF(NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": 8}, **render_config), near, far)
+    return render.NeRF(S.NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": 8}, **render_config), near, far)
 
 
 def test_render_config_without_the_keys_leaves_the_context_linear_and_world(monkeypatch):

@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 import scene_box_ref as B
+import support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 ENTRIES = ("nerf_ctx_set_scene_box", "nerf_ray_box_bounds", "nerf_get_z_values_rays")
 BOX_MESSAGE = "scene box needs finite lo < hi on every axis"
 
@@ -118,7 +117,7 @@ class _RecordingContext:
 def _model(monkeypatch, render_config, near=2.0, far=6.0):
     from nerf_and_dietnerf_amd import render
     monkeypatch.setattr(render, "Context", _RecordingContext)
-    return render.NeRF(NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": 8}, **render_config), near, far)
+    return render.NeRF(S.NET, dict({"n_render_samples_coarse": 8, "n_render_samples_fine": 8}, **render_config), near, far)
 
 
 def test_render_config_without_the_key_leaves_the_context_without_a_box(monkeypatch):

@@ -7,12 +7,11 @@ import re
 import numpy as np
 import pytest
 
+import support as S
 import train_culling_ref as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOX = [[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]]
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2}
 
 
 @pytest.fixture(scope="module")
@@ -165,7 +164,7 @@ def _model(render, grid_cfg, box=BOX):
         rc["scene_box"] = box
     if grid_cfg is not None:
         rc["occupancy_grid"] = grid_cfg
-    return render.NeRF(NET, rc, 2.0, 6.0)
+    return render.NeRF(S.NET, rc, 2.0, 6.0)
 
 
 def test_the_model_sets_the_train_flag_on_its_context(monkeypatch):

@@ -8,59 +8,13 @@ What is pinned, against reference output rather than against this repository's o
   * row (f2): the three tour builders (src/ExecutionRun.py:358-437) and the dataset loader feeding them
   * the fp16 single-pass mode: the reference produced these frames under `mixed_float16` (src/ExecutionRun.py:220-221)
 
-Limits of the pin, stated: the frames went through JPEG (MJPG) and uint8 rounding, and the reference draws fresh
-stratified jitter per frame (no seed), so the comparison is PSNR, not elementwise.  Frames of views *behind* the
-captured hemisphere (middle of the sphere tour) are dominated by that jitter: two renders of ours with different
-seeds agree there only to 24-30 dB.  The per-frame bar is therefore  min(34 dB, self-PSNR - 4.5 dB), where
-self-PSNR is measured between two seeds of the path under test; on the l_to_r and path tours it is 34 dB for
-every frame (measured >= 36.4 dB), and the tour means are pinned as well.
+Limits of the pin and the bars they lead to (PSNR per frame, not elementwise): tests/video_ref.py.
 """
-import os
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NET = {"hidden_layer_dim": 256, "last_hidden_layer_dim": 128, "leaky_relu_alpha": 0.05, "n_pos_enc_dim_xyz": 5,
-       "n_pos_enc_view_dir": 4, "n_angles_for_model": 2, "n_rays_in_batch_train": 4096, "n_rays_in_batch_render": 4096}
-RGB_BAR, RGB_SELF_MARGIN = 34.0, 4.5          # dB
-DEPTH_BAR, DEPTH_SELF_MARGIN = 30.0, 4.0      # dB (histogram equalisation amplifies small depth differences)
-RGB_MEAN_BAR = {"l_to_r": 39.5, "sphere": 33.0, "path": 36.5}      # measured 40.9 / 34.0 / 37.7
-DEPTH_MEAN_BAR = {"l_to_r": 37.0, "sphere": 27.0, "path": 36.0}    # measured 38.4 / 28.0 / 37.0
-
-
-def psnr(a, b):
-    return float(-10 * np.log10(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2) + 1e-30))
-
-
-@pytest.fixture(scope="module")
-def frames():
-    return np.load(os.path.join(ROOT, "tests", "golden", "alexander50_video_frames.npz"))
-
-
-@pytest.fixture(scope="module")
-def scene():
-    import nerf_and_dietnerf_amd as N
-    images, poses, fov, near, far, avg, scale = N.get_data_from_colmap(os.path.join(ROOT, "tests", "golden", "alexander50"))
-    return {"poses": poses, "fov": fov, "near": near, "far": far}
-
-
-def tours(frames, scene):
-    """The camera matrices the reference rendered, from the product's tour builders + the two fixture constants of
-    the reference's randomised scene analysis."""
-    import nerf_and_dietnerf_amd as N
-    fps, ti = int(frames["fps_render_video"]), int(frames["test_img_idx"])
-    sph = bool(frames["is_spherical_dataset"])
-    t = {"l_to_r": N.get_l_to_r_c2w_matrices_to_render(scene["poses"], ti, fps, sph),
-         "sphere": N.get_sphere_c2w_matrices_to_render(scene["poses"], ti, fps, sph, frames["estimated_intersection"]),
-         "path": N.get_path_c2w_matrices_to_render(scene["poses"], frames["img_indices_for_path_video"], fps)}
-    # the product's own scene analysis (nerf_and_dietnerf_amd/scene.py; the builders' default) arrives at the same tours:
-    # the 234 stored reference frames these matrices are pinned against pin the analysis with them
-    np.testing.assert_allclose(N.get_sphere_c2w_matrices_to_render(scene["poses"], ti, fps), t["sphere"], atol=1e-6)
-    np.testing.assert_allclose(N.get_l_to_r_c2w_matrices_to_render(scene["poses"], ti, fps), t["l_to_r"], atol=1e-6)
-    for name, m in t.items():
-        assert len(m) == int(frames[name + "_n_frames"])       # 300 / 720 / 1320 frames, as the reference wrote
-    return t
+from video_ref import (DEPTH_BAR, DEPTH_MEAN_BAR, DEPTH_SELF_MARGIN, NET, RGB_BAR, RGB_MEAN_BAR, RGB_SELF_MARGIN,
+                       frames, psnr, scene, tours)  # noqa: F401  (frames, scene: fixtures)
 
 
 def test_fixture_constants(frames, scene):

@@ -11,6 +11,7 @@ from isosurface_ref import lattice_points, lattice_step      # the density latti
 from scene_box_ref import ray_box_interval
 
 F = np.float32
+LO, HI = (-1.0, -1.2, -0.9), (1.1, 1.0, 1.3)          # the box of the volume tests: three different extents
 
 
 def camera_directions(points, c2w):
@@ -86,3 +87,30 @@ def march(volume, lo, hi, near, far, rays_orig, rays_dirs, n_steps, t_min=0.0, e
             T = np.where(alive, (T * (F(1) - alpha).astype(F)).astype(F), T)
             alive = alive & ~(T < t_min)
     return rgb, depth, (F(1) - T).astype(F)
+
+
+# ---- the media, rays and bar of tests/test_volume_host.py and tests/test_gpu_volume.py -------------------------------------------
+def march_bar(n_steps):
+    """(n_steps + 4) 2^-23 on rgb and opacity (times far on depth): a step adds about four roundings of quantities bounded
+    by 1 and one expf ulp."""
+    return (n_steps + 4) * 2.0 ** -23
+
+
+def rays_through_box(n, seed):
+    """Origins on the sphere of radius 4, aimed at points of the box: every ray hits between the tests' bounds 2 and 6."""
+    rng = np.random.default_rng(seed)
+    g = rng.normal(size=(n, 3))
+    o = 4.0 * g / np.linalg.norm(g, axis=1, keepdims=True)
+    t = rng.uniform(np.array(LO) * 0.8, np.array(HI) * 0.8, size=(n, 3))
+    d = (t - o) / np.linalg.norm(t - o, axis=1, keepdims=True)
+    o4 = np.concatenate([o, np.ones((n, 1))], axis=1).astype(F)
+    d4 = np.concatenate([d, np.zeros((n, 1))], axis=1).astype(F)
+    return o4, d4
+
+
+def random_volume(n, seed, sigma_scale=3.0):
+    rng = np.random.default_rng(seed)
+    v = rng.random((n, n, n, 4), dtype=F)
+    v[..., 3] = (v[..., 3] * F(sigma_scale)).astype(F)
+    v[..., 3][rng.random((n, n, n)) < 0.3] = 0.0        # empty vertices, as after the ReLU
+    return v
