@@ -35,7 +35,8 @@ extern "C" {
  * nerf_ray_occupancy_bounds) and the mesh entries (nerf_density_lattice, nerf_isosurface, nerf_isosurface_fetch,
  * nerf_mesh_colors) and the distortion-loss entries (nerf_train_set_distortion_weights, nerf_train_read_distortion_sums,
  * nerf_distortion_loss) and the radiance-volume entries (nerf_radiance_lattice, nerf_volume_sample, nerf_volume_march,
- * nerf_volume_render_image), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
+ * nerf_volume_render_image) and their spherical-harmonic forms (nerf_sh_radiance_lattice, nerf_sh_volume_sample,
+ * nerf_sh_volume_march, nerf_sh_volume_render_image), all marked "ABI 6+" below: they are additive -- no existing entry, struct or default changes -- so the
  * number that gates compatibility stays; a caller that may meet an older library of ABI 6 probes them with dlsym. */
 #define NERF_ABI_VERSION 6
 
@@ -282,6 +283,66 @@ int nerf_volume_march(nerf_ctx* ctx, const float* volume, int32_t n, const float
 int nerf_volume_render_image(nerf_ctx* ctx, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
                              float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
                              float* rgb, float* depth, float* opacity, int mem);
+
+/* ---- ABI 6+, view-dependent colour in the radiance volume: spherical harmonics per vertex (additive entry points) ----------
+ * The format.  Degree L in 0..3, K = (L + 1)^2 basis functions.  A texel is C(L) = 4 ceil((3 K + 1) / 4) float32 -- 4 / 16 /
+ * 28 / 52 for L = 0 / 1 / 2 / 3 -- so every texel is 16-byte aligned.  Channel 3 k + c holds the coefficient of basis
+ * function k for colour channel c (k < K, c < 3), channel 3 K the density after the ReLU, fmaxf(raw sigma, 0); the channels
+ * after it are exact zeros.  The volume is (n, n, n, C(L)) float32 indexed [iz, iy, ix, channel] on the lattice of
+ * nerf_radiance_lattice, n in 2..512: n^3 C(L) 4 bytes, 1.75 GiB at n = 256, L = 2.  Coefficients are in the colour domain
+ * (after the sigmoid, not logits); the colour towards u is clamp(sum_k Y_k(u) coef_k, 0, 1), the clamp by comparisons
+ * (x < 0 ? 0 : x > 1 ? 1 : x: a NaN stays NaN).  A degree-L volume whose coefficients above degree L' < L are +0 gives the
+ * bits of the degree-L' volume with the same (finite) coefficients: the extra terms add +-0 to sums that are not -0.
+ *   Basis.     Real, orthonormal on the sphere, u = (x, y, z), float32, the constants rounded to float32, every operation
+ *              rounded on its own, no FMA, in exactly this order (xx = x x, yy = y y, zz = z z, xy = x y, yz = y z, xz = x z):
+ *                Y0  = 0.28209479177387814
+ *                Y1  = 0.4886025119029199 y             Y2  = 0.4886025119029199 z          Y3 = 0.4886025119029199 x
+ *                Y4  = 1.0925484305920792 xy            Y5  = 1.0925484305920792 yz
+ *                Y6  = 0.31539156525252005 ((3 zz) - 1) Y7  = 1.0925484305920792 xz
+ *                Y8  = 0.5462742152960396 (xx - yy)
+ *                Y9  = 0.5900435899266435 (y ((3 xx) - yy))       Y10 = 2.890611442640554 (xy z)
+ *                Y11 = 0.4570457994644658 (y ((5 zz) - 1))        Y12 = 0.3731763325901154 (z ((5 zz) - 3))
+ *                Y13 = 0.4570457994644658 (x ((5 zz) - 1))        Y14 = 1.445305721320277 (z (xx - yy))
+ *                Y15 = 0.5900435899266435 (x (xx - (3 yy)))
+ *   Direction. u = d / |d|: s = (d_x d_x + d_y d_y) + d_z d_z, r = sqrt(s) correctly rounded, one correctly-rounded division
+ *              per component.  If s is 0 or not finite (a zero, NaN, Inf or overflowing d), u = (0, 0, 1).
+ *   Limits.    The volume answers for d / |d|, while the ray generator's directions have length 1 / cos of the angle to the
+ *              optical axis and the network sees that length.  A fit over the full sphere includes directions no camera saw.
+ *              Like every volume it is a snapshot of one network: nothing rebuilds it.
+ *
+ * nerf_sh_radiance_lattice: the bake.  dirs (D, 3) and proj (K, D), both HOST, D in 1..64, are the caller's projection table.
+ * For every vertex the network `which` is evaluated at the D directions dirs[j] exactly as given (the network takes raw
+ * directions: their length is the caller's choice), by the chunk loop and kernels of nerf_radiance_lattice -- the ctx's
+ * precision, encoding window and n_angles act as there; for n_angles == 0 the directions are ignored and the same path runs.
+ * colour_j[c] = the sigmoid of raw_j[c] as nerf_mesh_colors writes it; coef[k][c] = proj[k][0] colour_0[c], then
+ * + proj[k][j] colour_j[c] for j = 1 .. D - 1 in that order, each multiply and each add rounded on its own; sigma =
+ * fmaxf(raw_0[3], 0).  A pass through the network takes max(1, floor(2^20 / D)) vertices (D points each).  The table is kept
+ * in a device buffer of the ctx for the duration of the call.
+ *   The default table (what the Python helper sh_quadrature builds): the L + 1 Gauss-Legendre nodes in cos(theta) times
+ *   2 L + 1 equally spaced azimuths phi_m = (m + 1/2) 2 pi / (2 L + 1), node-major, D = 1 / 6 / 15 / 28, unit directions
+ *   (sin(theta) cos(phi), sin(theta) sin(phi), cos(theta)); proj[k][j] = q_j Y_k(dirs_j) with q_j = 2 pi w_node / (2 L + 1),
+ *   in float64, rounded once.  It is exact for the products Y_k Y_k' up to degree L.
+ * Fails, in this order: which not 0 or 1; no scene box ("an SH radiance lattice needs a scene box"); n outside 2..512; degree
+ * outside 0..3; D outside 1..64; a NULL table; a non-finite entry of dirs or proj; an all-zero direction; network not loaded. */
+int nerf_sh_radiance_lattice(nerf_ctx* ctx, int which, int32_t n, int32_t degree, const float* dirs, const float* proj,
+                             int32_t D, float* volume, int mem);
+/* nerf_sh_volume_sample: the SH volume at M points (M, 3) seen along dirs (M, 3) -> out (M, 4) = (r, g, b, sigma).  The cell
+ * and the weights are nerf_volume_sample's (the cell index is in [0, n - 2] for every input).  u and Y_k from dirs as above.
+ * At each of the cell's 8 vertices colour_c = Y_0 coef_0c, then + Y_k coef_kc for k = 1 .. K - 1 in order (multiply, add); the
+ * four values (r, g, b, sigma) are interpolated along x, then y, then z as in nerf_volume_sample; the colour is then clamped. */
+int nerf_sh_volume_sample(nerf_ctx* ctx, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3,
+                          const float* points, const float* dirs, int64_t M, float* out, int mem);
+/* nerf_sh_volume_march: nerf_volume_march with nerf_sh_volume_sample's value in step 4, u and Y_k computed once per ray from
+ * the ray's direction.  Non-finite rays are misses, misses give exact zeros, t_min acts as there.
+ * nerf_sh_volume_render_image: nerf_volume_render_image likewise.  One lane works on a ray at degrees 0 and 1, eight lanes
+ * (one cell vertex each) at degrees 2 and 3; the results do not depend on that (profiles/sh_volume_measure.json has both). */
+int nerf_sh_volume_march(nerf_ctx* ctx, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3,
+                         const float* rays_orig, const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb,
+                         float* depth, float* opacity, int mem);
+int nerf_sh_volume_render_image(nerf_ctx* ctx, const float* volume, int32_t n, int32_t degree, const float* lo3,
+                                const float* hi3, const float* c2w, float fov, int32_t H, int32_t W, int64_t ray_begin,
+                                int64_t ray_count, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
+                                int mem);
 
 /* replaces Keras load_weights / model.get_weights() order (src/ExecutionRun.py:228-231):
  * `blob` = the 22 tensors of one network, kernel(in,out) row-major then bias, layer order of

@@ -31,5 +31,6 @@ from .video import (get_c2w_matrices_between_2_c2w, get_c2w_matrices_between_2_c
                     render_video)
 from .mesh import read_ply, write_ply
 from .weights import blob_size, glorot_blob, layer_shapes
+from .sh import sh_basis, sh_basis_count, sh_least_squares, sh_quadrature, sh_texel_floats
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -73,6 +73,11 @@ SYMBOLS = [
     ("nerf_volume_sample", C.c_int, [_P, _P, _I32, _P, _P, _P, _I64, _P, C.c_int]),
     ("nerf_volume_march", C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, C.c_int]),
     ("nerf_volume_render_image", C.c_int, [_P, _P, _I32, _P, _P, _P, _F, _I32, _I32, _I64, _I64, _I32, _F, _P, _P, _P, C.c_int]),
+    ("nerf_sh_radiance_lattice", C.c_int, [_P, C.c_int, _I32, _I32, _P, _P, _I32, _P, C.c_int]),
+    ("nerf_sh_volume_sample", C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, C.c_int]),
+    ("nerf_sh_volume_march", C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, C.c_int]),
+    ("nerf_sh_volume_render_image", C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _F, _I32, _I32, _I64, _I64, _I32, _F, _P, _P, _P,
+                                              C.c_int]),
     ("nerf_blob_size", C.c_size_t, [C.POINTER(NerfConfig)]),
     ("nerf_load_weights", C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     ("nerf_ctx_set_encoding_window", C.c_int, [_P, _P, _P]),

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <vector>
 
+#include "field_device.h"
 #include "nerf_ctx.h"
 
 using namespace nerf;
@@ -160,6 +161,55 @@ int nerf_density_lattice(nerf_ctx* c, int which, int32_t n, const float* view_di
 int nerf_radiance_lattice(nerf_ctx* c, int which, int32_t n, const float* view_dir3, const float* camera_c2w16, float* volume,
                           int mem) {
     return lattice_query(c, which, "radiance lattice", n, view_dir3, camera_c2w16, 4, volume, mem);
+}
+
+int nerf_sh_radiance_lattice(nerf_ctx* c, int which, int32_t n, int32_t degree, const float* dirs, const float* proj, int32_t D,
+                             float* volume, int mem) {
+    const char* what = "SH radiance lattice";
+    ENTER(c);
+    if (!volume) return fail("NULL argument");
+    if (int r = query_ok(c, which, [&] {
+            if (!c->box_on) return fail("an %s needs a scene box (nerf_ctx_set_scene_box)", what);
+            if (int r = lattice_n_ok(what, n)) return r;
+            if (degree < 0 || degree > kShMaxDegree) return fail("%s: degree must be in 0..%d (got %d)", what, kShMaxDegree, degree);
+            if (D < 1 || D > kShMaxDirs) return fail("%s: D must be in 1..%d (got %d)", what, kShMaxDirs, D);
+            if (!dirs || !proj) return fail("%s: %s is NULL", what, dirs ? "proj" : "dirs");
+            for (int j = 0; j < D; ++j) {
+                const float* d = dirs + 3 * j;
+                for (int a = 0; a < 3; ++a)
+                    if (!std::isfinite(d[a])) return fail("%s: dirs[%d][%d] is not finite (%g)", what, j, a, d[a]);
+            }
+            const int K = sh_basis_count(degree);
+            for (int k = 0; k < K; ++k)
+                for (int j = 0; j < D; ++j)
+                    if (!std::isfinite(proj[k * D + j]))
+                        return fail("%s: proj[%d][%d] is not finite (%g)", what, k, j, proj[k * D + j]);
+            for (int j = 0; j < D; ++j)
+                if (dirs[3 * j] == 0.f && dirs[3 * j + 1] == 0.f && dirs[3 * j + 2] == 0.f)
+                    return fail("%s: dirs[%d] is the zero vector", what, j);
+            return 0;
+        })) return r;
+    const int K = sh_basis_count(degree), C = sh_texel_floats(degree);
+    const long long points = (long long)n * n * n;
+    // the call's table, directions then projection, in the ctx's device buffer; the caller's arrays are free again after it
+    if (int r = ensure(c, c->b_sh_table, (size_t)(3 + sh_basis_count(kShMaxDegree)) * kShMaxDirs * 4)) return r;   // the largest
+    float* table = (float*)c->b_sh_table.p;
+    HIP_OK(hipMemcpyAsync(table, dirs, (size_t)D * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(table + 3 * D, proj, (size_t)K * D * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    Staging st(c, mem);
+    float* out = st.out(c->b_lattice, volume, (size_t)points * C * 4);
+    if (st.err) return st.err;
+    const int r = for_each_chunk(c, which, points, std::max(1LL, kMeshChunk / D), D,
+        [&](Chunk& k) {
+            launch_sh_lattice_points(c->box, n, k.begin, k.m, D, table, k.xyz, k.view, c->stream);
+            return 0;
+        },
+        [&](const Chunk& k) {
+            launch_sh_project(k.raw, k.m, degree, D, table + 3 * D, out + (size_t)C * k.begin, c->stream);
+            return 0;
+        });
+    return r ? r : st.finish();
 }
 
 int nerf_mesh_colors(nerf_ctx* c, int which, const float* vertices, const float* normals, int64_t V, float* rgb, int mem) {

@@ -25,4 +25,10 @@ __device__ __forceinline__ float lattice_coord(const Lattice& l, int axis, int i
 
 __device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
+// The SH volume's texel (include/nerf_mi355.h: nerf_sh_radiance_lattice has the format): K basis functions of degree L,
+// 3 K coefficients, sigma, zeros up to a multiple of 4 floats -- 4 / 16 / 28 / 52.
+constexpr int kShMaxDegree = 3, kShMaxDirs = 64;
+__host__ __device__ constexpr int sh_basis_count(int degree) { return (degree + 1) * (degree + 1); }
+__host__ __device__ constexpr int sh_texel_floats(int degree) { return 4 * ((3 * sh_basis_count(degree) + 1 + 3) / 4); }
+
 }  // namespace nerf

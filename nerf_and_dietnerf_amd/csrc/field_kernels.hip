@@ -138,6 +138,59 @@ __global__ void raw_rgba_kernel(const float* __restrict__ raw, long long count, 
     reinterpret_cast<float4*>(texels)[t] = make_float4(raw_sigmoid(o.x), raw_sigmoid(o.y), raw_sigmoid(o.z), fmaxf(o.w, 0.f));
 }
 
+// ---- SH radiance lattice (nerf_sh_radiance_lattice has the rule) ----
+// the fill: point p of a chunk is vertex begin + p / D seen along direction p % D of the table (D, 3), as given
+__global__ void sh_lattice_points_kernel(const Lattice l, long long begin, long long count, int D, const float* __restrict__ table,
+                                         float* __restrict__ xyz, float* __restrict__ view) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const long long p = begin + t / D;
+    const int j = (int)(t % D), n = l.n;
+    const int i[3] = {(int)(p % n), (int)((p / n) % n), (int)(p / ((long long)n * n))};
+    xyz[3 * t + 0] = lattice_coord(l, 0, i[0]);
+    xyz[3 * t + 1] = lattice_coord(l, 1, i[1]);
+    xyz[3 * t + 2] = lattice_coord(l, 2, i[2]);
+    if (view) { view[3 * t + 0] = table[3 * j]; view[3 * t + 1] = table[3 * j + 1]; view[3 * t + 2] = table[3 * j + 2]; }
+}
+
+// the drain: raw (count * D, 4) -> texels (count, C(L)).  One thread per vertex; the K x 3 sums stay in registers, each
+// fed in the order of j; proj (K, D) is read at wave-uniform addresses.
+template <int L>
+__global__ void sh_project_kernel(const float* __restrict__ raw, long long count, int D, const float* __restrict__ proj,
+                                  float* __restrict__ texels) {
+    constexpr int K = sh_basis_count(L), C = sh_texel_floats(L);
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const float4* rows = reinterpret_cast<const float4*>(raw) + t * D;
+    float coef[3 * K];
+    float sigma = 0.f;
+    for (int j = 0; j < D; ++j) {
+        const float4 o = rows[j];
+        const float col[3] = {raw_sigmoid(o.x), raw_sigmoid(o.y), raw_sigmoid(o.z)};
+        if (j == 0) sigma = fmaxf(o.w, 0.f);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float w = proj[(size_t)k * D + j];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const float term = __fmul_rn(w, col[ch]);
+                coef[3 * k + ch] = j == 0 ? term : __fadd_rn(coef[3 * k + ch], term);
+            }
+        }
+    }
+    float4* out = reinterpret_cast<float4*>(texels + (size_t)t * C);
+#pragma unroll
+    for (int q = 0; q < C / 4; ++q) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ch = 4 * q + e;
+            v[e] = ch < 3 * K ? coef[ch < 3 * K ? ch : 0] : (ch == 3 * K ? sigma : 0.f);
+        }
+        out[q] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
 }  // namespace
 
 void launch_grid_points(const SceneBox& box, int R, long long cell_begin, long long n_cells, int spc, uint64_t seed,
@@ -185,6 +238,24 @@ void launch_camera_view(const float c2w[16], const float* xyz, long long count, 
 
 void launch_raw_rgba(const float* raw, long long count, float* texels, hipStream_t stream) {
     if (count > 0) hipLaunchKernelGGL(raw_rgba_kernel, dim3(blocks_for(count)), dim3(kBs), 0, stream, raw, count, texels);
+}
+
+void launch_sh_lattice_points(const SceneBox& box, int n, long long begin, long long count, int D, const float* table, float* xyz,
+                              float* view, hipStream_t stream) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(sh_lattice_points_kernel, dim3(blocks_for(count * D)), dim3(kBs), 0, stream,
+                       make_lattice(box.lo, box.hi, n), begin, count * D, D, table, xyz, view);
+}
+
+void launch_sh_project(const float* raw, long long count, int degree, int D, const float* proj, float* texels, hipStream_t stream) {
+    if (count <= 0) return;
+    const dim3 grid(blocks_for(count)), block(kBs);
+    switch (degree) {
+        case 0: hipLaunchKernelGGL(sh_project_kernel<0>, grid, block, 0, stream, raw, count, D, proj, texels); break;
+        case 1: hipLaunchKernelGGL(sh_project_kernel<1>, grid, block, 0, stream, raw, count, D, proj, texels); break;
+        case 2: hipLaunchKernelGGL(sh_project_kernel<2>, grid, block, 0, stream, raw, count, D, proj, texels); break;
+        default: hipLaunchKernelGGL(sh_project_kernel<3>, grid, block, 0, stream, raw, count, D, proj, texels); break;
+    }
 }
 
 }  // namespace nerf

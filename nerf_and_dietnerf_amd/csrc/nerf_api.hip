@@ -555,7 +555,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     DevBuf* bufs[] = {&c->b_orig, &c->b_dirs, &c->b_zc, &c->b_zf, &c->b_raw, &c->b_wc, &c->b_u0, &c->b_u1,
                       &c->b_in0, &c->b_in1, &c->b_in2, &c->b_grid[0], &c->b_grid[1], &c->b_gbounds, &c->b_gstate,
                       &c->b_mesh_v, &c->b_mesh_n, &c->b_mesh_t, &c->b_mesh_sigma, &c->b_mesh_mask, &c->b_mesh_first,
-                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice, &c->cull.mask, &c->cull.first,
+                      &c->b_mesh_count, &c->b_mesh_tfirst, &c->b_mesh_sums, &c->b_lattice, &c->b_sh_table, &c->cull.mask, &c->cull.first,
                       &c->b_csums, &c->b_cxyz, &c->b_cdirs, &c->b_craw};
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& b : c->b_out) if (b.p) (void)hipFree(b.p);

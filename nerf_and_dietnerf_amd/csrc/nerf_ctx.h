@@ -89,6 +89,7 @@ struct nerf_ctx {
     nerf::DevBuf b_mesh_v, b_mesh_n, b_mesh_t;                             // vertices, normals, triangles
     nerf::DevBuf b_mesh_sigma, b_mesh_mask, b_mesh_first, b_mesh_count, b_mesh_tfirst, b_mesh_sums;
     nerf::DevBuf b_lattice;                    // a host caller's lattice: baked, before it leaves; a volume, staged in
+    nerf::DevBuf b_sh_table;                   // nerf_sh_radiance_lattice: the call's directions (D, 3), then its projection (K, D)
     int num_cus = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;

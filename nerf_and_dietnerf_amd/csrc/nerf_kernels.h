@@ -289,6 +289,12 @@ void launch_raw_rgb(const float* raw, long long count, float* rgb, hipStream_t s
 // (count, 3); raw (count, 4) -> texels (count, 4), sigmoid of columns 0..2 and ReLU of column 3.
 void launch_camera_view(const float c2w[16], const float* xyz, long long count, float* view, hipStream_t stream);
 void launch_raw_rgba(const float* raw, long long count, float* texels, hipStream_t stream);
+// The SH radiance lattice (nerf_sh_radiance_lattice has the rule), field_kernels.hip too: vertices [begin, begin + count) of the
+// lattice, each D times, with the D directions of the device table (D, 3) (view nullable); raw (count * D, 4) -> texels (count,
+// C(degree)) by the device projection table proj (K, D).
+void launch_sh_lattice_points(const SceneBox& box, int n, long long begin, long long count, int D, const float* table, float* xyz,
+                              float* view, hipStream_t stream);
+void launch_sh_project(const float* raw, long long count, int degree, int D, const float* proj, float* texels, hipStream_t stream);
 // mesh_kernels.hip's exclusive scan for bit-mask items: out[i] = set bits of in[0..i), *total_dev = set bits of all N bytes;
 // sums: scratch of scan_sums_words(N) words.  No atomics: the result does not depend on the launch.
 size_t scan_sums_words(long long N);

@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import (NerfTrainConfig, NERF_MEM_DEVICE, NERF_MEM_HOST, NERF_NET_COARSE, NERF_NET_FINE, NERF_PRECISION_F16X3,
                    NERF_PRECISION_FP32, NerfConfig, NerfOutputs)
+from .sh import SH_MAX_DIRS, check_sh_degree, sh_basis_count, sh_degree_of, sh_quadrature, sh_texel_floats
 
 # configuration key names (src/ConfigurationKeys.py:64-111)
 N_RENDER_SAMPLES_FINE = "n_render_samples_fine"
@@ -700,6 +701,99 @@ class Context:
         _lib.check(self.lib.nerf_volume_render_image(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, c2w_h.ctypes.data,
                                                      float(fov), int(h), int(w), int(ray_begin), int(ray_count), steps, t, p0,
                                                      p1, p2, arr.mem))
+        return rgb, depth, opacity
+
+    # ---- SH radiance volume: view-dependent colour as spherical harmonics per vertex (include/nerf_mi355.h:
+    # nerf_sh_radiance_lattice has the format, nerf_sh_volume_sample the rule) ----
+    def sh_radiance_lattice(self, which, n, degree, dirs=None, proj=None, device_out=False):
+        """Network ``which`` baked onto the n^3 lattice of the scene box as spherical harmonics of degree ``degree`` (0..3) in the
+        view direction: an (n, n, n, C) float32 array indexed [iz, iy, ix, channel], C = 4 / 16 / 28 / 52, channel 3 k + c the
+        coefficient of basis function k for colour c, channel 3 K the density after the ReLU, zeros after it.  ``dirs`` (D, 3)
+        and ``proj`` (K, D), D in 1..64, are the projection table: the network is evaluated at every vertex along each of
+        ``dirs`` as given, and the coefficients are ``proj`` times the D colours.  Default: ``sh_quadrature(degree)``, a
+        full-sphere quadrature; ``sh_least_squares(degree, dirs)`` fits a caller's own directions.  One bake answers for every
+        pose -- for the unit direction d / |d|, while the network sees the ray generator's un-normalised directions, and a
+        full-sphere table includes directions no camera saw.  n^3 C 4 bytes (1.75 GiB at n = 256, degree 2): a numpy array, or
+        a torch-device tensor if ``device_out`` is set."""
+        degree = check_sh_degree(degree)
+        if (dirs is None) != (proj is None):
+            raise ValueError("SH radiance lattice: give both dirs and proj, or neither")
+        if dirs is None:
+            dirs, proj = sh_quadrature(degree)
+        k = sh_basis_count(degree)
+        dirs_a = np.ascontiguousarray(dirs.detach().cpu().numpy() if _is_torch(dirs) else dirs, dtype=np.float32)
+        if dirs_a.ndim != 2 or dirs_a.shape[1] != 3 or not 1 <= dirs_a.shape[0] <= SH_MAX_DIRS:
+            raise ValueError(f"SH radiance lattice: dirs must be (D, 3) with D in 1..{SH_MAX_DIRS}, got {dirs_a.shape}")
+        d = dirs_a.shape[0]
+        proj_a = _host_floats(proj, (k, d), "proj", exact=True)
+        if not (np.isfinite(dirs_a).all() and np.isfinite(proj_a).all()):
+            raise ValueError("SH radiance lattice: dirs and proj must be finite")
+        if not dirs_a.any(axis=1).all():
+            raise ValueError(f"SH radiance lattice: dirs[{int(np.argmin(dirs_a.any(axis=1)))}] is the zero vector")
+
+        def entry(h, which_, n_, out, mem):
+            return self.lib.nerf_sh_radiance_lattice(h, which_, n_, degree, dirs_a.ctypes.data, proj_a.ctypes.data, d, out, mem)
+        return self._lattice("SH radiance lattice", entry, which, n, (sh_texel_floats(degree),), [], None, device_out)
+
+    @staticmethod
+    def _sh_volume_args(volume, lo, hi, what):
+        """(n, degree, lo, hi) of an (n, n, n, C(degree)) volume, checked as the library checks them."""
+        shape = tuple(volume.shape)
+        if len(shape) != 4 or shape[0] != shape[1] or shape[0] != shape[2]:
+            raise ValueError(f"SH volume must be an (n, n, n, C) array, got {shape}")
+        degree = sh_degree_of(shape[3])
+        if not 2 <= shape[0] <= 512:
+            raise ValueError(f"{what}: n must be in 2..512 (got {shape[0]})")
+        lo_a, hi_a = _box_corners(lo, hi)
+        if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
+            raise ValueError(f"{what} needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
+        return shape[0], degree, lo_a, hi_a
+
+    def sample_sh_volume(self, volume, lo, hi, points, dirs):
+        """The SH ``volume`` (n, n, n, C) over the box (lo, hi) at ``points`` (M, 3) seen along ``dirs`` (M, 3, any length; a zero
+        or non-finite direction counts as (0, 0, 1)) -> (M, 4): the colour, clamped to [0, 1], and the density; numpy or
+        torch-device arrays (nerf_sh_volume_sample has the rule).  The degree follows from C."""
+        arr = self._arrays(volume, points, dirs)
+        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume sample")
+        m = int(points.shape[0])
+        pvol = arr.inp(volume, tuple(volume.shape))
+        pp, pd = arr.inp(points, (m, 3)), arr.inp(dirs, (m, 3))
+        out, po = arr.out((m, 4))
+        _lib.check(self.lib.nerf_sh_volume_sample(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data, pp, pd, m, po,
+                                                  arr.mem))
+        return out
+
+    def march_sh_volume(self, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min=0.0):
+        """march_volume through an SH ``volume`` (n, n, n, C): every sample's colour is the volume's towards the ray's own
+        direction -> (rgb (N, 3), depth (N,), opacity (N,)) (nerf_sh_volume_march)."""
+        arr = self._arrays(volume, rays_orig, rays_dirs)
+        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume march")
+        steps, t = self._march_args(n_steps, t_min)
+        nr = int(rays_orig.shape[0])
+        pvol = arr.inp(volume, tuple(volume.shape))
+        po, pd = arr.inp(rays_orig, (nr, 4)), arr.inp(rays_dirs, (nr, 4))
+        rgb, p0 = arr.out((nr, 3))
+        depth, p1 = arr.out((nr,))
+        opacity, p2 = arr.out((nr,))
+        _lib.check(self.lib.nerf_sh_volume_march(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data, po, pd, nr, steps,
+                                                 t, p0, p1, p2, arr.mem))
+        return rgb, depth, opacity
+
+    def render_sh_volume_image(self, volume, lo, hi, c2w, fov, h, w, n_steps, t_min=0.0, ray_begin=0, ray_count=0):
+        """render_volume_image through an SH ``volume`` (n, n, n, C): equal to get_rays_directions + march_sh_volume bit for
+        bit (nerf_sh_volume_render_image)."""
+        arr = self._arrays(volume)
+        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume render")
+        steps, t = self._march_args(n_steps, t_min)
+        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
+        pvol = arr.inp(volume, tuple(volume.shape))
+        lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
+        rgb, p0 = arr.out(lead + (3,))
+        depth, p1 = arr.out(lead)
+        opacity, p2 = arr.out(lead)
+        _lib.check(self.lib.nerf_sh_volume_render_image(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data,
+                                                        c2w_h.ctypes.data, float(fov), int(h), int(w), int(ray_begin),
+                                                        int(ray_count), steps, t, p0, p1, p2, arr.mem))
         return rgb, depth, opacity
 
     def ray_occupancy_bounds(self, rays_orig, rays_dirs):
@@ -1397,6 +1491,7 @@ class NeRF:
         self.grid_config = self._grid_config(render_config.get(OCCUPANCY_GRID), self.scene_box)
         self._grid_epochs = 0        # epochs fit() has run: the grid's schedule counts them
         self._preview = None         # bake_preview: (volume on the device, lo, hi, resolution)
+        self._preview_sh_degree = None     # ... and the SH degree of that volume (None: the plain RGB-sigma volume)
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_SAMPLES, False):
             self.ctx.set_sample_culling(True)
         if self.grid_config is not None and self.grid_config.get(GRID_CULL_TRAIN_SAMPLES, False):
@@ -1488,23 +1583,44 @@ class NeRF:
             write_ply(path, mesh["vertices"], mesh["triangles"], mesh["normals"], mesh.get("colors"))
         return mesh
 
-    def bake_preview(self, resolution: int = 256, which: Optional[int] = None, view_dir=None, camera=None) -> None:
+    def bake_preview(self, resolution: int = 256, which: Optional[int] = None, view_dir=None, camera=None, sh_degree=None,
+                     sh_dirs=None, sh_proj=None) -> None:
         """Bake network ``which`` (None: the fine network if it is loaded, else the coarse one) onto a ``resolution``^3
         RGB-sigma lattice over render_config["scene_box"] (Context.radiance_lattice) and keep it, as a device tensor together
         with the box it was baked on, for render_preview.  Colours are those of ONE view direction (``view_dir``, default
         (0, 0, 1)) or ONE camera (``camera``, a (4, 4) camera-to-world matrix): the preview shows no view-dependent effects
         from any other pose and is no parity mode of render_image.  It is a snapshot, like the occupancy grid: nothing
         rebuilds it -- training on, loading other weights or changing the box leave it as baked until this is called again.
-        16 bytes a vertex: 256 MiB at 256, 2 GiB at 512."""
+        16 bytes a vertex: 256 MiB at 256, 2 GiB at 512.
+
+        ``sh_degree`` (0..3): bake view-dependent colour instead, as spherical harmonics of that degree per vertex
+        (Context.sh_radiance_lattice; ``sh_dirs`` / ``sh_proj``: a projection table other than the default full-sphere one).
+        One bake then serves every pose, for the unit view direction; it cannot be combined with ``view_dir`` or ``camera``,
+        and a vertex takes 16 / 64 / 112 / 208 bytes."""
         if self.scene_box is None:
             raise ValueError(f"bake_preview needs render_config[{SCENE_BOX!r}]")
+        if sh_degree is None:
+            if sh_dirs is not None or sh_proj is not None:
+                raise ValueError("bake_preview: sh_dirs and sh_proj need sh_degree")
+
+            def bake():
+                return self.ctx.radiance_lattice(which, resolution, view_dir=view_dir, camera=camera, device_out=True)
+        else:
+            if view_dir is not None or camera is not None:
+                raise ValueError("bake_preview: sh_degree cannot be combined with view_dir or camera")
+            sh_degree = check_sh_degree(sh_degree)
+
+            def bake():
+                return self.ctx.sh_radiance_lattice(which, resolution, sh_degree, dirs=sh_dirs, proj=sh_proj, device_out=True)
         if which is None:
             which = NERF_NET_FINE if self.model_fine is not None and self.ctx.loaded[NERF_NET_FINE] else NERF_NET_COARSE
         self._preview = None
-        volume = self.ctx.radiance_lattice(which, resolution, view_dir=view_dir, camera=camera, device_out=True)
+        self._preview_sh_degree = None
+        volume = bake()
         if self.ctx.auto_check():            # precision "auto": the f16x3 pass overflowed, the context is in fp32 now
-            volume = self.ctx.radiance_lattice(which, resolution, view_dir=view_dir, camera=camera, device_out=True)
+            volume = bake()
         self._preview = (volume, tuple(self.scene_box[0]), tuple(self.scene_box[1]), int(resolution))
+        self._preview_sh_degree = sh_degree
 
     def render_preview(self, c2w, fov, h, w, n_steps: Optional[int] = None, t_min: float = 1.0 / 512.0):
         """The baked preview seen from camera ``c2w``: (rgb (h, w, 3), depth (h, w), opacity (h, w)) as torch-device
@@ -1517,8 +1633,8 @@ class NeRF:
         if self._preview is None:
             raise RuntimeError("render_preview: no preview is baked (call bake_preview first)")
         volume, lo, hi, resolution = self._preview
-        rgb, depth_sum, opacity = self.ctx.render_volume_image(volume, lo, hi, c2w, fov, h, w,
-                                                               2 * resolution if n_steps is None else n_steps, t_min)
+        march = self.ctx.render_volume_image if self._preview_sh_degree is None else self.ctx.render_sh_volume_image
+        rgb, depth_sum, opacity = march(volume, lo, hi, c2w, fov, h, w, 2 * resolution if n_steps is None else n_steps, t_min)
         depth = depth_sum.div_(opacity).masked_fill_(opacity <= 0, 0.0)      # on the device, no synchronisation
         return rgb, depth, opacity
 
