@@ -1,9 +1,9 @@
 // volume_kernels.hip -- the radiance volume: an (n, n, n, 4) float32 lattice of (r, g, b, sigma) over a box, indexed
 // [iz, iy, ix, channel], colour after the sigmoid and density after the ReLU (include/nerf_mi355.h: nerf_radiance_lattice has
-// the format, nerf_volume_sample the trilinear rule, nerf_volume_march the march).  Here: the trilinear sampler, the march and
-// their entry points.  The bake (nerf_radiance_lattice) is a field query: field_api.hip.  After them, the SH volume -- K
-// spherical-harmonic coefficients per colour and vertex in place of one colour (nerf_sh_radiance_lattice has the format) --
-// with its sampler, its march and their entry points; the cell, the lerp and the march's steps are the ones stated here once.
+// the format, nerf_volume_sample the trilinear rule, nerf_volume_march the march), and the SH volume -- K spherical-harmonic
+// coefficients per colour and vertex in place of one colour (nerf_sh_radiance_lattice has the format).  Here: the trilinear
+// sampler and the march, each written once over the two formats, and their entry points.  The bakes (nerf_radiance_lattice,
+// nerf_sh_radiance_lattice) are field queries: field_api.hip.
 //
 // Everything is float32 with every operation rounded on its own (the __f*_rn idiom of aux_kernels.hip), so the numpy
 // restatement of tests/volume_ref.py matches the sampler bit for bit and the march up to expf.
@@ -21,7 +21,8 @@ namespace nerf {
 namespace {
 
 // ---- trilinear sampling ----
-// the volume's texels and the lattice they sit on: field_device.h's, so the sampler's step is the bake's by construction
+// the volume's texels and the lattice they sit on: field_device.h's, so the sampler's step is the bake's by construction.  A
+// texel is Q float4: 1 in the plain format, C(L) / 4 in the SH format of degree L.
 struct VolumeArgs { const float4* texels; Lattice l; };
 
 VolumeArgs volume_args(const float* volume, int n, const float* lo3, const float* hi3) {
@@ -75,78 +76,9 @@ __device__ __forceinline__ float4 volume_value(const CellFetch& c) {
                        trilinear(v[0].w, v[1].w, v[2].w, v[3].w, v[4].w, v[5].w, v[6].w, v[7].w, c.f));
 }
 
-// one thread per point
-__global__ void volume_sample_kernel(const VolumeArgs g, const float* __restrict__ points, long long M, float* __restrict__ out) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= M) return;
-    CellFetch c;
-    volume_fetch(g, points[3 * t + 0], points[3 * t + 1], points[3 * t + 2], &c);
-    reinterpret_cast<float4*>(out)[t] = volume_value(c);
-}
-
-// ---- the march ----
-// One thread per ray, 64 consecutive rays per wavefront, one wavefront per workgroup: a 256 x 256 frame is 1024 wavefronts,
-// one per SIMD of the chip, so what hides the gathers' latency is the work one ray keeps in flight, not other wavefronts.  The
-// sample positions do not depend on the transmittance: the ray fetches the cells of kAhead steps (8 x kAhead 16-byte gathers)
-// and only then composites them, in order.  A ray under t_min stops fetching at the next group of steps; the steps of its
-// last group past the stop, and a last group's steps past n_steps, are fetched (their cells are in the volume like any
-// other) and not composited.  kAhead = 4 (161 VGPRs) against 2 and 8 (72, 300): 0.317 ms against 0.357 and 0.314 for the 256 x 256
-// frame through n = 256 at 512 steps, 2.80 ms against 2.60 and 4.26 for 1024 x 1024 (profiles/volume_ahead_ab.json).
-constexpr int kAhead = 4;
-
-__global__ __launch_bounds__(64) void volume_march_kernel(const VolumeArgs g, const BoxArgs bx, const float* __restrict__ orig,
-                                                          const float* __restrict__ dirs, long long N, int n_steps, float t_min,
-                                                          float* __restrict__ rgb, float* __restrict__ depth,
-                                                          float* __restrict__ opacity) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= N) return;
-    const float4 o = reinterpret_cast<const float4*>(orig)[r], d = reinterpret_cast<const float4*>(dirs)[r];
-    float a, b;
-    bool hit = ray_box_hit(bx, o, d, &a, &b);
-    // a ray with a non-finite component is a miss (ray_box_hit does not guard them: a NaN ray would "hit" on [near, far])
-    hit = hit && finite_f(o.x) && finite_f(o.y) && finite_f(o.z) && finite_f(d.x) && finite_f(d.y) && finite_f(d.z);
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f, cd = 0.0f, T = 1.0f;
-    if (hit) {
-        const float delta = __fdiv_rn(__fsub_rn(b, a), (float)n_steps);
-        bool alive = true;
-        for (int k0 = 0; k0 < n_steps && alive; k0 += kAhead) {
-            CellFetch c[kAhead];
-            float z[kAhead];
-#pragma unroll
-            for (int u = 0; u < kAhead; ++u) {
-                z[u] = __fadd_rn(a, __fmul_rn(__fadd_rn((float)(k0 + u), 0.5f), delta));
-                volume_fetch(g, __fadd_rn(o.x, __fmul_rn(d.x, z[u])), __fadd_rn(o.y, __fmul_rn(d.y, z[u])),
-                             __fadd_rn(o.z, __fmul_rn(d.z, z[u])), &c[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < kAhead; ++u) {
-                const float4 v = volume_value(c[u]);
-                const float e = expf(-__fmul_rn(v.w, delta));
-                const float alpha = __fsub_rn(1.0f, e);
-                const float w = __fmul_rn(alpha, T);
-                const bool on = alive && k0 + u < n_steps;          // predicated, not branched: the body is a few selects
-                cr = on ? __fadd_rn(cr, __fmul_rn(w, v.x)) : cr;
-                cg = on ? __fadd_rn(cg, __fmul_rn(w, v.y)) : cg;
-                cb = on ? __fadd_rn(cb, __fmul_rn(w, v.z)) : cb;
-                cd = on ? __fadd_rn(cd, __fmul_rn(w, z[u])) : cd;
-                T = on ? __fmul_rn(T, __fsub_rn(1.0f, alpha)) : T;
-                alive = alive && !(on && T < t_min);
-            }
-        }
-    }
-    if (rgb) { rgb[3 * r + 0] = cr; rgb[3 * r + 1] = cg; rgb[3 * r + 2] = cb; }
-    if (depth) depth[r] = cd;
-    if (opacity) opacity[r] = __fsub_rn(1.0f, T);
-}
-
 // ---- view-dependent colour: spherical harmonics per vertex (include/nerf_mi355.h: nerf_sh_radiance_lattice has the format, the
 // basis and the direction rule, nerf_sh_volume_sample the per-point rule) ----
 // A texel is Q = C(L) / 4 float4: channel 3 k + c the coefficient of basis function k for colour c, channel 3 K sigma.
-struct ShVolumeArgs { const float4* texels; Lattice l; };
-
-ShVolumeArgs sh_volume_args(const float* volume, int n, const float* lo3, const float* hi3) {
-    return {reinterpret_cast<const float4*>(volume), make_lattice(lo3, hi3, n)};
-}
 
 // u = d / |d|, (0, 0, 1) where |d|^2 is 0 or not finite
 __device__ __forceinline__ void sh_unit(float dx, float dy, float dz, float u[3]) {
@@ -218,7 +150,7 @@ __device__ __forceinline__ float4 clamp_colour(float4 v) { return make_float4(cl
 
 // the cell of a point: the texel of its lowest vertex and the three weights
 template <int L>
-__device__ __forceinline__ const float4* sh_cell(const ShVolumeArgs& g, float px, float py, float pz, float f[3]) {
+__device__ __forceinline__ const float4* sh_cell(const VolumeArgs& g, float px, float py, float pz, float f[3]) {
     const int n = g.l.n;
     const int ix = volume_cell(px, g.l.lo[0], g.l.step[0], n, &f[0]);
     const int iy = volume_cell(py, g.l.lo[1], g.l.step[1], n, &f[1]);
@@ -228,7 +160,7 @@ __device__ __forceinline__ const float4* sh_cell(const ShVolumeArgs& g, float px
 
 // all eight vertices of a cell by one lane -> the interpolated, clamped value
 template <int L>
-__device__ __forceinline__ float4 sh_value(const ShVolumeArgs& g, float px, float py, float pz, const float* Y) {
+__device__ __forceinline__ float4 sh_value(const VolumeArgs& g, float px, float py, float pz, const float* Y) {
     constexpr size_t Q = sh_texel_floats(L) / 4;
     float f[3];
     const float4* row = sh_cell<L>(g, px, py, pz, f);
@@ -242,32 +174,73 @@ __device__ __forceinline__ float4 sh_value(const ShVolumeArgs& g, float px, floa
     return clamp_colour(volume_value(c));
 }
 
-// one thread per point
+// ---- the two formats, as the sampler and the march see them ----
+// Either type gives "the value of the volume at a point, seen along a direction" to the thread that asks: towards() makes what
+// depends on the direction alone, K floats Y that the asking kernel keeps in a local array (as a member of a value of the
+// type, Y changed the register allocation of the SH marches of degree 1 to 3); fetch() starts the value at a point and leaves
+// an InFlight behind, value() finishes it, so that a march can start Ahead steps before it finishes the first.
+//
+// The plain format.  Only the sampler asks it: its march is spelled out (volume_march_kernel<PlainVolume>), so it has neither
+// towards() nor Ahead.
+struct PlainVolume {
+    static constexpr int K = 1;
+    static constexpr bool ViewDependent = false;                      // the same along every direction: Y stays unused
+    using InFlight = CellFetch;                                       // the eight texels, not yet interpolated
+    static __device__ __forceinline__ void fetch(const VolumeArgs& g, float px, float py, float pz, const float*, InFlight* c) {
+        volume_fetch(g, px, py, pz, c);
+    }
+    static __device__ __forceinline__ float4 value(const InFlight& c) { return volume_value(c); }
+};
+
+// The SH format of degree L.  A step gathers 8 x Q float4 per ray -- 8 / 32 / 56 / 104 -- where the plain format gathers 8, so
+// holding the cells of the steps in flight does not carry over: sh_vertex consumes a vertex's loads as they arrive, a step leaves
+// 4 values behind, and kShAhead[L] steps are in flight.  u and Y are made once, with the value: once per ray in the march.
+constexpr int kShAhead[kShMaxDegree + 1] = {4, 2, 1, 1};      // one lane per ray: steps in flight
+
 template <int L>
-__global__ void sh_volume_sample_kernel(const ShVolumeArgs g, const float* __restrict__ points, const float* __restrict__ dirs,
-                                        long long M, float* __restrict__ out) {
+struct ShVolume {
+    static constexpr int Degree = L, Ahead = kShAhead[L], K = sh_basis_count(L);
+    static constexpr bool ViewDependent = true;
+    using InFlight = float4;                                          // the value itself
+    static __device__ __forceinline__ void towards(float dx, float dy, float dz, float* Y) {
+        float u[3];
+        sh_unit(dx, dy, dz, u);
+        sh_basis<L>(u, Y);
+    }
+    static __device__ __forceinline__ void fetch(const VolumeArgs& g, float px, float py, float pz, const float* Y, InFlight* c) {
+        *c = sh_value<L>(g, px, py, pz, Y);
+    }
+    static __device__ __forceinline__ float4 value(const InFlight& c) { return c; }
+};
+
+// one thread per point; dirs (M, 3) is read by the SH formats alone (NULL for the plain one)
+template <class Format>
+__global__ void volume_sample_kernel(const VolumeArgs g, const float* __restrict__ points, const float* __restrict__ dirs,
+                                     long long M, float* __restrict__ out) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M) return;
-    float u[3], Y[sh_basis_count(L)];
-    sh_unit(dirs[3 * t + 0], dirs[3 * t + 1], dirs[3 * t + 2], u);
-    sh_basis<L>(u, Y);
-    reinterpret_cast<float4*>(out)[t] = sh_value<L>(g, points[3 * t + 0], points[3 * t + 1], points[3 * t + 2], Y);
+    float Y[Format::K];
+    if constexpr (Format::ViewDependent) Format::towards(dirs[3 * t + 0], dirs[3 * t + 1], dirs[3 * t + 2], Y);
+    typename Format::InFlight c;
+    Format::fetch(g, points[3 * t + 0], points[3 * t + 1], points[3 * t + 2], Y, &c);
+    reinterpret_cast<float4*>(out)[t] = Format::value(c);
 }
 
-// ---- the SH march ----
-// A step gathers 8 x Q float4 per ray -- 8 / 32 / 56 / 104 -- where the degree-less march gathers 8, so volume_march_kernel's
-// design (one ray per lane, the cells of kAhead steps held in registers) does not carry over.  Two mappings, the same
-// arithmetic in the same order, hence the same bits (profiles/sh_volume_measure.json has both):
-//   one lane per ray     volume_march_kernel's shape: sh_vertex consumes a vertex's loads as they arrive, so a step leaves
-//                        4 values behind; kShAhead[L] steps are in flight.
+// ---- the march ----
+// One lane per ray over either format; a ray under t_min stops fetching at the next group of steps; the steps of its last group
+// past the stop, and a last group's steps past n_steps, are fetched (their cells are in the volume like any other) and not
+// composited.  For the SH format there is a second mapping, the same arithmetic in the same order, hence the same bits
+// (profiles/sh_volume_measure.json has both):
+//   one lane per ray     volume_march_kernel<ShVolume<L>>.
 //   eight lanes per ray  one cell vertex each: a lane streams its own texel (Q contiguous 16-byte loads; the two x-neighbours
 //                        are 2 Q contiguous float4), the three lerps run across lanes -- x between lanes 1 apart, y 2 apart,
 //                        z 4 apart, each lane picking lower and upper by its own bit, so all eight end with the step's value
 //                        and composite it alike.  A 256 x 256 frame is 8 wavefronts per SIMD: other wavefronts hide the
 //                        latency, and two steps are in flight per lane.
-// Neither wins everywhere (launch_sh_degree has the times and the choice): at degrees 0 and 1 a lane's own 8 or 32 gathers
+// Neither wins everywhere (kShEightLanes has the times and the choice): at degrees 0 and 1 a lane's own 8 or 32 gathers
 // keep it busy and the eight-lane form pays its eightfold address and compositing arithmetic for nothing; at degree 3 one
 // lane's 104 gathers a step need 256 VGPRs and leave one wavefront per SIMD with nothing to switch to.
+
 // per ray: the box interval and, for a hit, the step
 struct MarchRay { float4 o, d; float a, delta; bool hit; };
 
@@ -277,19 +250,20 @@ __device__ __forceinline__ MarchRay march_ray(const BoxArgs& bx, const float* or
     m.d = reinterpret_cast<const float4*>(dirs)[r];
     float b;
     m.hit = ray_box_hit(bx, m.o, m.d, &m.a, &b);
+    // a ray with a non-finite component is a miss (ray_box_hit does not guard them: a NaN ray would "hit" on [near, far])
     m.hit = m.hit && finite_f(m.o.x) && finite_f(m.o.y) && finite_f(m.o.z) && finite_f(m.d.x) && finite_f(m.d.y) && finite_f(m.d.z);
     m.delta = __fdiv_rn(__fsub_rn(b, m.a), (float)n_steps);
     return m;
 }
 
-// steps 4 and 5 of nerf_volume_march for one sample, predicated as in volume_march_kernel
+// steps 4 and 5 of nerf_volume_march for one sample
 struct MarchSums { float cr = 0.0f, cg = 0.0f, cb = 0.0f, cd = 0.0f, T = 1.0f; bool alive = true; };
 
 __device__ __forceinline__ void march_step(MarchSums& s, float4 v, float z, float delta, bool in_range, float t_min) {
     const float e = expf(-__fmul_rn(v.w, delta));
     const float alpha = __fsub_rn(1.0f, e);
     const float w = __fmul_rn(alpha, s.T);
-    const bool on = s.alive && in_range;
+    const bool on = s.alive && in_range;                  // predicated, not branched: the body is a few selects
     s.cr = on ? __fadd_rn(s.cr, __fmul_rn(w, v.x)) : s.cr;
     s.cg = on ? __fadd_rn(s.cg, __fmul_rn(w, v.y)) : s.cg;
     s.cb = on ? __fadd_rn(s.cb, __fmul_rn(w, v.z)) : s.cb;
@@ -308,38 +282,97 @@ __device__ __forceinline__ float step_depth(float a, float delta, int k) {
     return __fadd_rn(a, __fmul_rn(__fadd_rn((float)k, 0.5f), delta));
 }
 
-constexpr int kShAhead[kShMaxDegree + 1] = {4, 2, 1, 1};      // one lane per ray: steps in flight
-constexpr int kShCornerAhead = 2;                             // eight lanes per ray: steps in flight
-
-template <int L>
-__global__ __launch_bounds__(64) void sh_march_ray_kernel(const ShVolumeArgs g, const BoxArgs bx, const float* __restrict__ orig,
+template <class Format>
+__global__ __launch_bounds__(64) void volume_march_kernel(const VolumeArgs g, const BoxArgs bx, const float* __restrict__ orig,
                                                           const float* __restrict__ dirs, long long N, int n_steps, float t_min,
                                                           float* __restrict__ rgb, float* __restrict__ depth,
                                                           float* __restrict__ opacity) {
-    constexpr int A = kShAhead[L];
+    constexpr int A = Format::Ahead;
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= N) return;
     const MarchRay m = march_ray(bx, orig, dirs, r, n_steps);
     MarchSums s;
     if (m.hit) {
-        float u[3], Y[sh_basis_count(L)];
-        sh_unit(m.d.x, m.d.y, m.d.z, u);
-        sh_basis<L>(u, Y);
+        float Y[Format::K];
+        Format::towards(m.d.x, m.d.y, m.d.z, Y);
         for (int k0 = 0; k0 < n_steps && s.alive; k0 += A) {
-            float4 v[A];
+            typename Format::InFlight c[A];
             float z[A];
 #pragma unroll
             for (int i = 0; i < A; ++i) {
                 z[i] = step_depth(m.a, m.delta, k0 + i);
-                v[i] = sh_value<L>(g, __fadd_rn(m.o.x, __fmul_rn(m.d.x, z[i])), __fadd_rn(m.o.y, __fmul_rn(m.d.y, z[i])),
-                                   __fadd_rn(m.o.z, __fmul_rn(m.d.z, z[i])), Y);
+                Format::fetch(g, __fadd_rn(m.o.x, __fmul_rn(m.d.x, z[i])), __fadd_rn(m.o.y, __fmul_rn(m.d.y, z[i])),
+                              __fadd_rn(m.o.z, __fmul_rn(m.d.z, z[i])), Y, &c[i]);
             }
 #pragma unroll
-            for (int i = 0; i < A; ++i) march_step(s, v[i], z[i], m.delta, k0 + i < n_steps, t_min);
+            for (int i = 0; i < A; ++i) march_step(s, Format::value(c[i]), z[i], m.delta, k0 + i < n_steps, t_min);
         }
     }
     march_store(s, r, rgb, depth, opacity);
 }
+
+// The plain format's march.  One thread per ray, 64 consecutive rays per wavefront, one wavefront per workgroup: a 256 x 256
+// frame is 1024 wavefronts, one per SIMD of the chip, so what hides the gathers' latency is the work one ray keeps in flight, not
+// other wavefronts.  The sample positions do not depend on the transmittance: the ray fetches the cells of kAhead steps
+// (8 x kAhead 16-byte gathers) and only then composites them, in order.  kAhead = 4 (161 VGPRs) against 2 and 8 (72, 300):
+// 0.317 ms against 0.357 and 0.314 for the 256 x 256 frame through n = 256 at 512 steps, 2.80 ms against 2.60 and 4.26 for
+// 1024 x 1024 (profiles/volume_ahead_ab.json).
+// It is the body above with InFlight = CellFetch, spelled out as it was before that body was shared: the same operations in the
+// same order, so the same bits, but the shared body compiles to 16 instructions fewer in another schedule and measured 0.7 %
+// slower on that frame with t_min = 1 / 512 (0.3149 against 0.3127 ms, medians of three fresh processes each whose own medians
+// lie within 0.0003 and 0.0002 ms; equal at t_min = 0; profiles/volume_refactor_ab_shared_body.json).  That is over the bar set
+// for the change, the parent's own range; processes of identical code differed by as much in a later call
+// (profiles/volume_refactor_ab.json), so a slower kernel is not established.  Both bodies are held to tests/volume_ref.py's
+// march by tests/test_gpu_volume.py and tests/test_gpu_sh_volume.py.
+constexpr int kAhead = 4;
+
+template <>
+__global__ __launch_bounds__(64) void volume_march_kernel<PlainVolume>(const VolumeArgs g, const BoxArgs bx,
+                                                                       const float* __restrict__ orig,
+                                                                       const float* __restrict__ dirs, long long N, int n_steps,
+                                                                       float t_min, float* __restrict__ rgb,
+                                                                       float* __restrict__ depth, float* __restrict__ opacity) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const float4 o = reinterpret_cast<const float4*>(orig)[r], d = reinterpret_cast<const float4*>(dirs)[r];
+    float a, b;
+    bool hit = ray_box_hit(bx, o, d, &a, &b);
+    hit = hit && finite_f(o.x) && finite_f(o.y) && finite_f(o.z) && finite_f(d.x) && finite_f(d.y) && finite_f(d.z);
+    float cr = 0.0f, cg = 0.0f, cb = 0.0f, cd = 0.0f, T = 1.0f;
+    if (hit) {
+        const float delta = __fdiv_rn(__fsub_rn(b, a), (float)n_steps);
+        bool alive = true;
+        for (int k0 = 0; k0 < n_steps && alive; k0 += kAhead) {
+            CellFetch c[kAhead];
+            float z[kAhead];
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) {
+                z[u] = __fadd_rn(a, __fmul_rn(__fadd_rn((float)(k0 + u), 0.5f), delta));
+                volume_fetch(g, __fadd_rn(o.x, __fmul_rn(d.x, z[u])), __fadd_rn(o.y, __fmul_rn(d.y, z[u])),
+                             __fadd_rn(o.z, __fmul_rn(d.z, z[u])), &c[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) {
+                const float4 v = volume_value(c[u]);
+                const float e = expf(-__fmul_rn(v.w, delta));
+                const float alpha = __fsub_rn(1.0f, e);
+                const float w = __fmul_rn(alpha, T);
+                const bool on = alive && k0 + u < n_steps;
+                cr = on ? __fadd_rn(cr, __fmul_rn(w, v.x)) : cr;
+                cg = on ? __fadd_rn(cg, __fmul_rn(w, v.y)) : cg;
+                cb = on ? __fadd_rn(cb, __fmul_rn(w, v.z)) : cb;
+                cd = on ? __fadd_rn(cd, __fmul_rn(w, z[u])) : cd;
+                T = on ? __fmul_rn(T, __fsub_rn(1.0f, alpha)) : T;
+                alive = alive && !(on && T < t_min);
+            }
+        }
+    }
+    if (rgb) { rgb[3 * r + 0] = cr; rgb[3 * r + 1] = cg; rgb[3 * r + 2] = cb; }
+    if (depth) depth[r] = cd;
+    if (opacity) opacity[r] = __fsub_rn(1.0f, T);
+}
+
+constexpr int kShCornerAhead = 2;                            // eight lanes per ray: steps in flight
 
 // the value of the lane `Mask` away (1, 2: inside the quad, a DPP move; 4: a swizzle of the 32-lane half)
 template <int Mask>
@@ -360,7 +393,7 @@ __device__ __forceinline__ float4 lerp_lanes(float4 mine, float f, bool upper) {
 
 // ray = thread / 8, vertex = thread % 8 = dx + 2 dy + 4 dz; the eight lanes of a ray share every branch
 template <int L>
-__global__ __launch_bounds__(256) void sh_march_corner_kernel(const ShVolumeArgs g, const BoxArgs bx, const float* __restrict__ orig,
+__global__ __launch_bounds__(256) void sh_march_corner_kernel(const VolumeArgs g, const BoxArgs bx, const float* __restrict__ orig,
                                                               const float* __restrict__ dirs, long long N, int n_steps,
                                                               float t_min, float* __restrict__ rgb, float* __restrict__ depth,
                                                               float* __restrict__ opacity) {
@@ -375,9 +408,8 @@ __global__ __launch_bounds__(256) void sh_march_corner_kernel(const ShVolumeArgs
     const MarchRay m = march_ray(bx, orig, dirs, r, n_steps);
     MarchSums s;
     if (m.hit) {
-        float u[3], Y[sh_basis_count(L)];
-        sh_unit(m.d.x, m.d.y, m.d.z, u);
-        sh_basis<L>(u, Y);
+        float Y[ShVolume<L>::K];
+        ShVolume<L>::towards(m.d.x, m.d.y, m.d.z, Y);
         for (int k0 = 0; k0 < n_steps && s.alive; k0 += A) {
             float4 v[A];
             float z[A], f[A][3];
@@ -399,28 +431,29 @@ __global__ __launch_bounds__(256) void sh_march_corner_kernel(const ShVolumeArgs
     if (corner == 0) march_store(s, r, rgb, depth, opacity);
 }
 
-// The trilinear sampler at points (M, 3) -> out (M, 4), and the march of N rays (any of rgb (N, 3), depth (N), opacity (N)
-// nullable) through an (n, n, n, 4) volume over (lo3, hi3); the cell index is held in [0, n - 2] wherever the volume is read.
-void launch_volume_sample(const float* volume, int n, const float* lo3, const float* hi3, const float* points, long long M,
-                          float* out, hipStream_t stream) {
-    if (M <= 0) return;
-    hipLaunchKernelGGL(volume_sample_kernel, dim3(blocks_for(M)), dim3(kBs), 0, stream, volume_args(volume, n, lo3, hi3), points,
-                       M, out);
+// ---- launches ----
+// a stored format on the host: plain, or SH of a degree in 0..3 (volume_ok's check)
+struct VolumeFormat {
+    bool sh;
+    int degree;
+    size_t texel_bytes() const { return sh ? (size_t)sh_texel_floats(degree) * 4 : 16; }
+};
+
+// fn(Format{}) for the format's type
+template <class Fn>
+void with_format(VolumeFormat f, Fn&& fn) {
+    if (!f.sh) return fn(PlainVolume{});
+    switch (f.degree) {
+        case 0: return fn(ShVolume<0>{});
+        case 1: return fn(ShVolume<1>{});
+        case 2: return fn(ShVolume<2>{});
+        default: return fn(ShVolume<3>{});
+    }
 }
 
-void launch_volume_march(const float* volume, int n, const float* lo3, const float* hi3, float near_b, float far_b,
-                         const float* orig, const float* dirs, long long N, int n_steps, float t_min, float* rgb, float* depth,
-                         float* opacity, hipStream_t stream) {
-    if (N <= 0) return;
-    SceneBox box;
-    for (int a = 0; a < 3; ++a) { box.lo[a] = lo3[a]; box.hi[a] = hi3[a]; }
-    hipLaunchKernelGGL(volume_march_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, stream, volume_args(volume, n, lo3, hi3),
-                       box_args(box, near_b, far_b), orig, dirs, N, n_steps, t_min, rgb, depth, opacity);
-}
-
-// The SH forms of the two launches above; degree in 0..3 is the caller's check.  The mapping is chosen per degree by the time
-// of a 256 x 256 frame through n = 256 at 512 steps (profiles/sh_volume_measure.json), one lane against eight lanes per ray:
-// 0.42 / 1.28 ms at degree 0, 1.04 / 1.41 at 1, 1.92 / 1.85 at 2, 9.02 / 3.46 at 3 (256 VGPRs, one wavefront per SIMD).
+// The SH march's mapping is chosen per degree by the time of a 256 x 256 frame through n = 256 at 512 steps
+// (profiles/sh_volume_measure.json), one lane against eight lanes per ray: 0.42 / 1.28 ms at degree 0, 1.04 / 1.41 at 1,
+// 1.92 / 1.85 at 2, 9.02 / 3.46 at 3 (256 VGPRs, one wavefront per SIMD).
 // -DNERF_SH_MARCH_LANES=1 or 8 forces one mapping for every degree: the A/B builds of tools/sh_volume_measure.py.
 #ifdef NERF_SH_MARCH_LANES
 constexpr bool kShEightLanes[kShMaxDegree + 1] = {NERF_SH_MARCH_LANES == 8, NERF_SH_MARCH_LANES == 8, NERF_SH_MARCH_LANES == 8,
@@ -429,43 +462,38 @@ constexpr bool kShEightLanes[kShMaxDegree + 1] = {NERF_SH_MARCH_LANES == 8, NERF
 constexpr bool kShEightLanes[kShMaxDegree + 1] = {false, false, true, true};
 #endif
 
-template <int L>
-void launch_sh_degree(bool march, const ShVolumeArgs& g, const BoxArgs& bx, const float* a, const float* b, long long count,
-                      int n_steps, float t_min, float* out0, float* out1, float* out2, hipStream_t stream) {
-    if (!march) {
-        hipLaunchKernelGGL(sh_volume_sample_kernel<L>, dim3(blocks_for(count)), dim3(kBs), 0, stream, g, a, b, count, out0);
-    } else if (kShEightLanes[L]) {
-        hipLaunchKernelGGL(sh_march_corner_kernel<L>, dim3(blocks_for(8 * count)), dim3(kBs), 0, stream, g, bx, a, b, count, n_steps,
-                           t_min, out0, out1, out2);
-    } else {
-        hipLaunchKernelGGL(sh_march_ray_kernel<L>, dim3(blocks_for(count, 64)), dim3(64), 0, stream, g, bx, a, b, count, n_steps,
-                           t_min, out0, out1, out2);
-    }
+// The trilinear sampler at points (M, 3), seen along dirs (M, 3; the SH formats alone) -> out (M, 4), and the march of N rays
+// (any of rgb (N, 3), depth (N), opacity (N) nullable) through a volume over (lo3, hi3); the cell index is held in [0, n - 2]
+// wherever the volume is read.
+void launch_volume_sample(VolumeFormat f, const float* volume, int n, const float* lo3, const float* hi3, const float* points,
+                          const float* dirs, long long M, float* out, hipStream_t stream) {
+    if (M <= 0) return;
+    const VolumeArgs g = volume_args(volume, n, lo3, hi3);
+    with_format(f, [&](auto format) {
+        hipLaunchKernelGGL(volume_sample_kernel<decltype(format)>, dim3(blocks_for(M)), dim3(kBs), 0, stream, g, points, dirs, M, out);
+    });
 }
 
-void launch_sh(int degree, bool march, const ShVolumeArgs& g, const BoxArgs& bx, const float* a, const float* b, long long count,
-               int n_steps, float t_min, float* out0, float* out1, float* out2, hipStream_t stream) {
-    if (count <= 0) return;
-    switch (degree) {
-        case 0: launch_sh_degree<0>(march, g, bx, a, b, count, n_steps, t_min, out0, out1, out2, stream); break;
-        case 1: launch_sh_degree<1>(march, g, bx, a, b, count, n_steps, t_min, out0, out1, out2, stream); break;
-        case 2: launch_sh_degree<2>(march, g, bx, a, b, count, n_steps, t_min, out0, out1, out2, stream); break;
-        default: launch_sh_degree<3>(march, g, bx, a, b, count, n_steps, t_min, out0, out1, out2, stream); break;
-    }
-}
-
-void launch_sh_volume_sample(const float* volume, int n, int degree, const float* lo3, const float* hi3, const float* points,
-                             const float* dirs, long long M, float* out, hipStream_t stream) {
-    launch_sh(degree, false, sh_volume_args(volume, n, lo3, hi3), BoxArgs{}, points, dirs, M, 0, 0.f, out, nullptr, nullptr, stream);
-}
-
-void launch_sh_volume_march(const float* volume, int n, int degree, const float* lo3, const float* hi3, float near_b, float far_b,
-                            const float* orig, const float* dirs, long long N, int n_steps, float t_min, float* rgb, float* depth,
-                            float* opacity, hipStream_t stream) {
+void launch_volume_march(VolumeFormat f, const float* volume, int n, const float* lo3, const float* hi3, float near_b, float far_b,
+                         const float* orig, const float* dirs, long long N, int n_steps, float t_min, float* rgb, float* depth,
+                         float* opacity, hipStream_t stream) {
+    if (N <= 0) return;
     SceneBox box;
     for (int a = 0; a < 3; ++a) { box.lo[a] = lo3[a]; box.hi[a] = hi3[a]; }
-    launch_sh(degree, true, sh_volume_args(volume, n, lo3, hi3), box_args(box, near_b, far_b), orig, dirs, N, n_steps, t_min, rgb,
-              depth, opacity, stream);
+    const VolumeArgs g = volume_args(volume, n, lo3, hi3);
+    const BoxArgs bx = box_args(box, near_b, far_b);
+    with_format(f, [&](auto format) {
+        using Format = decltype(format);
+        if constexpr (Format::ViewDependent) {
+            if (kShEightLanes[Format::Degree]) {
+                hipLaunchKernelGGL(sh_march_corner_kernel<Format::Degree>, dim3(blocks_for(8 * N)), dim3(kBs), 0, stream, g, bx, orig,
+                                   dirs, N, n_steps, t_min, rgb, depth, opacity);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(volume_march_kernel<Format>, dim3(blocks_for(N, 64)), dim3(64), 0, stream, g, bx, orig, dirs, N, n_steps,
+                           t_min, rgb, depth, opacity);
+    });
 }
 
 }  // namespace
@@ -473,10 +501,21 @@ void launch_sh_volume_march(const float* volume, int n, int degree, const float*
 
 using namespace nerf;
 
+// ---- entry points: one body each for sample, march and render-image, over the format ----
+// the `what` of a refusal
+enum VolumeCall { kSample, kMarch, kRender };
+static const char* what_of(VolumeFormat f, VolumeCall call) {
+    static const char* const names[2][3] = {{"volume sample", "volume march", "volume render"},
+                                            {"SH volume sample", "SH volume march", "SH volume render"}};
+    return names[f.sh][call];
+}
+
 // the arguments every volume call shares
-static int volume_ok(const char* what, const float* volume, int32_t n, const float* lo3, const float* hi3) {
+static int volume_ok(const char* what, const float* volume, int32_t n, VolumeFormat f, const float* lo3, const float* hi3) {
     if (!volume || !lo3 || !hi3) return fail("NULL argument");
     if (int r = lattice_n_ok(what, n)) return r;
+    if (f.sh && (f.degree < 0 || f.degree > kShMaxDegree))
+        return fail("%s: degree must be in 0..%d (got %d)", what, kShMaxDegree, f.degree);
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a]) || !(lo3[a] < hi3[a]))
             return fail("%s needs finite lo < hi on every axis (axis %d: lo %g, hi %g)", what, a, lo3[a], hi3[a]);
@@ -490,53 +529,52 @@ static int march_ok(int32_t n_steps, float t_min, const float* rgb, const float*
     return 0;
 }
 
-extern "C" {
-
-int nerf_volume_sample(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
-                       int64_t M, float* out, int mem) {
+static int volume_sample(nerf_ctx* c, VolumeFormat f, const float* volume, int32_t n, const float* lo3, const float* hi3,
+                         const float* points, const float* dirs, int64_t M, float* out, int mem) {
     ENTER(c);
-    if (int r = volume_ok("volume sample", volume, n, lo3, hi3)) return r;
+    if (int r = volume_ok(what_of(f, kSample), volume, n, f, lo3, hi3)) return r;
     if (M < 0) return fail("bad shape M=%lld", (long long)M);
     if (M == 0) return 0;
-    if (!points || !out) return fail("NULL argument");
+    if (!points || (f.sh && !dirs) || !out) return fail("NULL argument");
     Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * f.texel_bytes());
     const float* p = st.in(c->b_in0, points, (size_t)M * 12);
+    const float* d = f.sh ? st.in(c->b_in1, dirs, (size_t)M * 12) : nullptr;
     float* o = st.out(c->b_raw, out, (size_t)M * 16);
     if (st.err) return st.err;
-    launch_volume_sample(vol, n, lo3, hi3, p, M, o, c->stream);
+    launch_volume_sample(f, vol, n, lo3, hi3, p, d, M, o, c->stream);
     HIP_OK(hipGetLastError());
     return st.finish();
 }
 
-int nerf_volume_march(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
-                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
-                      int mem) {
+static int volume_march(nerf_ctx* c, VolumeFormat f, const float* volume, int32_t n, const float* lo3, const float* hi3,
+                        const float* rays_orig, const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb,
+                        float* depth, float* opacity, int mem) {
     ENTER(c);
-    if (int r = volume_ok("volume march", volume, n, lo3, hi3)) return r;
+    if (int r = volume_ok(what_of(f, kMarch), volume, n, f, lo3, hi3)) return r;
     if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
     if (N < 0) return fail("bad shape N=%lld", (long long)N);
     if (N == 0) return 0;
     if (!rays_orig || !rays_dirs) return fail("NULL argument");
     Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * f.texel_bytes());
     const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
     const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
     float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
     float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
     float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
     if (st.err) return st.err;
-    launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb, ddepth, dopac,
-                        c->stream);
+    launch_volume_march(f, vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb, ddepth,
+                        dopac, c->stream);
     HIP_OK(hipGetLastError());
     return st.finish();
 }
 
-int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
-                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
-                             float* rgb, float* depth, float* opacity, int mem) {
+static int volume_render_image(nerf_ctx* c, VolumeFormat f, const float* volume, int32_t n, const float* lo3, const float* hi3,
+                               const float* c2w, float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count,
+                               int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity, int mem) {
     ENTER(c);
-    if (int r = volume_ok("volume render", volume, n, lo3, hi3)) return r;
+    if (int r = volume_ok(what_of(f, kRender), volume, n, f, lo3, hi3)) return r;
     if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
     if (!c2w) return fail("NULL argument");
     if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
@@ -548,7 +586,7 @@ int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const 
     if (int r = ensure(c, c->b_orig, (size_t)batch * 16)) return r;
     if (int r = ensure(c, c->b_dirs, (size_t)batch * 16)) return r;
     Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * 16);
+    const float* vol = st.in(c->b_lattice, volume, (size_t)n * n * n * f.texel_bytes());
     float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
     float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
     float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
@@ -558,7 +596,7 @@ int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const 
         const long long m = std::min(batch, N - off);
         launch_raygen(c2w, fov, H, W, ray_begin + off, m, o, d, c->stream);
         if (c->ray_space == NERF_RAYS_NDC) launch_rays_to_ndc(o, d, m, fov, c->ndc_near_plane, o, d, c->stream);
-        launch_volume_march(vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
+        launch_volume_march(f, vol, n, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
                             drgb ? drgb + 3 * off : nullptr, ddepth ? ddepth + off : nullptr, dopac ? dopac + off : nullptr,
                             c->stream);
     }
@@ -566,93 +604,42 @@ int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const 
     return st.finish();
 }
 
-}  // extern "C"
+extern "C" {
 
-// ---- the SH forms: the same checks in the same order, the degree after n ----
-static int sh_volume_ok(const char* what, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3) {
-    if (!volume || !lo3 || !hi3) return fail("NULL argument");
-    if (int r = lattice_n_ok(what, n)) return r;
-    if (degree < 0 || degree > kShMaxDegree) return fail("%s: degree must be in 0..%d (got %d)", what, kShMaxDegree, degree);
-    return volume_ok(what, volume, n, lo3, hi3);
+int nerf_volume_sample(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* points,
+                       int64_t M, float* out, int mem) {
+    return volume_sample(c, {false, 0}, volume, n, lo3, hi3, points, nullptr, M, out, mem);
 }
 
-static size_t sh_volume_bytes(int32_t n, int32_t degree) { return (size_t)n * n * n * sh_texel_floats(degree) * 4; }
+int nerf_volume_march(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* rays_orig,
+                      const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity,
+                      int mem) {
+    return volume_march(c, {false, 0}, volume, n, lo3, hi3, rays_orig, rays_dirs, N, n_steps, t_min, rgb, depth, opacity, mem);
+}
 
-extern "C" {
+int nerf_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, const float* lo3, const float* hi3, const float* c2w,
+                             float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count, int32_t n_steps, float t_min,
+                             float* rgb, float* depth, float* opacity, int mem) {
+    return volume_render_image(c, {false, 0}, volume, n, lo3, hi3, c2w, fov, H, W, ray_begin, ray_count, n_steps, t_min, rgb, depth,
+                               opacity, mem);
+}
 
 int nerf_sh_volume_sample(nerf_ctx* c, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3,
                           const float* points, const float* dirs, int64_t M, float* out, int mem) {
-    ENTER(c);
-    if (int r = sh_volume_ok("SH volume sample", volume, n, degree, lo3, hi3)) return r;
-    if (M < 0) return fail("bad shape M=%lld", (long long)M);
-    if (M == 0) return 0;
-    if (!points || !dirs || !out) return fail("NULL argument");
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, sh_volume_bytes(n, degree));
-    const float* p = st.in(c->b_in0, points, (size_t)M * 12);
-    const float* d = st.in(c->b_in1, dirs, (size_t)M * 12);
-    float* o = st.out(c->b_raw, out, (size_t)M * 16);
-    if (st.err) return st.err;
-    launch_sh_volume_sample(vol, n, degree, lo3, hi3, p, d, M, o, c->stream);
-    HIP_OK(hipGetLastError());
-    return st.finish();
+    return volume_sample(c, {true, degree}, volume, n, lo3, hi3, points, dirs, M, out, mem);
 }
 
 int nerf_sh_volume_march(nerf_ctx* c, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3,
                          const float* rays_orig, const float* rays_dirs, int64_t N, int32_t n_steps, float t_min, float* rgb,
                          float* depth, float* opacity, int mem) {
-    ENTER(c);
-    if (int r = sh_volume_ok("SH volume march", volume, n, degree, lo3, hi3)) return r;
-    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
-    if (N < 0) return fail("bad shape N=%lld", (long long)N);
-    if (N == 0) return 0;
-    if (!rays_orig || !rays_dirs) return fail("NULL argument");
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, sh_volume_bytes(n, degree));
-    const float* o = st.in(c->b_orig, rays_orig, (size_t)N * 16);
-    const float* d = st.in(c->b_dirs, rays_dirs, (size_t)N * 16);
-    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
-    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
-    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
-    if (st.err) return st.err;
-    launch_sh_volume_march(vol, n, degree, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, N, n_steps, t_min, drgb,
-                           ddepth, dopac, c->stream);
-    HIP_OK(hipGetLastError());
-    return st.finish();
+    return volume_march(c, {true, degree}, volume, n, lo3, hi3, rays_orig, rays_dirs, N, n_steps, t_min, rgb, depth, opacity, mem);
 }
 
 int nerf_sh_volume_render_image(nerf_ctx* c, const float* volume, int32_t n, int32_t degree, const float* lo3, const float* hi3,
                                 const float* c2w, float fov, int32_t H, int32_t W, int64_t ray_begin, int64_t ray_count,
                                 int32_t n_steps, float t_min, float* rgb, float* depth, float* opacity, int mem) {
-    ENTER(c);
-    if (int r = sh_volume_ok("SH volume render", volume, n, degree, lo3, hi3)) return r;
-    if (int r = march_ok(n_steps, t_min, rgb, depth, opacity)) return r;
-    if (!c2w) return fail("NULL argument");
-    if (H <= 0 || W <= 0) return fail("bad image size %dx%d", H, W);
-    const long long total = (long long)H * W;
-    if (ray_count <= 0) { ray_begin = 0; ray_count = total; }
-    if (ray_begin < 0 || ray_begin + ray_count > total) return fail("ray slab [%lld,+%lld) outside %lld rays",
-                                                                    (long long)ray_begin, (long long)ray_count, total);
-    const long long N = ray_count, batch = std::min<long long>(N, 1 << 18);
-    if (int r = ensure(c, c->b_orig, (size_t)batch * 16)) return r;
-    if (int r = ensure(c, c->b_dirs, (size_t)batch * 16)) return r;
-    Staging st(c, mem);
-    const float* vol = st.in(c->b_lattice, volume, sh_volume_bytes(n, degree));
-    float* drgb = st.out(c->b_out[0], rgb, (size_t)N * 12);
-    float* ddepth = st.out(c->b_out[1], depth, (size_t)N * 4);
-    float* dopac = st.out(c->b_out[2], opacity, (size_t)N * 4);
-    if (st.err) return st.err;
-    float *o = (float*)c->b_orig.p, *d = (float*)c->b_dirs.p;
-    for (long long off = 0; off < N; off += batch) {      // as nerf_volume_render_image
-        const long long m = std::min(batch, N - off);
-        launch_raygen(c2w, fov, H, W, ray_begin + off, m, o, d, c->stream);
-        if (c->ray_space == NERF_RAYS_NDC) launch_rays_to_ndc(o, d, m, fov, c->ndc_near_plane, o, d, c->stream);
-        launch_sh_volume_march(vol, n, degree, lo3, hi3, c->cfg.near_boundary, c->cfg.far_boundary, o, d, m, n_steps, t_min,
-                               drgb ? drgb + 3 * off : nullptr, ddepth ? ddepth + off : nullptr, dopac ? dopac + off : nullptr,
-                               c->stream);
-    }
-    HIP_OK(hipGetLastError());
-    return st.finish();
+    return volume_render_image(c, {true, degree}, volume, n, lo3, hi3, c2w, fov, H, W, ray_begin, ray_count, n_steps, t_min, rgb,
+                               depth, opacity, mem);
 }
 
 }  // extern "C"

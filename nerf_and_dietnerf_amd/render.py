@@ -630,18 +630,71 @@ class Context:
         return self._lattice("radiance lattice", self.lib.nerf_radiance_lattice, which, n, (4,),
                              [(view_dir, (3,), "view_dir"), (camera, (4, 4), "camera")], None, device_out)
 
+    # The volume calls below exist in two forms, for the plain (n, n, n, 4) volume and for the SH volume (n, n, n, C) further
+    # down: one body each, told which by ``sh``; the library's SH entry points take the degree after n.
     @staticmethod
-    def _volume_args(volume, lo, hi, what):
-        """(n, lo, hi as float32 (3,) arrays) of an (n, n, n, 4) volume over (lo, hi), checked as the library checks them."""
+    def _volume_args(volume, lo, hi, what, sh):
+        """(n, degree -- None for the plain format --, lo, hi as float32 (3,) arrays) of an (n, n, n, 4) volume or an SH volume
+        (n, n, n, C(degree)) over (lo, hi), checked as the library checks them."""
         shape = tuple(volume.shape)
-        if len(shape) != 4 or shape[3] != 4 or shape[0] != shape[1] or shape[0] != shape[2]:
+        cube = len(shape) == 4 and shape[0] == shape[1] and shape[0] == shape[2]
+        if sh and not cube:
+            raise ValueError(f"SH volume must be an (n, n, n, C) array, got {shape}")
+        if not sh and not (cube and shape[3] == 4):
             raise ValueError(f"volume must be an (n, n, n, 4) array, got {shape}")
+        degree = sh_degree_of(shape[3]) if sh else None
         if not 2 <= shape[0] <= 512:
             raise ValueError(f"{what}: n must be in 2..512 (got {shape[0]})")
         lo_a, hi_a = _box_corners(lo, hi)
         if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
             raise ValueError(f"{what} needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
-        return shape[0], lo_a, hi_a
+        return shape[0], degree, lo_a, hi_a
+
+    def _volume_call(self, name, pvol, n, degree, lo_a, hi_a, *rest):
+        """nerf_volume_<name>, or with a degree nerf_sh_volume_<name>, on the arguments every volume call begins with."""
+        if degree is None:
+            fn, head = getattr(self.lib, f"nerf_volume_{name}"), (self.h, pvol, n)
+        else:
+            fn, head = getattr(self.lib, f"nerf_sh_volume_{name}"), (self.h, pvol, n, degree)
+        _lib.check(fn(*head, lo_a.ctypes.data, hi_a.ctypes.data, *rest))
+
+    def _sample_volume(self, sh, volume, lo, hi, points, dirs=None):
+        arr = self._arrays(volume, points, dirs)
+        n, degree, lo_a, hi_a = self._volume_args(volume, lo, hi, "SH volume sample" if sh else "volume sample", sh)
+        m = int(points.shape[0])
+        pvol = arr.inp(volume, tuple(volume.shape))
+        pp = arr.inp(points, (m, 3))
+        pd = (arr.inp(dirs, (m, 3)),) if sh else ()
+        out, po = arr.out((m, 4))
+        self._volume_call("sample", pvol, n, degree, lo_a, hi_a, pp, *pd, m, po, arr.mem)
+        return out
+
+    def _march_volume(self, sh, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min):
+        arr = self._arrays(volume, rays_orig, rays_dirs)
+        n, degree, lo_a, hi_a = self._volume_args(volume, lo, hi, "SH volume march" if sh else "volume march", sh)
+        steps, t = self._march_args(n_steps, t_min)
+        nr = int(rays_orig.shape[0])
+        pvol = arr.inp(volume, tuple(volume.shape))
+        po, pd = arr.inp(rays_orig, (nr, 4)), arr.inp(rays_dirs, (nr, 4))
+        rgb, p0 = arr.out((nr, 3))
+        depth, p1 = arr.out((nr,))
+        opacity, p2 = arr.out((nr,))
+        self._volume_call("march", pvol, n, degree, lo_a, hi_a, po, pd, nr, steps, t, p0, p1, p2, arr.mem)
+        return rgb, depth, opacity
+
+    def _render_volume_image(self, sh, volume, lo, hi, c2w, fov, h, w, n_steps, t_min, ray_begin, ray_count):
+        arr = self._arrays(volume)
+        n, degree, lo_a, hi_a = self._volume_args(volume, lo, hi, "SH volume render" if sh else "volume render", sh)
+        steps, t = self._march_args(n_steps, t_min)
+        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
+        pvol = arr.inp(volume, tuple(volume.shape))
+        lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
+        rgb, p0 = arr.out(lead + (3,))
+        depth, p1 = arr.out(lead)
+        opacity, p2 = arr.out(lead)
+        self._volume_call("render_image", pvol, n, degree, lo_a, hi_a, c2w_h.ctypes.data, float(fov), int(h), int(w),
+                          int(ray_begin), int(ray_count), steps, t, p0, p1, p2, arr.mem)
+        return rgb, depth, opacity
 
     @staticmethod
     def _march_args(n_steps, t_min):
@@ -656,13 +709,7 @@ class Context:
         """The (n, n, n, 4) ``volume`` over the box (lo, hi) at ``points`` (M, 3), trilinear -> (M, 4); numpy or torch-device
         arrays.  A point outside the box takes the value of the nearest face, a NaN coordinate gives NaN
         (nerf_volume_sample has the rule).  A numpy volume is staged to the device on every call: keep it on the device."""
-        arr = self._arrays(volume, points)
-        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume sample")
-        m = int(points.shape[0])
-        pvol, pp = arr.inp(volume, (n, n, n, 4)), arr.inp(points, (m, 3))
-        out, po = arr.out((m, 4))
-        _lib.check(self.lib.nerf_volume_sample(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, pp, m, po, arr.mem))
-        return out
+        return self._sample_volume(False, volume, lo, hi, points)
 
     def march_volume(self, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min=0.0):
         """Rays (N, 4) marched through the (n, n, n, 4) ``volume`` over the box (lo, hi) in ``n_steps`` equal steps of the
@@ -671,37 +718,14 @@ class Context:
         ray that misses the box gives zeros.  ``t_min`` in [0, 1): a ray stops once its transmittance falls below it, which
         changes rgb and opacity by at most t_min (nerf_volume_march has the rule).  A numpy volume is staged to the device on
         every call: keep it on the device."""
-        arr = self._arrays(volume, rays_orig, rays_dirs)
-        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume march")
-        steps, t = self._march_args(n_steps, t_min)
-        nr = int(rays_orig.shape[0])
-        pvol = arr.inp(volume, (n, n, n, 4))
-        po, pd = arr.inp(rays_orig, (nr, 4)), arr.inp(rays_dirs, (nr, 4))
-        rgb, p0 = arr.out((nr, 3))
-        depth, p1 = arr.out((nr,))
-        opacity, p2 = arr.out((nr,))
-        _lib.check(self.lib.nerf_volume_march(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, po, pd, nr, steps, t, p0, p1,
-                                              p2, arr.mem))
-        return rgb, depth, opacity
+        return self._march_volume(False, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min)
 
     def render_volume_image(self, volume, lo, hi, c2w, fov, h, w, n_steps, t_min=0.0, ray_begin=0, ray_count=0):
         """march_volume of the rays render_image makes for camera ``c2w`` (through rays_to_ndc on an "ndc" context), generated
         on the device -> (rgb, depth, opacity) shaped (h, w, ...), or (ray_count, ...) for a slab of rays; equal to
         get_rays_directions + march_volume bit for bit.  A numpy volume is staged to the device on every call: keep it on the
         device."""
-        arr = self._arrays(volume)
-        n, lo_a, hi_a = self._volume_args(volume, lo, hi, "volume render")
-        steps, t = self._march_args(n_steps, t_min)
-        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
-        pvol = arr.inp(volume, (n, n, n, 4))
-        lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
-        rgb, p0 = arr.out(lead + (3,))
-        depth, p1 = arr.out(lead)
-        opacity, p2 = arr.out(lead)
-        _lib.check(self.lib.nerf_volume_render_image(self.h, pvol, n, lo_a.ctypes.data, hi_a.ctypes.data, c2w_h.ctypes.data,
-                                                     float(fov), int(h), int(w), int(ray_begin), int(ray_count), steps, t, p0,
-                                                     p1, p2, arr.mem))
-        return rgb, depth, opacity
+        return self._render_volume_image(False, volume, lo, hi, c2w, fov, h, w, n_steps, t_min, ray_begin, ray_count)
 
     # ---- SH radiance volume: view-dependent colour as spherical harmonics per vertex (include/nerf_mi355.h:
     # nerf_sh_radiance_lattice has the format, nerf_sh_volume_sample the rule) ----
@@ -735,66 +759,21 @@ class Context:
             return self.lib.nerf_sh_radiance_lattice(h, which_, n_, degree, dirs_a.ctypes.data, proj_a.ctypes.data, d, out, mem)
         return self._lattice("SH radiance lattice", entry, which, n, (sh_texel_floats(degree),), [], None, device_out)
 
-    @staticmethod
-    def _sh_volume_args(volume, lo, hi, what):
-        """(n, degree, lo, hi) of an (n, n, n, C(degree)) volume, checked as the library checks them."""
-        shape = tuple(volume.shape)
-        if len(shape) != 4 or shape[0] != shape[1] or shape[0] != shape[2]:
-            raise ValueError(f"SH volume must be an (n, n, n, C) array, got {shape}")
-        degree = sh_degree_of(shape[3])
-        if not 2 <= shape[0] <= 512:
-            raise ValueError(f"{what}: n must be in 2..512 (got {shape[0]})")
-        lo_a, hi_a = _box_corners(lo, hi)
-        if not (np.isfinite(lo_a).all() and np.isfinite(hi_a).all() and (lo_a < hi_a).all()):
-            raise ValueError(f"{what} needs finite lo < hi on every axis (lo {lo_a.tolist()}, hi {hi_a.tolist()})")
-        return shape[0], degree, lo_a, hi_a
-
     def sample_sh_volume(self, volume, lo, hi, points, dirs):
         """The SH ``volume`` (n, n, n, C) over the box (lo, hi) at ``points`` (M, 3) seen along ``dirs`` (M, 3, any length; a zero
         or non-finite direction counts as (0, 0, 1)) -> (M, 4): the colour, clamped to [0, 1], and the density; numpy or
         torch-device arrays (nerf_sh_volume_sample has the rule).  The degree follows from C."""
-        arr = self._arrays(volume, points, dirs)
-        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume sample")
-        m = int(points.shape[0])
-        pvol = arr.inp(volume, tuple(volume.shape))
-        pp, pd = arr.inp(points, (m, 3)), arr.inp(dirs, (m, 3))
-        out, po = arr.out((m, 4))
-        _lib.check(self.lib.nerf_sh_volume_sample(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data, pp, pd, m, po,
-                                                  arr.mem))
-        return out
+        return self._sample_volume(True, volume, lo, hi, points, dirs)
 
     def march_sh_volume(self, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min=0.0):
         """march_volume through an SH ``volume`` (n, n, n, C): every sample's colour is the volume's towards the ray's own
         direction -> (rgb (N, 3), depth (N,), opacity (N,)) (nerf_sh_volume_march)."""
-        arr = self._arrays(volume, rays_orig, rays_dirs)
-        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume march")
-        steps, t = self._march_args(n_steps, t_min)
-        nr = int(rays_orig.shape[0])
-        pvol = arr.inp(volume, tuple(volume.shape))
-        po, pd = arr.inp(rays_orig, (nr, 4)), arr.inp(rays_dirs, (nr, 4))
-        rgb, p0 = arr.out((nr, 3))
-        depth, p1 = arr.out((nr,))
-        opacity, p2 = arr.out((nr,))
-        _lib.check(self.lib.nerf_sh_volume_march(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data, po, pd, nr, steps,
-                                                 t, p0, p1, p2, arr.mem))
-        return rgb, depth, opacity
+        return self._march_volume(True, volume, lo, hi, rays_orig, rays_dirs, n_steps, t_min)
 
     def render_sh_volume_image(self, volume, lo, hi, c2w, fov, h, w, n_steps, t_min=0.0, ray_begin=0, ray_count=0):
         """render_volume_image through an SH ``volume`` (n, n, n, C): equal to get_rays_directions + march_sh_volume bit for
         bit (nerf_sh_volume_render_image)."""
-        arr = self._arrays(volume)
-        n, degree, lo_a, hi_a = self._sh_volume_args(volume, lo, hi, "SH volume render")
-        steps, t = self._march_args(n_steps, t_min)
-        c2w_h = _host_floats(c2w, (4, 4), "c2w", exact=True)
-        pvol = arr.inp(volume, tuple(volume.shape))
-        lead = (int(h), int(w)) if ray_count <= 0 else (int(ray_count),)
-        rgb, p0 = arr.out(lead + (3,))
-        depth, p1 = arr.out(lead)
-        opacity, p2 = arr.out(lead)
-        _lib.check(self.lib.nerf_sh_volume_render_image(self.h, pvol, n, degree, lo_a.ctypes.data, hi_a.ctypes.data,
-                                                        c2w_h.ctypes.data, float(fov), int(h), int(w), int(ray_begin),
-                                                        int(ray_count), steps, t, p0, p1, p2, arr.mem))
-        return rgb, depth, opacity
+        return self._render_volume_image(True, volume, lo, hi, c2w, fov, h, w, n_steps, t_min, ray_begin, ray_count)
 
     def ray_occupancy_bounds(self, rays_orig, rays_dirs):
         """Rays (N,4) -> (bounds (N,2) float32, state (N,) int32) under the context's box, grid and bounds: state 2 and the

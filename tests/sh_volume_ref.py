@@ -1,15 +1,15 @@
 """Test-side restatement of the SH radiance volume (include/nerf_mi355.h: nerf_sh_radiance_lattice has the format, the basis and
 the direction rule, nerf_sh_volume_sample the per-point rule): direction normalisation, the basis, the bake's projection sum,
 the sampler and the march, in numpy float32 with the kernels' operations in the kernels' order, every operation rounded on its
-own.  The cell, the lerp, the march's bar and the tests' media and rays are tests/volume_ref.py's; nothing here touches the
-library.
+own.  The cell and the lerps (trilinear), the march itself, its bar and the tests' media and rays are tests/volume_ref.py's;
+nothing here touches the library.
 
 A volume is (n, n, n, C) indexed [iz, iy, ix, channel]: channel 3 k + c the coefficient of basis function k for colour c,
 channel 3 K the density, zeros after it; K = (L + 1)^2, C = 4 ceil((3 K + 1) / 4)."""
 import numpy as np
 
-from scene_box_ref import ray_box_interval
-from volume_ref import F, _cell, _lerp, lattice_step, march_bar, random_volume, rays_through_box  # noqa: F401 (re-exported)
+from scene_box_ref import ray_box_interval  # noqa: F401 (re-exported)
+from volume_ref import F, march as volume_march, march_bar, random_volume, rays_through_box, trilinear  # noqa: F401 (re-exported)
 
 MAX_DEGREE, MAX_DIRS, CHUNK_POINTS = 3, 64, 1 << 20
 C0 = F(0.28209479177387814)
@@ -132,29 +132,16 @@ def clamp01(x):
 
 def sample_unclamped(volume, lo, hi, points, y):
     """(M, 4) before the clamp, with the basis values y (M, K) given."""
-    v, p = np.asarray(volume, F), np.asarray(points, F)
-    n, degree = v.shape[0], degree_of(v)
-    k = basis_count(degree)
-    lo, step = np.asarray(lo, F), lattice_step(lo, hi, n)
-    ix, fx = _cell(p[:, 0], lo[0], step[0], n)
-    iy, fy = _cell(p[:, 1], lo[1], step[1], n)
-    iz, fz = _cell(p[:, 2], lo[2], step[2], n)
-    assert min(ix.min(), iy.min(), iz.min()) >= 0 and max(ix.max(), iy.max(), iz.max()) <= n - 2
+    k = basis_count(degree_of(np.asarray(volume)))
 
-    def vertex(dz, dy, dx):
-        t = v[iz + dz, iy + dy, ix + dx]
+    def vertex(t):
         coef = t[:, :3 * k].reshape(-1, k, 3)
         with np.errstate(all="ignore"):
             acc = (y[:, 0, None] * coef[:, 0]).astype(F)
             for b in range(1, k):
                 acc = (acc + (y[:, b, None] * coef[:, b]).astype(F)).astype(F)
         return np.concatenate([acc, t[:, 3 * k, None]], axis=1)
-    fx, fy, fz = fx[:, None], fy[:, None], fz[:, None]
-    v00 = _lerp(vertex(0, 0, 0), vertex(0, 0, 1), fx)
-    v10 = _lerp(vertex(0, 1, 0), vertex(0, 1, 1), fx)
-    v01 = _lerp(vertex(1, 0, 0), vertex(1, 0, 1), fx)
-    v11 = _lerp(vertex(1, 1, 0), vertex(1, 1, 1), fx)
-    return _lerp(_lerp(v00, v10, fy), _lerp(v01, v11, fy), fz)
+    return trilinear(volume, lo, hi, points, vertex)
 
 
 def sample(volume, lo, hi, points, dirs, y=None):
@@ -169,34 +156,16 @@ def sample(volume, lo, hi, points, dirs, y=None):
 def march(volume, lo, hi, near, far, rays_orig, rays_dirs, n_steps, t_min=0.0, exp=None, count_clamped=None):
     """volume_ref.march with this module's sample; u and Y once per ray.  ``count_clamped``: a list that receives the number of
     live samples whose colour the clamp changed."""
-    o, d = np.asarray(rays_orig, F), np.asarray(rays_dirs, F)
-    exp = exp or (lambda x: np.exp(x.astype(F)).astype(F))
-    a, b, hit, _ = ray_box_interval(o, d, lo, hi, near, far)
-    hit = hit & np.isfinite(o[:, :3]).all(axis=1) & np.isfinite(d[:, :3]).all(axis=1)
-    y = basis(degree_of(np.asarray(volume)), unit(d))
-    n = o.shape[0]
-    rgb, depth, T = np.zeros((n, 3), F), np.zeros(n, F), np.ones(n, F)
-    alive = hit.copy()
-    t_min = F(t_min)
-    clamped = 0
-    with np.errstate(all="ignore"):
-        delta = ((b - a).astype(F) / F(n_steps)).astype(F)
-        for k in range(n_steps):
-            if not alive.any():
-                break
-            z = (a + ((F(k) + F(0.5)) * delta).astype(F)).astype(F)
-            p = (o[:, :3] + (d[:, :3] * z[:, None]).astype(F)).astype(F)
-            raw = sample_unclamped(volume, lo, hi, np.where(alive[:, None], p, F(0)), y)
-            v = raw.copy()
-            v[:, :3] = clamp01(raw[:, :3])
-            clamped += int((v[alive, :3] != raw[alive, :3]).any(axis=1).sum())
-            e = exp(-(v[:, 3] * delta).astype(F))
-            alpha = (F(1) - e).astype(F)
-            w = (alpha * T).astype(F)
-            rgb = np.where(alive[:, None], (rgb + (w[:, None] * v[:, :3]).astype(F)).astype(F), rgb)
-            depth = np.where(alive, (depth + (w * z).astype(F)).astype(F), depth)
-            T = np.where(alive, (T * (F(1) - alpha).astype(F)).astype(F), T)
-            alive = alive & ~(T < t_min)
+    y = basis(degree_of(np.asarray(volume)), unit(np.asarray(rays_dirs, F)))
+    clamped = [0]
+
+    def value(p, alive):
+        raw = sample_unclamped(volume, lo, hi, p, y)
+        v = raw.copy()
+        v[:, :3] = clamp01(raw[:, :3])
+        clamped[0] += int((v[alive, :3] != raw[alive, :3]).any(axis=1).sum())
+        return v
+    out = volume_march(volume, lo, hi, near, far, rays_orig, rays_dirs, n_steps, t_min, exp, value)
     if count_clamped is not None:
-        count_clamped.append(clamped)
-    return rgb, depth, (F(1) - T).astype(F)
+        count_clamped.append(clamped[0])
+    return out

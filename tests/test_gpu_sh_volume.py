@@ -2,8 +2,6 @@
 bake against the public point queries (mesh_colors, density_lattice) and the restatement's projection sum bit for bit -- also
 across the chunk seam --, the march against the restatement up to expf, the invariances (zero padding, batching, host /
 device arrays, the image call), the refusals, and NeRF.bake_preview(sh_degree=...) / render_preview on the shipped checkpoint."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -11,14 +9,12 @@ from isosurface_ref import lattice_points
 from occupancy_ref import GOLDEN_BOX
 import sh_volume_ref as SH
 import support as S
-from volume_ref import HI, LO, march_bar, rays_through_box
+from volume_ref import FAR, HI, LO, NEAR, march_bar, march_rays, rays_through_box, same_f32, sample_points
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-NEAR, FAR = 0.5, 4.5            # as tests/test_gpu_volume.py: rays from the radius-4 sphere enter near 3 and some leave past 4.5
 DEGREES = (0, 1, 2, 3)
-same_f32 = functools.partial(S.assert_same_bits, dtype=F)
 
 
 @pytest.fixture(scope="module")
@@ -31,28 +27,6 @@ def ctx():
 
 
 # ---- 1. sampling equals the restatement bit for bit -----------------------------------------------------------------------------
-def sample_points(n, m=257, seed=0):
-    """The recipe of tests/test_gpu_volume.py: vertices, points on faces, points outside on every side, NaN and +-Inf
-    coordinates, and random points in and around the box -> ((m, 3), which have a NaN)."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(LO, F), np.array(HI, F)
-    vertices = lattice_points(LO, HI, n)
-    vertices = vertices[rng.permutation(len(vertices))[:32]]
-    inner = rng.uniform(lo, hi, (32, 3)).astype(F)
-    faces = inner.copy()
-    for k in range(len(faces)):
-        faces[k, k % 3] = (lo, hi)[(k // 3) % 2][k % 3]
-    outside = inner[:12].copy()
-    for k in range(12):
-        outside[k, k % 3] = (lo - F(0.5 + k), hi + F(0.25 + k))[(k // 3) % 2][k % 3]
-    odd = np.array([[np.nan, 0, 0], [0, np.nan, 0], [0, 0, np.nan], [np.nan, np.nan, np.nan], [np.inf, 0, 0], [0, -np.inf, 0],
-                    [0, 0, np.inf], [-np.inf, np.inf, -np.inf], [3e38, -3e38, 0]], F)
-    fixed = np.concatenate([vertices, faces, outside, odd])
-    rest = rng.uniform(lo - F(0.3), hi + F(0.3), (m - len(fixed), 3)).astype(F)
-    p = np.concatenate([fixed, rest])
-    return p, np.isnan(p).any(axis=1)
-
-
 def sample_dirs(m=257, seed=1):
     """Unit, un-normalised (1e-3 .. 1e3), axis-aligned, zero, non-finite and overflowing directions -> (m, 3), shuffled so
     that the odd ones do not meet the odd points."""
@@ -174,25 +148,6 @@ def test_bake_across_the_chunk_seam():
 
 
 # ---- 4. the march against the restatement -----------------------------------------------------------------------------------------
-def march_rays(n_rays, seed):
-    """The recipe of tests/test_gpu_volume.py: hits from the radius-4 sphere (some leave past FAR), origins inside the box and
-    close to it (cut by NEAR), misses, rays with a direction component exactly 0 inside and outside that slab, one NaN ray,
-    every fifth direction un-normalised -> (o, d)."""
-    rng = np.random.default_rng(seed)
-    special_o = np.array([[0.2, -0.3, 0.1, 1], [0.0, 0.1, 0.3, 1], [0.5, 0.2, 1.6, 1],
-                          [3.0, 0.0, 4.0, 1], [0.0, 0.0, 4.0, 1], [0.0, 0.0, -4.0, 1],
-                          [0.3, 0.2, 4.0, 1], [1.5, 0.2, 4.0, 1], [0.3, 0.2, 4.0, 1],
-                          [np.nan, 0.0, 4.0, 1]], F)
-    special_d = np.array([[0.3, 0.5, -0.8, 0], [-1, 0, 0, 0], [0.0, 0.1, -1, 0],
-                          [0, 0, -1, 0], [0, 0, 1, 0], [0, 0, -1, 0],
-                          [0, 0, -1, 0], [0, 0, -1, 0], [-0.0, -0.0, -1, 0],
-                          [0, 0, -1, 0]], F)
-    o, d = rays_through_box(n_rays - len(special_o), seed)
-    d[::5] *= F(1.7)
-    order = rng.permutation(n_rays)
-    return np.concatenate([o, special_o])[order], np.concatenate([d, special_d])[order]
-
-
 @pytest.mark.parametrize("n,n_rays", [(5, 37), (9, 257)])
 @pytest.mark.parametrize("degree", DEGREES)
 def test_march_against_the_restatement(ctx, degree, n, n_rays):

@@ -2,22 +2,18 @@
 bake against the public point queries (density_lattice, mesh_colors, model_predict), the march against the restatement up to
 expf, early termination, invariance under batching / host-device / the image call, the refusals, and NeRF.bake_preview /
 render_preview on the shipped checkpoint."""
-import functools
-
 import numpy as np
 import pytest
 
 from occupancy_ref import GOLDEN_BOX
 import support as S
 import volume_ref as V
-from volume_ref import HI, LO, march_bar, random_volume, rays_through_box
+from volume_ref import FAR, HI, LO, NEAR, march_bar, march_rays, random_volume, rays_through_box, same_f32, sample_points
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-NEAR, FAR = 0.5, 4.5            # the march's context: rays from the radius-4 sphere enter near 3 and some leave past 4.5
 VIEW = (0.6, -0.48, 0.64)
-same_f32 = functools.partial(S.assert_same_bits, dtype=F)      # what the library returns is float32 already
 
 
 @pytest.fixture(scope="module")
@@ -30,27 +26,6 @@ def ctx():
 
 
 # ---- 1. sampling equals the restatement bit for bit -----------------------------------------------------------------------------
-def sample_points(n, m=257, seed=0):
-    """Vertices, points on faces, points outside on every side, NaN and +-Inf coordinates, and random points in and around the
-    box -> (m, 3)."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(LO, F), np.array(HI, F)
-    vertices = V.lattice_points(LO, HI, n)
-    vertices = vertices[rng.permutation(len(vertices))[:32]]
-    inner = rng.uniform(lo, hi, (32, 3)).astype(F)
-    faces = inner.copy()
-    for k in range(len(faces)):
-        faces[k, k % 3] = (lo, hi)[(k // 3) % 2][k % 3]
-    outside = inner[:12].copy()
-    for k in range(12):
-        outside[k, k % 3] = (lo - F(0.5 + k), hi + F(0.25 + k))[(k // 3) % 2][k % 3]
-    odd = np.array([[np.nan, 0, 0], [0, np.nan, 0], [0, 0, np.nan], [np.nan, np.nan, np.nan], [np.inf, 0, 0], [0, -np.inf, 0],
-                    [0, 0, np.inf], [-np.inf, np.inf, -np.inf], [3e38, -3e38, 0]], F)
-    fixed = np.concatenate([vertices, faces, outside, odd])
-    rest = rng.uniform(lo - F(0.3), hi + F(0.3), (m - len(fixed), 3)).astype(F)
-    return np.concatenate([fixed, rest]), np.isnan(np.concatenate([fixed, rest])).any(axis=1)
-
-
 @pytest.mark.parametrize("n", [2, 3, 9])
 def test_sampling_equals_the_restatement(ctx, n):
     v = random_volume(n, n)
@@ -148,24 +123,6 @@ def test_bake_camera_mode(oracle, precision, inside):
 
 
 # ---- 4. the march against the restatement -----------------------------------------------------------------------------------------
-def march_rays(n_rays, seed):
-    """Hits from the radius-4 sphere (some leave past FAR), origins inside the box and close to it (cut by NEAR), misses, rays
-    with a direction component exactly 0 inside and outside that slab, one NaN ray -> (o, d, category names)."""
-    rng = np.random.default_rng(seed)
-    special_o = np.array([[0.2, -0.3, 0.1, 1], [0.0, 0.1, 0.3, 1], [0.5, 0.2, 1.6, 1],       # inside, inside, just outside
-                          [3.0, 0.0, 4.0, 1], [0.0, 0.0, 4.0, 1], [0.0, 0.0, -4.0, 1],       # three misses
-                          [0.3, 0.2, 4.0, 1], [1.5, 0.2, 4.0, 1], [0.3, 0.2, 4.0, 1],        # d_x = d_y = 0: in, out, -0.0
-                          [np.nan, 0.0, 4.0, 1]], F)
-    special_d = np.array([[0.3, 0.5, -0.8, 0], [-1, 0, 0, 0], [0.0, 0.1, -1, 0],
-                          [0, 0, -1, 0], [0, 0, 1, 0], [0, 0, -1, 0],
-                          [0, 0, -1, 0], [0, 0, -1, 0], [-0.0, -0.0, -1, 0],
-                          [0, 0, -1, 0]], F)
-    o, d = rays_through_box(n_rays - len(special_o), seed)
-    d[::5] *= F(1.7)                                                          # un-normalised directions
-    order = rng.permutation(n_rays)
-    return np.concatenate([o, special_o])[order], np.concatenate([d, special_d])[order]
-
-
 @pytest.mark.parametrize("n,n_rays", [(5, 37), (9, 257)])
 def test_march_against_the_restatement(ctx, n, n_rays):
     v = random_volume(n, 10 + n)

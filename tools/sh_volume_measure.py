@@ -2,14 +2,17 @@
 checkpoint, fine network, f16x3, device-resident arrays, times by a host clock around a device synchronise:
   bake      NeRF.bake_preview(n, sh_degree=L), default table, L = 0..3 at n = 128 and 256: median of three calls after one
             warm-up call
-  frame     a 256 x 256 preview frame of the test pose through the n = 256 volume at 512 steps per ray and t_min = 1 / 512, for
-            L = 0..3, beside the degree-less march (camera bake) and the network frame at 64 + 128 samples under the same box,
+  frame     a 256 x 256 preview frame of the test pose through the n = 256 volume at 512 steps per ray, t_min = 0 and 1 / 512, for
+            L = 0..3 and the degree-less march (camera bake), beside the network frame at 64 + 128 samples under the same box,
             all alternating inside each of ten rounds after two warm-up rounds; the march's gather rate: (rays that hit the box)
             x 512 steps x 8 texels x the texel's bytes over the frame time at t_min = 0
-  mappings  the same frames (SH only, t_min = 0 and 1 / 512) in fresh processes, alternating between two builds of this
+  mappings  the marched frames (SH and plain, t_min = 0 and 1 / 512) in fresh processes, alternating between two builds of this
             library that force one mapping of the march for every degree, -DNERF_SH_MARCH_LANES=8 (eight lanes per ray) and
             =1 (one lane per ray), two processes each; the two must give the same bits as each other and as the shipped
             choice, and a checksum of every frame says so
+  parent_lib  the same frames in fresh processes alternating between a build of the parent commit's library and this tree's,
+            three each: whether every frame has the same bits in all six, and per frame whether the median of this tree's
+            process medians exceeds the parent's by more than the range of the parent's own three
   bench     bench.py --gpus 1 in fresh processes alternating between a checkout of the parent commit (built) and this tree,
             two each
   quality   at the fixture's resolution, n = 128 and 256 with 2 n steps and t_min = 1 / 512, at the golden test pose and at
@@ -17,9 +20,11 @@ checkpoint, fine network, f16x3, device-resident arrays, times by a host clock a
             pose, over the whole frame and over the pixels the preview leaves opaque, for a constant-direction bake, a camera
             bake made AT THE GOLDEN POSE, and SH degrees 0..3 with the default table
 
-    python tools/sh_volume_measure.py [OUT.json] [--lanes1-lib LIB.so --lanes8-lib LIB.so] [--parent-tree DIR]
+    python tools/sh_volume_measure.py [OUT.json] [--lanes1-lib LIB.so --lanes8-lib LIB.so] [--parent-lib LIB.so]
+                                      [--parent-tree DIR] [--fresh-processes-only]
 (default OUT: sh_volume_measure.json in the current directory; a section whose libraries or tree are not given is recorded as
-"not measured").  A forced build: make -C nerf_and_dietnerf_amd/csrc EXTRA=-DNERF_SH_MARCH_LANES=1 OUT=<dir> BUILD=<dir>."""
+"not measured"; --fresh-processes-only leaves out bake, frame and quality, the sections this process measures itself).  A
+forced build: make -C nerf_and_dietnerf_amd/csrc EXTRA=-DNERF_SH_MARCH_LANES=1 OUT=<dir> BUILD=<dir>."""
 import argparse
 import hashlib
 import json
@@ -93,33 +98,33 @@ def time_round_robin(model, calls, rounds=10, warmup=2):
     return {k: stats(v) for k, v in times.items()}
 
 
-def sh_frames(model, ck, with_others):
-    """The frame section: every SH degree's n = 256 volume resident, marched in turn (with_others: beside the plain march
-    and the network frame) -> (stats, checksums of every SH frame's rgb)."""
+T_MINS = (("t_min_0", 0.0), ("t_min_1_512", T_MIN))
+
+
+def sh_frames(model, ck, network):
+    """The frame section: every SH degree's n = 256 volume resident, marched in turn beside the plain march (camera bake)
+    and, with ``network``, the network frame -> (stats, checksums of every marched frame's rgb)."""
     c2w, fov = ck["c2w_test"], float(ck["fov"])
     ctx = model.ctx
-    volumes = {}
+    calls = {}
     for degree in DEGREES:
         model.bake_preview(256, sh_degree=degree)
-        volumes[degree] = model._preview
-    calls, sums = {}, {}
-    for degree in DEGREES:
-        vol, lo, hi, _ = volumes[degree]
-        for name, t_min in (("t_min_0", 0.0), ("t_min_1_512", T_MIN)):
+        vol, lo, hi, _ = model._preview
+        for name, t_min in T_MINS:
             calls[f"sh{degree}_{name}"] = (lambda v=vol, t=t_min: ctx.render_sh_volume_image(v, lo, hi, c2w, fov, H, W, 512, t))
-            rgb = calls[f"sh{degree}_{name}"]()[0]
-            sums[f"sh{degree}_{name}"] = hashlib.sha256(rgb.cpu().numpy().tobytes()).hexdigest()[:16]
-    if with_others:
-        model.bake_preview(256, camera=c2w)
-        plain, lo, hi, _ = model._preview
-        calls["plain_t_min_1_512"] = lambda: ctx.render_volume_image(plain, lo, hi, c2w, fov, H, W, 512, T_MIN)
+    model.bake_preview(256, camera=c2w)
+    plain, lo, hi, _ = model._preview
+    for name, t_min in T_MINS:
+        calls[f"plain_{name}"] = (lambda t=t_min: ctx.render_volume_image(plain, lo, hi, c2w, fov, H, W, 512, t))
+    sums = {k: hashlib.sha256(call()[0].cpu().numpy().tobytes()).hexdigest()[:16] for k, call in calls.items()}
+    if network:
         calls["network_64_128"] = lambda: model.render_image(c2w, fov, H, W, seed=0, device_out=True, rgb_only=True)
     return time_round_robin(model, calls), sums
 
 
 def child_frames(out_path):
     model, ck = make_model()
-    frames, sums = sh_frames(model, ck, with_others=False)
+    frames, sums = sh_frames(model, ck, network=False)
     model.ctx.close()
     with open(out_path, "w") as f:
         json.dump({"frames": frames, "checksums": sums}, f)
@@ -148,23 +153,34 @@ def main():
     ap.add_argument("--lanes1-lib")
     ap.add_argument("--lanes8-lib")
     ap.add_argument("--parent-tree")
+    ap.add_argument("--parent-lib")
+    ap.add_argument("--fresh-processes-only", action="store_true")
     ap.add_argument("--child-frames")
     args = ap.parse_args()
     if args.child_frames:
         return child_frames(args.child_frames)
     out_path = os.path.abspath(args.out)
     os.makedirs(os.path.dirname(out_path), exist_ok=True)
-    import torch
-    from nerf_and_dietnerf_amd import sh_quadrature, sh_texel_floats
-    res = {"what": "SH radiance volume: bake, preview frame, the two march mappings, bench.py against the parent, preview "
-                   "quality; shipped epoch-95 checkpoint, fine network, f16x3, device-resident arrays, one MI355X; host clock "
-                   "around a device synchronise",
-           "command": "python tools/sh_volume_measure.py", "box": BOX, "t_min": T_MIN}
+    sections = "" if args.fresh_processes_only else "bake, preview frame, preview quality, "
+    res = {"what": f"SH radiance volume: {sections}the two march mappings, the parent commit's library against this one, bench.py "
+                   "against the parent; shipped epoch-95 checkpoint, fine network, f16x3, device-resident arrays, one MI355X; "
+                   "host clock around a device synchronise",
+           "command": "python tools/sh_volume_measure.py" + (" --fresh-processes-only" if args.fresh_processes_only else ""),
+           "box": BOX, "t_min": T_MIN}
 
     def save():
         with open(out_path, "w") as f:
             json.dump(res, f, indent=1)
 
+    sums = None if args.fresh_processes_only else one_process_sections(res, save)
+    fresh_process_sections(args, res, save, sums, out_path)
+    print(json.dumps(res, indent=1))
+
+
+def one_process_sections(res, save):
+    """bake, frame and quality, in this process -> the checksums of the frame section."""
+    import torch
+    from nerf_and_dietnerf_amd import sh_quadrature, sh_texel_floats
     model, ck = make_model()
     c2w, fov = ck["c2w_test"], float(ck["fov"])
     # ---- bake ----
@@ -181,7 +197,7 @@ def main():
             torch.cuda.empty_cache()
     save()
     # ---- frame ----
-    frames, sums = sh_frames(model, ck, with_others=True)
+    frames, sums = sh_frames(model, ck, network=True)
     ones = torch.ones((3, 3, 3, 4), device="cuda")
     hits = int((model.ctx.render_volume_image(ones, BOX[0], BOX[1], c2w, fov, H, W, 1)[2] > 0).sum().item())
     res["frame"] = {"height": H, "width": W, "n": 256, "n_steps": 512, "rounds": 10, "rays_that_hit_the_box": hits,
@@ -216,20 +232,46 @@ def main():
     del model
     torch.cuda.empty_cache()
     save()
+    return sums
+
+
+def alternate(libs, rounds, sums, out_path):
+    """Fresh child-frame processes, the libraries ``libs`` (name -> path, None: this tree's) in turn, ``rounds`` times ->
+    (whether every frame's checksum is the same in all of them and in ``sums`` if given, name -> frame -> each process's
+    median_ms)."""
+    runs = {name: [] for name in libs}
+    for rnd in range(rounds):
+        for name, lib in libs.items():
+            runs[name].append(run_child(lib, out_path + f".child_{name}_{rnd}.json"))
+            os.remove(out_path + f".child_{name}_{rnd}.json")
+            print(name, rnd, runs[name][-1]["frames"], flush=True)
+    all_sums = [r["checksums"] for v in runs.values() for r in v] + ([sums] if sums else [])
+    return all(s == all_sums[0] for s in all_sums), \
+        {name: {k: [r["frames"][k]["median_ms"] for r in v] for k in v[0]["frames"]} for name, v in runs.items()}
+
+
+def fresh_process_sections(args, res, save, sums, out_path):
     # ---- the two mappings, alternating processes ----
     if args.lanes1_lib and args.lanes8_lib and os.path.exists(args.lanes1_lib) and os.path.exists(args.lanes8_lib):
-        runs = {"eight_lanes_per_ray": [], "one_lane_per_ray": []}
-        for rnd in range(2):
-            for name, lib in (("eight_lanes_per_ray", args.lanes8_lib), ("one_lane_per_ray", args.lanes1_lib)):
-                runs[name].append(run_child(lib, out_path + f".child_{name}_{rnd}.json"))
-                os.remove(out_path + f".child_{name}_{rnd}.json")
-                print("mapping", name, rnd, runs[name][-1]["frames"], flush=True)
-        all_sums = [r["checksums"] for v in runs.values() for r in v] + [sums]
+        same, medians = alternate({"eight_lanes_per_ray": args.lanes8_lib, "one_lane_per_ray": args.lanes1_lib}, 2, sums, out_path)
         res["mappings"] = {"what": "fresh processes, A B A B; median_ms of each process's ten rounds",
-                           "same_bits_in_every_process_and_mapping": all(s == sums for s in all_sums),
-                           **{name: {k: [r["frames"][k]["median_ms"] for r in v] for k in v[0]["frames"]} for name, v in runs.items()}}
+                           "same_bits_in_every_process_and_mapping": same, **medians}
     else:
         res["mappings"] = "not measured (no --lanes1-lib and --lanes8-lib)"
+    save()
+    # ---- the parent commit's library against this tree's, alternating processes ----
+    if args.parent_lib and os.path.exists(args.parent_lib):
+        same, medians = alternate({"parent": args.parent_lib, "this": None}, 3, sums, out_path)
+        # a frame is no slower when the median of this tree's process medians exceeds the parent's by no more than the range
+        # (max - min) of the parent's own process medians: the run-to-run spread of the same call
+        verdict = {k: {"parent_median_ms": float(np.median(p)), "this_median_ms": float(np.median(medians["this"][k])),
+                       "parent_range_ms": max(p) - min(p),
+                       "no_slower": bool(np.median(medians["this"][k]) - np.median(p) <= max(p) - min(p))}
+                   for k, p in medians["parent"].items()}
+        res["parent_lib"] = {"what": "fresh processes, parent / this three times; median_ms of each process's ten rounds",
+                             "same_bits_in_every_process": same, **medians, "verdict": verdict}
+    else:
+        res["parent_lib"] = "not measured (no --parent-lib)"
     save()
     # ---- bench.py against the parent commit ----
     if args.parent_tree and os.path.exists(os.path.join(args.parent_tree, "bench.py")):
@@ -242,7 +284,6 @@ def main():
     else:
         res["bench"] = "not measured (no --parent-tree)"
     save()
-    print(json.dumps(res, indent=1))
 
 
 if __name__ == "__main__":
